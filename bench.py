@@ -21,6 +21,8 @@ steps (inputs resident in HBM, weak scaling: per-GPU batch fixed).  The batches 
                DESIGN.md 4.8), a few steps each after the headline measurement (not part of `value`).
   cpu_baseline the CPU oracle (oracle/ref_models.py, a pure-torch port pinned to the reference by golden
                vectors) running the same train step on the host cores, bounded sample, rank 0 at N=1 only.
+--dump-outputs DIR writes what rank 0's last timed step computed (model outputs, a seeded sample of the updated weights and of
+their gradients) as DIR/<name>.npy, so that two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import csv
@@ -215,6 +217,32 @@ def kill_group(child):
         pass
 
 
+DUMP_SAMPLE = 1 << 20               # elements of the flat weight / gradient arena kept by --dump-outputs (4 MB each in fp32)
+DUMP_LIMIT = 64 << 20                # bytes, all --dump-outputs files together
+
+
+def dump_arrays(out, arena):
+    """What one train step hands back, as host fp32 arrays: the model's outputs (loss, probs, logits, the two towers' embeddings)
+    and a seeded sample of the flat fp32 master weights after the AdamW update and of the gradients it applied.  Read before the
+    next step runs, outside the timed region."""
+    arrays = {k: getattr(out, k) for k in ("loss", "probs", "logits", "src_embeds", "tgt_embeds") if getattr(out, k, None) is not None}
+    idx = torch.randint(arena.numel, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values.to(arena.master.device)
+    arrays["master_weights_sample"] = arena.master[idx]
+    arrays["grad_sample"] = arena.grad[idx]
+    torch.cuda.synchronize()
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:                 # checked here, before the side measurements run
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT}-byte limit")
+    return arrays
+
+
+def write_dump(directory, arrays):
+    import numpy as np
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, f"{name}.npy"), np.asarray(a, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -240,7 +268,13 @@ def main():
     ap.add_argument("--variant-steps", type=int, default=4)
     ap.add_argument("--pmc-timeout", type=int, default=240, help="seconds per rocprofv3 --pmc child pass")
     ap.add_argument("--resident-batches", type=int, default=RESIDENT_BATCHES, help="global batches generated up front and kept in HBM")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what rank 0's last timed step "
+                    "computed to DIR/<name>.npy (fp32): the model outputs and a fixed sample of the updated weights and their gradients")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         # started bare (`python bench.py --gpus N`): this process has not touched the GPU (no torch.cuda call so far) and never will --
         # it starts the N ranks as a CHILD launcher, forwards rank 0's single JSON line and returns the launcher's exit code
@@ -297,7 +331,7 @@ def main():
     warm = int(0.3 * total_opt_steps)
     base_lr = 1e-5
 
-    def step(i, pool=None):
+    def step(i, pool=None, keep=None):
         pool = batches if pool is None else pool
         Fn.set_step_seed((args.seed * 1000003 + i + rank * 0x9E3779B1) & 0xFFFFFFFF)    # dropout streams differ per rank
         arena.zero_grad()
@@ -307,6 +341,8 @@ def main():
         scale = reducer.finish()
         arena.adamw_step(base_lr * linear_schedule(i, total_opt_steps, warm), betas=(0.9, 0.98), eps=1e-8, weight_decay=1e-5,
                          grad_scale=scale)
+        if keep is not None:
+            keep["out"] = out
         return out.loss
 
     def barrier():
@@ -321,9 +357,10 @@ def main():
     barrier()
     torch.cuda.synchronize()
     _lib.check(lib.ia_prof_begin(WGRAD_VARIANT, 400 * args.steps), "ia_prof_begin")
+    last = {} if args.dump_outputs else None
     t0 = time.perf_counter()
     for i in range(args.warmup, n_steps):
-        loss = step(i)
+        loss = step(i, keep=last if i == n_steps - 1 else None)
     torch.cuda.synchronize()
     barrier()
     torch.cuda.synchronize()
@@ -333,6 +370,7 @@ def main():
     alg_bytes = lib.ia_prof_bytes()
     in_region = (ms.value, fl.value, nl.value)
     final_loss_region = float(loss.detach())
+    dump = dump_arrays(last["out"], arena) if last is not None and rank == 0 else None
     if two_streams:
         # the roofline leg: the same step, both towers on ONE stream, so that an event interval around a launch holds that kernel alone
         _mm.TOWER_STREAMS = False
@@ -499,6 +537,8 @@ def main():
                 res["cpu_baseline"] = cpu_baseline(cfg, args.image_model, args.cpu_pairs, args.cpu_steps, args.seed)
             except Exception as e:  # the baseline must never take the GPU number down with it
                 res["cpu_baseline"] = {"value": None, "unit": "item-pairs/sec", "cores": os.cpu_count(), "kind": "port", "sample": f"failed: {e!r}"}
+        if dump is not None:
+            write_dump(args.dump_outputs, dump)
         sys.stdout.flush()
         os.write(result_fd, (json.dumps(res) + "\n").encode())
     if torch.distributed.is_initialized():

@@ -37,7 +37,7 @@ const char* ia_strerror(int code);
 /* Bumped whenever an entry point is added or the meaning of an argument / output changes (round 2 changed what IA_EPI_BIAS_GELU
  * stores in C2 and what IA_EPI_DGELU expects in aux): a caller built against another header must not run on this library.
  * item_alignment_amd/_lib.py refuses to load a library whose version differs from the one it was written for. */
-#define IA_ABI_VERSION 10
+#define IA_ABI_VERSION 11
 int ia_abi_version(void);
 
 /* ---- GEMM: torch.nn.Linear forward / dgrad / wgrad (src/models/text.py:1241 -> RobertaLayer dense
@@ -383,11 +383,14 @@ int ia_embed_ln_fwd(const int64_t* ids, const int64_t* type_ids, const int64_t* 
                     ia_stream_t stream);
 size_t ia_embed_ln_bwd_workspace_bytes(int M, int H);
 int ia_embed_ln_bwd(const void* dy, const void* z, const float* mean, const float* rstd, const float* gamma, const int64_t* ids,
-                    const int64_t* type_ids, const int64_t* pos_ids, const int32_t* extra_idx, const int32_t* row_order, float* dword,
-                    float* dtype, float* dpos, float* dextra, float* dgamma, float* dbeta, int M, int H, int L, int word_pad, int pos_pad,
+                    const int64_t* type_ids, const int64_t* pos_ids, const int32_t* extra_idx, const int32_t* row_order,
+                    const int32_t* word_order, const int32_t* pos_order, const int32_t* type_order, float* dword, float* dtype, float* dpos, float* dextra, float* dgamma, float* dbeta, int M, int H, int L, int word_pad, int pos_pad,
                     float drop_p, uint32_t seed, uint32_t stream_id, void* workspace, size_t workspace_bytes, ia_stream_t stream);
 /* row_order (int32 [M], may be NULL): the rows sorted by position id, for unpadded token rows that have no [M/L, L] grid — the
- * position / token-type gradients are then run-length accumulated along that list instead of down the columns of the grid */
+ * position / token-type gradients are then run-length accumulated along that list instead of down the columns of the grid.
+ * word_order / pos_order / type_order (int32 [M], required with dword / dpos / dtype): the rows stably sorted by the table row they
+ * add to (-1 = none: extra rows and word_pad rows for the word table, pos_pad rows for the position table, first).  Each table row
+ * is summed over its input rows in that order, so the table gradients are the same from run to run. */
 
 /* ---- ViT input side (timm PatchEmbed + cls token + pos_embed; src/models/multimodal.py:811) */
 int ia_im2col_patch(const float* images, void* patches, int B, int C, int S, int P, ia_stream_t stream);

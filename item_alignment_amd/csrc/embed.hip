@@ -97,7 +97,8 @@ __global__ __launch_bounds__(256) void embed_ln_bwd_kernel(const bf16* __restric
                                                            const int32_t* __restrict__ xidx, const int32_t* __restrict__ order,
                                                            float* __restrict__ dword,
                                                            float* __restrict__ dtype, float* __restrict__ dpos,
-                                                           float* __restrict__ dextra, float* __restrict__ part, int M, int H, int L,
+                                                           float* __restrict__ dextra, float* __restrict__ part,
+                                                           float* __restrict__ drow, int M, int H, int L,
                                                            int word_pad, int pos_pad, uint32_t thr16, float inv_keep, uint32_t seed,
                                                            uint32_t stream) {
   __shared__ float red[2][4][512];
@@ -188,6 +189,7 @@ __global__ __launch_bounds__(256) void embed_ln_bwd_kernel(const bf16* __restric
         if (col < H) {
           const float o = rs * (g[i][j] - s1 - xh[i][j] * s2);
           if (wdst) atomicAdd(wdst + col, o);
+          if (drow) drow[(size_t)row * H + col] = o;
           accp[i][j] += o;
           acct[i][j] += o;
         }
@@ -368,18 +370,117 @@ static void embed_bwd_grid(int M, int L, int& gx, int& gy) {
   gy = 8192 / (gx * 4); if (gy < 1) gy = 1; if (gy > S) gy = S;      // up to 2048 workgroups = the rows of the partial-sum workspace
 }
 
-extern "C" size_t ia_embed_ln_bwd_workspace_bytes(int M, int H) { return (size_t)2048 * 2 * H * sizeof(float); }
+// Deterministic table gradients.  The row kernel writes every row's input gradient to `drow` [M, H]; each table's rows are then
+// summed along a stable sort of the rows by table row (`order`, built by the caller), so that every table row is the sum of its
+// input rows in one fixed order (a float atomicAdd per row made the sums -- and every run after them -- differ from run to run).
+// Work is split into pieces of EMB_PIECE consecutive positions of `order`.  A run of equal keys that lies inside one piece is added
+// to the table by that piece; a run that crosses a piece boundary leaves its partial sums in `head` (the part in a piece the run
+// entered from the previous piece) and `tail` (the part in the piece where it starts), and the piece where it starts adds them up
+// in piece order.  Every table row is written by exactly one workgroup.
+constexpr int EMB_PIECE = 512;
+enum { EMB_WORD = 0, EMB_POS = 1, EMB_TYPE = 2 };
+
+// table row of `row` for table `kind`, -1: no gradient (padding_idx rows, extra rows redirected to dextra)
+__device__ __forceinline__ long emb_key(int kind, int row, const int64_t* ids, const int64_t* pids, const int64_t* tts,
+                                        const int32_t* xidx, int word_pad, int pos_pad) {
+  if (kind == EMB_WORD) return ((xidx && xidx[row] >= 0) || ids[row] == word_pad) ? -1 : (long)ids[row];
+  if (kind == EMB_POS) return pids[row] == pos_pad ? -1 : (long)pids[row];
+  return (long)tts[row];
+}
+
+// one thread = 4 consecutive columns; 8 rows of a piece in flight per thread (the walk is otherwise one dependent load at a time)
+__global__ __launch_bounds__(256) void emb_seg_piece_kernel(const float* __restrict__ drow, const int32_t* __restrict__ order, int kind,
+                                                            const int64_t* __restrict__ ids, const int64_t* __restrict__ pids,
+                                                            const int64_t* __restrict__ tts, const int32_t* __restrict__ xidx, int word_pad,
+                                                            int pos_pad, float* __restrict__ table, float* __restrict__ head,
+                                                            float* __restrict__ tail, long* __restrict__ pkeys, int M, int H) {
+  __shared__ long s_key[EMB_PIECE];
+  __shared__ int s_row[EMB_PIECE];
+  const int p = blockIdx.x, lo = p * EMB_PIECE, hi = min(M, lo + EMB_PIECE), n = hi - lo;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const int r = order[lo + i];
+    s_row[i] = r;
+    s_key[i] = emb_key(kind, r, ids, pids, tts, xidx, word_pad, pos_pad);
+  }
+  __syncthreads();
+  if (blockIdx.y == 0 && threadIdx.x == 0) { pkeys[2 * p] = s_key[0]; pkeys[2 * p + 1] = s_key[n - 1]; }   // for the join kernel
+  const int col = (blockIdx.y * 256 + threadIdx.x) * 4;
+  if (col >= H) return;
+  const long prev = lo > 0 ? emb_key(kind, order[lo - 1], ids, pids, tts, xidx, word_pad, pos_pad) : -2;
+  const long next = hi < M ? emb_key(kind, order[hi], ids, pids, tts, xidx, word_pad, pos_pad) : -2;
+  auto put = [](float* dst, const f32x4& v) { *reinterpret_cast<f32x4*>(dst) = v; };
+  auto finish = [&](long key, int rs, int re, const f32x4& acc) {
+    if (key < 0) return;
+    if (rs == 0 && key == prev) put(head + (size_t)p * H + col, acc);
+    else if (re == n && key == next) put(tail + (size_t)p * H + col, acc);
+    else {
+      float* t = table + (size_t)key * H + col;
+      f32x4 v = *reinterpret_cast<const f32x4*>(t);
+      v += acc;
+      put(t, v);
+    }
+  };
+  int rs = 0;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  for (int i0 = 0; i0 < n; i0 += 8) {
+    f32x4 v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      v[j] = i0 + j < n ? *reinterpret_cast<const f32x4*>(drow + (size_t)s_row[i0 + j] * H + col) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int i = i0 + j;
+      if (i >= n) break;
+      if (s_key[i] != s_key[rs]) {
+        finish(s_key[rs], rs, i, acc);
+        rs = i;
+        acc = f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+      acc += v[j];
+    }
+  }
+  finish(s_key[rs], rs, n, acc);
+}
+
+__global__ __launch_bounds__(256) void emb_seg_join_kernel(const long* __restrict__ pkeys, float* __restrict__ table,
+                                                           const float* __restrict__ head, const float* __restrict__ tail, int npieces, int H) {
+  const int p = blockIdx.x;
+  const int col = (blockIdx.y * 256 + threadIdx.x) * 4;
+  if (col >= H || p + 1 >= npieces) return;
+  const long key = pkeys[2 * p + 1];
+  if (key < 0 || pkeys[2 * (p + 1)] != key) return;                             // the piece's last run ends here
+  if (p > 0 && pkeys[2 * p] == key && pkeys[2 * p - 1] == key) return;           // ... and began in an earlier piece: not its owner
+  f32x4 s = *reinterpret_cast<const f32x4*>(tail + (size_t)p * H + col);
+  for (int q = p + 1;; ++q) {
+    s += *reinterpret_cast<const f32x4*>(head + (size_t)q * H + col);
+    if (q + 1 >= npieces || pkeys[2 * q + 1] != key || pkeys[2 * (q + 1)] != key) break;
+  }
+  float* t = table + (size_t)key * H + col;
+  f32x4 v = *reinterpret_cast<const f32x4*>(t);
+  v += s;
+  *reinterpret_cast<f32x4*>(t) = v;
+}
+
+static size_t emb_pieces(int M) { return ((size_t)M + EMB_PIECE - 1) / EMB_PIECE; }
+
+// workspace: [2048 x 2 x H] LayerNorm partial sums | [M x H] row gradients | [pieces x H] head | [pieces x H] tail  (fp32)
+//            | [pieces x 2] first / last key of each piece (int64)
+extern "C" size_t ia_embed_ln_bwd_workspace_bytes(int M, int H) {
+  return ((size_t)2048 * 2 * H + (size_t)M * H + 2 * emb_pieces(M) * H) * sizeof(float) + 2 * emb_pieces(M) * sizeof(long);
+}
 
 // word_pad / pos_pad: rows of the word / position tables that receive no gradient (nn.Embedding
 // padding_idx, reference base.py:213,234-236); pass -1 for none.  All gradients accumulate (+=).
 extern "C" int ia_embed_ln_bwd(const void* dy, const void* z, const float* mean, const float* rstd, const float* gamma,
                                const int64_t* ids, const int64_t* type_ids, const int64_t* pos_ids, const int32_t* extra_idx,
-                               const int32_t* row_order, float* dword, float* dtype, float* dpos, float* dextra, float* dgamma, float* dbeta,
+                               const int32_t* row_order, const int32_t* word_order, const int32_t* pos_order,
+                               const int32_t* type_order, float* dword, float* dtype, float* dpos, float* dextra, float* dgamma, float* dbeta,
                                int M, int H,
                                int L, int word_pad, int pos_pad, float drop_p, uint32_t seed, uint32_t stream_id, void* workspace,
                                size_t workspace_bytes, hipStream_t stream) {
   (void)hipGetLastError();  // drop stale status left by unrelated runtime calls (e.g. hipEventQuery -> NotReady)
   if (!dy || !z || !mean || !rstd || !gamma || !ids || !type_ids || !pos_ids) return IA_ERR_ARG;
+  if ((dword && !word_order) || (dpos && !pos_order) || (dtype && !type_order)) return IA_ERR_ARG;
   if (M <= 0 || (H & 7) || H > 4096) return IA_ERR_ARG;
   if (!workspace || workspace_bytes < ia_embed_ln_bwd_workspace_bytes(M, H)) return IA_ERR_WORKSPACE;
   uint32_t thr16; float inv_keep; drop_params(drop_p, thr16, inv_keep);
@@ -388,14 +489,30 @@ extern "C" int ia_embed_ln_bwd(const void* dy, const void* z, const float* mean,
   int gx, gy; embed_bwd_grid(M, L, gx, gy);
   if (row_order) gy = 1;
   const int nb = gx * gy, nv = (H + 511) / 512;
-  if ((size_t)nb * 2 * H * sizeof(float) > workspace_bytes) return IA_ERR_WORKSPACE;
+  if (nb > 2048) return IA_ERR_WORKSPACE;
   float* part = (float*)workspace;
+  const bool tables = dword || dtype || dpos;
+  float* drow = tables ? part + (size_t)2048 * 2 * H : nullptr;
+  float* head = part + (size_t)2048 * 2 * H + (size_t)M * H;
+  float* tail = head + emb_pieces(M) * H;
+  long* pkeys = reinterpret_cast<long*>(tail + emb_pieces(M) * H);
   dim3 grid(gx, gy), blk(256);
+  // the table pointers stay out of the row kernel (its run-length flushes and word-row writes are atomics): drow takes the rows
 #define IA_E(NV) hipLaunchKernelGGL((embed_ln_bwd_kernel<NV>), grid, blk, 0, stream, (const bf16*)dy, (const bf16*)z, mean, rstd, gamma, ids, \
-    type_ids, pos_ids, extra_idx, row_order, dword, dtype, dpos, dextra, part, M, H, L, word_pad, pos_pad, thr16, inv_keep, seed, stream_id)
+    type_ids, pos_ids, extra_idx, row_order, nullptr, nullptr, nullptr, dextra, part, drow, M, H, L, word_pad, pos_pad, thr16, inv_keep, seed, \
+    stream_id)
   switch (nv) { case 1: IA_E(1); break; case 2: IA_E(2); break; case 3: IA_E(3); break; case 4: IA_E(4); break; default: IA_E(8); }
 #undef IA_E
   hipLaunchKernelGGL(reduce2_kernel, dim3((2 * H + 31) / 32), dim3(1024), 0, stream, part, nb, H, dgamma, dbeta);
+  const dim3 sgrid((unsigned)emb_pieces(M), (unsigned)((H + 1023) / 1024));
+  const struct { int kind; const int32_t* order; float* table; } tab[3] = {{EMB_WORD, word_order, dword}, {EMB_POS, pos_order, dpos},
+                                                                             {EMB_TYPE, type_order, dtype}};
+  for (const auto& t : tab) {
+    if (!t.table) continue;
+    hipLaunchKernelGGL(emb_seg_piece_kernel, sgrid, blk, 0, stream, drow, t.order, t.kind, ids, pos_ids, type_ids, extra_idx, word_pad, pos_pad,
+                       t.table, head, tail, pkeys, M, H);
+    hipLaunchKernelGGL(emb_seg_join_kernel, sgrid, blk, 0, stream, pkeys, t.table, head, tail, (int)emb_pieces(M), H);
+  }
   return ia_check_launch();
 }
 

@@ -66,6 +66,19 @@ def reset_use_counts():
 
 
 # ------------------------------------------------------------------------------------------ embeddings
+def embed_table_orders(ids, tts, pids, extra_idx, word_pad, pos_pad):
+    """word_order, pos_order, type_order of ia_embed_ln_bwd: the rows stably sorted by the word / position / token-type table row they
+    add to (-1: none -- extra rows and word_pad rows of the word table, pos_pad rows of the position table).  The kernel sums every
+    table row over its rows in this fixed order, so the table gradients are the same from run to run."""
+    def order(key):
+        return torch.argsort(key.reshape(-1), stable=True).to(torch.int32)
+    none = torch.full_like(ids, -1)
+    word_key = torch.where(ids == word_pad, none, ids)
+    if extra_idx is not None:
+        word_key = torch.where(extra_idx.reshape(ids.shape) >= 0, none, word_key)
+    return [order(word_key), order(torch.where(pids == pos_pad, none, pids)), order(tts)]
+
+
 class EmbedLNFn(torch.autograd.Function):
     """word (+ redirected extra rows) + token type + position -> LayerNorm -> dropout (reference base.py:238-279)."""
 
@@ -105,8 +118,11 @@ class EmbedLNFn(torch.autograd.Function):
 
         def g(p):
             return p.grad.data_ptr() if p.requires_grad else None
+
+        orders = embed_table_orders(ids, tts, pids, extra_idx, emb.word_pad, emb.pos_pad)
         check(lib.ia_embed_ln_bwd(dy.data_ptr(), z.data_ptr(), mean.data_ptr(), rstd.data_ptr(), emb.LayerNorm.weight.data_ptr(),
-                                  ids.data_ptr(), tts.data_ptr(), pids.data_ptr(), ptr(extra_idx), ptr(ctx.row_order), g(emb.word_embeddings.weight),
+                                  ids.data_ptr(), tts.data_ptr(), pids.data_ptr(), ptr(extra_idx), ptr(ctx.row_order),
+                                  *(o.data_ptr() for o in orders), g(emb.word_embeddings.weight),
                                   g(emb.token_type_embeddings.weight), g(emb.position_embeddings.weight), ptr(dextra),
                                   g(emb.LayerNorm.weight), g(emb.LayerNorm.bias), M, H, ctx.seq_len, emb.word_pad, emb.pos_pad, ctx.drop, ctx.seed,
                                   ctx.stream_id, ws.data_ptr(), ws_bytes, stream_ptr()), "ia_embed_ln_bwd")

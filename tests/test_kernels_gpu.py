@@ -1610,3 +1610,60 @@ def test_gemm_dynamic_tile_claim_under_cu_contention(gpu):
     torch.cuda.synchronize()
     lib.ia_debug_gemm_dynamic(prev)
     assert torch.equal(d0, d1) and rel_err(d0, a.float() @ w.float()) < 2e-2
+
+
+def test_embed_ln_bwd_tables_across_pieces_match_an_independent_sum(gpu):
+    """ia_embed_ln_bwd's table gradients (embed.hip: rows summed along a stable sort of the rows by table row, in pieces of 512 sorted
+    positions; a run that crosses pieces is joined by the piece it starts in).  Here one word id covers ~1500 rows (a run over 3-4
+    pieces), token type 0 covers nearly all 2800 rows (every piece), positions make runs of 70 rows, and padding rows add to no word /
+    position row.  Against an fp64 index_add of the LayerNorm input gradient, and a second call must repeat the first bit for bit."""
+    from item_alignment_amd import _lib
+    from item_alignment_amd.models.functional import embed_table_orders
+    lib = _lib.load()
+    S, L, H, V, P, T, word_pad, pos_pad = 70, 40, 256, 300, 48, 2, 1, 1
+    M = S * L
+    gen = torch.Generator().manual_seed(5)
+    ids = torch.randint(2, V, (S, L), generator=gen)
+    ids.view(-1)[:1500] = 7
+    ids.view(-1)[torch.randperm(M, generator=gen)[:200]] = word_pad
+    pids = (torch.arange(L) + 2).repeat(S, 1)
+    pids[ids == word_pad] = pos_pad
+    tts = torch.zeros(S, L, dtype=torch.long)
+    tts.view(-1)[torch.randperm(M, generator=gen)[:100]] = 1
+    z = (torch.randn(M, H, generator=gen) * 2 + 0.5).to(torch.bfloat16)
+    dy = torch.randn(M, H, generator=gen).to(torch.bfloat16)
+    gamma = torch.rand(H, generator=gen) + 0.5
+    zf = z.double()
+    mean, var = zf.mean(1), zf.var(1, unbiased=False)
+    rstd = 1.0 / torch.sqrt(var + 1e-5)
+    # reference: LayerNorm input gradient per row in fp64, scattered with index_add
+    xhat = (zf - mean[:, None]) * rstd[:, None]
+    gg = dy.double() * gamma.double()
+    o = rstd[:, None] * (gg - gg.mean(1, keepdim=True) - xhat * (gg * xhat).mean(1, keepdim=True))
+    fi, fp, ft = ids.view(-1), pids.view(-1), tts.view(-1)
+    w_ok, p_ok = fi != word_pad, fp != pos_pad
+    want = {"word": torch.zeros(V, H, dtype=torch.float64).index_add_(0, fi[w_ok], o[w_ok]),
+            "pos": torch.zeros(P, H, dtype=torch.float64).index_add_(0, fp[p_ok], o[p_ok]),
+            "type": torch.zeros(T, H, dtype=torch.float64).index_add_(0, ft, o)}
+
+    dev = {k: v.to(gpu) for k, v in dict(ids=ids, pids=pids, tts=tts, z=z, dy=dy, gamma=gamma, mean=mean.float(), rstd=rstd.float()).items()}
+    orders = embed_table_orders(dev["ids"], dev["tts"], dev["pids"], None, word_pad, pos_pad)
+    ws_bytes = lib.ia_embed_ln_bwd_workspace_bytes(M, H)
+    ws = torch.empty(ws_bytes, device=gpu, dtype=torch.uint8)
+
+    def run():
+        got = {"word": torch.zeros(V, H, device=gpu), "pos": torch.zeros(P, H, device=gpu), "type": torch.zeros(T, H, device=gpu)}
+        dg, db = torch.zeros(H, device=gpu), torch.zeros(H, device=gpu)
+        _lib.check(lib.ia_embed_ln_bwd(dev["dy"].data_ptr(), dev["z"].data_ptr(), dev["mean"].data_ptr(), dev["rstd"].data_ptr(),
+                                       dev["gamma"].data_ptr(), dev["ids"].data_ptr(), dev["tts"].data_ptr(), dev["pids"].data_ptr(), None, None,
+                                       *(t.data_ptr() for t in orders), got["word"].data_ptr(), got["type"].data_ptr(), got["pos"].data_ptr(),
+                                       None, dg.data_ptr(), db.data_ptr(), M, H, L, word_pad, pos_pad, 0.0, 0, 0, ws.data_ptr(), ws_bytes,
+                                       _lib.stream_ptr()), "ia_embed_ln_bwd")
+        torch.cuda.synchronize()
+        return {k: v.cpu() for k, v in got.items()}
+
+    g1, g2 = run(), run()
+    for k in want:
+        assert torch.equal(g1[k], g2[k]), ("a second call must repeat the table gradient bit for bit", k)
+        assert rel_err(g1[k], want[k]) < 1e-5, (k, rel_err(g1[k], want[k]))
+    assert want["word"][7].abs().max() > 0 and g1["word"][word_pad].abs().max() == 0 and g1["pos"][pos_pad].abs().max() == 0
