@@ -37,7 +37,7 @@ const char* ia_strerror(int code);
 /* Bumped whenever an entry point is added or the meaning of an argument / output changes (round 2 changed what IA_EPI_BIAS_GELU
  * stores in C2 and what IA_EPI_DGELU expects in aux): a caller built against another header must not run on this library.
  * item_alignment_amd/_lib.py refuses to load a library whose version differs from the one it was written for. */
-#define IA_ABI_VERSION 11
+#define IA_ABI_VERSION 12
 int ia_abi_version(void);
 
 /* ---- GEMM: torch.nn.Linear forward / dgrad / wgrad (src/models/text.py:1241 -> RobertaLayer dense
@@ -447,6 +447,34 @@ int ia_adamw_flat(float* params, const float* grads, float* exp_avg, float* exp_
                   ia_stream_t stream);
 int ia_cast_f32_to_bf16(const float* src, void* dst, size_t n, ia_stream_t stream);
 int ia_cast_bf16_to_f32(const void* src, float* dst, size_t n, ia_stream_t stream);
+
+/* ---- knowledge-graph pretraining (pkgm_pretrain.py: torchkge PKGMModel / TransEModel scoring, MarginLoss, BernoulliNegativeSampler,
+ * Trainer + torch.optim.Adam with coupled L2; ABI 12).  fp32 tables, projection and gradients; ids int64.
+ * ia_kgpt_score runs B positive triples (h, t, r) and B negatives (nh, nt, r): hn = normalize(ent[h]), tn = normalize(ent[t]),
+ * score = -d(hn + rel[r], tn) - d(hn P^T, rel[r]) (the second term only when proj != NULL: PKGM; TransE passes NULL), d = |.|_2^2
+ * (norm 2) or |.|_1 (norm 1).  mode IA_KGPT_SCORE: pos / neg only.  IA_KGPT_GRAD: and the gradients of sum(dpos * pos + dneg * neg).
+ * IA_KGPT_MARGIN: and loss[0] = sum max(0, margin - pos + neg) with its gradients.  Gradients ACCUMULATE (+=) into dent [n_ent, D],
+ * drel [n_rel, D] and dproj [D, D]; ent_order is the stable sort of the 4B entity keys (h | nh | t | nt) by value, rel_order that of the
+ * 2B relation keys (r | r): every table row is the sum of its contributions in that order, so the gradients are bit-identical from run
+ * to run.  workspace >= ia_kgpt_workspace_bytes(B, D, proj != NULL). */
+#define IA_KGPT_SCORE 0
+#define IA_KGPT_GRAD 1
+#define IA_KGPT_MARGIN 2
+size_t ia_kgpt_workspace_bytes(int B, int D, int use_proj);
+int ia_kgpt_score(const float* ent, const float* rel, const float* proj, const int64_t* h, const int64_t* t, const int64_t* r,
+                  const int64_t* nh, const int64_t* nt, int B, int D, int n_ent, int n_rel, int norm, int mode, float margin,
+                  const float* dpos, const float* dneg, float* pos, float* neg, float* loss, const int32_t* ent_order, const int32_t* rel_order,
+                  float* dent, float* drel, float* dproj, void* workspace, size_t workspace_bytes, ia_stream_t stream);
+/* torch.optim.Adam step with coupled L2 (g += weight_decay * p) over n contiguous fp32 values (16-byte aligned); the gradient is set
+ * to zero in the same pass.  step counts from 1.  (ia_adamw_flat is the decoupled AdamW of the fine-tuning path.) */
+int ia_kgpt_adam_l2(float* params, float* grads, float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1, float beta2,
+                    float eps, float weight_decay, int step, ia_stream_t stream);
+/* x[i, :] /= max(|x[i, :]|_2, 1e-12) in place (PKGMModel.normalize_parameters) */
+int ia_kgpt_row_normalize(float* x, int rows, int D, ia_stream_t stream);
+/* one negative per fact: head replaced with probability bern_probs[r] (0.5 for r outside [0, n_probs)), the tail otherwise, by an id
+ * uniform in [1, n_ent); counter-based generator keyed by (seed, fact index) */
+int ia_kgpt_corrupt(const int64_t* h, const int64_t* t, const int64_t* r, int n, const float* bern_probs, int n_probs, int n_ent,
+                    uint64_t seed, int64_t* nh, int64_t* nt, ia_stream_t stream);
 
 /* ---- whole-layer drivers: one call = every launch of one encoder layer, in order, on `stream`.
  * Weights: bf16 shadows for the GEMM operands, fp32 masters for bias / LayerNorm vectors. */
