@@ -117,3 +117,103 @@ def test_cli_rejects_what_is_not_built(tmp_path, extra, msg):
     assert res.returncode != 0
     assert msg in res.stderr
     assert not (tmp_path / "out").exists()
+
+
+# ------------------------------------------------------------------------- the fp64 reference of tests/kgpt_reference.py, pinned
+# to torchkge's own fp32 results (the goldens), before the GPU tests use it at shapes where no golden exists
+import kgpt_reference as R  # noqa: E402
+
+TAU_GOLDEN = 1e-5
+
+
+def golden_case(name):
+    import json
+    z = golden(name)
+    meta = json.loads(bytes(z["meta"]).decode())
+    t = {k: torch.from_numpy(z[k]) for k in z.files if k != "meta"}
+    proj = t.get("init_proj_mat.weight")
+    return z, meta, t, proj
+
+
+def within(got, ref, S, tau, U=None):
+    """max over elements of (|got - ref| - U) / (tau * S): the share of the bound tau * S used (<= 1 inside it); an element with
+    S == 0 must match exactly."""
+    err = (got.double() - ref).abs() - (0 if U is None else U)
+    assert (err[S == 0] <= 0).all()
+    return (err.clamp_min(0) / (tau * torch.where(S > 0, S, torch.ones_like(S)))).max().item()
+
+
+@pytest.mark.parametrize("name", ["pkgm_l2", "pkgm_l1", "transe_l2"])
+def test_fp64_reference_reproduces_the_torchkge_step(name):
+    z, meta, t, proj = golden_case(name)
+    norm = 1 if meta["norm"] == "L1" else 2
+    ref = R.score_step(t["init_ent_emb.weight"], t["init_rel_emb.weight"], proj, t["h"], t["t"], t["r"], t["nh"], t["nt"], norm,
+                       margin=meta["margin"], sign_tol=True)
+    assert within(t["pos"], ref["pos"], ref["S_pos"], TAU_GOLDEN) <= 1.0
+    assert within(t["neg"], ref["neg"], ref["S_neg"], TAU_GOLDEN) <= 1.0
+    assert (meta["margin"] - ref["pos"] + ref["neg"]).abs().min() > 1e-4          # no hinge decision near a tie
+    assert abs(float(t["loss"][0]) - ref["loss"].item()) <= TAU_GOLDEN * (ref["S_pos"] + ref["S_neg"]).sum().item()
+    for key, g in (("ent_emb.weight", "ent"), ("rel_emb.weight", "rel"), ("proj_mat.weight", "proj")):
+        if proj is None and g == "proj":
+            continue
+        q = within(t["grad_" + key], ref["grad_" + g], ref["S_" + g], TAU_GOLDEN, ref["U_" + g])
+        assert q <= 1.0 / 4, (key, q)                                                 # torchkge's fp32 within tau / 4 * S
+    # the rows the golden's step never touched have exactly zero gradient in both
+    untouched = ref["count_ent"] == 0
+    assert untouched.any() and (t["grad_ent_emb.weight"][untouched] == 0).all() and (ref["grad_ent"][untouched] == 0).all()
+
+
+@pytest.mark.parametrize("name", ["pkgm_l2", "pkgm_l1", "transe_l2"])
+def test_fp64_reference_reproduces_the_torchkge_trajectory(name):
+    """3 x (step, coupled-L2 Adam, LambdaLR) and normalize_parameters() in fp64 against torchkge + torch.optim.Adam in fp32."""
+    z, meta, t, proj = golden_case(name)
+    norm = 1 if meta["norm"] == "L1" else 2
+    tabs = {"ent_emb.weight": t["init_ent_emb.weight"].double(), "rel_emb.weight": t["init_rel_emb.weight"].double()}
+    if proj is not None:
+        tabs["proj_mat.weight"] = proj.double()
+    state = {k: (torch.zeros_like(v), torch.zeros_like(v)) for k, v in tabs.items()}
+    lam = K.linear_schedule_lambda(meta["warmup_steps"], meta["total_steps"])
+    losses = []
+    for step in range(meta["traj_steps"]):
+        ref = R.score_step(tabs["ent_emb.weight"], tabs["rel_emb.weight"], tabs.get("proj_mat.weight"), t["h"], t["t"], t["r"], t["nh"],
+                           t["nt"], norm, margin=meta["margin"])
+        losses.append(ref["loss"].item())
+        for k, g in (("ent_emb.weight", "ent"), ("rel_emb.weight", "rel"), ("proj_mat.weight", "proj")):
+            if k not in tabs:
+                continue
+            m, v = state[k]
+            p, m, v, *_ = R.adam_l2(tabs[k], m, v, [ref["grad_" + g]], [meta["lr"] * lam(step)], eps=meta["eps"],
+                                    weight_decay=meta["weight_decay"], first_step=step + 1)
+            tabs[k], state[k] = p, (m, v)
+    tabs["ent_emb.weight"] = R.row_normalize(tabs["ent_emb.weight"])
+    np.testing.assert_allclose(losses, z["traj_losses"], rtol=1e-5)
+    for k, v in tabs.items():
+        got = torch.from_numpy(z["traj_" + k]).double()
+        assert (got - v).abs().max().item() <= 2e-5 * v.abs().max().item(), k
+
+
+def test_fp64_adam_reference_is_torch_adam():
+    """R.adam_l2 against torch.optim.Adam(foreach=False) run in fp64: the same formula, to fp64 rounding."""
+    g = torch.Generator().manual_seed(4)
+    p0 = torch.randn(37, generator=g, dtype=torch.float64)
+    grads = [torch.randn(37, generator=g, dtype=torch.float64) for _ in range(10)]
+    lrs = [1e-2 * (1 + 0.3 * i) for i in range(10)]
+    for wd in (0.0, 1e-5, 1e-2):
+        p = torch.nn.Parameter(p0.clone())
+        opt = torch.optim.Adam([p], lr=lrs[0], weight_decay=wd, foreach=False)
+        for gr, lr in zip(grads, lrs):
+            opt.param_groups[0]["lr"] = lr
+            p.grad = gr.clone()
+            opt.step()
+        want, m, v, *_ = R.adam_l2(p0, torch.zeros(37, dtype=torch.float64), torch.zeros(37, dtype=torch.float64), grads, lrs, weight_decay=wd)
+        assert torch.allclose(p.detach(), want, rtol=1e-13, atol=1e-15), wd
+        assert torch.allclose(opt.state[p]["exp_avg"], m, rtol=1e-13, atol=1e-15)
+        assert torch.allclose(opt.state[p]["exp_avg_sq"], v, rtol=1e-13, atol=1e-15)
+
+
+def test_fp64_row_normalize_reference():
+    x = torch.tensor([[3.0, 4.0], [0.0, 0.0], [1e-13, 0.0]], dtype=torch.float64)
+    y = R.row_normalize(x)
+    assert y.dtype == torch.float64
+    assert torch.equal(y[0], torch.tensor([0.6, 0.8], dtype=torch.float64)) and (y[1] == 0).all()
+    assert y[2, 0].item() == pytest.approx(0.1, rel=1e-12)                 # below eps: divided by 1e-12, as F.normalize does
