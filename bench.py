@@ -8,19 +8,23 @@ fp32 master weights, on synthetic pairs (BASELINE.json metric)
 
 One JSON line on rank 0.  `value` = pairs processed by ALL ranks / max-over-ranks wall time of the K timed
 steps (inputs resident in HBM, weak scaling: per-GPU batch fixed).  The batches are drawn without replacement from the
-50 000-pair synthetic set of SURVEY §8(d) (16 resident global batches; longer runs walk them again).  Extra objects:
-  roofline     the dominant kernel (by summed time: the wgrad GEMM instantiation), timed per launch with HIP
-               events on its launch stream: achieved = algorithmic FLOPs / time.  The headline region runs the image tower on a
-               second HIP stream (round 5 default, +1.5-2 % pairs/s), where a kernel's event interval also contains whatever the
-               other stream's kernels took from it -- so the event-timed leg is taken in a SEPARATE short single-stream pass of
-               the same step right after the timed region (`roofline.measured_in` says so; `frac_in_timed_region` is the
-               two-stream figure for comparison; --single-stream runs everything on one stream as in rounds 1-4).  `traffic` = HBM
-               bytes per launch from two rocprofv3 --pmc child passes of this same command, single-stream (FETCH_SIZE x 2 on
-               gfx950 + WRITE_SIZE, MI355X_MICROARCH.md HBM section), N = 1 only, null when rocprofv3 is unavailable.
-  variants     the same step with every sequence at the full 255 tokens, and with the unpadded text towers (--unpad,
-               DESIGN.md 4.8), a few steps each after the headline measurement (not part of `value`).
+50 000-pair synthetic set of SURVEY §8(d) (16 resident global batches; longer runs walk them again).
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, write --dump-outputs, print the line.  Its
+`roofline` is the dominant kernel (by summed time: the wgrad GEMM instantiation) timed per launch with HIP events on its launch
+stream inside the timed region: achieved = algorithmic FLOPs / time.  By default the timed region runs the image tower on a second
+HIP stream (round 5 default, +1.5-2 % pairs/s), where a kernel's event interval also contains whatever the other stream's kernels
+took from it (`roofline.measured_in` says so; --single-stream runs everything on one stream as in rounds 1-4).
+--full adds every side measurement after the timed region (none of them is part of `value`):
+  roofline     with two streams, the event-timed leg is taken again in a SEPARATE short single-stream pass of the same step
+               (`frac_in_timed_region` keeps the two-stream figure for comparison).  `traffic` = HBM bytes per launch from two
+               rocprofv3 --pmc child passes of this same command, single-stream (FETCH_SIZE x 2 on gfx950 + WRITE_SIZE,
+               MI355X_MICROARCH.md HBM section), N = 1 only, null when rocprofv3 is unavailable (--no-pmc skips them).
+  variants     the same step at 16 pairs per GPU, with every sequence at the full 255 tokens, with the unpadded text towers
+               (--unpad), forward only, and on the other stream arrangement, a few steps each (--no-variants).
+  attention_text  the share of the dense attention work the text attention kernels execute on the timed batches.
   cpu_baseline the CPU oracle (oracle/ref_models.py, a pure-torch port pinned to the reference by golden
-               vectors) running the same train step on the host cores, bounded sample, rank 0 at N=1 only.
+               vectors) running the same train step on the host cores, bounded sample, rank 0 at N=1 only (--no-cpu-baseline).
 --dump-outputs DIR writes what rank 0's last timed step computed (model outputs, a seeded sample of the updated weights and of
 their gradients) as DIR/<name>.npy, so that two builds run with the same arguments can be compared output for output.
 """
@@ -254,17 +258,20 @@ def main():
     ap.add_argument("--pairs-per-gpu", type=int, default=256)
     ap.add_argument("--image-model", default="vit_base_patch16_384")
     ap.add_argument("--seed", type=int, default=2345)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run every side measurement: the single-stream "
+                    "roofline pass, the rocprofv3 traffic passes, the variants, the text-attention shares and the CPU baseline; off by "
+                    "default: a plain run does only what the headline figure needs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU-oracle baseline")
     ap.add_argument("--cpu-pairs", type=int, default=2)
     ap.add_argument("--cpu-steps", type=int, default=3, help="timed CPU-oracle steps (BASELINE.md 3: 3 timed + 1 warm-up)")
     ap.add_argument("--single-stream", action="store_true", help="both towers on one HIP stream (the round 1-4 headline); default: the "
-                    "image tower on a second stream, the roofline leg in a separate single-stream pass")
-    ap.add_argument("--roofline-steps", type=int, default=3, help="steps of the separate single-stream pass behind `roofline`")
+                    "image tower on a second stream (with --full, the roofline leg in a separate single-stream pass)")
+    ap.add_argument("--roofline-steps", type=int, default=3, help="steps of the separate single-stream pass behind `roofline` (--full)")
     ap.add_argument("--full-length", action="store_true", help="all sequences at the full 255 tokens (mask all ones)")
     ap.add_argument("--unpad", action="store_true", help="text towers on the valid tokens only (IA_UNPAD=1, DESIGN.md 4.8); off by "
                     "default: the reference computes densely on the padding and the headline number keeps that workload")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the two rocprofv3 --pmc child passes behind roofline.traffic")
-    ap.add_argument("--no-variants", action="store_true", help="skip the full-length / unpadded side measurements")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: skip the two rocprofv3 --pmc child passes behind roofline.traffic")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: skip the variant side measurements")
     ap.add_argument("--variant-steps", type=int, default=4)
     ap.add_argument("--pmc-timeout", type=int, default=240, help="seconds per rocprofv3 --pmc child pass")
     ap.add_argument("--resident-batches", type=int, default=RESIDENT_BATCHES, help="global batches generated up front and kept in HBM")
@@ -371,7 +378,8 @@ def main():
     in_region = (ms.value, fl.value, nl.value)
     final_loss_region = float(loss.detach())
     dump = dump_arrays(last["out"], arena) if last is not None and rank == 0 else None
-    if two_streams:
+    separate_roofline = two_streams and args.full
+    if separate_roofline:
         # the roofline leg: the same step, both towers on ONE stream, so that an event interval around a launch holds that kernel alone
         _mm.TOWER_STREAMS = False
         try:
@@ -385,7 +393,7 @@ def main():
             alg_bytes = lib.ia_prof_bytes()
         finally:
             _mm.TOWER_STREAMS = True
-    n_steps_done = n_steps + (1 + args.roofline_steps if two_streams else 0)
+    n_steps_done = n_steps + (1 + args.roofline_steps if separate_roofline else 0)
     tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
     if world > 1 or iadist.FORCE:
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
@@ -410,7 +418,7 @@ def main():
                 "pairs_per_gpu": pairs_per_rank}
 
     variants = None
-    if not args.no_variants and not args.unpad and not args.full_length:
+    if args.full and not args.no_variants and not args.unpad and not args.full_length:
         from item_alignment_amd.models import text as _text
         variants = {}
         # SURVEY 8(d)'s smallest batch: 16 pairs per GPU = a step of ~30 ms, where the 1.64 GB gradient all-reduce is a third of the
@@ -494,30 +502,34 @@ def main():
                                 "flop_per_byte": intensity, "algorithmic_bytes_per_launch": alg_bytes / max(1, nl.value),
                                 "measured_in": (f"separate single-stream pass of {args.roofline_steps} steps right after the timed region (HIP "
                                                 "events on the launch stream; the timed region overlaps the towers on two streams)"
+                                                if separate_roofline else
+                                                "the timed region (HIP events on the launch stream; the towers overlap on two streams, so an "
+                                                "interval also holds what the other stream's kernels took; --full adds a single-stream pass)"
                                                 if two_streams else "the timed region (HIP events on the launch stream)"),
                                 "frac_in_timed_region": (in_region[1] / (in_region[0] * 1e-3) / 1e12 / 2500.0 if in_region[0] > 0 else None)})
         # Text attention: the kernels skip key tiles that hold no attendable key (right-padded batches), so a per-kernel MFMA fraction taken
         # from the DENSE 255 x 255 FLOP count flatters them.  From the attention masks of the timed batches: the share of
         # the dense key positions each kernel actually visits -- forward (attn_fwd3: 64-key tiles per sequence) and fused backward
         # (attn_bwd_fused: 32-key blocks per sequence); executed FLOPs per launch = dense FLOPs x this share.
-        try:
-            lens = torch.cat([torch.cat((b[1], b[6])).sum(1) for b in batches]).float()      # attention_mask_1 | attention_mask_2: tokens per sequence
-            L = batches[0][1].shape[1]
-            res["attention_text"] = {
-                "mean_tokens": round(lens.mean().item(), 1), "padded_len": L,
-                "executed_key_share_fwd": round((torch.ceil(lens / 64) * 64).clamp(max=L).mean().item() / L, 4),
-                "executed_key_share_bwd": round((torch.ceil(lens / 32) * 32).clamp(max=L).mean().item() / L, 4),
-                # the fused backward also leaves out 32-query blocks of padding (ia_layer_cfg::masked_rows_dead): live keys x live queries
-                "executed_share_bwd_keys_x_queries": round((((torch.ceil(lens / 32) * 32).clamp(max=L) / L) ** 2).mean().item(), 4),
-                "dense_flops_per_launch_fwd": 4.0 * 2 * B * 16 * L * L * 64, "dense_flops_per_launch_bwd": 10.0 * 2 * B * 16 * L * L * 64,
-                "note": "per-kernel TFLOP/s on EXECUTED work = dense_flops_per_launch x executed_key_share / the kernel's launch time "
-                        "(profiles/*_kernel_stats_summary.txt); the ViT kernels (no padding mask) execute 19 of their 20 32-key blocks"}
-        except Exception as e:      # (a diagnostic: never fail the line over it)
-            res["attention_text"] = {"error": repr(e)}
+        if args.full:
+            try:
+                lens = torch.cat([torch.cat((b[1], b[6])).sum(1) for b in batches]).float()  # attention_mask_1 | attention_mask_2: tokens per sequence
+                L = batches[0][1].shape[1]
+                res["attention_text"] = {
+                    "mean_tokens": round(lens.mean().item(), 1), "padded_len": L,
+                    "executed_key_share_fwd": round((torch.ceil(lens / 64) * 64).clamp(max=L).mean().item() / L, 4),
+                    "executed_key_share_bwd": round((torch.ceil(lens / 32) * 32).clamp(max=L).mean().item() / L, 4),
+                    # the fused backward also leaves out 32-query blocks of padding (ia_layer_cfg::masked_rows_dead): live keys x live queries
+                    "executed_share_bwd_keys_x_queries": round((((torch.ceil(lens / 32) * 32).clamp(max=L) / L) ** 2).mean().item(), 4),
+                    "dense_flops_per_launch_fwd": 4.0 * 2 * B * 16 * L * L * 64, "dense_flops_per_launch_bwd": 10.0 * 2 * B * 16 * L * L * 64,
+                    "note": "per-kernel TFLOP/s on EXECUTED work = dense_flops_per_launch x executed_key_share / the kernel's launch time "
+                            "(profiles/*_kernel_stats_summary.txt); the ViT kernels (no padding mask) execute 19 of their 20 32-key blocks"}
+            except Exception as e:      # (a diagnostic: never fail the line over it)
+                res["attention_text"] = {"error": repr(e)}
         res["config"]["dataset_pairs"] = DATASET_PAIRS
         res["config"]["resident_batches"] = n_batches
         res["peak_hbm_gib"] = round(torch.cuda.max_memory_allocated() / 2 ** 30, 1)      # this rank, incl. the resident batches
-        if world == 1 and not args.no_pmc:
+        if args.full and world == 1 and not args.no_pmc:
             # free this process's HBM first: the child runs build their own model and batches
             del batches
             import gc
@@ -532,7 +544,7 @@ def main():
             res["roofline"]["traffic_source"] = note
             if traffic:
                 res["roofline"]["traffic_GBps"] = traffic / (ms.value * 1e-3 / max(1, nl.value)) / 1e9
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 res["cpu_baseline"] = cpu_baseline(cfg, args.image_model, args.cpu_pairs, args.cpu_steps, args.seed)
             except Exception as e:  # the baseline must never take the GPU number down with it

@@ -346,3 +346,33 @@ def test_bench_gpus_2_launches_itself(gpu):
     res = json.loads(lines[0])
     assert res["n_gpus"] == 2 and res["config"]["global_batch"] == 32 and res["config"]["parallelism"] == "dp2"
     assert res["value"] > 0 and res["scaling"] == "weak"
+
+
+def test_bench_plain_run_is_lean_and_full_adds_the_side_measurements(gpu):
+    """A plain `bench.py` run prints the headline line with no side measurement (roofline from the timed region only); --full adds
+    the single-stream roofline pass, the variant lines, the text-attention shares and the CPU baseline (rocprofv3 passes skipped)."""
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "IA_DP_FORCE_COLLECTIVES", "IA_DP_BACKEND"):
+        env.pop(k, None)
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--pairs-per-gpu", "16"]
+
+    def line(extra):
+        r = subprocess.run(base + extra, capture_output=True, text=True, env=env, timeout=900, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, lines
+        return json.loads(lines[0])
+
+    plain = line([])
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["steps"] == 2 and plain["warmup"] == 1
+    assert plain["variants"] is None and "cpu_baseline" not in plain and "attention_text" not in plain
+    assert plain["roofline"]["traffic"] is None and plain["roofline"]["measured_in"].startswith("the timed region")
+    assert plain["roofline"]["frac"] > 0 and plain["mfma_fraction_dense"] is None
+
+    full = line(["--full", "--no-pmc", "--variant-steps", "1", "--roofline-steps", "1", "--cpu-pairs", "1", "--cpu-steps", "1"])
+    assert full["value"] > 0 and full["steps"] == 2
+    assert full["roofline"]["measured_in"].startswith("separate single-stream pass of 1 steps") and full["roofline"]["frac"] > 0
+    assert set(full["variants"]) == {"full_length_sequences", "unpadded_text_tower", "eval_forward_only", "single_stream"}
+    assert all(v["value"] > 0 for v in full["variants"].values()) and full["mfma_fraction_dense"] > 0
+    assert 0 < full["attention_text"]["executed_key_share_fwd"] <= 1
+    assert full["cpu_baseline"]["value"] > 0

@@ -22,6 +22,7 @@ case "$sub" in
   tests)
     python -m pytest "$@" -q -x 2>&1 | grep -E "passed|failed|error|^E  |^FAILED" | cut -c1-300 ;;
   bench)
+    set -- --full "$@"      # the traffic, variants and CPU baseline printed below are --full measurements
     python bench.py "$@" > gpurun_out/${TAG}_bench_line.json 2> gpurun_out/${TAG}_bench_line.err
     python - <<PY
 import json
