@@ -37,7 +37,7 @@ const char* ia_strerror(int code);
 /* Bumped whenever an entry point is added or the meaning of an argument / output changes (round 2 changed what IA_EPI_BIAS_GELU
  * stores in C2 and what IA_EPI_DGELU expects in aux): a caller built against another header must not run on this library.
  * item_alignment_amd/_lib.py refuses to load a library whose version differs from the one it was written for. */
-#define IA_ABI_VERSION 12
+#define IA_ABI_VERSION 13
 int ia_abi_version(void);
 
 /* ---- GEMM: torch.nn.Linear forward / dgrad / wgrad (src/models/text.py:1241 -> RobertaLayer dense
@@ -475,6 +475,21 @@ int ia_kgpt_row_normalize(float* x, int rows, int D, ia_stream_t stream);
  * uniform in [1, n_ent); counter-based generator keyed by (seed, fact index) */
 int ia_kgpt_corrupt(const int64_t* h, const int64_t* t, const int64_t* r, int n, const float* bern_probs, int n_probs, int n_ent,
                     uint64_t seed, int64_t* nh, int64_t* nt, ia_stream_t stream);
+/* Link-prediction ranks (torchkge LinkPredictionEvaluator; ABI 13).  One call ranks B queries on one side over the raw tables (no
+ * normalisation, no projection term: PKGM and TransE rank alike).  IA_KGPT_LP_TAIL: q = ent[h] + rel[r], true entity t;
+ * IA_KGPT_LP_HEAD: q = ent[t] - rel[r], true entity h.  d(q, c) = sum_k (q_k - c_k)^2 (norm 2) or sum_k |q_k - c_k| (norm 1), one fp32
+ * accumulator per pair summed in k order; score = -d.  rank[b] = 1 + #{c != true : d_c <= d_true} over all n_ent candidates (int64,
+ * ties count against the query).  Filter: grp_off [n_grp + 1] / grp_ids (int64 CSR, each group a sorted list of unique entity ids,
+ * offsets non-decreasing) and q_grp [B], the group of each query (outside [0, n_grp): none); filt_rank[b] = rank[b] minus the members
+ * other than the true id with d <= d_true.  grp_off == NULL: no filter, filt_rank = rank.  A query whose h, t or r lies outside its
+ * table gets rank = filt_rank = 0 and reads nothing.  scores != NULL: also scores[b * n_ent + c] = -d, the values the ranks compare
+ * (fp32 [B, n_ent]).  D % 4 == 0.  workspace >= ia_kgpt_lp_workspace_bytes(B, D) = O(B D), independent of n_ent. */
+#define IA_KGPT_LP_TAIL 0
+#define IA_KGPT_LP_HEAD 1
+size_t ia_kgpt_lp_workspace_bytes(int B, int D);
+int ia_kgpt_lp_rank(const float* ent, const float* rel, const int64_t* h, const int64_t* t, const int64_t* r, int B, int D, int n_ent,
+                    int n_rel, int norm, int side, const int64_t* grp_off, const int64_t* grp_ids, int n_grp, const int64_t* q_grp,
+                    int64_t* rank, int64_t* filt_rank, float* scores, void* workspace, size_t workspace_bytes, ia_stream_t stream);
 
 /* ---- whole-layer drivers: one call = every launch of one encoder layer, in order, on `stream`.
  * Weights: bf16 shadows for the GEMM operands, fp32 masters for bias / LayerNorm vectors. */

@@ -5,6 +5,7 @@ trainer loop with the reference's quirks (INTEGRATION.md "PKGM knowledge-graph p
 The tables (`ent_emb.weight`, `rel_emb.weight`) and the projection (`proj_mat.weight`) are fp32 and stay on the device; their
 gradients are dense fp32 buffers that `ia_kgpt_score` accumulates into and `CoupledAdam.step` (ia_kgpt_adam_l2) clears.
 """
+import io
 import math
 import os
 
@@ -221,17 +222,86 @@ def _max_id(path):
     return m
 
 
-def load_ccks(data_dir):
-    """train2id.txt (`from \\t rel \\t to`, integer ids as data_prepare.py writes them), entity2id.txt / relation2id.txt (`name \\t id`).
-    The integer columns are used as ids (the reference maps them through the name-keyed dictionaries: INTEGRATION.md)."""
-    rows = np.loadtxt(os.path.join(data_dir, "train2id.txt"), dtype=np.int64, delimiter="\t", ndmin=2)
-    n_ent = _max_id(os.path.join(data_dir, "entity2id.txt")) + 1
-    n_rel = _max_id(os.path.join(data_dir, "relation2id.txt")) + 1
+def _load_facts(data_dir, fname, n_ent, n_rel):
+    """One `from \\t rel \\t to` id file as a KnowledgeGraph; ids outside the id files are a ValueError."""
+    path = os.path.join(data_dir, fname)
+    with open(path, "r", encoding="utf-8") as f:
+        text = f.read()
+    rows = np.loadtxt(io.StringIO(text), dtype=np.int64, delimiter="\t", ndmin=2) if text.strip() else np.zeros((0, 3), np.int64)
     h, r, t = (torch.from_numpy(np.ascontiguousarray(rows[:, c])) for c in (0, 1, 2))
     for name, x, n in (("from", h, n_ent), ("to", t, n_ent), ("rel", r, n_rel)):
         if len(x) and (int(x.min()) < 0 or int(x.max()) >= n):
-            raise ValueError(f"train2id.txt column '{name}' holds ids outside [0, {n}) of the id files")
+            raise ValueError(f"{fname} column '{name}' holds ids outside [0, {n}) of the id files")
     return KnowledgeGraph(h, t, r, n_ent, n_rel)
+
+
+def load_ccks(data_dir):
+    """train2id.txt (`from \\t rel \\t to`, integer ids as data_prepare.py writes them), entity2id.txt / relation2id.txt (`name \\t id`).
+    The integer columns are used as ids (the reference maps them through the name-keyed dictionaries: INTEGRATION.md)."""
+    n_ent = _max_id(os.path.join(data_dir, "entity2id.txt")) + 1
+    n_rel = _max_id(os.path.join(data_dir, "relation2id.txt")) + 1
+    return _load_facts(data_dir, "train2id.txt", n_ent, n_rel)
+
+
+class FilterGroups:
+    """The filter of one side as CSR groups: for every (anchor, relation) key of the loaded facts the sorted, unique ids of the entities
+    that complete a known fact -- torchkge's dict_of_tails[(h, r)] (anchor h, members t) or dict_of_heads[(t, r)] (anchor t, members h).
+    `keys` = anchor * n_rel + relation, ascending; group g holds ids[offsets[g]:offsets[g + 1]].  Memory is O(loaded facts)."""
+
+    def __init__(self, keys, offsets, ids, n_rel):
+        self.keys, self.offsets, self.ids, self.n_rel = keys, offsets, ids, n_rel
+
+    @classmethod
+    def build(cls, anchor, relation, member, n_rel):
+        anchor, relation, member = (np.asarray(x, dtype=np.int64) for x in (anchor, relation, member))
+        key = anchor * n_rel + relation
+        order = np.lexsort((member, key))
+        key, member = key[order], member[order]
+        keep = np.ones(len(key), dtype=bool)
+        keep[1:] = (key[1:] != key[:-1]) | (member[1:] != member[:-1])
+        key, member = key[keep], member[keep]
+        keys, starts = np.unique(key, return_index=True)
+        return cls(keys, np.append(starts, len(key)).astype(np.int64), member, n_rel)
+
+    def __len__(self):
+        return len(self.keys)
+
+    def group_of(self, anchor, relation):
+        """Group index of each (anchor, relation) pair, -1 where the key has no group."""
+        key = np.asarray(anchor, dtype=np.int64) * self.n_rel + np.asarray(relation, dtype=np.int64)
+        if not len(self.keys):
+            return np.full(key.shape, -1, dtype=np.int64)
+        g = np.minimum(np.searchsorted(self.keys, key), len(self.keys) - 1)
+        return np.where(self.keys[g] == key, g, -1).astype(np.int64)
+
+    def members(self, g):
+        return self.ids[self.offsets[g]:self.offsets[g + 1]]
+
+
+class KGFilters:
+    """Both filters of link prediction over every loaded fact: `tails` keyed by (h, r), `heads` keyed by (t, r)."""
+
+    def __init__(self, heads, tails):
+        self.heads, self.tails = heads, tails
+
+    @classmethod
+    def build(cls, kgs):
+        kgs = [k for k in kgs if k is not None]
+        h, t, r = (np.concatenate([getattr(k, a).numpy() for k in kgs]) for a in ("head_idx", "tail_idx", "relations"))
+        n_rel = kgs[0].n_rel
+        return cls(FilterGroups.build(t, r, h, n_rel), FilterGroups.build(h, r, t, n_rel))
+
+
+def load_ccks_splits(data_dir, do_eval, do_test):
+    """The reference's load_ccks(data_dir, do_eval, do_test): train2id.txt, then valid2id.txt (do_eval) and test2id.txt (do_test), ids as
+    written.  Returns (train, valid or None, test or None, KGFilters over all loaded facts).  Loading valid2id.txt widens the filter,
+    so the test metrics depend on --do_eval, as in the reference."""
+    n_ent = _max_id(os.path.join(data_dir, "entity2id.txt")) + 1
+    n_rel = _max_id(os.path.join(data_dir, "relation2id.txt")) + 1
+    train = _load_facts(data_dir, "train2id.txt", n_ent, n_rel)
+    valid = _load_facts(data_dir, "valid2id.txt", n_ent, n_rel) if do_eval else None
+    test = _load_facts(data_dir, "test2id.txt", n_ent, n_rel) if do_test else None
+    return train, valid, test, KGFilters.build([train, valid, test])
 
 
 def bernoulli_probs(kg):
@@ -319,3 +389,149 @@ def train(model, kg, optimizer, scheduler, *, n_epochs, batch_size, margin, save
             save_state_dict(model, save_path.format(epoch + 1))
     save_state_dict(model, save_path.format(epoch + 1))
     return means
+
+
+# ------------------------------------------------------------------------------------------------ link-prediction evaluation
+LP_TAIL, LP_HEAD = 0, 1
+
+
+class _DeviceGroups:
+    """FilterGroups on the device (int64 offsets / ids) for ia_kgpt_lp_rank."""
+
+    def __init__(self, groups, dev):
+        self.groups = groups
+        self.off = torch.from_numpy(groups.offsets).to(dev)
+        ids = groups.ids if len(groups.ids) else np.zeros(1, np.int64)
+        self.ids = torch.from_numpy(np.ascontiguousarray(ids)).to(dev)
+        self.n = len(groups)
+
+
+def lp_rank(ent, rel, h, t, r, norm, side, groups=None, q_grp=None, want_scores=False, workspace=None):
+    """One ia_kgpt_lp_rank call over B queries on one side (LP_TAIL: rank t among all entities, LP_HEAD: rank h), on the raw tables.
+    groups: a FilterGroups (or its _DeviceGroups) and q_grp the group index of each query (int64 [B], -1 = none); None = unfiltered.
+    Returns (rank, filt_rank) int64 [B], and the fp32 [B, n_ent] scores the ranks compare when want_scores."""
+    lib = _lib.load()
+    if not ent.is_cuda:
+        raise RuntimeError("link-prediction ranking runs on the GPU")
+    dev = ent.device
+    for name, x in (("ent", ent), ("rel", rel)):
+        if x.dtype != F32 or x.dim() != 2 or not x.is_contiguous() or x.device != dev:
+            raise ValueError(f"{name} must be a contiguous 2-D fp32 table on {dev}, got {tuple(x.shape)} {x.dtype} on {x.device} "
+                             f"(contiguous: {x.is_contiguous()})")
+    if rel.shape[1] != ent.shape[1]:
+        raise ValueError(f"ent and rel widths differ: {ent.shape[1]} != {rel.shape[1]}")
+    h, t, r = (x.to(dev).contiguous().long() for x in (h, t, r))
+    B = h.shape[0]
+    n_ent, D = ent.shape
+    rank = torch.empty(B, device=dev, dtype=torch.int64)
+    filt = torch.empty(B, device=dev, dtype=torch.int64)
+    scores = torch.empty(B, n_ent, device=dev, dtype=F32) if want_scores else None
+    nbytes = lib.ia_kgpt_lp_workspace_bytes(B, D)
+    if workspace is None or workspace.numel() < nbytes:
+        workspace = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    gp = (None, None, 0, None)
+    if groups is not None:
+        dg = groups if isinstance(groups, _DeviceGroups) else _DeviceGroups(groups, dev)
+        qg = torch.as_tensor(q_grp, dtype=torch.int64).to(dev).contiguous()
+        gp = (dg.off.data_ptr(), dg.ids.data_ptr(), dg.n, qg.data_ptr())
+    check(lib.ia_kgpt_lp_rank(ent.data_ptr(), rel.data_ptr(), h.data_ptr(), t.data_ptr(), r.data_ptr(), B, D, n_ent, rel.shape[0], norm, side,
+                              *gp, rank.data_ptr(), filt.data_ptr(), None if scores is None else scores.data_ptr(), workspace.data_ptr(),
+                              nbytes, stream_ptr()), "ia_kgpt_lp_rank")
+    return (rank, filt, scores) if want_scores else (rank, filt)
+
+
+class NotYetEvaluatedError(RuntimeError):
+    pass
+
+
+class LinkPredictionEvaluator:
+    """torchkge LinkPredictionEvaluator on the device: raw and filtered ranks of the true head and the true tail of every fact of `kg`
+    among all entities, scored on the model's raw tables (no normalisation, no projection term: PKGM ranks like TransE).  `filters`
+    (KGFilters) hold the known facts of every loaded split.  The metrics are torchkge's fp32 expressions over the CPU int64 ranks."""
+
+    def __init__(self, model, knowledge_graph, filters):
+        self.model, self.kg, self.filters = model, knowledge_graph, filters
+        n = knowledge_graph.n_facts
+        self.rank_true_heads = torch.empty(n, dtype=torch.int64)
+        self.rank_true_tails = torch.empty(n, dtype=torch.int64)
+        self.filt_rank_true_heads = torch.empty(n, dtype=torch.int64)
+        self.filt_rank_true_tails = torch.empty(n, dtype=torch.int64)
+        self.evaluated = False
+
+    @torch.no_grad()
+    def evaluate(self, b_size, verbose=False):
+        """Ranks in file order, b_size queries per kernel call (the ranks do not depend on it).  verbose is accepted for torchkge's
+        signature; there is no progress bar."""
+        if b_size <= 0:
+            raise ValueError(f"b_size must be positive, got {b_size}")
+        ent, rel = self.model.ent_emb.weight.data, self.model.rel_emb.weight.data
+        dev = ent.device
+        kg = self.kg
+        n = kg.n_facts
+        h, t, r = (x.to(dev) for x in (kg.head_idx, kg.tail_idx, kg.relations))
+        hn, tn, rn = (x.numpy() for x in (kg.head_idx, kg.tail_idx, kg.relations))
+        sides = ((LP_TAIL, _DeviceGroups(self.filters.tails, dev), self.filters.tails.group_of(hn, rn)),
+                 (LP_HEAD, _DeviceGroups(self.filters.heads, dev), self.filters.heads.group_of(tn, rn)))
+        out = {s: (torch.empty(n, device=dev, dtype=torch.int64), torch.empty(n, device=dev, dtype=torch.int64)) for s, _, _ in sides}
+        ws = torch.empty(_lib.load().ia_kgpt_lp_workspace_bytes(max(1, min(b_size, n)), ent.shape[1]), device=dev, dtype=torch.uint8)
+        for i0 in range(0, n, b_size):
+            sl = slice(i0, min(n, i0 + b_size))
+            for side, dg, qg in sides:
+                rk, fr = lp_rank(ent, rel, h[sl], t[sl], r[sl], self.model.norm, side, dg, qg[sl], workspace=ws)
+                out[side][0][sl] = rk
+                out[side][1][sl] = fr
+        self.rank_true_tails, self.filt_rank_true_tails = (x.cpu() for x in out[LP_TAIL])
+        self.rank_true_heads, self.filt_rank_true_heads = (x.cpu() for x in out[LP_HEAD])
+        self.evaluated = True
+
+    def _check(self):
+        if not self.evaluated:
+            raise NotYetEvaluatedError("Evaluator not evaluated call LinkPredictionEvaluator.evaluate")
+
+    def mean_rank(self):
+        self._check()
+        sum_ = (self.rank_true_heads.float().mean() + self.rank_true_tails.float().mean()).item()
+        filt_sum = (self.filt_rank_true_heads.float().mean() + self.filt_rank_true_tails.float().mean()).item()
+        return sum_ / 2, filt_sum / 2
+
+    def hit_at_k_heads(self, k=10):
+        self._check()
+        head_hit = (self.rank_true_heads <= k).float().mean()
+        filt_head_hit = (self.filt_rank_true_heads <= k).float().mean()
+        return head_hit.item(), filt_head_hit.item()
+
+    def hit_at_k_tails(self, k=10):
+        self._check()
+        tail_hit = (self.rank_true_tails <= k).float().mean()
+        filt_tail_hit = (self.filt_rank_true_tails <= k).float().mean()
+        return tail_hit.item(), filt_tail_hit.item()
+
+    def hit_at_k(self, k=10):
+        self._check()
+        head_hit, filt_head_hit = self.hit_at_k_heads(k=k)
+        tail_hit, filt_tail_hit = self.hit_at_k_tails(k=k)
+        return (head_hit + tail_hit) / 2, (filt_head_hit + filt_tail_hit) / 2
+
+    def mrr(self):
+        self._check()
+        head_mrr = (self.rank_true_heads.float() ** (-1)).mean()
+        tail_mrr = (self.rank_true_tails.float() ** (-1)).mean()
+        filt_head_mrr = (self.filt_rank_true_heads.float() ** (-1)).mean()
+        filt_tail_mrr = (self.filt_rank_true_tails.float() ** (-1)).mean()
+        return (head_mrr + tail_mrr).item() / 2, (filt_head_mrr + filt_tail_mrr).item() / 2
+
+    def results_text(self, k=None, n_digits=3):
+        """The lines print_results prints, as one string."""
+        self._check()
+        if k is None:
+            k = 10
+        lines = []
+        for i in ([k] if isinstance(k, int) else list(k)):
+            lines.append("Hit@{} : {} \t\t Filt. Hit@{} : {}".format(i, round(self.hit_at_k(k=i)[0], n_digits), i,
+                                                                     round(self.hit_at_k(k=i)[1], n_digits)))
+        lines.append("Mean Rank : {} \t Filt. Mean Rank : {}".format(int(self.mean_rank()[0]), int(self.mean_rank()[1])))
+        lines.append("MRR : {} \t\t Filt. MRR : {}".format(round(self.mrr()[0], n_digits), round(self.mrr()[1], n_digits)))
+        return "\n".join(lines) + "\n"
+
+    def print_results(self, k=None, n_digits=3):
+        print(self.results_text(k, n_digits), end="", flush=True)
