@@ -12,12 +12,12 @@
 // flavours (y = xW^T, dx = dy W, dW = dy^T x; torch.nn.Linear under autograd, reference
 // src/models/text.py:1241 -> transformers RobertaLayer) all stream each operand from HBM once.
 //
-// Two tile configurations share staging / epilogue code:
-//   T256: 256x256x64 per 512-thread workgroup (8 waves as 2x4, 128x64 per wave, 4x2 MFMA 32x32x16
-//         fragments, 128 KiB LDS double buffer) - the large-M encoder GEMMs.  The 128x64 wave tile halves
-//         the LDS bytes read per MFMA relative to T128 (whose 64x64 wave tile saturates the LDS port).
-//   T128: 128x128x64 per 256-thread workgroup (4 waves as 2x2, 64x64 per wave, 4x4 MFMA 16x16x32) -
-//         small outputs (heads, tiny test shapes).
+// Two tile configurations (make_plan chooses by output size):
+//   T256W: 256x256x64 per 256-thread workgroup (4 waves as 2x2, one per SIMD, 128x128 per wave, 4x4 MFMA 32x32x16
+//          fragments, 128 KiB LDS double buffer), persistent over output tiles - the large-M encoder GEMMs.  T256LA is
+//          its plain-NT variant whose k pipeline runs on into the next tile.
+//   T128:  128x128x64 per 256-thread workgroup (4 waves as 2x2, 64x64 per wave, 4x4 MFMA 16x16x32) -
+//          small outputs (heads, tiny test shapes), the shifted-view convolution GEMMs and channel groups.
 // LDS is filled by buffer_load ... lds (16 B/lane; out-of-range rows arrive as zeros, so ragged M / K
 // tails need no extra code) with the XOR swizzle applied on the source side.  The MFMA is issued with
 // swapped operands (C^T fragments) so each lane ends up with runs of consecutive output columns.
@@ -54,7 +54,7 @@ struct GemmArgs {
   int qcols; float qscale;
   int tiles_m, tiles_n;
   int splits, nk_per_split;   // split-K (fp32 output only): split s owns k-tiles [s*nk_per_split, ...)
-  float* csum_part;           // EPI_DGELU_CS: [ceil(M/128)][N] fp32 column sums of each 128-row block of the output (T256 only)
+  float* csum_part;           // EPI_DGELU_CS: [ceil(M/128)][N] fp32 column sums of each 128-row block of the output (256-wide kernels only)
   int split_id;               // set inside the kernels (derived from the XCD-aware work order)
   float* ws;                  // [splits][M][N] fp32 partials when splits > 1
   // weight-gradient form (A, B k-strided, fp32 C), T128: rsum_out[group * M + m] += sum_k A[k][m] -- the bias gradient of the layer,
@@ -145,8 +145,8 @@ IA_DEV void epi_store4(const GemmArgs& p, int m, int n, f32x4 v) {
 }
 
 // One 16-byte global store = one VMEM instruction (hipcc emits a single global_store_dwordx4 for an aligned 16-byte vector store;
-// tools/check_gemm_isa.sh counts them).  The persistent T256 kernel leaves a tile's output stores in flight while the next tile's
-// main loop starts and waits with a COUNTED s_waitcnt vmcnt(N) for the k-tile DMA issued before them (vmcnt retires in order), so
+// tools/check_gemm_isa.sh counts them).  The persistent 256-wide kernels leave a tile's output stores in flight while the next tile's
+// main loop starts and wait with a COUNTED s_waitcnt vmcnt(N) for the k-tile DMA issued before them (vmcnt retires in order), so
 // the number of store instructions per epilogue must be known exactly.  The store is a plain (compiler-visible) one on purpose: the
 // epilogue's aux / bias loads are software-pipelined two slices ahead of the stores, and only when hipcc counts the stores too does
 // it wait for such a load with vmcnt(k > 0) and leave the younger stores in flight (an asm store is invisible to its counters: every
@@ -161,7 +161,7 @@ constexpr int epi_stores_per_call() { return OUTF32 ? 2 : (EPI == EPI_BIAS_GELU 
 template <int EPI>
 constexpr int epi_extra_stores() { return EPI == EPI_DGELU_CS ? 2 : 0; }     // the wave's column-sum partial: two 16-byte stores
 
-// v = 8 consecutive output columns n..n+7 of row m (row-coalesced epilogue of the T256 kernel).  PRE: bias (pb0 | pb1) and aux (ax)
+// v = 8 consecutive output columns n..n+7 of row m (row-coalesced epilogue of the 256-wide kernels).  PRE: bias (pb0 | pb1) and aux (ax)
 // were fetched ahead by the caller; else they are loaded here.
 // BUF (full tiles of the one-wave-per-SIMD kernel, bf16 outputs): the output streams are addressed through buffer windows over the
 // wave's rows with one 32-bit lane offset (io.off) instead of 64-bit pointer arithmetic per access (3 VALU instructions each)
@@ -551,352 +551,16 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs p) {
 }
 }  // namespace t128
 
-// ============================================================================== T256 (8 waves, 32x32x16)
-namespace t256 {
-constexpr int BM = 256, BN = 256, TILE_BYTES = 32768;
-constexpr int STAGE_BYTES = 16 * 64 * 4;                   // per-wave epilogue slot: 16 rows x 64 columns fp32
-constexpr int LDS_BYTES = 2 * 2 * TILE_BYTES + 8 * STAGE_BYTES;   // 128 KiB k-tile double buffer + 32 KiB = all 160 KiB of the CU
-
-template <bool KS>
-IA_DEV void stage_tile(__amdgpu_buffer_rsrc_t rs, char* s, int kt, int x0, int ld, int K, int tid, int wave) {
-  // k-contiguous: [256 rows(x)][64 k], 128 B rows, chunk XOR (row>>1)&7 (conflict-free ds_read_b128 for any
-  // 16 rows distinct mod 16); k-strided: [64 rows(k)][256 x], 512 B rows, 32 B slot XOR (k&3)
-#pragma unroll
-  for (int issue = 0; issue < 4; ++issue) {
-    uint32_t off;
-    if (!KS) {
-      const int row = issue * 64 + (tid >> 3);
-      const int c = (tid & 7) ^ ((row >> 1) & 7);
-      const int k = kt * BK + c * 8;
-      off = (uint32_t)(((x0 + row) * ld + k) * 2);
-      if (k >= K) off = OOB;
-    } else {
-      const int row = issue * 16 + (tid >> 5);
-      const int c = (tid & 31) ^ ((row & 3) << 2);
-      const int k = kt * BK + row;
-      off = (uint32_t)((k * ld + x0 + c * 8) * 2);
-      if (k >= K) off = OOB;
-    }
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, IA_LDS(s + issue * 8192 + wave * 1024), 16, off, 0, 0, 0);
-  }
-}
-
-// fragment of MFMA 32x32x16: lane (i = lane&31, half = lane>>5) holds operand row i, k = half*8 .. +7
-IA_DEV bf16x8 frag_kc(const char* s, int row, int chunk) {
-  return *reinterpret_cast<const bf16x8*>(s + row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4));
-}
-
-// same fragment out of a k-strided tile: each 16-lane group transposes a [4 k][16 col] block; lane (i -> column
-// col0 + i, half) gets k rows k0 + 8*half + {0..3} from the first read and + {4..7} from the second, i.e. the
-// standard k order of the MFMA operand.
-IA_DEV bf16x8 frag_ks(const char* s, int k0, int col0, int lane) {
-  const int p = lane & 15, G = lane >> 4;
-  const int row = k0 + 8 * (G >> 1) + (p >> 2);
-  const int col = col0 + 16 * (G & 1) + (p & 3) * 4;
-  const int addr = row * 512 + ((((col >> 3) ^ ((row & 3) << 2))) << 4) + (col & 7) * 2;
-  const uint32_t a = ia_lds_addr(s) + (uint32_t)addr;   // asm reads: main_loop waits lgkmcnt(0) before the MFMAs
-  s16x4 lo = ia_tr_read<0>(a);
-  s16x4 hi = ia_tr_read<4 * 512>(a);
-  s16x8 r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, r);
-}
-
-// Ping-pong main loop of one wave group (GRP 0: rows 0..127 of the block tile and the A-operand DMA;
-// GRP 1: rows 128..255 and the B-operand DMA).  See the schedule comment in gemm_kernel.
-template <int GRP, bool AKS, bool BKS, int PEND>
-IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][2], __amdgpu_buffer_rsrc_t rs, int x0, int ld, int kt0, int kta0,
-                      int n_tiles, int nk_all, int wn, int lane, bool prologue_only, bool stores_in_flight) {
-  // rs is this workgroup's buffer window (rsrc_at): x0 and the k-tile index used for ADDRESSES (kta0 + u) are relative to its
-  // origin -- tile row 0 of a k-contiguous operand (kta0 = kt0: the k offset is a column), slab row 0 of a k-strided one (kta0 = 0)
-  constexpr bool MYKS = GRP ? BKS : AKS;            // layout of the operand this group streams
-  const int hh = lane >> 5, li = lane & 31;
-  const int gt = wn * 64 + lane;                    // thread index inside the group (0..255)
-  // One per-lane byte offset serves all 8 DMA pieces of a half tile: the swizzled chunk a lane fetches does not
-  // depend on the piece (the row advance per piece is a multiple of the swizzle period), so piece and k-tile
-  // advances are both scalars folded into the instruction's soffset.
-  uint32_t voff0, piece_step;
-  if (!MYKS) {
-    const int row = gt >> 3;
-    voff0 = (uint32_t)(((x0 + row) * ld + (((gt & 7) ^ ((row >> 1) & 7)) * 8)) * 2);
-    piece_step = (uint32_t)(32 * ld * 2);
-  } else {
-    const int row = gt >> 5;
-    voff0 = (uint32_t)((row * ld + x0 + (((gt & 31) ^ ((row & 3) << 2)) * 8)) * 2);
-    piece_step = (uint32_t)(8 * ld * 2);
-  }
-  const uint32_t kstep = MYKS ? (uint32_t)(BK * ld * 2) : (uint32_t)(BK * 2);
-  const bool ragged_k = (p.K & (BK - 1)) != 0;
-  char* const my_half = smem + (GRP ? TILE_BYTES : 0) + wn * 1024;
-
-  auto dma_piece = [&](int u, int i) {             // piece i of this group's half of k-tile u -> buffer u&1
-    char* dst = my_half + (u & 1) * 2 * TILE_BYTES + i * 4096;
-    const int kt = kt0 + u, kta = kta0 + u;
-    if (!ragged_k || kt != nk_all - 1) {
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, IA_LDS(dst), 16, voff0, (int)(kta * kstep + i * piece_step), 0, 0);
-    } else {                                        // last, partial k-tile: lanes past K fetch zeros
-      const int k = MYKS ? kt * BK + i * 8 + (gt >> 5) : kt * BK + ((gt & 7) ^ (((gt >> 3) >> 1) & 7)) * 8;
-      const uint32_t off = k < p.K ? voff0 + kta * kstep + i * piece_step : OOB;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, IA_LDS(dst), 16, off, 0, 0, 0);
-    }
-  };
-
-  if (prologue_only) {       // called ahead of time (before the previous tile's epilogue): just start the first two k-tiles
-#pragma unroll
-    for (int i = 0; i < 8; ++i) dma_piece(0, i);
-    if (n_tiles > 1) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) dma_piece(1, i);
-    }
-    return;
-  }
-  // the prologue DMA of this tile.  After a full-tile epilogue exactly PEND store instructions were issued behind it and
-  // may stay in flight (vmcnt retires in order: at most PEND outstanding <=> every older DMA piece has landed).
-  if (stores_in_flight) asm volatile("s_waitcnt vmcnt(%0)" : : "n"(PEND) : "memory");
-  else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  if (GRP == 1) __builtin_amdgcn_s_barrier();      // G1 idles through phase 0
-
-  // B fragment row i <-> n so that a lane ends up with 16 consecutive output columns (k-contiguous B only)
-  const int nperm = ((li >> 2) & 1) * 16 + (li >> 3) * 4 + (li & 3);
-  const bool dma_on = !(IA_DBG(p) & 2);
-
-  for (int u = 0; u < n_tiles; ++u) {
-    const char* sA = smem + (u & 1) * 2 * TILE_BYTES;
-    const char* sB = sA + TILE_BYTES;
-    // ------------------------------------------------------------------ LOAD phase
-    if (GRP == 0 && u >= 1 && u + 1 < n_tiles && dma_on) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) dma_piece(u + 1, i);
-    }
-    bf16x8 af[4][4], bfr[4][2];
-    if (!(IA_DBG(p) & 8) || u == 0)
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi) {
-        if (AKS) af[ks][mi] = frag_ks(sA, ks * 16, GRP * 128 + mi * 32, lane);
-        else af[ks][mi] = frag_kc(sA, GRP * 128 + mi * 32 + li, ks * 2 + hh);
-      }
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni) {
-        if (BKS) bfr[ks][ni] = frag_ks(sB, ks * 16, wn * 64 + ni * 32, lane);
-        else bfr[ks][ni] = frag_kc(sB, wn * 64 + ni * 32 + nperm, ks * 2 + hh);
-      }
-    }
-    // G1's DMA issued in its previous COMPUTE (none yet at u == 0: do not drain the previous tile's stores there)
-    if (GRP == 1 && u >= 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    if (!(IA_DBG(p) & 16)) __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    // ------------------------------------------------------------------ COMPUTE phase
-    // G1 streams its 8 DMA pieces of k-tile u+2 in the shadow of its own MFMAs: one piece per 4 MFMAs
-    const bool stage_now = GRP == 1 && u + 2 < n_tiles && dma_on;
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi) {
-        if (GRP == 1 && (mi & 1) == 0 && stage_now) dma_piece(u + 2, ks * 2 + (mi >> 1));
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bfr[ks][ni], af[ks][mi], acc[mi][ni], 0, 0, 0);
-      }
-    __builtin_amdgcn_s_setprio(0);
-    if (GRP == 0 && u >= 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // G0's DMA issued in this iteration's LOAD (u >= 1)
-    __builtin_amdgcn_sched_barrier(0);
-    if (!(IA_DBG(p) & 16)) __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  if (GRP == 0) __builtin_amdgcn_s_barrier();      // matches G1's last phase
-}
-
-template <bool AKS, bool BKS, int EPI, bool OUTF32>
-__global__ __launch_bounds__(512) void gemm_kernel(GemmArgs p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane0 = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 2, wn = wave & 3;          // 2 x 4 waves, 128 x 64 each; waves w and w+4 share a SIMD
-  const int nk_all = (p.K + BK - 1) / BK;
-  const int total_tiles = p.tiles_m * p.tiles_n;
-  // Split-K launches are a 1-D grid of tiles x splits workgroups whose XCD-aware order has the split OUTERMOST: one XCD's run of
-  // 32 work items is then an 8 x 4 block of tiles of ONE k-slab, i.e. 12 operand panel streams per XCD instead of 36 when the
-  // splits of a tile shared an XCD (HBM bytes of the fc1 weight gradient: 2.2 GB -> 0.9 GB per launch, algorithmic 0.67 GB).
-  int first_tile = blockIdx.x;          // index into the tile work order
-  bool ordered = false;                 // first_tile already is a position of that order (no XCD renumbering inside run())
-  p.split_id = 0;
-  if (p.splits > 1) {
-    const int w = xcd_chunk(blockIdx.x, gridDim.x);
-    p.split_id = w / total_tiles;
-    first_tile = w % total_tiles;
-    ordered = true;
-  }
-  const int kt0 = p.split_id * p.nk_per_split;
-  const int n_tiles = min(nk_all, kt0 + p.nk_per_split) - kt0;
-
-  // Ping-pong schedule.  The 8 waves form two groups (grp = wm: rows 0..127 / 128..255 of the block tile); every
-  // SIMD hosts one wave of each group.  A wave alternates a LOAD phase (all 24 fragment reads of one k-tile into
-  // registers) and a COMPUTE phase (its 32 MFMAs from registers); group 1 runs one phase behind group 0, so on
-  // each SIMD one wave feeds the matrix pipe while the other one reads LDS.  One s_barrier per phase boundary.
-  //   phase 2u   : G0 LOAD(u)     | G1 COMPUTE(u-1)
-  //   phase 2u+1 : G0 COMPUTE(u)  | G1 LOAD(u)
-  // LDS holds two k-tiles; tile u+2 goes into the buffer of tile u once both groups have read it (after phase
-  // 2u+1): G0 streams the A half during its LOAD(u+1), G1 the B half between the MFMAs of its COMPUTE(u), and
-  // each waits for its own DMA one phase later, i.e. before the barrier that ends phase 2u+3.
-  //
-  // The workgroup is persistent over output tiles (one workgroup per CU): the DMA of the NEXT tile's first two
-  // k-tiles is issued before the current tile's epilogue (which stages through LDS outside the k-tile buffers), so the
-  // ~2 us HBM round trip of a tile prologue hides behind the epilogue instead of idling the CU.
-  constexpr int PEND = 16 * epi_stores_per_call<EPI, OUTF32>() + epi_extra_stores<EPI>();   // store instructions of one full-tile epilogue, per wave
-  static_assert(PEND < 60, "vmcnt is a 6-bit counter");
-  auto coords = [&](int tile, int& bm, int& bn) {
-    if (ordered) tile_of_order(p, tile, bm, bn); else tile_of_index(p, tile, total_tiles, bm, bn);
-  };
-  auto run = [&](int tile, bool prologue_only, f32x16 (&acc)[4][2], bool stores_in_flight) {
-    int bm, bn;
-    coords(tile, bm, bn);
-    // keep per-lane address arithmetic from being hoisted out of the tile loop (it would stay live across the
-    // epilogue and push the 256-register kernel into scratch): every call derives it afresh from an opaque lane id
-    int lane = lane0;
-    asm volatile("" : "+v"(lane));
-    if (wm == 0) main_loop<0, AKS, BKS, PEND>(p, smem, acc, rsrc_at(p.A, p.a_bytes, (uint64_t)(AKS ? kt0 * BK : bm * BM) * p.lda), AKS ? bm * BM : 0, p.lda,
-                                               kt0, AKS ? 0 : kt0, n_tiles, nk_all, wn, lane, prologue_only, stores_in_flight);
-    else         main_loop<1, AKS, BKS, PEND>(p, smem, acc, rsrc_at(p.B, p.b_bytes, (uint64_t)(BKS ? kt0 * BK : bn * BN) * p.ldb), BKS ? bn * BN : 0, p.ldb,
-                                               kt0, BKS ? 0 : kt0, n_tiles, nk_all, wn, lane, prologue_only, stores_in_flight);
-  };
-
-  if ((IA_DBG(p) & 2048) && ((blockIdx.x >> 3) & 1)) {     // ablation: every other CU of an XCD starts (dbg >> 16) us late
-    const unsigned long long t0 = wall_clock64();
-    while (wall_clock64() - t0 < (unsigned long long)(IA_DBG(p) >> 16) * 100ull) __builtin_amdgcn_s_sleep(8);
-  }
-  f32x16 acc[4][2];
-  int tile = first_tile;
-  run(tile, true, acc, false);
-  bool stores_in_flight = false;
-  while (true) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    run(tile, false, acc, stores_in_flight);
-    const int next = ordered ? total_tiles : tile + gridDim.x;      // a split-K workgroup owns exactly one (tile, k-slab)
-
-    // The k-tile buffers are free once the main loop's last barrier has passed: start the NEXT tile's first two k-tiles
-    // now, so their HBM round trip (~2 us) runs under this tile's epilogue.
-    if (next < total_tiles) run(next, true, acc, false);
-
-    // Epilogue through a wave-private LDS slot outside the k-tile buffers (no workgroup barrier).  The MFMA C^T fragments
-    // give each lane 4-element runs scattered over 32 rows, which as direct global stores cost ~11 us per tile (64 separate
-    // segments per store instruction).  Instead a wave stages 16 rows x 64 columns of fp32 (4 KiB, 16-byte chunks XOR-swizzled
-    // by row: conflict-free both ways), then streams them out: bias / residual / GELU inputs are read and all outputs written
-    // as full 128-byte row segments, 8 rows per instruction.  C^T fragment: lane (m = li, half hh) register r <-> fragment
-    // row i = (r&3) + 8*(r>>2) + 4*hh; k-contiguous B: n = hh*16 + r; k-strided B: n = i.
-    int bm, bn;
-    coords(tile, bm, bn);
-    const int m0 = bm * BM + wm * 128, n0 = bn * BN + wn * 64;
-    int lane_e = lane0;
-    asm volatile("" : "+v"(lane_e));
-    const int hh = lane_e >> 5, li = lane_e & 31;
-    char* stg = smem + 2 * 2 * TILE_BYTES + wave * STAGE_BYTES;
-    const int wrow = li & 15, rrow = lane_e >> 3, c8 = lane_e & 7;
-    // this wave's 128 x 64 part lies entirely inside C: no row / column guards, the store count of the tile is exact
-    const bool full = m0 + 128 <= p.M && n0 + 64 <= p.N;
-    constexpr bool HAS_BIAS = EPI == EPI_BIAS || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_GELU_ACT || EPI == EPI_BIAS_ADD;
-    constexpr bool HAS_AUX = EPI == EPI_ADD || EPI == EPI_BIAS_ADD || EPI == EPI_DGELU || EPI == EPI_DGELU_CS;
-    // Slice c (c = 0..15) = rows (c>>2)*32 + ((c>>1)&1)*16 + (c&1)*8 + rrow of this wave's part, the lane's 8 columns n0 + c8*8.
-    // PRE (full parts): the bias - the same 8 columns for all slices - is read once per tile, and the aux operand runs AHEAD slices
-    // ahead of the stores: VMEM retires in order, so a load issued behind a store can only be waited for by draining that store;
-    // issued ahead, hipcc's own counters leave the younger stores in flight (vmcnt(2 * AHEAD) in the steady state).
-    constexpr int AHEAD = 4;
-    auto drain_tile = [&](auto PREFETCHED) {
-      constexpr bool PRE = decltype(PREFETCHED)::value;
-      f32x4 pb0, pb1;          // only read when the epilogue has a bias (left undefined otherwise: no registers, no spill)
-      float cs[8];
-      if (EPI == EPI_DGELU_CS) {      // zeroed here, opaquely: a hoisted zero vector would live (and spill) across the whole main loop
-#pragma unroll
-        for (int j = 0; j < 8; ++j) asm volatile("v_mov_b32 %0, 0" : "=v"(cs[j]));
-      }
-      bf16x8 ax[AHEAD + 1];
-      auto aux_of = [&](int c) {
-        const int row = m0 + (c >> 2) * 32 + ((c >> 1) & 1) * 16 + (c & 1) * 8 + rrow;
-        return *reinterpret_cast<const bf16x8*>(p.aux + (size_t)row * p.ldaux + n0 + c8 * 8);
-      };
-      if (PRE && HAS_BIAS) { pb0 = *reinterpret_cast<const f32x4*>(p.bias + n0 + c8 * 8); pb1 = *reinterpret_cast<const f32x4*>(p.bias + n0 + c8 * 8 + 4); }
-      if (PRE && HAS_AUX) {
-#pragma unroll
-        for (int c = 0; c < AHEAD; ++c) ax[c] = aux_of(c);
-      }
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi) {
-#pragma unroll
-        for (int h16 = 0; h16 < 2; ++h16) {
-          if ((li >> 4) == h16) {
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-              for (int rg = 0; rg < 4; ++rg) {
-                const int chunk = (ni * 32 + (BKS ? rg * 8 + hh * 4 : hh * 16 + rg * 4)) >> 2;
-                const f32x4 v = {acc[mi][ni][rg * 4], acc[mi][ni][rg * 4 + 1], acc[mi][ni][rg * 4 + 2], acc[mi][ni][rg * 4 + 3]};
-                *reinterpret_cast<f32x4*>(stg + wrow * 256 + ((chunk ^ wrow) << 4)) = v;
-              }
-          }
-          __builtin_amdgcn_wave_barrier();
-#pragma unroll
-          for (int it = 0; it < 2; ++it) {
-            const int row = it * 8 + rrow;
-            const f32x4 lo = *reinterpret_cast<const f32x4*>(stg + row * 256 + (((2 * c8) ^ row) << 4));
-            const f32x4 hi = *reinterpret_cast<const f32x4*>(stg + row * 256 + (((2 * c8 + 1) ^ row) << 4));
-            const int m = m0 + mi * 32 + h16 * 16 + row, n = n0 + c8 * 8;
-            const int c = mi * 4 + h16 * 2 + it;
-            if (PRE) {
-              if (HAS_AUX && c + AHEAD < 16) {
-                ax[(c + AHEAD) % (AHEAD + 1)] = aux_of(c + AHEAD);
-                asm volatile("" ::: "memory");      // the load stays in front of this slice's store (hipcc would sink it behind)
-              }
-              if (!(IA_DBG(p) & 64)) epi_store8<EPI, OUTF32, true>(p, m, n, lo, hi, pb0, pb1, ax[c % (AHEAD + 1)], cs);
-            } else {
-              if (m < p.M && n < p.N && !(IA_DBG(p) & 64)) epi_store8<EPI, OUTF32, false>(p, m, n, lo, hi, pb0, pb1, ax[0], cs);
-            }
-            if (IA_DBG(p) & 64) asm volatile("" : : "v"(lo), "v"(hi));
-          }
-          __builtin_amdgcn_wave_barrier();
-        }
-      }
-      if (EPI == EPI_DGELU_CS) {
-        // column sums of this wave's 128 rows: the 8 lanes that share a column group (lane & 7) differ in lane bits 3..5
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-          float v = cs[r];
-          v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, v), __builtin_bit_cast(int, v), 0x128, 0xF, 0xF,
-                                                                     false));                    // row_ror:8   -> lane ^ 8
-          v = ia_add_xor32(ia_add_xor16(v));                                                      // lane ^ 16, lane ^ 32 (common.h)
-          cs[r] = v;
-        }
-        if (rrow == 0 && n0 + c8 * 8 < p.N) {      // lanes 0..7: 8 consecutive columns each (two 16-byte stores, counted in PEND)
-          float* dst = p.csum_part + (size_t)(m0 >> 7) * p.N + n0 + c8 * 8;
-          gstore16(dst, f32x4{cs[0], cs[1], cs[2], cs[3]});
-          gstore16(dst + 4, f32x4{cs[4], cs[5], cs[6], cs[7]});
-        }
-      }
-    };
-    if (!(IA_DBG(p) & 32)) {
-      if (full && (HAS_BIAS || HAS_AUX) && !(IA_DBG(p) & 256)) drain_tile(std::true_type{}); else drain_tile(std::false_type{});
-    }
-    if (next >= total_tiles) break;
-    // a wave whose 128 x 64 part of the tile was clipped by M or N issued fewer stores than PEND: drain instead of counting
-    stores_in_flight = !(IA_DBG(p) & 96) && full;
-    if (!stores_in_flight) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    tile = next;
-  }
-}
-}  // namespace t256
-
 // ============================================================================== T256W (4 waves, 128 x 128 per wave, 32x32x16)
-// Same 256 x 256 x 64 block tile, LDS image, DMA pieces, tile order and epilogue as T256, but ONE wave per SIMD owning a 128 x 128
-// part (256 accumulators in AGPRs): 8 fragment reads per 16 MFMAs instead of 12, i.e. 128 + 64 KiB of LDS traffic per k-tile where
-// T256 moves 192 + 64 KiB.  With one wave per SIMD nothing else hides latency, so the wave pipelines itself, on the schedule of
+// 256 x 256 x 64 block tile per 256-thread workgroup, ONE wave per SIMD owning a 128 x 128 part (256 accumulators in AGPRs): 8 fragment
+// reads per 16 MFMAs, i.e. 128 + 64 KiB of LDS traffic per k-tile -- the 64 x 64 wave tile of T128 saturates the LDS port.  (Until
+// round 4 a second 256 x 256 kernel, T256, ran two waves per SIMD on 128 x 64 wave tiles -- 12 reads per 16 MFMAs, 192 + 64 KiB -- for
+// the VALU-heavy epilogues; removed once this kernel won those too: bias + GELU 412 -> 405 us, x GELU' + column sums 317 -> 313 us at
+// 32640 x 4096 x 1024, step +0.65 % on the same box.)
+// The workgroup is persistent over output tiles (one workgroup per CU: the kernel takes all of its LDS): the DMA of the NEXT tile's
+// first two k-tiles is issued before the current tile's epilogue, which stages through LDS outside the k-tile buffers, so the ~2 us
+// HBM round trip of a tile prologue hides behind the epilogue instead of idling the CU.
+// With one wave per SIMD nothing else hides latency, so the wave pipelines itself, on the schedule of
 // the library's hand-written 256x256x64 kernels (read off their disassembly): the WHOLE k-tile of fragments lives in registers
 // (four sets of 8 fragments), so the LDS buffer of k-tile u is free after the first HALF of iteration u; k-tile u+2 is then
 // requested piece by piece between the MFMAs of the second half (one 1-KiB LDS-DMA per two MFMAs, never a burst), stays in flight
@@ -906,29 +570,11 @@ __global__ __launch_bounds__(512) void gemm_kernel(GemmArgs p) {
 //   k-step 1: MFMAs on set 1 | reads of set 3;  lgkmcnt(0), barrier B1: every wave holds all of k-tile u -> its buffer is free
 //   k-step 2: MFMAs on set 2 | DMA pieces 0..7 of k-tile u+2
 //   k-step 3: vmcnt(8), barrier B2: k-tile u+1 has landed;  MFMAs on set 3 | reads of set 0 of k-tile u+1, DMA pieces 8..15
-#ifndef IA_T256W_ROUND
-#define IA_T256W_ROUND 1       // which GEMM forms run the ROUND k-loop schedule: 0 none, 1 k-contiguous A and B (forward GEMMs), 2 all but the weight-gradient form
-#endif
-#ifndef IA_T256W_MFMA16
-#define IA_T256W_MFMA16 0
-#endif
-#ifndef IA_T256W_NOREADS
-#define IA_T256W_NOREADS 0
-#endif
-#ifndef IA_T256W_SPREAD3
-#define IA_T256W_SPREAD3 0     // second k-loop schedule (a k-strided operand): DMA pieces one per three MFMAs over k-steps 2, 3 and the next k-step 0
-                               // -- measured: data gradient +-0, weight gradient -0.9 % (what helps the forward forms does not help these)
-#endif
-#ifndef IA_T256W_KS_LANEOFF
-#define IA_T256W_KS_LANEOFF 1  // k-strided operands: whole DMA address in the lane offset (hardware range check) instead of compare + select per piece
-#endif
-
+// (the forward GEMMs run a second schedule, ROUND: see main_loop)
 namespace t256w {
-using t256::BM;
-using t256::BN;
-using t256::TILE_BYTES;
-using t256::STAGE_BYTES;
-using t256::LDS_BYTES;
+constexpr int BM = 256, BN = 256, TILE_BYTES = 32768;        // one operand's k-tile: 256 rows x 64 k (or 64 k x 256 columns) of bf16
+constexpr int STAGE_BYTES = 16 * 64 * 4;                   // epilogue staging slot (16 rows x 64 columns fp32); each of the four waves owns two
+constexpr int LDS_BYTES = 2 * 2 * TILE_BYTES + 8 * STAGE_BYTES;   // 128 KiB k-tile double buffer (A | B, twice) + 4 x 8 KiB = all 160 KiB of the CU
 
 // One operand's four fragments of a k-step.  A k-strided operand's fragment arrives as two transpose reads: the halves are kept
 // apart until the wait (the wait asm ties the RAW read destinations; assembling the 128-bit value earlier could be scheduled as
@@ -1005,9 +651,6 @@ template <int N> IA_DEV void tie6(Op<true>& a, Op<true>& b, Op<true>& c, Op<true
 // fragment j (0..3: A, 4..7: B) of k-step S of the k-tile at bufoff
 template <int S, bool KS>
 IA_DEV void read_frag(Op<KS>& f, int j, const uint32_t (&base)[4], uint32_t bufoff) {
-#if IA_T256W_NOREADS      // timing experiment only: the MFMAs run on whatever the registers hold
-  return;
-#endif
   if constexpr (!KS) {
     const uint32_t a = base[S] + bufoff;
     if (j == 0) f.v[0] = rd128<0>(a);
@@ -1020,17 +663,37 @@ IA_DEV void read_frag(Op<KS>& f, int j, const uint32_t (&base)[4], uint32_t bufo
   }
 }
 
-#ifndef IA_T256W_PEEL
-#define IA_T256W_PEEL 1
-#endif
+// the 16 MFMAs of one k-step on the fragment sets fa / fb; filler(i) is issued right behind MFMA i and pinned there
+// FRESH (the first k-step of a tile's peeled first trip): the MFMAs take a zero C operand, so nothing has to clear the accumulators
+// (two 16x16x32 MFMAs in place of each 32x32x16 ran 8-14 % slower: the MFMA shape is not what separates this loop from the vendor's)
+template <bool FRESH, typename FA, typename FB, typename Filler>
+IA_DEV void mfma_step(f32x16 (&acc)[4][4], const FA& fa, const FB& fb, Filler&& filler) {
+  bf16x8 va[4], vb[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { va[j] = frag_of(fa, j); vb[j] = frag_of(fb, j); }
+#pragma unroll
+  for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni) {
+      if constexpr (FRESH) {
+        const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vb[ni], va[mi], z, 0, 0, 0);
+      } else acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vb[ni], va[mi], acc[mi][ni], 0, 0, 0);
+      filler(mi * 4 + ni);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
 template <bool AKS, bool BKS, int PEND, bool PEEL_OK = true>
 IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdgpu_buffer_rsrc_t rsA, __amdgpu_buffer_rsrc_t rsB, int xa, int xb,
                       int kt0, int ktaA0, int ktaB0, int n_tiles, int nk_all, int wm, int wn, int wave, int lane, bool prologue_only,
                       bool stores_in_flight) {
-  constexpr bool ROUND = IA_T256W_ROUND == 2 ? !(AKS && BKS) : IA_T256W_ROUND == 1 ? !AKS && !BKS : false;      // the k loop's schedule (below)
+  constexpr bool ROUND = !AKS && !BKS;      // the k loop's schedule (below)
   const int li = lane & 31;
   const int gt = wave * 64 + lane;                  // thread index inside the workgroup (0..255)
-  // ---- DMA: 8 pieces per operand and k-tile, one lane offset per operand (see t256::main_loop)
+  // ---- DMA: 8 pieces per operand and k-tile.  One per-lane byte offset serves all 8 pieces of an operand: the swizzled chunk a lane
+  // fetches does not depend on the piece (the row advance per piece is a multiple of the swizzle period), so the piece and k-tile
+  // advances are both scalars folded into the instruction's soffset.
   uint32_t voffA, stepA, voffB, stepB;
   if (!AKS) { const int row = gt >> 3; voffA = (uint32_t)(((xa + row) * p.lda + (((gt & 7) ^ ((row >> 1) & 7)) * 8)) * 2); stepA = (uint32_t)(32 * p.lda * 2); }
   else { const int row = gt >> 5; voffA = (uint32_t)((row * p.lda + xa + (((gt & 31) ^ ((row & 3) << 2)) * 8)) * 2); stepA = (uint32_t)(8 * p.lda * 2); }
@@ -1054,13 +717,13 @@ IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdg
     const int kt = kt0 + u, kta = (dbg & 4) ? 0 : (isB ? ktaB0 : ktaA0) + u;      // dbg 4: every k-tile re-fetches k-tile 0 (cache-resident)
     const bool ks = isB ? BKS : AKS;
     const uint32_t soff = (uint32_t)kta * (isB ? kstepB : kstepA) + (uint32_t)j * (isB ? stepB : stepA);
-    if (ks && IA_T256W_KS_LANEOFF) {
+    if (ks) {
       // k-strided operand: k is the ROW of the tensor, so a piece past K (the tail of the last k-tile, the look-ahead k-tiles behind it)
       // lies behind the end of the buffer window -- provided its whole address sits in the LANE offset (the hardware's range check does
       // not see the scalar offset): one v_add per piece instead of add + compare + select.  (A split-K slab's look-ahead reads the next
       // slab's first rows instead of zeros: nobody consumes that buffer.)  Data gradient +4 %, weight gradient +0.7 %; the memory-side
-      // fetches of both went UP 4-8 % with it (FETCH_SIZE 0.996 -> 1.076 GB per weight-gradient launch, same box, IA_T256W_KS_LANEOFF=0
-      // against 1): far more than the two look-ahead k-tiles -- the workgroups that share a panel out of one L2 drift further apart.
+      // fetches of both went UP 4-8 % with it (FETCH_SIZE 0.996 -> 1.076 GB per weight-gradient launch, same box, against compare +
+      // select per piece): far more than the two look-ahead k-tiles -- the workgroups that share a panel out of one L2 drift further apart.
       const uint32_t off = dma_on ? (isB ? voffB : voffA) + soff : OOB;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(isB ? rsB : rsA, IA_LDS(dst), 16, off, 0, 0, 0);
     } else {
@@ -1089,27 +752,18 @@ IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdg
   uint32_t runA = voffA + (uint32_t)((dbg & 4) ? 0 : ktaA0 + 2) * kstepA, runB = voffB + (uint32_t)((dbg & 4) ? 0 : ktaB0 + 2) * kstepB;
   auto dma_run = [&](int u, int i) {
     const bool isB = i >= 8;
-    if (!(isB ? BKS : AKS) || !IA_T256W_KS_LANEOFF || (dbg & 4)) { dma_piece(u, i); return; }
+    if (!(isB ? BKS : AKS) || (dbg & 4)) { dma_piece(u, i); return; }
     const int j = i & 7;
     char* dst = my_part + (isB ? TILE_BYTES : 0) + (u & 1) * 2 * TILE_BYTES + j * 4096;
     const uint32_t off = (isB ? runB : runA) + (uint32_t)j * (isB ? stepB : stepA);
     __builtin_amdgcn_raw_ptr_buffer_load_lds(isB ? rsB : rsA, IA_LDS(dst), 16, dma_on ? off : OOB, 0, 0, 0);
   };
 
-  // pieces 10 .. 15 (B pieces 2 .. 7) of the k-tile BEFORE the running one (the spread form of the second schedule issues them a trip late)
-  auto dma_prev = [&](int u, int i) {
-    if (!BKS || !IA_T256W_KS_LANEOFF || (dbg & 4)) { dma_piece(u, i); return; }
-    const int j = i & 7;
-    char* dst = my_part + TILE_BYTES + (u & 1) * 2 * TILE_BYTES + j * 4096;
-    const uint32_t off = runB - kstepB + (uint32_t)j * stepB;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, IA_LDS(dst), 16, dma_on ? off : OOB, 0, 0, 0);
-  };
-
   if (prologue_only) {       // called ahead of time (before the previous tile's epilogue): just start the first two k-tiles
 #pragma unroll
     for (int i = 0; i < 16; ++i) dma_piece(0, i);
 #pragma unroll
-    for (int i = 0; i < (ROUND ? 12 : IA_T256W_SPREAD3 ? 10 : 16); ++i) dma_piece(1, i);      // (zero-filled when it does not exist; the rest: see the loops)
+    for (int i = 0; i < (ROUND ? 12 : 16); ++i) dma_piece(1, i);      // (zero-filled when it does not exist; the rest: see the loops)
     return;
   }
   // the prologue DMA of this tile.  After a full-tile epilogue exactly PEND store instructions were issued behind it and
@@ -1134,35 +788,6 @@ IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdg
 #pragma unroll
   for (int j = 0; j < 4; ++j) read_frag<0>(b0, j, baseB, 0u);
 
-  // the 16 MFMAs of one k-step; filler(i) is issued right behind MFMA i and pinned there
-  // FRESH (the first k-step of a tile under IA_T256W_PEEL): the MFMAs take a zero C operand, so nothing has to clear the accumulators
-  auto step = [&](const auto& fa, const auto& fb, auto&& filler, auto FRESH_T) {
-    constexpr bool FRESH = decltype(FRESH_T)::value;
-    bf16x8 va[4], vb[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { va[j] = frag_of(fa, j); vb[j] = frag_of(fb, j); }
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) {
-#if IA_T256W_MFMA16      // timing experiment only (results are garbage): two 16x16x32 MFMAs in place of one 32x32x16, same operand registers
-        {
-          f32x16& c = acc[mi][ni];
-          f32x4 c0 = {c[0], c[1], c[2], c[3]}, c1 = {c[4], c[5], c[6], c[7]};
-          c0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vb[ni], va[mi], c0, 0, 0, 0);
-          c1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vb[ni], va[mi], c1, 0, 0, 0);
-          c[0] = c0[0]; c[1] = c0[1]; c[2] = c0[2]; c[3] = c0[3]; c[4] = c1[0]; c[5] = c1[1]; c[6] = c1[2]; c[7] = c1[3];
-        }
-#else
-        if constexpr (FRESH) {
-          const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vb[ni], va[mi], z, 0, 0, 0);
-        } else acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vb[ni], va[mi], acc[mi][ni], 0, 0, 0);
-#endif
-        filler(mi * 4 + ni);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-  };
   using Acc = std::false_type;
 
   uint32_t bo = 0;
@@ -1176,44 +801,44 @@ IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdg
   // on the round-2 order below).
   if constexpr (ROUND) {
   uint32_t offA = OOB, offB = off_of(1, true);
-  // one trip = one k-tile.  IA_T256W_PEEL: the first trip of a tile is its own copy of the body whose k-step 0 writes the accumulators
+  // one trip = one k-tile.  PEEL_OK: the first trip of a tile is its own copy of the body whose k-step 0 writes the accumulators
   // with a zero C operand -- the 256 v_accvgpr_write per tile and wave that cleared them (in the epilogue: an issue-bound stretch) are
   // gone; the loop behind it runs at least once more (a k-tile past the end reads zeros: K <= 64 pays one empty trip).
   auto trip = [&](auto FIRST_T) {
     const uint32_t bn = bo ^ (uint32_t)(2 * TILE_BYTES);
     tie2<0>(a0, b0);
-    step(a0, b0, [&](int i) {      // (no reads behind the last four MFMAs: they cover the latency of the last reads)
+    mfma_step<decltype(FIRST_T)::value>(acc, a0, b0, [&](int i) {      // (no reads behind the last four MFMAs: they cover the latency of the last reads)
       if (i < 4) { read_frag<1>(a1, i, baseA, bo); read_frag<1>(b1, i, baseB, bo); }
       else if (i < 8) { read_frag<2>(a2, i - 4, baseA, bo); read_frag<2>(b2, i - 4, baseB, bo); }
       else if (i < 12) { read_frag<3>(a3, i - 8, baseA, bo); read_frag<3>(b3, i - 8, baseB, bo); }
       if (i % 4 == 3) dma_c(u + 1, 12 + i / 4, offB);      // the last four pieces of k-tile u+1 (into the other buffer)
       if (i == 12) offA = off_of(u + 2, false);
-    }, FIRST_T);
+    });
     tie6<0>(a1, b1, a2, b2, a3, b3);
     __builtin_amdgcn_sched_barrier(0);
     if (!(dbg & 16)) __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-    step(a1, b1, [&](int i) {
+    mfma_step<false>(acc, a1, b1, [&](int i) {
       if (i % 4 == 1) dma_c(u + 2, i / 4, offA);
-    }, Acc{});
-    step(a2, b2, [&](int i) {
+    });
+    mfma_step<false>(acc, a2, b2, [&](int i) {
       if (i % 4 == 1) dma_c(u + 2, 4 + i / 4, offA);
       if (i == 14) offB = off_of(u + 2, true);
-    }, Acc{});
+    });
     // k-tile u+1 has landed (its last four pieces went out under k-step 0): only the 8 pieces just issued may be outstanding
     asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     if (!(dbg & 16)) __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-    step(a3, b3, [&](int i) {      // set 0 of k-tile u+1 in the first half: the second half covers the reads' latency
+    mfma_step<false>(acc, a3, b3, [&](int i) {      // set 0 of k-tile u+1 in the first half: the second half covers the reads' latency
       if (i < 4) read_frag<0>(a0, i, baseA, bn);
       else if (i < 8) read_frag<0>(b0, i - 4, baseB, bn);
       if (i % 4 == 3) dma_c(u + 2, 8 + i / 4, offB);
-    }, Acc{});
+    });
     bo = bn;
     ++u;
     };
-  if constexpr (IA_T256W_PEEL && PEEL_OK) {
+  if constexpr (PEEL_OK) {
     trip(std::true_type{});
     do { trip(Acc{}); } while (u < n_tiles);
   } else {
@@ -1227,45 +852,40 @@ IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdg
     const uint32_t bn = bo ^ (uint32_t)(2 * TILE_BYTES);
     // k-step 0: sets 1 and 2 requested, one fragment behind each MFMA
     tie<0>(a0); tie<0>(b0);
-    step(a0, b0, [&](int i) {
+    mfma_step<false>(acc, a0, b0, [&](int i) {
       if (i < 4) read_frag<1>(a1, i, baseA, bo);
       else if (i < 8) read_frag<1>(b1, i - 4, baseB, bo);
       else if (i < 12) read_frag<2>(a2, i - 8, baseA, bo);
       else read_frag<2>(b2, i - 12, baseB, bo);
-      // spread form: the DMA pieces of a k-tile one per THREE MFMAs over k-steps 2, 3 and the next trip's k-step 0 (5 + 5 + 6; the
-      // tile prologue issues 16 + 10): at one per two the VMEM port queues up (see the ROUND schedule)
-      if (IA_T256W_SPREAD3 && i % 3 == 0) dma_prev(u + 1, 10 + i / 3);
-    }, Acc{});
+    });
     // k-step 1: set 3 requested in the first half
     tie<NR15>(a1); tie<NR15>(b1);
-    step(a1, b1, [&](int i) {
+    mfma_step<false>(acc, a1, b1, [&](int i) {
       if (i < 4) read_frag<3>(a3, i, baseA, bo);
       else if (i < 8) read_frag<3>(b3, i - 4, baseB, bo);
-    }, Acc{});
+    });
     // every fragment of k-tile u is in registers: once all waves are here its buffer is free for k-tile u+2
     tie<0>(a2); tie<0>(b2); tie<0>(a3); tie<0>(b3);
     __builtin_amdgcn_sched_barrier(0);
     if (!(dbg & 16)) __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-    // k-step 2: the A half of k-tile u+2, one piece per two MFMAs
-    step(a2, b2, [&](int i) {
-      if (IA_T256W_SPREAD3) { if (i % 3 == 1) dma_run(u + 2, i / 3); }
-      else if (i & 1) dma_run(u + 2, i >> 1);
-    }, Acc{});
-    // k-step 3: k-tile u+1 has landed (this wave's share: all but the 8 / 5 pieces just issued; everybody's: the barrier)
-    if (IA_T256W_SPREAD3) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+    // k-step 2: the A half of k-tile u+2, one piece per two MFMAs (one per three, spread over k-steps 2, 3 and the next trip's
+    // k-step 0, measured data gradient +-0, weight gradient -0.9 %: what helps the forward forms does not help these)
+    mfma_step<false>(acc, a2, b2, [&](int i) {
+      if (i & 1) dma_run(u + 2, i >> 1);
+    });
+    // k-step 3: k-tile u+1 has landed (this wave's share: all but the 8 pieces just issued; everybody's: the barrier)
+    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     if (!(dbg & 16)) __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-    step(a3, b3, [&](int i) {
-      if (IA_T256W_SPREAD3) { if (i % 3 == 2) dma_run(u + 2, 5 + i / 3); }
-      else if (i & 1) dma_run(u + 2, 8 + (i >> 1));
+    mfma_step<false>(acc, a3, b3, [&](int i) {
+      if (i & 1) dma_run(u + 2, 8 + (i >> 1));
       if (!(i & 1)) {
         if (i < 8) read_frag<0>(a0, i >> 1, baseA, bn);
         else read_frag<0>(b0, (i - 8) >> 1, baseB, bn);
       }
-    }, Acc{});
+    });
     bo = bn;
     ++u;
     // one running lane offset per k-strided operand, opaque to the loop optimiser: left alone it keeps SIXTEEN induction variables
@@ -1355,7 +975,18 @@ IA_DEV void drain_half_plain(const GemmArgs& p, f32x16 (&acc)[4][4], int m0, int
   }
 }
 
-// the T256 epilogue arithmetic (see t256::gemm_kernel) for one 128 x 64 half (NH = 0 / 1) of the wave's 128 x 128 part
+// The fused epilogues (bias / residual / GELU / x GELU' / fp32 output) for one 128 x 64 half (NH = 0 / 1) of the wave's 128 x 128 part,
+// through the wave's private LDS slots outside the k-tile buffers (no workgroup barrier).  The MFMA C^T fragments give each lane
+// 4-element runs scattered over 32 rows, which as direct global stores cost ~11 us per tile (64 separate segments per store
+// instruction).  Instead the wave stages 32 rows x 64 columns of fp32 (16-byte chunks XOR-swizzled by row: conflict-free both ways),
+// then streams them out: bias / residual / GELU inputs are read and all outputs written as full 128-byte row segments, 8 rows per
+// instruction.  C^T fragment: lane (m = li, half hh) register r <-> fragment row i = (r&3) + 8*(r>>2) + 4*hh; k-contiguous B:
+// n = hh*16 + r; k-strided B: n = i.
+// Slice c (c = 0..15) = rows (c>>2)*32 + ((c>>1)&1)*16 + (c&1)*8 + rrow of the half, the lane's 8 columns n0 + c8*8.  PRE (`full`: the
+// half lies entirely inside C, so no row / column guards and the store count of the tile is exact): the bias -- the same 8 columns
+// for all slices -- is read once per tile, and the aux operand runs AHEAD slices ahead of the stores: VMEM retires in order, so a load
+// issued behind a store can only be waited for by draining that store; issued ahead, hipcc's own counters leave the younger stores in
+// flight (vmcnt(2 * AHEAD) in the steady state).
 template <int EPI, bool OUTF32, bool BKS, int NH>
 IA_DEV void drain_half(const GemmArgs& p, f32x16 (&acc)[4][4], int m0, int n0, char* stg, int lane_e, bool full, bool bias_ready, f32x4 bias_lo,
                        f32x4 bias_hi) {
@@ -1366,9 +997,9 @@ IA_DEV void drain_half(const GemmArgs& p, f32x16 (&acc)[4][4], int m0, int n0, c
   constexpr int AHEAD = 4;
   auto drain = [&](auto PREFETCHED) {
     constexpr bool PRE = decltype(PREFETCHED)::value;
-    f32x4 pb0, pb1;
+    f32x4 pb0, pb1;          // only read when the epilogue has a bias (left undefined otherwise: no registers, no spill)
     float cs[8];
-    if (EPI == EPI_DGELU_CS) {
+    if (EPI == EPI_DGELU_CS) {      // zeroed here, opaquely: a hoisted zero vector would live (and spill) across the whole main loop
 #pragma unroll
       for (int j = 0; j < 8; ++j) asm volatile("v_mov_b32 %0, 0" : "=v"(cs[j]));
     }
@@ -1441,7 +1072,7 @@ IA_DEV void drain_half(const GemmArgs& p, f32x16 (&acc)[4][4], int m0, int n0, c
         if (PRE) {
           if (HAS_AUX && c + AHEAD < 16) {
             ax[(c + AHEAD) % (AHEAD + 1)] = aux_of(c + AHEAD);
-            asm volatile("" ::: "memory");
+            asm volatile("" ::: "memory");      // the load stays in front of this slice's store (hipcc would sink it behind)
           }
           io.off = voffC + (uint32_t)((mi * 32 + it * 8) * p.ldc * 2);
           if (!(IA_DBG(p) & 64)) epi_store8<EPI, OUTF32, true, BUF>(p, m, n, lo[it], hi[it], pb0, pb1, ax[c % (AHEAD + 1)], cs, &io);
@@ -1452,14 +1083,15 @@ IA_DEV void drain_half(const GemmArgs& p, f32x16 (&acc)[4][4], int m0, int n0, c
       }
     }
     if (EPI == EPI_DGELU_CS) {
+      // column sums of this half's 128 rows: the 8 lanes that share a column group (lane & 7) differ in lane bits 3..5
 #pragma unroll
       for (int r = 0; r < 8; ++r) {
         float v = cs[r];
-        v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, v), __builtin_bit_cast(int, v), 0x128, 0xF, 0xF, false));
-        v = ia_add_xor32(ia_add_xor16(v));
+        v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, v), __builtin_bit_cast(int, v), 0x128, 0xF, 0xF, false));   // row_ror:8 -> lane ^ 8
+        v = ia_add_xor32(ia_add_xor16(v));                                                      // lane ^ 16, lane ^ 32 (common.h)
         cs[r] = v;
       }
-      if (rrow == 0 && n0 + c8 * 8 < p.N) {
+      if (rrow == 0 && n0 + c8 * 8 < p.N) {      // lanes 0..7: 8 consecutive columns each (two 16-byte stores, counted in PEND)
         float* dst = p.csum_part + (size_t)(m0 >> 7) * p.N + n0 + c8 * 8;
         gstore16(dst, f32x4{cs[0], cs[1], cs[2], cs[3]});
         gstore16(dst + 4, f32x4{cs[4], cs[5], cs[6], cs[7]});
@@ -1477,10 +1109,13 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
   const int wm = wave >> 1, wn = wave & 1;          // 2 x 2 waves, 128 x 128 each, one per SIMD
   const int nk_all = (p.K + BK - 1) / BK;
   const int total_tiles = p.tiles_m * p.tiles_n;
-  int first_tile = blockIdx.x;
-  bool ordered = false;
+  // Split-K launches are a 1-D grid of tiles x splits workgroups whose XCD-aware order has the split OUTERMOST: one XCD's run of
+  // 32 work items is then an 8 x 4 block of tiles of ONE k-slab, i.e. 12 operand panel streams per XCD instead of 36 when the
+  // splits of a tile shared an XCD (HBM bytes of the fc1 weight gradient: 2.2 GB -> 0.9 GB per launch, algorithmic 0.67 GB).
+  int first_tile = blockIdx.x;          // index into the tile work order
+  bool ordered = false;                 // first_tile already is a position of that order (no XCD renumbering in coords())
   p.split_id = 0;
-  if (p.splits > 1) {                  // 1-D grid of tiles x splits, XCD-aware with the split outermost (see t256::gemm_kernel)
+  if (p.splits > 1) {
     const int w = xcd_chunk(blockIdx.x, gridDim.x);
     p.split_id = w / total_tiles;
     first_tile = w % total_tiles;
@@ -1637,7 +1272,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
           for (int q = 0; q < 4; ++q) bct[ni][q] *= ts;
       }
     } else if (bias_pre) asm volatile("s_waitcnt vmcnt(0)" : "+v"(pbv[0]), "+v"(pbv[1]), "+v"(pbv[2]), "+v"(pbv[3]));
-    int next = ordered ? total_tiles : tile + gridDim.x;
+    int next = ordered ? total_tiles : tile + gridDim.x;      // a split-K workgroup owns exactly one (tile, k-slab)
     if (dyn) {
       next = claim_resolve();
       // the claim for the tile AFTER next goes out here, in front of next's prologue DMA and this tile's epilogue: VMEM retires in
@@ -1656,7 +1291,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
     // the loop, where it would stay live across it and spill)
     int m0 = m0_pre, n0 = n0_pre;
     asm volatile("" : "+s"(m0), "+s"(n0));
-    char* stg = smem + 2 * 2 * TILE_BYTES + wave * 2 * STAGE_BYTES;      // 8 KiB per wave (t256's eight 4-KiB slots, two per wave)
+    char* stg = smem + 2 * 2 * TILE_BYTES + wave * 2 * STAGE_BYTES;      // 8 KiB per wave: two staging slots
     if (!(IA_DBG(p) & 32)) {
       if constexpr (EPI == EPI_NONE && !OUTF32) {
         drain_half_plain<BKS, 0, false>(p, acc, m0, n0, stg, lane_e, bct);
@@ -1670,6 +1305,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
       }
     }
     if (next >= total_tiles) break;
+    // a wave whose 128 x 128 part of the tile was clipped by M or N issued fewer stores than PEND: drain instead of counting
     stores_in_flight = !(IA_DBG(p) & 96) && full;
     if (!stores_in_flight) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     tile = next;
@@ -1689,9 +1325,6 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
 // k-tile 1 is in flight: the drain runs, and the next tile's first trip starts where a steady-state trip would -- no prologue burst, no
 // prologue wait, no barrier, no exposed read.  The loop-carried pipeline state is the fragment set a0 / b0 (32 VGPRs, live across the
 // drain: the plain kernel has ~100 to spare there) and the LDS buffer parity.  One tile boundary = drain only.
-#ifndef IA_T256LA
-#define IA_T256LA 1
-#endif
 namespace t256la {
 using namespace t256w;
 
@@ -1775,23 +1408,6 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-  auto step = [&](const Op<false>& fa, const Op<false>& fb, auto&& filler, auto FRESH_T) {
-    constexpr bool FRESH = decltype(FRESH_T)::value;
-    bf16x8 va[4], vb[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { va[j] = frag_of(fa, j); vb[j] = frag_of(fb, j); }
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) {
-        if constexpr (FRESH) {
-          const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vb[ni], va[mi], z, 0, 0, 0);
-        } else acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vb[ni], va[mi], acc[mi][ni], 0, 0, 0);
-        filler(mi * 4 + ni);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-  };
   using Acc = std::false_type;
 
   const f32x4 no_bias[4][4] = {};
@@ -1810,34 +1426,34 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
       constexpr bool FIRST = decltype(FIRST_T)::value;
       const uint32_t bn_ = bo ^ (uint32_t)(2 * TILE_BYTES);
       tie2<0>(a0, b0);
-      step(a0, b0, [&](int i) {
+      mfma_step<FIRST>(acc, a0, b0, [&](int i) {
         if (i < 4) { read_frag<1>(a1, i, baseA, bo); read_frag<1>(b1, i, baseB, bo); }
         else if (i < 8) { read_frag<2>(a2, i - 4, baseA, bo); read_frag<2>(b2, i - 4, baseB, bo); }
         else if (i < 12) { read_frag<3>(a3, i - 8, baseA, bo); read_frag<3>(b3, i - 8, baseB, bo); }
         if (!FIRST && i % 4 == 3) dma(u + 1, 12 + i / 4, okB, bn_);       // the last four pieces of k-tile u+1 (into the other buffer)
         if (i == 12) okA = off_of(u + 2);
-      }, FIRST_T);
+      });
       tie6<0>(a1, b1, a2, b2, a3, b3);
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
-      step(a1, b1, [&](int i) {
+      mfma_step<false>(acc, a1, b1, [&](int i) {
         if (i % 4 == 1) dma(u + 2, i / 4, okA, bo);
-      }, Acc{});
-      step(a2, b2, [&](int i) {
+      });
+      mfma_step<false>(acc, a2, b2, [&](int i) {
         if (i % 4 == 1) dma(u + 2, 4 + i / 4, okA, bo);
         if (i == 14) okB = off_of(u + 2);
-      }, Acc{});
+      });
       if constexpr (FIRST) asm volatile("s_waitcnt vmcnt(40)" ::: "memory");      // 8 pieces + the previous tile's 32 stores
       else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
-      step(a3, b3, [&](int i) {
+      mfma_step<false>(acc, a3, b3, [&](int i) {
         if (i < 4) read_frag<0>(a0, i, baseA, bn_);
         else if (i < 8) read_frag<0>(b0, i - 4, baseB, bn_);
         if (i % 4 == 3) dma(u + 2, 8 + i / 4, okB, bo);
-      }, Acc{});
+      });
       bo = bn_;
       ++u;
     };
@@ -2009,60 +1625,27 @@ int launch(GemmArgs a, bool big, hipStream_t st) {
   constexpr int vid = AKS * 1000 + BKS * 100 + EPI * 10 + (OUTF32 ? 1 : 0);
   const bool rec = g_prof.on && g_prof.variant == vid && g_prof.n < g_prof.cap;
   if (rec) (void)hipEventRecord(g_prof.ev[2 * g_prof.n], st);
-  // Two 256 x 256 kernels: t256w (one wave per SIMD, 128 x 128 wave tiles) has the faster k loop, t256 (two waves per SIMD) had the
-  // faster epilogue when that is VALU-heavy (GELU forward, x GELU' data gradient) -- until round 4's k loop: since then t256w wins
-  // those too (bias + GELU 412 -> 405 us, x GELU' + column sums 317 -> 313 us at 32640 x 4096 x 1024, step +0.65 % same box).
-  // IA_GEMM_WIDE=0 runs everything on t256, 3 the round-3 split (heavy epilogues on t256) for A/B runs.
-  static int wide = -1;
-  if (wide < 0) { const char* e = getenv("IA_GEMM_WIDE"); wide = e ? atoi(e) : 1; }
-  constexpr bool heavy_epi = EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_GELU_ACT || EPI == EPI_DGELU || EPI == EPI_DGELU_CS;
-  if (big && (wide == 1 || wide == 2 || (wide == 3 && !heavy_epi))) {
-    a.tiles_m = (a.M + t256::BM - 1) / t256::BM; a.tiles_n = (a.N + t256::BN - 1) / t256::BN;
-    static bool attr_set_w = false;
-    auto kern = t256w::gemm_kernel<AKS, BKS, EPI, OUTF32>;
-    if (!attr_set_w) {
-      if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, t256::LDS_BYTES) != hipSuccess) return IA_ERR_LAUNCH;
-      attr_set_w = true;
-    }
-    const int ntile = a.tiles_m * a.tiles_n;
-    const int gx = a.splits > 1 ? ntile * a.splits : (ntile < 256 ? ntile : 256);
-    // persistent launches with more than one tile per workgroup claim their tiles dynamically (IA_GEMM_DYNAMIC=0: the static order)
-    a.tile_ctr = (a.splits == 1 && ntile > gx) ? next_ctr_slot() : nullptr;
-    // plain NT form, several tiles per workgroup, static order: the look-ahead kernel (t256la; IA_GEMM_LA=0 keeps t256w)
-    int la = IA_T256LA;
-    { const char* e = getenv("IA_GEMM_LA"); if (e) la = atoi(e); }       // (read per launch: tests and A/B runs switch it in one process)
-    if constexpr (!AKS && !BKS && EPI == EPI_NONE && !OUTF32) {
-      if (la && a.splits == 1 && ntile > gx && !a.tile_ctr && a.K >= 2 * BK && !(IA_DBG(a))) {
-        static bool attr_set_la = false;
-        if (!attr_set_la) {
-          if (hipFuncSetAttribute((const void*)t256la::gemm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, t256::LDS_BYTES) != hipSuccess)
-            return IA_ERR_LAUNCH;
-          attr_set_la = true;
-        }
-        hipLaunchKernelGGL(t256la::gemm_kernel, dim3(gx), dim3(256), t256::LDS_BYTES, st, a);
-        if (rec) {
-          (void)hipEventRecord(g_prof.ev[2 * g_prof.n + 1], st);
-          g_prof.flops += 2.0 * a.M * a.N * a.K;
-          g_prof.bytes += 2.0 * ((double)a.M * a.K + (double)a.N * a.K) + 2.0 * a.M * a.N;
-          ++g_prof.n;
-        }
-        return ia_check_launch();
-      }
-    }
-    hipLaunchKernelGGL(kern, dim3(gx), dim3(256), t256::LDS_BYTES, st, a);
-  } else if (big) {
-    a.tiles_m = (a.M + t256::BM - 1) / t256::BM; a.tiles_n = (a.N + t256::BN - 1) / t256::BN;
-    static bool attr_set = false;
-    auto kern = t256::gemm_kernel<AKS, BKS, EPI, OUTF32>;
-    if (!attr_set) {
-      if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, t256::LDS_BYTES) != hipSuccess) return IA_ERR_LAUNCH;
-      attr_set = true;
-    }
+  if (big) {
+    a.tiles_m = (a.M + t256w::BM - 1) / t256w::BM; a.tiles_n = (a.N + t256w::BN - 1) / t256w::BN;
     const int ntile = a.tiles_m * a.tiles_n;
     // split-K: one workgroup per (tile, k-slab), 1-D so the kernel can order them XCD-aware with the slab outermost;
     // otherwise persistent over tiles, one workgroup per CU
     const int gx = a.splits > 1 ? ntile * a.splits : (ntile < 256 ? ntile : 256);
-    hipLaunchKernelGGL(kern, dim3(gx), dim3(512), t256::LDS_BYTES, st, a);
+    // persistent launches with more than one tile per workgroup claim their tiles dynamically (IA_GEMM_DYNAMIC=0: the static order)
+    a.tile_ctr = (a.splits == 1 && ntile > gx) ? next_ctr_slot() : nullptr;
+    void (*kern)(GemmArgs) = t256w::gemm_kernel<AKS, BKS, EPI, OUTF32>;
+    static bool attr_set[2] = {false, false};      // per kernel: [0] this instantiation of t256w, [1] t256la
+    int la = 0;
+    // plain NT form, several tiles per workgroup, static order: the look-ahead kernel (t256la; IA_GEMM_LA=0 keeps t256w)
+    if constexpr (!AKS && !BKS && EPI == EPI_NONE && !OUTF32) {
+      const char* e = getenv("IA_GEMM_LA");       // (read per launch: tests and A/B runs switch it in one process)
+      if ((e ? atoi(e) : 1) && a.splits == 1 && ntile > gx && !a.tile_ctr && a.K >= 2 * BK && !(IA_DBG(a))) { kern = t256la::gemm_kernel; la = 1; }
+    }
+    if (!attr_set[la]) {
+      if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, t256w::LDS_BYTES) != hipSuccess) return IA_ERR_LAUNCH;
+      attr_set[la] = true;
+    }
+    hipLaunchKernelGGL(kern, dim3(gx), dim3(256), t256w::LDS_BYTES, st, a);
   } else {
     a.tiles_m = (a.M + t128::BM - 1) / t128::BM; a.tiles_n = (a.N + t128::BN - 1) / t128::BN;
     hipLaunchKernelGGL((t128::gemm_kernel<AKS, BKS, EPI, OUTF32>), dim3(a.tiles_m * a.tiles_n * a.splits * a.groups), dim3(256), 0, st, a);
@@ -2140,6 +1723,20 @@ size_t ia_gemm_view_workspace_bytes(int M, int N, int K, int groups) {
   return pl.splits > 1 ? (size_t)groups * pl.splits * M * (N + 1) * sizeof(float) : 0;      // + the row-sum partials (bias gradient)
 }
 
+// EPI_DGELU_CS (k-contiguous A, bf16 output): csum (fp32 [N]) += column sums of the output -- the bias gradient of the Linear in front
+// of the GELU
+template <bool BKS>
+static int launch_dgelu_colsum(GemmArgs& g, bool big, float* csum, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  if (!csum || !workspace || workspace_bytes < ia_gemm_colsum_workspace_bytes(g.M, g.N) || g.ldc != g.N) return IA_ERR_WORKSPACE;
+  if (!big) {                                  // small shapes: plain epilogue, then the stand-alone column-sum kernel
+    int rc = launch<false, BKS, EPI_DGELU, false>(g, false, stream);
+    return rc ? rc : ia_colsum(g.C, g.ldc, g.M, g.N, csum, 1, workspace, workspace_bytes, stream);
+  }
+  g.csum_part = (float*)workspace;
+  int rc = launch<false, BKS, EPI_DGELU_CS, false>(g, true, stream);
+  return rc ? rc : ia_sum_rows_f32((const float*)workspace, ((g.M + 255) / 256) * 2, g.N, csum, 1, stream);
+}
+
 static int gemm_core(const void* A, int a_kstrided, int lda, const void* B, int b_kstrided, int ldb, void* C, int c_is_f32, int ldc, int M,
                      int N, int K, int epilogue, const float* bias, const void* aux, int ldaux, void* C2, int accumulate, void* workspace,
                      size_t workspace_bytes, const IaViewGemm* view, hipStream_t stream, int qcols, float qscale) {
@@ -2207,33 +1804,14 @@ static int gemm_core(const void* A, int a_kstrided, int lda, const void* B, int 
       case EPI_ADD: return launch<false, false, EPI_ADD, false>(g, big, stream);
       // (the data-gradient epilogues on a k-contiguous B: the transposed weight shadows of ia_layer_weights::wt_*)
       case EPI_DGELU: return launch<false, false, EPI_DGELU, false>(g, big, stream);
-      case EPI_DGELU_CS: {
-        if (!C2 || !workspace || workspace_bytes < ia_gemm_colsum_workspace_bytes(M, N) || ldc != N) return IA_ERR_WORKSPACE;
-        if (!big) {
-          int rc = launch<false, false, EPI_DGELU, false>(g, false, stream);
-          return rc ? rc : ia_colsum(C, ldc, M, N, (float*)C2, 1, workspace, workspace_bytes, stream);
-        }
-        g.csum_part = (float*)workspace;
-        int rc = launch<false, false, EPI_DGELU_CS, false>(g, true, stream);
-        return rc ? rc : ia_sum_rows_f32((const float*)workspace, ((M + 255) / 256) * 2, N, (float*)C2, 1, stream);
-      }
+      case EPI_DGELU_CS: return launch_dgelu_colsum<false>(g, big, (float*)C2, workspace, workspace_bytes, stream);
     }
   } else if (!a_kstrided && b_kstrided && !c_is_f32) {
     switch (epilogue) {
       case EPI_NONE: return launch<false, true, EPI_NONE, false>(g, big, stream);
       case EPI_ADD: return launch<false, true, EPI_ADD, false>(g, big, stream);
       case EPI_DGELU: return launch<false, true, EPI_DGELU, false>(g, big, stream);
-      case EPI_DGELU_CS: {
-        // C2 (fp32 [N]) += column sums of the output: the bias gradient of the Linear in front of the GELU
-        if (!C2 || !workspace || workspace_bytes < ia_gemm_colsum_workspace_bytes(M, N) || ldc != N) return IA_ERR_WORKSPACE;
-        if (!big) {                                  // small shapes: plain epilogue, then the stand-alone column-sum kernel
-          int rc = launch<false, true, EPI_DGELU, false>(g, false, stream);
-          return rc ? rc : ia_colsum(C, ldc, M, N, (float*)C2, 1, workspace, workspace_bytes, stream);
-        }
-        g.csum_part = (float*)workspace;
-        int rc = launch<false, true, EPI_DGELU_CS, false>(g, true, stream);
-        return rc ? rc : ia_sum_rows_f32((const float*)workspace, ((M + 255) / 256) * 2, N, (float*)C2, 1, stream);
-      }
+      case EPI_DGELU_CS: return launch_dgelu_colsum<true>(g, big, (float*)C2, workspace, workspace_bytes, stream);
     }
   } else if (a_kstrided && b_kstrided && c_is_f32) {
     if (epilogue == EPI_NONE) {
@@ -2305,10 +1883,10 @@ extern "C" int ia_debug_cu_hog(int workgroups, float milliseconds, hipStream_t s
   if (workgroups <= 0 || workgroups > 256 || !(milliseconds > 0.f) || milliseconds > 1000.f) return IA_ERR_ARG;
   static bool attr_set = false;
   if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)cu_hog_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, t256::LDS_BYTES) != hipSuccess) return IA_ERR_LAUNCH;
+    if (hipFuncSetAttribute((const void*)cu_hog_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, t256w::LDS_BYTES) != hipSuccess) return IA_ERR_LAUNCH;
     attr_set = true;
   }
-  hipLaunchKernelGGL(cu_hog_kernel, dim3(workgroups), dim3(256), t256::LDS_BYTES, stream, (unsigned long long)(milliseconds * 1e5f));
+  hipLaunchKernelGGL(cu_hog_kernel, dim3(workgroups), dim3(256), t256w::LDS_BYTES, stream, (unsigned long long)(milliseconds * 1e5f));
   return ia_check_launch();
 }
 

@@ -1,5 +1,5 @@
-"""Edge shapes of the 256x256 GEMM kernels (one / two k-tiles, ragged K, ragged M / N, split-K weight gradients) against torch, for
-IA_GEMM_WIDE = 0 / 1 / unset.  usage: python tools/abl/gemm_edge.py"""
+"""Edge shapes of the 256x256 GEMM kernels (one / two k-tiles, ragged K, ragged M / N, split-K weight gradients) against torch.
+usage: python tools/abl/gemm_edge.py"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
@@ -21,6 +21,6 @@ for (M, N, K) in [(1024, 1024, 64), (1024, 1024, 128), (1024, 768, 8), (1000, 52
     errs.append(((ops.gemm(a, wt, b_kstrided=True).float() - ref).abs().max() / sc).item())
     errs.append(((ops.gemm(at, wt, a_kstrided=True, b_kstrided=True, out_f32=True) - ref).abs().max() / sc).item())
     worst = max(worst, max(errs))
-    print(f"WIDE={os.environ.get('IA_GEMM_WIDE', 'policy')} M={M} N={N} K={K}: " + " ".join(f"{e:.1e}" for e in errs), flush=True)
+    print(f"M={M} N={N} K={K}: " + " ".join(f"{e:.1e}" for e in errs), flush=True)
 print("worst", worst)
 assert worst < 1.2e-2

@@ -1,5 +1,5 @@
 """Ablation: does the row stride (leading dimension) of A / B / C change the 256x256 GEMM rate?  (power-of-two strides vs padded)
-usage: python tools/abl/gemm_ld.py  (IA_GEMM_WIDE=0/1 picks the kernel)"""
+usage: python tools/abl/gemm_ld.py"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
@@ -24,7 +24,7 @@ def run(M, N, K, lda, ldb, ldc, bks=0):
     for _ in range(10): f()
     e.record(); torch.cuda.synchronize()
     t = s.elapsed_time(e) / 10 * 1e-3
-    print(f"WIDE={os.environ.get('IA_GEMM_WIDE','0')} M={M} N={N} K={K} lda={lda} ldb={ldb} ldc={ldc} bks={bks}: {t*1e6:7.1f} us {2*M*N*K/t/1e12:7.1f} TF/s", flush=True)
+    print(f"M={M} N={N} K={K} lda={lda} ldb={ldb} ldc={ldc} bks={bks}: {t*1e6:7.1f} us {2*M*N*K/t/1e12:7.1f} TF/s", flush=True)
 
 
 for M, N, K in [(8192, 8192, 8192), (65280, 4096, 1024), (65280, 1024, 4096)]:

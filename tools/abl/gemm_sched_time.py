@@ -1,4 +1,4 @@
-"""Times large GEMM shapes with the one-wave-per-SIMD kernel (IA_GEMM_WIDE=1).  usage: IA_GEMM_WIDE=1 python tools/abl/gemm_sched_time.py tag"""
+"""Times large GEMM shapes with the one-wave-per-SIMD kernel.  usage: python tools/abl/gemm_sched_time.py tag"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch

@@ -17,4 +17,4 @@ s.record()
 for _ in range(10): fn()
 e.record(); torch.cuda.synchronize()
 t = s.elapsed_time(e) / 10 * 1e-3
-print(f"WIDE={os.environ.get('IA_GEMM_WIDE','0')} DBG={os.environ.get('IA_GEMM_DBG','0'):>4} M={M} N={N} K={K} {aks}{bks}: {t*1e6:8.1f} us {2*M*N*K/t/1e12:7.1f} TF/s")
+print(f"DBG={os.environ.get('IA_GEMM_DBG','0'):>4} M={M} N={N} K={K} {aks}{bks}: {t*1e6:8.1f} us {2*M*N*K/t/1e12:7.1f} TF/s")

@@ -1,6 +1,6 @@
 #!/bin/bash
 # rocprofv3 kernel stats of a short bench run -> gpurun_out/<tag>_kernel_stats.csv + summary.  usage: tools/prof_bench.sh <tag> [bench args]
-# (environment variables such as IA_GEMM_WIDE are inherited by the profiled python3 process)
+# (environment variables such as IA_GEMM_DYNAMIC are inherited by the profiled python3 process)
 tag=$1; shift
 cd /tmp && export TMPDIR=/tmp
 out=$GRAFT_REPO_ROOT/gpurun_out
