@@ -177,7 +177,8 @@ int ia_swiglu_bwd(const void* dout, const void* src, int ld_src, void* dsrc, int
  * (F.normalize over a size-1 dim), r [B*P, Dk] = rel[r_p]; its backward scatters dr into the relation table's gradient
  * (fp32 atomics; the entity table gets none, d sign = 0).  rows: rows[b, row0 + p] = h[b] + r[b, p],
  * rows[b, row0 + P + p] = hp[b] - r[b, p] inside a [B, rows_per_item, H] buffer (hp = proj_mat(h), computed by the
- * caller with ia_linear_small_fwd). */
+ * caller with ia_linear_small_fwd).  Dk % 4 == 0 (gather forward), H % 4 == 0 (rows forward), 0 <= row0, row0 + 2P <= rows_per_item;
+ * sign(+-0) = +0. */
 int ia_kg_gather_fwd(const float* ent_table, const float* rel_table, const int64_t* ids, int ld_ids, int ent_col, int rel_lo,
                      float* h_sign, float* r, int B, int P, int Dk, ia_stream_t stream);
 int ia_kg_gather_bwd(const float* dr, const int64_t* ids, int ld_ids, int rel_lo, float* rel_grad, int B, int P, int Dk,
@@ -214,7 +215,8 @@ int ia_conv_nhwc_bwd_data(const void* dy, const void* what, void* dx, int B, int
 int ia_conv_nhwc_bwd_weight(const void* x, const void* dy, float* dwhat, float* dbias, int B, int H, int W, int C, int Cout, int k,
                             int stride, int groups, int cols_valid, void* workspace, size_t workspace_bytes, ia_stream_t stream);
 /* ScaledStdConv2d weight: what[o][t*Cgp + c] = (w[o][c][t] - mean_o) * rstd_o * gain[o] * scale (statistics over the
- * Cg*kk fan-in, biased variance, eps inside the sqrt; channels Cg..Cgp-1 zero).  bwd accumulates into dw / dgain. */
+ * Cg*kk fan-in, biased variance taken in two passes about the mean, eps inside the sqrt; channels Cg..Cgp-1 zero; Cgp >= Cg).
+ * bwd accumulates into dw / dgain (either may be NULL). */
 int ia_ws_conv_weight_fwd(const float* w, const float* gain, void* what, float* mean, float* rstd, int Cout, int Cg, int kk, int Cgp,
                           float scale, float eps, ia_stream_t stream);
 int ia_ws_conv_weight_bwd(const float* dwhat, const float* w, const float* gain, const float* mean, const float* rstd, float* dw,
@@ -376,7 +378,9 @@ int ia_color_jitter_step_u8(uint8_t* frames, const int* op, const float* factor,
 int ia_u8_to_nchw_normalized(const uint8_t* src, const uint8_t* flip, float* out, int B, int S0, int S1, const float* mean3,
                              const float* std3, ia_stream_t stream);
 
-/* ---- embeddings (src/models/base.py:238-279, :501-556, :394-442) */
+/* ---- embeddings (src/models/base.py:238-279, :501-556, :394-442).  0 < H <= 4096, H % 8 == 0; extra_idx (may be NULL) needs extra;
+ * z_out = bf16(word|extra + type + pos), mean / rstd are the statistics of that rounded z.  The backward call returns IA_ERR_WORKSPACE
+ * for a workspace below ia_embed_ln_bwd_workspace_bytes(M, H). */
 int ia_embed_ln_fwd(const int64_t* ids, const int64_t* type_ids, const int64_t* pos_ids, const int32_t* extra_idx, const float* word,
                     const float* type, const float* pos, const float* extra, const float* gamma, const float* beta, void* z_out,
                     void* y, float* mean, float* rstd, int M, int H, float eps, float drop_p, uint32_t seed, uint32_t stream_id,
@@ -392,13 +396,15 @@ int ia_embed_ln_bwd(const void* dy, const void* z, const float* mean, const floa
  * add to (-1 = none: extra rows and word_pad rows for the word table, pos_pad rows for the position table, first).  Each table row
  * is summed over its input rows in that order, so the table gradients are the same from run to run. */
 
-/* ---- ViT input side (timm PatchEmbed + cls token + pos_embed; src/models/multimodal.py:811) */
+/* ---- ViT input side (timm PatchEmbed + cls token + pos_embed; src/models/multimodal.py:811).  im2col: P % 8 == 0, S % P == 0, patch
+ * column = (c, ph, pw).  tokens: H > 0, H % 8 == 0. */
 int ia_im2col_patch(const float* images, void* patches, int B, int C, int S, int P, ia_stream_t stream);
 int ia_vit_tokens_fwd(const void* patch, const float* cls, const float* pos, void* tokens, int B, int NP, int H, ia_stream_t stream);
 int ia_vit_tokens_bwd(const void* dtokens, void* dpatch, float* dcls, float* dpos, int B, int NP, int H, int accumulate,
                       ia_stream_t stream);
 
-/* ---- CLS row pick with dropout (features[:, 0, :] -> dropout, src/models/base.py:104,140-141) */
+/* ---- CLS row pick with dropout (features[:, 0, :] -> dropout, src/models/base.py:104,140-141).  src / dsrc rows are ld elements apart
+ * (ld >= H, any H > 0); the dropout element index is b * H + col; the backward call needs distinct rows. */
 int ia_gather_rows_fwd(const void* src, int ld, const int32_t* rows, float* out, int B, int H, float drop_p, uint32_t seed,
                        uint32_t stream_id, ia_stream_t stream);
 int ia_gather_rows_bwd(const float* dout, int ld, const int32_t* rows, void* dsrc, int B, int H, float drop_p, uint32_t seed,
@@ -419,7 +425,7 @@ int ia_pair_head_ce_bwd(const float* probs, const int64_t* labels, const float* 
 /* span means of the auxiliary attribute-pair task (reference text.py:66-102 AuxiliaryTaskPair: mean of the token rows of a
  * key:value span, for the source and the target item; the pair head + CE above finishes it).  spans [S][2] int32 = absolute
  * (first row, end row) into seq [rows, ld] bf16; out [S][H] fp32.  Backward: dseq [B*L, H] bf16 overwritten; span_ptr [B+1]
- * delimits the spans of each sample. */
+ * delimits the spans of each sample.  H > 0, H % 8 == 0, ld % 8 == 0. */
 int ia_span_mean_fwd(const void* seq, int ld, const int* spans, float* out, int S, int H, ia_stream_t stream);
 int ia_span_mean_bwd(const float* dout, const int* spans, const int* span_ptr, void* dseq, int B, int L, int H, ia_stream_t stream);
 

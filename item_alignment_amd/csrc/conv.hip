@@ -127,12 +127,15 @@ __global__ __launch_bounds__(256) void ws_weight_fwd_kernel(const float* __restr
   if (o >= Cout) return;
   const int fan = Cg * kk;
   const float* wo = w + (size_t)o * fan;
-  float s = 0.f, ss = 0.f;
-  for (int i = lane; i < fan; i += 64) { const float v = wo[i]; s += v; ss += v * v; }
-  s = wave_sum(s); ss = wave_sum(ss);
-  const float mu = s / fan;
-  const float var = fmaxf(ss / fan - mu * mu, 0.f);
-  const float rs = rsqrtf(var + eps);
+  // two passes, like the LayerNorm kernels: E[w^2] - mean^2 in fp32 loses the variance of a filter whose mean is large against its
+  // spread (mean 0.5, std 1e-3: rstd off by several per cent); the row is in cache for the second pass and is read again below anyway
+  float s = 0.f;
+  for (int i = lane; i < fan; i += 64) s += wo[i];
+  const float mu = wave_sum(s) / fan;
+  float q = 0.f;
+  for (int i = lane; i < fan; i += 64) { const float d = wo[i] - mu; q += d * d; }
+  const float var = wave_sum(q) / fan;
+  const float rs = 1.f / sqrtf(var + eps);      // correctly rounded square root and quotient (one wave per filter, once per step)
   if (lane == 0) { mean[o] = mu; rstd[o] = rs; }
   const float a = rs * gain[o] * scale;
   for (int i = lane; i < kk * Cgp; i += 64) {

@@ -351,7 +351,7 @@ extern "C" int ia_embed_ln_fwd(const int64_t* ids, const int64_t* type_ids, cons
                                float drop_p, uint32_t seed, uint32_t stream_id, hipStream_t stream) {
   (void)hipGetLastError();  // drop stale status left by unrelated runtime calls (e.g. hipEventQuery -> NotReady)
   if (!ids || !type_ids || !pos_ids || !word || !type || !pos || !gamma || !beta || !z_out || !y || !mean || !rstd) return IA_ERR_ARG;
-  if (M <= 0 || (H & 7) || H > 4096 || (extra_idx && !extra)) return IA_ERR_ARG;
+  if (M <= 0 || H <= 0 || (H & 7) || H > 4096 || (extra_idx && !extra)) return IA_ERR_ARG;
   uint32_t thr16; float inv_keep; drop_params(drop_p, thr16, inv_keep);
   dim3 grid((M + 3) / 4), blk(256);
   const int nv = (H + 511) / 512;
@@ -481,7 +481,7 @@ extern "C" int ia_embed_ln_bwd(const void* dy, const void* z, const float* mean,
   (void)hipGetLastError();  // drop stale status left by unrelated runtime calls (e.g. hipEventQuery -> NotReady)
   if (!dy || !z || !mean || !rstd || !gamma || !ids || !type_ids || !pos_ids) return IA_ERR_ARG;
   if ((dword && !word_order) || (dpos && !pos_order) || (dtype && !type_order)) return IA_ERR_ARG;
-  if (M <= 0 || (H & 7) || H > 4096) return IA_ERR_ARG;
+  if (M <= 0 || H <= 0 || (H & 7) || H > 4096) return IA_ERR_ARG;
   if (!workspace || workspace_bytes < ia_embed_ln_bwd_workspace_bytes(M, H)) return IA_ERR_WORKSPACE;
   uint32_t thr16; float inv_keep; drop_params(drop_p, thr16, inv_keep);
   if (L <= 0 || M % L) L = M;      // no sequence structure given: every row is its own position
@@ -527,7 +527,7 @@ extern "C" int ia_im2col_patch(const float* images, void* patches, int B, int C,
 extern "C" int ia_vit_tokens_fwd(const void* patch, const float* cls, const float* pos, void* tokens, int B, int NP, int H,
                                  hipStream_t stream) {
   (void)hipGetLastError();  // drop stale status left by unrelated runtime calls (e.g. hipEventQuery -> NotReady)
-  if (!patch || !cls || !pos || !tokens || B <= 0 || NP <= 0 || (H & 7)) return IA_ERR_ARG;
+  if (!patch || !cls || !pos || !tokens || B <= 0 || NP <= 0 || H <= 0 || (H & 7)) return IA_ERR_ARG;
   hipLaunchKernelGGL(vit_tokens_fwd_kernel, dim3(grid_for((size_t)B * (NP + 1) * H / 8)), dim3(256), 0, stream, (const bf16*)patch, cls, pos,
                      (bf16*)tokens, B, NP, H);
   return ia_check_launch();
@@ -536,7 +536,7 @@ extern "C" int ia_vit_tokens_fwd(const void* patch, const float* cls, const floa
 extern "C" int ia_vit_tokens_bwd(const void* dtokens, void* dpatch, float* dcls, float* dpos, int B, int NP, int H, int accumulate,
                                  hipStream_t stream) {
   (void)hipGetLastError();  // drop stale status left by unrelated runtime calls (e.g. hipEventQuery -> NotReady)
-  if (!dtokens || !dpatch || !dcls || !dpos || B <= 0 || NP <= 0 || (H & 7)) return IA_ERR_ARG;
+  if (!dtokens || !dpatch || !dcls || !dpos || B <= 0 || NP <= 0 || H <= 0 || (H & 7)) return IA_ERR_ARG;
   hipLaunchKernelGGL(vit_tokens_bwd_kernel, dim3(grid_for((size_t)(NP + 1) * H / 8)), dim3(256), 0, stream, (const bf16*)dtokens,
                      (bf16*)dpatch, dcls, dpos, B, NP, H, accumulate);
   return ia_check_launch();

@@ -399,7 +399,7 @@ extern "C" int ia_ln_bwd2_rows(const void* dy, const void* dy2, const void* dres
                                float drop_p, uint32_t seed, uint32_t stream_id, const uint8_t* row_live, void* workspace,
                                size_t workspace_bytes, int accumulate, hipStream_t stream) {
   (void)hipGetLastError();  // drop stale status left by unrelated runtime calls (e.g. hipEventQuery -> NotReady)
-  if (!dy || !z || !mean || !rstd || !gamma || !dz || M <= 0 || (H & 7) || H > 512 * MAXV) return IA_ERR_ARG;
+  if (!dy || !z || !mean || !rstd || !gamma || !dz || M <= 0 || H <= 0 || (H & 7) || H > 512 * MAXV) return IA_ERR_ARG;
   if (workspace_bytes < ia_ln_bwd_workspace_bytes(M, H) || !workspace) return IA_ERR_WORKSPACE;
   const uint32_t thr16 = drop_p > 0.f ? (uint32_t)(drop_p * 65536.f + 0.5f) : 0u;
   if (thr16 && !dx) return IA_ERR_ARG;
