@@ -37,7 +37,7 @@ const char* ia_strerror(int code);
 /* Bumped whenever an entry point is added or the meaning of an argument / output changes (round 2 changed what IA_EPI_BIAS_GELU
  * stores in C2 and what IA_EPI_DGELU expects in aux): a caller built against another header must not run on this library.
  * item_alignment_amd/_lib.py refuses to load a library whose version differs from the one it was written for. */
-#define IA_ABI_VERSION 13
+#define IA_ABI_VERSION 14
 int ia_abi_version(void);
 
 /* ---- GEMM: torch.nn.Linear forward / dgrad / wgrad (src/models/text.py:1241 -> RobertaLayer dense
@@ -573,6 +573,50 @@ int ia_layer_bwd(const ia_layer_cfg* cfg, const ia_layer_weights* w, const ia_la
 int ia_layer_bwd2(const ia_layer_cfg* cfg, const ia_layer_weights* w, const ia_layer_grads* g, const void* x, const uint8_t* key_mask,
                   const void* y, const void* stash, const void* dy, const void* dy2, void* dx, void* dx2, void* scratch,
                   size_t scratch_bytes, ia_stream_t stream);
+
+/* ---- GCNII graph encoder of the graph two-tower model (reference src/models/graph.py; csrc/gcn.hip), fp32 in and out.  (ABI 14)
+ * The adjacency is CSR: rowptr int64 [N+1], col int32 or int64 [nnz] (col_is_64), val fp32 [nnz] or NULL = all ones.  C (node
+ * width): a multiple of 32 in [32, 512]; N * max(C, F) < 2^32.  Matrices are row-major, 16-byte aligned.  A dropout mask is a
+ * function of (seed, stream_id, element index): element e of stream s is kept iff the 16-bit half (e & 1) of ia_rng(seed, s, e >> 1)
+ * is >= round(p * 65536); kept elements are scaled by 1 / (1 - round(p * 65536) / 65536).  No float atomics anywhere: results are
+ * bit-identical from run to run.  long_rows (int32 [n_long]): the rows with more than IA_GCN_LONG_ROW neighbours; each is summed by a
+ * whole workgroup instead of one wave.  The list must hold EVERY such row, or be NULL: with NULL every row is summed by one wave
+ * (correct, slow for hub rows); with a list, a row over the limit that the list lacks is written by nobody.  A listed row at or
+ * under the limit is left to its wave. */
+#define IA_GCN_LONG_ROW 512
+#define IA_GCN_SLAB_ROWS 1024   /* node rows per partial product of the weight gradients (the longest fp32 sum feeding dW) */
+/* h = (1 - alpha) * A (drop(x)) + alpha * x0 */
+int ia_gcn_propagate_fwd(const int64_t* rowptr, const void* col, int col_is_64, const float* val, const float* x, const float* x0,
+                         float* h, int N, int C, float alpha, float drop_p, uint32_t seed, uint32_t stream_id,
+                         const int32_t* long_rows, int n_long, ia_stream_t stream);
+/* The same gather over the CSR of A^T: dx = keep / (1 - p) * (1 - alpha) * A^T dh  (overwritten; NULL: added into dx0 instead, for
+ * the layer whose input x is x0 itself);  dx0 = (dx0_accumulate ? dx0 : 0) + alpha * dh. */
+int ia_gcn_propagate_bwd(const int64_t* rowptr_t, const void* col_t, int col_is_64, const float* val_t, const float* dh, float* dx,
+                         float* dx0, int dx0_accumulate, int N, int C, float alpha, float drop_p, uint32_t seed, uint32_t stream_id,
+                         const int32_t* long_rows_t, int n_long_t, ia_stream_t stream);
+/* out = drop(relu((1 - beta) h + beta h W)), W [C, C] (GCN2Conv weight1); drop_p = 0 for every layer but a last one whose output
+ * dropout is fused here.  out > 0 exactly where the backward passes a gradient. */
+int ia_gcn_mix_fwd(const float* h, const float* W, float* out, int N, int C, float beta, float drop_p, uint32_t seed, uint32_t stream_id,
+                   ia_stream_t stream);
+/* workspace of ia_gcn_mix_bwd (F = 0) and ia_gcn_input_bwd: ceil(N / IA_GCN_SLAB_ROWS) partial [C, max(C, F)] products */
+size_t ia_gcn_workspace_bytes(int N, int C, int F);
+/* dpre = dout * (out > 0) / (1 - p);  dh = (1 - beta) dpre + beta dpre W^T (overwritten, no aliasing);  dW += beta h^T dpre
+ * (dW NULL: skipped). */
+int ia_gcn_mix_bwd(const float* dout, const float* out, const float* h, const float* W, float* dh, float* dW, int N, int C, float beta,
+                   float drop_p, void* workspace, size_t workspace_bytes, ia_stream_t stream);
+/* x0 = relu(drop(X) W^T + bias): X [N, F] (F a multiple of 4), W [C, F], bias [C] */
+int ia_gcn_input_fwd(const float* X, const float* W, const float* bias, float* x0, int N, int F, int C, float drop_p, uint32_t seed,
+                     uint32_t stream_id, ia_stream_t stream);
+/* dpre = dx0 * (x0 > 0);  dW += dpre^T drop(X);  db += column sums of dpre */
+int ia_gcn_input_bwd(const float* dx0, const float* x0, const float* X, float* dW, float* db, int N, int F, int C, float drop_p,
+                     uint32_t seed, uint32_t stream_id, void* workspace, size_t workspace_bytes, ia_stream_t stream);
+/* out[r] = drop(x[idx[r]]), r < R (mask element r * C + c);  idx outside [0, N) reads a zero row */
+int ia_gcn_pair_gather_fwd(const float* x, const int32_t* idx, float* out, int R, int C, int N, float drop_p, uint32_t seed,
+                           uint32_t stream_id, ia_stream_t stream);
+/* dnode[idx[r]] += drop-mask(r) * dout[r]; order int32 [R] = the rows r stably sorted by idx[r]: a node that occurs in several rows is
+ * summed in that order by a single writer. */
+int ia_gcn_pair_scatter_bwd(const float* dout, const int32_t* idx, const int32_t* order, float* dnode, int R, int C, int N, float drop_p,
+                            uint32_t seed, uint32_t stream_id, ia_stream_t stream);
 
 /* ---- data-parallel gradient exchange (pure data parallelism, one process per GPU; reference loop being sharded:
  * finetune_multimodal.py:371-468).  RCCL over xGMI behind four calls, for hosts that bind only this header (the Python host of this

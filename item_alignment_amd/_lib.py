@@ -153,6 +153,15 @@ SIGNATURES = {
     "ia_kgpt_corrupt": (i32, [vp, vp, vp, i32, vp, i32, i32, C.c_uint64, vp, vp, vp]),
     "ia_kgpt_lp_workspace_bytes": (sz, [i32, i32]),
     "ia_kgpt_lp_rank": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, sz, vp]),
+    "ia_gcn_propagate_fwd": (i32, [vp, vp, i32, vp, vp, vp, vp, i32, i32, f32, f32, u32, u32, vp, i32, vp]),
+    "ia_gcn_propagate_bwd": (i32, [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, f32, f32, u32, u32, vp, i32, vp]),
+    "ia_gcn_mix_fwd": (i32, [vp, vp, vp, i32, i32, f32, f32, u32, u32, vp]),
+    "ia_gcn_workspace_bytes": (sz, [i32, i32, i32]),
+    "ia_gcn_mix_bwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, vp, sz, vp]),
+    "ia_gcn_input_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, f32, u32, u32, vp]),
+    "ia_gcn_input_bwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, f32, u32, u32, vp, sz, vp]),
+    "ia_gcn_pair_gather_fwd": (i32, [vp, vp, vp, i32, i32, i32, f32, u32, u32, vp]),
+    "ia_gcn_pair_scatter_bwd": (i32, [vp, vp, vp, vp, i32, i32, i32, f32, u32, u32, vp]),
     "ia_cast_f32_to_bf16": (i32, [vp, vp, sz, vp]),
     "ia_cast_bf16_to_f32": (i32, [vp, vp, sz, vp]),
     "ia_layer_stash_bytes": (sz, [C.POINTER(LayerCfg)]),
@@ -172,7 +181,7 @@ SIGNATURES = {
 _lib = None
 
 
-ABI_VERSION = 13      # = IA_ABI_VERSION of include/itemalign.h (tests/test_cabi_symbols.py keeps the two in step)
+ABI_VERSION = 14      # = IA_ABI_VERSION of include/itemalign.h (tests/test_cabi_symbols.py keeps the two in step)
 
 
 class ItemAlignError(RuntimeError):

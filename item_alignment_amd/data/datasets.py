@@ -416,3 +416,21 @@ class PairedMultimodalDataset(Dataset):
         except Exception:
             pass
         return rec
+
+
+def collate_gnn(inputs):
+    """reference data.py:262-274: the list of pair dicts, unchanged."""
+    return inputs
+
+
+class GCNDataset(Dataset):
+    """reference data.py:1036-1043: pair dicts (src_idx, tgt_idx, src_item_id, tgt_item_id, optional item_label)."""
+
+    def __init__(self, data):
+        self.data = data
+
+    def __getitem__(self, item):
+        return self.data[item]
+
+    def __len__(self):
+        return len(self.data)

@@ -8,3 +8,4 @@ from .text import (RobertaModel, RobertaOneTower, RobertaTwoTower, RobertaPKGMMo
 from .image import VisionTransformer, VitTwoTower, NFNetTwoTower, ResNetTwoTower, create_model
 from .multimodal import (RobertaImageModel, RobertaImageOneTower, RobertaImageTwoTower, CoCaModel, CoCaForItemAlignment, LayerNorm,
                          Residual, RotaryEmbedding, SwiGLU, ParallelTransformerBlock, CrossAttention)
+from .graph import GCN, GCN2Conv, GCNTwoTower, GraphAdjacency, load_adjacency

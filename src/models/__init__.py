@@ -4,3 +4,4 @@ from item_alignment_amd.models import *  # noqa: F401,F403
 from item_alignment_amd.models import (RobertaModel, RobertaOneTower, RobertaTwoTower, PKGMOneTower, PKGMTwoTower, TextCNNTwoTower,  # noqa: F401
                                        RobertaImageOneTower, RobertaImageTwoTower, CoCaForItemAlignment, NFNetTwoTower, VitTwoTower,
                                        ResNetTwoTower)
+from item_alignment_amd.models import GCN, GCNTwoTower, GraphAdjacency, load_adjacency  # noqa: F401,E402
