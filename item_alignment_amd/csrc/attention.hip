@@ -408,7 +408,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs p) {
   if (!active) return;
   const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
   const float inv = l_tot > 0.f ? p.inv_keep / l_tot : 0.f;
-  if (q < Lq && hh == 0 && p.lse2) p.lse2[((size_t)b * p.nh + h) * p.Lq + q] = m_ref + __builtin_amdgcn_logf(l_tot);
+  // a row without any attendable key (l_tot == 0): lse2 = 0, not -inf -- the backward forms exp2(s - lse2) with s = -1e30 there
+  if (q < Lq && hh == 0 && p.lse2) p.lse2[((size_t)b * p.nh + h) * p.Lq + q] = l_tot > 0.f ? m_ref + __builtin_amdgcn_logf(l_tot) : 0.f;
   // the K/V ring is free after the loop's last barrier: wave-private staging slots at its start
   store_block_rows(smem + wave * EPI_SLOT, o0, o1, inv, false, p.out + (qbase + q0) * p.ld_o + h * 64, p.ld_o, Lq - q0, lane);
 }
@@ -788,7 +789,8 @@ __global__ __launch_bounds__(256, QB == 1 ? 3 : 2) void attn_fwd3_kernel(AttnArg
     const float l_tot = row[qb].l_run + swap32(row[qb].l_run);
     const float inv = l_tot > 0.f ? p.inv_keep / l_tot : 0.f;
     if (qq0 + lq < Lq && hh == 0 && p.lse2)
-      p.lse2[((size_t)b * p.nh + h) * p.Lq + qq0 + lq] = row[qb].m_ref * (PRESCALE ? 1.f : p.sc) + __builtin_amdgcn_logf(l_tot);
+      p.lse2[((size_t)b * p.nh + h) * p.Lq + qq0 + lq] =      // no attendable key (l_tot == 0): 0, not -inf (the backward's exp2(s - lse2))
+          l_tot > 0.f ? row[qb].m_ref * (PRESCALE ? 1.f : p.sc) + __builtin_amdgcn_logf(l_tot) : 0.f;
     store_block_rows(smem + EPI_OFF + (wave * QB + qb) * EPI_SLOT, o[qb][0], o[qb][1], inv, false, p.out + (qbase + qq0) * p.ld_o + h * 64, p.ld_o,
                      Lq - qq0, lane);
   }
