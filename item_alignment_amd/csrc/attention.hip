@@ -1,21 +1,28 @@
 // Fused multi-head self-attention for the RoBERTa / ViT towers (head dim 64), gfx950.
 //
-// Forward:  O = softmax(Q K^T * scale + key_mask) V   per (sequence, head), flash style:
-// K/V stream through LDS in 64-key tiles (buffer_load ... lds, double buffered), scores never
-// leave registers. Reference arithmetic: transformers RobertaSelfAttention (eager path) called from
-// src/models/text.py:1241, and timm Attention called from src/models/multimodal.py:811.
+// Forward:  O = softmax(Q K^T * scale + key_mask) V   per (sequence, head), flash style: K/V stream through an LDS ring in 64-key
+// tiles (buffer_load ... lds), scores never leave registers.  Reference arithmetic: transformers RobertaSelfAttention (eager path)
+// called from src/models/text.py:1241, and timm Attention called from src/models/multimodal.py:811.
 //
-// Everything is computed transposed so that softmax statistics are lane-local:
+// The forward and the dQ side are computed transposed so that softmax statistics are lane-local:
 //   S^T[key][q] = K Q^T   : MFMA 32x32x16, A = K fragment (LDS, ds_read_b128), B = Q fragment (registers)
 //                            -> lane (q = lane&31) holds 32 keys of its own query, partner lane^32 the rest
 //   O^T[d][q]  += V^T P^T : A = V^T fragment (ds_read_b64_tr_b16 from the row-major V tile), B = P^T taken
 //                            straight from the S^T accumulators (bf16-packed), no cross-lane traffic.
 // The k-slot <-> key permutation inside a 16-key block is the one the accumulator layout dictates
 // (slot (half,j) <-> key (j&3) + 8*(j>>2) + 4*half) and the V^T transpose read follows it.
+// Every kernel multiplies K with the SAME operand q' = bf16(q * scale * log2 e) -- rounded in the kernel, or already by the QKV
+// projection (AttnArgs::q_prescaled) -- so an accumulator is exp2's argument and the P the backward recomputes is the P the saved log-sum-exp belongs to.
 //
-// Backward = two kernels, both recompute P from Q, K and the saved log-sum-exp:
-//   attn_bwd_dq  (block owns 128 queries, S^T orientation):  dQ^T += K^T dS^T
-//   attn_bwd_dkv (block owns 128 keys,   S orientation):     dV^T += dO^T P ; dK^T += Q^T dS
+// Three kernel families, all recomputing P from Q, K and the saved log-sum-exp in the backward:
+//   fwd3  attn_fwd3_kernel<DROPOUT, QB>: a workgroup owns 128 (QB = 1) or 256 (QB = 2) queries; launch_fwd picks by how full the last
+//         256-query block is.
+//   bwd3  the pair behind every backward the fused kernel does not serve (Lq != Lk, packed rows, <= 32 or > 256 tokens):
+//         attn_bwd3_dq_kernel  (workgroup owns 128 queries, S^T orientation):  dQ^T += K^T dS^T, leaves delta = rowsum(dO o O) behind for
+//         attn_bwd3_dkv_kernel (workgroup owns 128 keys,    S orientation):    dV^T += dO^T P ; dK^T += Q^T dS.
+//         IA_ATTN_EXACT_DELTA=1 (read per call) puts attn_bwd3_delta_kernel in front: delta = sum_k P dP in fp32, and bypasses bwdf.
+//   bwdf  attn_bwd_fused_kernel: plain self-attention of 33 .. 256 tokens, one persistent workgroup per (sequence, head) item, dQ, dK
+//         and dV from one evaluation of P and dS (fused_applies decides).
 #include "common.h"
 #include <type_traits>
 #include <cstdlib>
@@ -23,6 +30,7 @@
 // flag bits of ia_attn_bwd_bias_ex (include/itemalign.h; this file does not include the public header)
 #define IA_ATTN_Q_PRESCALED 1
 #define IA_ATTN_MASKED_ROWS_DEAD 2
+extern "C" size_t ia_attn_bwd_bias_workspace_bytes(int B, int nh, int L);
 
 namespace {
 
@@ -44,7 +52,7 @@ struct AttnArgs {
   uint32_t q_bytes, kv_bytes, o_bytes;
   float sc;                                       // softmax scale * log2(e)
   float scale;                                    // softmax scale
-  int q_prescaled;                                // q rows already hold q * sc rounded to bf16 (ia_gemm_bf16_qscale): the round-3/4
+  int q_prescaled;                                // q rows already hold q * sc rounded to bf16 (ia_gemm_bf16_qscale): the
                                                   // kernels skip their own pre-scaling; dq stays dL/dq of the UNSCALED q
   uint32_t thr16; float inv_keep; uint32_t seed;
   float* cs_part;                                 // backward, optional: [b*ntile + tile][3*nh*64] fp32 column sums of this workgroup's
@@ -55,26 +63,11 @@ struct AttnArgs {
 };
 
 // Workgroups are dealt round-robin to the 8 XCDs (each with its own L2): renumber them so that consecutive
-// work items -- the 128-row tiles of one (sequence, head), which all stream the same K/V -- share an XCD.
-IA_DEV void attn_block_coords(const AttnArgs& p, int len, int& tile, int& h, int& b) {
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int per = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-#ifdef IA_NO_XCD
-  int w = bid;
-#else
-  int w = (xcd < r ? xcd * (per + 1) : r * (per + 1) + (xcd - r) * per) + idx;
-#endif
-  const int nt = (len + 127) >> 7;
-  tile = w % nt; w /= nt;
-  h = w % p.nh; b = w / p.nh;
-}
-
-// the same with `rows` queries (keys) per workgroup instead of 128
-IA_DEV void attn_block_coords_n(const AttnArgs& p, int len, int rows, int& tile, int& h, int& b) {
+// work items -- the nt row tiles of one (sequence, head), which all stream the same K/V -- share an XCD.
+IA_DEV void attn_block_coords(const AttnArgs& p, int nt, int& tile, int& h, int& b) {
   const int nwg = gridDim.x, bid = blockIdx.x;
   const int per = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
   int w = (xcd < r ? xcd * (per + 1) : r * (per + 1) + (xcd - r) * per) + idx;
-  const int nt = (len + rows - 1) / rows;
   tile = w % nt; w /= nt;
   h = w % p.nh; b = w / p.nh;
 }
@@ -96,19 +89,6 @@ IA_DEV void build_valid_table(const AttnArgs& p, uint32_t (*s_valid)[2], size_t 
 IA_DEV int swz_b128(int row) { return (row >> 1) & 7; }   // two 128-byte rows span the 64 banks: conflict-free for any 16 consecutive rows
 // tile read with the transpose read (row-major [row][64 d]); 32 B slot XOR
 IA_DEV int swz_tr(int row) { return ((row >> 1) & 1) << 2; }
-
-template <bool TR>
-IA_DEV void stage64(__amdgpu_buffer_rsrc_t rs, char* s, size_t row0, int nvalid, int ld, int col0, int tid, int wave) {
-  // 64 rows x 64 columns (bf16) -> 8 KiB, two issues of 256 lanes x 16 B
-#pragma unroll
-  for (int issue = 0; issue < 2; ++issue) {
-    const int row = issue * 32 + (tid >> 3);
-    const int c = (tid & 7) ^ (TR ? swz_tr(row) : swz_b128(row));
-    uint32_t off = (uint32_t)(((row0 + row) * ld + col0 + c * 8) * 2);
-    if (row >= nvalid) off = OOB;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, IA_LDS(s + issue * 4096 + wave * 1024), 16, off, 0, 0, 0);
-  }
-}
 
 // A wave's own 32 rows x 64 columns (this head's slice of q / k / v / o / dO rows row0 .. row0+31) into a wave-private 4 KiB LDS
 // slot in the ds_read_b128 layout of frag_b128: four 16-byte LDS-DMA issues, each moving 8 whole 128-byte rows.  (Loaded straight into
@@ -150,12 +130,6 @@ struct TrPair {   // the two A^T fragments (columns 0..31 and 32..63) of one 16-
   IA_DEV bf16x8 a0() const { s16x8 r = {lo0[0], lo0[1], lo0[2], lo0[3], hi0[0], hi0[1], hi0[2], hi0[3]}; return __builtin_bit_cast(bf16x8, r); }
   IA_DEV bf16x8 a1() const { s16x8 r = {lo1[0], lo1[1], lo1[2], lo1[3], hi1[0], hi1[1], hi1[2], hi1[3]}; return __builtin_bit_cast(bf16x8, r); }
 };
-// rows ROW0 .. ROW0+15 (ROW0 a multiple of 16) of the tile whose lane bases are b0 / b1 (tr_lane_off for col0 = 0 / 32)
-template <int ROW0>
-IA_DEV void tr_issue(TrPair& f, uint32_t b0, uint32_t b1) {
-  f.lo0 = tr_read<ROW0 * 128>(b0); f.hi0 = tr_read<ROW0 * 128 + 1024>(b0);
-  f.lo1 = tr_read<ROW0 * 128>(b1); f.hi1 = tr_read<ROW0 * 128 + 1024>(b1);
-}
 // wait until at most N LDS operations issued after this pair are still outstanding (LDS returns in order)
 template <int N>
 IA_DEV void tr_wait(TrPair& f) {
@@ -236,187 +210,9 @@ IA_DEV void zero_cs_row(float* cs_out, int lane) {
   if (lane < 16) *reinterpret_cast<f32x4*>(cs_out + lane * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
 }
 
-// One 64-key tile of the forward pass for this wave's 32 queries (S^T orientation, see the header comment).
-//
-// Online softmax with a lazily updated reference: probabilities are formed as exp2(s*sc - m_ref) against the
-// reference m_ref the lane already holds, and m_ref only moves (with the O / l rescale that implies) when some
-// row of the wave would exceed 2^RESCALE_THR or has nothing accumulated yet. The result is the same softmax
-// (any reference cancels in O / l); the common tile costs fma + max + exp2 per score and no cross-lane traffic.
-// m_ref is shared by the two lanes of a query (lane, lane^32); l_run is this lane's half of the row sum.
-constexpr float RESCALE_THR = 8.f;
-
-template <int BUF, bool DROPOUT>
-IA_DEV void fwd_tile(const AttnArgs& p, const char* smem, const bf16x8 (&qf)[4], uint32_t valid_lo, uint32_t valid_hi,
-                     float& m_ref, float& l_run, f32x16& o0, f32x16& o1, int lane, int q, int kt, uint32_t rk) {
-  const int hh = lane >> 5, lq = lane & 31;
-  const char* sK = smem + BUF * 16384;
-  f32x16 s0 = zero16(), s1 = zero16();
-#pragma unroll
-  for (int kb = 0; kb < 4; ++kb) {
-    const bf16x8 k0 = frag_b128(sK, lq, kb * 2 + hh);
-    const bf16x8 k1 = frag_b128(sK, 32 + lq, kb * 2 + hh);
-    s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k0, qf[kb], s0, 0, 0, 0);
-    s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k1, qf[kb], s1, 0, 0, 0);
-  }
-  // V^T fragments of the first two 16-key steps land while the softmax runs
-  const uint32_t vb0 = lds_addr(smem) + tr_lane_off(lane, 0), vb1 = lds_addr(smem) + tr_lane_off(lane, 32);
-  constexpr int VOFF = (BUF * 16384 + 8192) / 128;   // tr_issue takes its offset in 128-byte rows
-  TrPair va, vb;
-  tr_issue<VOFF>(va, vb0, vb1);
-  tr_issue<VOFF + 16>(vb, vb0, vb1);
-  if ((valid_lo & valid_hi) != 0xFFFFFFFFu) {   // wave-uniform: only a ragged / padded tile pays for the selects
-    asm volatile("" ::: "memory");   // keeps hipcc from flattening this branch into 64 always-executed selects
-    const uint32_t vlo = hh ? valid_lo >> 4 : valid_lo, vhi = hh ? valid_hi >> 4 : valid_hi;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int bit = (r & 3) + 8 * (r >> 2);
-      if (!((vlo >> bit) & 1)) s0[r] = -INFINITY;
-      if (!((vhi >> bit) & 1)) s1[r] = -INFINITY;
-    }
-  }
-  const float neg_m = -m_ref;
-  float tmax = -INFINITY;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    s0[r] = __builtin_fmaf(s0[r], p.sc, neg_m);
-    s1[r] = __builtin_fmaf(s1[r], p.sc, neg_m);
-    tmax = fmaxf(tmax, fmaxf(s0[r], s1[r]));
-  }
-  if (__ballot(tmax > RESCALE_THR || l_run == 0.f) != 0ull) {   // wave-uniform, rare after the first tile
-    const float tm = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-    const bool fresh = (l_run + __shfl_xor(l_run, 32, 64)) == 0.f;   // nothing accumulated: re-basing is free
-    const float delta = (tm == -INFINITY) ? 0.f : (fresh ? tm : fmaxf(tm, 0.f));
-    const float alpha = fresh ? 0.f : __builtin_amdgcn_exp2f(-delta);
-    m_ref += delta;
-    l_run *= alpha;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { s0[r] -= delta; s1[r] -= delta; o0[r] *= alpha; o1[r] *= alpha; }
-  }
-  float rs = 0.f;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    s0[r] = __builtin_amdgcn_exp2f(s0[r]);
-    s1[r] = __builtin_amdgcn_exp2f(s1[r]);
-    rs += s0[r] + s1[r];
-  }
-  l_run += rs;
-  if (DROPOUT) {
-    // key = kt*64 + ACC_ROW(r, hh) (+ 32 for the second block): pair constant = tile part (scalar) + lane part (hh) + immediate
-    const uint32_t tile_c = (uint32_t)(kt * 32) * IA_RNG_PAIR_C + (uint32_t)(2 * hh) * IA_RNG_PAIR_C;
-#pragma unroll
-    for (int r = 0; r < 16; r += 2) {
-      constexpr uint32_t C = IA_RNG_PAIR_C;
-      const uint32_t imm = (uint32_t)(((r & 3) >> 1) + 4 * (r >> 2)) * C;      // (ACC_ROW(r, 0) >> 1) * C, r even
-      const uint32_t ra = ia_rng_pair(rk, tile_c + imm);
-      const uint32_t rb = ia_rng_pair(rk, tile_c + imm + 16u * C);
-      if ((ra & 0xFFFFu) < p.thr16) s0[r] = 0.f;
-      if ((ra >> 16) < p.thr16) s0[r + 1] = 0.f;
-      if ((rb & 0xFFFFu) < p.thr16) s1[r] = 0.f;
-      if ((rb >> 16) < p.thr16) s1[r + 1] = 0.f;
-    }
-  }
-  bf16x8 pf[4];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    pf[0][j] = f2bf(s0[j]); pf[1][j] = f2bf(s0[8 + j]);
-    pf[2][j] = f2bf(s1[j]); pf[3][j] = f2bf(s1[8 + j]);
-  }
-  tr_wait<4>(va);
-  o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va.a0(), pf[0], o0, 0, 0, 0);
-  o1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va.a1(), pf[0], o1, 0, 0, 0);
-  TrPair vc, vd;
-  tr_issue<VOFF + 32>(vc, vb0, vb1);
-  tr_wait<4>(vb);
-  o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vb.a0(), pf[1], o0, 0, 0, 0);
-  o1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vb.a1(), pf[1], o1, 0, 0, 0);
-  tr_issue<VOFF + 48>(vd, vb0, vb1);
-  tr_wait<4>(vc);
-  o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vc.a0(), pf[2], o0, 0, 0, 0);
-  o1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vc.a1(), pf[2], o1, 0, 0, 0);
-  tr_wait<0>(vd);
-  o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vd.a0(), pf[3], o0, 0, 0, 0);
-  o1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vd.a1(), pf[3], o1, 0, 0, 0);
-}
-
 // ------------------------------------------------------------------------------------------ forward
-template <bool DROPOUT>
-__global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs p) {
-  // K | V tile, double buffered, then the valid-key table. One __shared__ object only: with a second one hipcc
-  // drains vmcnt(0) before every LDS read while a DMA is in flight.
-  __shared__ __attribute__((aligned(16))) char smem[2 * 16384 + MAX_KT * 8];
-  uint32_t (*s_valid)[2] = reinterpret_cast<uint32_t (*)[2]>(smem + 2 * 16384);
-  const int tid = threadIdx.x, lane = tid & 63, hh = lane >> 5, lq = lane & 31;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  int tile, h, b;
-  attn_block_coords(p, p.Lq, tile, h, b);
-  int Lq = p.Lq, L = p.Lk;                        // L: keys
-  size_t qbase = (size_t)b * Lq, rowbase = (size_t)b * L;
-  if (p.cu) {                                     // packed rows: this sequence's own length and first row
-    const int s0 = p.cu[b];
-    Lq = L = p.cu[b + 1] - s0;
-    qbase = rowbase = (size_t)s0;
-    if (tile * 128 >= Lq) return;                 // block-uniform, before any barrier
-  }
-  const int q0 = tile * 128 + wave * 32;
-  const bool active = q0 < Lq;
-  const int q = q0 + lq;
-
-  const __amdgpu_buffer_rsrc_t rsK = ia_rsrc(p.k, p.kv_bytes);
-  const __amdgpu_buffer_rsrc_t rsV = ia_rsrc(p.v, p.kv_bytes);
-
-  bf16x8 qf[4];
-  float m_ref = 0.f, l_run = 0.f;
-  f32x16 o0 = zero16(), o1 = zero16();
-  const int nkt = (L + 63) >> 6;
-  const uint32_t rk = DROPOUT ? ia_rng_row(p.seed, (uint32_t)(b * p.nh + h), (uint32_t)q) : 0u;      // row key of this lane's query
-  auto prefetch = [&](int buf, int kt) {
-    if (kt < nkt) {
-      char* nb = smem + buf * 16384;
-      stage64<false>(rsK, nb, rowbase + kt * 64, L - kt * 64, p.ld_kv, h * 64, tid, wave);
-      stage64<true>(rsV, nb + 8192, rowbase + kt * 64, L - kt * 64, p.ld_kv, h * 64, tid, wave);
-    }
-  };
-  auto compute = [&](auto BUF, int kt) {
-    if (active) {
-      const uint32_t valid_lo = __builtin_amdgcn_readfirstlane(s_valid[kt][0]);
-      const uint32_t valid_hi = __builtin_amdgcn_readfirstlane(s_valid[kt][1]);
-      // a tile with no attendable key contributes nothing
-      if ((valid_lo | valid_hi) != 0u)
-        fwd_tile<decltype(BUF)::value, DROPOUT>(p, smem, qf, valid_lo, valid_hi, m_ref, l_run, o0, o1, lane, q, kt, rk);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  };
-  // this wave's 32 query rows travel through its 4 KiB of the second ring slot (free until tile 1 is prefetched after the barrier)
-  char* qslot = smem + 16384 + wave * 4096;
-  stage_rows32(ia_rsrc(p.q, p.q_bytes), qslot, qbase + q0, Lq - q0, p.ld_q, h * 64, lane);
-  prefetch(0, 0);
-  build_valid_table(p, s_valid, rowbase, L, lane, wave);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-  for (int kb = 0; kb < 4; ++kb) qf[kb] = frag_b128(qslot, lq, kb * 2 + hh);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __syncthreads();
-  for (int kt = 0; kt < nkt; kt += 2) {
-    prefetch(1, kt + 1);
-    compute(std::integral_constant<int, 0>{}, kt);
-    if (kt + 1 < nkt) {
-      prefetch(0, kt + 2);
-      compute(std::integral_constant<int, 1>{}, kt + 1);
-    }
-  }
-  if (!active) return;
-  const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-  const float inv = l_tot > 0.f ? p.inv_keep / l_tot : 0.f;
-  // a row without any attendable key (l_tot == 0): lse2 = 0, not -inf -- the backward forms exp2(s - lse2) with s = -1e30 there
-  if (q < Lq && hh == 0 && p.lse2) p.lse2[((size_t)b * p.nh + h) * p.Lq + q] = l_tot > 0.f ? m_ref + __builtin_amdgcn_logf(l_tot) : 0.f;
-  // the K/V ring is free after the loop's last barrier: wave-private staging slots at its start
-  store_block_rows(smem + wave * EPI_SLOT, o0, o1, inv, false, p.out + (qbase + q0) * p.ld_o + h * 64, p.ld_o, Lq - q0, lane);
-}
-
-// ------------------------------------------------------------------------------------------ forward, round 3
-// Same arithmetic and tile geometry (4 waves x 32 queries, 64-key tiles, S^T orientation) as attn_fwd_kernel above, rebuilt around
-// what tools/abl/issue_model.hip and the PMC passes of round 3 measured on an MI355X (profiles/r03_issue_model.txt, r03_pmc_mfma.csv):
+// 4 waves x 32 queries (QB = 1), 64-key tiles, S^T orientation (header comment), built around what tools/abl/issue_model.hip and the
+// PMC passes of round 3 measured on an MI355X (profiles/r03_issue_model.txt, r03_pmc_mfma.csv):
 // at head dim 64 the kernel is bound by instruction ISSUE -- the waves of a SIMD spent their time issuing ~155 VALU + ~90 SALU
 // instructions per 16 MFMAs -- so the loop is stripped to what the arithmetic needs:
 //  * softmax = 32 exp2 + 16 packed adds + 16 packed converts per tile.  The query fragments are pre-scaled by scale*log2(e) once per
@@ -434,17 +230,12 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs p) {
 //  * the DMA of tile t+2 is issued at the top of tile t and only K(t+1) is waited for there (counted vmcnt), one raw s_barrier per
 //    tile; QB = 1 (32 queries per wave): 48 KiB of LDS and <= 168 VGPRs, three workgroups per CU; QB = 2 (64 queries per wave, half
 //    the K / V traffic per MFMA): 64 KiB and <= 251 VGPRs, two per CU -- launch_fwd picks by how full the last 256-query block is.
-#ifndef IA_F3_PRESCALE
-#define IA_F3_PRESCALE 1     // 1: Q fragments carry scale * log2(e) (one more bf16 rounding of q, no multiply per score); 0: exp2(s * sc)
-#endif
 namespace fwd3 {
-constexpr bool PRESCALE = IA_F3_PRESCALE != 0;
 // LDS: K0 K1 | V0 V1 | K2 V2 | valid-key table.  Q is staged in K2 + V2 (first filled behind the first barrier), the epilogue rows in
 // K0.. (behind a last barrier).
 constexpr int k_slot(int s) { return s == 2 ? 32768 : s * 8192; }
 constexpr int v_slot(int s) { return s == 2 ? 40960 : 16384 + s * 8192; }
 constexpr int Q_OFF = 32768, EPI_OFF = 0, TAB_OFF = 49152, SMEM = TAB_OFF + MAX_KT * 8;
-constexpr float L_HI = 1.1529215e18f;                                             // 2^60
 constexpr uint32_t L_LO_BITS = 0x0D800000u, L_HI_BITS = 0x5D800000u;              // bits of 2^-100, 2^60
 constexpr float NEG_BIG = -1e30f;
 constexpr uint32_t NEG_BIG_BF16 = 0xF14Au;                                        // bf16(-1e30)
@@ -525,10 +316,11 @@ IA_DEV uint32_t drop_pair(uint32_t w, uint32_t h, uint32_t thr1) {
   return d;
 }
 
-// p = exp2(s [* sc]) in place
-IA_DEV void exp_block(f32x16& s, float sc) {
+// p = exp2(s) in place.  (The second parameter is unused: without it hipcc numbers two registers of attn_fwd3_kernel differently, and
+// the prune that folded the scale away kept the device code identical, tools/cmp_kernel_asm.py.)
+IA_DEV void exp_block(f32x16& s, float) {
 #pragma unroll
-  for (int r = 0; r < 16; ++r) s[r] = __builtin_amdgcn_exp2f(PRESCALE ? s[r] : s[r] * sc);
+  for (int r = 0; r < 16; ++r) s[r] = __builtin_amdgcn_exp2f(s[r]);
 }
 // The block's probabilities as the B fragments of its two PV k-steps (bf16), and this lane's part of the row sum taken from the
 // ROUNDED values (v_dot2c_f32_bf16 against packed ones, exact in fp32): O = sum(p^ v) / sum(p^) is then a convex combination of the v
@@ -551,11 +343,9 @@ IA_DEV float pack_sum(bf16x8& pa, bf16x8& pb, const f32x16& s) {
 // Rare: a lane's row sum left [2^-100, 2^60] (or is not finite) at this block.  The block's scores are recomputed (its K fragments are
 // still in their registers), the reference moves to the larger of the block's maximum and the running log-sum-exp, everything
 // accumulated so far follows; `other`: scores of the tile's second block, already formed against the old reference (or null).
-// sc: what exp2's argument is multiplied by (1 with pre-scaled queries); m_ref lives in the accumulators' units.
+// m_ref lives in the accumulators' units (log2 domain: the query fragments carry scale * log2 e).
 IA_DEV void rebase(f32x16& s, f32x16* other, f32x16& o0, f32x16& o1, Row& row, const bf16x8& k0, const bf16x8& k1, const bf16x8& k2,
-                   const bf16x8& k3, const bf16x8 (&qf)[4], uint32_t valid, int lane, float sc) {
-  if (PRESCALE) sc = 1.f;
-  const float inv_sc = 1.f / sc;
+                   const bf16x8& k3, const bf16x8 (&qf)[4], uint32_t valid, int lane) {
   qk_block(s, k0, k1, k2, k3, qf, false, (lane & 32) ? 0u : 0x3F80u, valid, lane);      // reference 0
   float tm = NEG_BIG;
 #pragma unroll
@@ -564,17 +354,17 @@ IA_DEV void rebase(f32x16& s, f32x16* other, f32x16& o0, f32x16& o1, Row& row, c
   const float l_prev = row.l_run + swap32(row.l_run);
   const bool have_prev = l_prev > 0.f, have_blk = tm > 0.5f * NEG_BIG;
   float m_new = row.m_ref;
-  if (have_prev) m_new = row.m_ref + __builtin_amdgcn_logf(l_prev) * inv_sc;      // v_log_f32 = log2
+  if (have_prev) m_new = row.m_ref + __builtin_amdgcn_logf(l_prev);      // v_log_f32 = log2
   if (have_blk) m_new = have_prev ? fmaxf(m_new, tm) : tm;
   m_new = bf2f(f2bf(m_new));
   const float shift = row.m_ref - m_new;
-  const float alpha = have_prev ? __builtin_amdgcn_exp2f(shift * sc) : 0.f;
+  const float alpha = have_prev ? __builtin_amdgcn_exp2f(shift) : 0.f;
   row.m_ref = m_new;
   row.refw = (lane & 32) ? 0u : (0x3F80u | ((uint32_t)__builtin_bit_cast(uint16_t, f2bf(-m_new)) << 16));
   row.l_run *= alpha;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    s[r] = __builtin_amdgcn_exp2f((s[r] - m_new) * sc);
+    s[r] = __builtin_amdgcn_exp2f(s[r] - m_new);
     o0[r] *= alpha; o1[r] *= alpha;
   }
   if (other) {
@@ -597,7 +387,7 @@ __global__ __launch_bounds__(256, QB == 1 ? 3 : 2) void attn_fwd3_kernel(AttnArg
   const int tid = threadIdx.x, lane = tid & 63, hh = lane >> 5, lq = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   int tile, h, b;
-  attn_block_coords_n(p, p.Lq, ROWS, tile, h, b);
+  attn_block_coords(p, (p.Lq + ROWS - 1) / ROWS, tile, h, b);
   int Lq = p.Lq, L = p.Lk;
   size_t qbase = (size_t)b * Lq, rowbase = (size_t)b * L;
   if (p.cu) {
@@ -661,7 +451,7 @@ __global__ __launch_bounds__(256, QB == 1 ? 3 : 2) void attn_fwd3_kernel(AttnArg
     for (int kb = 0; kb < 4; ++kb) {
       const bf16x8 raw = frag_b128(smem + (qb ? QX_OFF : Q_OFF) + wave * 4096, lq, kb * 2 + hh);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) qf[qb][kb][j] = (PRESCALE && !p.q_prescaled) ? f2bf(bf2f(raw[j]) * p.sc) : raw[j];
+      for (int j = 0; j < 8; ++j) qf[qb][kb][j] = !p.q_prescaled ? f2bf(bf2f(raw[j]) * p.sc) : raw[j];
     }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
@@ -729,7 +519,7 @@ __global__ __launch_bounds__(256, QB == 1 ? 3 : 2) void attn_fwd3_kernel(AttnArg
       if (__builtin_expect(__ballot(__builtin_bit_cast(uint32_t, tot) - L_LO_BITS > L_HI_BITS - L_LO_BITS) != 0ull, 0)) {
         if (plain_b) valid_b = __builtin_amdgcn_readfirstlane(s_valid[t][blk]);
         rebase(sc, blk == 0 ? &s[qb][1] : nullptr, o[qb][0], o[qb][1], row[qb], kf[blk], kf[2 + blk], kf[4 + blk], kf[6 + blk], qf[qb], valid_b,
-               lane, p.sc);
+               lane);
         rs = pack_sum(pf[qb][0], pf[qb][1], sc);
         has_ref = true;
       }
@@ -790,185 +580,15 @@ __global__ __launch_bounds__(256, QB == 1 ? 3 : 2) void attn_fwd3_kernel(AttnArg
     const float inv = l_tot > 0.f ? p.inv_keep / l_tot : 0.f;
     if (qq0 + lq < Lq && hh == 0 && p.lse2)
       p.lse2[((size_t)b * p.nh + h) * p.Lq + qq0 + lq] =      // no attendable key (l_tot == 0): 0, not -inf (the backward's exp2(s - lse2))
-          l_tot > 0.f ? row[qb].m_ref * (PRESCALE ? 1.f : p.sc) + __builtin_amdgcn_logf(l_tot) : 0.f;
+          l_tot > 0.f ? row[qb].m_ref + __builtin_amdgcn_logf(l_tot) : 0.f;
     store_block_rows(smem + EPI_OFF + (wave * QB + qb) * EPI_SLOT, o[qb][0], o[qb][1], inv, false, p.out + (qbase + qq0) * p.ld_o + h * 64, p.ld_o,
                      Lq - qq0, lane);
   }
 }
 
 // ------------------------------------------------------------------------------------- backward: dQ
-// One 64-key tile for this wave's 32 queries: dQ^T += K^T dS^T with dS^T = P^T (dP^T - delta) (the softmax scale is
-// applied once, when dQ is stored).
-template <bool DROPOUT>
-IA_DEV void dq_tile(const AttnArgs& p, const char* sK, const bf16x8 (&qf)[4], const bf16x8 (&gf)[4], uint32_t valid_lo,
-                    uint32_t valid_hi, float lse, float dlt, f32x16& dq0, f32x16& dq1, int lane, int q, int kt, uint32_t rk) {
-  const int hh = lane >> 5, lq = lane & 31;
-  const char* sKt = sK + 8192;
-  const char* sV = sK + 16384;
-  f32x16 s0 = zero16(), s1 = zero16(), dp0 = zero16(), dp1 = zero16();
-#pragma unroll
-  for (int kb = 0; kb < 4; ++kb) {
-    const bf16x8 k0 = frag_b128(sK, lq, kb * 2 + hh);
-    const bf16x8 k1 = frag_b128(sK, 32 + lq, kb * 2 + hh);
-    s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k0, qf[kb], s0, 0, 0, 0);
-    s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k1, qf[kb], s1, 0, 0, 0);
-    const bf16x8 v0 = frag_b128(sV, lq, kb * 2 + hh);
-    const bf16x8 v1 = frag_b128(sV, 32 + lq, kb * 2 + hh);
-    dp0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(v0, gf[kb], dp0, 0, 0, 0);
-    dp1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(v1, gf[kb], dp1, 0, 0, 0);
-  }
-  const uint32_t kb0 = lds_addr(sKt) + tr_lane_off(lane, 0), kb1 = lds_addr(sKt) + tr_lane_off(lane, 32);
-  TrPair ka, kb_;
-  tr_issue<0>(ka, kb0, kb1);
-  tr_issue<16>(kb_, kb0, kb1);
-  if ((valid_lo & valid_hi) != 0xFFFFFFFFu) {   // wave-uniform
-    asm volatile("" ::: "memory");   // keeps hipcc from flattening this branch into 64 always-executed selects
-    const uint32_t vlo = hh ? valid_lo >> 4 : valid_lo, vhi = hh ? valid_hi >> 4 : valid_hi;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int bit = (r & 3) + 8 * (r >> 2);
-      if (!((vlo >> bit) & 1)) s0[r] = -INFINITY;
-      if (!((vhi >> bit) & 1)) s1[r] = -INFINITY;
-    }
-  }
-  const float neg_lse = -lse;
-  const uint32_t tile_c = (uint32_t)(kt * 32) * IA_RNG_PAIR_C + (uint32_t)(2 * hh) * IA_RNG_PAIR_C;      // as in fwd_tile
-#pragma unroll
-  for (int r = 0; r < 16; r += 2) {
-    uint32_t ra = 0xFFFFFFFFu, rb = 0xFFFFFFFFu;       // one draw per pair of neighbouring keys (r, r+1)
-    if (DROPOUT) {
-      constexpr uint32_t C = IA_RNG_PAIR_C;
-      const uint32_t imm = (uint32_t)(((r & 3) >> 1) + 4 * (r >> 2)) * C;
-      ra = ia_rng_pair(rk, tile_c + imm);
-      rb = ia_rng_pair(rk, tile_c + imm + 16u * C);
-    }
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const float pa = __builtin_amdgcn_exp2f(__builtin_fmaf(s0[r + e], p.sc, neg_lse));
-      const float pb = __builtin_amdgcn_exp2f(__builtin_fmaf(s1[r + e], p.sc, neg_lse));
-      float da = dp0[r + e], db = dp1[r + e];
-      if (DROPOUT) {
-        da = ((e ? ra >> 16 : ra & 0xFFFFu) >= p.thr16) ? da * p.inv_keep : 0.f;
-        db = ((e ? rb >> 16 : rb & 0xFFFFu) >= p.thr16) ? db * p.inv_keep : 0.f;
-      }
-      s0[r + e] = pa * (da - dlt);
-      s1[r + e] = pb * (db - dlt);
-    }
-  }
-  bf16x8 sf[4];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    sf[0][j] = f2bf(s0[j]); sf[1][j] = f2bf(s0[8 + j]);
-    sf[2][j] = f2bf(s1[j]); sf[3][j] = f2bf(s1[8 + j]);
-  }
-  tr_wait<4>(ka);
-  dq0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka.a0(), sf[0], dq0, 0, 0, 0);
-  dq1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka.a1(), sf[0], dq1, 0, 0, 0);
-  TrPair kc, kd;
-  tr_issue<32>(kc, kb0, kb1);
-  tr_wait<4>(kb_);
-  dq0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kb_.a0(), sf[1], dq0, 0, 0, 0);
-  dq1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kb_.a1(), sf[1], dq1, 0, 0, 0);
-  tr_issue<48>(kd, kb0, kb1);
-  tr_wait<4>(kc);
-  dq0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kc.a0(), sf[2], dq0, 0, 0, 0);
-  dq1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kc.a1(), sf[2], dq1, 0, 0, 0);
-  tr_wait<0>(kd);
-  dq0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kd.a0(), sf[3], dq0, 0, 0, 0);
-  dq1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kd.a1(), sf[3], dq1, 0, 0, 0);
-}
-
-template <bool DROPOUT>
-__global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnArgs p) {
-  // per buffer: K (b128 layout) | K (transpose-read layout) | V (b128 layout) = 24 KiB; then the valid-key table
-  // + 24 KiB: the prologue stages 12 KiB of q / dO / o rows per wave in the 48 KiB behind ring slot 0
-  __shared__ __attribute__((aligned(16))) char smem[3 * 24576 + MAX_KT * 8];
-  uint32_t (*s_valid)[2] = reinterpret_cast<uint32_t (*)[2]>(smem + 3 * 24576);
-  const int tid = threadIdx.x, lane = tid & 63, hh = lane >> 5, lq = lane & 31;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  int tile, h, b;
-  attn_block_coords(p, p.Lq, tile, h, b);
-  int Lq = p.Lq, L = p.Lk;                        // L: keys
-  size_t qbase = (size_t)b * Lq, rowbase = (size_t)b * L;
-  if (p.cu) {                                     // packed rows: this sequence's own length and first row
-    const int s0 = p.cu[b];
-    Lq = L = p.cu[b + 1] - s0;
-    qbase = rowbase = (size_t)s0;
-    if (tile * 128 >= Lq) return;                 // block-uniform, before any barrier
-  }
-  const int q0 = tile * 128 + wave * 32;
-  const bool active = q0 < Lq;
-  const int q = q0 + lq;
-  const int qc = q < Lq ? q : Lq - 1;
-  const __amdgpu_buffer_rsrc_t rsK = ia_rsrc(p.k, p.kv_bytes);
-  const __amdgpu_buffer_rsrc_t rsV = ia_rsrc(p.v, p.kv_bytes);
-  const uint32_t rk = DROPOUT ? ia_rng_row(p.seed, (uint32_t)(b * p.nh + h), (uint32_t)q) : 0u;      // row key of this lane's query
-  const int nkt = (L + 63) >> 6;
-
-  // One memory round trip for the whole prologue: this wave's q / dO / o rows (wave-private 4 KiB slots behind ring slot 0), the
-  // first key tile, the saved log-sum-exp and the mask bytes are all requested before the single wait.
-  char* rslot = smem + 24576 + wave * 12288;
-  stage_rows32(ia_rsrc(p.q, p.q_bytes), rslot, qbase + q0, Lq - q0, p.ld_q, h * 64, lane);
-  stage_rows32(ia_rsrc(p.d_o, p.o_bytes), rslot + 4096, qbase + q0, Lq - q0, p.ld_o, h * 64, lane);
-  stage_rows32(ia_rsrc(p.o, p.o_bytes), rslot + 8192, qbase + q0, Lq - q0, p.ld_o, h * 64, lane);
-  stage64<false>(rsK, smem, rowbase, L, p.ld_kv, h * 64, tid, wave);
-  stage64<true>(rsK, smem + 8192, rowbase, L, p.ld_kv, h * 64, tid, wave);
-  stage64<false>(rsV, smem + 16384, rowbase, L, p.ld_kv, h * 64, tid, wave);
-  const size_t sidx = ((size_t)b * p.nh + h) * p.Lq + qc;
-  const float lse = p.lse2[sidx];
-  build_valid_table(p, s_valid, rowbase, L, lane, wave);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  bf16x8 qf[4], gf[4];
-  // delta = rowsum(dO * O) of this lane's query: each lane of the pair (lane, lane^32) holds half of the 64 columns.
-  // Written out for the dK/dV kernel, which runs after this one on the same stream.
-  float dlt = 0.f;
-#pragma unroll
-  for (int kb = 0; kb < 4; ++kb) {
-    qf[kb] = frag_b128(rslot, lq, kb * 2 + hh);
-    gf[kb] = frag_b128(rslot + 4096, lq, kb * 2 + hh);
-    const bf16x8 ov = frag_b128(rslot + 8192, lq, kb * 2 + hh);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) dlt += bf2f(ov[j]) * bf2f(gf[kb][j]);
-  }
-  dlt += __shfl_xor(dlt, 32, 64);
-  if (active && hh == 0 && q < Lq) p.delta[sidx] = dlt;
-  f32x16 dq0 = zero16(), dq1 = zero16();
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __syncthreads();
-
-  for (int kt = 0; kt < nkt; ++kt) {
-    const int buf = kt & 1;
-    if (kt + 1 < nkt) {
-      char* nb = smem + (buf ^ 1) * 24576;
-      const size_t r0 = rowbase + (kt + 1) * 64; const int nv = L - (kt + 1) * 64;
-      stage64<false>(rsK, nb, r0, nv, p.ld_kv, h * 64, tid, wave);
-      stage64<true>(rsK, nb + 8192, r0, nv, p.ld_kv, h * 64, tid, wave);
-      stage64<false>(rsV, nb + 16384, r0, nv, p.ld_kv, h * 64, tid, wave);
-    }
-    if (active) {
-      const uint32_t valid_lo = __builtin_amdgcn_readfirstlane(s_valid[kt][0]);
-      const uint32_t valid_hi = __builtin_amdgcn_readfirstlane(s_valid[kt][1]);
-      if ((valid_lo | valid_hi) != 0u)
-        dq_tile<DROPOUT>(p, smem + buf * 24576, qf, gf, valid_lo, valid_hi, lse, dlt, dq0, dq1, lane, q, kt, rk);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  }
-  float* cs_lds = p.cs_part ? reinterpret_cast<float*>(smem + 4 * EPI_SLOT) + wave * 64 : nullptr;      // behind the four store slots
-  if (!active && !cs_lds) return;
-  if (active) store_block_rows(smem + wave * EPI_SLOT, dq0, dq1, p.scale, false, p.dq + (qbase + q0) * p.ld_dq + h * 64, p.ld_dq, Lq - q0, lane, cs_lds);
-  else zero_cs_row(cs_lds, lane);
-  if (cs_lds) {           // workgroup-uniform: one row of the partial-sum matrix per workgroup
-    __syncthreads();
-    if (wave == 0) {
-      const float* c = reinterpret_cast<const float*>(smem + 4 * EPI_SLOT);
-      p.cs_part[(size_t)(b * ((p.Lq + 127) >> 7) + tile) * (3 * p.nh * 64) + h * 64 + lane] = (c[lane] + c[64 + lane]) + (c[128 + lane] + c[192 + lane]);
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------- backward, round 3: dQ
-// The round-2 kernel above, rebuilt like the forward (issue-bound at head dim 64, so the loop carries only what the arithmetic needs):
+// A workgroup owns 128 queries (S^T orientation); built like the forward (issue-bound at head dim 64, so the loop carries only what
+// the arithmetic needs):
 //  * S^T = K (Q scale log2e)^T - lse and dP^T - delta come out of the matrix pipe: the first MFMA of each chain takes a 16-register
 //    block holding -lse / -delta of the lane's query as its C operand (both are constants of the whole kernel), so P = exp2(acc) and
 //    dS = P * acc': 32 exp2 + 32 multiplies + 16 packed converts per 24 MFMAs; the query fragments are pre-scaled exactly as in the
@@ -983,8 +603,8 @@ using namespace fwd3;
 // One LDS image of a [64 rows][64 bf16] tile that BOTH read forms take without bank conflicts: the 16-byte chunk of row r is XORed
 // with swz_u(r).  ds_read_b128 (a lane group = 16 rows of one column chunk) needs 8 different values over the even (and the odd)
 // rows of its group; ds_read_b64_tr_b16 (a lane group = 4 rows x 32 bytes) needs rows r and r+2 to differ above bit 0.  With
-// x = (r >> 1) & 7, swz_u = ((x & 1) << 2) | (x >> 1) does both.  The round-2 kernels kept two copies of K (dQ kernel) and of Q and dO
-// (dK/dV kernel) in different layouts: a third / a half of their LDS-DMA traffic.
+// x = (r >> 1) & 7, swz_u = ((x & 1) << 2) | (x >> 1) does both.  (One copy per read form, as the first kernels kept them,
+// costs a third (dQ kernel) / a half (dK/dV kernel) more LDS-DMA traffic.)
 IA_DEV int swz_u(int row) { const int x = (row >> 1) & 7; return ((x & 1) << 2) | (x >> 1); }
 // transpose-read lane offset inside such a tile (rows 0..7 of the 16-row step; rows 8..15 sit at (this ^ 32) + 1024)
 IA_DEV uint32_t tr_lane_off_u(int lane, int col0) {
@@ -1025,7 +645,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd3_dq_kernel(AttnArgs p) {
   const int tid = threadIdx.x, lane = tid & 63, hh = lane >> 5, lq = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   int tile, h, b;
-  attn_block_coords(p, p.Lq, tile, h, b);
+  attn_block_coords(p, (p.Lq + 127) >> 7, tile, h, b);
   int Lq = p.Lq, L = p.Lk;
   size_t qbase = (size_t)b * Lq, rowbase = (size_t)b * L;
   if (p.cu) {
@@ -1089,7 +709,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd3_dq_kernel(AttnArgs p) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       dlt += bf2f(ov[j]) * bf2f(gf[kb][j]);
-      qf[kb][j] = (PRESCALE && !p.q_prescaled) ? f2bf(bf2f(raw[j]) * p.sc) : raw[j];
+      qf[kb][j] = !p.q_prescaled ? f2bf(bf2f(raw[j]) * p.sc) : raw[j];
     }
   }
   dlt += swap32(dlt);
@@ -1099,7 +719,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd3_dq_kernel(AttnArgs p) {
   else if (active && hh == 0 && q < Lq) p.delta[sidx] = dlt;       // for the dK/dV kernel, which runs behind this one on the stream
   f32x16 nl, nd;                                              // C operands: -lse, -delta (dropout: the mask sits between dP and delta)
 #pragma unroll
-  for (int r = 0; r < 16; ++r) { nl[r] = PRESCALE ? -lse : -lse / p.sc; nd[r] = DROPOUT ? 0.f : -dlt; }
+  for (int r = 0; r < 16; ++r) { nl[r] = -lse; nd[r] = DROPOUT ? 0.f : -dlt; }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   int nkt = nkt_all;
@@ -1186,16 +806,16 @@ __global__ __launch_bounds__(256, 2) void attn_bwd3_dq_kernel(AttnArgs p) {
         float a_lo, a_hi, b_lo, b_hi;
         keep_pair(ia_rng_pair(rk, tile_c + imm), thr1, a_lo, a_hi);
         keep_pair(ia_rng_pair(rk, tile_c + imm + 16u * C), thr1, b_lo, b_hi);
-        s0[r] = __builtin_amdgcn_exp2f(PRESCALE ? s0[r] : s0[r] * p.sc) * __builtin_fmaf(dp0[r] * a_lo, p.inv_keep, -dlt);
-        s0[r + 1] = __builtin_amdgcn_exp2f(PRESCALE ? s0[r + 1] : s0[r + 1] * p.sc) * __builtin_fmaf(dp0[r + 1] * a_hi, p.inv_keep, -dlt);
-        s1[r] = __builtin_amdgcn_exp2f(PRESCALE ? s1[r] : s1[r] * p.sc) * __builtin_fmaf(dp1[r] * b_lo, p.inv_keep, -dlt);
-        s1[r + 1] = __builtin_amdgcn_exp2f(PRESCALE ? s1[r + 1] : s1[r + 1] * p.sc) * __builtin_fmaf(dp1[r + 1] * b_hi, p.inv_keep, -dlt);
+        s0[r] = __builtin_amdgcn_exp2f(s0[r]) * __builtin_fmaf(dp0[r] * a_lo, p.inv_keep, -dlt);
+        s0[r + 1] = __builtin_amdgcn_exp2f(s0[r + 1]) * __builtin_fmaf(dp0[r + 1] * a_hi, p.inv_keep, -dlt);
+        s1[r] = __builtin_amdgcn_exp2f(s1[r]) * __builtin_fmaf(dp1[r] * b_lo, p.inv_keep, -dlt);
+        s1[r + 1] = __builtin_amdgcn_exp2f(s1[r + 1]) * __builtin_fmaf(dp1[r + 1] * b_hi, p.inv_keep, -dlt);
       }
     } else {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        s0[r] = __builtin_amdgcn_exp2f(PRESCALE ? s0[r] : s0[r] * p.sc) * dp0[r];
-        s1[r] = __builtin_amdgcn_exp2f(PRESCALE ? s1[r] : s1[r] * p.sc) * dp1[r];
+        s0[r] = __builtin_amdgcn_exp2f(s0[r]) * dp0[r];
+        s1[r] = __builtin_amdgcn_exp2f(s1[r]) * dp1[r];
       }
     }
     bf16x8 sf[4];
@@ -1253,7 +873,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd3_delta_kernel(AttnArgs p) {
   const int tid = threadIdx.x, lane = tid & 63, hh = lane >> 5, lq = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   int tile, h, b;
-  attn_block_coords(p, p.Lq, tile, h, b);
+  attn_block_coords(p, (p.Lq + 127) >> 7, tile, h, b);
   int Lq = p.Lq, L = p.Lk;
   size_t qbase = (size_t)b * Lq, rowbase = (size_t)b * L;
   if (p.cu) {
@@ -1310,11 +930,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd3_delta_kernel(AttnArgs p) {
     const bf16x8 raw = frag_b128(rq, lq, kb * 2 + hh);
     gf[kb] = frag_b128(rg, lq, kb * 2 + hh);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) qf[kb][j] = (PRESCALE && !p.q_prescaled) ? f2bf(bf2f(raw[j]) * p.sc) : raw[j];
+    for (int j = 0; j < 8; ++j) qf[kb][j] = !p.q_prescaled ? f2bf(bf2f(raw[j]) * p.sc) : raw[j];
   }
   f32x16 nl, nd;                                              // C operands: -lse, 0
 #pragma unroll
-  for (int r = 0; r < 16; ++r) { nl[r] = PRESCALE ? -lse : -lse / p.sc; nd[r] = 0.f; }
+  for (int r = 0; r < 16; ++r) { nl[r] = -lse; nd[r] = 0.f; }
   float dsum = 0.f;                                           // this lane's part of sum_k P dP of its query (its 16 key rows of every block)
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
@@ -1386,17 +1006,17 @@ __global__ __launch_bounds__(256, 2) void attn_bwd3_delta_kernel(AttnArgs p) {
         float a_lo, a_hi, b_lo, b_hi;
         keep_pair(ia_rng_pair(rk, tile_c + imm), thr1, a_lo, a_hi);
         keep_pair(ia_rng_pair(rk, tile_c + imm + 16u * C), thr1, b_lo, b_hi);
-        dsum += __builtin_amdgcn_exp2f(PRESCALE ? s0[r] : s0[r] * p.sc) * (dp0[r] * a_lo * p.inv_keep);
-        dsum += __builtin_amdgcn_exp2f(PRESCALE ? s0[r + 1] : s0[r + 1] * p.sc) * (dp0[r + 1] * a_hi * p.inv_keep);
-        dsum += __builtin_amdgcn_exp2f(PRESCALE ? s1[r] : s1[r] * p.sc) * (dp1[r] * b_lo * p.inv_keep);
-        dsum += __builtin_amdgcn_exp2f(PRESCALE ? s1[r + 1] : s1[r + 1] * p.sc) * (dp1[r + 1] * b_hi * p.inv_keep);
+        dsum += __builtin_amdgcn_exp2f(s0[r]) * (dp0[r] * a_lo * p.inv_keep);
+        dsum += __builtin_amdgcn_exp2f(s0[r + 1]) * (dp0[r + 1] * a_hi * p.inv_keep);
+        dsum += __builtin_amdgcn_exp2f(s1[r]) * (dp1[r] * b_lo * p.inv_keep);
+        dsum += __builtin_amdgcn_exp2f(s1[r + 1]) * (dp1[r + 1] * b_hi * p.inv_keep);
       }
     } else {
       float u0 = 0.f, u1 = 0.f;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        u0 += __builtin_amdgcn_exp2f(PRESCALE ? s0[r] : s0[r] * p.sc) * dp0[r];
-        u1 += __builtin_amdgcn_exp2f(PRESCALE ? s1[r] : s1[r] * p.sc) * dp1[r];
+        u0 += __builtin_amdgcn_exp2f(s0[r]) * dp0[r];
+        u1 += __builtin_amdgcn_exp2f(s1[r]) * dp1[r];
       }
       dsum += u0 + u1;
     }
@@ -1413,167 +1033,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd3_delta_kernel(AttnArgs p) {
   if (active && hh == 0 && q < Lq) p.delta[sidx] = dsum;
 }
 
-// ---------------------------------------------------------------------------------- backward: dK, dV
-// S orientation: rows = queries (accumulator registers), column = key = lane. A column of P / dS only ever reaches
-// that key's dK / dV, so the key mask needs no per-element work: a masked key's outputs are simply stored as zero.
-// Rows past the end of the sequence cost nothing either: their Q, dO, lse and delta arrive zero-filled from the DMA
-// (P = 1, dP = 0, dS = 0).
-template <bool DROPOUT>
-__global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(AttnArgs p) {
-  // per buffer: Q (b128) | Q (transpose-read) | dO (b128) | dO (transpose-read) | lse[64] | delta[64]
-  constexpr int BUF = 32768 + 512;
-  // + 1 KiB: under dropout every wave keeps the 64 row keys (ia_rng_row) of the current query tile in a private 256-byte slot
-  __shared__ __attribute__((aligned(16))) char smem[2 * BUF + 1024];
-  const int tid = threadIdx.x, lane = tid & 63, hh = lane >> 5, lk = lane & 31;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  int tile, h, b;
-  attn_block_coords(p, p.Lk, tile, h, b);
-  int Lq = p.Lq, L = p.Lk;                        // L: keys
-  size_t qbase = (size_t)b * Lq, rowbase = (size_t)b * L;
-  if (p.cu) {
-    const int s0 = p.cu[b];
-    Lq = L = p.cu[b + 1] - s0;
-    qbase = rowbase = (size_t)s0;
-    if (tile * 128 >= L) return;
-  }
-  const int k0 = tile * 128 + wave * 32;
-  const bool active = k0 < L;
-  const int key = k0 + lk;
-  const int kc = key < L ? key : L - 1;
-  const bool key_ok = key < L && (p.mask == nullptr || p.mask[rowbase + kc] != 0);
-
-  const __amdgpu_buffer_rsrc_t rsQ = ia_rsrc(p.q, p.q_bytes);
-  const __amdgpu_buffer_rsrc_t rsG = ia_rsrc(p.d_o, p.o_bytes);
-  const __amdgpu_buffer_rsrc_t rsL = ia_rsrc(p.lse2 + ((size_t)b * p.nh + h) * p.Lq, (uint32_t)Lq * 4u);
-  const __amdgpu_buffer_rsrc_t rsD = ia_rsrc(p.delta + ((size_t)b * p.nh + h) * p.Lq, (uint32_t)Lq * 4u);
-  const uint32_t stream_id = (uint32_t)(b * p.nh + h);
-  // dropout draw of (q, key): key is this lane -> its pair constant and the half of the draw it reads are lane constants
-  const uint32_t pc = pair_c_of(key), ush = (uint32_t)(key & 1) * 16u;
-  uint32_t* const s_rk = reinterpret_cast<uint32_t*>(smem + 2 * BUF) + wave * 64;
-
-  f32x16 dk0 = zero16(), dk1 = zero16(), dv0 = zero16(), dv1 = zero16();
-  const int nqt = (Lq + 63) >> 6;
-  auto stage_all = [&](char* s, int qt) {
-    const size_t r0 = qbase + (size_t)qt * 64; const int nv = Lq - qt * 64;
-    stage64<false>(rsQ, s, r0, nv, p.ld_q, h * 64, tid, wave);
-    stage64<true>(rsQ, s + 8192, r0, nv, p.ld_q, h * 64, tid, wave);
-    stage64<false>(rsG, s + 16384, r0, nv, p.ld_o, h * 64, tid, wave);
-    stage64<true>(rsG, s + 24576, r0, nv, p.ld_o, h * 64, tid, wave);
-    // 64 x fp32 each, one 4-byte-per-lane DMA; out-of-range rows read as zero
-    if (wave == 0) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsL, IA_LDS(s + 32768), 4, (uint32_t)(qt * 64 + lane) * 4u, 0, 0, 0);
-    if (wave == 1) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsD, IA_LDS(s + 32768 + 256), 4, (uint32_t)(qt * 64 + lane) * 4u, 0, 0, 0);
-  };
-  // this wave's 32 key rows of K and V travel through wave-private 4 KiB slots of the second ring slot (free until the loop
-  // prefetches query tile 1 behind the barrier), requested together with query tile 0
-  char* kslot = smem + BUF + wave * 8192;
-  stage_rows32(ia_rsrc(p.k, p.kv_bytes), kslot, rowbase + k0, L - k0, p.ld_kv, h * 64, lane);
-  stage_rows32(ia_rsrc(p.v, p.kv_bytes), kslot + 4096, rowbase + k0, L - k0, p.ld_kv, h * 64, lane);
-  stage_all(smem, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  bf16x8 kf[4], vf[4];
-#pragma unroll
-  for (int kb = 0; kb < 4; ++kb) {
-    kf[kb] = frag_b128(kslot, lk, kb * 2 + hh);
-    vf[kb] = frag_b128(kslot + 4096, lk, kb * 2 + hh);
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __syncthreads();
-
-  for (int qt = 0; qt < nqt; ++qt) {
-    const int buf = qt & 1;
-    if (qt + 1 < nqt) stage_all(smem + (buf ^ 1) * BUF, qt + 1);
-    if (active) {
-      if (DROPOUT) {      // row keys of this tile's 64 queries, one per lane (the wave's LDS operations complete in order: no barrier)
-        s_rk[lane] = ia_rng_row(p.seed, stream_id, (uint32_t)(qt * 64 + lane));
-        __builtin_amdgcn_wave_barrier();
-      }
-      const char* sQ = smem + buf * BUF;
-      const char* sG = sQ + 16384;
-      const uint32_t qt0 = lds_addr(sQ + 8192) + tr_lane_off(lane, 0), qt1 = lds_addr(sQ + 8192) + tr_lane_off(lane, 32);
-      const uint32_t gt0 = lds_addr(sQ + 24576) + tr_lane_off(lane, 0), gt1 = lds_addr(sQ + 24576) + tr_lane_off(lane, 32);
-      const float* sL = reinterpret_cast<const float*>(sQ + 32768);
-      const float* sD = sL + 64;
-      auto sub_tile = [&](auto QS) {
-        constexpr int qs = decltype(QS)::value;
-        const int qb = qt * 64 + qs * 32;     // first query of this 32-row sub tile
-        // S[q][key] = Q K^T ; dP[q][key] = dO V^T   (rows = q in registers, column = key = lane)
-        f32x16 s = zero16(), dp = zero16();
-#pragma unroll
-        for (int kb = 0; kb < 4; ++kb) {
-          const bf16x8 a = frag_b128(sQ, qs * 32 + lk, kb * 2 + hh);
-          s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, kf[kb], s, 0, 0, 0);
-          const bf16x8 g = frag_b128(sG, qs * 32 + lk, kb * 2 + hh);
-          dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(g, vf[kb], dp, 0, 0, 0);
-        }
-        TrPair g0, a0, g1, a1;
-        tr_issue<qs * 32>(g0, gt0, gt1);
-        tr_issue<qs * 32>(a0, qt0, qt1);
-        tr_issue<qs * 32 + 16>(g1, gt0, gt1);
-        tr_issue<qs * 32 + 16>(a1, qt0, qt1);
-        bf16x8 pf[2], sf[2];
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg) {
-          const int qoff = qs * 32 + 8 * rg + 4 * hh;              // 4 consecutive queries
-          const f32x4 ls = *reinterpret_cast<const f32x4*>(sL + qoff);
-          const f32x4 dl = *reinterpret_cast<const f32x4*>(sD + qoff);
-          u32x4 rkq = {0u, 0u, 0u, 0u};
-          if (DROPOUT) rkq = *reinterpret_cast<const u32x4*>(s_rk + qoff);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const int r = rg * 4 + j;
-            const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], p.sc, -ls[j]));
-            float d = dp[r];
-            float pd = pv;
-            if (DROPOUT) {
-              const bool keep = ((ia_rng_pair(rkq[j], pc) >> ush) & 0xFFFFu) >= p.thr16;
-              d = keep ? d * p.inv_keep : 0.f;
-              pd = keep ? pv * p.inv_keep : 0.f;
-            }
-            const float ds = pv * (d - dl[j]);
-            pf[r >> 3][r & 7] = f2bf(pd);
-            sf[r >> 3][r & 7] = f2bf(ds);
-          }
-        }
-        // dV^T[d][key] += dO^T[d][q] P[q][key] ; dK^T[d][key] += Q^T[d][q] dS[q][key]
-        tr_wait<12>(g0);
-        dv0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(g0.a0(), pf[0], dv0, 0, 0, 0);
-        dv1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(g0.a1(), pf[0], dv1, 0, 0, 0);
-        tr_wait<8>(a0);
-        dk0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0.a0(), sf[0], dk0, 0, 0, 0);
-        dk1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0.a1(), sf[0], dk1, 0, 0, 0);
-        tr_wait<4>(g1);
-        dv0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(g1.a0(), pf[1], dv0, 0, 0, 0);
-        dv1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(g1.a1(), pf[1], dv1, 0, 0, 0);
-        tr_wait<0>(a1);
-        dk0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1.a0(), sf[1], dk0, 0, 0, 0);
-        dk1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1.a1(), sf[1], dk1, 0, 0, 0);
-      };
-      sub_tile(std::integral_constant<int, 0>{});
-      if (qt * 64 + 32 < Lq) sub_tile(std::integral_constant<int, 1>{});
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  }
-  float* cs_lds = p.cs_part ? reinterpret_cast<float*>(smem + 8 * EPI_SLOT) + wave * 128 : nullptr;     // behind the eight store slots: dk | dv sums
-  if (!active && !cs_lds) return;
-  if (active) {
-    // a masked key's outputs are zero (its P is not bounded by the saved log-sum-exp, so the accumulators may hold inf / nan)
-    store_block_rows(smem + wave * 2 * EPI_SLOT, dk0, dk1, p.scale, !key_ok, p.dk + (rowbase + k0) * p.ld_dkv + h * 64, p.ld_dkv, L - k0, lane, cs_lds);
-    store_block_rows(smem + (wave * 2 + 1) * EPI_SLOT, dv0, dv1, 1.f, !key_ok, p.dv + (rowbase + k0) * p.ld_dkv + h * 64, p.ld_dkv, L - k0, lane,
-                     cs_lds ? cs_lds + 64 : nullptr);
-  } else { zero_cs_row(cs_lds, lane); zero_cs_row(cs_lds + 64, lane); }
-  if (cs_lds) {
-    __syncthreads();
-    if (wave < 2) {         // wave 0: the dk columns, wave 1: the dv columns
-      const float* c = reinterpret_cast<const float*>(smem + 8 * EPI_SLOT) + wave * 64;
-      p.cs_part[(size_t)(b * ((p.Lk + 127) >> 7) + tile) * (3 * p.nh * 64) + (1 + wave) * p.nh * 64 + h * 64 + lane] =
-          (c[lane] + c[128 + lane]) + (c[256 + lane] + c[384 + lane]);
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------ backward, round 3: dK, dV
-// attn_bwd_dkv_kernel rebuilt on the same lines as attn_bwd3_dq_kernel.  S orientation (rows = queries in the accumulator registers,
+// ------------------------------------------------------------------------------ backward: dK, dV
+// A workgroup owns 128 keys; built on the same lines as attn_bwd3_dq_kernel.  S orientation (rows = queries in the accumulator registers,
 // column = key = lane), one 32-query sub tile at a time:
 //  * the wave's K / V fragments are negated (round 4: the scale * log2 e sits on the Q tile, rounded in LDS exactly as the forward
 //    rounds its pre-scaled query fragments) and the chains start from the +lse / +delta values of the
@@ -1594,7 +1055,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd3_dkv_kernel(AttnArgs p) {
   const int tid = threadIdx.x, lane = tid & 63, hh = lane >> 5, lk = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   int tile, h, b;
-  attn_block_coords(p, p.Lk, tile, h, b);
+  attn_block_coords(p, (p.Lk + 127) >> 7, tile, h, b);
   int Lq = p.Lq, L = p.Lk;
   size_t qbase = (size_t)b * Lq, rowbase = (size_t)b * L;
   if (p.cu) {
@@ -1666,7 +1127,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd3_dkv_kernel(AttnArgs p) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) { kf[kb][j] = f2bf(-bf2f(kr[j])); vf[kb][j] = f2bf(-bf2f(vr[j])); }
   }
-  const bool scale_q = PRESCALE && !p.q_prescaled;        // q arrives pre-scaled from the QKV projection: nothing to do per tile
+  const bool scale_q = !p.q_prescaled;                    // q arrives pre-scaled from the QKV projection: nothing to do per tile
   if (scale_q) {                                          // query tile 0 (stage 0) is pre-scaled here, see prescale() below
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -1750,7 +1211,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd3_dkv_kernel(AttnArgs p) {
           const f32x4 ls = *reinterpret_cast<const f32x4*>(sL + 8 * rg);
           const f32x4 dl = *reinterpret_cast<const f32x4*>(sL + 64 + 8 * rg);
 #pragma unroll
-          for (int j = 0; j < 4; ++j) { s[rg * 4 + j] = PRESCALE ? ls[j] : ls[j] / sc; dlr[rg * 4 + j] = dl[j]; dp[rg * 4 + j] = DROPOUT ? 0.f : dl[j]; }
+          for (int j = 0; j < 4; ++j) { s[rg * 4 + j] = ls[j]; dlr[rg * 4 + j] = dl[j]; dp[rg * 4 + j] = DROPOUT ? 0.f : dl[j]; }
         }
       }
       bf16x8 xq, xg, yq, yg;                              // Q / dO fragments of even / odd k-steps
@@ -1779,7 +1240,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd3_dkv_kernel(AttnArgs p) {
       }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const float pv = __builtin_amdgcn_exp2f(PRESCALE ? -s[r] : -s[r] * sc);      // exp2(s' - lse)
+        const float pv = __builtin_amdgcn_exp2f(-s[r]);      // exp2(s' - lse)
         float pd = pv, nds;
         if (DROPOUT) {
           const uint32_t hsh = ia_rng_pair(rkq[r >> 2][r & 3], pc);
@@ -1826,7 +1287,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd3_dkv_kernel(AttnArgs p) {
   if (!active && !cs_lds) return;
   if (active) {
     // dK = scale sum dS q; the accumulators hold sum (-dS) q' with q' = q scale log2 e
-    store_block_rows(smem + wave * 2 * EPI_SLOT, dk0, dk1, PRESCALE ? -1.f / LOG2E : -p.scale, !key_ok, p.dk + (rowbase + k0) * p.ld_dkv + h * 64, p.ld_dkv,
+    store_block_rows(smem + wave * 2 * EPI_SLOT, dk0, dk1, -1.f / LOG2E, !key_ok, p.dk + (rowbase + k0) * p.ld_dkv + h * 64, p.ld_dkv,
                      L - k0, lane, cs_lds);
     store_block_rows(smem + (wave * 2 + 1) * EPI_SLOT, dv0, dv1, DROPOUT ? p.inv_keep : 1.f, !key_ok, p.dv + (rowbase + k0) * p.ld_dkv + h * 64,
                      p.ld_dkv, L - k0, lane, cs_lds ? cs_lds + 64 : nullptr);
@@ -1860,15 +1321,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd3_dkv_kernel(AttnArgs p) {
 //    exposed.  No global load is issued inside the loop except through LDS-DMA (a register load would drain the in-order VMEM
 //    queue), and every wait on the DMA is a counted vmcnt that is exact or stricter than needed whether or not stores are counted.
 // Deterministic (no atomics).  A masked / out-of-range key gets +1e30 on its column's reference (P = 0 exactly).
-#ifndef IA_FUSED_SWAP
-#define IA_FUSED_SWAP 1      // 1: the second wave of every SIMD runs its part A one step ahead inside an item (below); 0: all waves in step
-#endif
-#ifndef IA_FUSED_ABL
-#define IA_FUSED_ABL 0       // development: timing ablations of the fused backward (tools/abl/run_fused_abl.sh); results are wrong when != 0
-#endif
 namespace bwdf {
 using namespace bwd3;
-constexpr int ABL = IA_FUSED_ABL;
 constexpr int NW = 8, RING = 4;
 // ring slot: Q | dO | O rows of one 32-query block (4 KiB each, unified layout) | lse[32] | 128 B the lse piece's out-of-range lanes
 // zero | delta[32] | dropout row keys[32].  The lse piece is a 64-lane DMA of wave 0 whose lanes 32 .. 63 write zeros behind the 32
@@ -2133,7 +1587,6 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_kernel(AttnArgs p) {
           }
           const uint32_t k0_ = ka0 + so;
           bf16x8 xq, xg, yq, yg;
-          if (!(ABL & 128)) {
           xq = lds_read_b128<SL_Q>(k0_); xg = lds_read_b128<SL_G>(k0_);
           yq = lds_read_b128<SL_Q>(k0_ ^ 32u); yg = lds_read_b128<SL_G>(k0_ ^ 32u);
           asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(xq), "+v"(xg));
@@ -2144,17 +1597,12 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_kernel(AttnArgs p) {
           yq = lds_read_b128<SL_Q>(k0_ ^ 96u); yg = lds_read_b128<SL_G>(k0_ ^ 96u);
           asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(xq), "+v"(xg));
           s = mfma(xq, kf[2], s); dp = mfma(xg, vf[2], dp);
-          }
           const uint32_t a0_ = t0 + so, a1_ = a0_ + t1d, a0x = a0_ ^ 32u, a1x = a1_ ^ 32u;
           TrPair g0, q0, g1, q1;                          // dO^T and Q'^T fragments of the block's two 16-query steps
-          if (!(ABL & 64)) {
           read_tr<SL_G, 0>(g0, a0_, a1_, a0x, a1x);
           read_tr<SL_Q, 0>(q0, a0_, a1_, a0x, a1x);
-          }
-          if (!(ABL & 128)) {
           asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(yq), "+v"(yg));
           s = mfma(yq, kf[3], s); dp = mfma(yg, vf[3], dp);
-          }
           bf16x8 pf[2], sf[2];
           const uint32_t* const rkp = reinterpret_cast<const uint32_t*>(smem + RING_OFF + slot * SLOT + SL_RK) + 4 * hh;
           // probabilities and -dS of 8 accumulator rows (one 16-query MFMA step): HALF = 0 / 1
@@ -2163,10 +1611,9 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_kernel(AttnArgs p) {
 #pragma unroll
             for (int rr = 0; rr < 8; ++rr) {
               const int r = hf * 8 + rr;
-              const float pv = (ABL & 2) ? s[r] : __builtin_amdgcn_exp2f(-s[r]);      // exp2(q' . k - lse)
+              const float pv = __builtin_amdgcn_exp2f(-s[r]);      // exp2(q' . k - lse)
               float pd = pv, nds;
-              if (ABL & 2) nds = dp[r];
-              else if (DROPOUT) {
+              if (DROPOUT) {
                 const int qo = 8 * (r >> 2) + (r & 3);    // this register's query inside the block, minus 4 hh
                 const uint32_t dr = (ia_rng_pair(rkp[qo], pc) >> ush) & 0xFFFFu;
                 const float mk = __builtin_fminf(__builtin_fmaxf((float)((int)dr - (int)thr1), 0.f), 1.f);      // 0 iff dropped
@@ -2180,34 +1627,28 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_kernel(AttnArgs p) {
             }
             // -dS^T to the exchange slot: row = key (this lane), two groups of 4 consecutive queries
             const int xa = xwo + par * XT;
-            if (!(ABL & 8)) {
             *reinterpret_cast<bf16x4*>(smem + (xa ^ (hf * 32))) = bf16x4{sf[hf][0], sf[hf][1], sf[hf][2], sf[hf][3]};
             *reinterpret_cast<bf16x4*>(smem + (xa ^ (hf * 32 + 16))) = bf16x4{sf[hf][4], sf[hf][5], sf[hf][6], sf[hf][7]};
-            }
           };
           half(std::integral_constant<int, 0>{});
           // the second step's fragments are requested only now: the first step's MFMAs run under the second half's exp2 / multiplies
-          if (!(ABL & 64)) {
           read_tr<SL_G, 16>(g1, a0_, a1_, a0x, a1x);
           read_tr<SL_Q, 16>(q1, a0_, a1_, a0x, a1x);
           tr_wait<12>(g0);
           dv0 = mfma(g0.a0(), pf[0], dv0); dv1 = mfma(g0.a1(), pf[0], dv1);
           tr_wait<8>(q0);
           dk0 = mfma(q0.a0(), sf[0], dk0); dk1 = mfma(q0.a1(), sf[0], dk1);
-          }
           half(std::integral_constant<int, 1>{});
-          if (!(ABL & 64)) {
           tr_wait<4>(g1);
           dv0 = mfma(g1.a0(), pf[1], dv0); dv1 = mfma(g1.a1(), pf[1], dv1);
           tr_wait<0>(q1);
           dk0 = mfma(q1.a0(), sf[1], dk0); dk1 = mfma(q1.a1(), sf[1], dk1);
-          } else { dv0[0] += bf2f(pf[0][0]) + bf2f(pf[1][0]); dk0[0] += bf2f(sf[0][0]) + bf2f(sf[1][0]); }
         }
       }
     };
     // ---- the other half of the interval: look-ahead DMA, part C of step g-1, and at an item boundary the epilogue
     auto part_c = [&]() {
-      if (haveA && g >= 1 && !(ABL & 16)) {
+      if (haveA && g >= 1) {
         // the slot of step g-1 is free (every wave passed the barrier behind its part A): block g+3 goes there; the stage is free once
         // every wave has read it, i.e. behind the barrier of the item's first step
         if (cj == 1) { issue_kv(kvn); adv(kvn); }
@@ -2220,7 +1661,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_kernel(AttnArgs p) {
         s16x4 lo[8], hi[8];
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
         // (vbits still belongs to the item of step g-1 here: a new item's part A runs behind this part C)
-        if (!(ABL & 1) && (!p.dead_queries || ((vbits >> pcj) & 1u))) {
+        if (!p.dead_queries || ((vbits >> pcj) & 1u)) {
 #pragma unroll
         for (int k = 0; k < 8; ++k) { lo[k] = tr_read<0>(xr + k * 2 * XT); hi[k] = tr_read<16 * XP>(xr2 + k * 2 * XT); }
 #define IA_DQ_STEP(k, n)                                                                                   \
@@ -2283,7 +1724,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_kernel(AttnArgs p) {
     };
     part_c();
     if (!haveA) break;
-    if (!IA_FUSED_SWAP || grp == 0 || first) part_a(g, first, cj);
+    if (grp == 0 || first) part_a(g, first, cj);
     // ---- the next block: wait for this wave's pieces of it, prepare it, publish everything with the step's barrier
     {
       // pieces issued after the ones waited for: the ring pieces of this and the previous interval (4), plus the 9 stage pieces when
@@ -2295,11 +1736,11 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_kernel(AttnArgs p) {
       int nj = cj + 1;
       Cur nc = cons;
       if (nj == nb) { nj = 0; adv(nc); }
-      if (!(ABL & 4)) prep(nc.it, nj, (g + 1) & (RING - 1));
+      prep(nc.it, nj, (g + 1) & (RING - 1));
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (!(ABL & 32)) __builtin_amdgcn_s_barrier();
-    if (IA_FUSED_SWAP && grp != 0 && !last) part_a(g + 1, false, cj + 1);      // group 1 runs one part A ahead inside an item
+    __builtin_amdgcn_s_barrier();
+    if (grp != 0 && !last) part_a(g + 1, false, cj + 1);      // group 1 runs one part A ahead inside an item
     prev = cons; pcj = cj;
     if (++cj == nb) { cj = 0; adv(cons); }
   }
@@ -2340,68 +1781,81 @@ int fill_args(AttnArgs& a, int B, int nh, int Lq, int Lk, int ld_q, int ld_kv, i
   return IA_OK;
 }
 
-// development switches (round 3): IA_ATTN_FWD=2 / IA_ATTN_BWD=0 run the round-2 kernels for A/B measurements on one box
-int bwd_version() {
-  // bit 0: round-3 dQ kernel, bit 1: round-3 dK/dV kernel, bit 2: the fused one-kernel backward where it applies (L <= 256)
-  static const int v = [] { const char* e = getenv("IA_ATTN_BWD"); return e ? atoi(e) : 7; }();
-  return v;
-}
-template <bool D> void launch_dkv(const AttnArgs& a, dim3 grid, hipStream_t st) {
-  if ((bwd_version() & 2) || a.q_prescaled) hipLaunchKernelGGL(attn_bwd3_dkv_kernel<D>, grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(attn_bwd_dkv_kernel<D>, grid, dim3(256), 0, st, a);
-}
-template <bool D> void launch_dq(const AttnArgs& a, dim3 grid, hipStream_t st) {
-  if ((bwd_version() & 1) || a.q_prescaled) hipLaunchKernelGGL(attn_bwd3_dq_kernel<D>, grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(attn_bwd_dq_kernel<D>, grid, dim3(256), 0, st, a);
-}
 // read on every call (a test / a fine-tuning script may switch it inside one process)
 bool exact_delta_on() { const char* e = getenv("IA_ATTN_EXACT_DELTA"); return e && atoi(e) != 0; }
 // The fused backward serves plain self-attention (one length for queries and keys, padded rows) of 33 .. 256 tokens
 bool fused_applies(const AttnArgs& a) {
-  return (bwd_version() & 4) && !a.exact_delta && a.cu == nullptr && a.Lq == a.Lk && a.Lq > 32 && a.Lq <= 256 && a.delta != nullptr;
+  return !a.exact_delta && a.cu == nullptr && a.Lq == a.Lk && a.Lq > 32 && a.Lq <= 256 && a.delta != nullptr;
 }
-// dQ then dK/dV (the pair of kernels behind every backward entry point that is not served by the fused kernel)
-void launch_pair(AttnArgs& a, dim3 gq, dim3 gk, hipStream_t st) {
-  if (a.exact_delta) {
-    if (a.thr16) hipLaunchKernelGGL(attn_bwd3_delta_kernel<true>, gq, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(attn_bwd3_delta_kernel<false>, gq, dim3(256), 0, st, a);
-    // (the round-3 kernels only: the round-2 dQ kernel knows nothing of the flag)
-    if (a.thr16) { hipLaunchKernelGGL(attn_bwd3_dq_kernel<true>, gq, dim3(256), 0, st, a); hipLaunchKernelGGL(attn_bwd3_dkv_kernel<true>, gk, dim3(256), 0, st, a); }
-    else { hipLaunchKernelGGL(attn_bwd3_dq_kernel<false>, gq, dim3(256), 0, st, a); hipLaunchKernelGGL(attn_bwd3_dkv_kernel<false>, gk, dim3(256), 0, st, a); }
-    return;
-  }
-  if (a.thr16) { launch_dq<true>(a, gq, st); launch_dkv<true>(a, gk, st); }
-  else { launch_dq<false>(a, gq, st); launch_dkv<false>(a, gk, st); }
-}
-void launch_fused(const AttnArgs& a, hipStream_t st) {
+template <bool D> void launch_fused(const AttnArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(attn_key_bits_kernel, dim3(a.B), dim3(64), 0, st, a.mask, reinterpret_cast<uint32_t*>(a.delta), a.Lk);
   const int per_x = (a.B * a.nh + 7) / 8;
   const dim3 grid(8 * (per_x < 32 ? per_x : 32));        // one 512-thread workgroup per CU, a multiple of the 8 XCDs
-  if (a.thr16) hipLaunchKernelGGL(attn_bwd_fused_kernel<true>, grid, dim3(512), 0, st, a);
-  else hipLaunchKernelGGL(attn_bwd_fused_kernel<false>, grid, dim3(512), 0, st, a);
+  hipLaunchKernelGGL(attn_bwd_fused_kernel<D>, grid, dim3(512), 0, st, a);
 }
-int fwd_version() {
-  // 2: round-2 kernel, 3: 128 queries per workgroup, 4: 256, default 0: by shape
-  static const int v = [] { const char* e = getenv("IA_ATTN_FWD"); return e ? atoi(e) : 0; }();
-  return v;
+// the optional exact-delta pre-pass, dQ, then dK/dV (behind every backward entry point that is not served by the fused kernel)
+template <bool D> void launch_pair(const AttnArgs& a, hipStream_t st) {
+  const dim3 gq(((a.Lq + 127) / 128) * a.nh * a.B), gk(((a.Lk + 127) / 128) * a.nh * a.B), blk(256);
+  if (a.exact_delta) hipLaunchKernelGGL(attn_bwd3_delta_kernel<D>, gq, blk, 0, st, a);
+  hipLaunchKernelGGL(attn_bwd3_dq_kernel<D>, gq, blk, 0, st, a);
+  hipLaunchKernelGGL(attn_bwd3_dkv_kernel<D>, gk, blk, 0, st, a);
 }
-// grid: the workgroup count for 128 queries per workgroup (the round-2 geometry); the 256-query kernel derives its own
-void launch_fwd(const AttnArgs& a, dim3 grid, hipStream_t stream) {
-  const dim3 blk(256);
-  const int v = fwd_version();
-  if (v == 2 && !a.q_prescaled) {                        // (the round-2 kernels multiply every score by sc themselves)
-    if (a.thr16) hipLaunchKernelGGL(attn_fwd_kernel<true>, grid, blk, 0, stream, a);
-    else hipLaunchKernelGGL(attn_fwd_kernel<false>, grid, blk, 0, stream, a);
-  } else if (v == 3 || (v != 4 && ((a.Lq - 1) & 255) < 128)) {
-    // 128 queries per workgroup when the last 256-query block would be less than half full (ViT: 577 = 2 x 256 + 65); measured
-    // (profiles/r03_attention_variants.txt): 256-query workgroups are 3-6 % faster at L = 220 / 255, equal at 510, 3 % slower at 577
-    if (a.thr16) hipLaunchKernelGGL((attn_fwd3_kernel<true, 1>), grid, blk, 0, stream, a);
-    else hipLaunchKernelGGL((attn_fwd3_kernel<false, 1>), grid, blk, 0, stream, a);
-  } else {
-    const dim3 g2(((a.Lq + 255) / 256) * a.nh * a.B);
-    if (a.thr16) hipLaunchKernelGGL((attn_fwd3_kernel<true, 2>), g2, blk, 0, stream, a);
-    else hipLaunchKernelGGL((attn_fwd3_kernel<false, 2>), g2, blk, 0, stream, a);
-  }
+template <bool D> void launch_bwd(const AttnArgs& a, hipStream_t st) {
+  if (fused_applies(a)) launch_fused<D>(a, st);
+  else launch_pair<D>(a, st);
+}
+template <bool D> void launch_fwd(const AttnArgs& a, hipStream_t st) {
+  // 128 queries per workgroup when the last 256-query block would be less than half full (ViT: 577 = 2 x 256 + 65); measured
+  // (profiles/r03_attention_variants.txt): 256-query workgroups are 3-6 % faster at L = 220 / 255, equal at 510, 3 % slower at 577
+  if (((a.Lq - 1) & 255) < 128) hipLaunchKernelGGL((attn_fwd3_kernel<D, 1>), dim3(((a.Lq + 127) / 128) * a.nh * a.B), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((attn_fwd3_kernel<D, 2>), dim3(((a.Lq + 255) / 256) * a.nh * a.B), dim3(256), 0, st, a);
+}
+
+// What the packed ("varlen") entry points add: sequence b owns token rows cu[b] .. cu[b+1] of `total` rows in all
+struct Packed { const int* cu; int total; };
+// What the bias forms of the backward add: the QKV bias gradient and the workspace its per-workgroup partial sums go through
+struct BiasOut { float* dbias; void* workspace; size_t workspace_bytes; };
+
+// The one place that checks the arguments of a forward / backward entry point and fills AttnArgs.  pk / bias: null for the entry points
+// without them.  flags: IA_ATTN_* (the caller has rejected unknown bits).
+int attn_fwd_impl(int flags, const void* q, int ld_q, const void* k, const void* v, int ld_kv, const uint8_t* key_mask, const Packed* pk, void* out,
+                  int ld_o, float* lse2, int B, int nh, int Lq, int Lk, float scale, float drop_p, uint32_t seed, hipStream_t stream) {
+  (void)hipGetLastError();  // drop stale status left by unrelated runtime calls (e.g. hipEventQuery -> NotReady)
+  if (!q || !k || !v || !out || (pk && (!pk->cu || pk->total <= 0))) return IA_ERR_ARG;
+  AttnArgs a{};
+  const int rc = fill_args(a, B, nh, Lq, Lk, ld_q, ld_kv, ld_o, scale, drop_p, seed, pk ? pk->total : 0);
+  if (rc) return rc;
+  a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.out = (bf16*)out; a.mask = key_mask; a.lse2 = lse2;
+  a.cu = pk ? pk->cu : nullptr;
+  a.q_prescaled = (flags & IA_ATTN_Q_PRESCALED) ? 1 : 0;
+  if (a.thr16) launch_fwd<true>(a, stream);
+  else launch_fwd<false>(a, stream);
+  return ia_check_launch();
+}
+
+int attn_bwd_impl(int flags, const void* q, int ld_q, const void* k, const void* v, int ld_kv, const uint8_t* key_mask, const Packed* pk,
+                  const void* out, const void* d_out, int ld_o, const float* lse2, float* delta, void* dq, int ld_dq, void* dk, void* dv, int ld_dkv,
+                  const BiasOut* bias, int B, int nh, int Lq, int Lk, float scale, float drop_p, uint32_t seed, hipStream_t stream) {
+  (void)hipGetLastError();  // drop stale status left by unrelated runtime calls (e.g. hipEventQuery -> NotReady)
+  if (!q || !k || !v || !out || !d_out || !lse2 || !delta || !dq || !dk || !dv) return IA_ERR_ARG;
+  if ((pk && (!pk->cu || pk->total <= 0)) || (bias && !bias->dbias)) return IA_ERR_ARG;
+  if (bias && (!bias->workspace || bias->workspace_bytes < ia_attn_bwd_bias_workspace_bytes(B, nh, Lq))) return IA_ERR_WORKSPACE;
+  AttnArgs a{};
+  int rc = fill_args(a, B, nh, Lq, Lk, ld_q, ld_kv, ld_o, scale, drop_p, seed, pk ? pk->total : 0);
+  if (rc) return rc;
+  if ((ld_dq & 7) || (ld_dkv & 7) || ld_dq < nh * 64 || ld_dkv < nh * 64) return IA_ERR_ARG;
+  a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.o = (const bf16*)out; a.d_o = (const bf16*)d_out;
+  a.mask = key_mask; a.lse2 = const_cast<float*>(lse2); a.delta = delta; a.cu = pk ? pk->cu : nullptr;
+  a.dq = (bf16*)dq; a.dk = (bf16*)dk; a.dv = (bf16*)dv; a.ld_dq = ld_dq; a.ld_dkv = ld_dkv;
+  a.cs_part = bias ? (float*)bias->workspace : nullptr;
+  a.q_prescaled = (flags & IA_ATTN_Q_PRESCALED) ? 1 : 0;
+  a.dead_queries = ((flags & IA_ATTN_MASKED_ROWS_DEAD) && key_mask) ? 1 : 0;
+  a.exact_delta = exact_delta_on() ? 1 : 0;
+  if (a.thr16) launch_bwd<true>(a, stream);
+  else launch_bwd<false>(a, stream);
+  rc = ia_check_launch();
+  if (rc || !bias) return rc;
+  return ia_sum_rows_f32((const float*)bias->workspace, B * ((Lq + 127) / 128), 3 * nh * 64, bias->dbias, 1, stream);
 }
 
 }  // namespace
@@ -2410,26 +1864,10 @@ void launch_fwd(const AttnArgs& a, dim3 grid, hipStream_t stream) {
 // ld_o), k / v rows are b*Lk + j (stride ld_kv); head h sits at column h*64 of each.  Multi-query attention (one K/V
 // head shared by all query heads, reference multimodal.py:590-616) is the nh = 1 case with the query heads folded
 // into rows: q viewed as [B, n*heads, 64] (ld_q = 64), Lq = n*heads.  key_mask is [B, Lk].
-static int attn_fwd_impl(int q_prescaled, const void* q, int ld_q, const void* k, const void* v, int ld_kv, const uint8_t* key_mask, void* out,
-                             int ld_o, float* lse2, int B, int nh, int Lq, int Lk, float scale, float drop_p, uint32_t seed,
-                             hipStream_t stream) {
-  (void)hipGetLastError();  // drop stale status left by unrelated runtime calls (e.g. hipEventQuery -> NotReady)
-  if (!q || !k || !v || !out) return IA_ERR_ARG;
-  AttnArgs a{};
-  int rc = fill_args(a, B, nh, Lq, Lk, ld_q, ld_kv, ld_o, scale, drop_p, seed);
-  if (rc) return rc;
-  if (q_prescaled && !fwd3::PRESCALE) return IA_ERR_ARG;
-  a.q_prescaled = q_prescaled;
-  a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.out = (bf16*)out; a.mask = key_mask; a.lse2 = lse2;
-  dim3 grid(((Lq + 127) / 128) * nh * B), blk(256);
-  launch_fwd(a, grid, stream);
-  return ia_check_launch();
-}
-
 extern "C" int ia_attn_fwd_x(const void* q, int ld_q, const void* k, const void* v, int ld_kv, const uint8_t* key_mask, void* out,
                              int ld_o, float* lse2, int B, int nh, int Lq, int Lk, float scale, float drop_p, uint32_t seed,
                              hipStream_t stream) {
-  return attn_fwd_impl(0, q, ld_q, k, v, ld_kv, key_mask, out, ld_o, lse2, B, nh, Lq, Lk, scale, drop_p, seed, stream);
+  return attn_fwd_impl(0, q, ld_q, k, v, ld_kv, key_mask, nullptr, out, ld_o, lse2, B, nh, Lq, Lk, scale, drop_p, seed, stream);
 }
 
 // delta: caller-provided scratch of B*nh*Lq floats (filled by the dQ kernel, read by the dK/dV kernel).
@@ -2437,20 +1875,8 @@ extern "C" int ia_attn_bwd_x(const void* q, int ld_q, const void* k, const void*
                              const void* out, const void* d_out, int ld_o, const float* lse2, float* delta, void* dq, int ld_dq,
                              void* dk, void* dv, int ld_dkv, int B, int nh, int Lq, int Lk, float scale, float drop_p, uint32_t seed,
                              hipStream_t stream) {
-  (void)hipGetLastError();  // drop stale status left by unrelated runtime calls (e.g. hipEventQuery -> NotReady)
-  if (!q || !k || !v || !out || !d_out || !lse2 || !delta || !dq || !dk || !dv) return IA_ERR_ARG;
-  AttnArgs a{};
-  int rc = fill_args(a, B, nh, Lq, Lk, ld_q, ld_kv, ld_o, scale, drop_p, seed);
-  if (rc) return rc;
-  if ((ld_dq & 7) || (ld_dkv & 7) || ld_dq < nh * 64 || ld_dkv < nh * 64) return IA_ERR_ARG;
-  a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.o = (const bf16*)out; a.d_o = (const bf16*)d_out;
-  a.mask = key_mask; a.lse2 = const_cast<float*>(lse2); a.delta = delta;
-  a.dq = (bf16*)dq; a.dk = (bf16*)dk; a.dv = (bf16*)dv; a.ld_dq = ld_dq; a.ld_dkv = ld_dkv;
-  dim3 gq(((Lq + 127) / 128) * nh * B), gk(((Lk + 127) / 128) * nh * B), blk(256);
-  a.exact_delta = exact_delta_on() ? 1 : 0;
-  if (fused_applies(a)) launch_fused(a, stream);
-  else launch_pair(a, gq, gk, stream);
-  return ia_check_launch();
+  return attn_bwd_impl(0, q, ld_q, k, v, ld_kv, key_mask, nullptr, out, d_out, ld_o, lse2, delta, dq, ld_dq, dk, dv, ld_dkv, nullptr, B, nh, Lq, Lk,
+                       scale, drop_p, seed, stream);
 }
 
 // Self-attention over a packed projection: q, k, v point at the first column of head 0 of each operand and share
@@ -2458,21 +1884,21 @@ extern "C" int ia_attn_bwd_x(const void* q, int ld_q, const void* k, const void*
 extern "C" int ia_attn_fwd(const void* q, const void* k, const void* v, int ld_qkv, const uint8_t* key_mask, void* out,
                            int ld_o, float* lse2, int B, int nh, int L, float scale, float drop_p, uint32_t seed,
                            hipStream_t stream) {
-  return ia_attn_fwd_x(q, ld_qkv, k, v, ld_qkv, key_mask, out, ld_o, lse2, B, nh, L, L, scale, drop_p, seed, stream);
+  return attn_fwd_impl(0, q, ld_qkv, k, v, ld_qkv, key_mask, nullptr, out, ld_o, lse2, B, nh, L, L, scale, drop_p, seed, stream);
 }
 
 // ia_attn_fwd on a projection whose q columns already hold q * scale * log2(e) rounded to bf16 (ia_gemm_bf16_qscale): no kernel of the
 // forward / backward pair scales q again, so all of them exponentiate bit-identical products
 extern "C" int ia_attn_fwd_ps(const void* q, const void* k, const void* v, int ld_qkv, const uint8_t* key_mask, void* out, int ld_o,
                               float* lse2, int B, int nh, int L, float scale, float drop_p, uint32_t seed, hipStream_t stream) {
-  return attn_fwd_impl(1, q, ld_qkv, k, v, ld_qkv, key_mask, out, ld_o, lse2, B, nh, L, L, scale, drop_p, seed, stream);
+  return attn_fwd_impl(IA_ATTN_Q_PRESCALED, q, ld_qkv, k, v, ld_qkv, key_mask, nullptr, out, ld_o, lse2, B, nh, L, L, scale, drop_p, seed, stream);
 }
 
 extern "C" int ia_attn_bwd(const void* q, const void* k, const void* v, int ld_qkv, const uint8_t* key_mask, const void* out,
                            const void* d_out, int ld_o, const float* lse2, float* delta, void* dq, void* dk, void* dv,
                            int ld_dqkv, int B, int nh, int L, float scale, float drop_p, uint32_t seed, hipStream_t stream) {
-  return ia_attn_bwd_x(q, ld_qkv, k, v, ld_qkv, key_mask, out, d_out, ld_o, lse2, delta, dq, ld_dqkv, dk, dv, ld_dqkv, B, nh, L, L, scale,
-                       drop_p, seed, stream);
+  return attn_bwd_impl(0, q, ld_qkv, k, v, ld_qkv, key_mask, nullptr, out, d_out, ld_o, lse2, delta, dq, ld_dqkv, dk, dv, ld_dqkv, nullptr, B, nh, L, L,
+                       scale, drop_p, seed, stream);
 }
 
 // ia_attn_bwd that also returns the bias gradient of the fused QKV projection: dbias[3*nh*64] (q | k | v order) += column sums of
@@ -2483,50 +1909,6 @@ extern "C" size_t ia_attn_bwd_bias_workspace_bytes(int B, int nh, int L) {
   return (size_t)B * ((L + 127) / 128) * 3 * nh * 64 * sizeof(float);
 }
 
-static int attn_bwd_bias_impl(int flags, const void* q, const void* k, const void* v, int ld_qkv, const uint8_t* key_mask, const void* out,
-                              const void* d_out, int ld_o, const float* lse2, float* delta, void* dq, void* dk, void* dv, int ld_dqkv,
-                              float* dbias, void* workspace, size_t workspace_bytes, int B, int nh, int L, float scale, float drop_p,
-                              uint32_t seed, hipStream_t stream) {
-  (void)hipGetLastError();
-  if (!q || !k || !v || !out || !d_out || !lse2 || !delta || !dq || !dk || !dv || !dbias) return IA_ERR_ARG;
-  if (!workspace || workspace_bytes < ia_attn_bwd_bias_workspace_bytes(B, nh, L)) return IA_ERR_WORKSPACE;
-  AttnArgs a{};
-  int rc = fill_args(a, B, nh, L, L, ld_qkv, ld_qkv, ld_o, scale, drop_p, seed);
-  if (rc) return rc;
-  if ((ld_dqkv & 7) || ld_dqkv < nh * 64) return IA_ERR_ARG;
-  a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.o = (const bf16*)out; a.d_o = (const bf16*)d_out;
-  a.mask = key_mask; a.lse2 = const_cast<float*>(lse2); a.delta = delta;
-  a.dq = (bf16*)dq; a.dk = (bf16*)dk; a.dv = (bf16*)dv; a.ld_dq = ld_dqkv; a.ld_dkv = ld_dqkv;
-  a.cs_part = (float*)workspace;
-  const int q_prescaled = flags & IA_ATTN_Q_PRESCALED;
-  if (q_prescaled && !fwd3::PRESCALE) return IA_ERR_ARG;
-  a.q_prescaled = q_prescaled ? 1 : 0;
-  a.dead_queries = ((flags & IA_ATTN_MASKED_ROWS_DEAD) && key_mask) ? 1 : 0;
-  dim3 grid(((L + 127) / 128) * nh * B), blk(256);
-  a.exact_delta = exact_delta_on() ? 1 : 0;
-  if (fused_applies(a)) launch_fused(a, stream);
-  else launch_pair(a, grid, grid, stream);
-  rc = ia_check_launch();
-  if (rc) return rc;
-  return ia_sum_rows_f32((const float*)workspace, B * ((L + 127) / 128), 3 * nh * 64, dbias, 1, stream);
-}
-
-extern "C" int ia_attn_bwd_bias(const void* q, const void* k, const void* v, int ld_qkv, const uint8_t* key_mask, const void* out,
-                                const void* d_out, int ld_o, const float* lse2, float* delta, void* dq, void* dk, void* dv, int ld_dqkv,
-                                float* dbias, void* workspace, size_t workspace_bytes, int B, int nh, int L, float scale, float drop_p,
-                                uint32_t seed, hipStream_t stream) {
-  return attn_bwd_bias_impl(0, q, k, v, ld_qkv, key_mask, out, d_out, ld_o, lse2, delta, dq, dk, dv, ld_dqkv, dbias, workspace, workspace_bytes,
-                            B, nh, L, scale, drop_p, seed, stream);
-}
-// backward of ia_attn_fwd_ps: q as the forward saw it (pre-scaled); dq is still dL/d(q before the scale), i.e. what the QKV projection's
-// weight / input gradients consume unchanged
-extern "C" int ia_attn_bwd_bias_ps(const void* q, const void* k, const void* v, int ld_qkv, const uint8_t* key_mask, const void* out,
-                                   const void* d_out, int ld_o, const float* lse2, float* delta, void* dq, void* dk, void* dv, int ld_dqkv,
-                                   float* dbias, void* workspace, size_t workspace_bytes, int B, int nh, int L, float scale, float drop_p,
-                                   uint32_t seed, hipStream_t stream) {
-  return attn_bwd_bias_impl(IA_ATTN_Q_PRESCALED, q, k, v, ld_qkv, key_mask, out, d_out, ld_o, lse2, delta, dq, dk, dv, ld_dqkv, dbias, workspace,
-                            workspace_bytes, B, nh, L, scale, drop_p, seed, stream);
-}
 // ia_attn_bwd_bias with flags (IA_ATTN_*): IA_ATTN_Q_PRESCALED = the _ps form; IA_ATTN_MASKED_ROWS_DEAD = the caller guarantees that d_out is
 // zero at every masked position (an encoder whose masked positions never reach the loss: they are masked as keys in every layer and no
 // head reads them) -- the one-kernel backward then skips the 32-query blocks that hold only masked positions; results are identical.
@@ -2535,67 +1917,54 @@ extern "C" int ia_attn_bwd_bias_ex(int flags, const void* q, const void* k, cons
                                    float* dbias, void* workspace, size_t workspace_bytes, int B, int nh, int L, float scale, float drop_p,
                                    uint32_t seed, hipStream_t stream) {
   if (flags & ~(IA_ATTN_Q_PRESCALED | IA_ATTN_MASKED_ROWS_DEAD)) return IA_ERR_ARG;
-  return attn_bwd_bias_impl(flags, q, k, v, ld_qkv, key_mask, out, d_out, ld_o, lse2, delta, dq, dk, dv, ld_dqkv, dbias, workspace, workspace_bytes,
-                            B, nh, L, scale, drop_p, seed, stream);
+  const BiasOut bias{dbias, workspace, workspace_bytes};
+  return attn_bwd_impl(flags, q, ld_qkv, k, v, ld_qkv, key_mask, nullptr, out, d_out, ld_o, lse2, delta, dq, ld_dqkv, dk, dv, ld_dqkv, &bias, B, nh, L, L,
+                       scale, drop_p, seed, stream);
+}
+extern "C" int ia_attn_bwd_bias(const void* q, const void* k, const void* v, int ld_qkv, const uint8_t* key_mask, const void* out,
+                                const void* d_out, int ld_o, const float* lse2, float* delta, void* dq, void* dk, void* dv, int ld_dqkv,
+                                float* dbias, void* workspace, size_t workspace_bytes, int B, int nh, int L, float scale, float drop_p,
+                                uint32_t seed, hipStream_t stream) {
+  return ia_attn_bwd_bias_ex(0, q, k, v, ld_qkv, key_mask, out, d_out, ld_o, lse2, delta, dq, dk, dv, ld_dqkv, dbias, workspace, workspace_bytes, B, nh,
+                             L, scale, drop_p, seed, stream);
+}
+// backward of ia_attn_fwd_ps: q as the forward saw it (pre-scaled); dq is still dL/d(q before the scale), i.e. what the QKV projection's
+// weight / input gradients consume unchanged
+extern "C" int ia_attn_bwd_bias_ps(const void* q, const void* k, const void* v, int ld_qkv, const uint8_t* key_mask, const void* out,
+                                   const void* d_out, int ld_o, const float* lse2, float* delta, void* dq, void* dk, void* dv, int ld_dqkv,
+                                   float* dbias, void* workspace, size_t workspace_bytes, int B, int nh, int L, float scale, float drop_p,
+                                   uint32_t seed, hipStream_t stream) {
+  return ia_attn_bwd_bias_ex(IA_ATTN_Q_PRESCALED, q, k, v, ld_qkv, key_mask, out, d_out, ld_o, lse2, delta, dq, dk, dv, ld_dqkv, dbias, workspace,
+                             workspace_bytes, B, nh, L, scale, drop_p, seed, stream);
 }
 
 // Packed ("unpadded") self-attention: the token rows of all sequences lie back to back, sequence b owning rows
 // cu_seqlens[b] .. cu_seqlens[b+1] (int32 [B+1], device; total_tokens = cu_seqlens[B]); no key mask — every key of a sequence is
 // attendable.  Lmax = longest sequence (sets the grid and the row stride of lse2 / delta, which stay [B, nh, Lmax]).  Same
 // arithmetic as ia_attn_fwd / ia_attn_bwd on the valid tokens of a right-padded batch; padded positions are simply absent.
-static int attn_fwd_varlen_impl(int q_prescaled, const void* q, const void* k, const void* v, int ld_qkv, const int* cu_seqlens, int total_tokens,
-                                void* out, int ld_o, float* lse2, int B, int nh, int Lmax, float scale, float drop_p, uint32_t seed,
-                                hipStream_t stream) {
-  (void)hipGetLastError();
-  if (!q || !k || !v || !out || !cu_seqlens || total_tokens <= 0) return IA_ERR_ARG;
-  AttnArgs a{};
-  int rc = fill_args(a, B, nh, Lmax, Lmax, ld_qkv, ld_qkv, ld_o, scale, drop_p, seed, total_tokens);
-  if (rc) return rc;
-  a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.out = (bf16*)out; a.mask = nullptr; a.lse2 = lse2; a.cu = cu_seqlens;
-  if (q_prescaled && !fwd3::PRESCALE) return IA_ERR_ARG;
-  a.q_prescaled = q_prescaled;
-  dim3 grid(((Lmax + 127) / 128) * nh * B);
-  launch_fwd(a, grid, stream);
-  return ia_check_launch();
-}
+// The _ps forms take the pre-scaled q of ia_attn_fwd_ps.  The packed backward always runs the kernel pair.
 extern "C" int ia_attn_fwd_varlen(const void* q, const void* k, const void* v, int ld_qkv, const int* cu_seqlens, int total_tokens, void* out,
                                   int ld_o, float* lse2, int B, int nh, int Lmax, float scale, float drop_p, uint32_t seed, hipStream_t stream) {
-  return attn_fwd_varlen_impl(0, q, k, v, ld_qkv, cu_seqlens, total_tokens, out, ld_o, lse2, B, nh, Lmax, scale, drop_p, seed, stream);
+  const Packed pk{cu_seqlens, total_tokens};
+  return attn_fwd_impl(0, q, ld_qkv, k, v, ld_qkv, nullptr, &pk, out, ld_o, lse2, B, nh, Lmax, Lmax, scale, drop_p, seed, stream);
 }
 extern "C" int ia_attn_fwd_varlen_ps(const void* q, const void* k, const void* v, int ld_qkv, const int* cu_seqlens, int total_tokens, void* out,
                                      int ld_o, float* lse2, int B, int nh, int Lmax, float scale, float drop_p, uint32_t seed,
                                      hipStream_t stream) {
-  return attn_fwd_varlen_impl(1, q, k, v, ld_qkv, cu_seqlens, total_tokens, out, ld_o, lse2, B, nh, Lmax, scale, drop_p, seed, stream);
-}
-
-static int attn_bwd_varlen_impl(int q_prescaled, const void* q, const void* k, const void* v, int ld_qkv, const int* cu_seqlens, int total_tokens,
-                                const void* out, const void* d_out, int ld_o, const float* lse2, float* delta, void* dq, void* dk, void* dv,
-                                int ld_dqkv, int B, int nh, int Lmax, float scale, float drop_p, uint32_t seed, hipStream_t stream) {
-  (void)hipGetLastError();
-  if (!q || !k || !v || !out || !d_out || !lse2 || !delta || !dq || !dk || !dv || !cu_seqlens || total_tokens <= 0) return IA_ERR_ARG;
-  AttnArgs a{};
-  int rc = fill_args(a, B, nh, Lmax, Lmax, ld_qkv, ld_qkv, ld_o, scale, drop_p, seed, total_tokens);
-  if (rc) return rc;
-  if ((ld_dqkv & 7) || ld_dqkv < nh * 64) return IA_ERR_ARG;
-  a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.o = (const bf16*)out; a.d_o = (const bf16*)d_out;
-  a.mask = nullptr; a.lse2 = const_cast<float*>(lse2); a.delta = delta; a.cu = cu_seqlens;
-  a.dq = (bf16*)dq; a.dk = (bf16*)dk; a.dv = (bf16*)dv; a.ld_dq = ld_dqkv; a.ld_dkv = ld_dqkv;
-  if (q_prescaled && !fwd3::PRESCALE) return IA_ERR_ARG;
-  a.q_prescaled = q_prescaled;
-  dim3 grid(((Lmax + 127) / 128) * nh * B), blk(256);
-  a.exact_delta = exact_delta_on() ? 1 : 0;
-  launch_pair(a, grid, grid, stream);
-  return ia_check_launch();
+  const Packed pk{cu_seqlens, total_tokens};
+  return attn_fwd_impl(IA_ATTN_Q_PRESCALED, q, ld_qkv, k, v, ld_qkv, nullptr, &pk, out, ld_o, lse2, B, nh, Lmax, Lmax, scale, drop_p, seed, stream);
 }
 extern "C" int ia_attn_bwd_varlen(const void* q, const void* k, const void* v, int ld_qkv, const int* cu_seqlens, int total_tokens,
                                   const void* out, const void* d_out, int ld_o, const float* lse2, float* delta, void* dq, void* dk, void* dv,
                                   int ld_dqkv, int B, int nh, int Lmax, float scale, float drop_p, uint32_t seed, hipStream_t stream) {
-  return attn_bwd_varlen_impl(0, q, k, v, ld_qkv, cu_seqlens, total_tokens, out, d_out, ld_o, lse2, delta, dq, dk, dv, ld_dqkv, B, nh, Lmax, scale,
-                              drop_p, seed, stream);
+  const Packed pk{cu_seqlens, total_tokens};
+  return attn_bwd_impl(0, q, ld_qkv, k, v, ld_qkv, nullptr, &pk, out, d_out, ld_o, lse2, delta, dq, ld_dqkv, dk, dv, ld_dqkv, nullptr, B, nh, Lmax, Lmax,
+                       scale, drop_p, seed, stream);
 }
 extern "C" int ia_attn_bwd_varlen_ps(const void* q, const void* k, const void* v, int ld_qkv, const int* cu_seqlens, int total_tokens,
                                      const void* out, const void* d_out, int ld_o, const float* lse2, float* delta, void* dq, void* dk, void* dv,
                                      int ld_dqkv, int B, int nh, int Lmax, float scale, float drop_p, uint32_t seed, hipStream_t stream) {
-  return attn_bwd_varlen_impl(1, q, k, v, ld_qkv, cu_seqlens, total_tokens, out, d_out, ld_o, lse2, delta, dq, dk, dv, ld_dqkv, B, nh, Lmax, scale,
-                              drop_p, seed, stream);
+  const Packed pk{cu_seqlens, total_tokens};
+  return attn_bwd_impl(IA_ATTN_Q_PRESCALED, q, ld_qkv, k, v, ld_qkv, nullptr, &pk, out, d_out, ld_o, lse2, delta, dq, ld_dqkv, dk, dv, ld_dqkv, nullptr, B,
+                       nh, Lmax, Lmax, scale, drop_p, seed, stream);
 }

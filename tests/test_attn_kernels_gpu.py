@@ -3,8 +3,8 @@ element for ctx, lse2, dq, dk and dv, within the derived bars of attn_reference.
 kernels' rounding by tests/test_attn_reference_host.py; never fitted to a GPU result).  Every call runs on sentinel-filled outputs with
 pad columns and 64 guard rows that have to come back bit-unchanged.  Every comparison prints max error / bound (`-s` shows them).
 
-No test sets IA_ATTN_FWD / IA_ATTN_BWD (read once per process; they select the development kernels), so the kernels under test are
-attn_fwd3_kernel<*, 1 | 2>, attn_bwd_fused_kernel (33 <= L <= 256), attn_bwd3_dq / _dkv / _delta_kernel.
+The dispatch follows the shape alone (launch_fwd, fused_applies) plus IA_ATTN_EXACT_DELTA, so the kernels under test are all the file
+has: attn_fwd3_kernel<*, 1 | 2>, attn_bwd_fused_kernel (33 <= L <= 256), attn_bwd3_dq / _dkv / _delta_kernel.
 """
 import math
 import os

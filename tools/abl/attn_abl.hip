@@ -1,4 +1,5 @@
-// Ablation / timing harness for the attention kernels (no torch): includes attention.hip compiled with -DIA_ABL=n.
+// Timing harness for the attention kernels (no torch): includes attention.hip.
+// build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -Wno-unused-value -I../../include attn_abl.hip -o attn_abl0
 // usage: attn_abl B L nh [mode: 0 fwd, 1 bwd] ; prints average time of 20 launches.
 #ifndef IA_ATTN_SRC
 #define IA_ATTN_SRC "../../item_alignment_amd/csrc/attention.hip"

@@ -1,5 +1,5 @@
 // Development harness for the attention kernels (no torch): includes attention.hip, checks the forward (and backward) against an fp32
-// host reference on a few (sequence, head) pairs and times the launches.  Kernel variants are picked with IA_ATTN_FWD / IA_ATTN_BWD.
+// host reference on a few (sequence, head) pairs and times the launches (build: build_dev.sh).
 // usage: attn_dev B L nh [mode: 0 fwd, 1 bwd] [drop] [amp: input std * 4] [masked: 0 none, 1 right padding + a hole]
 //        [check: 0 time only, 1 compare sampled (sequence, head) pairs with the host reference, N >= 2: also N launches whose whole
 //         output is scanned for non-finite / absurd entries -- rare timing-dependent faults do not show up in the sampled check]
@@ -54,8 +54,6 @@ int main(int argc, char** argv) {
   if (fwd()) { printf("fwd launch failed\n"); return 1; }
   if (mode == 1 && bwd()) { printf("bwd launch failed\n"); return 1; }
   if (hipDeviceSynchronize() != hipSuccess) { printf("kernel fault: %s\n", hipGetErrorString(hipGetLastError())); return 1; }
-  const char* fv = getenv("IA_ATTN_FWD"); const char* bv = getenv("IA_ATTN_BWD");
-  char tag[64]; snprintf(tag, sizeof tag, "fwd=%s bwd=%s", fv ? fv : "-", bv ? bv : "-");
   if (check && drop == 0.f) {
     std::vector<uint16_t> ho(T * H), hg(T * 3 * H); std::vector<float> hl((size_t)B * nh * L);
     hipMemcpy(ho.data(), out, T * H * 2, hipMemcpyDeviceToHost);
@@ -106,7 +104,7 @@ int main(int argc, char** argv) {
         }
       }
     }
-    printf("[%s] B=%d L=%d nh=%d amp=%.1f masked=%d: O rel err %.2e  lse abs err %.2e", tag, B, L, nh, amp, masked, eo / mo, el);
+    printf("B=%d L=%d nh=%d amp=%.1f masked=%d: O rel err %.2e  lse abs err %.2e", B, L, nh, amp, masked, eo / mo, el);
     if (mode == 1) printf("  dq %.2e dk %.2e dv %.2e", eg[0] / mg[0], eg[1] / mg[1], eg[2] / mg[2]);
     printf("\n");
   }
@@ -135,8 +133,8 @@ int main(int argc, char** argv) {
         ++nbad;
       }
     }
-    printf("[%s] scan: %zu bad of %zu\n", tag, nbad, hg.size());
+    printf("scan: %zu bad of %zu\n", nbad, hg.size());
   }
-  printf("[%s] mode=%d B=%d L=%d nh=%d drop=%.2f masked=%d: %.1f us avg (%.1f best)  %.1f TF/s\n", tag, mode, B, L, nh, drop, masked, us, usb, fl / us * 1e-6);
+  printf("mode=%d B=%d L=%d nh=%d drop=%.2f masked=%d: %.1f us avg (%.1f best)  %.1f TF/s\n", mode, B, L, nh, drop, masked, us, usb, fl / us * 1e-6);
   return 0;
 }

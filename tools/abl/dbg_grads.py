@@ -24,7 +24,7 @@ for n, p in zip(arena.names, arena.params):
     g = p.grad
     if not torch.isfinite(g).all():
         bad.append((n, int((~torch.isfinite(g)).sum()), g.numel()))
-print(f"BWD={os.environ.get('IA_ATTN_BWD')} pairs={pairs}: {len(bad)} params with non-finite grads")
+print(f"pairs={pairs}: {len(bad)} params with non-finite grads")
 for x in bad[:12] + bad[-12:]:
     print("   ", x)
 tot = {}
