@@ -270,9 +270,9 @@ int ia_conv3x3_padded_bwd_data(const void* dyp, const void* what, void* dxp, int
  * (input with halo staged once by LDS-DMA, the nine taps as LDS row offsets) instead of nine shifted reads per tile through the
  * L2 -> LDS path.  The data gradient is the same kernel on dy with the tap-flipped, transposed bank: ia_conv3x3_flip_weights(what ->
  * what_t [Cin][9 * Cout / groups], the same number of elements), then ia_conv3x3_padded_bwd_data_t.  ia_conv3x3_direct_supported:
- * 1 when forward AND data gradient of the shape take that path (IA_CONV_DIRECT=0 switches it off).  ia_conv3x3_padded_bwd_weight
+ * 1 when forward AND data gradient of the shape take that path.  ia_conv3x3_padded_bwd_weight
  * takes its direct form by itself for the same channel pairs when the launch covers >= 10^5 pixels (transpose reads of the dy and x
- * tiles, one fp32 bank per workgroup, fixed-order fold: bit-reproducible; IA_CONV_DIRECT_WGRAD=0 switches it off);
+ * tiles, one fp32 bank per workgroup, fixed-order fold: bit-reproducible);
  * ia_conv3x3_padded_workspace_bytes covers both forms. */
 int ia_conv3x3_direct_supported(int Cin, int Cout, int groups);
 int ia_conv3x3_flip_weights(const void* what, void* what_t, int Cin, int Cout, int groups, ia_stream_t stream);
@@ -284,23 +284,20 @@ int ia_conv3x3_padded_bwd_weight(const void* xp, const void* dyp, float* dwhat, 
 /* 3x3 / stride 2 / padding 1 between bordered layouts: xp [B, H+2, W+2, Cin] (zero border) -> yp [B, Ho+2, Wo+2, Cout], Ho = (H-1)/2 + 1
  * (border of yp not written).  The strided convolutions of timm's NormFreeNet (nfnet.py: conv2 of the first block of stages 2-4,
  * 64 channels per group; stem conv4, 64 -> 128) behind reference src/models/image.py:254-257, without a patch matrix: forward = one
- * kernel over the four parity views of x, weight gradient = the direct weight-gradient kernel on those views, data gradient = GEMM +
- * gather between the bordered layouts.  ia_conv3x3_s2_supported: 1 for Cin = Cout = 64 * groups, or groups = 1, Cin = 64, Cout = 64 n
- * (0 also when IA_CONV_S2_DIRECT=0): other shapes go through ia_conv_nhwc_*.  One workspace size serves both gradient calls. */
+ * kernel over the four parity views of x, weight gradient = one kernel over the same views, data gradient = one kernel over the four
+ * parity classes of dx.  ia_conv3x3_s2_supported: 1 for Cin = Cout = 64 * groups, or groups = 1, Cin = 64, Cout = 64 n: other shapes go
+ * through ia_conv_nhwc_*.  The workspace is the weight gradient's. */
 int ia_conv3x3_s2_supported(int Cin, int Cout, int groups);
 size_t ia_conv3x3_s2_padded_workspace_bytes(int B, int H, int W, int Cin, int Cout, int groups);
 /* y_compact != 0: yp / dyp are [B, Ho, Wo, Cout] without a border (the stem's last convolution feeds compact consumers) */
 int ia_conv3x3_s2_padded_fwd(const void* xp, const void* what, const float* bias, void* yp, int B, int H, int W, int Cin, int Cout,
                              int groups, int y_compact, ia_stream_t stream);
-int ia_conv3x3_s2_padded_bwd_data(const void* dyp, const void* what, void* dxp, int B, int H, int W, int Cin, int Cout, int groups,
-                                  int y_compact, void* workspace, size_t workspace_bytes, ia_stream_t stream);
 int ia_conv3x3_s2_padded_bwd_weight(const void* xp, const void* dyp, float* dwhat, float* dbias, int B, int H, int W, int Cin, int Cout,
                                     int groups, int y_compact, void* workspace, size_t workspace_bytes, ia_stream_t stream);
-/* the data gradient as one kernel over the four parity classes of dx (ia_conv3x3_s2_dgrad_supported): what_t from
+/* the data gradient (every shape of ia_conv3x3_s2_supported): what_t from
  * ia_conv3x3_flip_weights, dyp bordered with a ZERO border (or compact: y_compact), dxp bordered (interior written).  Cin = Cout = 64 * groups;
  * groups = 1, Cin = 64, Cout = 64 n runs as n launches over the 64-channel slices of dy that add up in dx, what_t then holds n banks
  * (ia_conv3x3_flip_weights(what, what_t, Cout, Cout, n)) */
-int ia_conv3x3_s2_dgrad_supported(int Cin, int Cout, int groups);
 int ia_conv3x3_s2_padded_bwd_data_t(const void* dyp, const void* what_t, void* dxp, int B, int H, int W, int Cin, int Cout, int groups,
                                     int y_compact, ia_stream_t stream);
 /* y = silu(x) * scale between the compact [B,H,W,C] and the zero-bordered [B,H+2,W+2,C] layouts (one flag per side); the

@@ -85,38 +85,6 @@ __global__ __launch_bounds__(256) void col2im3_kernel(const bf16* __restrict__ d
   *reinterpret_cast<bf16x8*>(dx + pix * C + c) = o;
 }
 
-// the same gather between BORDERED layouts (stride 2): dcols rows are the pixels of [B, Ho + 2, Wo + 2], dx is [B, H + 2, W + 2, C]; only the
-// interior of dx is written (its reader, the SiLU backward in front, looks at nothing else)
-__global__ __launch_bounds__(256) void col2im3_s2_padded_kernel(const bf16* __restrict__ dcols, bf16* __restrict__ dx, int H, int W, int C, int Cg,
-                                                                int Ho, int Wo, int y_compact, size_t total) {
-  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= total) return;
-  const int c8n = C >> 3;
-  const int c = (int)(idx % c8n) * 8;
-  const size_t pix = idx / c8n;
-  const int ix = (int)(pix % W), iy = (int)((pix / W) % H);
-  const size_t b = pix / ((size_t)W * H);
-  const int g = c / Cg, cg = c % Cg;
-  float acc[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc[j] = 0.f;
-#pragma unroll
-  for (int t = 0; t < 9; ++t) {
-    const int ny = iy + 1 - t / 3, nx = ix + 1 - t % 3;
-    if (ny < 0 || nx < 0 || (ny & 1) || (nx & 1)) continue;
-    const int oy = ny >> 1, ox = nx >> 1;
-    if (oy >= Ho || ox >= Wo) continue;
-    const size_t orow = y_compact ? (b * Ho + oy) * Wo + ox : (b * (Ho + 2) + oy + 1) * (Wo + 2) + ox + 1;
-    const bf16x8 v = *reinterpret_cast<const bf16x8*>(dcols + orow * (size_t)(9 * C) + (size_t)g * 9 * Cg + t * Cg + cg);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j] += bf2f(v[j]);
-  }
-  bf16x8 o;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) o[j] = f2bf(acc[j]);
-  *reinterpret_cast<bf16x8*>(dx + ((b * (H + 2) + iy + 1) * (size_t)(W + 2) + ix + 1) * C + c) = o;
-}
-
 // ------------------------------------------------------------------------------ weight standardisation
 // ScaledStdConv2d: what[o][t*Cgp + c] = (w[o][c][t] - mean_o) * rstd_o * gain[o] * scale, statistics over the real fan-in
 // (Cg*kk, biased variance, eps inside the sqrt); channels c >= Cg (padding of the 3-channel stem) are zero.  One wave per o.
@@ -783,7 +751,19 @@ extern "C" int ia_eca_fwd_linear(const void* x, const void* a, const void* what,
 extern "C" size_t ia_eca_bwd_workspace_bytes(int B, int HW, int C) { return ia_gap_workspace_bytes(B, HW, C) + (size_t)2 * B * C * sizeof(float); }
 // everything behind the spatial partial sums of dout * x (part, in the workspace): gate gradient, conv1d weight gradient, dx
 static int eca_bwd_tail(const void* dout, const float* conv_w, int k, const float* pooled, const float* gate, void* dx, float* dconv_w, int B,
-                        int HW, int C, float coef, void* workspace, hipStream_t stream);
+                        int HW, int C, float coef, void* workspace, hipStream_t stream) {
+  const int ns = nsplit_of(HW);
+  float* part = (float*)workspace;
+  float* dgate = part + (size_t)B * ns * C;
+  float* dpooled = dgate + (size_t)B * C;
+  hipLaunchKernelGGL(spatial_finish_kernel, dim3((B * C + 255) / 256), dim3(256), 0, stream, (const float*)part, dgate, C, ns, coef, B * C);
+  hipLaunchKernelGGL(eca_gate_bwd_kernel, dim3((B * C + 255) / 256), dim3(256), 0, stream, (const float*)dgate, gate, conv_w, dpooled, C, k, B * C);
+  if (dconv_w) hipLaunchKernelGGL(eca_gate_wgrad_kernel, dim3(k), dim3(1024), 0, stream, (const float*)dgate, gate, pooled, dconv_w, B, C, k);
+  const size_t total = (size_t)B * HW * (C >> 3);
+  hipLaunchKernelGGL(scale_residual_bwd_kernel, dim3(blocks_of(total)), dim3(256), 0, stream, (const bf16*)dout, gate, (const float*)dpooled,
+                     (bf16*)dx, HW, C, coef, total);
+  return ia_check_launch();
+}
 
 extern "C" int ia_eca_bwd(const void* dout, const void* x, const float* conv_w, int k, const float* pooled, const float* gate, void* dx,
                           float* dconv_w, int B, int HW, int C, float coef, void* workspace, size_t workspace_bytes, hipStream_t stream) {
@@ -809,21 +789,6 @@ extern "C" int ia_eca_silu_bwd(const void* dact, const void* dact2, const void* 
   hipLaunchKernelGGL(silu_bwd_dot_kernel, dim3(ns, B), dim3(256), 0, stream, (const bf16*)dact, (const bf16*)dact2, (const bf16*)out,
                      (const bf16*)dout_direct, (const bf16*)x, (bf16*)dtot, (float*)workspace, HW, C, ns, act_scale);
   return eca_bwd_tail(dtot, conv_w, k, pooled, gate, dx, dconv_w, B, HW, C, coef, workspace, stream);
-}
-
-static int eca_bwd_tail(const void* dout, const float* conv_w, int k, const float* pooled, const float* gate, void* dx, float* dconv_w, int B,
-                        int HW, int C, float coef, void* workspace, hipStream_t stream) {
-  const int ns = nsplit_of(HW);
-  float* part = (float*)workspace;
-  float* dgate = part + (size_t)B * ns * C;
-  float* dpooled = dgate + (size_t)B * C;
-  hipLaunchKernelGGL(spatial_finish_kernel, dim3((B * C + 255) / 256), dim3(256), 0, stream, (const float*)part, dgate, C, ns, coef, B * C);
-  hipLaunchKernelGGL(eca_gate_bwd_kernel, dim3((B * C + 255) / 256), dim3(256), 0, stream, (const float*)dgate, gate, conv_w, dpooled, C, k, B * C);
-  if (dconv_w) hipLaunchKernelGGL(eca_gate_wgrad_kernel, dim3(k), dim3(1024), 0, stream, (const float*)dgate, gate, pooled, dconv_w, B, C, k);
-  const size_t total = (size_t)B * HW * (C >> 3);
-  hipLaunchKernelGGL(scale_residual_bwd_kernel, dim3(blocks_of(total)), dim3(256), 0, stream, (const bf16*)dout, gate, (const float*)dpooled,
-                     (bf16*)dx, HW, C, coef, total);
-  return ia_check_launch();
 }
 
 // ------------------------------------------------------------------------ 3x3 stride-1 convolution without a patch matrix
@@ -858,7 +823,6 @@ struct Args {
   const bf16* xp; const bf16* w; const float* bias; bf16* yp;
   int B, H, W, Cin, Cout, groups;
   int tiles_x, tiles_y;
-  int dbg;                     // IA_CONV_DBG (timing ablations, results wrong): 1 = no stores, 4 = no input DMA after the first tile
 };
 
 template <int CI> IA_DEV int akey(int P) { return CI == 64 ? (P & 7) : CI == 32 ? ((P >> 1) & 3) : 0; }     // swizzle key of input pixel P
@@ -976,7 +940,7 @@ __global__ __launch_bounds__(256) void conv3x3_direct_kernel(Args p) {
   int buf = 0;
 #pragma unroll 1
   for (int t = slot; t < ntiles; t += nslots, buf ^= 1) {
-    if (t + nslots < ntiles && !(p.dbg & 4)) stage(t + nslots, buf ^ 1);
+    if (t + nslots < ntiles) stage(t + nslots, buf ^ 1);
     const uint32_t in = sbase + W_BYTES + buf * IN_BYTES;
     f32x4 acc[4][NI];
 #pragma unroll
@@ -1025,7 +989,7 @@ __global__ __launch_bounds__(256) void conv3x3_direct_kernel(Args p) {
     for (int mi = 0; mi < 4; ++mi) {
       const int q = wave * 64 + mi * 16 + li;
       const int y = q / TW, x = q - y * TW;
-      if (q >= TILE_PX || y0 + y > p.H || x0 + x > p.W || (p.dbg & 1)) continue;
+      if (q >= TILE_PX || y0 + y > p.H || x0 + x > p.W) continue;
       bf16* const dst = p.yp + (((size_t)b * PH + (y0 + y)) * PW + (x0 + x)) * p.Cout + (size_t)grp * CO + g * (CO / 4);
       if constexpr (NI == 1) {
         bf16x4 o;
@@ -1379,37 +1343,45 @@ __global__ __launch_bounds__(256) void flip_weights_kernel(const bf16* __restric
   wt[((size_t)grp * CI + ci) * (9 * CO) + (8 - tap) * CO + co] = w[idx];
 }
 
-static bool enabled() {
-  static const bool on = [] { const char* e = getenv("IA_CONV_DIRECT"); return !e || atoi(e) != 0; }();
-  return on;
-}
-static bool wgrad_enabled() {
-  static const bool on = [] { const char* e = getenv("IA_CONV_DIRECT_WGRAD"); return !e || atoi(e) != 0; }();
-  return on;
-}
 // smallest B * H * W the direct weight gradient takes (below it the split-K GEMM is faster); IA_CONV_DIRECT_WGRAD_MIN overrides it --
 // read on every call, so that a test can route small ragged maps through the direct kernel
 static size_t wgrad_min_pixels() {
   const char* e = getenv("IA_CONV_DIRECT_WGRAD_MIN");
   return e ? (size_t)atol(e) : 100000;
 }
-static bool pair_ok(int ci, int co) {
-  return (ci == 64 && co == 64) || (ci == 16 && co == 32) || (ci == 32 && co == 64) || (ci == 64 && co == 32) || (ci == 32 && co == 16);
+// channels per group (ci, co) the direct forward / data-gradient kernel is built for, and those of the direct weight gradient
+#define DCONV_PAIRS(X) X(64, 64) X(16, 32) X(32, 64) X(64, 32) X(32, 16)
+#define DCONV_WGRAD_PAIRS(X) X(64, 64) X(16, 32) X(32, 64)
+#define DCONV_IS_PAIR(CI, CO) || (ci == CI && co == CO)
+static bool pair_ok(int ci, int co) { return false DCONV_PAIRS(DCONV_IS_PAIR); }
+static bool wgrad_ok(int ci, int co) { return false DCONV_WGRAD_PAIRS(DCONV_IS_PAIR); }
+
+// ---- what every launcher below does
+// more dynamic LDS than a launch gets by default: raise the kernel's limit, once (`done` is the caller's flag for this kernel)
+static int allow_lds(const void* kern, int bytes, bool& done) {
+  if (!done) {
+    if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return IA_ERR_LAUNCH;
+    done = true;
+  }
+  return IA_OK;
 }
+static void tiles_of(int H, int W, int& tiles_x, int& tiles_y) { tiles_x = (W + TW - 1) / TW; tiles_y = (H + TH - 1) / TH; }
+// persistent workgroups per channel group: the 256 CUs, twice where two workgroups' LDS fit on one (the direct kernel's ~220 registers
+// allow it), dealt to the groups; at most one per tile, at least one
+static long slots_per_group(int lds_bytes, int groups, long ntiles) {
+  const int per_cu = (160 * 1024) / lds_bytes >= 2 ? 2 : 1;
+  long n = (256L * per_cu) / groups;
+  if (n > ntiles) n = ntiles;
+  return n < 1 ? 1 : n;
+}
+
 template <int CI, int CO>
-static int launch_t(Args a, hipStream_t stream) {
+static int launch_t(const Args& a, hipStream_t stream) {
   using G = Geo<CI, CO>;
   auto kern = conv3x3_direct_kernel<CI, CO>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES) != hipSuccess) return IA_ERR_LAUNCH;
-    attr_set = true;
-  }
-  const long ntiles = (long)a.B * a.tiles_x * a.tiles_y;
-  const int per_cu = (160 * 1024) / G::LDS_BYTES >= 2 ? 2 : 1;      // (the kernel's ~220 registers allow two workgroups per CU)
-  long per_group = (256L * per_cu) / a.groups;
-  if (per_group > ntiles) per_group = ntiles;
-  if (per_group < 1) per_group = 1;
+  static bool lds_set = false;
+  if (const int rc = allow_lds((const void*)kern, G::LDS_BYTES, lds_set)) return rc;
+  const long per_group = slots_per_group(G::LDS_BYTES, a.groups, (long)a.B * a.tiles_x * a.tiles_y);
   hipLaunchKernelGGL(kern, dim3((unsigned)(per_group * a.groups)), dim3(256), G::LDS_BYTES, stream, a);
   return ia_check_launch();
 }
@@ -1418,13 +1390,10 @@ static int launch(const void* xp, const void* w, const float* bias, void* yp, in
   Args a;
   a.xp = (const bf16*)xp; a.w = (const bf16*)w; a.bias = bias; a.yp = (bf16*)yp;
   a.B = B; a.H = H; a.W = W; a.Cin = groups * ci; a.Cout = groups * co; a.groups = groups;
-  a.tiles_x = (W + TW - 1) / TW; a.tiles_y = (H + TH - 1) / TH;
-  { static int dbg = -1; if (dbg < 0) { const char* e = getenv("IA_CONV_DBG"); dbg = e ? atoi(e) : 0; } a.dbg = dbg; }
-  if (ci == 64 && co == 64) return launch_t<64, 64>(a, stream);
-  if (ci == 16 && co == 32) return launch_t<16, 32>(a, stream);
-  if (ci == 32 && co == 64) return launch_t<32, 64>(a, stream);
-  if (ci == 64 && co == 32) return launch_t<64, 32>(a, stream);
-  if (ci == 32 && co == 16) return launch_t<32, 16>(a, stream);
+  tiles_of(H, W, a.tiles_x, a.tiles_y);
+#define X(CI, CO) if (ci == CI && co == CO) return launch_t<CI, CO>(a, stream);
+  DCONV_PAIRS(X)
+#undef X
   return IA_ERR_UNSUPPORTED;
 }
 // ---------------------------------------------------------------------------------------------- direct weight gradient
@@ -1462,18 +1431,16 @@ struct WArgs {
   const bf16* xp; const bf16* dyp; float* part;      // part: [workgroups][CO * 9 * CI + CO] fp32 partial banks (+ bias sums)
   int B, H, W, Cin, Cout, groups;                    // H, W: height / width of dy
   int tiles_x, tiles_y;
-  // x as a strided view (the stride-2 convolution's weight gradient, below): bordered x pixel of view pixel (r, c) = (xs r + offy, xs c + offx)
-  // in a tensor of XH x XW interior pixels; group g reads channels g * in_gstride ..  Stride 1: xs = 1, off = 0, XH = H, XW = W, in_gstride = CI.
-  int XH, XW, xs, offy, offx, in_gstride;
+  // read by conv3x3_wgrad_s2_kernel alone (the stride-1 kernel has x of dy's size, group g at channels g * CI, and a bordered dy):
+  int XH, XW;                  // x has XH x XW interior pixels (H = (XH - 1) / 2 + 1)
+  int unused[3];               // (the strided view of the four-launch form; closing the gap moves the two fields below in the kernel
+                               // arguments, and hipcc then allocates conv3x3_wgrad_s2_kernel's scalar registers differently)
+  int in_gstride;              // group g reads x's channels g * in_gstride ..
   int dy_compact;              // dyp is [B, H, W, Cout] without a border
 };
 
-// TAPS: bit t = kernel tap t is wanted (a parity view of the stride-2 form needs 1, 2 or 4 of the nine).  A compile-time mask: a run-time
-// branch around the transpose reads is a merge point at which hipcc copies the fragment registers before the data has arrived
-// (tools/lint_asm_waits.py caught exactly that); with CI = 64 a wave's j-th column block IS tap j, so the mask folds away.
-template <int CI, int CO, int TAPS = 0x1FF>
+template <int CI, int CO>
 __global__ __launch_bounds__(256) void conv3x3_wgrad_kernel(WArgs p) {
-  static_assert(TAPS == 0x1FF || CI == 64, "tap masks need the block <-> tap identity of CI = 64");
   using G = WGeo<CI, CO>;
   // (every Geo constant used inside the lambdas is copied to a local first: `X_BYTES` written inside an argument of the LDS-DMA
   // builtin made hipcc drop this kernel's host launch stub -- undefined symbol at load time, tests/test_cabi_symbols.py)
@@ -1489,23 +1456,21 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_kernel(WArgs p) {
   typedef __attribute__((address_space(3))) char lds_char;
   lds_char* const lsm = (lds_char*)IA_LDS(smem);
   const uint32_t sbase = ia_lds_addr(smem);
-  const int XPW = p.XW + 2, XPH = p.XH + 2;
-  const int YW = p.dy_compact ? p.W : PW, YH = p.dy_compact ? p.H : PH, yo = p.dy_compact ? 1 : 0;      // dy's own row pitch / origin shift
-  const size_t total_x = (size_t)p.B * XPH * XPW * p.Cin, total_y = (size_t)p.B * YH * YW * p.Cout;
+  const size_t total_x = (size_t)p.B * PH * PW * p.Cin, total_y = (size_t)p.B * PH * PW * p.Cout;
 
   auto tile_of = [&](int t, int& b, int& y0, int& x0) {
     const int tx = t % p.tiles_x, r = t / p.tiles_x;
     const int ty = r % p.tiles_y;
     b = r / p.tiles_y; y0 = 1 + ty * TH; x0 = 1 + tx * TW;
   };
-  const uint32_t lane_x = (uint32_t)(((lane / XNC) * p.xs * p.Cin + (((lane % XNC) ^ tkey<CI>(lane / XNC)) * 8)) * 2);
+  const uint32_t lane_x = (uint32_t)(((lane / XNC) * p.Cin + (((lane % XNC) ^ tkey<CI>(lane / XNC)) * 8)) * 2);
   const int ypix = lane / YNC;                               // pixel of this lane inside a dy piece
   const uint32_t lane_y = (uint32_t)((ypix * p.Cout + (((lane % YNC) ^ tkey<CO>(ypix)) * 8)) * 2);
   auto stage = [&](int t, int buf) {
     int b, y0, x0;
     tile_of(t, b, y0, x0);
     {   // x tile: rows y0 - 1 .. y0 + 8, pixels x0 - 1 .. x0 + 30 (as the forward kernel)
-      const size_t org = (((size_t)b * XPH + p.xs * (y0 - 1) + p.offy) * XPW + p.xs * (x0 - 1) + p.offx) * p.Cin + (size_t)grp * p.in_gstride;
+      const size_t org = (((size_t)b * PH + (y0 - 1)) * PW + (x0 - 1)) * p.Cin + (size_t)grp * CI;
       const size_t rem = org < total_x ? (total_x - org) * 2 : 0;
       const __amdgpu_buffer_rsrc_t rs = ia_rsrc(p.xp + (rem ? org : 0), (uint32_t)(rem < 0x7FFFFFF0ull ? rem : 0x7FFFFFF0ull));
       constexpr int PPP = 64 / XNC;
@@ -1516,13 +1481,13 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_kernel(WArgs p) {
           const int r = pc / (TWP / PPP), c = pc - r * (TWP / PPP);
           // whole address in the lane offset (range-checked; see the forward kernel): x past the end of the tensor arrives as zeros --
           // read through the scalar offset it was whatever lies behind the allocation, and 0 (masked dy) x NaN = NaN in dW
-          const uint32_t adv = (uint32_t)((r * XPW + c * PPP) * p.xs * p.Cin * 2);
+          const uint32_t adv = (uint32_t)((r * PW + c * PPP) * p.Cin * 2);
           __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, lsm + buf * STAGE + pc * 1024, 16, lane_x + adv, 0, 0, 0);
         }
       }
     }
     {   // dy tile: rows y0 .. y0 + 7, pixels x0 .. x0 + 31; pixels 30, 31 of a row, pixels right of the image and rows below it -> zeros
-      const size_t org = (((size_t)b * YH + (y0 - yo)) * YW + (x0 - yo)) * p.Cout + (size_t)grp * CO;
+      const size_t org = (((size_t)b * PH + y0) * PW + x0) * p.Cout + (size_t)grp * CO;
       const size_t rem = (total_y - org) * 2;
       const __amdgpu_buffer_rsrc_t rs = ia_rsrc(p.dyp + org, (uint32_t)(rem < 0x7FFFFFF0ull ? rem : 0x7FFFFFF0ull));
       constexpr int PPP = 64 / YNC;
@@ -1533,7 +1498,7 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_kernel(WArgs p) {
           const int r = pc / (TWP / PPP), c = pc - r * (TWP / PPP);
           const int col = c * PPP + ypix;
           const bool ok = col < TW && x0 + col <= p.W && y0 + r <= p.H;
-          const uint32_t voff = ok ? lane_y + (uint32_t)((r * YW + c * PPP) * p.Cout * 2) : 0xFFFFFFF0u;
+          const uint32_t voff = ok ? lane_y + (uint32_t)((r * PW + c * PPP) * p.Cout * 2) : 0xFFFFFFF0u;
           __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, lsm + buf * STAGE + X_BYTES + pc * 1024, 16, voff, 0, 0, 0);
         }
       }
@@ -1581,7 +1546,7 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_kernel(WArgs p) {
       for (int j = 0; j < NBW; ++j) {
         const int nb = wave + 4 * j < NB ? wave + 4 * j : NB - 1;      // column block (tap, 16 input channels), wave-uniform (clamped: unused)
         const int tap = nb / (CI / 16), cb = nb - tap * (CI / 16);
-        if (TAPS == 0x1FF || ((TAPS >> j) & 1)) bf[set][j] = tr_pair<CI>(xs, r * TWP + tpx + (tap / 3) * TWP + tap % 3, cb * 16 + tch);
+        bf[set][j] = tr_pair<CI>(xs, r * TWP + tpx + (tap / 3) * TWP + tap % 3, cb * 16 + tch);
       }
     };
     load(0, 0);
@@ -1593,7 +1558,7 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_kernel(WArgs p) {
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int j = 0; j < NBW; ++j)
-        if (wave + 4 * j < NB && (TAPS == 0x1FF || ((TAPS >> j) & 1))) {
+        if (wave + 4 * j < NB) {
 #pragma unroll
           for (int mi = 0; mi < MB; ++mi) acc[mi][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[r & 1][j], af[r & 1][mi], acc[mi][j], 0, 0, 0);
         }
@@ -1622,7 +1587,8 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_kernel(WArgs p) {
 // The stride-2 form in ONE launch (64 -> 64 channels per group): work list (tile, parity view of x) as in the forward kernel -- the dy tile is
 // fetched once per tile and serves the four views, the x buffers alternate per view, and every view's taps accumulate straight into the
 // column blocks of the REAL taps (rows even: kernel tap ty -> dy = 2 ty; rows odd: ty = 0 -> dy = 1; the same for the columns), so the bank has
-// the stride-1 layout and the stride-1 fold applies.  Against four masked launches: dy read once instead of four times, one launch.
+// the stride-1 layout and the stride-1 fold applies.  (It replaced four launches of the stride-1 kernel, one per view with its taps masked
+// and a fold that dropped the other 27 tap sums: dy read once instead of four times, one launch -- DESIGN.md round 6.)
 __global__ __launch_bounds__(256) void conv3x3_wgrad_s2_kernel(WArgs p) {
   constexpr int CI = 64, CO = 64;
   using G = WGeo<CI, CO>;
@@ -1773,127 +1739,48 @@ __global__ __launch_bounds__(256) void wgrad_fold_kernel(const float* __restrict
   else if (dbias) dbias[grp * (bank - wsize) + (e - wsize)] += sum;
 }
 
-// the stride-2 form: four launches of the weight-gradient kernel, one per parity view of x (view v = 2 (rows odd) + (columns odd)), each with
-// its own region of `part`; tap (dy, dx) of the convolution is kernel tap (ty, tx) of one view -- dy = 0 -> (rows even, ty = 0), dy = 1 ->
-// (rows odd, ty = 0), dy = 2 -> (rows even, ty = 1), the same for the columns -- the other 27 tap sums the four launches produce are dropped
-__global__ __launch_bounds__(256) void wgrad_fold_s2_kernel(const float* __restrict__ part, float* __restrict__ dwhat, float* __restrict__ dbias, int groups,
-                                                            int per_group, int bank, int wsize, int CI, size_t region) {
-  const int idx = blockIdx.x * 256 + threadIdx.x;      // element of [groups][bank]
-  if (idx >= groups * bank) return;
-  const int grp = idx / bank, e = idx - grp * bank;
-  int v = 0, src = e;
-  if (e < wsize) {
-    const int co = e / (9 * CI), rest = e - co * (9 * CI), tap = rest / CI, ci = rest - tap * CI;
-    const int dy = tap / 3, dx = tap - dy * 3;
-    v = ((dy == 1) << 1) | (dx == 1);
-    const int tk = (dy == 2 ? 3 : 0) + (dx == 2 ? 1 : 0);
-    src = co * (9 * CI) + tk * CI + ci;
-  }
-  const float* pv = part + (size_t)v * region;
-  float sum = 0.f;
-  for (int s = 0; s < per_group; ++s) sum += pv[(size_t)(s * groups + grp) * bank + src];
-  if (e < wsize) dwhat[(size_t)grp * wsize + e] = sum;
-  else if (dbias) dbias[grp * (bank - wsize) + (e - wsize)] += sum;
-}
-
-// IA_CONV_S2_WGRAD_MERGED=0: the four masked view launches instead of the one-launch kernel (read per call: A/B in one process)
-static bool wgrad_s2_merged() {
-  const char* e = getenv("IA_CONV_S2_WGRAD_MERGED");
-  return !e || atoi(e) != 0;
-}
-template <int TAPS>
-static int wgrad_view_launch(const WArgs& a, unsigned grid, hipStream_t stream) {
-  using G = WGeo<64, 64>;
-  auto kern = conv3x3_wgrad_kernel<64, 64, TAPS>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES) != hipSuccess) return IA_ERR_LAUNCH;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), G::LDS_BYTES, stream, a);
-  return IA_OK;
-}
-
-template <int CI, int CO>
-static int wgrad_t(WArgs a, float* dwhat, float* dbias, hipStream_t stream) {
-  using G = WGeo<CI, CO>;
-  auto kern = conv3x3_wgrad_kernel<CI, CO>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES) != hipSuccess) return IA_ERR_LAUNCH;
-    attr_set = true;
-  }
-  const long ntiles = (long)a.B * a.tiles_x * a.tiles_y;
-  const int per_cu = (160 * 1024) / G::LDS_BYTES >= 2 ? 2 : 1;
-  long per_group = (256L * per_cu) / a.groups;
-  if (per_group > ntiles) per_group = ntiles;
-  if (per_group < 1) per_group = 1;
-  const int wsize = CO * 9 * CI, bank = wsize + CO;
-  if (a.xs == 2 && wgrad_s2_merged()) {
-    if constexpr (CI == 64 && CO == 64) {
-      auto k2 = conv3x3_wgrad_s2_kernel;
-      static bool attr2 = false;
-      if (!attr2) {
-        if (hipFuncSetAttribute((const void*)k2, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES) != hipSuccess) return IA_ERR_LAUNCH;
-        attr2 = true;
-      }
-      hipLaunchKernelGGL(k2, dim3((unsigned)(per_group * a.groups)), dim3(256), G::LDS_BYTES, stream, a);
-      hipLaunchKernelGGL(wgrad_fold_kernel, dim3((a.groups * bank + 255) / 256), dim3(256), 0, stream, a.part, dwhat, dbias, a.groups, (int)per_group, bank, wsize);
-      return ia_check_launch();
-    } else {
-      return IA_ERR_UNSUPPORTED;
-    }
-  }
-  if (a.xs == 2) {
-    const size_t region = (size_t)per_group * a.groups * bank;
-    float* const part = a.part;
-    if constexpr (CI == 64 && CO == 64) {
-      for (int v = 0; v < 4; ++v) {      // taps wanted: rows even -> ty = 0, 1, rows odd -> ty = 0; the same for the columns (tap = 3 ty + tx)
-        a.offy = v >> 1; a.offx = v & 1; a.part = part + (size_t)v * region;
-        const unsigned grid = (unsigned)(per_group * a.groups);
-        const int rc = v == 0 ? wgrad_view_launch<0x1B>(a, grid, stream) : v == 1 ? wgrad_view_launch<0x09>(a, grid, stream)
-                     : v == 2 ? wgrad_view_launch<0x03>(a, grid, stream) : wgrad_view_launch<0x01>(a, grid, stream);
-        if (rc) return rc;
-      }
-    } else {
-      return IA_ERR_UNSUPPORTED;
-    }
-    hipLaunchKernelGGL(wgrad_fold_s2_kernel, dim3((a.groups * bank + 255) / 256), dim3(256), 0, stream, part, dwhat, dbias, a.groups, (int)per_group, bank,
-                       wsize, CI, region);
-    return ia_check_launch();
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)(per_group * a.groups)), dim3(256), G::LDS_BYTES, stream, a);
+// a weight-gradient kernel over the tiles of `a`, then the fold of its workgroups' banks
+static int wgrad_launch(void (*kern)(WArgs), int lds_bytes, bool& lds_set, int ci, int co, const WArgs& a, float* dwhat, float* dbias, hipStream_t stream) {
+  if (const int rc = allow_lds((const void*)kern, lds_bytes, lds_set)) return rc;
+  const long per_group = slots_per_group(lds_bytes, a.groups, (long)a.B * a.tiles_x * a.tiles_y);
+  const int wsize = co * 9 * ci, bank = wsize + co;
+  hipLaunchKernelGGL(kern, dim3((unsigned)(per_group * a.groups)), dim3(256), lds_bytes, stream, a);
   hipLaunchKernelGGL(wgrad_fold_kernel, dim3((a.groups * bank + 255) / 256), dim3(256), 0, stream, a.part, dwhat, dbias, a.groups, (int)per_group, bank, wsize);
   return ia_check_launch();
 }
+template <int CI, int CO>
+static int wgrad_t(const WArgs& a, float* dwhat, float* dbias, hipStream_t stream) {
+  static bool lds_set = false;
+  return wgrad_launch(conv3x3_wgrad_kernel<CI, CO>, WGeo<CI, CO>::LDS_BYTES, lds_set, CI, CO, a, dwhat, dbias, stream);
+}
 static size_t wgrad_workspace(int ci, int co, int groups) {
-  const int per_cu = 2;                                        // upper bound of wgrad_t's choice
+  const int per_cu = 2;                                        // upper bound of slots_per_group's choice
   return (size_t)((256L * per_cu) / groups) * groups * ((size_t)co * 9 * ci + co) * sizeof(float);
 }
 static int wgrad(const void* xp, const void* dyp, float* dwhat, float* dbias, int B, int H, int W, int ci, int co, int groups, void* ws, hipStream_t stream) {
-  WArgs a;
+  WArgs a{};
   a.xp = (const bf16*)xp; a.dyp = (const bf16*)dyp; a.part = (float*)ws;
   a.B = B; a.H = H; a.W = W; a.Cin = groups * ci; a.Cout = groups * co; a.groups = groups;
-  a.tiles_x = (W + TW - 1) / TW; a.tiles_y = (H + TH - 1) / TH;
-  a.XH = H; a.XW = W; a.xs = 1; a.offy = a.offx = 0; a.in_gstride = ci; a.dy_compact = 0;
-  if (ci == 64 && co == 64) return wgrad_t<64, 64>(a, dwhat, dbias, stream);
-  if (ci == 16 && co == 32) return wgrad_t<16, 32>(a, dwhat, dbias, stream);
-  if (ci == 32 && co == 64) return wgrad_t<32, 64>(a, dwhat, dbias, stream);
+  tiles_of(H, W, a.tiles_x, a.tiles_y);
+#define X(CI, CO) if (ci == CI && co == CO) return wgrad_t<CI, CO>(a, dwhat, dbias, stream);
+  DCONV_WGRAD_PAIRS(X)
+#undef X
   return IA_ERR_UNSUPPORTED;
 }
 // stride 2, 64 -> 64 channels per group: x [B, XH + 2, XW + 2, Cin] bordered, dy [B, H + 2, W + 2, Cout] bordered (H = (XH - 1) / 2 + 1);
 // shared_input: every output group reads input channels 0 .. 63 (Cin = 64)
 static int wgrad_s2(const void* xp, const void* dyp, float* dwhat, float* dbias, int B, int XH, int XW, int Cin, int Cout, int groups, int shared_input,
                     int dy_compact, void* ws, hipStream_t stream) {
-  WArgs a;
+  WArgs a{};
   a.xp = (const bf16*)xp; a.dyp = (const bf16*)dyp; a.part = (float*)ws;
   a.H = (XH - 1) / 2 + 1; a.W = (XW - 1) / 2 + 1;
   a.B = B; a.Cin = Cin; a.Cout = Cout; a.groups = groups;
-  a.tiles_x = (a.W + TW - 1) / TW; a.tiles_y = (a.H + TH - 1) / TH;
-  a.XH = XH; a.XW = XW; a.xs = 2; a.offy = a.offx = 0; a.in_gstride = shared_input ? 0 : 64; a.dy_compact = dy_compact;
-  return wgrad_t<64, 64>(a, dwhat, dbias, stream);
+  tiles_of(a.H, a.W, a.tiles_x, a.tiles_y);
+  a.XH = XH; a.XW = XW; a.in_gstride = shared_input ? 0 : 64; a.dy_compact = dy_compact;
+  static bool lds_set = false;
+  return wgrad_launch(conv3x3_wgrad_s2_kernel, WGeo<64, 64>::LDS_BYTES, lds_set, 64, 64, a, dwhat, dbias, stream);
 }
-static size_t wgrad_s2_workspace(int groups) { return 4 * wgrad_workspace(64, 64, groups); }
+static size_t wgrad_s2_workspace(int groups) { return wgrad_workspace(64, 64, groups); }
 
 // slices > 1: groups = 1, Cin = 64, Cout = 64 * slices; wt = `slices` banks back to back (ia_conv3x3_flip_weights with groups = slices)
 static int launch_s2_dgrad(const void* gp, const void* wt, void* dxp, int B, int H, int W, int Cin, int Cout, int groups, int slices, int g_compact,
@@ -1902,18 +1789,12 @@ static int launch_s2_dgrad(const void* gp, const void* wt, void* dxp, int B, int
   a.gp = (const bf16*)gp; a.wt = (const bf16*)wt; a.dxp = (bf16*)dxp;
   a.B = B; a.H = H; a.W = W; a.Ho = (H - 1) / 2 + 1; a.Wo = (W - 1) / 2 + 1;
   a.Cin = Cin; a.Cout = Cout; a.groups = groups; a.g_choff = 0; a.accumulate = 0; a.g_compact = g_compact;
-  a.tiles_x = (a.Wo + TW - 1) / TW; a.tiles_y = (a.Ho + TH - 1) / TH;      // cells: ceil(H / 2) x ceil(W / 2) = Ho x Wo
+  tiles_of(a.Ho, a.Wo, a.tiles_x, a.tiles_y);                  // cells: ceil(H / 2) x ceil(W / 2) = Ho x Wo
   using G = Geo<64, 64>;
   auto kern = conv3x3_s2_dgrad_kernel;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES) != hipSuccess) return IA_ERR_LAUNCH;
-    attr_set = true;
-  }
-  const long ntiles = (long)a.B * a.tiles_x * a.tiles_y;
-  long per_group = 256L / groups;
-  if (per_group > ntiles) per_group = ntiles;
-  if (per_group < 1) per_group = 1;
+  static bool lds_set = false;
+  if (const int rc = allow_lds((const void*)kern, G::LDS_BYTES, lds_set)) return rc;
+  const long per_group = slots_per_group(G::LDS_BYTES, groups, (long)a.B * a.tiles_x * a.tiles_y);
   for (int sl = 0; sl < slices; ++sl) {
     a.g_choff = sl * 64; a.accumulate = sl > 0; a.wt = (const bf16*)wt + (size_t)sl * 64 * 9 * 64;
     hipLaunchKernelGGL(kern, dim3((unsigned)(per_group * groups)), dim3(256), G::LDS_BYTES, stream, a);
@@ -1928,22 +1809,15 @@ static int launch_s2(const void* xp, const void* w, const float* bias, void* yp,
   a.xp = (const bf16*)xp; a.w = (const bf16*)w; a.bias = bias; a.yp = (bf16*)yp;
   a.B = B; a.XH = XH; a.XW = XW; a.H = (XH - 1) / 2 + 1; a.W = (XW - 1) / 2 + 1;
   a.Cin = Cin; a.Cout = Cout; a.groups = groups; a.in_gstride = shared_input ? 0 : 64; a.out_compact = out_compact;
-  a.tiles_x = (a.W + TW - 1) / TW; a.tiles_y = (a.H + TH - 1) / TH;
+  tiles_of(a.H, a.W, a.tiles_x, a.tiles_y);
   using G = Geo<64, 64>;
   auto kern = conv3x3_s2_kernel<64>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES) != hipSuccess) return IA_ERR_LAUNCH;
-    attr_set = true;
-  }
-  const long ntiles = (long)a.B * a.tiles_x * a.tiles_y;
-  long per_group = 256L / groups;
-  if (per_group > ntiles) per_group = ntiles;
-  if (per_group < 1) per_group = 1;
+  static bool lds_set = false;
+  if (const int rc = allow_lds((const void*)kern, G::LDS_BYTES, lds_set)) return rc;
+  const long per_group = slots_per_group(G::LDS_BYTES, groups, (long)a.B * a.tiles_x * a.tiles_y);
   hipLaunchKernelGGL(kern, dim3((unsigned)(per_group * groups)), dim3(256), G::LDS_BYTES, stream, a);
   return ia_check_launch();
 }
-static bool wgrad_ok(int ci, int co) { return (ci == 64 && co == 64) || (ci == 16 && co == 32) || (ci == 32 && co == 64); }
 }  // namespace dconv
 
 static int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
@@ -1963,7 +1837,9 @@ extern "C" int ia_conv3x3_padded_fwd(const void* xp, const void* what, const flo
   if (!xp || !what || !yp) return IA_ERR_ARG;
   const size_t Mp = (size_t)B * (H + 2) * (W + 2);
   const int ci = Cin / groups, co = Cout / groups;
-  if (dconv::pair_ok(ci, co) && groups <= 64 && dconv::enabled()) return dconv::launch(xp, what, bias, yp, B, H, W, ci, co, groups, stream);
+  // the direct kernels wherever they are built (C3: 406.5 pairs/s on the shifted-view GEMMs -> 456.6 with the direct forward and data
+  // gradient -> 469.7 with the direct weight gradient); every other channel pair keeps the view GEMM
+  if (dconv::pair_ok(ci, co) && groups <= 64) return dconv::launch(xp, what, bias, yp, B, H, W, ci, co, groups, stream);
   IaViewGemm v{};
   v.A = xp; v.lda = Cin; v.B = what; v.ldb = 9 * ci; v.C = yp; v.ldc = Cout;
   v.M = (int)Mp; v.N = co; v.K = 9 * ci; v.bias = bias;
@@ -1994,7 +1870,7 @@ extern "C" int ia_conv3x3_padded_bwd_data(const void* dyp, const void* what, voi
 // tap-flipped, transposed filter bank written by ia_conv3x3_flip_weights.  Other shapes: IA_ERR_UNSUPPORTED (ia_conv3x3_padded_bwd_data).
 extern "C" int ia_conv3x3_direct_supported(int Cin, int Cout, int groups) {
   return groups > 0 && groups <= 64 && Cin % groups == 0 && Cout % groups == 0 && dconv::pair_ok(Cin / groups, Cout / groups) &&
-         dconv::pair_ok(Cout / groups, Cin / groups) && dconv::enabled();
+         dconv::pair_ok(Cout / groups, Cin / groups);
 }
 extern "C" int ia_conv3x3_flip_weights(const void* what, void* what_t, int Cin, int Cout, int groups, hipStream_t stream) {
   (void)hipGetLastError();
@@ -2035,7 +1911,7 @@ extern "C" int ia_conv3x3_padded_bwd_weight(const void* xp, const void* dyp, flo
   const int ci = Cin / groups, co = Cout / groups;
   // (small maps keep the split-K GEMM: with a handful of tiles per workgroup the per-workgroup banks and their fold cost more than they
   // save -- 25 x 25: 0.049 against 0.036 ms at 32 images)
-  if (dconv::wgrad_ok(ci, co) && groups <= 64 && (size_t)B * H * W >= dconv::wgrad_min_pixels() && dconv::enabled() && dconv::wgrad_enabled())
+  if (dconv::wgrad_ok(ci, co) && groups <= 64 && (size_t)B * H * W >= dconv::wgrad_min_pixels())
     return dconv::wgrad(xp, dyp, dwhat, dbias, B, H, W, ci, co, groups, workspace, stream);
   IaViewGemm v{};
   v.A = dyp; v.a_kstrided = 1; v.lda = Cout; v.B = xp; v.b_kstrided = 1; v.ldb = Cin; v.C = dwhat; v.c_is_f32 = 1; v.ldc = 9 * ci;
@@ -2047,18 +1923,14 @@ extern "C" int ia_conv3x3_padded_bwd_weight(const void* xp, const void* dyp, flo
   return ia_gemm_view(v, stream);
 }
 
-// y = silu(x) * scale moving between the compact [B,H,W,C] and the zero-bordered [B,H+2,W+2,C] layouts (flags per side)
 // ---------------------------------------------------------------------------------------------- 3x3 / stride 2 on the bordered domain
 // xp [B, H + 2, W + 2, Cin] (zero border) -> yp [B, Ho + 2, Wo + 2, Cout] (border not written; y_compact: [B, Ho, Wo, Cout], and so
-// is dyp), Ho = (H - 1) / 2 + 1: the strided
-// convolutions of the NF-Net stage transitions (64 -> 64 channels per group) and of its stem (64 -> 128: output halves over one shared input
-// slice) without a patch matrix -- forward by dconv::conv3x3_s2_kernel, weight gradient by four launches of the direct weight-gradient
-// kernel on the parity views of x; the data gradient keeps the GEMM + gather form, between bordered layouts.  IA_CONV_S2_DIRECT=0 reports
-// every shape as unsupported (callers fall back to ia_conv_nhwc_*).
-static bool s2_enabled() {
-  const char* e = getenv("IA_CONV_S2_DIRECT");
-  return !e || atoi(e) != 0;
-}
+// is dyp), Ho = (H - 1) / 2 + 1: the strided convolutions of the NF-Net stage transitions (64 -> 64 channels per group) and of its stem
+// (64 -> 128: output halves over one shared input slice) without a patch matrix -- forward by dconv::conv3x3_s2_kernel over the four
+// parity views of x, weight gradient by dconv::conv3x3_wgrad_s2_kernel over the same views, data gradient by
+// dconv::conv3x3_s2_dgrad_kernel over the four parity classes of dx.  (Against the patch-matrix path of ia_conv_nhwc_*: C3 +8.8 % on one
+// box; the data gradient had a GEMM + gather form first, 521 -> 536 pairs/s -- DESIGN.md round 6.)  Other shapes are reported as
+// unsupported and go through ia_conv_nhwc_*.
 // virtual groups of 64 output channels; *shared = every one of them reads input channels 0 .. 63
 static int s2_groups(int Cin, int Cout, int groups, int* shared) {
   *shared = 0;
@@ -2068,7 +1940,7 @@ static int s2_groups(int Cin, int Cout, int groups, int* shared) {
 }
 extern "C" int ia_conv3x3_s2_supported(int Cin, int Cout, int groups) {
   int shared;
-  return dconv::enabled() && dconv::wgrad_enabled() && s2_enabled() && s2_groups(Cin, Cout, groups, &shared) > 0;
+  return s2_groups(Cin, Cout, groups, &shared) > 0;
 }
 static int s2_ok(int B, int H, int W, int Cin, int Cout, int groups, int* vg, int* shared) {
   if (B <= 0 || H <= 0 || W <= 0 || groups <= 0 || Cin <= 0 || Cout <= 0) return IA_ERR_ARG;
@@ -2080,9 +1952,7 @@ static int s2_ok(int B, int H, int W, int Cin, int Cout, int groups, int* vg, in
 extern "C" size_t ia_conv3x3_s2_padded_workspace_bytes(int B, int H, int W, int Cin, int Cout, int groups) {
   int vg, shared;
   if (s2_ok(B, H, W, Cin, Cout, groups, &vg, &shared)) return 0;
-  const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-  const size_t dcols = (size_t)B * (Ho + 2) * (Wo + 2) * 9 * Cin * 2, wg = dconv::wgrad_s2_workspace(vg);
-  return dcols > wg ? dcols : wg;
+  return dconv::wgrad_s2_workspace(vg);
 }
 extern "C" int ia_conv3x3_s2_padded_fwd(const void* xp, const void* what, const float* bias, void* yp, int B, int H, int W, int Cin, int Cout,
                                         int groups, int y_compact, hipStream_t stream) {
@@ -2104,39 +1974,10 @@ extern "C" int ia_conv3x3_s2_padded_bwd_weight(const void* xp, const void* dyp, 
   if (!workspace || workspace_bytes < dconv::wgrad_s2_workspace(vg)) return IA_ERR_WORKSPACE;
   return dconv::wgrad_s2(xp, dyp, dwhat, dbias, B, H, W, Cin, Cout, vg, shared, y_compact, workspace, stream);
 }
-// dxp [B, H + 2, W + 2, Cin] (interior written) from dyp [B, Ho + 2, Wo + 2, Cout] (border rows may hold anything finite)
-extern "C" int ia_conv3x3_s2_padded_bwd_data(const void* dyp, const void* what, void* dxp, int B, int H, int W, int Cin, int Cout, int groups,
-                                             int y_compact, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  (void)hipGetLastError();
-  int vg, shared;
-  int rc = s2_ok(B, H, W, Cin, Cout, groups, &vg, &shared);
-  if (rc) return rc;
-  if (!dyp || !what || !dxp) return IA_ERR_ARG;
-  const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, Cg = Cin / groups, Ng = Cout / groups, K = 9 * Cg;
-  const size_t Mp = y_compact ? (size_t)B * Ho * Wo : (size_t)B * (Ho + 2) * (Wo + 2);
-  if (!workspace || workspace_bytes < Mp * 9 * Cin * 2) return IA_ERR_WORKSPACE;
-  bf16* dcols = (bf16*)workspace;
-  for (int gi = 0; gi < groups && !rc; ++gi)
-    rc = ia_gemm_bf16((const bf16*)dyp + gi * Ng, 0, Cout, (const bf16*)what + (size_t)gi * Ng * K, 1, K, dcols + (size_t)gi * K, 0, 9 * Cin, (int)Mp, K,
-                      Ng, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, stream);
-  if (rc) return rc;
-  const size_t total = (size_t)B * H * W * (Cin >> 3);
-  hipLaunchKernelGGL(col2im3_s2_padded_kernel, dim3(blocks_of(total)), dim3(256), 0, stream, dcols, (bf16*)dxp, H, W, Cin, Cg, Ho, Wo, y_compact, total);
-  return ia_check_launch();
-}
-
-// The data gradient without the patch-matrix detour (ia_conv3x3_s2_dgrad_supported): Cin = Cout = 64 * groups (the stage transitions), and
-// groups = 1, Cin = 64, Cout = 64 n (the stem) as n launches over the 64-channel slices of dy that add up in dx -- there what_t holds n
-// banks, ia_conv3x3_flip_weights(what, what_t, Cout, Cout, n).
+// The data gradient: Cin = Cout = 64 * groups (the stage transitions), and groups = 1, Cin = 64, Cout = 64 n (the stem) as n launches over
+// the 64-channel slices of dy that add up in dx -- there what_t holds n banks, ia_conv3x3_flip_weights(what, what_t, Cout, Cout, n).
 // what_t = the tap-flipped transposed bank of ia_conv3x3_flip_weights, dyp compact (y_compact) or bordered [B, Ho + 2, Wo + 2, Cout] with a ZERO border, dxp bordered
 // [B, H + 2, W + 2, Cin] (interior written)
-extern "C" int ia_conv3x3_s2_dgrad_supported(int Cin, int Cout, int groups) {
-  const char* e = getenv("IA_CONV_S2_DGRAD");                    // 0: off; 1: 64-channel groups only; default: the sliced 64 -> 64 n form too
-  const int mode = e ? atoi(e) : 2;
-  int shared;
-  const int vg = s2_groups(Cin, Cout, groups, &shared);
-  return mode > 0 && dconv::enabled() && s2_enabled() && vg > 0 && (!shared || mode > 1);
-}
 extern "C" int ia_conv3x3_s2_padded_bwd_data_t(const void* dyp, const void* what_t, void* dxp, int B, int H, int W, int Cin, int Cout, int groups,
                                                int y_compact, hipStream_t stream) {
   (void)hipGetLastError();
@@ -2148,6 +1989,7 @@ extern "C" int ia_conv3x3_s2_padded_bwd_data_t(const void* dyp, const void* what
                 : dconv::launch_s2_dgrad(dyp, what_t, dxp, B, H, W, Cin, Cout, vg, 1, y_compact, stream);
 }
 
+// y = silu(x) * scale moving between the compact [B,H,W,C] and the zero-bordered [B,H+2,W+2,C] layouts (flags per side)
 extern "C" int ia_silu_pad_fwd(const void* x, void* y, int B, int H, int W, int C, float scale, int in_padded, int out_padded, hipStream_t stream) {
   (void)hipGetLastError();
   if (!x || !y || B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 7)) return IA_ERR_ARG;

@@ -20,9 +20,6 @@ from .base import HipModule
 
 BF16, F32 = torch.bfloat16, torch.float32
 NONLIN_GAMMA_SILU = 1.7881293296813965          # timm nfnet.py _nonlin_gamma['silu']
-# stride-1 grouped 3x3 convolutions run as shifted-view GEMMs over a zero-bordered tensor; IA_CONV_PATCH_MATRIX=1 keeps the
-# gathered patch matrix for them too (A/B measurement switch, tools/config_bench.py)
-PADDED_CONV = os.environ.get("IA_CONV_PATCH_MATRIX", "0") != "1"
 FUSE_TAIL_ACT = os.environ.get("IA_NFNET_FUSE_TAIL", "1") != "0"   # a block's tail pass also writes the next block's opening activation (EcaResidualFn)
 FUSE_TAIL_BWD = os.environ.get("IA_NFNET_FUSE_TAIL", "1") == "1"   # ... and its backward folds SiLU' and the gate gradient's spatial sums into one pass
 ECA_LINEAR = os.environ.get("IA_ECA_LINEAR", "1") != "0"      # ECA pooling from conv3's input (EcaResidualFn); 0: the reduction over conv3's output
@@ -172,7 +169,7 @@ class PaddedStdConvFn(torch.autograd.Function):
 class PaddedS2ConvFn(torch.autograd.Function):
     """ScaledStdConv2d, 3x3 / stride 2 (64 channels per group, or the stem's 64 -> 128), from the zero-bordered domain at H x W to the
     bordered -- or, `y_compact`, the compact -- domain at ceil(H/2) x ceil(W/2) without a patch matrix (ia_conv3x3_s2_padded_*: forward over
-    the four parity views of x, weight gradient = the direct kernel on those views, data gradient = GEMM + gather).  Borders as for
+    the four parity views of x, weight gradient over the same views, data gradient over the four parity classes of dx).  Borders as for
     PaddedStdConvFn: the input's must be zero, the output's is garbage, the incoming gradient's is not read."""
 
     @staticmethod
@@ -208,20 +205,16 @@ class PaddedS2ConvFn(torch.autograd.Function):
         ws = _ws(dev, wsb)
         dxp = None
         if ctx.need_dx:
+            # one kernel over the four parity classes of dx, on the tap-flipped transposed bank (the incoming gradient's border is zero:
+            # the SiLU backward behind this convolution writes it)
             dxp = torch.empty_like(xp)
-            if lib.ia_conv3x3_s2_dgrad_supported(Cin, Cout, g):
-                # one kernel over the four parity classes of dx, on the tap-flipped transposed bank (the incoming gradient's border is zero:
-                # the SiLU backward behind this convolution writes it)
-                what_t = torch.empty((Cout, 9 * ci), device=dev, dtype=BF16)
-                if Cout == Cin:
-                    check(lib.ia_conv3x3_flip_weights(what.data_ptr(), what_t.data_ptr(), Cin, Cout, g, stream_ptr()), "ia_conv3x3_flip_weights")
-                else:       # the stem's 64 -> 128: one bank per 64-channel slice of dy (the flip sees them as groups of a 128 -> 128 layout)
-                    check(lib.ia_conv3x3_flip_weights(what.data_ptr(), what_t.data_ptr(), Cout, Cout, Cout // 64, stream_ptr()), "ia_conv3x3_flip_weights")
-                check(lib.ia_conv3x3_s2_padded_bwd_data_t(dyp.data_ptr(), what_t.data_ptr(), dxp.data_ptr(), B, H, W, Cin, Cout, g, yc, stream_ptr()),
-                      "ia_conv3x3_s2_padded_bwd_data_t")
-            else:
-                check(lib.ia_conv3x3_s2_padded_bwd_data(dyp.data_ptr(), what.data_ptr(), dxp.data_ptr(), B, H, W, Cin, Cout, g, yc, ws.data_ptr(), wsb,
-                                                        stream_ptr()), "ia_conv3x3_s2_padded_bwd_data")
+            what_t = torch.empty((Cout, 9 * ci), device=dev, dtype=BF16)
+            if Cout == Cin:
+                check(lib.ia_conv3x3_flip_weights(what.data_ptr(), what_t.data_ptr(), Cin, Cout, g, stream_ptr()), "ia_conv3x3_flip_weights")
+            else:       # the stem's 64 -> 128: one bank per 64-channel slice of dy (the flip sees them as groups of a 128 -> 128 layout)
+                check(lib.ia_conv3x3_flip_weights(what.data_ptr(), what_t.data_ptr(), Cout, Cout, Cout // 64, stream_ptr()), "ia_conv3x3_flip_weights")
+            check(lib.ia_conv3x3_s2_padded_bwd_data_t(dyp.data_ptr(), what_t.data_ptr(), dxp.data_ptr(), B, H, W, Cin, Cout, g, yc, stream_ptr()),
+                  "ia_conv3x3_s2_padded_bwd_data_t")
         if conv.weight.requires_grad:
             dwhat = torch.empty((Cout, 9 * ci), device=dev, dtype=F32)
             bg = conv.bias.grad.data_ptr() if conv.bias is not None and conv.bias.requires_grad else None
@@ -476,12 +469,12 @@ class ScaledStdConv2d(nn.Module):
     def shifted_views(self):
         """3x3 / stride 1 / power-of-two channels per group: runs without a patch matrix on the zero-bordered domain"""
         ci, co = self.in_channels // self.groups, self.out_channels // self.groups
-        return (PADDED_CONV and self.kernel_size == 3 and self.stride == 1 and ci >= 8 and co >= 8 and not (ci & (ci - 1)) and not (co & (co - 1)))
+        return (self.kernel_size == 3 and self.stride == 1 and ci >= 8 and co >= 8 and not (ci & (ci - 1)) and not (co & (co - 1)))
 
     @property
     def strided_direct(self):
         """3x3 / stride 2 with a shape the patch-matrix-free strided kernels take (64 channels per group; the stem's 64 -> 128)"""
-        return (PADDED_CONV and self.kernel_size == 3 and self.stride == 2
+        return (self.kernel_size == 3 and self.stride == 2
                 and bool(_lib.load().ia_conv3x3_s2_supported(self.in_channels, self.out_channels, self.groups)))
 
     def fits_padded(self, B, H, W):

@@ -27,7 +27,7 @@ from .. import _lib, ops
 from .._lib import check, ptr, stream_ptr
 from . import functional as Fn
 from .base import HipModule
-from .nfnet import PADDED_CONV, FeatureMap, GapFn, _ws, make_divisible
+from .nfnet import FeatureMap, GapFn, _ws, make_divisible
 
 BF16, F32 = torch.bfloat16, torch.float32
 
@@ -250,7 +250,7 @@ class Conv3x3Fn(torch.autograd.Function):
         C, Cout, s = conv.in_channels, conv.out_channels, conv.stride
         dev = x.device
         what = _packed_weight(conv, C, 9 * C)
-        padded = (PADDED_CONV and s == 1 and not (C & (C - 1)) and not (Cout & (Cout - 1)) and C >= 8 and Cout >= 8
+        padded = (s == 1 and not (C & (C - 1)) and not (Cout & (Cout - 1)) and C >= 8 and Cout >= 8
                   and B * (H + 2) * (W + 2) < 0x7FFFFFFF)
         ctx.padded = padded
         if padded:

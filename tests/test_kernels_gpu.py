@@ -1003,13 +1003,8 @@ def test_conv3x3_stride2_without_a_patch_matrix(gpu, B, H, W, Cin, Cout, groups,
     assert torch.isfinite(dwhat).all()
     assert rel_err(dwhat, dw_ref) < 2e-3 and rel_err(dbias - 0.5, br.grad) < 2e-3
     dyz = bordered(dy, 0.0)
-    dxp = torch.full((B, H + 2, W + 2, Cin), 9.0, device=gpu, dtype=torch.bfloat16)
-    check(lib.ia_conv3x3_s2_padded_bwd_data(dyz.data_ptr(), what.data_ptr(), dxp.data_ptr(), B, H, W, Cin, Cout, groups, yc, ws.data_ptr(), wsb, stream_ptr()),
-          "s2_dgrad")
-    assert rel_err(dxp[:, 1:-1, 1:-1], xr.grad.permute(0, 2, 3, 1)) < 2e-2
     # the one-kernel data gradient over the four parity classes of dx (flipped bank; zero-bordered or compact dy); the 64 -> 128 form runs
     # as two launches over the 64-channel slices of dy that add up in dx (one bf16 rounding more)
-    assert lib.ia_conv3x3_s2_dgrad_supported(Cin, Cout, groups) == 1
     what_t = torch.empty((Cout, 9 * Cg), device=gpu, dtype=torch.bfloat16)
     if Cin == Cout:
         check(lib.ia_conv3x3_flip_weights(what.data_ptr(), what_t.data_ptr(), Cin, Cout, groups, stream_ptr()), "flip")
