@@ -37,7 +37,7 @@ const char* ia_strerror(int code);
 /* Bumped whenever an entry point is added or the meaning of an argument / output changes (round 2 changed what IA_EPI_BIAS_GELU
  * stores in C2 and what IA_EPI_DGELU expects in aux): a caller built against another header must not run on this library.
  * item_alignment_amd/_lib.py refuses to load a library whose version differs from the one it was written for. */
-#define IA_ABI_VERSION 14
+#define IA_ABI_VERSION 15
 int ia_abi_version(void);
 
 /* ---- GEMM: torch.nn.Linear forward / dgrad / wgrad (src/models/text.py:1241 -> RobertaLayer dense
@@ -614,6 +614,40 @@ int ia_gcn_pair_gather_fwd(const float* x, const int32_t* idx, float* out, int R
  * summed in that order by a single writer. */
 int ia_gcn_pair_scatter_bwd(const float* dout, const int32_t* idx, const int32_t* order, float* dnode, int R, int C, int N, float drop_p,
                             uint32_t seed, uint32_t stream_id, ia_stream_t stream);
+
+/* ---- TextCNN tower (reference src/models/text.py:1496-1527; csrc/textcnn.hip).  (ABI 15)
+ * S filter sizes K_s (sizes: HOST array of S ints, S <= IA_TEXTCNN_MAX_SIZES), F filters each, NF = S * F features, NT = F * sum K_s
+ * taps, NTP = NT rounded up to a multiple of 8.  W / bias / dW / db are HOST arrays of S device pointers, one per filter size, in the
+ * layout of the reference's Conv2d(2, F, (K_s, H)): weight fp32 [F, 2, K_s, H], bias fp32 [F].  x_c [B * L, H] bf16 is the embedding
+ * LayerNorm output of channel c.  The convolution runs as two ia_gemm_bf16 calls, P [B * L, ldp] (fp32) = x_0 taps_0^T, then
+ * += x_1 taps_1^T (accumulate), against the tap shadow taps [2][NTP, H] bf16 whose row -- the column of P --
+ *     n(s, k, f) = F * (K_0 + .. + K_{s-1}) + k * F + f          (size index, then k, then f)
+ * holds W_s[f, c, k, :]; rows NT .. NTP-1 are zero.  pre[b, s, f, t] = bias_s[f] + sum_{k < K_s} P[b * L + t + k][n(s, k, f)].
+ * IA_ERR_ARG: L < max K_s (the reference's Conv2d raises there), H % 8 != 0, a non-positive count, a dropout rate outside [0, 1).
+ * The two dropouts (TextCNN.dropout, rate p1, and the pair head's own, rate p2) are independent draws on feature element
+ * e = b * NF + j, j = s * F + f, of streams stream_id1 / stream_id2: each keeps e iff the 16-bit half (e & 1) of its 32-bit draw at
+ * counter e >> 1 is >= round(p * 65536); an element both keep is scaled by 1 / ((1 - p1')(1 - p2')), p' = round(p * 65536) / 65536.
+ * A rate of 0 draws nothing.  The backward calls re-evaluate the masks from the same (seed, stream ids). */
+#define IA_TEXTCNN_MAX_SIZES 8
+/* fp32 conv weights -> taps (every element of [2][NTP, H] written); run after each optimiser step */
+int ia_textcnn_pack_taps(const float* const* W, const int* sizes, int S, int F, int H, void* taps, ia_stream_t stream);
+/* feat [B, NF] fp32 = dropouts(max_t relu(pre)), argmax [B, NF] int32 = the winning t, ties to the lowest t; a feature whose best
+ * pre-activation is <= 0 is exactly 0 with argmax -1 (it sends no gradient).  ldp >= NT. */
+int ia_textcnn_pool_fwd(const float* P, int ldp, const float* const* bias, const int* sizes, int S, int F, int B, int L, float p1,
+                        float p2, uint32_t seed, uint32_t stream_id1, uint32_t stream_id2, float* feat, int32_t* argmax,
+                        ia_stream_t stream);
+/* g [B, NF] fp32 = dloss/dfeat; g' = g * keep-and-scale where argmax >= 0, else 0.
+ * dW_s[f, c, k, :] = sum_b g'[b, j] x_c[b, argmax[b, j] + k, :], db_s[f] = sum_b g'[b, j] (db may be NULL): overwritten, b summed in
+ * index order, no atomics. */
+int ia_textcnn_pool_bwd_w(const float* g, const int32_t* argmax, const void* x0, const void* x1, const int* sizes, int S, int F, int B,
+                          int L, int H, float p1, float p2, uint32_t seed, uint32_t stream_id1, uint32_t stream_id2, float* const* dW,
+                          float* const* db, ia_stream_t stream);
+/* dx [B * L, H] bf16, every row written: dx[b, argmax[b, j] + k, :] = sum over the (s, f, k) that land there, in that order, of
+ * g'[b, j] W_s[f, 0, k, :], in fp32 with one bf16 rounding; rows no winning window covers are exactly zero.  Channel 0 only
+ * (embedding2 of the reference is frozen). */
+int ia_textcnn_pool_bwd_x(const float* g, const int32_t* argmax, const float* const* W, const int* sizes, int S, int F, int B, int L,
+                          int H, float p1, float p2, uint32_t seed, uint32_t stream_id1, uint32_t stream_id2, void* dx,
+                          ia_stream_t stream);
 
 /* ---- data-parallel gradient exchange (pure data parallelism, one process per GPU; reference loop being sharded:
  * finetune_multimodal.py:371-468).  RCCL over xGMI behind four calls, for hosts that bind only this header (the Python host of this

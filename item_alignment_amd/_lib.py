@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libitemalign_hip.so")
 
 vp, i32, u32, f32, sz = C.c_void_p, C.c_int, C.c_uint32, C.c_float, C.c_size_t
+PP, IP = C.POINTER(C.c_void_p), C.POINTER(C.c_int)      # host arrays of device pointers / of ints (the ia_textcnn_* calls)
 
 
 class LayerWeights(C.Structure):
@@ -160,6 +161,10 @@ SIGNATURES = {
     "ia_gcn_input_bwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, f32, u32, u32, vp, sz, vp]),
     "ia_gcn_pair_gather_fwd": (i32, [vp, vp, vp, i32, i32, i32, f32, u32, u32, vp]),
     "ia_gcn_pair_scatter_bwd": (i32, [vp, vp, vp, vp, i32, i32, i32, f32, u32, u32, vp]),
+    "ia_textcnn_pack_taps": (i32, [PP, IP, i32, i32, i32, vp, vp]),
+    "ia_textcnn_pool_fwd": (i32, [vp, i32, PP, IP, i32, i32, i32, i32, f32, f32, u32, u32, u32, vp, vp, vp]),
+    "ia_textcnn_pool_bwd_w": (i32, [vp, vp, vp, vp, IP, i32, i32, i32, i32, i32, f32, f32, u32, u32, u32, PP, PP, vp]),
+    "ia_textcnn_pool_bwd_x": (i32, [vp, vp, PP, IP, i32, i32, i32, i32, i32, f32, f32, u32, u32, u32, vp, vp]),
     "ia_cast_f32_to_bf16": (i32, [vp, vp, sz, vp]),
     "ia_cast_bf16_to_f32": (i32, [vp, vp, sz, vp]),
     "ia_layer_stash_bytes": (sz, [C.POINTER(LayerCfg)]),
@@ -179,7 +184,7 @@ SIGNATURES = {
 _lib = None
 
 
-ABI_VERSION = 14      # = IA_ABI_VERSION of include/itemalign.h (tests/test_cabi_symbols.py keeps the two in step)
+ABI_VERSION = 15      # = IA_ABI_VERSION of include/itemalign.h (tests/test_cabi_symbols.py keeps the two in step)
 
 
 class ItemAlignError(RuntimeError):

@@ -98,13 +98,18 @@ def freeze_and_resume(args, model):
 
 
 def pick_device(model):
-    """HIP models need the GPU.  TextCNN (BASELINE config C1, the reference's CPU plumbing case) is plain torch and stays on the host
-    cores: there is no torch-eager GPU path in this package."""
+    """HIP models need the GPU.  TextCNN (BASELINE config C1) runs on the local GPU when one is visible -- its CUDA-input forward goes
+    through the HIP kernels (models/text.py TextCNN._features_hip) -- and as plain torch on the host cores otherwise."""
     from .models.base import HipModule
-    if isinstance(model, HipModule):
-        if not torch.cuda.is_available():
-            raise SystemExit("this model runs on the MI355X HIP engine only (no CPU path); no GPU is visible")
+    from .models.text import TextCNNTwoTower
+    hip = isinstance(model, HipModule)
+    if hip and not torch.cuda.is_available():
+        raise SystemExit("this model runs on the MI355X HIP engine only (no CPU path); no GPU is visible")
+    if hip or (isinstance(model, TextCNNTwoTower) and torch.cuda.is_available()):
         local = int(os.environ.get("LOCAL_RANK", "0"))
         torch.cuda.set_device(local)
-        return torch.device("cuda", local)
-    return torch.device("cpu")
+        device = torch.device("cuda", local)
+    else:
+        device = torch.device("cpu")
+    logger.info(f"device: {device} ({type(model).__name__})")
+    return device

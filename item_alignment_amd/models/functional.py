@@ -739,3 +739,127 @@ class PairSimFn(torch.autograd.Function):
         check(lib.ia_pair_sim_bwd(x.data_ptr(), y.data_ptr(), sim.data_ptr(), probs.data_ptr(), ptr(dsim), ptr(dprobs), dx.data_ptr(),
                                   dy.data_ptr(), B, D, ctx.measure, stream_ptr()), "ia_pair_sim_bwd")
         return dx, dy, None
+
+
+# --------------------------------------------------------------------------------------------- TextCNN
+# The TextCNN two-tower keeps its parameters as ordinary nn.Parameters outside the arena (TorchAdamW steps them), so these two
+# Functions take the parameters as inputs and hand their gradients back to autograd instead of adding into `.grad` views.
+class TextCNNTowerFn(torch.autograd.Function):
+    """input ids [B, L] -> TextCNN features [B, NF] (reference text.py:1516-1527 plus the pair head's dropout, base.py:104-105):
+    ia_embed_ln_fwd per channel, the tap projection P = x_0 taps_0^T + x_1 taps_1^T (two ia_gemm_bf16, the second accumulating),
+    ia_textcnn_pool_fwd.  `keep` False (torch.no_grad): nothing is kept for a backward.
+    params = embedding1's (word, type, position, LayerNorm weight, LayerNorm bias), the conv weights, the conv biases."""
+
+    @staticmethod
+    def forward(ctx, ids, tcnn, taps, p_embed, p1, p2, stream_base, keep, *params):
+        from .. import ops
+        from .base import create_position_ids_from_input_ids
+        lib = _lib.load()
+        _need_gpu(ids, "input_ids")
+        sizes, S = tcnn.filter_sizes, len(tcnn.filter_sizes)
+        conv_w, conv_b = params[5:5 + S], params[5 + S:5 + 2 * S]
+        B, L = ids.shape
+        ids = ids.contiguous()
+        M, H, dev = B * L, conv_w[0].shape[3], ids.device
+        if L < max(sizes):
+            raise ValueError(f"TextCNN: sequence length {L} is shorter than the largest filter size {max(sizes)}")
+        tts = torch.zeros_like(ids)
+        seed = step_seed()
+        xs, saved = [], []
+        scratch = None
+        for c, emb in enumerate((tcnn.embedding1, tcnn.embedding2)):
+            pids = create_position_ids_from_input_ids(ids, emb.padding_idx).contiguous()
+            x = torch.empty((M, H), device=dev, dtype=BF16)
+            if keep and c == 0:
+                z, mean, rstd = torch.empty((M, H), device=dev, dtype=BF16), torch.empty(M, device=dev, dtype=F32), torch.empty(M, device=dev, dtype=F32)
+            else:          # statistics nobody reads again (frozen channel / forward only): one scratch set
+                if scratch is None:
+                    scratch = (torch.empty((M, H), device=dev, dtype=BF16), torch.empty(M, device=dev, dtype=F32), torch.empty(M, device=dev, dtype=F32))
+                z, mean, rstd = scratch
+            word, type_, pos, gamma, beta = params[:5] if c == 0 else (emb.word_embeddings.weight, emb.token_type_embeddings.weight,
+                                                                       emb.position_embeddings.weight, emb.LayerNorm.weight, emb.LayerNorm.bias)
+            check(lib.ia_embed_ln_fwd(ids.data_ptr(), tts.data_ptr(), pids.data_ptr(), None, word.data_ptr(), type_.data_ptr(), pos.data_ptr(),
+                                      None, gamma.data_ptr(), beta.data_ptr(), z.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                                      M, H, emb.LayerNorm.eps, p_embed, seed, stream_base + c, stream_ptr()), "ia_embed_ln_fwd")
+            xs.append(x)
+            if c == 0:
+                saved = [pids, z, mean, rstd]
+        P = ops.gemm(xs[0], taps[0], out_f32=True)
+        ops.gemm(xs[1], taps[1], out=P, out_f32=True, accumulate=True)
+        feat, arg = ops.textcnn_pool_fwd(P, list(conv_b), sizes, B, L, p1=p1, p2=p2, seed=seed, stream_id1=stream_base + 2,
+                                         stream_id2=stream_base + 3)
+        if keep:
+            ctx.tcnn, ctx.drop, ctx.shape = tcnn, (p_embed, p1, p2, seed, stream_base), (B, L, H)
+            ctx.n_params = len(params)
+            ctx.save_for_backward(*params, ids, tts, xs[0], xs[1], arg, *saved)
+        return feat
+
+    @staticmethod
+    def backward(ctx, g):
+        from .. import ops
+        lib = _lib.load()
+        tcnn = ctx.tcnn
+        sizes, S = tcnn.filter_sizes, len(tcnn.filter_sizes)
+        params, acts = ctx.saved_tensors[:ctx.n_params], ctx.saved_tensors[ctx.n_params:]
+        word, type_, pos, gamma, beta = params[:5]
+        conv_w = list(params[5:5 + S])
+        p_embed, p1, p2, seed, sb = ctx.drop
+        B, L, H = ctx.shape
+        ids, tts, x0, x1, arg, pids, z, mean, rstd = acts
+        g = g.contiguous().to(F32)
+        kw = dict(p1=p1, p2=p2, seed=seed, stream_id1=sb + 2, stream_id2=sb + 3)
+        dW, db = ops.textcnn_pool_bwd_w(g, arg, x0, x1, sizes, conv_w[0].shape[0], L, **kw)
+        need = ctx.needs_input_grad[8:13]
+        demb = [None] * 5
+        if any(need):
+            dx = ops.textcnn_pool_bwd_x(g, arg, conv_w, sizes, L, **kw)
+            emb = tcnn.embedding1
+            demb = [torch.zeros_like(p) if n else None for p, n in zip((word, type_, pos, gamma, beta), need)]
+            M = B * L
+            ws_bytes = lib.ia_embed_ln_bwd_workspace_bytes(M, H)
+            ws = torch.empty(ws_bytes, device=g.device, dtype=torch.uint8)
+            orders = embed_table_orders(ids, tts, pids, None, emb.padding_idx, emb.padding_idx)
+            check(lib.ia_embed_ln_bwd(dx.data_ptr(), z.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), ids.data_ptr(),
+                                      tts.data_ptr(), pids.data_ptr(), None, None, *(o.data_ptr() for o in orders), *(ptr(t) for t in demb[:3]),
+                                      None, ptr(demb[3]), ptr(demb[4]), M, H, L, emb.padding_idx, emb.padding_idx, p_embed, seed, sb,
+                                      ws.data_ptr(), ws_bytes, stream_ptr()), "ia_embed_ln_bwd")
+        wneed, bneed = ctx.needs_input_grad[13:13 + S], ctx.needs_input_grad[13 + S:13 + 2 * S]
+        return (None,) * 8 + tuple(demb) + tuple(w if n else None for w, n in zip(dW, wneed)) + tuple(b if n else None for b, n in zip(db, bneed))
+
+
+class PairHeadCEParamFn(torch.autograd.Function):
+    """PairHeadCEFn for a head whose weight and bias are plain parameters: the same two kernels, gradients returned to autograd."""
+
+    @staticmethod
+    def forward(ctx, x, y, weight, bias, labels):
+        lib = _lib.load()
+        _need_gpu(x, "features")
+        x, y = x.contiguous(), y.contiguous()
+        B, D = x.shape
+        Cn = weight.shape[0]
+        logits = torch.empty((B, Cn), device=x.device, dtype=F32)
+        probs = torch.empty((B, Cn), device=x.device, dtype=F32)
+        loss = torch.zeros((), device=x.device, dtype=F32)
+        per = torch.empty(B, device=x.device, dtype=F32)
+        check(lib.ia_pair_head_ce_fwd(x.data_ptr(), y.data_ptr(), weight.data_ptr(), ptr(bias), ptr(labels), logits.data_ptr(),
+                                      probs.data_ptr(), loss.data_ptr(), per.data_ptr(), B, D, Cn, stream_ptr()), "ia_pair_head_ce_fwd")
+        ctx.save_for_backward(x, y, weight, probs)
+        ctx.labels, ctx.has_bias = labels, bias is not None
+        ctx.mark_non_differentiable(logits, probs)
+        return logits, probs, loss
+
+    @staticmethod
+    def backward(ctx, _dlogits, _dprobs, dloss):
+        lib = _lib.load()
+        x, y, weight, probs = ctx.saved_tensors
+        if ctx.labels is None:
+            raise RuntimeError("PairHeadCEParamFn.backward without labels")
+        B, D = x.shape
+        Cn = weight.shape[0]
+        dloss = dloss.contiguous().to(F32)
+        dx, dyv = torch.empty_like(x), torch.empty_like(y)
+        dW = torch.zeros_like(weight)
+        db = torch.zeros(Cn, device=x.device, dtype=F32) if ctx.has_bias else None
+        check(lib.ia_pair_head_ce_bwd(probs.data_ptr(), ctx.labels.data_ptr(), dloss.data_ptr(), x.data_ptr(), y.data_ptr(), weight.data_ptr(),
+                                      dx.data_ptr(), dyv.data_ptr(), dW.data_ptr(), ptr(db), B, D, Cn, stream_ptr()), "ia_pair_head_ce_bwd")
+        return dx, dyv, dW, db, None

@@ -412,8 +412,9 @@ class PKGMTwoTower(RobertaTwoTower):
 
 # --------------------------------------------------------------------------------------------- TextCNN
 class _CpuEmbeddings(nn.Module):
-    """RobertaEmbeddings for the TextCNN plumbing config (BASELINE.json configs[0], CPU via finetune_text.py):
-    plain torch modules; this model family never touches the HIP engine (no kernel required)."""
+    """RobertaEmbeddings of the TextCNN model (BASELINE.json configs[0]) as plain torch modules: what runs when the input is on the
+    CPU.  With the input on the GPU the same parameters are read by ia_embed_ln_fwd / _bwd (TextCNN._features_hip) and this
+    forward is not called."""
 
     def __init__(self, config):
         super().__init__()
@@ -434,11 +435,15 @@ class _CpuEmbeddings(nn.Module):
 
 
 class TextCNN(nn.Module):
-    """reference text.py:1496-1527."""
+    """reference text.py:1496-1527.  Input on the CPU: plain torch, as the reference.  Input on the GPU: Fn.TextCNNTowerFn (embedding
+    gather + LayerNorm kernels, the tap projection through the bf16 GEMM, csrc/textcnn.hip for relu + max over time and its
+    backward); the parameters stay ordinary nn.Parameters outside any arena."""
 
     def __init__(self, config, embedding_state_dict):
         super().__init__()
         filter_sizes = [int(i) for i in config.filter_sizes.split(",")]
+        self.filter_sizes = filter_sizes
+        self._taps, self._taps_key = None, None
         self.embedding1 = _CpuEmbeddings(config)
         self.embedding1.load_state_dict(embedding_state_dict, strict=False)
         self.embedding2 = _CpuEmbeddings(config)
@@ -449,10 +454,35 @@ class TextCNN(nn.Module):
         self.dropout = nn.Dropout(config.hidden_dropout_prob)
 
     def forward(self, x):
+        if x.is_cuda:
+            return self._features_hip(x, 0.0, 3001)
         x = torch.stack((self.embedding1(x), self.embedding2(x)), dim=1)
         x = [F.relu(conv(x)).squeeze(3) for conv in self.convs1]
         x = [F.max_pool1d(i, i.size(2)).squeeze(2) for i in x]
         return self.dropout(torch.cat(x, 1))
+
+    def tap_shadow(self):
+        """bf16 [2, NTP, H] copy of the conv weights in tap order (include/itemalign.h), repacked whenever a weight has been written
+        since the last pack -- after every optimiser step while training, once for an evaluation."""
+        from .. import ops
+        ws = [c.weight for c in self.convs1]
+        key = tuple((w.data_ptr(), w._version) for w in ws)
+        if key != self._taps_key:
+            with torch.no_grad():
+                reuse = self._taps if (self._taps is not None and self._taps.device == ws[0].device) else None
+                self._taps = ops.textcnn_pack_taps([w.detach() for w in ws], self.filter_sizes, reuse)
+            self._taps_key = key
+        return self._taps
+
+    def _features_hip(self, ids, p_head, stream_base):
+        """dropout_head(dropout(features)) on the GPU: both dropouts are drawn inside ia_textcnn_pool_fwd (p_head = 0: the first only).
+        As with nn.Dropout on the CPU path, the rates follow self.training alone; torch.no_grad only decides what is kept."""
+        training = self.training
+        e1 = self.embedding1
+        params = [e1.word_embeddings.weight, e1.token_type_embeddings.weight, e1.position_embeddings.weight, e1.LayerNorm.weight,
+                  e1.LayerNorm.bias] + [c.weight for c in self.convs1] + [c.bias for c in self.convs1]
+        return Fn.TextCNNTowerFn.apply(ids, self, self.tap_shadow(), e1.dropout.p if training else 0.0, self.dropout.p if training else 0.0,
+                                       p_head if training else 0.0, stream_base, torch.is_grad_enabled(), *params)
 
 
 class _TorchTwoTowerHead(nn.Module):
@@ -484,8 +514,27 @@ class TextCNNTwoTower(nn.Module):
     def forward(self, input_ids_1=None, attention_mask_1=None, token_type_ids_1=None, position_ids_1=None, input_ids_2=None,
                 attention_mask_2=None, token_type_ids_2=None, position_ids_2=None, head_mask=None, inputs_embeds=None, labels=None,
                 output_attentions=None, output_hidden_states=None, return_dict=None):
+        if input_ids_1.is_cuda:
+            return self._forward_hip(input_ids_1, input_ids_2, labels)
         o1, o2 = self.textcnn(input_ids_1), self.textcnn(input_ids_2)
         src, tgt, logits, probs = self.classifier(o1, o2)
         src, tgt, probs = probs[:, 0], probs[:, 1], probs[:, 1]
         loss = apply_loss(self.loss_fct, self.config, logits, labels, src, tgt, ce_too=True) if labels is not None else None
         return SequenceClassifierOutput(loss=loss, probs=probs, logits=logits, src_embeds=src, tgt_embeds=tgt)
+
+    def _forward_hip(self, ids1, ids2, labels):
+        """The same forward with the input on the GPU: one Fn.TextCNNTowerFn per tower (the head's dropout is drawn in its pool kernel),
+        then the fused pair head + cross-entropy; the other loss types take the [B, 2] logits as on the CPU."""
+        head = self.classifier
+        o1 = self.textcnn._features_hip(ids1, head.dropout.p, 3001)
+        o2 = self.textcnn._features_hip(ids2, head.dropout.p, 3011)
+        w, b = head.out_proj.weight, head.out_proj.bias
+        if labels is None or self.config.loss_type == "ce":
+            logits, probs2, loss = Fn.PairHeadCEParamFn.apply(o1, o2, w, b, None if labels is None else labels.contiguous())
+            if labels is None:
+                loss = None
+        else:
+            logits = F.linear(torch.cat((o1, o2), dim=1), w, b)
+            probs2 = torch.softmax(logits, dim=1)
+            loss = apply_loss(self.loss_fct, self.config, logits, labels, probs2[:, 0], probs2[:, 1], ce_too=True)
+        return SequenceClassifierOutput(loss=loss, probs=probs2[:, 1], logits=logits, src_embeds=probs2[:, 0], tgt_embeds=probs2[:, 1])

@@ -174,3 +174,72 @@ def cast_to_f32(src, dst=None):
         dst = torch.empty(src.shape, device=src.device, dtype=F32)
     check(lib.ia_cast_bf16_to_f32(src.data_ptr(), dst.data_ptr(), src.numel(), stream_ptr()), "ia_cast_bf16_to_f32")
     return dst
+
+
+# ------------------------------------------------------------------------------------------------ TextCNN tower
+def textcnn_taps(sizes, num_filters):
+    """(NT, NTP): the tap columns of the projection P and their count rounded up to a multiple of 8 (the leading dimension of P)."""
+    nt = num_filters * sum(sizes)
+    return nt, (nt + 7) & ~7
+
+
+def _ptr_array(tensors):
+    return (_lib.vp * len(tensors))(*(None if t is None else t.data_ptr() for t in tensors))
+
+
+def _int_array(values):
+    return (_lib.i32 * len(values))(*values)
+
+
+def textcnn_pack_taps(weights, sizes, taps=None):
+    """weights: the fp32 Conv2d weights [F, 2, K, H], one per filter size -> the bf16 tap shadow [2, NTP, H] (include/itemalign.h)."""
+    lib = _lib.load()
+    for w in weights:
+        _need(w, F32, "conv weight")
+    F_, H = weights[0].shape[0], weights[0].shape[3]
+    if taps is None:
+        taps = torch.empty((2, textcnn_taps(sizes, F_)[1], H), device=weights[0].device, dtype=BF16)
+    _need(taps, BF16, "taps")
+    check(lib.ia_textcnn_pack_taps(_ptr_array(weights), _int_array(sizes), len(sizes), F_, H, taps.data_ptr(), stream_ptr()),
+          "ia_textcnn_pack_taps")
+    return taps
+
+
+def textcnn_pool_fwd(P, biases, sizes, B, L, *, p1=0.0, p2=0.0, seed=0, stream_id1=0, stream_id2=0):
+    """P [B * L, ldp] fp32 -> (feat [B, NF] fp32, argmax [B, NF] int32)."""
+    lib = _lib.load()
+    _need(P, F32, "P")
+    for b in biases:
+        _need(b, F32, "conv bias")
+    F_ = biases[0].shape[0]
+    feat = torch.empty((B, F_ * len(sizes)), device=P.device, dtype=F32)
+    arg = torch.empty((B, F_ * len(sizes)), device=P.device, dtype=torch.int32)
+    check(lib.ia_textcnn_pool_fwd(P.data_ptr(), P.shape[1], _ptr_array(biases), _int_array(sizes), len(sizes), F_, B, L, p1, p2, seed,
+                                  stream_id1, stream_id2, feat.data_ptr(), arg.data_ptr(), stream_ptr()), "ia_textcnn_pool_fwd")
+    return feat, arg
+
+
+def textcnn_pool_bwd_w(g, arg, x0, x1, sizes, num_filters, L, *, p1=0.0, p2=0.0, seed=0, stream_id1=0, stream_id2=0):
+    """-> ([dW_s fp32 [F, 2, K_s, H]], [db_s fp32 [F]])"""
+    lib = _lib.load()
+    _need(g, F32, "g"); _need(arg, torch.int32, "argmax"); _need(x0, BF16, "x0"); _need(x1, BF16, "x1")
+    B, H = g.shape[0], x0.shape[1]
+    dW = [torch.empty((num_filters, 2, K, H), device=g.device, dtype=F32) for K in sizes]
+    db = [torch.empty(num_filters, device=g.device, dtype=F32) for _ in sizes]
+    check(lib.ia_textcnn_pool_bwd_w(g.data_ptr(), arg.data_ptr(), x0.data_ptr(), x1.data_ptr(), _int_array(sizes), len(sizes), num_filters,
+                                    B, L, H, p1, p2, seed, stream_id1, stream_id2, _ptr_array(dW), _ptr_array(db), stream_ptr()),
+          "ia_textcnn_pool_bwd_w")
+    return dW, db
+
+
+def textcnn_pool_bwd_x(g, arg, weights, sizes, L, *, p1=0.0, p2=0.0, seed=0, stream_id1=0, stream_id2=0):
+    """-> dx of channel 0, bf16 [B * L, H]"""
+    lib = _lib.load()
+    _need(g, F32, "g"); _need(arg, torch.int32, "argmax")
+    for w in weights:
+        _need(w, F32, "conv weight")
+    B, F_, H = g.shape[0], weights[0].shape[0], weights[0].shape[3]
+    dx = torch.empty((B * L, H), device=g.device, dtype=BF16)
+    check(lib.ia_textcnn_pool_bwd_x(g.data_ptr(), arg.data_ptr(), _ptr_array(weights), _int_array(sizes), len(sizes), F_, B, L, H, p1, p2,
+                                    seed, stream_id1, stream_id2, dx.data_ptr(), stream_ptr()), "ia_textcnn_pool_bwd_x")
+    return dx
