@@ -6,7 +6,6 @@
 //   pre-LN   ViT block           (timm vision_transformer.Block, called at src/models/multimodal.py:811,
 //            src/models/image.py:459)
 #include "common.h"
-#include <cstdlib>
 #include "../../include/itemalign.h"
 
 namespace {
@@ -15,24 +14,60 @@ inline size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
 // token rows of the layer: B*L padded rows, or the packed total when the sequences are unpadded (cu_seqlens)
 inline size_t rows_of(const ia_layer_cfg* c) { return c->cu_seqlens ? (size_t)c->total_tokens : (size_t)c->B * c->L; }
 
-struct Stash {
-  char* qkv; char* ctx; char* t0; char* t1; char* t2; char* hpre; char* hact;   // hpre holds gelu'(pre-activation) (IA_EPI_BIAS_GELU C2), hact the activation
+// hands out consecutive 256-byte-aligned pieces of one allocation (a null base only counts the bytes)
+struct Carver {
+  char* base; size_t bytes = 0;
+  char* take(size_t b) { char* r = base ? base + bytes : nullptr; bytes += al(b); return r; }
+};
+
+// The buffers of one layer forward, by role.  The training stash gives each role its own memory (the backward reads them all); the
+// forward-only scratch aliases the ones whose contents are dead by the time the memory is written again.
+struct FwdBufs {
+  char* qkv; char* ctx;
+  char* xn;     // pre-LN only: LN1(x), the QKV projection's input
+  char* proj;   // attention output projection; the LayerNorm after it leaves the residual sum here (post-LN: z1, pre-LN: x1)
+  char* ln;     // the LayerNorm output that feeds the FFN (post-LN: y1 = LN1(z1), pre-LN: LN2(x1))
+  char* ffn;    // post-LN only: FFN output, then z2 in place (pre-LN writes the layer output straight from the fc2 epilogue)
+  char* hpre;   // gelu'(pre-activation) (IA_EPI_BIAS_GELU C2); null in the forward-only form
+  char* hact;   // FFN hidden activation
   float* lse; float* mean1; float* rstd1; float* mean2; float* rstd2;
   size_t bytes;
 };
 
-Stash carve_stash(const ia_layer_cfg* c, void* base) {
+// the three [M, H] row buffers in the order the layer shape uses them
+void name_rows(FwdBufs& s, bool pre_ln, char* t0, char* t1, char* t2) {
+  if (pre_ln) { s.xn = t0; s.proj = t1; s.ln = t2; s.ffn = nullptr; }
+  else { s.xn = nullptr; s.proj = t0; s.ln = t1; s.ffn = t2; }
+}
+
+FwdBufs carve_stash(const ia_layer_cfg* c, void* base) {
   const size_t M = rows_of(c), H = c->H, I = c->I;
-  char* p = (char*)base;
-  Stash s;
-  auto take = [&](size_t b) { char* r = p; p += al(b); return r; };
-  s.qkv = take(M * 3 * H * 2); s.ctx = take(M * H * 2);
-  s.t0 = take(M * H * 2); s.t1 = take(M * H * 2); s.t2 = take(M * H * 2);
-  s.hpre = take(M * I * 2); s.hact = take(M * I * 2);
-  s.lse = (float*)take((size_t)c->B * c->nh * c->L * 4);
-  s.mean1 = (float*)take(M * 4); s.rstd1 = (float*)take(M * 4);
-  s.mean2 = (float*)take(M * 4); s.rstd2 = (float*)take(M * 4);
-  s.bytes = (size_t)(p - (char*)base);
+  Carver a{(char*)base};
+  FwdBufs s;
+  s.qkv = a.take(M * 3 * H * 2); s.ctx = a.take(M * H * 2);
+  char* t0 = a.take(M * H * 2); char* t1 = a.take(M * H * 2); char* t2 = a.take(M * H * 2);
+  name_rows(s, c->pre_ln, t0, t1, t2);
+  s.hpre = a.take(M * I * 2); s.hact = a.take(M * I * 2);
+  s.lse = (float*)a.take((size_t)c->B * c->nh * c->L * 4);
+  s.mean1 = (float*)a.take(M * 4); s.rstd1 = (float*)a.take(M * 4);
+  s.mean2 = (float*)a.take(M * 4); s.rstd2 = (float*)a.take(M * 4);
+  s.bytes = a.bytes;
+  return s;
+}
+
+// forward only: no gelu' stream, one pair of LayerNorm statistics, and two row buffers -- the third role reuses t0 once its first
+// contents are consumed (post-LN: z1 by LN1, pre-LN: LN1(x) by the QKV projection)
+FwdBufs carve_infer(const ia_layer_cfg* c, void* base) {
+  const size_t M = rows_of(c), H = c->H, I = c->I;
+  Carver a{(char*)base};
+  FwdBufs s;
+  s.qkv = a.take(M * 3 * H * 2); s.ctx = a.take(M * H * 2);
+  char* t0 = a.take(M * H * 2); char* t1 = a.take(M * H * 2);
+  name_rows(s, c->pre_ln, t0, t1, t0);
+  s.hpre = nullptr; s.hact = a.take(M * I * 2);
+  s.lse = (float*)a.take((size_t)c->B * c->nh * c->L * 4);
+  s.mean1 = s.mean2 = (float*)a.take(M * 4); s.rstd1 = s.rstd2 = (float*)a.take(M * 4);
+  s.bytes = a.bytes;
   return s;
 }
 
@@ -44,20 +79,19 @@ size_t max3(size_t a, size_t b, size_t c) { return a > b ? (a > c ? a : c) : (b 
 
 Scratch carve_scratch(const ia_layer_cfg* c, void* base) {
   const size_t M = rows_of(c), H = c->H, I = c->I;
-  char* p = (char*)base;
+  Carver a{(char*)base};
   Scratch s;
-  auto take = [&](size_t b) { char* r = p; p += al(b); return r; };
-  s.g0 = take(M * H * 2); s.g1 = take(M * H * 2); s.g2 = take(M * H * 2);
-  s.gI = take(M * I * 2); s.gqkv = take(M * 3 * H * 2);
-  s.delta = (float*)take((size_t)c->B * c->nh * c->L * 4);
+  s.g0 = a.take(M * H * 2); s.g1 = a.take(M * H * 2); s.g2 = a.take(M * H * 2);
+  s.gI = a.take(M * I * 2); s.gqkv = a.take(M * 3 * H * 2);
+  s.delta = (float*)a.take((size_t)c->B * c->nh * c->L * 4);
   s.ws_bytes = max3(ia_ln_bwd_workspace_bytes((int)M, (int)H), ia_gemm_colsum_workspace_bytes((int)M, (int)I),
                     max3(ia_colsum_workspace_bytes((int)M, (int)(3 * H)), ia_attn_bwd_bias_workspace_bytes(c->B, c->nh, c->L), 0));
-  s.ws = take(s.ws_bytes);
+  s.ws = a.take(s.ws_bytes);
   // split-K partial sums of the four weight-gradient GEMMs (largest of them)
   s.gws_bytes = max3(ia_gemm_workspace_bytes((int)(3 * H), (int)H, (int)M, 1), ia_gemm_workspace_bytes((int)I, (int)H, (int)M, 1),
                      max3(ia_gemm_workspace_bytes((int)H, (int)I, (int)M, 1), ia_gemm_workspace_bytes((int)H, (int)H, (int)M, 1), 0));
-  s.gws = take(s.gws_bytes);
-  s.bytes = (size_t)(p - (char*)base);
+  s.gws = a.take(s.gws_bytes);
+  s.bytes = a.bytes;
   return s;
 }
 
@@ -69,25 +103,18 @@ bool cfg_ok(const ia_layer_cfg* c) {
 #define IA_TRY(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
 
 // Data gradient dx[M, n_in] = dy[M, k_out] W[k_out, n_in] (+ epilogue): through the transposed shadow wt[n_in, k_out] when the caller
-// provides one (both operands k-contiguous: the faster form, ia_layer_weights::wt_*), else W read k-strided.  IA_DGRAD_NT=0: A/B switch.
-bool dgrad_nt() {
-  static const bool on = [] { const char* e = getenv("IA_DGRAD_NT"); return !e || atoi(e) != 0; }();
-  return on;
-}
+// provides one (both operands k-contiguous: the faster form, ia_layer_weights::wt_*), else W read k-strided.
 int dgrad(const void* dy, int k_out, const void* w, const void* wt, int n_in, void* dx, int M, int epilogue, const void* aux, int ldaux, void* c2,
           void* ws, size_t ws_bytes, ia_stream_t st) {
-  if (wt && dgrad_nt())
+  if (wt)
     return ia_gemm_bf16(dy, 0, k_out, wt, 0, k_out, dx, 0, n_in, M, n_in, k_out, epilogue, nullptr, aux, ldaux, c2, 0, ws, ws_bytes, st);
   return ia_gemm_bf16(dy, 0, k_out, w, 1, n_in, dx, 0, n_in, M, n_in, k_out, epilogue, nullptr, aux, ldaux, c2, 0, ws, ws_bytes, st);
 }
 
 // The QKV projection of a layer writes q already multiplied by softmax scale * log2(e) (one bf16 rounding, in the GEMM epilogue where
 // the value is still fp32) and the attention kernels are told so: none of forward / dQ / dK-dV / fused backward re-scales its q tiles.
-// Needs the q | k boundary on a 128-column tile boundary of the GEMM; IA_Q_PRESCALE=0 switches it off for A/B runs.
-bool q_prescale(const ia_layer_cfg* c) {
-  static const bool on = [] { const char* e = getenv("IA_Q_PRESCALE"); return !e || atoi(e) != 0; }();
-  return on && (c->H & 127) == 0;
-}
+// Needs the q | k boundary on a 128-column tile boundary of the GEMM; other hidden sizes take the plain projection and kernels.
+bool q_prescale(const ia_layer_cfg* c) { return (c->H & 127) == 0; }
 int qkv_proj(const ia_layer_cfg* c, const void* x, const ia_layer_weights* w, void* qkv, int M, float scale, ia_stream_t st) {
   const int H = c->H;
   if (q_prescale(c)) return ia_gemm_bf16_qscale(x, H, w->w_qkv, H, qkv, 3 * H, M, 3 * H, H, w->b_qkv, H, scale * 1.4426950408889634f, st);
@@ -121,6 +148,46 @@ int attn_bwd(const ia_layer_cfg* c, const char* qkv, const uint8_t* key_mask, co
                              gqkv + (size_t)H * 2, gqkv + (size_t)2 * H * 2, 3 * H, db_qkv, ws, ws_bytes, c->B, c->nh, c->L, scale, drop, seed, st);
 }
 
+// Every launch of one layer forward.  keep = the training form, which leaves what the backward needs in s: the dropout masks' seeds,
+// gelu'(pre-activation) beside the activation, and the post-LN residual sums z1 / z2.  Without it (evaluation / prediction, reference
+// finetune_multimodal.py:470-563, 661-775) the launches and roundings are the same -- evaluation reproduces the training forward bit for
+// bit when dropout is off -- minus those outputs, so s may alias buffers (carve_infer).
+int layer_forward(const ia_layer_cfg* c, const ia_layer_weights* w, const void* x, const uint8_t* key_mask, void* y, const FwdBufs& s,
+                  bool keep, ia_stream_t st) {
+  const int M = (int)rows_of(c), H = c->H, I = c->I;
+  const float scale = 0.125f;  // 1/sqrt(64)
+  const int gelu = keep ? IA_EPI_BIAS_GELU : IA_EPI_BIAS_GELU_ACT;
+  if (!c->pre_ln) {
+    const float hidden_drop = keep ? c->hidden_drop : 0.f, attn_drop = keep ? c->attn_drop : 0.f;
+    const uint32_t seed = keep ? c->seed : 0u, attn_seed = keep ? c->seed * 2654435761u + c->layer_id * 97u + 17u : 0u;
+    const uint32_t ln1_stream = keep ? c->layer_id * 4u + 0u : 0u, ln2_stream = keep ? c->layer_id * 4u + 1u : 0u;
+    // qkv = x Wqkv^T + b
+    IA_TRY(qkv_proj(c, x, w, s.qkv, M, scale, st));
+    IA_TRY(attn_fwd(c, s.qkv, key_mask, s.ctx, s.lse, scale, attn_drop, attn_seed, st));
+    // z1 = x + dropout(ctx Wo^T + b_o); y1 = LN1(z1)
+    IA_TRY(ia_gemm_bf16(s.ctx, 0, H, w->w_o, 0, H, s.proj, 0, H, M, H, H, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, st));
+    IA_TRY(ia_ln_fwd(s.proj, w->b_o, x, keep ? s.proj : nullptr, s.ln, s.mean1, s.rstd1, w->ln1_g, w->ln1_b, M, H, c->eps, hidden_drop, seed,
+                     ln1_stream, st));
+    // h = gelu(y1 W1^T + b1)
+    IA_TRY(ia_gemm_bf16(s.ln, 0, H, w->w_fc1, 0, H, s.hact, 0, I, M, I, H, gelu, w->b_fc1, nullptr, 0, s.hpre, 0, nullptr, 0, st));
+    // z2 = y1 + dropout(h W2^T + b2); y = LN2(z2)
+    IA_TRY(ia_gemm_bf16(s.hact, 0, I, w->w_fc2, 0, I, s.ffn, 0, H, M, H, I, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, st));
+    IA_TRY(ia_ln_fwd(s.ffn, w->b_fc2, s.ln, keep ? s.ffn : nullptr, y, s.mean2, s.rstd2, w->ln2_g, w->ln2_b, M, H, c->eps, hidden_drop, seed,
+                     ln2_stream, st));
+  } else {   // no dropout (timm ViT default; ia_layer_fwd refuses it)
+    IA_TRY(ia_ln_fwd(x, nullptr, nullptr, nullptr, s.xn, s.mean1, s.rstd1, w->ln1_g, w->ln1_b, M, H, c->eps, 0.f, 0, 0, st));
+    IA_TRY(qkv_proj(c, s.xn, w, s.qkv, M, scale, st));
+    IA_TRY(attn_fwd(c, s.qkv, key_mask, s.ctx, s.lse, scale, 0.f, 0, st));
+    // x1 = x + ctx Wo^T + b_o and LN2(x1): the bias and the residual are added by the LayerNorm kernel (it streams the rows anyway),
+    // so the projection keeps the plain epilogue; proj receives x1 in place of the raw projection (the fc2 epilogue's residual)
+    IA_TRY(ia_gemm_bf16(s.ctx, 0, H, w->w_o, 0, H, s.proj, 0, H, M, H, H, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, st));
+    IA_TRY(ia_ln_fwd(s.proj, w->b_o, x, s.proj, s.ln, s.mean2, s.rstd2, w->ln2_g, w->ln2_b, M, H, c->eps, 0.f, 0, 0, st));
+    IA_TRY(ia_gemm_bf16(s.ln, 0, H, w->w_fc1, 0, H, s.hact, 0, I, M, I, H, gelu, w->b_fc1, nullptr, 0, s.hpre, 0, nullptr, 0, st));
+    IA_TRY(ia_gemm_bf16(s.hact, 0, I, w->w_fc2, 0, I, y, 0, H, M, H, I, IA_EPI_BIAS_ADD, w->b_fc2, s.proj, H, nullptr, 0, nullptr, 0, st));
+  }
+  return IA_OK;
+}
+
 }  // namespace
 
 extern "C" size_t ia_layer_stash_bytes(const ia_layer_cfg* cfg) {
@@ -135,95 +202,27 @@ extern "C" size_t ia_layer_bwd_scratch_bytes(const ia_layer_cfg* cfg) {
   return carve_scratch(cfg, nullptr).bytes;
 }
 
-extern "C" int ia_layer_fwd(const ia_layer_cfg* c, const ia_layer_weights* w, const void* x, const uint8_t* key_mask, void* y,
-                            void* stash, ia_stream_t st) {
-  (void)hipGetLastError();  // drop stale status left by unrelated runtime calls (e.g. hipEventQuery -> NotReady)
-  if (!cfg_ok(c) || !w || !x || !y || !stash) return IA_ERR_ARG;
-  const int M = (int)rows_of(c), H = c->H, I = c->I;
-  const Stash s = carve_stash(c, stash);
-  const float scale = 0.125f;  // 1/sqrt(64)
-  const uint32_t attn_seed = c->seed * 2654435761u + c->layer_id * 97u + 17u;
-  if (!c->pre_ln) {
-    // qkv = x Wqkv^T + b
-    IA_TRY(qkv_proj(c, x, w, s.qkv, M, scale, st));
-    IA_TRY(attn_fwd(c, s.qkv, key_mask, s.ctx, s.lse, scale, c->attn_drop, attn_seed, st));
-    // z1 = x + dropout(ctx Wo^T + b_o); y1 = LN1(z1)
-    IA_TRY(ia_gemm_bf16(s.ctx, 0, H, w->w_o, 0, H, s.t0, 0, H, M, H, H, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, st));
-    IA_TRY(ia_ln_fwd(s.t0, w->b_o, x, s.t0, s.t1, s.mean1, s.rstd1, w->ln1_g, w->ln1_b, M, H, c->eps, c->hidden_drop, c->seed,
-                     c->layer_id * 4u + 0u, st));
-    // h = gelu(y1 W1^T + b1)
-    IA_TRY(ia_gemm_bf16(s.t1, 0, H, w->w_fc1, 0, H, s.hact, 0, I, M, I, H, IA_EPI_BIAS_GELU, w->b_fc1, nullptr, 0, s.hpre, 0, nullptr, 0, st));
-    // z2 = y1 + dropout(h W2^T + b2); y = LN2(z2)
-    IA_TRY(ia_gemm_bf16(s.hact, 0, I, w->w_fc2, 0, I, s.t2, 0, H, M, H, I, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, st));
-    IA_TRY(ia_ln_fwd(s.t2, w->b_fc2, s.t1, s.t2, y, s.mean2, s.rstd2, w->ln2_g, w->ln2_b, M, H, c->eps, c->hidden_drop, c->seed,
-                     c->layer_id * 4u + 1u, st));
-  } else {
-    if (c->hidden_drop > 0.f || c->attn_drop > 0.f) return IA_ERR_UNSUPPORTED;  // timm ViT default: no dropout
-    IA_TRY(ia_ln_fwd(x, nullptr, nullptr, nullptr, s.t0, s.mean1, s.rstd1, w->ln1_g, w->ln1_b, M, H, c->eps, 0.f, 0, 0, st));
-    IA_TRY(qkv_proj(c, s.t0, w, s.qkv, M, scale, st));
-    IA_TRY(attn_fwd(c, s.qkv, key_mask, s.ctx, s.lse, scale, 0.f, 0, st));
-    // x1 = x + ctx Wo^T + b_o and LN2(x1): the bias and the residual are added by the LayerNorm kernel (it streams the rows anyway),
-    // so the projection keeps the plain epilogue; t1 receives x1 in place of the raw projection
-    IA_TRY(ia_gemm_bf16(s.ctx, 0, H, w->w_o, 0, H, s.t1, 0, H, M, H, H, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, st));
-    IA_TRY(ia_ln_fwd(s.t1, w->b_o, x, s.t1, s.t2, s.mean2, s.rstd2, w->ln2_g, w->ln2_b, M, H, c->eps, 0.f, 0, 0, st));
-    IA_TRY(ia_gemm_bf16(s.t2, 0, H, w->w_fc1, 0, H, s.hact, 0, I, M, I, H, IA_EPI_BIAS_GELU, w->b_fc1, nullptr, 0, s.hpre, 0, nullptr, 0, st));
-    IA_TRY(ia_gemm_bf16(s.hact, 0, I, w->w_fc2, 0, I, y, 0, H, M, H, I, IA_EPI_BIAS_ADD, w->b_fc2, s.t1, H, nullptr, 0, nullptr, 0, st));
-  }
-  return IA_OK;
-}
-
-// ---- forward only (evaluation / prediction, reference finetune_multimodal.py:470-563, 661-775): the same launches as ia_layer_fwd
-// minus everything that exists for the backward pass -- no gelu'(pre-activation) stream (IA_EPI_BIAS_GELU_ACT), no pre-LayerNorm
-// sums z, no dropout -- in a transient scratch that every layer of a stack can share.
-namespace {
-struct Infer { char* qkv; char* ctx; char* t0; char* t1; char* h; float* lse; float* mean; float* rstd; size_t bytes; };
-Infer carve_infer(const ia_layer_cfg* c, void* base) {
-  const size_t M = rows_of(c), H = c->H, I = c->I;
-  char* p = (char*)base;
-  Infer s;
-  auto take = [&](size_t b) { char* r = p; p += al(b); return r; };
-  s.qkv = take(M * 3 * H * 2); s.ctx = take(M * H * 2); s.t0 = take(M * H * 2); s.t1 = take(M * H * 2); s.h = take(M * I * 2);
-  s.lse = (float*)take((size_t)c->B * c->nh * c->L * 4);
-  s.mean = (float*)take(M * 4); s.rstd = (float*)take(M * 4);
-  s.bytes = (size_t)(p - (char*)base);
-  return s;
-}
-}  // namespace
-
 extern "C" size_t ia_layer_infer_scratch_bytes(const ia_layer_cfg* cfg) {
   (void)hipGetLastError();
   if (!cfg_ok(cfg)) return 0;
   return carve_infer(cfg, nullptr).bytes;
 }
 
+extern "C" int ia_layer_fwd(const ia_layer_cfg* c, const ia_layer_weights* w, const void* x, const uint8_t* key_mask, void* y,
+                            void* stash, ia_stream_t st) {
+  (void)hipGetLastError();  // drop stale status left by unrelated runtime calls (e.g. hipEventQuery -> NotReady)
+  if (!cfg_ok(c) || !w || !x || !y || !stash) return IA_ERR_ARG;
+  if (c->pre_ln && (c->hidden_drop > 0.f || c->attn_drop > 0.f)) return IA_ERR_UNSUPPORTED;  // timm ViT default: no dropout
+  return layer_forward(c, w, x, key_mask, y, carve_stash(c, stash), true, st);
+}
+
+// forward only, in a transient scratch that every layer of a stack can share
 extern "C" int ia_layer_fwd_infer(const ia_layer_cfg* c, const ia_layer_weights* w, const void* x, const uint8_t* key_mask, void* y,
                                   void* scratch, size_t scratch_bytes, ia_stream_t st) {
   (void)hipGetLastError();
   if (!cfg_ok(c) || !w || !x || !y || !scratch) return IA_ERR_ARG;
   if (scratch_bytes < ia_layer_infer_scratch_bytes(c)) return IA_ERR_WORKSPACE;
-  const int M = (int)rows_of(c), H = c->H, I = c->I;
-  const Infer s = carve_infer(c, scratch);
-  const float scale = 0.125f;
-  if (!c->pre_ln) {
-    IA_TRY(qkv_proj(c, x, w, s.qkv, M, scale, st));
-    IA_TRY(attn_fwd(c, s.qkv, key_mask, s.ctx, s.lse, scale, 0.f, 0, st));
-    IA_TRY(ia_gemm_bf16(s.ctx, 0, H, w->w_o, 0, H, s.t0, 0, H, M, H, H, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, st));
-    IA_TRY(ia_ln_fwd(s.t0, w->b_o, x, nullptr, s.t1, s.mean, s.rstd, w->ln1_g, w->ln1_b, M, H, c->eps, 0.f, 0, 0, st));
-    IA_TRY(ia_gemm_bf16(s.t1, 0, H, w->w_fc1, 0, H, s.h, 0, I, M, I, H, IA_EPI_BIAS_GELU_ACT, w->b_fc1, nullptr, 0, nullptr, 0, nullptr, 0, st));
-    IA_TRY(ia_gemm_bf16(s.h, 0, I, w->w_fc2, 0, I, s.t0, 0, H, M, H, I, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, st));
-    IA_TRY(ia_ln_fwd(s.t0, w->b_fc2, s.t1, nullptr, y, s.mean, s.rstd, w->ln2_g, w->ln2_b, M, H, c->eps, 0.f, 0, 0, st));
-  } else {
-    IA_TRY(ia_ln_fwd(x, nullptr, nullptr, nullptr, s.t0, s.mean, s.rstd, w->ln1_g, w->ln1_b, M, H, c->eps, 0.f, 0, 0, st));
-    IA_TRY(qkv_proj(c, s.t0, w, s.qkv, M, scale, st));
-    IA_TRY(attn_fwd(c, s.qkv, key_mask, s.ctx, s.lse, scale, 0.f, 0, st));
-    // x1 = x + ctx Wo^T + b_o is formed by the LayerNorm kernel exactly as in ia_layer_fwd (same roundings: evaluation reproduces the
-    // training forward bit for bit when dropout is off); t1 receives x1, the fc2 epilogue's residual
-    IA_TRY(ia_gemm_bf16(s.ctx, 0, H, w->w_o, 0, H, s.t1, 0, H, M, H, H, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, st));
-    IA_TRY(ia_ln_fwd(s.t1, w->b_o, x, s.t1, s.t0, s.mean, s.rstd, w->ln2_g, w->ln2_b, M, H, c->eps, 0.f, 0, 0, st));
-    IA_TRY(ia_gemm_bf16(s.t0, 0, H, w->w_fc1, 0, H, s.h, 0, I, M, I, H, IA_EPI_BIAS_GELU_ACT, w->b_fc1, nullptr, 0, nullptr, 0, nullptr, 0, st));
-    IA_TRY(ia_gemm_bf16(s.h, 0, I, w->w_fc2, 0, I, y, 0, H, M, H, I, IA_EPI_BIAS_ADD, w->b_fc2, s.t1, H, nullptr, 0, nullptr, 0, st));
-  }
-  return IA_OK;
+  return layer_forward(c, w, x, key_mask, y, carve_infer(c, scratch), false, st);
 }
 
 extern "C" int ia_layer_bwd2(const ia_layer_cfg* c, const ia_layer_weights* w, const ia_layer_grads* g, const void* x,
@@ -245,31 +244,29 @@ extern "C" int ia_layer_bwd2(const ia_layer_cfg* c, const ia_layer_weights* w, c
   if (c->pre_ln && (dy2 || dx2)) return IA_ERR_UNSUPPORTED;
   if (scratch_bytes < ia_layer_bwd_scratch_bytes(c)) return IA_ERR_WORKSPACE;
   const int M = (int)rows_of(c), H = c->H, I = c->I;
-  const Stash s = carve_stash(c, const_cast<void*>(stash));
+  const FwdBufs s = carve_stash(c, const_cast<void*>(stash));
   const Scratch k = carve_scratch(c, scratch);
   const float scale = 0.125f;
   const uint32_t attn_seed = c->seed * 2654435761u + c->layer_id * 97u + 17u;
   const bool drop = c->hidden_drop > 0.f;
   if (!c->pre_ln) {
     // masked_rows_dead: every gradient row of a masked position is exactly zero (ia_layer_cfg): the LayerNorm backward kernels skip them
-    // (IA_LN_ROWS=0: the LayerNorm part off, for A/B runs)
-    static const bool ln_rows = [] { const char* e = getenv("IA_LN_ROWS"); return !e || atoi(e) != 0; }();
-    const uint8_t* const live = (c->masked_rows_dead && !c->cu_seqlens && ln_rows) ? key_mask : nullptr;
+    const uint8_t* const live = (c->masked_rows_dead && !c->cu_seqlens) ? key_mask : nullptr;
     // The two residual additions of a post-LN layer make each LayerNorm output's gradient a sum of two terms; both LayerNorm
     // backward kernels take the two terms (ia_ln_bwd2), so the GEMMs in front of them keep the plain epilogue.
     // LN2 backward: d(output) = dy (+ dy2) -> dz2 in g0, masked branch gradient -> g1 (or g0 when p == 0)
-    IA_TRY(ia_ln_bwd2_rows(dy, dy2, nullptr, s.t2, s.mean2, s.rstd2, w->ln2_g, k.g0, drop ? k.g1 : nullptr, g->ln2_g, g->ln2_b, g->b_fc2, M, H,
+    IA_TRY(ia_ln_bwd2_rows(dy, dy2, nullptr, s.ffn, s.mean2, s.rstd2, w->ln2_g, k.g0, drop ? k.g1 : nullptr, g->ln2_g, g->ln2_b, g->b_fc2, M, H,
                            c->hidden_drop, c->seed, c->layer_id * 4u + 1u, live, k.ws, k.ws_bytes, 1, st));
     const char* d_ffn = drop ? k.g1 : k.g0;
     IA_TRY(ia_gemm_bf16(d_ffn, 1, H, s.hact, 1, I, g->w_fc2, 1, I, H, I, M, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 1, k.gws, k.gws_bytes, st));
     // d(pre-activation) = (d_ffn W2) * gelu'(pre), and its column sums (the fc1 bias gradient) out of the same epilogue
     IA_TRY(dgrad(d_ffn, H, w->w_fc2, w->wt_fc2, I, k.gI, M, IA_EPI_DGELU_COLSUM, s.hpre, I, g->b_fc1, k.ws, k.ws_bytes, st));
-    IA_TRY(ia_gemm_bf16(k.gI, 1, I, s.t1, 1, H, g->w_fc1, 1, H, I, H, M, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 1, k.gws, k.gws_bytes, st));
+    IA_TRY(ia_gemm_bf16(k.gI, 1, I, s.ln, 1, H, g->w_fc1, 1, H, I, H, M, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 1, k.gws, k.gws_bytes, st));
     IA_TRY(dgrad(k.gI, I, w->w_fc1, w->wt_fc1, H, k.g2, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st));
     // LN1 backward: d(y1) = g2 (through fc1) + g0 (residual into LN2) -> dz1 (the layer input's residual-path gradient) in
     // dz1buf: the caller's dx2 when the split form is wanted, else g0 (in place over the term just consumed)
     char* dz1buf = dx2 ? (char*)dx2 : k.g0;
-    IA_TRY(ia_ln_bwd2_rows(k.g2, k.g0, nullptr, s.t0, s.mean1, s.rstd1, w->ln1_g, dz1buf, drop ? k.g1 : nullptr, g->ln1_g, g->ln1_b, g->b_o, M, H,
+    IA_TRY(ia_ln_bwd2_rows(k.g2, k.g0, nullptr, s.proj, s.mean1, s.rstd1, w->ln1_g, dz1buf, drop ? k.g1 : nullptr, g->ln1_g, g->ln1_b, g->b_o, M, H,
                            c->hidden_drop, c->seed, c->layer_id * 4u + 0u, live, k.ws, k.ws_bytes, 1, st));
     const char* d_att = drop ? k.g1 : dz1buf;
     IA_TRY(ia_gemm_bf16(d_att, 1, H, s.ctx, 1, H, g->w_o, 1, H, H, H, M, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 1, k.gws, k.gws_bytes, st));
@@ -284,15 +281,15 @@ extern "C" int ia_layer_bwd2(const ia_layer_cfg* c, const ia_layer_weights* w, c
     if (!c->dy_colsum_done) IA_TRY(ia_colsum(dy, H, M, H, g->b_fc2, 1, k.ws, k.ws_bytes, st));
     IA_TRY(ia_gemm_bf16(dy, 1, H, s.hact, 1, I, g->w_fc2, 1, I, H, I, M, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 1, k.gws, k.gws_bytes, st));
     IA_TRY(dgrad(dy, H, w->w_fc2, w->wt_fc2, I, k.gI, M, IA_EPI_DGELU_COLSUM, s.hpre, I, g->b_fc1, k.ws, k.ws_bytes, st));
-    IA_TRY(ia_gemm_bf16(k.gI, 1, I, s.t2, 1, H, g->w_fc1, 1, H, I, H, M, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 1, k.gws, k.gws_bytes, st));
+    IA_TRY(ia_gemm_bf16(k.gI, 1, I, s.ln, 1, H, g->w_fc1, 1, H, I, H, M, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 1, k.gws, k.gws_bytes, st));
     IA_TRY(dgrad(k.gI, I, w->w_fc1, w->wt_fc1, H, k.g0, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st));
     // LN2 backward (+ residual path dy) -> g1 = d x2 ; its column sum is the proj-bias gradient
-    IA_TRY(ia_ln_bwd(k.g0, dy, s.t1, s.mean2, s.rstd2, w->ln2_g, k.g1, nullptr, g->ln2_g, g->ln2_b, g->b_o, M, H, 0.f, 0, 0, k.ws,
+    IA_TRY(ia_ln_bwd(k.g0, dy, s.proj, s.mean2, s.rstd2, w->ln2_g, k.g1, nullptr, g->ln2_g, g->ln2_b, g->b_o, M, H, 0.f, 0, 0, k.ws,
                      k.ws_bytes, 1, st));
     IA_TRY(ia_gemm_bf16(k.g1, 1, H, s.ctx, 1, H, g->w_o, 1, H, H, H, M, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 1, k.gws, k.gws_bytes, st));
     IA_TRY(dgrad(k.g1, H, w->w_o, w->wt_o, H, k.g2, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st));
     IA_TRY(attn_bwd(c, s.qkv, key_mask, s.ctx, k.g2, s.lse, k.delta, k.gqkv, g->b_qkv, k.ws, k.ws_bytes, scale, 0.f, 0, st));
-    IA_TRY(ia_gemm_bf16(k.gqkv, 1, 3 * H, s.t0, 1, H, g->w_qkv, 1, H, 3 * H, H, M, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 1, k.gws, k.gws_bytes, st));
+    IA_TRY(ia_gemm_bf16(k.gqkv, 1, 3 * H, s.xn, 1, H, g->w_qkv, 1, H, 3 * H, H, M, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 1, k.gws, k.gws_bytes, st));
     IA_TRY(dgrad(k.gqkv, 3 * H, w->w_qkv, w->wt_qkv, H, k.g0, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st));
     // dx = LN1'(g0) + g1 is the incoming gradient of the block below: its column sums (that block's fc2 bias gradient) come out of
     // this kernel's partial sums instead of a separate pass over [M, H] there (cfg->dx_colsum_out)

@@ -17,13 +17,6 @@ from .._lib import LayerCfg, LayerGrads, LayerWeights
 from . import functional as Fn
 
 ACT_NONE, ACT_TANH = 0, 1
-# transposed bf16 shadows of the encoder layers' 2-D weights (+2 B / parameter of HBM, one batched transpose per optimiser step): the
-# backward's data-gradient GEMMs run in the k-contiguous form; IA_TRANSPOSED_SHADOWS=0 keeps the k-strided form (no extra copy)
-import os as _os
-TRANSPOSED_SHADOWS = _os.environ.get("IA_TRANSPOSED_SHADOWS", "1") != "0"
-# padded text towers: the attention backward skips query blocks that hold only masked positions when the model reads none of them
-# (RobertaEncoder.forward(masked_rows_dead=True), set by RobertaModel under the same condition that allows IA_UNPAD); 0 = compute every row
-MASKED_ROWS_DEAD = _os.environ.get("IA_MASKED_ROWS_DEAD", "1") != "0"
 
 
 class SequenceClassifierOutput(OrderedDict):
@@ -336,10 +329,11 @@ class _EngineStack:
             for name in ("w_o", "w_fc1", "w_fc2"):
                 setattr(w, name, A.shadow_of(d[name]).data_ptr())
                 setattr(g, name, d[name].grad.data_ptr())
-            if TRANSPOSED_SHADOWS:          # W^T copies for the data-gradient GEMMs (arena.register_transposed)
-                w.wt_qkv = A.register_transposed(qkv_w).data_ptr()
-                for name in ("w_o", "w_fc1", "w_fc2"):
-                    setattr(w, "wt" + name[1:], A.register_transposed(d[name]).data_ptr())
+            # transposed bf16 shadows of the 2-D weights (+2 B / parameter of HBM, one batched transpose per optimiser step,
+            # arena.register_transposed): the backward's data-gradient GEMMs run in the k-contiguous form
+            w.wt_qkv = A.register_transposed(qkv_w).data_ptr()
+            for name in ("w_o", "w_fc1", "w_fc2"):
+                setattr(w, "wt" + name[1:], A.register_transposed(d[name]).data_ptr())
             for name in ("b_o", "ln1_g", "ln1_b", "b_fc1", "b_fc2", "ln2_g", "ln2_b"):
                 setattr(w, name, d[name].data_ptr())
                 setattr(g, name, d[name].grad.data_ptr())
@@ -410,7 +404,7 @@ class RobertaEncoder(nn.Module, _EngineStack):
         km = None
         if attention_mask is not None:
             km = (attention_mask != 0).to(torch.uint8).contiguous()
-        self.__dict__["_masked_rows_dead"] = bool(masked_rows_dead and km is not None and MASKED_ROWS_DEAD)
+        self.__dict__["_masked_rows_dead"] = bool(masked_rows_dead and km is not None)
         outs = Fn.EncoderStackFn.apply(hidden_states.reshape(B * L, H), self.anchor, self, km, B, L, torch.is_grad_enabled(), None)
         return (hidden_states,) + tuple(o.view(B, L, H) for o in outs)
 

@@ -7,8 +7,6 @@ return None for parameter inputs: autograd only carries activation gradients bet
 """
 import ctypes as C
 
-import os
-
 import torch
 
 from .. import _lib
@@ -450,9 +448,6 @@ class PatchEmbedFn(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------ CoCa multimodal layers (cross_attn ensemble)
-_TRANSPOSED = os.environ.get("IA_TRANSPOSED_SHADOWS", "1") != "0"      # (models/base.py reads the same switch for the encoder layers)
-
-
 def _gemm(lib, a, a_ks, lda, b, b_ks, ldb, c, c_f32, ldc, M, N, K, epi=0, aux=None, ldaux=0, accumulate=0, what="ia_gemm_bf16"):
     ws_bytes = lib.ia_gemm_workspace_bytes(M, N, K, int(c_f32))
     ws = torch.empty(ws_bytes, device=c.device, dtype=torch.uint8) if ws_bytes else None
@@ -485,7 +480,7 @@ class LinearBf16Fn(torch.autograd.Function):
         ctx.x, ctx.swiglu_src, ctx.x_shape = (None, swiglu_src, (M, K)) if swiglu_src is not None else (x, None, (M, K))
         # W^T image for the data gradient (k-contiguous NT form: x 1.02-1.16 per launch over the k-strided form, profiles/r05_nn_vs_nt.txt;
         # the encoder layers have had theirs since round 5).  No extra memory: shadow_t spans the whole arena once anybody registers.
-        ctx.wt = owner.arena.register_transposed(weight) if (_TRANSPOSED and ctx.needs_input_grad[0] and M >= 1024) else None
+        ctx.wt = owner.arena.register_transposed(weight) if (ctx.needs_input_grad[0] and M >= 1024) else None
         ctx.need_dx, ctx.has_add = ctx.needs_input_grad[0], add is not None
         return y
 

@@ -8,7 +8,6 @@ gather + one GEMM per group (csrc/conv.hip).  Module / parameter names are timm'
 `stages.{s}.{b}.attn_last.conv.weight`, `final_conv.*`, `head.fc.*`.
 """
 import math
-import os
 
 import torch
 from torch import nn
@@ -20,9 +19,6 @@ from .base import HipModule
 
 BF16, F32 = torch.bfloat16, torch.float32
 NONLIN_GAMMA_SILU = 1.7881293296813965          # timm nfnet.py _nonlin_gamma['silu']
-FUSE_TAIL_ACT = os.environ.get("IA_NFNET_FUSE_TAIL", "1") != "0"   # a block's tail pass also writes the next block's opening activation (EcaResidualFn)
-FUSE_TAIL_BWD = os.environ.get("IA_NFNET_FUSE_TAIL", "1") == "1"   # ... and its backward folds SiLU' and the gate gradient's spatial sums into one pass
-ECA_LINEAR = os.environ.get("IA_ECA_LINEAR", "1") != "0"      # ECA pooling from conv3's input (EcaResidualFn); 0: the reduction over conv3's output
 
 NFNET_CONFIGS = {   # timm nfnet.py model_cfgs (_nfnet_cfg): depths, channels, feat_mult
     "eca_nfnet_l0": ((1, 2, 6, 3), (256, 512, 1536, 1536), 1.5),
@@ -43,6 +39,30 @@ def _ws(dev, nbytes):
     return torch.empty(max(int(nbytes), 16), device=dev, dtype=torch.uint8)
 
 
+def _standardised(conv, ci, kk, Cgp):
+    """the standardised bf16 weight [Cout, kk * Cgp] (tap-major, ci of Cgp channels per group used) of a ScaledStdConv2d, with the
+    per-filter statistics its backward needs"""
+    dev, Cout = conv.weight.device, conv.out_channels
+    what = torch.empty((Cout, kk * Cgp), device=dev, dtype=BF16)
+    mean = torch.empty(Cout, device=dev, dtype=F32)
+    rstd = torch.empty(Cout, device=dev, dtype=F32)
+    check(_lib.load().ia_ws_conv_weight_fwd(conv.weight.data_ptr(), conv.gain.data_ptr(), what.data_ptr(), mean.data_ptr(), rstd.data_ptr(), Cout,
+                                            ci, kk, Cgp, conv.scale, conv.eps, stream_ptr()), "ia_ws_conv_weight_fwd")
+    return what, mean, rstd
+
+
+def _standardised_bwd(conv, dwhat, mean, rstd, ci, kk, Cgp):
+    """the standardised weight's gradient back through the standardisation into the arena (weight and gain)"""
+    check(_lib.load().ia_ws_conv_weight_bwd(dwhat.data_ptr(), conv.weight.data_ptr(), conv.gain.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                                            conv.weight.grad.data_ptr(), conv.gain.grad.data_ptr(), conv.out_channels, ci, kk, Cgp, conv.scale,
+                                            stream_ptr()), "ia_ws_conv_weight_bwd")
+    Fn._notify([p for p in (conv.weight, conv.bias, conv.gain) if p is not None])
+
+
+def _bias_grad_ptr(conv):
+    return conv.bias.grad.data_ptr() if conv.bias is not None and conv.bias.requires_grad else None
+
+
 # ----------------------------------------------------------------------------------------- autograd glue
 class StdConvFn(torch.autograd.Function):
     """ScaledStdConv2d on NHWC rows: standardise the weight (ia_ws_conv_weight_fwd), convolve (ia_conv_nhwc_fwd); backward
@@ -56,11 +76,7 @@ class StdConvFn(torch.autograd.Function):
         C, Cout, k, s, g = conv.in_pad, conv.out_channels, conv.kernel_size, conv.stride, conv.groups
         Cg, Cgp, kk = conv.weight.shape[1], C // g, k * k
         dev = x.device
-        what = torch.empty((Cout, kk * Cgp), device=dev, dtype=BF16)
-        mean = torch.empty(Cout, device=dev, dtype=F32)
-        rstd = torch.empty(Cout, device=dev, dtype=F32)
-        check(lib.ia_ws_conv_weight_fwd(conv.weight.data_ptr(), conv.gain.data_ptr(), what.data_ptr(), mean.data_ptr(), rstd.data_ptr(), Cout, Cg,
-                                        kk, Cgp, conv.scale, conv.eps, stream_ptr()), "ia_ws_conv_weight_fwd")
+        what, mean, rstd = _standardised(conv, Cg, kk, Cgp)
         Ho, Wo = (H, W) if k == 1 else ((H - 1) // s + 1, (W - 1) // s + 1)
         y = torch.empty((B * Ho * Wo, Cout), device=dev, dtype=BF16)
         wsb = lib.ia_conv_nhwc_workspace_bytes(B, H, W, C, Cout, k, s, g)
@@ -92,15 +108,11 @@ class StdConvFn(torch.autograd.Function):
                                             stream_ptr()), "ia_conv_nhwc_bwd_data")
         if conv.weight.requires_grad:
             dwhat = torch.empty((Cout, kk * Cgp), device=dev, dtype=F32)
-            bg = conv.bias.grad.data_ptr() if conv.bias is not None and conv.bias.requires_grad else None
             wws = ctx.cols_ws if ctx.cols_ws is not None else ws
-            check(lib.ia_conv_nhwc_bwd_weight(x.data_ptr(), dy.data_ptr(), dwhat.data_ptr(), bg, B, H, W, C, Cout, k, s, g,
+            check(lib.ia_conv_nhwc_bwd_weight(x.data_ptr(), dy.data_ptr(), dwhat.data_ptr(), _bias_grad_ptr(conv), B, H, W, C, Cout, k, s, g,
                                               int(ctx.cols_ws is not None), wws.data_ptr(), wsb, stream_ptr()), "ia_conv_nhwc_bwd_weight")
             ctx.cols_ws = None
-            check(lib.ia_ws_conv_weight_bwd(dwhat.data_ptr(), conv.weight.data_ptr(), conv.gain.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                            conv.weight.grad.data_ptr(), conv.gain.grad.data_ptr(), Cout, Cg, kk, Cgp, conv.scale, stream_ptr()),
-                  "ia_ws_conv_weight_bwd")
-            Fn._notify([p for p in (conv.weight, conv.bias, conv.gain) if p is not None])
+            _standardised_bwd(conv, dwhat, mean, rstd, Cg, kk, Cgp)
         ctx.saved = None
         return dx, None, None, None, None, None
 
@@ -119,11 +131,7 @@ class PaddedStdConvFn(torch.autograd.Function):
         Cin, Cout, g = conv.in_channels, conv.out_channels, conv.groups
         ci = Cin // g
         dev = xp.device
-        what = torch.empty((Cout, 9 * ci), device=dev, dtype=BF16)
-        mean = torch.empty(Cout, device=dev, dtype=F32)
-        rstd = torch.empty(Cout, device=dev, dtype=F32)
-        check(lib.ia_ws_conv_weight_fwd(conv.weight.data_ptr(), conv.gain.data_ptr(), what.data_ptr(), mean.data_ptr(), rstd.data_ptr(), Cout, ci, 9,
-                                        ci, conv.scale, conv.eps, stream_ptr()), "ia_ws_conv_weight_fwd")
+        what, mean, rstd = _standardised(conv, ci, 9, ci)
         yp = torch.empty((xp.shape[0], Cout), device=dev, dtype=BF16)
         check(lib.ia_conv3x3_padded_fwd(xp.data_ptr(), what.data_ptr(), ptr(conv.bias), yp.data_ptr(), B, H, W, Cin, Cout, g, stream_ptr()),
               "ia_conv3x3_padded_fwd")
@@ -153,15 +161,11 @@ class PaddedStdConvFn(torch.autograd.Function):
                       "ia_conv3x3_padded_bwd_data")
         if conv.weight.requires_grad:
             dwhat = torch.empty((Cout, 9 * ci), device=dev, dtype=F32)
-            bg = conv.bias.grad.data_ptr() if conv.bias is not None and conv.bias.requires_grad else None
             wsb = lib.ia_conv3x3_padded_workspace_bytes(B, H, W, Cin, Cout, g)
             ws = _ws(dev, wsb)
-            check(lib.ia_conv3x3_padded_bwd_weight(xp.data_ptr(), dyp.data_ptr(), dwhat.data_ptr(), bg, B, H, W, Cin, Cout, g, ws.data_ptr(), wsb,
-                                                   stream_ptr()), "ia_conv3x3_padded_bwd_weight")
-            check(lib.ia_ws_conv_weight_bwd(dwhat.data_ptr(), conv.weight.data_ptr(), conv.gain.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                            conv.weight.grad.data_ptr(), conv.gain.grad.data_ptr(), Cout, ci, 9, ci, conv.scale, stream_ptr()),
-                  "ia_ws_conv_weight_bwd")
-            Fn._notify([p for p in (conv.weight, conv.bias, conv.gain) if p is not None])
+            check(lib.ia_conv3x3_padded_bwd_weight(xp.data_ptr(), dyp.data_ptr(), dwhat.data_ptr(), _bias_grad_ptr(conv), B, H, W, Cin, Cout, g,
+                                                   ws.data_ptr(), wsb, stream_ptr()), "ia_conv3x3_padded_bwd_weight")
+            _standardised_bwd(conv, dwhat, mean, rstd, ci, 9, ci)
         ctx.saved = None
         return dxp, None, None, None, None, None
 
@@ -179,11 +183,7 @@ class PaddedS2ConvFn(torch.autograd.Function):
         Cin, Cout, g = conv.in_channels, conv.out_channels, conv.groups
         ci = Cin // g
         dev = xp.device
-        what = torch.empty((Cout, 9 * ci), device=dev, dtype=BF16)
-        mean = torch.empty(Cout, device=dev, dtype=F32)
-        rstd = torch.empty(Cout, device=dev, dtype=F32)
-        check(lib.ia_ws_conv_weight_fwd(conv.weight.data_ptr(), conv.gain.data_ptr(), what.data_ptr(), mean.data_ptr(), rstd.data_ptr(), Cout, ci, 9,
-                                        ci, conv.scale, conv.eps, stream_ptr()), "ia_ws_conv_weight_fwd")
+        what, mean, rstd = _standardised(conv, ci, 9, ci)
         Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
         rows = B * Ho * Wo if y_compact else B * (Ho + 2) * (Wo + 2)
         yp = torch.empty((rows, Cout), device=dev, dtype=BF16)
@@ -217,13 +217,9 @@ class PaddedS2ConvFn(torch.autograd.Function):
                   "ia_conv3x3_s2_padded_bwd_data_t")
         if conv.weight.requires_grad:
             dwhat = torch.empty((Cout, 9 * ci), device=dev, dtype=F32)
-            bg = conv.bias.grad.data_ptr() if conv.bias is not None and conv.bias.requires_grad else None
-            check(lib.ia_conv3x3_s2_padded_bwd_weight(xp.data_ptr(), dyp.data_ptr(), dwhat.data_ptr(), bg, B, H, W, Cin, Cout, g, yc, ws.data_ptr(), wsb,
-                                                      stream_ptr()), "ia_conv3x3_s2_padded_bwd_weight")
-            check(lib.ia_ws_conv_weight_bwd(dwhat.data_ptr(), conv.weight.data_ptr(), conv.gain.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                            conv.weight.grad.data_ptr(), conv.gain.grad.data_ptr(), Cout, ci, 9, ci, conv.scale, stream_ptr()),
-                  "ia_ws_conv_weight_bwd")
-            Fn._notify([p for p in (conv.weight, conv.bias, conv.gain) if p is not None])
+            check(lib.ia_conv3x3_s2_padded_bwd_weight(xp.data_ptr(), dyp.data_ptr(), dwhat.data_ptr(), _bias_grad_ptr(conv), B, H, W, Cin, Cout, g, yc,
+                                                      ws.data_ptr(), wsb, stream_ptr()), "ia_conv3x3_s2_padded_bwd_weight")
+            _standardised_bwd(conv, dwhat, mean, rstd, ci, 9, ci)
         ctx.saved = None
         return dxp, None, None, None, None, None, None
 
@@ -326,14 +322,13 @@ class EcaResidualFn(torch.autograd.Function):
 
     pre = (a, what, bias): x = a what^T + bias is the output of a 1x1 convolution (conv3): the ECA pooling mean_HW(x) is then taken as
     (mean_HW a) what^T + bias -- exact, the mean commutes with the per-pixel linear map -- from the 4 x narrower tensor a
-    (ia_eca_fwd_linear, round 6; IA_ECA_LINEAR=0 keeps the reduction over x for A/B runs).
-    act_mode 1 / 2 (with pre): the same pass also writes act = silu(out) * act_scale, the activation the NEXT block opens with
+    (ia_eca_fwd_linear, round 6).
+    act_mode 1 / 2: the same pass also writes act = silu(out) * act_scale, the activation the NEXT block opens with
     (act1(x) * beta; mode 2 hands it out twice: a downsampling block feeds it to conv1 and to the projected shortcut), so `out` is not
-    read back by a SiLU pass of its own; the gradient that arrives through act is folded into out's by ia_silu_bwd(_sum) here -- the
-    same kernels SiluFn.backward ran, the same arithmetic."""
+    read back by a SiLU pass of its own; the gradient that arrives through act is folded into out's by ia_eca_silu_bwd."""
 
     @staticmethod
-    def forward(ctx, x, shortcut, conv_w, eca, B, HW, coef, pre=None, act_scale=1.0, act_mode=0):
+    def forward(ctx, x, shortcut, conv_w, eca, B, HW, coef, pre, act_scale=1.0, act_mode=0):
         lib = _lib.load()
         x, shortcut = x.contiguous(), shortcut.contiguous()
         C, k = x.shape[1], conv_w.shape[-1]
@@ -341,22 +336,14 @@ class EcaResidualFn(torch.autograd.Function):
         out = torch.empty_like(x)
         pooled = torch.empty((B, C), device=dev, dtype=F32)
         gate = torch.empty((B, C), device=dev, dtype=F32)
-        act = None
-        if pre is not None and ECA_LINEAR:
-            a, what, bias = pre
-            Cmid = a.shape[1]
-            wsb = lib.ia_eca_fwd_linear_workspace_bytes(B, HW, Cmid)
-            ws = _ws(dev, wsb)
-            if act_mode:
-                act = torch.empty_like(x)
-            check(lib.ia_eca_fwd_linear(x.data_ptr(), a.data_ptr(), what.data_ptr(), ptr(bias), Cmid, conv_w.data_ptr(), k, shortcut.data_ptr(),
-                                        out.data_ptr(), ptr(act), act_scale, pooled.data_ptr(), gate.data_ptr(), B, HW, C, coef, ws.data_ptr(), wsb,
-                                        stream_ptr()), "ia_eca_fwd_linear")
-        else:
-            wsb = lib.ia_gap_workspace_bytes(B, HW, C)
-            ws = _ws(dev, wsb)
-            check(lib.ia_eca_fwd(x.data_ptr(), conv_w.data_ptr(), k, shortcut.data_ptr(), out.data_ptr(), pooled.data_ptr(), gate.data_ptr(), B, HW, C,
-                                 coef, ws.data_ptr(), wsb, stream_ptr()), "ia_eca_fwd")
+        a, what, bias = pre
+        Cmid = a.shape[1]
+        wsb = lib.ia_eca_fwd_linear_workspace_bytes(B, HW, Cmid)
+        ws = _ws(dev, wsb)
+        act = torch.empty_like(x) if act_mode else None
+        check(lib.ia_eca_fwd_linear(x.data_ptr(), a.data_ptr(), what.data_ptr(), ptr(bias), Cmid, conv_w.data_ptr(), k, shortcut.data_ptr(),
+                                    out.data_ptr(), ptr(act), act_scale, pooled.data_ptr(), gate.data_ptr(), B, HW, C, coef, ws.data_ptr(), wsb,
+                                    stream_ptr()), "ia_eca_fwd_linear")
         ctx.eca, ctx.saved, ctx.dims = eca, (x, pooled, gate), (B, HW, C, k, coef)
         ctx.act_scale, ctx.out = act_scale, (out if act is not None else None)
         if act is None:
@@ -372,8 +359,7 @@ class EcaResidualFn(torch.autograd.Function):
         w = ctx.eca.conv.weight
         if ctx.out is not None:
             # out's whole gradient = what arrives at `out` itself (the next block's identity shortcut; nothing for a downsampling block)
-            # + (dact [+ dact2]) * act_scale * silu'(out): formed by ia_eca_silu_bwd in the pass that also takes the gate gradient's spatial
-            # sums (IA_NFNET_FUSE_TAIL=2: by ia_silu_bwd(_sum) first, then the plain ia_eca_bwd -- the two-kernel form, for A/B runs)
+            # + (dact [+ dact2]) * act_scale * silu'(out): formed by ia_eca_silu_bwd in the pass that also takes the gate gradient's spatial sums
             g1, g2 = (dact, dact2) if dact is not None else (dact2, None)
             out, ctx.out = ctx.out, None
             if g1 is not None:
@@ -381,24 +367,16 @@ class EcaResidualFn(torch.autograd.Function):
                 dadd = None if dout is None else dout.contiguous()
                 g1 = g1.contiguous()
                 g2 = None if g2 is None else g2.contiguous()
-                if FUSE_TAIL_BWD:
-                    dx = torch.empty_like(x)
-                    wsb = lib.ia_eca_bwd_workspace_bytes(B, HW, C)
-                    ws = _ws(dtot.device, wsb)
-                    check(lib.ia_eca_silu_bwd(g1.data_ptr(), ptr(g2), out.data_ptr(), ptr(dadd), ctx.act_scale, x.data_ptr(), w.data_ptr(), k,
-                                              pooled.data_ptr(), gate.data_ptr(), dtot.data_ptr(), dx.data_ptr(),
-                                              w.grad.data_ptr() if w.requires_grad else None, B, HW, C, coef, ws.data_ptr(), wsb, stream_ptr()),
-                          "ia_eca_silu_bwd")
-                    Fn._notify([w])
-                    ctx.saved = None
-                    return dx, dtot, None, None, None, None, None, None, None, None
-                if g2 is None:
-                    check(lib.ia_silu_bwd(g1.data_ptr(), out.data_ptr(), ptr(dadd), dtot.data_ptr(), out.numel(), ctx.act_scale, stream_ptr()),
-                          "ia_silu_bwd")
-                else:
-                    check(lib.ia_silu_bwd_sum(g1.data_ptr(), g2.data_ptr(), out.data_ptr(), ptr(dadd), dtot.data_ptr(), out.numel(), ctx.act_scale,
-                                              stream_ptr()), "ia_silu_bwd_sum")
-                dout = dtot
+                dx = torch.empty_like(x)
+                wsb = lib.ia_eca_bwd_workspace_bytes(B, HW, C)
+                ws = _ws(dtot.device, wsb)
+                check(lib.ia_eca_silu_bwd(g1.data_ptr(), ptr(g2), out.data_ptr(), ptr(dadd), ctx.act_scale, x.data_ptr(), w.data_ptr(), k,
+                                          pooled.data_ptr(), gate.data_ptr(), dtot.data_ptr(), dx.data_ptr(),
+                                          w.grad.data_ptr() if w.requires_grad else None, B, HW, C, coef, ws.data_ptr(), wsb, stream_ptr()),
+                      "ia_eca_silu_bwd")
+                Fn._notify([w])
+                ctx.saved = None
+                return dx, dtot, None, None, None, None, None, None, None, None
         if dout is None:
             ctx.saved = None
             return (None,) * 10
@@ -567,10 +545,11 @@ class NormFreeBlock(nn.Module):
         else:
             out = self.conv2(act(out))
             out = act(self.conv2b(act(out)))
-        a = out.t                                                 # conv3's input [B*H*W, mid] (contiguous: every producer above allocates it)
+        a = out.t                                                 # conv3's input [B*H*W, mid]
+        assert a.is_contiguous(), "conv3's input must be contiguous rows (every producer above allocates it): the ECA pooling reads it"
         out = self.conv3(out)
-        pre = (a, self.conv3.__dict__.pop("_last_what"), self.conv3.bias) if a.is_contiguous() else None
-        fuse = next_block is not None and pre is not None and ECA_LINEAR and FUSE_TAIL_ACT
+        pre = (a, self.conv3.__dict__.pop("_last_what"), self.conv3.bias)
+        fuse = next_block is not None
         mode = 0 if not fuse else (2 if next_block.downsample is not None else 1)
         y = EcaResidualFn.apply(out.t, shortcut, self.attn_last.conv.weight, self.attn_last, out.B, out.H * out.W, self.attn_gain * self.alpha, pre,
                                 next_block.beta if fuse else 1.0, mode)

@@ -216,7 +216,7 @@ def test_c5_full_width_coca_pair(gpu):
     # eps * mean_k(K) -- small against |dq| of a trained model, comparable to that weak covariance here.  Every layer below averages
     # the same effect over its 255 query rows (layer 0: 0.017).  DESIGN.md 5 records it as a deviation of bf16 context storage.
     # Being noise, the figure moves with any change of a rounding point upstream: 0.9740 / 0.274 since the QKV projection rounds
-    # q * scale * log2 e once (IA_Q_PRESCALE=1) instead of q and then q * sc inside the kernels (0.9858 / 0.268).
+    # q * scale * log2 e once (the engine's q pre-scale) instead of q and then q * sc inside the kernels (0.9858 / 0.268).
     # Round 5 -- the exception is MEASURED here, not only argued: the same oracle under bf16 storage rounding with delta taken the
     # flash way (rowsum(dO o O_rounded), oracle.ref_models.rounding(bf16, flash_delta=True)) moves this one tensor by the same order
     # (tools/c5_delta_probe.py, profiles/r05_c5_delta_probe.txt: fp32 vs bf16 0.029, fp32 vs bf16 + flash delta 0.212, HIP vs fp32

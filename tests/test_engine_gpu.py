@@ -47,7 +47,9 @@ def ref_layer(P, x, mask, nh, pre_ln, eps):
 
 
 @pytest.mark.parametrize("B,L,nh,pre_ln,masked", [(3, 40, 2, False, True), (2, 255, 4, False, True), (2, 65, 2, True, False),
-                                                   (2, 577, 12, True, False), (2, 510, 16, False, True)])
+                                                   (2, 577, 12, True, False), (2, 510, 16, False, True),
+                                                   # hidden sizes off the 128 multiple: the un-prescaled QKV projection and attention kernels
+                                                   (2, 40, 3, False, True), (2, 65, 1, True, False)])
 def test_layer_fwd_bwd(gpu, B, L, nh, pre_ln, masked):
     from item_alignment_amd import _lib
     from item_alignment_amd._lib import LayerCfg, LayerGrads, LayerWeights
