@@ -37,6 +37,12 @@ SIGNATURES = {
     "ia_gemm_bf16": (i32, [vp, i32, i32, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp, sz, vp]),
     "ia_gemm_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "ia_gemm_colsum_workspace_bytes": (sz, [i32, i32]),
+    "ia_gemm_wgrad_rows_workspace_bytes": (sz, [i32, i32, i32]),
+    "ia_gemm_wgrad_rows_filters": (i32, [i32, i32, i32]),
+    "ia_gemm_wgrad_rows": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, vp, i32, vp, sz, vp]),
+    "ia_ktile_mask_bytes": (sz, [i32]),
+    "ia_ktile_mask": (i32, [vp, i32, vp, vp]),
+    "ia_ktile_mask_host": (i32, [vp, i32, vp]),
     "ia_prof_begin": (i32, [i32, i32]),
     "ia_prof_end": (i32, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i32)]),
     "ia_prof_bytes": (C.c_double, []),
@@ -184,7 +190,7 @@ SIGNATURES = {
 _lib = None
 
 
-ABI_VERSION = 15      # = IA_ABI_VERSION of include/itemalign.h (tests/test_cabi_symbols.py keeps the two in step)
+ABI_VERSION = 16      # = IA_ABI_VERSION of include/itemalign.h (tests/test_cabi_symbols.py keeps the two in step)
 
 
 class ItemAlignError(RuntimeError):

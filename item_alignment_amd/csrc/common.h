@@ -197,4 +197,9 @@ extern "C" size_t ia_colsum_workspace_bytes(int M, int N);
 extern "C" int ia_colsum(const void* x, int ld, int M, int N, float* out, int accumulate, void* workspace, size_t workspace_bytes,
                          hipStream_t stream);
 __attribute__((visibility("hidden"))) size_t ia_gemm_view_workspace_bytes(int M, int N, int K, int groups);
+// dW[N_out, N_in] (+)= dY^T X over the k-tiles (64 token rows each) whose bit is set in ktile_mask (ia_ktile_mask): the weight-gradient
+// form of ia_gemm_bf16 for a caller that has the mask of its rows already (ia_layer_bwd2: one mask, four weight gradients)
+__attribute__((visibility("hidden"))) int ia_gemm_wgrad_masked(const void* dY, int ldy, const void* X, int ldx, float* dW, int ldw, int N_out,
+                                                               int N_in, int M_rows, const uint32_t* ktile_mask, int accumulate,
+                                                               void* workspace, size_t workspace_bytes, hipStream_t stream);
 

@@ -72,7 +72,7 @@ FwdBufs carve_infer(const ia_layer_cfg* c, void* base) {
 }
 
 struct Scratch {
-  char* g0; char* g1; char* g2; char* gI; char* gqkv; float* delta; char* ws; size_t ws_bytes; char* gws; size_t gws_bytes; size_t bytes;
+  char* g0; char* g1; char* g2; char* gI; char* gqkv; float* delta; char* ws; size_t ws_bytes; char* gws; size_t gws_bytes; uint32_t* live_kt; size_t bytes;
 };
 
 size_t max3(size_t a, size_t b, size_t c) { return a > b ? (a > c ? a : c) : (b > c ? b : c); }
@@ -91,6 +91,8 @@ Scratch carve_scratch(const ia_layer_cfg* c, void* base) {
   s.gws_bytes = max3(ia_gemm_workspace_bytes((int)(3 * H), (int)H, (int)M, 1), ia_gemm_workspace_bytes((int)I, (int)H, (int)M, 1),
                      max3(ia_gemm_workspace_bytes((int)H, (int)I, (int)M, 1), ia_gemm_workspace_bytes((int)H, (int)H, (int)M, 1), 0));
   s.gws = a.take(s.gws_bytes);
+  // masked_rows_dead: which 64-row k-tiles of the weight gradients hold a live row (one bit each)
+  s.live_kt = (uint32_t*)a.take(ia_ktile_mask_bytes((int)M));
   s.bytes = a.bytes;
   return s;
 }
@@ -109,6 +111,12 @@ int dgrad(const void* dy, int k_out, const void* w, const void* wt, int n_in, vo
   if (wt)
     return ia_gemm_bf16(dy, 0, k_out, wt, 0, k_out, dx, 0, n_in, M, n_in, k_out, epilogue, nullptr, aux, ldaux, c2, 0, ws, ws_bytes, st);
   return ia_gemm_bf16(dy, 0, k_out, w, 1, n_in, dx, 0, n_in, M, n_in, k_out, epilogue, nullptr, aux, ldaux, c2, 0, ws, ws_bytes, st);
+}
+
+// Weight gradient dW[n_out, n_in] += dy[M, n_out]^T x[M, n_in]; with a live-k-tile mask, over the k-tiles that hold a live row only
+int wgrad(const void* dy, int n_out, const void* x, int n_in, float* dw, int M, const uint32_t* live_kt, void* ws, size_t ws_bytes, ia_stream_t st) {
+  if (live_kt) return ia_gemm_wgrad_masked(dy, n_out, x, n_in, dw, n_in, n_out, n_in, M, live_kt, 1, ws, ws_bytes, st);
+  return ia_gemm_bf16(dy, 1, n_out, x, 1, n_in, dw, 1, n_in, n_out, n_in, M, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 1, ws, ws_bytes, st);
 }
 
 // The QKV projection of a layer writes q already multiplied by softmax scale * log2(e) (one bf16 rounding, in the GEMM epilogue where
@@ -250,18 +258,21 @@ extern "C" int ia_layer_bwd2(const ia_layer_cfg* c, const ia_layer_weights* w, c
   const uint32_t attn_seed = c->seed * 2654435761u + c->layer_id * 97u + 17u;
   const bool drop = c->hidden_drop > 0.f;
   if (!c->pre_ln) {
-    // masked_rows_dead: every gradient row of a masked position is exactly zero (ia_layer_cfg): the LayerNorm backward kernels skip them
+    // masked_rows_dead: every gradient row of a masked position is exactly zero (ia_layer_cfg): the LayerNorm backward kernels skip them,
+    // and the four weight gradients skip the 64-row k-tiles that hold nothing else (one bitmask per call, in scratch)
     const uint8_t* const live = (c->masked_rows_dead && !c->cu_seqlens) ? key_mask : nullptr;
+    const uint32_t* const live_kt = live ? k.live_kt : nullptr;
+    if (live) IA_TRY(ia_ktile_mask(live, M, k.live_kt, st));
     // The two residual additions of a post-LN layer make each LayerNorm output's gradient a sum of two terms; both LayerNorm
     // backward kernels take the two terms (ia_ln_bwd2), so the GEMMs in front of them keep the plain epilogue.
     // LN2 backward: d(output) = dy (+ dy2) -> dz2 in g0, masked branch gradient -> g1 (or g0 when p == 0)
     IA_TRY(ia_ln_bwd2_rows(dy, dy2, nullptr, s.ffn, s.mean2, s.rstd2, w->ln2_g, k.g0, drop ? k.g1 : nullptr, g->ln2_g, g->ln2_b, g->b_fc2, M, H,
                            c->hidden_drop, c->seed, c->layer_id * 4u + 1u, live, k.ws, k.ws_bytes, 1, st));
     const char* d_ffn = drop ? k.g1 : k.g0;
-    IA_TRY(ia_gemm_bf16(d_ffn, 1, H, s.hact, 1, I, g->w_fc2, 1, I, H, I, M, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 1, k.gws, k.gws_bytes, st));
+    IA_TRY(wgrad(d_ffn, H, s.hact, I, (float*)g->w_fc2, M, live_kt, k.gws, k.gws_bytes, st));
     // d(pre-activation) = (d_ffn W2) * gelu'(pre), and its column sums (the fc1 bias gradient) out of the same epilogue
     IA_TRY(dgrad(d_ffn, H, w->w_fc2, w->wt_fc2, I, k.gI, M, IA_EPI_DGELU_COLSUM, s.hpre, I, g->b_fc1, k.ws, k.ws_bytes, st));
-    IA_TRY(ia_gemm_bf16(k.gI, 1, I, s.ln, 1, H, g->w_fc1, 1, H, I, H, M, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 1, k.gws, k.gws_bytes, st));
+    IA_TRY(wgrad(k.gI, I, s.ln, H, (float*)g->w_fc1, M, live_kt, k.gws, k.gws_bytes, st));
     IA_TRY(dgrad(k.gI, I, w->w_fc1, w->wt_fc1, H, k.g2, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st));
     // LN1 backward: d(y1) = g2 (through fc1) + g0 (residual into LN2) -> dz1 (the layer input's residual-path gradient) in
     // dz1buf: the caller's dx2 when the split form is wanted, else g0 (in place over the term just consumed)
@@ -269,10 +280,10 @@ extern "C" int ia_layer_bwd2(const ia_layer_cfg* c, const ia_layer_weights* w, c
     IA_TRY(ia_ln_bwd2_rows(k.g2, k.g0, nullptr, s.proj, s.mean1, s.rstd1, w->ln1_g, dz1buf, drop ? k.g1 : nullptr, g->ln1_g, g->ln1_b, g->b_o, M, H,
                            c->hidden_drop, c->seed, c->layer_id * 4u + 0u, live, k.ws, k.ws_bytes, 1, st));
     const char* d_att = drop ? k.g1 : dz1buf;
-    IA_TRY(ia_gemm_bf16(d_att, 1, H, s.ctx, 1, H, g->w_o, 1, H, H, H, M, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 1, k.gws, k.gws_bytes, st));
+    IA_TRY(wgrad(d_att, H, s.ctx, H, (float*)g->w_o, M, live_kt, k.gws, k.gws_bytes, st));
     IA_TRY(dgrad(d_att, H, w->w_o, w->wt_o, H, k.g2, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st));
     IA_TRY(attn_bwd(c, s.qkv, key_mask, s.ctx, k.g2, s.lse, k.delta, k.gqkv, g->b_qkv, k.ws, k.ws_bytes, scale, c->attn_drop, attn_seed, st));
-    IA_TRY(ia_gemm_bf16(k.gqkv, 1, 3 * H, x, 1, H, g->w_qkv, 1, H, 3 * H, H, M, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 1, k.gws, k.gws_bytes, st));
+    IA_TRY(wgrad(k.gqkv, 3 * H, x, H, (float*)g->w_qkv, M, live_kt, k.gws, k.gws_bytes, st));
     if (dx2)   // split form: dx = the attention sub-block's data gradient, dx2 = dz1 (already written)
       IA_TRY(dgrad(k.gqkv, 3 * H, w->w_qkv, w->wt_qkv, H, dx, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st));
     else

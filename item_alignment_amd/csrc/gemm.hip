@@ -40,10 +40,22 @@ constexpr int BK = 64;
 constexpr uint32_t OOB = 0xFFFFFFF0u;
 
 enum { EPI_NONE = 0, EPI_BIAS = 1, EPI_BIAS_GELU = 2, EPI_ADD = 3, EPI_DGELU = 4, EPI_BIAS_ADD = 5, EPI_DGELU_CS = 6, EPI_BIAS_GELU_ACT = 7 };
+// EPI_NONE_LIVE (library-internal, t256w only): EPI_NONE behind a k loop over the live k-tiles.  The weight-gradient form dW = dY^T X has
+// the token rows as k: a k-tile whose rows of dY are all zeros adds +-0 to every accumulator, so leaving it out changes no bit of the
+// fp32 sums -- the k-slabs of a split-K launch and the order of the reduction stay what they are, a slab just takes fewer trips.
+constexpr int EPI_NONE_LIVE = 8;
 // EPI_BIAS_GELU_ACT: the forward-only form of EPI_BIAS_GELU (activation only: no derivative is evaluated or stored)
 
 struct GemmArgs {
-  const bf16* A; const bf16* B; void* C; bf16* C2; const float* bias; const bf16* aux;
+  const bf16* A; const bf16* B; void* C; bf16* C2;
+  union {
+    const float* bias;
+    // Weight-gradient form of the 256-wide kernel only (IA_EPI_NONE: no bias; the member shares its slot so that no other kernel's
+    // argument block moves): bit t of this bitmask set = k-tile t (k rows 64t .. 64t+63) has at least one row of A that is not known
+    // to be all zeros; a workgroup walks only the set bits of its k-slab (t256w::gemm_kernel<true, true, EPI_NONE_LIVE, true>).  NULL = every k-tile.
+    const uint32_t* live_kt;
+  };
+  const bf16* aux;
   int M, N, K;
   int lda, ldb, ldc, ldaux;
   uint64_t a_bytes, b_bytes;  // bytes addressable from A / B (to the end of the tensor); each workgroup re-bases a < 2 GiB buffer window inside them
@@ -574,6 +586,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs p) {
 namespace t256w {
 constexpr int BM = 256, BN = 256, TILE_BYTES = 32768;        // one operand's k-tile: 256 rows x 64 k (or 64 k x 256 columns) of bf16
 constexpr int STAGE_BYTES = 16 * 64 * 4;                   // epilogue staging slot (16 rows x 64 columns fp32); each of the four waves owns two
+constexpr int LIVE_MAX_KTILES = 64 * 32;                   // EPI_NONE_LIVE: a k-slab's live-k-tile mask is one 32-bit word per lane
 constexpr int LDS_BYTES = 2 * 2 * TILE_BYTES + 8 * STAGE_BYTES;   // 128 KiB k-tile double buffer (A | B, twice) + 4 x 8 KiB = all 160 KiB of the CU
 
 // One operand's four fragments of a k-step.  A k-strided operand's fragment arrives as two transpose reads: the halves are kept
@@ -684,10 +697,35 @@ IA_DEV void mfma_step(f32x16 (&acc)[4][4], const FA& fa, const FB& fb, Filler&& 
     }
 }
 
-template <bool AKS, bool BKS, int PEND, bool PEEL_OK = true>
+// Walk over the set bits of a k-slab's live-k-tile mask in increasing order.  Lane l of `mv` holds bits 32l .. 32l+31 of the slab (every
+// wave holds the same 64 words, fetched once in front of the first prologue DMA); the walk itself is SALU plus one v_readlane per step --
+// no memory operation, so it can sit next to the k loop's counted waits, and no branch.  Once the bits are used up next() keeps
+// returning the index behind the last one it gave: the look-ahead pieces past the end then address what they address in the dense
+// kernel (the k-tiles right behind the last one consumed).
+struct LiveWalk {
+  uint64_t rest;      // words with a set bit that have not been opened yet
+  uint32_t w;         // bits of the open word not handed out yet
+  int wi, cur;        // the open word; the last index handed out
+};
+IA_DEV void live_start(LiveWalk& k, uint32_t mv) { k.rest = __ballot(mv != 0u); k.w = 0u; k.wi = 0; k.cur = -1; }
+IA_DEV int live_next(LiveWalk& k, uint32_t mv) {
+  const bool open = k.w == 0u, any = k.rest != 0ull;
+  const int wi = open ? (any ? __builtin_ctzll(k.rest) : 0) : k.wi;
+  const uint32_t fetched = __builtin_amdgcn_readlane(mv, wi);
+  const uint32_t w = open ? (any ? fetched : 0u) : k.w;
+  k.rest = open ? (k.rest & (k.rest - 1ull)) : k.rest;
+  const int idx = w != 0u ? wi * 32 + __builtin_ctz(w) : k.cur + 1;
+  k.w = w & (w - 1u); k.wi = wi; k.cur = idx;
+  return idx;
+}
+
+// LIVE (both operands k-strided): the k loop runs over the n_tiles set bits of live_mv (the slab's live k-tiles, see LiveWalk) instead of
+// k-tiles 0 .. n_tiles-1 of the slab.
+template <bool AKS, bool BKS, int PEND, bool PEEL_OK = true, bool LIVE = false>
 IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdgpu_buffer_rsrc_t rsA, __amdgpu_buffer_rsrc_t rsB, int xa, int xb,
                       int kt0, int ktaA0, int ktaB0, int n_tiles, int nk_all, int wm, int wn, int wave, int lane, bool prologue_only,
-                      bool stores_in_flight) {
+                      bool stores_in_flight, uint32_t live_mv = 0u) {
+  static_assert(!LIVE || (AKS && BKS), "the live-k-tile walk advances the running lane offsets of two k-strided operands");
   constexpr bool ROUND = !AKS && !BKS;      // the k loop's schedule (below)
   const int li = lane & 31;
   const int gt = wave * 64 + lane;                  // thread index inside the workgroup (0..255)
@@ -706,6 +744,10 @@ IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdg
   char* const my_part = smem + wave * 1024;
   const int dbg = IA_GEMM_DBG_HOOKS ? p.dbg : 0;       // the timing ablations (IA_GEMM_DBG bits 2 / 4 / 16) exist in tools builds only
   const bool dma_on = !(dbg & 2);
+  // LIVE: the slab-relative indices of the first two live k-tiles (the prologue's)
+  [[maybe_unused]] LiveWalk lw;
+  int live0 = 0, live1 = 1;
+  if constexpr (LIVE) { live_start(lw, live_mv); live0 = live_next(lw, live_mv); live1 = live_next(lw, live_mv); }
 
   // piece i (0..7: A, 8..15: B) of k-tile u -> buffer u & 1.  Branch-free (a branch next to the accumulator updates makes hipcc copy
   // all 256 of them): lim = number of valid k in this k-tile (0 for a k-tile past the end: the whole piece goes out of range and
@@ -714,7 +756,8 @@ IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdg
     const bool isB = i >= 8;
     const int j = i & 7;
     char* dst = my_part + (isB ? TILE_BYTES : 0) + (u & 1) * 2 * TILE_BYTES + j * 4096;
-    const int kt = kt0 + u, kta = (dbg & 4) ? 0 : (isB ? ktaB0 : ktaA0) + u;      // dbg 4: every k-tile re-fetches k-tile 0 (cache-resident)
+    const int kt = kt0 + u;
+    const int kta = (dbg & 4) ? 0 : (isB ? ktaB0 : ktaA0) + (LIVE ? (u == 0 ? live0 : live1) : u);      // dbg 4: every k-tile re-fetches k-tile 0 (cache-resident)
     const bool ks = isB ? BKS : AKS;
     const uint32_t soff = (uint32_t)kta * (isB ? kstepB : kstepA) + (uint32_t)j * (isB ? stepB : stepA);
     if (ks) {
@@ -724,7 +767,9 @@ IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdg
       // slab's first rows instead of zeros: nobody consumes that buffer.)  Data gradient +4 %, weight gradient +0.7 %; the memory-side
       // fetches of both went UP 4-8 % with it (FETCH_SIZE 0.996 -> 1.076 GB per weight-gradient launch, same box, against compare +
       // select per piece): far more than the two look-ahead k-tiles -- the workgroups that share a panel out of one L2 drift further apart.
-      const uint32_t off = dma_on ? (isB ? voffB : voffA) + soff : OOB;
+      // (LIVE: a slab with fewer than two live k-tiles has nothing behind them to address -- those prologue k-tiles go out of range and
+      // arrive as zeros, which is what the one trip of a slab without any live k-tile multiplies)
+      const uint32_t off = (dma_on && (!LIVE || u < n_tiles)) ? (isB ? voffB : voffA) + soff : OOB;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(isB ? rsB : rsA, IA_LDS(dst), 16, off, 0, 0, 0);
     } else {
       const int lim = (u < n_tiles && dma_on) ? p.K - kt * BK : 0;
@@ -749,7 +794,9 @@ IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdg
   };
 
   // second schedule (a k-strided operand): in-loop pieces of k-tile u+2; the k-strided operand's k-tile advance lives in a running lane offset
-  uint32_t runA = voffA + (uint32_t)((dbg & 4) ? 0 : ktaA0 + 2) * kstepA, runB = voffB + (uint32_t)((dbg & 4) ? 0 : ktaB0 + 2) * kstepB;
+  int live2 = 2;
+  if constexpr (LIVE) { if (!prologue_only) live2 = live_next(lw, live_mv); }      // (the prologue call stops at the first two)
+  uint32_t runA = voffA + (uint32_t)((dbg & 4) ? 0 : ktaA0 + live2) * kstepA, runB = voffB + (uint32_t)((dbg & 4) ? 0 : ktaB0 + live2) * kstepB;
   auto dma_run = [&](int u, int i) {
     const bool isB = i >= 8;
     if (!(isB ? BKS : AKS) || (dbg & 4)) { dma_piece(u, i); return; }
@@ -890,8 +937,15 @@ IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdg
     ++u;
     // one running lane offset per k-strided operand, opaque to the loop optimiser: left alone it keeps SIXTEEN induction variables
     // (one per piece) and bumps them all in the last MFMA gap of the trip
-    if (AKS) { runA += kstepA; asm volatile("" : "+v"(runA)); }
-    if (BKS) { runB += kstepB; asm volatile("" : "+v"(runB)); }
+    if constexpr (LIVE) {      // on to the next live k-tile: the same trip, a longer stride
+      const int at = lw.cur;
+      const uint32_t hop = (uint32_t)(live_next(lw, live_mv) - at);
+      runA += hop * kstepA; asm volatile("" : "+v"(runA));
+      runB += hop * kstepB; asm volatile("" : "+v"(runB));
+    } else {
+      if (AKS) { runA += kstepA; asm volatile("" : "+v"(runA)); }
+      if (BKS) { runB += kstepB; asm volatile("" : "+v"(runB)); }
+    }
   } while (u < n_tiles);
   tie<0>(a0); tie<0>(b0);      // dead, but in flight (see the ROUND loop's exit)
 }
@@ -1101,8 +1155,13 @@ IA_DEV void drain_half(const GemmArgs& p, f32x16 (&acc)[4][4], int m0, int n0, c
   if (full && (HAS_BIAS || HAS_AUX) && !(IA_DBG(p) & 256)) drain(std::true_type{}); else drain(std::false_type{});
 }
 
-template <bool AKS, bool BKS, int EPI, bool OUTF32>
+// EPI_ = EPI_NONE_LIVE: the plain epilogue behind a k loop over the live k-tiles only (GemmArgs::live_kt; weight-gradient form).  A value
+// of the epilogue parameter, not a parameter of its own: the other instantiations keep their names in profiles and traces.
+template <bool AKS, bool BKS, int EPI_, bool OUTF32>
 __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
+  constexpr bool LIVE = EPI_ == EPI_NONE_LIVE;
+  constexpr int EPI = LIVE ? (int)EPI_NONE : EPI_;
+  static_assert(!LIVE || (AKS && BKS && OUTF32), "live k-tiles: the weight-gradient form only");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane0 = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1122,7 +1181,20 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
     ordered = true;
   }
   const int kt0 = p.split_id * p.nk_per_split;
-  const int n_tiles = min(nk_all, kt0 + p.nk_per_split) - kt0;
+  int n_tiles = min(nk_all, kt0 + p.nk_per_split) - kt0;
+  // LIVE: the 64 mask words of this k-slab, one per lane (the host refuses the mask for slabs of more than 2048 k-tiles), fetched
+  // here -- one vector load pair per lane, waited for on the spot -- so that the k loop's walk over them touches no memory.  A slab starts
+  // at any bit of the mask: each lane shifts its 32 bits out of two words, and clips them to the slab's end.
+  uint32_t live_mv = 0u;
+  if constexpr (LIVE) {
+    const int nw = (nk_all + 31) >> 5, first = kt0 + 32 * lane0, wlo = first >> 5, sh = first & 31, left = n_tiles - 32 * lane0;
+    const uint32_t lo = wlo < nw ? p.live_kt[wlo] : 0u, hi = wlo + 1 < nw ? p.live_kt[wlo + 1] : 0u;
+    live_mv = sh ? (lo >> sh) | (hi << (32 - sh)) : lo;
+    live_mv = left >= 32 ? live_mv : (left > 0 ? live_mv & ((1u << left) - 1u) : 0u);
+    n_tiles = 0;
+    for (uint64_t rest = __ballot(live_mv != 0u); rest; rest &= rest - 1ull)
+      n_tiles += __builtin_popcount(__builtin_amdgcn_readlane(live_mv, __builtin_ctzll(rest)));
+  }
   constexpr int PEND = 2 * (16 * epi_stores_per_call<EPI, OUTF32>() + epi_extra_stores<EPI>());   // store instructions of one full-tile epilogue, per wave
   auto coords = [&](int tile, int& bm, int& bn) {
     if (ordered) tile_of_order(p, tile, bm, bn); else tile_of_index(p, tile, total_tiles, bm, bn);
@@ -1135,8 +1207,8 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
     const uint64_t oa = (uint64_t)(AKS ? kt0 * BK : bm * BM) * p.lda, ob = (uint64_t)(BKS ? kt0 * BK : bn * BN) * p.ldb;
     // (the bf16 bias form keeps 64 bias values in registers across the main loop -- 468 of 512: the peeled first trip spilled there)
     constexpr bool PEEL_OK = !(EPI == EPI_BIAS && !OUTF32 && !BKS);
-    main_loop<AKS, BKS, PEND, PEEL_OK>(p, smem, acc, rsrc_at(p.A, p.a_bytes, oa), rsrc_at(p.B, p.b_bytes, ob), AKS ? bm * BM : 0, BKS ? bn * BN : 0, kt0,
-                              AKS ? 0 : kt0, BKS ? 0 : kt0, n_tiles, nk_all, wm, wn, wave, lane, prologue_only, stores_in_flight);
+    main_loop<AKS, BKS, PEND, PEEL_OK, LIVE>(p, smem, acc, rsrc_at(p.A, p.a_bytes, oa), rsrc_at(p.B, p.b_bytes, ob), AKS ? bm * BM : 0, BKS ? bn * BN : 0, kt0,
+                              AKS ? 0 : kt0, BKS ? 0 : kt0, n_tiles, nk_all, wm, wn, wave, lane, prologue_only, stores_in_flight, live_mv);
   };
 
   // ---- Dynamic tile claim (persistent launches).  With the static order every workgroup owns the tiles bid, bid + gridDim.x, ...: a
@@ -1312,6 +1384,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
   }
   leave();
 }
+
 }  // namespace t256w
 
 
@@ -1623,7 +1696,10 @@ uint32_t* next_ctr_slot() {
 template <bool AKS, bool BKS, int EPI, bool OUTF32>
 int launch(GemmArgs a, bool big, hipStream_t st) {
   constexpr int vid = AKS * 1000 + BKS * 100 + EPI * 10 + (OUTF32 ? 1 : 0);
-  const bool rec = g_prof.on && g_prof.variant == vid && g_prof.n < g_prof.cap;
+  // (a launch over the live k-tiles only is not recorded: the host cannot know how many k-tiles it executed, and the recorded FLOPs are
+  // those of launches that executed all of theirs)
+  constexpr bool WGRAD = AKS && BKS && EPI == EPI_NONE && OUTF32;      // the form that may carry a live-k-tile mask (GemmArgs::live_kt)
+  const bool rec = g_prof.on && g_prof.variant == vid && g_prof.n < g_prof.cap && !(WGRAD && a.live_kt);
   if (rec) (void)hipEventRecord(g_prof.ev[2 * g_prof.n], st);
   if (big) {
     a.tiles_m = (a.M + t256w::BM - 1) / t256w::BM; a.tiles_n = (a.N + t256w::BN - 1) / t256w::BN;
@@ -1634,8 +1710,11 @@ int launch(GemmArgs a, bool big, hipStream_t st) {
     // persistent launches with more than one tile per workgroup claim their tiles dynamically (IA_GEMM_DYNAMIC=0: the static order)
     a.tile_ctr = (a.splits == 1 && ntile > gx) ? next_ctr_slot() : nullptr;
     void (*kern)(GemmArgs) = t256w::gemm_kernel<AKS, BKS, EPI, OUTF32>;
-    static bool attr_set[2] = {false, false};      // per kernel: [0] this instantiation of t256w, [1] t256la
+    static bool attr_set[3] = {false, false, false};      // per kernel: [0] this instantiation of t256w, [1] t256la, [2] the live-k-tile weight gradient
     int la = 0;
+    if constexpr (WGRAD) {
+      if (a.live_kt) { kern = t256w::gemm_kernel<true, true, EPI_NONE_LIVE, true>; la = 2; }
+    }
     // plain NT form, several tiles per workgroup, static order: the look-ahead kernel (t256la; IA_GEMM_LA=0 keeps t256w)
     if constexpr (!AKS && !BKS && EPI == EPI_NONE && !OUTF32) {
       const char* e = getenv("IA_GEMM_LA");       // (read per launch: tests and A/B runs switch it in one process)
@@ -1681,7 +1760,8 @@ extern "C" size_t ia_gemm_workspace_bytes(int M, int N, int K, int c_is_f32) {
 
 static int gemm_core(const void* A, int a_kstrided, int lda, const void* B, int b_kstrided, int ldb, void* C, int c_is_f32, int ldc, int M,
                      int N, int K, int epilogue, const float* bias, const void* aux, int ldaux, void* C2, int accumulate, void* workspace,
-                     size_t workspace_bytes, const IaViewGemm* view, hipStream_t stream, int qcols = 0, float qscale = 1.f);
+                     size_t workspace_bytes, const IaViewGemm* view, hipStream_t stream, int qcols = 0, float qscale = 1.f,
+                     const uint32_t* live_kt = nullptr);
 
 // workspace of an IA_EPI_DGELU_COLSUM GEMM: one fp32 row of N partial sums per 128-row block of the output (and never less than
 // the stand-alone column-sum kernel needs, which small shapes fall back to)
@@ -1705,6 +1785,79 @@ extern "C" int ia_gemm_bf16_qscale(const void* A, int lda, const void* B, int ld
                                    int scaled_cols, float col_scale, hipStream_t stream) {
   return gemm_core(A, 0, lda, B, 0, ldb, C, 0, ldc, M, N, K, EPI_BIAS, bias, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, stream, scaled_cols,
                    col_scale);
+}
+
+// ---- weight gradient over the live rows only
+// bit t of the mask = OR of row_live over rows 64t .. 64t+63 (clipped to M).  One function for the device kernel and the host entry.
+static __host__ __device__ inline uint32_t ktile_live(const uint8_t* row_live, int M, int t) {
+  const uint8_t* r = row_live + (size_t)t * BK;
+  const int n = M - t * BK < BK ? M - t * BK : BK;
+  uint64_t any = 0;
+  if (n == BK && ((uintptr_t)r & 7) == 0) {
+    for (int i = 0; i < BK / 8; ++i) any |= reinterpret_cast<const uint64_t*>(r)[i];
+  } else {
+    for (int i = 0; i < n; ++i) any |= r[i];
+  }
+  return any != 0 ? 1u : 0u;
+}
+namespace {
+// one thread per k-tile, one 64-bit ballot per wave = two whole mask words, stored by lanes 0 and 32 (plain stores, no atomics)
+__global__ __launch_bounds__(256) void ktile_mask_kernel(const uint8_t* __restrict__ row_live, int M, int nk, uint32_t* __restrict__ mask) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  const uint64_t b = __ballot(t < nk && ktile_live(row_live, M, t));
+  if ((threadIdx.x & 31) == 0 && t < nk) mask[t >> 5] = (uint32_t)(b >> (threadIdx.x & 32));
+}
+inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+}  // namespace
+
+extern "C" size_t ia_ktile_mask_bytes(int M_rows) {
+  if (M_rows <= 0) return 0;
+  return (size_t)(((M_rows + BK - 1) / BK + 31) / 32) * sizeof(uint32_t);
+}
+extern "C" int ia_ktile_mask(const uint8_t* row_live, int M_rows, uint32_t* mask, hipStream_t stream) {
+  (void)hipGetLastError();
+  if (!row_live || !mask || M_rows <= 0) return IA_ERR_ARG;
+  const int nk = (M_rows + BK - 1) / BK;
+  hipLaunchKernelGGL(ktile_mask_kernel, dim3((nk + 255) / 256), dim3(256), 0, stream, row_live, M_rows, nk, mask);
+  return ia_check_launch();
+}
+extern "C" int ia_ktile_mask_host(const uint8_t* row_live, int M_rows, uint32_t* mask) {
+  if (!row_live || !mask || M_rows <= 0) return IA_ERR_ARG;
+  const int nk = (M_rows + BK - 1) / BK;
+  for (int w = 0; w < (nk + 31) / 32; ++w) mask[w] = 0u;
+  for (int t = 0; t < nk; ++t) mask[t >> 5] |= ktile_live(row_live, M_rows, t) << (t & 31);
+  return IA_OK;
+}
+// library-internal (common.h): the weight gradient with a mask already built (ia_layer_bwd2 builds one per call for its four)
+int ia_gemm_wgrad_masked(const void* dY, int ldy, const void* X, int ldx, float* dW, int ldw, int N_out, int N_in, int M_rows,
+                         const uint32_t* ktile_mask, int accumulate, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  return gemm_core(dY, 1, ldy, X, 1, ldx, dW, 1, ldw, N_out, N_in, M_rows, EPI_NONE, nullptr, nullptr, 0, nullptr, accumulate, workspace,
+                   workspace_bytes, nullptr, stream, 0, 1.f, ktile_mask);
+}
+extern "C" size_t ia_gemm_wgrad_rows_workspace_bytes(int N_out, int N_in, int M_rows) {
+  if (N_out <= 0 || N_in <= 0 || M_rows <= 0) return 0;
+  return al256(ia_gemm_workspace_bytes(N_out, N_in, M_rows, 1)) + ia_ktile_mask_bytes(M_rows);
+}
+// 1: a call of this shape with row_live and the workspace of the query above walks the live k-tiles (256-wide kernel, at most
+// LIVE_MAX_KTILES k-tiles per k-slab); 0: it runs every k-tile, like ia_gemm_bf16 (the same conditions as gemm_core's)
+extern "C" int ia_gemm_wgrad_rows_filters(int N_out, int N_in, int M_rows) {
+  if (N_out <= 0 || N_in <= 0 || M_rows <= 0) return 0;
+  const Plan pl = make_plan(N_out, N_in, M_rows, true);
+  const int nk = (M_rows + BK - 1) / BK;
+  return pl.big && (nk + pl.splits - 1) / pl.splits <= t256w::LIVE_MAX_KTILES ? 1 : 0;
+}
+extern "C" int ia_gemm_wgrad_rows(const void* dY, int ldy, const void* X, int ldx, float* dW, int ldw, int N_out, int N_in, int M_rows,
+                                  const uint8_t* row_live, int accumulate, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  if (!row_live)
+    return gemm_core(dY, 1, ldy, X, 1, ldx, dW, 1, ldw, N_out, N_in, M_rows, EPI_NONE, nullptr, nullptr, 0, nullptr, accumulate, workspace,
+                     workspace_bytes, nullptr, stream);
+  if (N_out <= 0 || N_in <= 0 || M_rows <= 0) return IA_ERR_ARG;
+  // the split-K partials in front, the mask behind them
+  const size_t split_bytes = al256(ia_gemm_workspace_bytes(N_out, N_in, M_rows, 1));
+  if (!workspace || workspace_bytes < split_bytes + ia_ktile_mask_bytes(M_rows) || ((uintptr_t)workspace & 15)) return IA_ERR_WORKSPACE;
+  uint32_t* mask = reinterpret_cast<uint32_t*>((char*)workspace + split_bytes);
+  int rc = ia_ktile_mask(row_live, M_rows, mask, stream);
+  return rc ? rc : ia_gemm_wgrad_masked(dY, ldy, X, ldx, dW, ldw, N_out, N_in, M_rows, mask, accumulate, workspace, split_bytes, stream);
 }
 
 // GEMM with shifted operand views and channel groups batched into one launch (see GemmArgs): the building block of the
@@ -1739,7 +1892,7 @@ static int launch_dgelu_colsum(GemmArgs& g, bool big, float* csum, void* workspa
 
 static int gemm_core(const void* A, int a_kstrided, int lda, const void* B, int b_kstrided, int ldb, void* C, int c_is_f32, int ldc, int M,
                      int N, int K, int epilogue, const float* bias, const void* aux, int ldaux, void* C2, int accumulate, void* workspace,
-                     size_t workspace_bytes, const IaViewGemm* view, hipStream_t stream, int qcols, float qscale) {
+                     size_t workspace_bytes, const IaViewGemm* view, hipStream_t stream, int qcols, float qscale, const uint32_t* live_kt) {
   const uint64_t a_window = view ? view->a_window : 0, b_window = view ? view->b_window : 0;
   const int groups = view ? view->groups : 1;
   (void)hipGetLastError();  // drop stale status left by unrelated runtime calls (e.g. hipEventQuery -> NotReady)
@@ -1788,6 +1941,12 @@ static int gemm_core(const void* A, int a_kstrided, int lda, const void* B, int 
     const uint64_t wb = (b_kstrided ? slab : tile) * (uint64_t)ldb * 2 + (b_kstrided ? 0 : (uint64_t)K * 2);
     if (wa >= 0x7FFFFFF0ull || wb >= 0x7FFFFFF0ull) return IA_ERR_ARG;
   }
+  // the live-k-tile mask: the 256-wide weight-gradient kernel only, one mask word per lane and k-slab (anything else runs dense)
+  // GemmArgs::live_kt shares the slot of GemmArgs::bias (filled above from the caller's argument): in the weight-gradient form, whose
+  // 256-wide kernel reads the slot as the mask, it is overwritten HERE for every caller -- a stray bias passed with IA_EPI_NONE, the
+  // shifted views of ia_gemm_view -- so the kernel sees a mask or NULL, never a bias.  launch<true, true, EPI_NONE, true> is reached
+  // from this function only; a new call site that fills GemmArgs for this form must do the same.
+  if (a_kstrided && b_kstrided && c_is_f32 && epilogue == EPI_NONE) g.live_kt = (big && g.nk_per_split <= t256w::LIVE_MAX_KTILES) ? live_kt : nullptr;
   const bool needs_bias = epilogue == EPI_BIAS || epilogue == EPI_BIAS_GELU || epilogue == EPI_BIAS_GELU_ACT || epilogue == EPI_BIAS_ADD;
   const bool needs_aux = epilogue == EPI_ADD || epilogue == EPI_DGELU || epilogue == EPI_BIAS_ADD || epilogue == EPI_DGELU_CS;
   if (needs_bias && !bias) return IA_ERR_ARG;

@@ -60,6 +60,34 @@ def gemm(a, b, *, a_kstrided=False, b_kstrided=False, epilogue=EPI_NONE, bias=No
     return out
 
 
+def ktile_mask(row_live):
+    """bit (t & 31) of word t >> 5 = any(row_live[64t : 64t + 64]) (uint8 [M] on the GPU) -> int32 words"""
+    lib = _lib.load()
+    _need(row_live, torch.uint8, "row_live")
+    M = row_live.numel()
+    out = torch.empty(lib.ia_ktile_mask_bytes(M) // 4, device=row_live.device, dtype=torch.int32)
+    check(lib.ia_ktile_mask(row_live.data_ptr(), M, out.data_ptr(), stream_ptr()), "ia_ktile_mask")
+    return out
+
+
+def gemm_wgrad_rows(dy, x, row_live=None, *, out=None, accumulate=False):
+    """dW[N_out, N_in] (+)= dy[M, N_out]^T x[M, N_in] in fp32; row_live (uint8 [M]) == 0 promises that row of dy is all zeros, and
+    64-row blocks without a live row are skipped (ia_gemm_wgrad_rows).  row_live=None is gemm(..., a_kstrided, b_kstrided, out_f32)."""
+    lib = _lib.load()
+    _need(dy, BF16, "dy"); _need(x, BF16, "x"); _need(row_live, torch.uint8, "row_live")
+    (M, n_out), (Mx, n_in) = dy.shape, x.shape
+    if M != Mx or (row_live is not None and row_live.numel() != M):
+        raise ValueError("gemm_wgrad_rows: dy, x and row_live must have the same number of rows")
+    if out is None:
+        out = torch.empty((n_out, n_in), device=dy.device, dtype=F32)
+    _need(out, F32, "out")
+    ws_bytes = lib.ia_gemm_wgrad_rows_workspace_bytes(n_out, n_in, M)
+    ws = torch.empty(ws_bytes, device=dy.device, dtype=torch.uint8)
+    check(lib.ia_gemm_wgrad_rows(dy.data_ptr(), n_out, x.data_ptr(), n_in, out.data_ptr(), n_in, n_out, n_in, M, ptr(row_live),
+                                 int(accumulate), ws.data_ptr(), ws_bytes, stream_ptr()), "ia_gemm_wgrad_rows")
+    return out
+
+
 def ln_fwd(x, gamma, beta, eps, *, bias=None, residual=None, write_z=True, drop_p=0.0, seed=0, stream_id=0):
     lib = _lib.load()
     _need(x, BF16, "x"); _need(gamma, F32, "gamma"); _need(beta, F32, "beta"); _need(bias, F32, "bias"); _need(residual, BF16, "residual")
