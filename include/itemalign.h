@@ -37,7 +37,7 @@ const char* ia_strerror(int code);
 /* Bumped whenever an entry point is added or the meaning of an argument / output changes (round 2 changed what IA_EPI_BIAS_GELU
  * stores in C2 and what IA_EPI_DGELU expects in aux): a caller built against another header must not run on this library.
  * item_alignment_amd/_lib.py refuses to load a library whose version differs from the one it was written for. */
-#define IA_ABI_VERSION 16
+#define IA_ABI_VERSION 17
 int ia_abi_version(void);
 
 /* ---- GEMM: torch.nn.Linear forward / dgrad / wgrad (src/models/text.py:1241 -> RobertaLayer dense
@@ -181,6 +181,16 @@ int ia_attn_fwd_x(const void* q, int ld_q, const void* k, const void* v, int ld_
 int ia_attn_bwd_x(const void* q, int ld_q, const void* k, const void* v, int ld_kv, const uint8_t* key_mask, const void* out,
                   const void* d_out, int ld_o, const float* lse2, float* delta, void* dq, int ld_dq, void* dk, void* dv, int ld_dkv,
                   int B, int nh, int Lq, int Lk, float scale, float drop_p, uint32_t seed, ia_stream_t stream);
+/* (ABI 17) Causal form, the decoder layers of CoCa pre-training (src/models/multimodal.py:529-626 with is_decoding=True): Lq = fold * Lk
+ * queries per (sequence, head), query row i attends key j iff j <= i / fold (integer division).  fold = 1 is causal self-attention;
+ * the decoder block is nh = 1, fold = heads with the query heads folded into rows.  No key mask and no dropout.  Layouts, lse2
+ * [B, nh, Lq] and the delta scratch as for the x form; Lk <= 2048; every pointer 16-byte aligned, every stride a multiple of 8.  The
+ * backward adds dk / dv up in a fixed order (no floating-point atomics): two calls on the same inputs give the same bits. */
+int ia_attn_fwd_causal_x(const void* q, int ld_q, const void* k, const void* v, int ld_kv, void* out, int ld_o, float* lse2, int B, int nh,
+                         int Lk, int fold, float scale, ia_stream_t stream);
+int ia_attn_bwd_causal_x(const void* q, int ld_q, const void* k, const void* v, int ld_kv, const void* out, const void* d_out, int ld_o,
+                         const float* lse2, float* delta, void* dq, int ld_dq, void* dk, void* dv, int ld_dkv, int B, int nh, int Lk,
+                         int fold, float scale, ia_stream_t stream);
 
 /* ---- CoCa multimodal-layer element-wise ops (src/models/multimodal.py:495-524).
  * rotary_split: src rows [M, ld_src] hold q (nh heads x 64) | k (64) | v (64) from column 0 (the head of the fused

@@ -65,6 +65,8 @@ SIGNATURES = {
     "ia_gemm_bf16_qscale": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, vp, i32, f32, vp]),
     "ia_attn_fwd_x": (i32, [vp, i32, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, f32, f32, u32, vp]),
     "ia_attn_bwd_x": (i32, [vp, i32, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, f32, f32, u32, vp]),
+    "ia_attn_fwd_causal_x": (i32, [vp, i32, vp, vp, i32, vp, i32, vp, i32, i32, i32, i32, f32, vp]),
+    "ia_attn_bwd_causal_x": (i32, [vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, f32, vp]),
     "ia_rotary_split_fwd": (i32, [vp, i32, vp, vp, i32, i32, i32, vp]),
     "ia_rotary_split_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, vp]),
     "ia_swiglu_fwd": (i32, [vp, i32, vp, i32, i32, vp]),
@@ -190,7 +192,7 @@ SIGNATURES = {
 _lib = None
 
 
-ABI_VERSION = 16      # = IA_ABI_VERSION of include/itemalign.h (tests/test_cabi_symbols.py keeps the two in step)
+ABI_VERSION = 17      # = IA_ABI_VERSION of include/itemalign.h (tests/test_cabi_symbols.py keeps the two in step)
 
 
 class ItemAlignError(RuntimeError):

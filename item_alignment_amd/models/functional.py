@@ -640,6 +640,39 @@ class AttentionXFn(torch.autograd.Function):
         return dq, dkv, None, None, None, None, None
 
 
+class AttentionCausalXFn(torch.autograd.Function):
+    """Causal form of AttentionXFn (ia_attn_fwd_causal_x / ia_attn_bwd_causal_x): Lq = fold * Lk queries per sequence, query row i
+    attends key j iff j <= i // fold.  q: [B*fold*Lk, nh*64]; kv: [B*Lk, 2*nh*64] = k | v.  The decoder block passes nh = 1 and
+    fold = heads with the query heads folded into rows (row r belongs to token r // heads)."""
+
+    @staticmethod
+    def forward(ctx, q, kv, B, nh, Lk, fold, scale):
+        lib = _lib.load()
+        q, kv = q.contiguous(), kv.contiguous()
+        H, Lq = nh * 64, fold * Lk
+        out = torch.empty((B * Lq, H), device=q.device, dtype=BF16)
+        lse = torch.empty((B, nh, Lq), device=q.device, dtype=F32)
+        check(lib.ia_attn_fwd_causal_x(q.data_ptr(), H, kv.data_ptr(), kv.data_ptr() + 2 * H, 2 * H, out.data_ptr(), H, lse.data_ptr(), B, nh,
+                                       Lk, fold, scale, stream_ptr()), "ia_attn_fwd_causal_x")
+        ctx.saved, ctx.dims = (q, kv, out, lse), (B, nh, Lk, fold, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = _lib.load()
+        q, kv, out, lse = ctx.saved
+        B, nh, Lk, fold, scale = ctx.dims
+        H = nh * 64
+        dout = dout.contiguous()
+        dq, dkv = torch.empty_like(q), torch.empty_like(kv)
+        delta = torch.empty((B, nh, fold * Lk), device=q.device, dtype=F32)
+        check(lib.ia_attn_bwd_causal_x(q.data_ptr(), H, kv.data_ptr(), kv.data_ptr() + 2 * H, 2 * H, out.data_ptr(), dout.data_ptr(), H,
+                                       lse.data_ptr(), delta.data_ptr(), dq.data_ptr(), H, dkv.data_ptr(), dkv.data_ptr() + 2 * H, 2 * H, B, nh,
+                                       Lk, fold, scale, stream_ptr()), "ia_attn_bwd_causal_x")
+        ctx.saved = None
+        return dq, dkv, None, None, None, None, None
+
+
 # -------------------------------------------------------------------------------- PKGM rows, similarity head
 class KGGatherFn(torch.autograd.Function):
     """sign(ent_emb[e]) [B, Dk] and rel_emb[r_1..P] [B*P, Dk] for one item side (reference base.py:347-367)."""

@@ -139,14 +139,16 @@ def _check_head_dim(dim_head):
 
 
 class ParallelTransformerBlock(nn.Module):
-    """reference multimodal.py:529-626 (is_decoding False, no attention mask — CoCaForItemAlignment passes none, :1007):
-    LN -> one fused projection -> multi-query attention with rotary q/k  ||  SwiGLU feed-forward -> attn_out + ff_out."""
+    """reference multimodal.py:529-626 (no `attn_mask` argument -- nothing in the reference passes one):
+    LN -> one fused projection -> multi-query attention with rotary q/k  ||  SwiGLU feed-forward -> attn_out + ff_out.
+    is_decoding=True (the decoder layers of CoCa pre-training) puts the reference's triu mask on the attention: token i attends
+    tokens j <= i.  The reference's `mask` and `pos_emb` buffers are non-persistent caches, so there is nothing to keep here:
+    state-dict keys are the same either way."""
 
     def __init__(self, dim, dim_head=64, heads=8, ff_mult=4, is_decoding=False):
         super().__init__()
         _check_head_dim(dim_head)
-        if is_decoding:
-            raise NotImplementedError("causal decoding blocks are not on the item-alignment path")
+        self.is_decoding = bool(is_decoding)
         self.norm = LayerNorm(dim)
         attn_inner_dim, ff_inner_dim = dim_head * heads, dim * ff_mult
         self.fused_dims = (attn_inner_dim, dim_head, dim_head, ff_inner_dim * 2)
@@ -162,7 +164,10 @@ class ParallelTransformerBlock(nn.Module):
         fused = Fn.LinearBf16Fn.apply(xn, None, self.fused_attn_ff_proj.weight, self)
         q, kv, s = Fn.FusedSplitFn.apply(fused, n, h, self.ff_inner_dim)
         # multi-query attention: every query head attends to the single k/v head -> fold the heads into query rows
-        o = Fn.AttentionXFn.apply(q.view(B * n * h, 64), kv, B, 1, n * h, n, self.scale)
+        if self.is_decoding:      # folded row r is head r % h of token r // h: it attends keys j <= r // h
+            o = Fn.AttentionCausalXFn.apply(q.view(B * n * h, 64), kv, B, 1, n, h, self.scale)
+        else:
+            o = Fn.AttentionXFn.apply(q.view(B * n * h, 64), kv, B, 1, n * h, n, self.scale)
         y = Fn.LinearBf16Fn.apply(o.view(B * n, h * 64), residual, self.attn_out.weight, self)
         # (s is not kept for ff_out's weight gradient: backward recomputes it from the x | gate columns of `fused`, which FusedSplitFn holds)
         return Fn.LinearBf16Fn.apply(s, y, self.ff_out[1].weight, self, (fused, h * 64 + 128, self.ff_inner_dim))
