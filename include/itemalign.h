@@ -37,7 +37,7 @@ const char* ia_strerror(int code);
 /* Bumped whenever an entry point is added or the meaning of an argument / output changes (round 2 changed what IA_EPI_BIAS_GELU
  * stores in C2 and what IA_EPI_DGELU expects in aux): a caller built against another header must not run on this library.
  * item_alignment_amd/_lib.py refuses to load a library whose version differs from the one it was written for. */
-#define IA_ABI_VERSION 17
+#define IA_ABI_VERSION 18
 int ia_abi_version(void);
 
 /* ---- GEMM: torch.nn.Linear forward / dgrad / wgrad (src/models/text.py:1241 -> RobertaLayer dense
@@ -88,6 +88,34 @@ int ia_gemm_wgrad_rows(const void* dY, int ldy, const void* X, int ldx, float* d
 size_t ia_ktile_mask_bytes(int M_rows);
 int ia_ktile_mask(const uint8_t* row_live, int M_rows, uint32_t* mask, ia_stream_t stream);
 int ia_ktile_mask_host(const uint8_t* row_live, int M_rows, uint32_t* mask);
+/* (ABI 18) The data gradient of a Linear over padded token rows: dX[M_rows, N_in] = dY[M_rows, K_out] W (+ epilogue), bf16 -- ia_gemm_bf16's
+ * data-gradient form (A = dY k-contiguous; B = W [K_out, N_in] k-strided, w_kstrided = 1, or its transposed shadow [N_in, K_out],
+ * w_kstrided = 0; epilogue IA_EPI_NONE, IA_EPI_ADD or IA_EPI_DGELU_COLSUM with aux / C2 as there) -- and a row filter.  row_live [M_rows]
+ * uint8 or NULL.  Contract: row_live[m] == 0 = the caller guarantees that row m of dY is all zeros and, for IA_EPI_ADD, that row m of aux
+ * is all zeros (ia_layer_cfg::masked_rows_dead).  The rows are taken in blocks of 32: a block without a live row is neither fetched nor
+ * multiplied, its rows of dX are WRITTEN AS ZEROS (+0; the unfiltered call may give -0 where 0 * gelu' < 0) and they add nothing to the
+ * column sums of IA_EPI_DGELU_COLSUM.  Every other element of dX is bit-identical to ia_gemm_bf16's; the column sums add the same fp32
+ * terms in another grouping (the per-tile partials cover other rows), so C2 agrees up to fp32 summation order.  NULL = the ia_gemm_bf16
+ * call.  With row_live the workspace (32-byte aligned, ia_gemm_dgrad_rows_workspace_bytes: column-sum partials + the block list) is
+ * required.  ia_gemm_dgrad_rows_filters: 1 when a call of this shape with contiguous rows (ldy = K_out, ldx = ldaux = N_in) honours
+ * row_live (outputs of at least 160 tiles of 256 x 256, every operand below 2 GiB), 0 when it runs every row as ia_gemm_bf16 does (the
+ * result is the same either way). */
+size_t ia_gemm_dgrad_rows_workspace_bytes(int M_rows, int N_in, int K_out);
+int ia_gemm_dgrad_rows_filters(int M_rows, int N_in, int K_out);
+int ia_gemm_dgrad_rows(const void* dY, int ldy, const void* W, int w_kstrided, int ldw, void* dX, int ldx, int M_rows, int N_in, int K_out,
+                       int epilogue, const void* aux, int ldaux, void* C2, const uint8_t* row_live, void* workspace, size_t workspace_bytes,
+                       ia_stream_t stream);
+/* the block list itself (int32, ia_row_blocks_bytes(M_rows) bytes, 32-byte aligned), nb = ceil(M_rows / 32), nbr = nb rounded up to 8:
+ * list[0] = number of live blocks, list[1] = number of dead blocks, list[2] = nb, list[3..7] = 0; list[8 ..] = the ascending indices of the
+ * blocks (rows 32t .. 32t+31, clipped to M_rows) that hold a live row; list[8 + nbr ..] = the ascending indices of the others.  Entries
+ * behind either count are unspecified.  ia_row_blocks writes it on the device (one launch, no host synchronisation); ia_row_blocks_host
+ * is a diagnostic hook: the same list from host memory through the per-block function the device kernel calls. */
+size_t ia_row_blocks_bytes(int M_rows);
+int ia_row_blocks(const uint8_t* row_live, int M_rows, int* list, ia_stream_t stream);
+int ia_row_blocks_host(const uint8_t* row_live, int M_rows, int* list);
+/* Diagnostics (tests, A/B runs): on == 0 makes ia_layer_bwd2 run its data gradients over every row although
+ * ia_layer_cfg::masked_rows_dead is set (the block list is withheld; every other row filter stays); returns the previous setting. */
+int ia_debug_dgrad_rows(int on);
 
 /* per-launch HIP-event timing of one GEMM instantiation (variant = a_kstrided*1000 + b_kstrided*100 + epilogue*10 + c_is_f32),
  * recorded on the launch stream; used by bench.py for the roofline of the dominant kernel. */

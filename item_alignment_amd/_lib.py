@@ -43,6 +43,13 @@ SIGNATURES = {
     "ia_ktile_mask_bytes": (sz, [i32]),
     "ia_ktile_mask": (i32, [vp, i32, vp, vp]),
     "ia_ktile_mask_host": (i32, [vp, i32, vp]),
+    "ia_gemm_dgrad_rows_workspace_bytes": (sz, [i32, i32, i32]),
+    "ia_gemm_dgrad_rows_filters": (i32, [i32, i32, i32]),
+    "ia_gemm_dgrad_rows": (i32, [vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, sz, vp]),
+    "ia_row_blocks_bytes": (sz, [i32]),
+    "ia_row_blocks": (i32, [vp, i32, vp, vp]),
+    "ia_row_blocks_host": (i32, [vp, i32, vp]),
+    "ia_debug_dgrad_rows": (i32, [i32]),
     "ia_prof_begin": (i32, [i32, i32]),
     "ia_prof_end": (i32, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i32)]),
     "ia_prof_bytes": (C.c_double, []),
@@ -192,7 +199,7 @@ SIGNATURES = {
 _lib = None
 
 
-ABI_VERSION = 17      # = IA_ABI_VERSION of include/itemalign.h (tests/test_cabi_symbols.py keeps the two in step)
+ABI_VERSION = 18      # = IA_ABI_VERSION of include/itemalign.h (tests/test_cabi_symbols.py keeps the two in step)
 
 
 class ItemAlignError(RuntimeError):

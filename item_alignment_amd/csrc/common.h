@@ -203,3 +203,12 @@ __attribute__((visibility("hidden"))) int ia_gemm_wgrad_masked(const void* dY, i
                                                                int N_in, int M_rows, const uint32_t* ktile_mask, int accumulate,
                                                                void* workspace, size_t workspace_bytes, hipStream_t stream);
 
+// dX[M_rows, N_in] = dY[M_rows, K_out] W (+ epilogue: IA_EPI_NONE, IA_EPI_ADD or IA_EPI_DGELU_COLSUM) over the 32-row blocks of the live
+// list of row_blocks (ia_row_blocks), dead blocks written as zeros: the data-gradient form of ia_gemm_bf16 for a caller that has the list
+// of its rows already (ia_layer_bwd2: one list, four data gradients).  row_blocks == NULL or a shape the remapped kernel does not serve:
+// every row, as ia_gemm_bf16.
+__attribute__((visibility("hidden"))) int ia_gemm_dgrad_blocks(const void* dY, int ldy, const void* W, int w_kstrided, int ldw, void* dX, int ldx,
+                                                               int M_rows, int N_in, int K_out, int epilogue, const void* aux, int ldaux, void* C2,
+                                                               const int* row_blocks, void* workspace, size_t workspace_bytes,
+                                                               hipStream_t stream);
+

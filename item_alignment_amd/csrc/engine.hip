@@ -72,7 +72,7 @@ FwdBufs carve_infer(const ia_layer_cfg* c, void* base) {
 }
 
 struct Scratch {
-  char* g0; char* g1; char* g2; char* gI; char* gqkv; float* delta; char* ws; size_t ws_bytes; char* gws; size_t gws_bytes; uint32_t* live_kt; size_t bytes;
+  char* g0; char* g1; char* g2; char* gI; char* gqkv; float* delta; char* ws; size_t ws_bytes; char* gws; size_t gws_bytes; uint32_t* live_kt; int* row_blk; size_t bytes;
 };
 
 size_t max3(size_t a, size_t b, size_t c) { return a > b ? (a > c ? a : c) : (b > c ? b : c); }
@@ -93,6 +93,8 @@ Scratch carve_scratch(const ia_layer_cfg* c, void* base) {
   s.gws = a.take(s.gws_bytes);
   // masked_rows_dead: which 64-row k-tiles of the weight gradients hold a live row (one bit each)
   s.live_kt = (uint32_t*)a.take(ia_ktile_mask_bytes((int)M));
+  // ... and which 32-row blocks of the data gradients do (the live list and the dead list, ia_row_blocks)
+  s.row_blk = (int*)a.take(ia_row_blocks_bytes((int)M));
   s.bytes = a.bytes;
   return s;
 }
@@ -102,12 +104,19 @@ bool cfg_ok(const ia_layer_cfg* c) {
   return c && c->B > 0 && c->L > 0 && c->H > 0 && c->I > 0 && c->nh > 0 && c->H == c->nh * 64 && (c->H & 7) == 0 && (c->I & 7) == 0;
 }
 
+// Diagnostics: 0 withholds the block list from the data gradients of ia_layer_bwd2 (they run every row); returns the previous setting.
+int g_dgrad_rows = 1;
+
 #define IA_TRY(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
 
 // Data gradient dx[M, n_in] = dy[M, k_out] W[k_out, n_in] (+ epilogue): through the transposed shadow wt[n_in, k_out] when the caller
 // provides one (both operands k-contiguous: the faster form, ia_layer_weights::wt_*), else W read k-strided.
+// With a block list (ia_row_blocks), over the 32-row blocks that hold a live row only; the other rows of dx are written as zeros.
 int dgrad(const void* dy, int k_out, const void* w, const void* wt, int n_in, void* dx, int M, int epilogue, const void* aux, int ldaux, void* c2,
-          void* ws, size_t ws_bytes, ia_stream_t st) {
+          void* ws, size_t ws_bytes, ia_stream_t st, const int* row_blk = nullptr) {
+  if (row_blk)
+    return ia_gemm_dgrad_blocks(dy, k_out, wt ? wt : w, wt ? 0 : 1, wt ? k_out : n_in, dx, n_in, M, n_in, k_out, epilogue, aux, ldaux, c2, row_blk,
+                                ws, ws_bytes, st);
   if (wt)
     return ia_gemm_bf16(dy, 0, k_out, wt, 0, k_out, dx, 0, n_in, M, n_in, k_out, epilogue, nullptr, aux, ldaux, c2, 0, ws, ws_bytes, st);
   return ia_gemm_bf16(dy, 0, k_out, w, 1, n_in, dx, 0, n_in, M, n_in, k_out, epilogue, nullptr, aux, ldaux, c2, 0, ws, ws_bytes, st);
@@ -198,6 +207,12 @@ int layer_forward(const ia_layer_cfg* c, const ia_layer_weights* w, const void* 
 
 }  // namespace
 
+extern "C" int ia_debug_dgrad_rows(int on) {
+  const int was = g_dgrad_rows;
+  g_dgrad_rows = on ? 1 : 0;
+  return was;
+}
+
 extern "C" size_t ia_layer_stash_bytes(const ia_layer_cfg* cfg) {
   (void)hipGetLastError();  // drop stale status left by unrelated runtime calls (e.g. hipEventQuery -> NotReady)
   if (!cfg_ok(cfg)) return 0;
@@ -259,10 +274,14 @@ extern "C" int ia_layer_bwd2(const ia_layer_cfg* c, const ia_layer_weights* w, c
   const bool drop = c->hidden_drop > 0.f;
   if (!c->pre_ln) {
     // masked_rows_dead: every gradient row of a masked position is exactly zero (ia_layer_cfg): the LayerNorm backward kernels skip them,
-    // and the four weight gradients skip the 64-row k-tiles that hold nothing else (one bitmask per call, in scratch)
+    // the four weight gradients skip the 64-row k-tiles that hold nothing else (one bitmask per call, in scratch), and the three plain data
+    // gradients (fc1, out-projection, QKV) the 32-row blocks (one block list per call; their dead rows are written as zeros: the attention backward, the pair
+    // kernels and the embedding backward read every row)
     const uint8_t* const live = (c->masked_rows_dead && !c->cu_seqlens) ? key_mask : nullptr;
     const uint32_t* const live_kt = live ? k.live_kt : nullptr;
+    const int* const row_blk = (live && g_dgrad_rows) ? k.row_blk : nullptr;
     if (live) IA_TRY(ia_ktile_mask(live, M, k.live_kt, st));
+    if (row_blk) IA_TRY(ia_row_blocks(live, M, k.row_blk, st));
     // The two residual additions of a post-LN layer make each LayerNorm output's gradient a sum of two terms; both LayerNorm
     // backward kernels take the two terms (ia_ln_bwd2), so the GEMMs in front of them keep the plain epilogue.
     // LN2 backward: d(output) = dy (+ dy2) -> dz2 in g0, masked branch gradient -> g1 (or g0 when p == 0)
@@ -271,9 +290,11 @@ extern "C" int ia_layer_bwd2(const ia_layer_cfg* c, const ia_layer_weights* w, c
     const char* d_ffn = drop ? k.g1 : k.g0;
     IA_TRY(wgrad(d_ffn, H, s.hact, I, (float*)g->w_fc2, M, live_kt, k.gws, k.gws_bytes, st));
     // d(pre-activation) = (d_ffn W2) * gelu'(pre), and its column sums (the fc1 bias gradient) out of the same epilogue
+    // (every row, although the remapped kernel serves this epilogue: its column-sum partials would cover other rows, and the fc1 bias
+    // gradient would equal the unfiltered one only up to fp32 summation order -- the backward stays bit-identical to masked_rows_dead = 0)
     IA_TRY(dgrad(d_ffn, H, w->w_fc2, w->wt_fc2, I, k.gI, M, IA_EPI_DGELU_COLSUM, s.hpre, I, g->b_fc1, k.ws, k.ws_bytes, st));
     IA_TRY(wgrad(k.gI, I, s.ln, H, (float*)g->w_fc1, M, live_kt, k.gws, k.gws_bytes, st));
-    IA_TRY(dgrad(k.gI, I, w->w_fc1, w->wt_fc1, H, k.g2, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st));
+    IA_TRY(dgrad(k.gI, I, w->w_fc1, w->wt_fc1, H, k.g2, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, row_blk));
     // LN1 backward: d(y1) = g2 (through fc1) + g0 (residual into LN2) -> dz1 (the layer input's residual-path gradient) in
     // dz1buf: the caller's dx2 when the split form is wanted, else g0 (in place over the term just consumed)
     char* dz1buf = dx2 ? (char*)dx2 : k.g0;
@@ -281,13 +302,13 @@ extern "C" int ia_layer_bwd2(const ia_layer_cfg* c, const ia_layer_weights* w, c
                            c->hidden_drop, c->seed, c->layer_id * 4u + 0u, live, k.ws, k.ws_bytes, 1, st));
     const char* d_att = drop ? k.g1 : dz1buf;
     IA_TRY(wgrad(d_att, H, s.ctx, H, (float*)g->w_o, M, live_kt, k.gws, k.gws_bytes, st));
-    IA_TRY(dgrad(d_att, H, w->w_o, w->wt_o, H, k.g2, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st));
+    IA_TRY(dgrad(d_att, H, w->w_o, w->wt_o, H, k.g2, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, row_blk));
     IA_TRY(attn_bwd(c, s.qkv, key_mask, s.ctx, k.g2, s.lse, k.delta, k.gqkv, g->b_qkv, k.ws, k.ws_bytes, scale, c->attn_drop, attn_seed, st));
     IA_TRY(wgrad(k.gqkv, 3 * H, x, H, (float*)g->w_qkv, M, live_kt, k.gws, k.gws_bytes, st));
     if (dx2)   // split form: dx = the attention sub-block's data gradient, dx2 = dz1 (already written)
-      IA_TRY(dgrad(k.gqkv, 3 * H, w->w_qkv, w->wt_qkv, H, dx, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st));
+      IA_TRY(dgrad(k.gqkv, 3 * H, w->w_qkv, w->wt_qkv, H, dx, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, row_blk));
     else
-      IA_TRY(dgrad(k.gqkv, 3 * H, w->w_qkv, w->wt_qkv, H, dx, M, IA_EPI_ADD, dz1buf, H, nullptr, nullptr, 0, st));
+      IA_TRY(dgrad(k.gqkv, 3 * H, w->w_qkv, w->wt_qkv, H, dx, M, IA_EPI_ADD, dz1buf, H, nullptr, nullptr, 0, st, row_blk));
   } else {
     if (!c->dy_colsum_done) IA_TRY(ia_colsum(dy, H, M, H, g->b_fc2, 1, k.ws, k.ws_bytes, st));
     IA_TRY(ia_gemm_bf16(dy, 1, H, s.hact, 1, I, g->w_fc2, 1, I, H, I, M, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 1, k.gws, k.gws_bytes, st));

@@ -44,6 +44,11 @@ enum { EPI_NONE = 0, EPI_BIAS = 1, EPI_BIAS_GELU = 2, EPI_ADD = 3, EPI_DGELU = 4
 // the token rows as k: a k-tile whose rows of dY are all zeros adds +-0 to every accumulator, so leaving it out changes no bit of the
 // fp32 sums -- the k-slabs of a split-K launch and the order of the reduction stay what they are, a slab just takes fewer trips.
 constexpr int EPI_NONE_LIVE = 8;
+// EPI_ROWS + e (library-internal, t256w only; e = EPI_NONE, EPI_ADD or EPI_DGELU_CS, k-contiguous A, bf16 output): epilogue e behind a row
+// remap.  The data gradient dX = dY W has the token rows as M: a row of dY that is all zeros gives a row of zeros, so only the 32-row
+// blocks that hold a live row are computed -- an M-tile is eight consecutive entries of the live-block list (GemmArgs::row_blk) instead
+// of 256 consecutive rows -- and the dead blocks are written as zeros by a fill launch.  No live row's arithmetic changes.
+constexpr int EPI_ROWS = 16;
 // EPI_BIAS_GELU_ACT: the forward-only form of EPI_BIAS_GELU (activation only: no derivative is evaluated or stored)
 
 struct GemmArgs {
@@ -54,6 +59,8 @@ struct GemmArgs {
     // argument block moves): bit t of this bitmask set = k-tile t (k rows 64t .. 64t+63) has at least one row of A that is not known
     // to be all zeros; a workgroup walks only the set bits of its k-slab (t256w::gemm_kernel<true, true, EPI_NONE_LIVE, true>).  NULL = every k-tile.
     const uint32_t* live_kt;
+    // Row-remapped data-gradient form of the 256-wide kernel only (EPI_ROWS + e: no bias either): the block list ia_row_blocks wrote.
+    const int* row_blk;
   };
   const bf16* aux;
   int M, N, K;
@@ -697,6 +704,26 @@ IA_DEV void mfma_step(f32x16 (&acc)[4][4], const FA& fa, const FB& fb, Filler&& 
     }
 }
 
+// EPI_ROWS: the eight 32-row blocks of remapped M-tile bm (-1: the list has no such entry -- the tail of the last tile).  One scalar
+// load, waited for on the spot (lgkmcnt(0) is the strictest form of every LDS wait around it); the address is uniform and 32-byte
+// aligned (eight header words in front of the list, eight entries per tile).
+struct Blk8 { int b[8]; };
+struct RowOff { uint32_t o[8]; };      // byte offset of each A piece's first row (the scalar offset of its DMA)
+struct RowBlk { int r[4]; };           // first row of each of the wave's four 32-row blocks, -1 = none
+constexpr int ROW_BLK_HDR = 8;         // list header: [0] live blocks, [1] dead blocks, [2] blocks; the live list follows
+IA_DEV Blk8 load_blk8(const int* list, int bm, int n_live) {
+  typedef int i32x8 __attribute__((ext_vector_type(8)));
+  const uint64_t a64 = (uint64_t)(list + ROW_BLK_HDR + bm * 8);
+  const uint32_t alo = __builtin_amdgcn_readfirstlane((uint32_t)a64), ahi = __builtin_amdgcn_readfirstlane((uint32_t)(a64 >> 32));
+  const uint64_t addr = ((uint64_t)ahi << 32) | alo;
+  i32x8 v;
+  asm volatile("s_nop 4\n\ts_load_dwordx8 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(v) : "s"(addr) : "memory");
+  Blk8 r;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) r.b[j] = bm * 8 + j < n_live ? v[j] : -1;
+  return r;
+}
+
 // Walk over the set bits of a k-slab's live-k-tile mask in increasing order.  Lane l of `mv` holds bits 32l .. 32l+31 of the slab (every
 // wave holds the same 64 words, fetched once in front of the first prologue DMA); the walk itself is SALU plus one v_readlane per step --
 // no memory operation, so it can sit next to the k loop's counted waits, and no branch.  Once the bits are used up next() keeps
@@ -721,10 +748,12 @@ IA_DEV int live_next(LiveWalk& k, uint32_t mv) {
 
 // LIVE (both operands k-strided): the k loop runs over the n_tiles set bits of live_mv (the slab's live k-tiles, see LiveWalk) instead of
 // k-tiles 0 .. n_tiles-1 of the slab.
-template <bool AKS, bool BKS, int PEND, bool PEEL_OK = true, bool LIVE = false>
+// ROWS (k-contiguous A): piece j of A starts at row offset ro.o[j] (a scalar, where j * stepA sits otherwise) of a window over all of A.
+template <bool AKS, bool BKS, int PEND, bool PEEL_OK = true, bool LIVE = false, bool ROWS = false>
 IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdgpu_buffer_rsrc_t rsA, __amdgpu_buffer_rsrc_t rsB, int xa, int xb,
                       int kt0, int ktaA0, int ktaB0, int n_tiles, int nk_all, int wm, int wn, int wave, int lane, bool prologue_only,
-                      bool stores_in_flight, uint32_t live_mv = 0u) {
+                      bool stores_in_flight, uint32_t live_mv = 0u, RowOff ro = RowOff{}) {
+  static_assert(!ROWS || !AKS, "the row remap moves the pieces of a k-contiguous A");
   static_assert(!LIVE || (AKS && BKS), "the live-k-tile walk advances the running lane offsets of two k-strided operands");
   constexpr bool ROUND = !AKS && !BKS;      // the k loop's schedule (below)
   const int li = lane & 31;
@@ -759,7 +788,7 @@ IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdg
     const int kt = kt0 + u;
     const int kta = (dbg & 4) ? 0 : (isB ? ktaB0 : ktaA0) + (LIVE ? (u == 0 ? live0 : live1) : u);      // dbg 4: every k-tile re-fetches k-tile 0 (cache-resident)
     const bool ks = isB ? BKS : AKS;
-    const uint32_t soff = (uint32_t)kta * (isB ? kstepB : kstepA) + (uint32_t)j * (isB ? stepB : stepA);
+    const uint32_t soff = (uint32_t)kta * (isB ? kstepB : kstepA) + ((ROWS && !isB) ? ro.o[j] : (uint32_t)j * (isB ? stepB : stepA));
     if (ks) {
       // k-strided operand: k is the ROW of the tensor, so a piece past K (the tail of the last k-tile, the look-ahead k-tiles behind it)
       // lies behind the end of the buffer window -- provided its whole address sits in the LANE offset (the hardware's range check does
@@ -789,7 +818,7 @@ IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdg
     const int j = i & 7;
     char* dst = my_part + (isB ? TILE_BYTES : 0) + (u & 1) * 2 * TILE_BYTES + j * 4096;
     const int kta = (dbg & 4) ? 0 : (isB ? ktaB0 : ktaA0) + u;
-    const uint32_t soff = (uint32_t)kta * (isB ? kstepB : kstepA) + (uint32_t)j * (isB ? stepB : stepA);
+    const uint32_t soff = (uint32_t)kta * (isB ? kstepB : kstepA) + ((ROWS && !isB) ? ro.o[j] : (uint32_t)j * (isB ? stepB : stepA));
     __builtin_amdgcn_raw_ptr_buffer_load_lds(isB ? rsB : rsA, IA_LDS(dst), 16, off, (int)soff, 0, 0);
   };
 
@@ -955,8 +984,10 @@ IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdg
 // row-major staging) and a lane reads back exactly the 16 bytes it stores.  Same pipelining and accumulator clearing as drain_half.
 // WITH_BIAS (k-contiguous B only): bct[ni][q] = the bias of the lane's columns ni*32 + hh*16 + 4q .. +3 (accumulator layout, fetched
 // before the main loop), added in fp32 before the rounding.
-template <bool BKS, int NH, bool WITH_BIAS>
-IA_DEV void drain_half_plain(const GemmArgs& p, f32x16 (&acc)[4][4], int m0, int n0, char* stg, int lane_e, const f32x4 (&bct)[4][4], float ts = 1.f) {
+// ROWS: block mi of the wave's rows starts at row rb.r[mi] (none: its stores leave behind the window), the window covers all of C.
+template <bool BKS, int NH, bool WITH_BIAS, bool ROWS = false>
+IA_DEV void drain_half_plain(const GemmArgs& p, f32x16 (&acc)[4][4], int m0, int n0, char* stg, int lane_e, const f32x4 (&bct)[4][4], float ts = 1.f,
+                             RowBlk rb = RowBlk{}) {
   static_assert(!(WITH_BIAS && BKS), "bias rows are laid out for the k-contiguous B fragment permutation");
   const int hh = lane_e >> 5, li = lane_e & 31, rrow = lane_e >> 3, c8 = lane_e & 7;
   auto stage = [&](int mi) {
@@ -1002,9 +1033,9 @@ IA_DEV void drain_half_plain(const GemmArgs& p, f32x16 (&acc)[4][4], int m0, int
   // out, so the hardware drops both -- no execution-mask branches, one 32-bit add per store instead of a 64-bit multiply-add chain
   // (the global_store form of rounds 1-3 spent ~400 scalar / branch / address instructions per wave and tile on clipping that a full
   // tile never needs).  The row advance sits in the LANE offset: the range check does not see a scalar offset.
-  const int rows_left = p.M - m0;
+  const int rows_left = ROWS ? p.M : p.M - m0;
   const uint64_t wbytes = rows_left > 0 ? (uint64_t)rows_left * p.ldc * 2 : 0;
-  const __amdgpu_buffer_rsrc_t rsC = ia_rsrc(reinterpret_cast<bf16*>(p.C) + (size_t)m0 * p.ldc, (uint32_t)(wbytes < 0x7FFFFFF0ull ? wbytes : 0x7FFFFFF0ull));
+  const __amdgpu_buffer_rsrc_t rsC = ia_rsrc(reinterpret_cast<bf16*>(p.C) + (ROWS ? (size_t)0 : (size_t)m0 * p.ldc), (uint32_t)(wbytes < 0x7FFFFFF0ull ? wbytes : 0x7FFFFFF0ull));
   const int ncol = n0 + c8 * 8;
   const uint32_t voffC = ncol < p.N ? (uint32_t)((rrow * p.ldc + ncol) * 2) : 0x80000000u;
   stage(0);
@@ -1022,7 +1053,8 @@ IA_DEV void drain_half_plain(const GemmArgs& p, f32x16 (&acc)[4][4], int m0, int
     if (mi < 3) stage(mi + 1);        // the other slot: no wait for the reads above (LDS operations of a wave complete in order)
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
-      const uint32_t off = voffC + (uint32_t)((mi * 32 + it * 8) * p.ldc * 2);
+      uint32_t off = voffC + (uint32_t)((mi * 32 + it * 8) * p.ldc * 2);
+      if constexpr (ROWS) off = rb.r[mi] >= 0 ? voffC + (uint32_t)(rb.r[mi] + it * 8) * (uint32_t)(p.ldc * 2) : 0x80000000u;
       if (!IA_GEMM_DBG_HOOKS || !(p.dbg & 64)) __builtin_amdgcn_raw_buffer_store_b128(v[it], rsC, (int)off, 0, 0);
       else asm volatile("" : : "v"(v[it]));
     }
@@ -1041,9 +1073,10 @@ IA_DEV void drain_half_plain(const GemmArgs& p, f32x16 (&acc)[4][4], int m0, int
 // for all slices -- is read once per tile, and the aux operand runs AHEAD slices ahead of the stores: VMEM retires in order, so a load
 // issued behind a store can only be waited for by draining that store; issued ahead, hipcc's own counters leave the younger stores in
 // flight (vmcnt(2 * AHEAD) in the steady state).
-template <int EPI, bool OUTF32, bool BKS, int NH>
+// ROWS: m0 is the wave's first row in the REMAPPED order (it numbers the column-sum partial); block mi lies at row rb.r[mi] of C and aux.
+template <int EPI, bool OUTF32, bool BKS, int NH, bool ROWS = false>
 IA_DEV void drain_half(const GemmArgs& p, f32x16 (&acc)[4][4], int m0, int n0, char* stg, int lane_e, bool full, bool bias_ready, f32x4 bias_lo,
-                       f32x4 bias_hi) {
+                       f32x4 bias_hi, RowBlk rb = RowBlk{}) {
   const int hh = lane_e >> 5, li = lane_e & 31;
   const int rrow = lane_e >> 3, c8 = lane_e & 7;
   constexpr bool HAS_BIAS = EPI == EPI_BIAS || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_GELU_ACT || EPI == EPI_BIAS_ADD;
@@ -1061,8 +1094,8 @@ IA_DEV void drain_half(const GemmArgs& p, f32x16 (&acc)[4][4], int m0, int n0, c
     // full tiles with bf16 outputs: buffer windows over the wave's rows (from row m0 to the end of the tensor), one lane offset each
     constexpr bool BUF = PRE && !OUTF32;
     const auto window = [&](const void* base, int ld) {
-      const uint64_t bytes = (uint64_t)(p.M - m0) * ld * 2;
-      return ia_rsrc(reinterpret_cast<const bf16*>(base) + (size_t)m0 * ld, (uint32_t)(bytes < 0x7FFFFFF0ull ? bytes : 0x7FFFFFF0ull));
+      const uint64_t bytes = (uint64_t)(ROWS ? p.M : p.M - m0) * ld * 2;
+      return ia_rsrc(reinterpret_cast<const bf16*>(base) + (ROWS ? (size_t)0 : (size_t)m0 * ld), (uint32_t)(bytes < 0x7FFFFFF0ull ? bytes : 0x7FFFFFF0ull));
     };
     BufIO io{ia_rsrc(nullptr, 0), ia_rsrc(nullptr, 0), 0u};
     __amdgpu_buffer_rsrc_t rsAux = ia_rsrc(nullptr, 0);
@@ -1074,7 +1107,8 @@ IA_DEV void drain_half(const GemmArgs& p, f32x16 (&acc)[4][4], int m0, int n0, c
       if (HAS_AUX) { rsAux = window(p.aux, p.ldaux); voffAux = (uint32_t)((rrow * p.ldaux + n0 + c8 * 8) * 2); }
     }
     auto aux_of = [&](int c) {
-      const int row_in = (c >> 2) * 32 + ((c >> 1) & 1) * 16 + (c & 1) * 8;
+      int row_in = (c >> 2) * 32 + ((c >> 1) & 1) * 16 + (c & 1) * 8;
+      if constexpr (ROWS) row_in = rb.r[c >> 2] + (c & 3) * 8;      // (PRE: every block of a full tile exists)
       if (BUF) return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rsAux, (int)(voffAux + (uint32_t)(row_in * p.ldaux * 2)), 0, 0));
       return *reinterpret_cast<const bf16x8*>(p.aux + (size_t)(m0 + row_in + rrow) * p.ldaux + n0 + c8 * 8);
     };
@@ -1121,17 +1155,17 @@ IA_DEV void drain_half(const GemmArgs& p, f32x16 (&acc)[4][4], int m0, int n0, c
 #pragma unroll
       for (int it = 0; it < 4; ++it) {
         const int row = it * 8 + rrow;
-        const int m = m0 + mi * 32 + row, n = n0 + c8 * 8;
+        const int m = ROWS ? rb.r[mi] + row : m0 + mi * 32 + row, n = n0 + c8 * 8;
         const int c = mi * 4 + it;
         if (PRE) {
           if (HAS_AUX && c + AHEAD < 16) {
             ax[(c + AHEAD) % (AHEAD + 1)] = aux_of(c + AHEAD);
             asm volatile("" ::: "memory");      // the load stays in front of this slice's store (hipcc would sink it behind)
           }
-          io.off = voffC + (uint32_t)((mi * 32 + it * 8) * p.ldc * 2);
+          io.off = voffC + (uint32_t)(((ROWS ? rb.r[mi] : mi * 32) + it * 8) * p.ldc * 2);
           if (!(IA_DBG(p) & 64)) epi_store8<EPI, OUTF32, true, BUF>(p, m, n, lo[it], hi[it], pb0, pb1, ax[c % (AHEAD + 1)], cs, &io);
         } else {
-          if (m < p.M && n < p.N && !(IA_DBG(p) & 64)) epi_store8<EPI, OUTF32, false>(p, m, n, lo[it], hi[it], pb0, pb1, ax[0], cs);
+          if ((!ROWS || rb.r[mi] >= 0) && m < p.M && n < p.N && !(IA_DBG(p) & 64)) epi_store8<EPI, OUTF32, false>(p, m, n, lo[it], hi[it], pb0, pb1, ax[0], cs);
         }
         if (IA_DBG(p) & 64) asm volatile("" : : "v"(lo[it]), "v"(hi[it]));
       }
@@ -1160,13 +1194,21 @@ IA_DEV void drain_half(const GemmArgs& p, f32x16 (&acc)[4][4], int m0, int n0, c
 template <bool AKS, bool BKS, int EPI_, bool OUTF32>
 __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
   constexpr bool LIVE = EPI_ == EPI_NONE_LIVE;
-  constexpr int EPI = LIVE ? (int)EPI_NONE : EPI_;
+  constexpr bool ROWS = EPI_ >= EPI_ROWS;
+  constexpr int EPI = LIVE ? (int)EPI_NONE : (ROWS ? EPI_ - EPI_ROWS : EPI_);
   static_assert(!LIVE || (AKS && BKS && OUTF32), "live k-tiles: the weight-gradient form only");
+  static_assert(!ROWS || (!AKS && !OUTF32 && (EPI == EPI_NONE || EPI == EPI_ADD || EPI == EPI_DGELU_CS)), "row remap: the data-gradient forms only");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane0 = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;          // 2 x 2 waves, 128 x 128 each, one per SIMD
   const int nk_all = (p.K + BK - 1) / BK;
+  // ROWS: the number of M-tiles comes from the device-side list (eight live 32-row blocks per tile); the host sized the grid for every row
+  [[maybe_unused]] int n_live = 0;
+  if constexpr (ROWS) {
+    n_live = __builtin_amdgcn_readfirstlane(p.row_blk[0]);
+    p.tiles_m = (n_live + 7) >> 3;
+  }
   const int total_tiles = p.tiles_m * p.tiles_n;
   // Split-K launches are a 1-D grid of tiles x splits workgroups whose XCD-aware order has the split OUTERMOST: one XCD's run of
   // 32 work items is then an 8 x 4 block of tiles of ONE k-slab, i.e. 12 operand panel streams per XCD instead of 36 when the
@@ -1204,11 +1246,17 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
     coords(tile, bm, bn);
     int lane = lane0;
     asm volatile("" : "+v"(lane));      // keep per-lane address arithmetic from being hoisted across the tile loop
-    const uint64_t oa = (uint64_t)(AKS ? kt0 * BK : bm * BM) * p.lda, ob = (uint64_t)(BKS ? kt0 * BK : bn * BN) * p.ldb;
+    RowOff ro{};
+    if constexpr (ROWS) {      // a block the list does not have: the tile's first block once more (computed, never stored)
+      const Blk8 bl = load_blk8(p.row_blk, bm, n_live);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) ro.o[j] = (uint32_t)(bl.b[j] >= 0 ? bl.b[j] : bl.b[0]) * (uint32_t)(32 * p.lda * 2);
+    }
+    const uint64_t oa = (uint64_t)(AKS ? kt0 * BK : (ROWS ? 0 : bm * BM)) * p.lda, ob = (uint64_t)(BKS ? kt0 * BK : bn * BN) * p.ldb;
     // (the bf16 bias form keeps 64 bias values in registers across the main loop -- 468 of 512: the peeled first trip spilled there)
     constexpr bool PEEL_OK = !(EPI == EPI_BIAS && !OUTF32 && !BKS);
-    main_loop<AKS, BKS, PEND, PEEL_OK, LIVE>(p, smem, acc, rsrc_at(p.A, p.a_bytes, oa), rsrc_at(p.B, p.b_bytes, ob), AKS ? bm * BM : 0, BKS ? bn * BN : 0, kt0,
-                              AKS ? 0 : kt0, BKS ? 0 : kt0, n_tiles, nk_all, wm, wn, wave, lane, prologue_only, stores_in_flight, live_mv);
+    main_loop<AKS, BKS, PEND, PEEL_OK, LIVE, ROWS>(p, smem, acc, rsrc_at(p.A, p.a_bytes, oa), rsrc_at(p.B, p.b_bytes, ob), AKS ? bm * BM : 0, BKS ? bn * BN : 0, kt0,
+                              AKS ? 0 : kt0, BKS ? 0 : kt0, n_tiles, nk_all, wm, wn, wave, lane, prologue_only, stores_in_flight, live_mv, ro);
   };
 
   // ---- Dynamic tile claim (persistent launches).  With the static order every workgroup owns the tiles bid, bid + gridDim.x, ...: a
@@ -1291,6 +1339,9 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
     if (first_tile < 0) { leave(); return; }
     claim_issue();                                                    // the second tile's claim travels under the first main loop
   }
+  if constexpr (ROWS) {
+    if (!dyn && first_tile >= total_tiles) return;                    // fewer live tiles than workgroups (none at all: every row is dead)
+  }
 
   f32x16 acc[4][4];
 #pragma unroll
@@ -1364,6 +1415,26 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
     int m0 = m0_pre, n0 = n0_pre;
     asm volatile("" : "+s"(m0), "+s"(n0));
     char* stg = smem + 2 * 2 * TILE_BYTES + wave * 2 * STAGE_BYTES;      // 8 KiB per wave: two staging slots
+    bool full_e = full;
+    if constexpr (ROWS) {
+      // the wave's four blocks; a tile counts as full (exact store count, unguarded epilogue) when all eight of its blocks exist and
+      // none of them is the partial last block of M
+      const Blk8 bl = load_blk8(p.row_blk, bm, n_live);
+      RowBlk rb;
+#pragma unroll
+      for (int mi = 0; mi < 4; ++mi) rb.r[mi] = (wm ? bl.b[4 + mi] : bl.b[mi]) * 32;      // (-1 -> negative: none)
+      const bool rows_ok = bl.b[7] >= 0 && bl.b[7] * 32 + 32 <= p.M;
+      full_e = rows_ok && n0_pre + 128 <= p.N;
+      if (!(IA_DBG(p) & 32)) {
+        if constexpr (EPI == EPI_NONE) {
+          drain_half_plain<BKS, 0, false, true>(p, acc, m0, n0, stg, lane_e, bct, 1.f, rb);
+          drain_half_plain<BKS, 1, false, true>(p, acc, m0, n0 + 64, stg, lane_e, bct, 1.f, rb);
+        } else {
+          drain_half<EPI, OUTF32, BKS, 0, true>(p, acc, m0, n0, stg, lane_e, full_e || (rows_ok && n0 + 64 <= p.N), false, pbv[0], pbv[1], rb);
+          drain_half<EPI, OUTF32, BKS, 1, true>(p, acc, m0, n0 + 64, stg, lane_e, full_e, false, pbv[2], pbv[3], rb);
+        }
+      }
+    } else
     if (!(IA_DBG(p) & 32)) {
       if constexpr (EPI == EPI_NONE && !OUTF32) {
         drain_half_plain<BKS, 0, false>(p, acc, m0, n0, stg, lane_e, bct);
@@ -1378,7 +1449,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
     }
     if (next >= total_tiles) break;
     // a wave whose 128 x 128 part of the tile was clipped by M or N issued fewer stores than PEND: drain instead of counting
-    stores_in_flight = !(IA_DBG(p) & 96) && full;
+    stores_in_flight = !(IA_DBG(p) & 96) && full_e;
     if (!stores_in_flight) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     tile = next;
   }
@@ -1401,20 +1472,45 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
 namespace t256la {
 using namespace t256w;
 
+// ROWS (GemmArgs::row_blk, see EPI_ROWS): an M-tile is eight entries of the live-block list.  A's windows cover the whole operand (empty
+// behind the last tile, as before) and every A piece takes its row offset -- the current tile's or the next one's -- as a scalar.
+template <bool ROWS>
 __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane0 = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
   const int nk_all = (p.K + BK - 1) / BK;             // >= 2 (the host sends shorter K to T256W)
+  [[maybe_unused]] int n_live = 0;
+  if constexpr (ROWS) {
+    n_live = __builtin_amdgcn_readfirstlane(p.row_blk[0]);
+    p.tiles_m = (n_live + 7) >> 3;
+  }
   const int total_tiles = p.tiles_m * p.tiles_n;
   const int n_tiles = nk_all;
+  if constexpr (ROWS) {
+    if ((int)blockIdx.x >= total_tiles) return;          // fewer live tiles than workgroups
+  }
   auto coords = [&](int tile, int& bm, int& bn) { tile_of_index(p, tile, total_tiles, bm, bn); };
   // a tile's operand windows; a tile index past the end gives empty windows: every piece of it reads zeros
   auto window_a = [&](int tile) {
     int bm = 0, bn = 0;
     if (tile < total_tiles) coords(tile, bm, bn);
-    return tile < total_tiles ? rsrc_at(p.A, p.a_bytes, (uint64_t)bm * BM * p.lda) : ia_rsrc(p.A, 0u);
+    return tile < total_tiles ? rsrc_at(p.A, p.a_bytes, ROWS ? (uint64_t)0 : (uint64_t)bm * BM * p.lda) : ia_rsrc(p.A, 0u);
+  };
+  // ROWS: the row offsets of a tile's eight A pieces (a block the list does not have: the tile's first block once more, never stored)
+  auto rows_a = [&](int tile) {
+    RowOff ro{};
+    if constexpr (ROWS) {
+      if (tile < total_tiles) {
+        int bm = 0, bn = 0;
+        coords(tile, bm, bn);
+        const Blk8 bl = load_blk8(p.row_blk, bm, n_live);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) ro.o[j] = (uint32_t)(bl.b[j] >= 0 ? bl.b[j] : bl.b[0]) * (uint32_t)(32 * p.lda * 2);
+      }
+    }
+    return ro;
   };
   auto window_b = [&](int tile) {
     int bm = 0, bn = 0;
@@ -1442,6 +1538,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
   int tile = blockIdx.x;
   __amdgpu_buffer_rsrc_t rsA = window_a(tile), rsB = window_b(tile);
   __amdgpu_buffer_rsrc_t rsAn = window_a(tile + (int)gridDim.x), rsBn = window_b(tile + (int)gridDim.x);
+  [[maybe_unused]] RowOff roA = rows_a(tile), roAn = rows_a(tile + (int)gridDim.x);
 
   // k-tile v of the CURRENT tile (v >= n_tiles: k-tile v - n_tiles of the NEXT tile) -> lane offset of its pieces, or out of range
   auto off_of = [&](int v) -> uint32_t {
@@ -1453,7 +1550,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
     const bool isB = i >= 8, nx = v >= n_tiles;
     const int j = i & 7, kt = nx ? v - n_tiles : v;
     char* dst = my_part + (isB ? TILE_BYTES : 0) + buf + j * 4096;
-    const uint32_t soff = (uint32_t)kt * (uint32_t)(BK * 2) + (uint32_t)j * (isB ? stepB : stepA);
+    const uint32_t soff = (uint32_t)kt * (uint32_t)(BK * 2) + ((ROWS && !isB) ? (nx ? roAn.o[j] : roA.o[j]) : (uint32_t)j * (isB ? stepB : stepA));
     const uint32_t off = ok ? (isB ? voffB : voffA) : OOB;
     __builtin_amdgcn_raw_ptr_buffer_load_lds(isB ? (nx ? rsBn : rsB) : (nx ? rsAn : rsA), IA_LDS(dst), 16, off, (int)soff, 0, 0);
   };
@@ -1545,12 +1642,22 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
     int m0 = m0_pre, n0 = n0_pre;
     asm volatile("" : "+s"(m0), "+s"(n0));
     char* stg = smem + 2 * 2 * TILE_BYTES + wave * 2 * STAGE_BYTES;
+    if constexpr (ROWS) {
+      const Blk8 bl = load_blk8(p.row_blk, bm, n_live);
+      RowBlk rb;
+#pragma unroll
+      for (int mi = 0; mi < 4; ++mi) rb.r[mi] = (wm ? bl.b[4 + mi] : bl.b[mi]) * 32;      // (-1 -> negative: none)
+      drain_half_plain<false, 0, false, true>(p, acc, m0, n0, stg, lane_e, no_bias, 1.f, rb);
+      drain_half_plain<false, 1, false, true>(p, acc, m0, n0 + 64, stg, lane_e, no_bias, 1.f, rb);
+    } else {
     drain_half_plain<false, 0, false>(p, acc, m0, n0, stg, lane_e, no_bias);
     drain_half_plain<false, 1, false>(p, acc, m0, n0 + 64, stg, lane_e, no_bias);
+    }
     tile += (int)gridDim.x;
     if (tile >= total_tiles) break;
     rsA = rsAn; rsB = rsBn;
     rsAn = window_a(tile + (int)gridDim.x); rsBn = window_b(tile + (int)gridDim.x);
+    if constexpr (ROWS) { roA = roAn; roAn = rows_a(tile + (int)gridDim.x); }
   }
   tie2<0>(a0, b0);                                        // dead, but in flight
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // the look-ahead pieces of the tile that does not exist target this workgroup's LDS
@@ -1693,13 +1800,38 @@ uint32_t* next_ctr_slot() {
   return base + (size_t)(g_launch_seq.fetch_add(1u, std::memory_order_relaxed) % CTR_SLOTS) * CTR_WORDS;
 }
 
+// EPI_ROWS launches: the rows of the dead 32-row blocks of C (bf16 [M, N], N a multiple of 8) written as zeros -- not every consumer of a
+// data gradient filters its rows -- and, with column-sum partials, the partial rows behind the last remapped M-tile (the second stage
+// sums a row count the host knows: one pair per 256 rows of M).  Dead blocks and partial rows are dealt out over the grid.
+__global__ __launch_bounds__(256) void zero_dead_rows_kernel(const int* __restrict__ list, bf16* __restrict__ C, int ldc, int M, int N,
+                                                             float* __restrict__ csum_part, int part_rows) {
+  const int n_live = list[0], n_dead = list[1], nbr = (list[2] + 7) & ~7;
+  const int* dead = list + t256w::ROW_BLK_HDR + nbr;
+  const int n8 = N >> 3;
+  const u32x4 z = {0u, 0u, 0u, 0u};
+  for (int d = blockIdx.x; d < n_dead; d += gridDim.x) {
+    const int r0 = dead[d] * 32;
+    for (int i = threadIdx.x; i < 32 * n8; i += 256) {
+      const int r = r0 + i / n8, c = (i % n8) * 8;
+      if (r < M) *reinterpret_cast<u32x4*>(C + (size_t)r * ldc + c) = z;
+    }
+  }
+  if (csum_part) {
+    const int first = ((n_live + 7) >> 3) * 2;
+    const size_t total = part_rows > first ? (size_t)(part_rows - first) * N : 0;
+    float* base = csum_part + (size_t)first * N;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) base[i] = 0.f;
+  }
+}
+
 template <bool AKS, bool BKS, int EPI, bool OUTF32>
 int launch(GemmArgs a, bool big, hipStream_t st) {
   constexpr int vid = AKS * 1000 + BKS * 100 + EPI * 10 + (OUTF32 ? 1 : 0);
+  constexpr bool DROWS = !AKS && !OUTF32 && (EPI == EPI_NONE || EPI == EPI_ADD || EPI == EPI_DGELU_CS);   // the forms that may carry a block list (GemmArgs::row_blk)
   // (a launch over the live k-tiles only is not recorded: the host cannot know how many k-tiles it executed, and the recorded FLOPs are
   // those of launches that executed all of theirs)
   constexpr bool WGRAD = AKS && BKS && EPI == EPI_NONE && OUTF32;      // the form that may carry a live-k-tile mask (GemmArgs::live_kt)
-  const bool rec = g_prof.on && g_prof.variant == vid && g_prof.n < g_prof.cap && !(WGRAD && a.live_kt);
+  const bool rec = g_prof.on && g_prof.variant == vid && g_prof.n < g_prof.cap && !(WGRAD && a.live_kt) && !(DROWS && a.row_blk);
   if (rec) (void)hipEventRecord(g_prof.ev[2 * g_prof.n], st);
   if (big) {
     a.tiles_m = (a.M + t256w::BM - 1) / t256w::BM; a.tiles_n = (a.N + t256w::BN - 1) / t256w::BN;
@@ -1710,7 +1842,7 @@ int launch(GemmArgs a, bool big, hipStream_t st) {
     // persistent launches with more than one tile per workgroup claim their tiles dynamically (IA_GEMM_DYNAMIC=0: the static order)
     a.tile_ctr = (a.splits == 1 && ntile > gx) ? next_ctr_slot() : nullptr;
     void (*kern)(GemmArgs) = t256w::gemm_kernel<AKS, BKS, EPI, OUTF32>;
-    static bool attr_set[3] = {false, false, false};      // per kernel: [0] this instantiation of t256w, [1] t256la, [2] the live-k-tile weight gradient
+    static bool attr_set[5] = {false, false, false, false, false};      // per kernel: [0] this instantiation of t256w, [1] t256la, [2] the live-k-tile weight gradient, [3] / [4] the row remap of [0] / [1]
     int la = 0;
     if constexpr (WGRAD) {
       if (a.live_kt) { kern = t256w::gemm_kernel<true, true, EPI_NONE_LIVE, true>; la = 2; }
@@ -1718,7 +1850,16 @@ int launch(GemmArgs a, bool big, hipStream_t st) {
     // plain NT form, several tiles per workgroup, static order: the look-ahead kernel (t256la; IA_GEMM_LA=0 keeps t256w)
     if constexpr (!AKS && !BKS && EPI == EPI_NONE && !OUTF32) {
       const char* e = getenv("IA_GEMM_LA");       // (read per launch: tests and A/B runs switch it in one process)
-      if ((e ? atoi(e) : 1) && a.splits == 1 && ntile > gx && !a.tile_ctr && a.K >= 2 * BK && !(IA_DBG(a))) { kern = t256la::gemm_kernel; la = 1; }
+      if ((e ? atoi(e) : 1) && a.splits == 1 && ntile > gx && !a.tile_ctr && a.K >= 2 * BK && !(IA_DBG(a))) { kern = t256la::gemm_kernel<false>; la = 1; }
+    }
+    // data gradient over the live 32-row blocks: the remapped form of the kernel chosen above, dead rows zeroed first
+    if constexpr (DROWS) {
+      if (a.row_blk) {
+        if (la == 1) kern = t256la::gemm_kernel<true>;      // (the look-ahead kernel's remapped form where the dense call takes that kernel)
+        else kern = t256w::gemm_kernel<false, BKS, EPI_ROWS + EPI, false>;
+        la = la == 1 ? 4 : 3;
+        hipLaunchKernelGGL(zero_dead_rows_kernel, dim3(1024), dim3(256), 0, st, a.row_blk, (bf16*)a.C, a.ldc, a.M, a.N, a.csum_part, ((a.M + 255) / 256) * 2);
+      }
     }
     if (!attr_set[la]) {
       if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, t256w::LDS_BYTES) != hipSuccess) return IA_ERR_LAUNCH;
@@ -1761,7 +1902,7 @@ extern "C" size_t ia_gemm_workspace_bytes(int M, int N, int K, int c_is_f32) {
 static int gemm_core(const void* A, int a_kstrided, int lda, const void* B, int b_kstrided, int ldb, void* C, int c_is_f32, int ldc, int M,
                      int N, int K, int epilogue, const float* bias, const void* aux, int ldaux, void* C2, int accumulate, void* workspace,
                      size_t workspace_bytes, const IaViewGemm* view, hipStream_t stream, int qcols = 0, float qscale = 1.f,
-                     const uint32_t* live_kt = nullptr);
+                     const uint32_t* live_kt = nullptr, const int* row_blocks = nullptr);
 
 // workspace of an IA_EPI_DGELU_COLSUM GEMM: one fp32 row of N partial sums per 128-row block of the output (and never less than
 // the stand-alone column-sum kernel needs, which small shapes fall back to)
@@ -1787,6 +1928,115 @@ extern "C" int ia_gemm_bf16_qscale(const void* A, int lda, const void* B, int ld
                    col_scale);
 }
 
+// ---- data gradient over the live 32-row blocks only
+// The remapped kernel addresses A, C and aux through one 32-bit buffer window each that covers the whole tensor, 16 bytes per lane.
+static bool dgrad_rows_fit(int M, int lda, int ldc, int ldaux) {
+  const uint64_t lim = 0x7FFFFFF0ull, rows = (uint64_t)M + 32;
+  return rows * lda * 2 < lim && rows * ldc * 2 < lim && rows * (uint64_t)ldaux * 2 < lim && !(ldc & 7) && !(ldaux & 7);
+}
+// block t = rows 32t .. 32t+31 (clipped to M): live = any row_live set.  One function for the device kernel and the host entry.
+static __host__ __device__ inline bool row_block_live(const uint8_t* row_live, int M, int t) {
+  const uint8_t* r = row_live + (size_t)t * 32;
+  const int n = M - t * 32 < 32 ? M - t * 32 : 32;
+  uint64_t any = 0;
+  if (n == 32 && ((uintptr_t)r & 7) == 0) {
+    for (int i = 0; i < 4; ++i) any |= reinterpret_cast<const uint64_t*>(r)[i];
+  } else {
+    for (int i = 0; i < n; ++i) any |= r[i];
+  }
+  return any != 0;
+}
+namespace {
+inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+// One wave, no LDS (a workgroup that asks for none can start beside the persistent GEMM workgroups of another stream, which hold all of
+// a CU's LDS).  Lane l looks at blocks 64i + l: first the flags of up to 64 rounds i are gathered into one 64-bit word per lane (loads
+// only, so they overlap), then every round is one ballot: a block's place in the live list is the number of live blocks in front of it,
+// in the dead list the number of dead ones (t minus that).
+__global__ __launch_bounds__(64) void row_blocks_kernel(const uint8_t* __restrict__ row_live, int M, int nb, int* __restrict__ out) {
+  const int nbr = (nb + 7) & ~7;
+  int* const live = out + t256w::ROW_BLK_HDR;
+  int* const dead = live + nbr;
+  const int lane = threadIdx.x;
+  int base = 0;
+  for (int c0 = 0; c0 < nb; c0 += 64 * 64) {
+    uint64_t flags = 0;
+#pragma unroll 8
+    for (int i = 0; i < 64; ++i) {
+      const int t = c0 + i * 64 + lane;
+      if (t < nb && row_block_live(row_live, M, t)) flags |= 1ull << i;
+    }
+    for (int i = 0; i < 64 && c0 + i * 64 < nb; ++i) {
+      const int t = c0 + i * 64 + lane;
+      const bool lv = (flags >> i) & 1ull;
+      const uint64_t b = __ballot(lv);
+      const int at = base + __popcll(b & ((1ull << lane) - 1ull));
+      if (t < nb) { if (lv) live[at] = t; else dead[t - at] = t; }
+      base += __popcll(b);
+    }
+  }
+  if (lane < t256w::ROW_BLK_HDR) out[lane] = lane == 0 ? base : (lane == 1 ? nb - base : (lane == 2 ? nb : 0));
+}
+}  // namespace
+
+extern "C" size_t ia_row_blocks_bytes(int M_rows) {
+  if (M_rows <= 0) return 0;
+  const size_t nbr = (size_t)(((M_rows + 31) / 32 + 7) & ~7);
+  return (t256w::ROW_BLK_HDR + 2 * nbr) * sizeof(int);
+}
+extern "C" int ia_row_blocks(const uint8_t* row_live, int M_rows, int* list, hipStream_t stream) {
+  (void)hipGetLastError();
+  if (!row_live || !list || M_rows <= 0 || ((uintptr_t)list & 31)) return IA_ERR_ARG;
+  hipLaunchKernelGGL(row_blocks_kernel, dim3(1), dim3(64), 0, stream, row_live, M_rows, (M_rows + 31) / 32, list);
+  return ia_check_launch();
+}
+extern "C" int ia_row_blocks_host(const uint8_t* row_live, int M_rows, int* list) {
+  if (!row_live || !list || M_rows <= 0) return IA_ERR_ARG;
+  const int nb = (M_rows + 31) / 32, nbr = (nb + 7) & ~7;
+  int* const live = list + t256w::ROW_BLK_HDR;
+  int* const dead = live + nbr;
+  int n_live = 0;
+  for (int t = 0; t < nb; ++t) {
+    if (row_block_live(row_live, M_rows, t)) live[n_live++] = t; else dead[t - n_live] = t;
+  }
+  for (int i = 0; i < t256w::ROW_BLK_HDR; ++i) list[i] = 0;
+  list[0] = n_live; list[1] = nb - n_live; list[2] = nb;
+  return IA_OK;
+}
+// library-internal (common.h): the data gradient with a list already built (ia_layer_bwd2 builds one per call for its four)
+int ia_gemm_dgrad_blocks(const void* dY, int ldy, const void* W, int w_kstrided, int ldw, void* dX, int ldx, int M_rows, int N_in, int K_out,
+                         int epilogue, const void* aux, int ldaux, void* C2, const int* row_blocks, void* workspace, size_t workspace_bytes,
+                         hipStream_t stream) {
+  if (epilogue != EPI_NONE && epilogue != EPI_ADD && epilogue != EPI_DGELU_CS) return IA_ERR_UNSUPPORTED;
+  return gemm_core(dY, 0, ldy, W, w_kstrided, ldw, dX, 0, ldx, M_rows, N_in, K_out, epilogue, nullptr, aux, ldaux, C2, 0, workspace,
+                   workspace_bytes, nullptr, stream, 0, 1.f, nullptr, row_blocks);
+}
+extern "C" size_t ia_gemm_dgrad_rows_workspace_bytes(int M_rows, int N_in, int K_out) {
+  if (M_rows <= 0 || N_in <= 0 || K_out <= 0) return 0;
+  return al256(ia_gemm_colsum_workspace_bytes(M_rows, N_in)) + ia_row_blocks_bytes(M_rows);
+}
+// 1: a call of this shape (rows contiguous: ldy = K_out, ldx = ldaux = N_in) with row_live computes the live 32-row blocks only; 0: it
+// runs every row, like ia_gemm_bf16 (the same conditions as gemm_core's)
+extern "C" int ia_gemm_dgrad_rows_filters(int M_rows, int N_in, int K_out) {
+  if (M_rows <= 0 || N_in <= 0 || K_out <= 0 || (K_out & 7)) return 0;
+  return make_plan(M_rows, N_in, K_out, false).big && dgrad_rows_fit(M_rows, K_out, N_in, N_in) ? 1 : 0;
+}
+extern "C" int ia_gemm_dgrad_rows(const void* dY, int ldy, const void* W, int w_kstrided, int ldw, void* dX, int ldx, int M_rows, int N_in,
+                                  int K_out, int epilogue, const void* aux, int ldaux, void* C2, const uint8_t* row_live, void* workspace,
+                                  size_t workspace_bytes, hipStream_t stream) {
+  if (epilogue != EPI_NONE && epilogue != EPI_ADD && epilogue != EPI_DGELU_CS) return IA_ERR_UNSUPPORTED;
+  if (!row_live)
+    return gemm_core(dY, 0, ldy, W, w_kstrided, ldw, dX, 0, ldx, M_rows, N_in, K_out, epilogue, nullptr, aux, ldaux, C2, 0, workspace,
+                     workspace_bytes, nullptr, stream);
+  if (M_rows <= 0 || N_in <= 0 || K_out <= 0) return IA_ERR_ARG;
+  // the column-sum partials in front, the block list behind them
+  const size_t cs_bytes = al256(ia_gemm_colsum_workspace_bytes(M_rows, N_in));
+  if (!workspace || workspace_bytes < cs_bytes + ia_row_blocks_bytes(M_rows) || ((uintptr_t)workspace & 31)) return IA_ERR_WORKSPACE;
+  int* list = reinterpret_cast<int*>((char*)workspace + cs_bytes);
+  int rc = ia_row_blocks(row_live, M_rows, list, stream);
+  return rc ? rc : ia_gemm_dgrad_blocks(dY, ldy, W, w_kstrided, ldw, dX, ldx, M_rows, N_in, K_out, epilogue, aux, ldaux, C2, list, workspace,
+                                        cs_bytes, stream);
+}
+
 // ---- weight gradient over the live rows only
 // bit t of the mask = OR of row_live over rows 64t .. 64t+63 (clipped to M).  One function for the device kernel and the host entry.
 static __host__ __device__ inline uint32_t ktile_live(const uint8_t* row_live, int M, int t) {
@@ -1807,7 +2057,6 @@ __global__ __launch_bounds__(256) void ktile_mask_kernel(const uint8_t* __restri
   const uint64_t b = __ballot(t < nk && ktile_live(row_live, M, t));
   if ((threadIdx.x & 31) == 0 && t < nk) mask[t >> 5] = (uint32_t)(b >> (threadIdx.x & 32));
 }
-inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 }  // namespace
 
 extern "C" size_t ia_ktile_mask_bytes(int M_rows) {
@@ -1892,7 +2141,8 @@ static int launch_dgelu_colsum(GemmArgs& g, bool big, float* csum, void* workspa
 
 static int gemm_core(const void* A, int a_kstrided, int lda, const void* B, int b_kstrided, int ldb, void* C, int c_is_f32, int ldc, int M,
                      int N, int K, int epilogue, const float* bias, const void* aux, int ldaux, void* C2, int accumulate, void* workspace,
-                     size_t workspace_bytes, const IaViewGemm* view, hipStream_t stream, int qcols, float qscale, const uint32_t* live_kt) {
+                     size_t workspace_bytes, const IaViewGemm* view, hipStream_t stream, int qcols, float qscale, const uint32_t* live_kt,
+                     const int* row_blocks) {
   const uint64_t a_window = view ? view->a_window : 0, b_window = view ? view->b_window : 0;
   const int groups = view ? view->groups : 1;
   (void)hipGetLastError();  // drop stale status left by unrelated runtime calls (e.g. hipEventQuery -> NotReady)
@@ -1947,6 +2197,9 @@ static int gemm_core(const void* A, int a_kstrided, int lda, const void* B, int 
   // shifted views of ia_gemm_view -- so the kernel sees a mask or NULL, never a bias.  launch<true, true, EPI_NONE, true> is reached
   // from this function only; a new call site that fills GemmArgs for this form must do the same.
   if (a_kstrided && b_kstrided && c_is_f32 && epilogue == EPI_NONE) g.live_kt = (big && g.nk_per_split <= t256w::LIVE_MAX_KTILES) ? live_kt : nullptr;
+  // the block list of the row-remapped data gradient shares the slot too (these epilogues have no bias): a list or NULL, never a bias
+  if (!a_kstrided && !c_is_f32 && (epilogue == EPI_NONE || epilogue == EPI_ADD || epilogue == EPI_DGELU_CS))
+    g.row_blk = (row_blocks && big && !g.dbg && dgrad_rows_fit(M, lda, ldc, aux ? ldaux : 0)) ? row_blocks : nullptr;
   const bool needs_bias = epilogue == EPI_BIAS || epilogue == EPI_BIAS_GELU || epilogue == EPI_BIAS_GELU_ACT || epilogue == EPI_BIAS_ADD;
   const bool needs_aux = epilogue == EPI_ADD || epilogue == EPI_DGELU || epilogue == EPI_BIAS_ADD || epilogue == EPI_DGELU_CS;
   if (needs_bias && !bias) return IA_ERR_ARG;

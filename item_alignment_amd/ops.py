@@ -88,6 +88,41 @@ def gemm_wgrad_rows(dy, x, row_live=None, *, out=None, accumulate=False):
     return out
 
 
+def row_blocks(row_live):
+    """The 32-row block list of ia_row_blocks (uint8 [M] on the GPU -> int32 words): [0] live count, [1] dead count, [2] blocks,
+    the ascending live blocks from word 8, the ascending dead blocks from word 8 + blocks rounded up to 8."""
+    lib = _lib.load()
+    _need(row_live, torch.uint8, "row_live")
+    M = row_live.numel()
+    out = torch.empty(lib.ia_row_blocks_bytes(M) // 4, device=row_live.device, dtype=torch.int32)
+    check(lib.ia_row_blocks(row_live.data_ptr(), M, out.data_ptr(), stream_ptr()), "ia_row_blocks")
+    return out
+
+
+def gemm_dgrad_rows(dy, w, row_live=None, *, w_kstrided=True, epilogue=EPI_NONE, aux=None, out=None, colsum_out=None):
+    """dX[M, N_in] = dy[M, K_out] W (+ EPI_NONE / EPI_ADD / EPI_DGELU_COLSUM); w: [K_out, N_in] (w_kstrided) or its transpose
+    [N_in, K_out].  row_live (uint8 [M]) == 0 promises that row of dy (and of aux for EPI_ADD) is all zeros: 32-row blocks without a
+    live row are skipped and written as zeros (ia_gemm_dgrad_rows).  row_live=None is gemm(dy, w, b_kstrided=w_kstrided, ...)."""
+    lib = _lib.load()
+    _need(dy, BF16, "dy"); _need(w, BF16, "w"); _need(aux, BF16, "aux"); _need(row_live, torch.uint8, "row_live")
+    _need(colsum_out, F32, "colsum_out")
+    M, K = dy.shape
+    Kw, N = w.shape if w_kstrided else w.shape[::-1]
+    if K != Kw or (row_live is not None and row_live.numel() != M):
+        raise ValueError("gemm_dgrad_rows: dy, w and row_live do not fit together")
+    if epilogue == EPI_DGELU_COLSUM and colsum_out is None:
+        raise ValueError("gemm_dgrad_rows: EPI_DGELU_COLSUM needs colsum_out")
+    if out is None:
+        out = torch.empty((M, N), device=dy.device, dtype=BF16)
+    _need(out, BF16, "out")
+    ws_bytes = lib.ia_gemm_dgrad_rows_workspace_bytes(M, N, K)
+    ws = torch.empty(ws_bytes, device=dy.device, dtype=torch.uint8)
+    check(lib.ia_gemm_dgrad_rows(dy.data_ptr(), K, w.data_ptr(), int(w_kstrided), w.shape[1], out.data_ptr(), N, M, N, K, epilogue,
+                                 ptr(aux), N if aux is not None else 0, ptr(colsum_out), ptr(row_live), ws.data_ptr(), ws_bytes,
+                                 stream_ptr()), "ia_gemm_dgrad_rows")
+    return out
+
+
 def ln_fwd(x, gamma, beta, eps, *, bias=None, residual=None, write_z=True, drop_p=0.0, seed=0, stream_id=0):
     lib = _lib.load()
     _need(x, BF16, "x"); _need(gamma, F32, "gamma"); _need(beta, F32, "beta"); _need(bias, F32, "bias"); _need(residual, BF16, "residual")
