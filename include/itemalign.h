@@ -37,7 +37,7 @@ const char* ia_strerror(int code);
 /* Bumped whenever an entry point is added or the meaning of an argument / output changes (round 2 changed what IA_EPI_BIAS_GELU
  * stores in C2 and what IA_EPI_DGELU expects in aux): a caller built against another header must not run on this library.
  * item_alignment_amd/_lib.py refuses to load a library whose version differs from the one it was written for. */
-#define IA_ABI_VERSION 18
+#define IA_ABI_VERSION 19
 int ia_abi_version(void);
 
 /* ---- GEMM: torch.nn.Linear forward / dgrad / wgrad (src/models/text.py:1241 -> RobertaLayer dense
@@ -116,6 +116,23 @@ int ia_row_blocks_host(const uint8_t* row_live, int M_rows, int* list);
 /* Diagnostics (tests, A/B runs): on == 0 makes ia_layer_bwd2 run its data gradients over every row although
  * ia_layer_cfg::masked_rows_dead is set (the block list is withheld; every other row filter stays); returns the previous setting. */
 int ia_debug_dgrad_rows(int on);
+/* Diagnostics (tests, A/B runs; ABI 19): on == 0 makes ia_layer_fwd / ia_layer_fwd_infer run every row although
+ * ia_layer_cfg::masked_rows_dead has bit 2 set; returns the previous setting. */
+int ia_debug_fwd_rows(int on);
+/* (ABI 19) The forward GEMM Y[M_rows, N_out] = X[M_rows, K_in] W[N_out, K_in]^T of ia_gemm_bf16 / ia_gemm_bf16_qscale (both operands
+ * k-contiguous, bf16 output; epilogue IA_EPI_NONE, IA_EPI_BIAS with scaled_cols / col_scale, IA_EPI_BIAS_GELU with C2, or
+ * IA_EPI_BIAS_GELU_ACT) with a row filter.  row_live [M_rows] uint8 or NULL.  Contract: row_live[m] == 0 = nobody who needs a defined value
+ * reads row m of Y / C2 (a padded position under ia_layer_cfg::masked_rows_dead bit 2).  The rows are taken in blocks of 32: a block
+ * without a live row is neither fetched nor multiplied.  fill_dead_rows != 0: its rows of Y (and C2) are written as zeros;
+ * fill_dead_rows == 0: they are not written at all (they keep what the buffer held).  Every row of a block that holds a live row is
+ * bit-identical to the unfiltered call's.  NULL = the unfiltered call.  With row_live the workspace (32-byte aligned,
+ * ia_gemm_fwd_rows_workspace_bytes: the block list) is required.  ia_gemm_fwd_rows_filters: 1 when a call of this shape with
+ * contiguous rows (ldx = K_in, ldy = N_out) honours row_live, 0 when it runs every row. */
+size_t ia_gemm_fwd_rows_workspace_bytes(int M_rows);
+int ia_gemm_fwd_rows_filters(int M_rows, int N_out, int K_in);
+int ia_gemm_fwd_rows(const void* X, int ldx, const void* W, int ldw, void* Y, int ldy, int M_rows, int N_out, int K_in, int epilogue,
+                     const float* bias, void* C2, int scaled_cols, float col_scale, const uint8_t* row_live, int fill_dead_rows,
+                     void* workspace, size_t workspace_bytes, ia_stream_t stream);
 
 /* per-launch HIP-event timing of one GEMM instantiation (variant = a_kstrided*1000 + b_kstrided*100 + epilogue*10 + c_is_f32),
  * recorded on the launch stream; used by bench.py for the roofline of the dominant kernel. */
@@ -139,6 +156,12 @@ int ia_debug_gemm_dynamic(int on);
 int ia_ln_fwd(const void* x, const float* bias, const void* residual, void* z_out, void* y, float* mean, float* rstd,
               const float* gamma, const float* beta, int M, int H, float eps, float drop_p, uint32_t seed, uint32_t stream_id,
               ia_stream_t stream);
+/* (ABI 19) ia_ln_fwd with a row filter: row_live [M] uint8 or NULL (= ia_ln_fwd).  A row with row_live[m] == 0 reads none of its input
+ * streams and leaves as zeros in y, in z_out when given (also in place), and in mean / rstd.  Live rows are bit-identical: the dropout
+ * stream is indexed by position. */
+int ia_ln_fwd_rows(const void* x, const float* bias, const void* residual, void* z_out, void* y, float* mean, float* rstd,
+                   const float* gamma, const float* beta, int M, int H, float eps, float drop_p, uint32_t seed, uint32_t stream_id,
+                   const uint8_t* row_live, ia_stream_t stream);
 size_t ia_ln_bwd_workspace_bytes(int M, int H);
 /* dz = LN'(dy) + dres; dx = dropout-masked dz (only when drop_p > 0); dgamma/dbeta/dbias (+)= column sums */
 int ia_ln_bwd(const void* dy, const void* dres, const void* z, const float* mean, const float* rstd, const float* gamma, void* dz,
@@ -601,8 +624,20 @@ typedef struct {
   int dy_colsum_done;
   /* (ABI 8) nonzero: no output of a masked position (key_mask == 0) reaches the loss, so the gradient arriving at such rows is exactly
    * zero in every layer -- the attention backward may skip query blocks made of masked positions only (IA_ATTN_MASKED_ROWS_DEAD).
-   * Zero = the round-5 behaviour (every row is computed). */
+   * Zero = the round-5 behaviour (every row is computed).
+   * (ABI 19) A bit set.  Bit 1 (value 1): the meaning above -- the backward skips.  Bit 2 (value 2), only together with bit 1, on padded
+   * rows with a key mask: nobody reads the layer's output at a masked position either, so the forward of a post-LN layer skips too -- the
+   * four GEMMs the 32-row blocks made of masked positions, the two LayerNorms the masked rows.  y, the LayerNorm outputs and sums are
+   * zeros at masked positions; q / k / v and the FFN activation (with its derivative) are zeros in blocks without a live row; the two
+   * projection outputs are not written there (their LayerNorm writes zeros over the stash's copy).  A stash written under 3 must be
+   * consumed by a backward with bit 1 set.  Every value the unmasked positions produce, and every gradient, is bit-identical to
+   * masked_rows_dead = 1. */
   int masked_rows_dead;
+  /* (ABI 19) optional, device pointers, NULL = the layer call builds its own: the 32-row block list (ia_row_blocks) and the live-k-tile
+   * mask (ia_ktile_mask) of key_mask taken as row_live [B * L].  The mask is the same for every layer of a stack, forward and backward:
+   * a caller builds the two once per step and hands them to every call.  Read only under masked_rows_dead (padded rows, post-LN). */
+  const int* row_blocks;
+  const uint32_t* live_ktiles;
 } ia_layer_cfg;
 
 /* per-layer activation stash (saved by forward, read by backward) and shared backward scratch */

@@ -27,7 +27,8 @@ class LayerGrads(C.Structure):
 class LayerCfg(C.Structure):
     _fields_ = [("B", i32), ("L", i32), ("H", i32), ("I", i32), ("nh", i32), ("pre_ln", i32), ("eps", f32),
                 ("hidden_drop", f32), ("attn_drop", f32), ("seed", u32), ("layer_id", u32), ("cu_seqlens", vp), ("total_tokens", i32),
-                ("dx_colsum_out", vp), ("dy_colsum_done", i32), ("masked_rows_dead", i32)]
+                ("dx_colsum_out", vp), ("dy_colsum_done", i32), ("masked_rows_dead", i32),
+                ("row_blocks", vp), ("live_ktiles", vp)]
 
 
 # name -> (restype, argtypes); must list every symbol include/itemalign.h declares
@@ -50,12 +51,17 @@ SIGNATURES = {
     "ia_row_blocks": (i32, [vp, i32, vp, vp]),
     "ia_row_blocks_host": (i32, [vp, i32, vp]),
     "ia_debug_dgrad_rows": (i32, [i32]),
+    "ia_gemm_fwd_rows_workspace_bytes": (sz, [i32]),
+    "ia_gemm_fwd_rows_filters": (i32, [i32, i32, i32]),
+    "ia_gemm_fwd_rows": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, i32, f32, vp, i32, vp, sz, vp]),
+    "ia_debug_fwd_rows": (i32, [i32]),
     "ia_prof_begin": (i32, [i32, i32]),
     "ia_prof_end": (i32, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i32)]),
     "ia_prof_bytes": (C.c_double, []),
     "ia_debug_cu_hog": (i32, [i32, C.c_float, vp]),
     "ia_debug_gemm_dynamic": (i32, [i32]),
     "ia_ln_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, u32, u32, vp]),
+    "ia_ln_fwd_rows": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, u32, u32, vp, vp]),
     "ia_ln_bwd_workspace_bytes": (sz, [i32, i32]),
     "ia_ln_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, u32, u32, vp, sz, i32, vp]),
     "ia_ln_bwd2": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, u32, u32, vp, sz, i32, vp]),
@@ -199,7 +205,7 @@ SIGNATURES = {
 _lib = None
 
 
-ABI_VERSION = 18      # = IA_ABI_VERSION of include/itemalign.h (tests/test_cabi_symbols.py keeps the two in step)
+ABI_VERSION = 19      # = IA_ABI_VERSION of include/itemalign.h (tests/test_cabi_symbols.py keeps the two in step)
 
 
 class ItemAlignError(RuntimeError):

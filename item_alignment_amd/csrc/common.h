@@ -211,4 +211,11 @@ __attribute__((visibility("hidden"))) int ia_gemm_dgrad_blocks(const void* dY, i
                                                                int M_rows, int N_in, int K_out, int epilogue, const void* aux, int ldaux, void* C2,
                                                                const int* row_blocks, void* workspace, size_t workspace_bytes,
                                                                hipStream_t stream);
+// Y[M_rows, N_out] = X[M_rows, K_in] W[N_out, K_in]^T (+ epilogue: IA_EPI_NONE, IA_EPI_BIAS with scaled_cols / col_scale, IA_EPI_BIAS_GELU
+// with C2, IA_EPI_BIAS_GELU_ACT) over the 32-row blocks of the live list only -- the forward form for a caller whose dead rows nobody
+// reads (layer_forward under masked_rows_dead bit 2).  fill_dead_rows: the dead blocks' rows of Y (and C2) are written as zeros, else not
+// written at all.  row_blocks == NULL or a shape the remapped kernel does not serve: every row, as ia_gemm_bf16 / ia_gemm_bf16_qscale.
+__attribute__((visibility("hidden"))) int ia_gemm_fwd_blocks(const void* X, int ldx, const void* W, int ldw, void* Y, int ldy, int M_rows, int N_out,
+                                                             int K_in, int epilogue, const float* bias, void* C2, int scaled_cols, float col_scale,
+                                                             const int* row_blocks, int fill_dead_rows, hipStream_t stream);
 

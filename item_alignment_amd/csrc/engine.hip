@@ -31,6 +31,7 @@ struct FwdBufs {
   char* hpre;   // gelu'(pre-activation) (IA_EPI_BIAS_GELU C2); null in the forward-only form
   char* hact;   // FFN hidden activation
   float* lse; float* mean1; float* rstd1; float* mean2; float* rstd2;
+  int* row_blk;  // masked_rows_dead bit 2: the forward's own 32-row block list (when the caller hands none in ia_layer_cfg::row_blocks)
   size_t bytes;
 };
 
@@ -51,6 +52,7 @@ FwdBufs carve_stash(const ia_layer_cfg* c, void* base) {
   s.lse = (float*)a.take((size_t)c->B * c->nh * c->L * 4);
   s.mean1 = (float*)a.take(M * 4); s.rstd1 = (float*)a.take(M * 4);
   s.mean2 = (float*)a.take(M * 4); s.rstd2 = (float*)a.take(M * 4);
+  s.row_blk = (int*)a.take(ia_row_blocks_bytes((int)M));
   s.bytes = a.bytes;
   return s;
 }
@@ -67,6 +69,7 @@ FwdBufs carve_infer(const ia_layer_cfg* c, void* base) {
   s.hpre = nullptr; s.hact = a.take(M * I * 2);
   s.lse = (float*)a.take((size_t)c->B * c->nh * c->L * 4);
   s.mean1 = s.mean2 = (float*)a.take(M * 4); s.rstd1 = s.rstd2 = (float*)a.take(M * 4);
+  s.row_blk = (int*)a.take(ia_row_blocks_bytes((int)M));
   s.bytes = a.bytes;
   return s;
 }
@@ -106,6 +109,8 @@ bool cfg_ok(const ia_layer_cfg* c) {
 
 // Diagnostics: 0 withholds the block list from the data gradients of ia_layer_bwd2 (they run every row); returns the previous setting.
 int g_dgrad_rows = 1;
+// ... and 0 makes layer_forward run every row under masked_rows_dead bit 2 (ia_debug_fwd_rows)
+int g_fwd_rows = 1;
 
 #define IA_TRY(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
 
@@ -132,8 +137,12 @@ int wgrad(const void* dy, int n_out, const void* x, int n_in, float* dw, int M, 
 // the value is still fp32) and the attention kernels are told so: none of forward / dQ / dK-dV / fused backward re-scales its q tiles.
 // Needs the q | k boundary on a 128-column tile boundary of the GEMM; other hidden sizes take the plain projection and kernels.
 bool q_prescale(const ia_layer_cfg* c) { return (c->H & 127) == 0; }
-int qkv_proj(const ia_layer_cfg* c, const void* x, const ia_layer_weights* w, void* qkv, int M, float scale, ia_stream_t st) {
+int qkv_proj(const ia_layer_cfg* c, const void* x, const ia_layer_weights* w, void* qkv, int M, float scale, ia_stream_t st,
+             const int* row_blk = nullptr) {
   const int H = c->H;
+  if (row_blk)      // the live 32-row blocks only, the others as zeros: the attention kernels read every row of q, k and v
+    return ia_gemm_fwd_blocks(x, H, w->w_qkv, H, qkv, 3 * H, M, 3 * H, H, IA_EPI_BIAS, w->b_qkv, nullptr, q_prescale(c) ? H : 0,
+                              q_prescale(c) ? scale * 1.4426950408889634f : 1.f, row_blk, 1, st);
   if (q_prescale(c)) return ia_gemm_bf16_qscale(x, H, w->w_qkv, H, qkv, 3 * H, M, 3 * H, H, w->b_qkv, H, scale * 1.4426950408889634f, st);
   return ia_gemm_bf16(x, 0, H, w->w_qkv, 0, H, qkv, 0, 3 * H, M, 3 * H, H, IA_EPI_BIAS, w->b_qkv, nullptr, 0, nullptr, 0, nullptr, 0, st);
 }
@@ -160,7 +169,7 @@ int attn_bwd(const ia_layer_cfg* c, const char* qkv, const uint8_t* key_mask, co
                                 gqkv, gqkv + (size_t)H * 2, gqkv + (size_t)2 * H * 2, 3 * H, c->B, c->nh, c->L, scale, drop, seed, st);
     return rc ? rc : ia_colsum(gqkv, 3 * H, (int)rows_of(c), 3 * H, db_qkv, 1, ws, ws_bytes, st);
   }
-  const int flags = (ps ? IA_ATTN_Q_PRESCALED : 0) | (c->masked_rows_dead ? IA_ATTN_MASKED_ROWS_DEAD : 0);
+  const int flags = (ps ? IA_ATTN_Q_PRESCALED : 0) | ((c->masked_rows_dead & 1) ? IA_ATTN_MASKED_ROWS_DEAD : 0);
   return ia_attn_bwd_bias_ex(flags, qkv, qkv + (size_t)H * 2, qkv + (size_t)2 * H * 2, 3 * H, key_mask, ctx, dctx, H, lse, delta, gqkv,
                              gqkv + (size_t)H * 2, gqkv + (size_t)2 * H * 2, 3 * H, db_qkv, ws, ws_bytes, c->B, c->nh, c->L, scale, drop, seed, st);
 }
@@ -178,19 +187,35 @@ int layer_forward(const ia_layer_cfg* c, const ia_layer_weights* w, const void* 
     const float hidden_drop = keep ? c->hidden_drop : 0.f, attn_drop = keep ? c->attn_drop : 0.f;
     const uint32_t seed = keep ? c->seed : 0u, attn_seed = keep ? c->seed * 2654435761u + c->layer_id * 97u + 17u : 0u;
     const uint32_t ln1_stream = keep ? c->layer_id * 4u + 0u : 0u, ln2_stream = keep ? c->layer_id * 4u + 1u : 0u;
+    // masked_rows_dead bits 1 + 2 (padded rows, a key mask): nobody reads this layer's output at a masked position.  Such a row is a
+    // masked key of every attention (P = 0 exactly), no head reads it, and its incoming gradient is exactly zero, so whatever the stash
+    // holds for it meets an exact zero in every weight-gradient sum: its values may be anything finite.  The GEMMs run the 32-row blocks
+    // that hold a live row only (one block list per call, or the caller's), the LayerNorms the live rows only (dead rows leave as zeros).
+    // Zeros are written where somebody reads every row: q / k / v (the attention kernels), the FFN activation and its derivative (the
+    // fc2 weight gradient's partly live k-tiles, the every-row x gelu' epilogue).  The two projection outputs in front of the LayerNorms
+    // are not filled: only their LayerNorm reads them, which skips the dead rows and, in the training form, overwrites them in place.
+    const uint8_t* const live = ((c->masked_rows_dead & 3) == 3 && !c->cu_seqlens && key_mask && g_fwd_rows) ? key_mask : nullptr;
+    const int* row_blk = nullptr;
+    if (live) {
+      row_blk = c->row_blocks;
+      if (!row_blk) { IA_TRY(ia_row_blocks(live, M, s.row_blk, st)); row_blk = s.row_blk; }
+    }
     // qkv = x Wqkv^T + b
-    IA_TRY(qkv_proj(c, x, w, s.qkv, M, scale, st));
+    IA_TRY(qkv_proj(c, x, w, s.qkv, M, scale, st, row_blk));
     IA_TRY(attn_fwd(c, s.qkv, key_mask, s.ctx, s.lse, scale, attn_drop, attn_seed, st));
     // z1 = x + dropout(ctx Wo^T + b_o); y1 = LN1(z1)
-    IA_TRY(ia_gemm_bf16(s.ctx, 0, H, w->w_o, 0, H, s.proj, 0, H, M, H, H, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, st));
-    IA_TRY(ia_ln_fwd(s.proj, w->b_o, x, keep ? s.proj : nullptr, s.ln, s.mean1, s.rstd1, w->ln1_g, w->ln1_b, M, H, c->eps, hidden_drop, seed,
-                     ln1_stream, st));
+    if (row_blk) IA_TRY(ia_gemm_fwd_blocks(s.ctx, H, w->w_o, H, s.proj, H, M, H, H, IA_EPI_NONE, nullptr, nullptr, 0, 1.f, row_blk, 0, st));
+    else IA_TRY(ia_gemm_bf16(s.ctx, 0, H, w->w_o, 0, H, s.proj, 0, H, M, H, H, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, st));
+    IA_TRY(ia_ln_fwd_rows(s.proj, w->b_o, x, keep ? s.proj : nullptr, s.ln, s.mean1, s.rstd1, w->ln1_g, w->ln1_b, M, H, c->eps, hidden_drop, seed,
+                          ln1_stream, live, st));
     // h = gelu(y1 W1^T + b1)
-    IA_TRY(ia_gemm_bf16(s.ln, 0, H, w->w_fc1, 0, H, s.hact, 0, I, M, I, H, gelu, w->b_fc1, nullptr, 0, s.hpre, 0, nullptr, 0, st));
+    if (row_blk) IA_TRY(ia_gemm_fwd_blocks(s.ln, H, w->w_fc1, H, s.hact, I, M, I, H, gelu, w->b_fc1, s.hpre, 0, 1.f, row_blk, 1, st));
+    else IA_TRY(ia_gemm_bf16(s.ln, 0, H, w->w_fc1, 0, H, s.hact, 0, I, M, I, H, gelu, w->b_fc1, nullptr, 0, s.hpre, 0, nullptr, 0, st));
     // z2 = y1 + dropout(h W2^T + b2); y = LN2(z2)
-    IA_TRY(ia_gemm_bf16(s.hact, 0, I, w->w_fc2, 0, I, s.ffn, 0, H, M, H, I, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, st));
-    IA_TRY(ia_ln_fwd(s.ffn, w->b_fc2, s.ln, keep ? s.ffn : nullptr, y, s.mean2, s.rstd2, w->ln2_g, w->ln2_b, M, H, c->eps, hidden_drop, seed,
-                     ln2_stream, st));
+    if (row_blk) IA_TRY(ia_gemm_fwd_blocks(s.hact, I, w->w_fc2, I, s.ffn, H, M, H, I, IA_EPI_NONE, nullptr, nullptr, 0, 1.f, row_blk, 0, st));
+    else IA_TRY(ia_gemm_bf16(s.hact, 0, I, w->w_fc2, 0, I, s.ffn, 0, H, M, H, I, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, st));
+    IA_TRY(ia_ln_fwd_rows(s.ffn, w->b_fc2, s.ln, keep ? s.ffn : nullptr, y, s.mean2, s.rstd2, w->ln2_g, w->ln2_b, M, H, c->eps, hidden_drop, seed,
+                          ln2_stream, live, st));
   } else {   // no dropout (timm ViT default; ia_layer_fwd refuses it)
     IA_TRY(ia_ln_fwd(x, nullptr, nullptr, nullptr, s.xn, s.mean1, s.rstd1, w->ln1_g, w->ln1_b, M, H, c->eps, 0.f, 0, 0, st));
     IA_TRY(qkv_proj(c, s.xn, w, s.qkv, M, scale, st));
@@ -206,6 +231,12 @@ int layer_forward(const ia_layer_cfg* c, const ia_layer_weights* w, const void* 
 }
 
 }  // namespace
+
+extern "C" int ia_debug_fwd_rows(int on) {
+  const int was = g_fwd_rows;
+  g_fwd_rows = on ? 1 : 0;
+  return was;
+}
 
 extern "C" int ia_debug_dgrad_rows(int on) {
   const int was = g_dgrad_rows;
@@ -277,11 +308,13 @@ extern "C" int ia_layer_bwd2(const ia_layer_cfg* c, const ia_layer_weights* w, c
     // the four weight gradients skip the 64-row k-tiles that hold nothing else (one bitmask per call, in scratch), and the three plain data
     // gradients (fc1, out-projection, QKV) the 32-row blocks (one block list per call; their dead rows are written as zeros: the attention backward, the pair
     // kernels and the embedding backward read every row)
-    const uint8_t* const live = (c->masked_rows_dead && !c->cu_seqlens) ? key_mask : nullptr;
-    const uint32_t* const live_kt = live ? k.live_kt : nullptr;
-    const int* const row_blk = (live && g_dgrad_rows) ? k.row_blk : nullptr;
-    if (live) IA_TRY(ia_ktile_mask(live, M, k.live_kt, st));
-    if (row_blk) IA_TRY(ia_row_blocks(live, M, k.row_blk, st));
+    // (the mask is the same for every layer of a stack and step: a caller that built the bitmask and the list once hands them in
+    // ia_layer_cfg::live_ktiles / row_blocks, and the two launches per call go)
+    const uint8_t* const live = ((c->masked_rows_dead & 1) && !c->cu_seqlens) ? key_mask : nullptr;
+    const uint32_t* const live_kt = live ? (c->live_ktiles ? c->live_ktiles : k.live_kt) : nullptr;
+    const int* const row_blk = (live && g_dgrad_rows) ? (c->row_blocks ? c->row_blocks : k.row_blk) : nullptr;
+    if (live && !c->live_ktiles) IA_TRY(ia_ktile_mask(live, M, k.live_kt, st));
+    if (row_blk && !c->row_blocks) IA_TRY(ia_row_blocks(live, M, k.row_blk, st));
     // The two residual additions of a post-LN layer make each LayerNorm output's gradient a sum of two terms; both LayerNorm
     // backward kernels take the two terms (ia_ln_bwd2), so the GEMMs in front of them keep the plain epilogue.
     // LN2 backward: d(output) = dy (+ dy2) -> dz2 in g0, masked branch gradient -> g1 (or g0 when p == 0)

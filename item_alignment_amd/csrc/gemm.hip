@@ -44,10 +44,13 @@ enum { EPI_NONE = 0, EPI_BIAS = 1, EPI_BIAS_GELU = 2, EPI_ADD = 3, EPI_DGELU = 4
 // the token rows as k: a k-tile whose rows of dY are all zeros adds +-0 to every accumulator, so leaving it out changes no bit of the
 // fp32 sums -- the k-slabs of a split-K launch and the order of the reduction stay what they are, a slab just takes fewer trips.
 constexpr int EPI_NONE_LIVE = 8;
-// EPI_ROWS + e (library-internal, t256w only; e = EPI_NONE, EPI_ADD or EPI_DGELU_CS, k-contiguous A, bf16 output): epilogue e behind a row
-// remap.  The data gradient dX = dY W has the token rows as M: a row of dY that is all zeros gives a row of zeros, so only the 32-row
+// EPI_ROWS + e (library-internal, t256w only; k-contiguous A, bf16 output): epilogue e behind a row remap.  The data gradient dX = dY W
+// (e = EPI_NONE, EPI_ADD or EPI_DGELU_CS) has the token rows as M: a row of dY that is all zeros gives a row of zeros, so only the 32-row
 // blocks that hold a live row are computed -- an M-tile is eight consecutive entries of the live-block list (GemmArgs::row_blk) instead
 // of 256 consecutive rows -- and the dead blocks are written as zeros by a fill launch.  No live row's arithmetic changes.
+// The forward forms (e = EPI_NONE, EPI_BIAS with qcols / qscale, EPI_BIAS_GELU with both outputs, EPI_BIAS_GELU_ACT; both operands
+// k-contiguous) skip the blocks whose rows nobody reads (padded positions under ia_layer_cfg::masked_rows_dead bit 2); there the fill is
+// the caller's choice (GemmArgs::rows_fill): without it the dead blocks of C / C2 are not written at all.
 constexpr int EPI_ROWS = 16;
 // EPI_BIAS_GELU_ACT: the forward-only form of EPI_BIAS_GELU (activation only: no derivative is evaluated or stored)
 
@@ -59,8 +62,6 @@ struct GemmArgs {
     // argument block moves): bit t of this bitmask set = k-tile t (k rows 64t .. 64t+63) has at least one row of A that is not known
     // to be all zeros; a workgroup walks only the set bits of its k-slab (t256w::gemm_kernel<true, true, EPI_NONE_LIVE, true>).  NULL = every k-tile.
     const uint32_t* live_kt;
-    // Row-remapped data-gradient form of the 256-wide kernel only (EPI_ROWS + e: no bias either): the block list ia_row_blocks wrote.
-    const int* row_blk;
   };
   const bf16* aux;
   int M, N, K;
@@ -94,6 +95,14 @@ struct GemmArgs {
   // Dynamic tile claim (t256w, persistent launches): 8 per-XCD claim counters + 1 exit counter of this launch's slot (zero on entry,
   // zeroed again by the last workgroup to leave); NULL = the static order (tile + gridDim.x).
   uint32_t* tile_ctr;
+  // Row-remapped form of the 256-wide kernels only (EPI_ROWS + e): the block list ia_row_blocks wrote, NULL = every row.  Behind every
+  // member the other kernels read, so their argument blocks keep their layout.  rows_fill (host side): the launch writes the dead
+  // blocks' rows of C (and C2) as zeros first.
+  const int* row_blk;
+  int rows_fill, fill_m;      // fill_m: the rows the fill covers (M, unless the remapped launch leaves its last rows to a launch of their own)
+  // EPI_ROWS + EPI_BIAS: every wave takes the row-layout epilogue, (acc + bias) * qscale -- the launch over the rows behind the last whole
+  // 128-row part of M, which the dense kernel rounds that way (gemm_core)
+  int rows_guarded;
 };
 
 // One slot per launch in flight (launches of different streams may overlap; a slot comes round again after CTR_SLOTS launches).
@@ -724,6 +733,27 @@ IA_DEV Blk8 load_blk8(const int* list, int bm, int n_live) {
   return r;
 }
 
+// GemmArgs::rows_guarded (EPI_ROWS + EPI_BIAS only): the launch is ONE M-tile made of the live blocks behind the last whole 128-row part
+// of M -- at most four, the last entries of the ascending live list, taken from its end backwards (so the ones that exist come first;
+// the kernel runs no tile when the first does not exist, so b[0], which stands in for the missing ones, is always a real block).
+template <bool GUARDABLE>
+IA_DEV Blk8 tile_blocks(const GemmArgs& p, int bm, int n_live) {
+  if constexpr (GUARDABLE) {
+    if (p.rows_guarded) {
+      const int tb0 = (p.M & ~127) >> 5;
+      Blk8 r;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        int v = -1;
+        if (j < 4 && n_live - 1 - j >= 0) v = __builtin_amdgcn_readfirstlane(p.row_blk[ROW_BLK_HDR + n_live - 1 - j]);
+        r.b[j] = v >= tb0 ? v : -1;
+      }
+      return r;
+    }
+  }
+  return load_blk8(p.row_blk, bm, n_live);
+}
+
 // Walk over the set bits of a k-slab's live-k-tile mask in increasing order.  Lane l of `mv` holds bits 32l .. 32l+31 of the slab (every
 // wave holds the same 64 words, fetched once in front of the first prologue DMA); the walk itself is SALU plus one v_readlane per step --
 // no memory operation, so it can sit next to the k loop's counted waits, and no branch.  Once the bits are used up next() keeps
@@ -1196,8 +1226,11 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
   constexpr bool LIVE = EPI_ == EPI_NONE_LIVE;
   constexpr bool ROWS = EPI_ >= EPI_ROWS;
   constexpr int EPI = LIVE ? (int)EPI_NONE : (ROWS ? EPI_ - EPI_ROWS : EPI_);
+  constexpr bool GUARDABLE = ROWS && EPI == EPI_BIAS;      // (tile_blocks)
   static_assert(!LIVE || (AKS && BKS && OUTF32), "live k-tiles: the weight-gradient form only");
-  static_assert(!ROWS || (!AKS && !OUTF32 && (EPI == EPI_NONE || EPI == EPI_ADD || EPI == EPI_DGELU_CS)), "row remap: the data-gradient forms only");
+  static_assert(!ROWS || (!AKS && !OUTF32 && (EPI == EPI_NONE || EPI == EPI_ADD || EPI == EPI_DGELU_CS ||
+                                              (!BKS && (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_GELU_ACT)))),
+                "row remap: the data-gradient forms and the k-contiguous forward forms only");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane0 = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1208,6 +1241,14 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
   if constexpr (ROWS) {
     n_live = __builtin_amdgcn_readfirstlane(p.row_blk[0]);
     p.tiles_m = (n_live + 7) >> 3;
+    if constexpr (GUARDABLE) {
+      // one M-tile, or none when no live block lies behind the last whole 128-row part (the usual case: the end of the last sequence
+      // is padding) -- every workgroup returns before its first DMA: tile_blocks would have no block to address
+      if (p.rows_guarded) {
+        const int last = n_live > 0 ? __builtin_amdgcn_readfirstlane(p.row_blk[ROW_BLK_HDR + n_live - 1]) : -1;
+        p.tiles_m = last >= ((p.M & ~127) >> 5) ? 1 : 0;
+      }
+    }
   }
   const int total_tiles = p.tiles_m * p.tiles_n;
   // Split-K launches are a 1-D grid of tiles x splits workgroups whose XCD-aware order has the split OUTERMOST: one XCD's run of
@@ -1248,7 +1289,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
     asm volatile("" : "+v"(lane));      // keep per-lane address arithmetic from being hoisted across the tile loop
     RowOff ro{};
     if constexpr (ROWS) {      // a block the list does not have: the tile's first block once more (computed, never stored)
-      const Blk8 bl = load_blk8(p.row_blk, bm, n_live);
+      const Blk8 bl = tile_blocks<GUARDABLE>(p, bm, n_live);
 #pragma unroll
       for (int j = 0; j < 8; ++j) ro.o[j] = (uint32_t)(bl.b[j] >= 0 ? bl.b[j] : bl.b[0]) * (uint32_t)(32 * p.lda * 2);
     }
@@ -1369,7 +1410,9 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
     f32x4 bct[4][4] = {};
     int lane_b = lane0;
     asm volatile("" : "+v"(lane_b));
-    const bool bias_pre = HAS_BIAS_K && full;
+    // (ROWS: the bias depends on the columns only, and which rounding an EPI_BIAS element takes -- accumulator layout or row layout --
+    // must not depend on where the remap put its row: every wave whose columns lie inside N takes the form a dense full tile takes)
+    const bool bias_pre = HAS_BIAS_K && (ROWS ? n0_pre + 128 <= p.N && !(BIAS_CT && p.rows_guarded) : full);
     if (bias_pre && BIAS_CT) {
       const float* bp = p.bias + n0_pre + (lane_b >> 5) * 16;
 #pragma unroll
@@ -1419,7 +1462,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
     if constexpr (ROWS) {
       // the wave's four blocks; a tile counts as full (exact store count, unguarded epilogue) when all eight of its blocks exist and
       // none of them is the partial last block of M
-      const Blk8 bl = load_blk8(p.row_blk, bm, n_live);
+      const Blk8 bl = tile_blocks<GUARDABLE>(p, bm, n_live);
       RowBlk rb;
 #pragma unroll
       for (int mi = 0; mi < 4; ++mi) rb.r[mi] = (wm ? bl.b[4 + mi] : bl.b[mi]) * 32;      // (-1 -> negative: none)
@@ -1429,9 +1472,14 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
         if constexpr (EPI == EPI_NONE) {
           drain_half_plain<BKS, 0, false, true>(p, acc, m0, n0, stg, lane_e, bct, 1.f, rb);
           drain_half_plain<BKS, 1, false, true>(p, acc, m0, n0 + 64, stg, lane_e, bct, 1.f, rb);
+        } else if (BIAS_CT && bias_pre) {      // (a block the list does not have, a row past M: the stores fall behind the window)
+          if constexpr (BIAS_CT) {
+            drain_half_plain<false, 0, true, true>(p, acc, m0, n0, stg, lane_e, bct, ts, rb);
+            drain_half_plain<false, 1, true, true>(p, acc, m0, n0 + 64, stg, lane_e, bct, ts, rb);
+          }
         } else {
-          drain_half<EPI, OUTF32, BKS, 0, true>(p, acc, m0, n0, stg, lane_e, full_e || (rows_ok && n0 + 64 <= p.N), false, pbv[0], pbv[1], rb);
-          drain_half<EPI, OUTF32, BKS, 1, true>(p, acc, m0, n0 + 64, stg, lane_e, full_e, false, pbv[2], pbv[3], rb);
+          drain_half<EPI, OUTF32, BKS, 0, true>(p, acc, m0, n0, stg, lane_e, full_e || (rows_ok && n0 + 64 <= p.N), bias_pre, pbv[0], pbv[1], rb);
+          drain_half<EPI, OUTF32, BKS, 1, true>(p, acc, m0, n0 + 64, stg, lane_e, full_e, bias_pre, pbv[2], pbv[3], rb);
         }
       }
     } else
@@ -1827,7 +1875,9 @@ __global__ __launch_bounds__(256) void zero_dead_rows_kernel(const int* __restri
 template <bool AKS, bool BKS, int EPI, bool OUTF32>
 int launch(GemmArgs a, bool big, hipStream_t st) {
   constexpr int vid = AKS * 1000 + BKS * 100 + EPI * 10 + (OUTF32 ? 1 : 0);
-  constexpr bool DROWS = !AKS && !OUTF32 && (EPI == EPI_NONE || EPI == EPI_ADD || EPI == EPI_DGELU_CS);   // the forms that may carry a block list (GemmArgs::row_blk)
+  // the forms that may carry a block list (GemmArgs::row_blk): the data gradients, and the forward epilogues on k-contiguous operands
+  constexpr bool DROWS = !AKS && !OUTF32 && (EPI == EPI_NONE || EPI == EPI_ADD || EPI == EPI_DGELU_CS ||
+                                             (!BKS && (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_GELU_ACT)));
   // (a launch over the live k-tiles only is not recorded: the host cannot know how many k-tiles it executed, and the recorded FLOPs are
   // those of launches that executed all of theirs)
   constexpr bool WGRAD = AKS && BKS && EPI == EPI_NONE && OUTF32;      // the form that may carry a live-k-tile mask (GemmArgs::live_kt)
@@ -1835,6 +1885,7 @@ int launch(GemmArgs a, bool big, hipStream_t st) {
   if (rec) (void)hipEventRecord(g_prof.ev[2 * g_prof.n], st);
   if (big) {
     a.tiles_m = (a.M + t256w::BM - 1) / t256w::BM; a.tiles_n = (a.N + t256w::BN - 1) / t256w::BN;
+    if (a.row_blk && a.rows_guarded) a.tiles_m = 1;      // (the launch over the last blocks of the list: one M-tile, one workgroup per N-tile)
     const int ntile = a.tiles_m * a.tiles_n;
     // split-K: one workgroup per (tile, k-slab), 1-D so the kernel can order them XCD-aware with the slab outermost;
     // otherwise persistent over tiles, one workgroup per CU
@@ -1852,13 +1903,16 @@ int launch(GemmArgs a, bool big, hipStream_t st) {
       const char* e = getenv("IA_GEMM_LA");       // (read per launch: tests and A/B runs switch it in one process)
       if ((e ? atoi(e) : 1) && a.splits == 1 && ntile > gx && !a.tile_ctr && a.K >= 2 * BK && !(IA_DBG(a))) { kern = t256la::gemm_kernel<false>; la = 1; }
     }
-    // data gradient over the live 32-row blocks: the remapped form of the kernel chosen above, dead rows zeroed first
+    // over the live 32-row blocks: the remapped form of the kernel chosen above, dead rows zeroed first where the caller asks for it
     if constexpr (DROWS) {
       if (a.row_blk) {
         if (la == 1) kern = t256la::gemm_kernel<true>;      // (the look-ahead kernel's remapped form where the dense call takes that kernel)
         else kern = t256w::gemm_kernel<false, BKS, EPI_ROWS + EPI, false>;
         la = la == 1 ? 4 : 3;
-        hipLaunchKernelGGL(zero_dead_rows_kernel, dim3(1024), dim3(256), 0, st, a.row_blk, (bf16*)a.C, a.ldc, a.M, a.N, a.csum_part, ((a.M + 255) / 256) * 2);
+        if (a.rows_fill)
+          hipLaunchKernelGGL(zero_dead_rows_kernel, dim3(1024), dim3(256), 0, st, a.row_blk, (bf16*)a.C, a.ldc, a.fill_m, a.N, a.csum_part, ((a.M + 255) / 256) * 2);
+        if (a.rows_fill && EPI == EPI_BIAS_GELU)
+          hipLaunchKernelGGL(zero_dead_rows_kernel, dim3(1024), dim3(256), 0, st, a.row_blk, a.C2, a.ldc, a.fill_m, a.N, (float*)nullptr, 0);
       }
     }
     if (!attr_set[la]) {
@@ -1902,7 +1956,7 @@ extern "C" size_t ia_gemm_workspace_bytes(int M, int N, int K, int c_is_f32) {
 static int gemm_core(const void* A, int a_kstrided, int lda, const void* B, int b_kstrided, int ldb, void* C, int c_is_f32, int ldc, int M,
                      int N, int K, int epilogue, const float* bias, const void* aux, int ldaux, void* C2, int accumulate, void* workspace,
                      size_t workspace_bytes, const IaViewGemm* view, hipStream_t stream, int qcols = 0, float qscale = 1.f,
-                     const uint32_t* live_kt = nullptr, const int* row_blocks = nullptr);
+                     const uint32_t* live_kt = nullptr, const int* row_blocks = nullptr, int rows_fill = 1, int tail_of = 0);      // tail_of: below
 
 // workspace of an IA_EPI_DGELU_COLSUM GEMM: one fp32 row of N partial sums per 128-row block of the output (and never less than
 // the stand-alone column-sum kernel needs, which small shapes fall back to)
@@ -2009,6 +2063,30 @@ int ia_gemm_dgrad_blocks(const void* dY, int ldy, const void* W, int w_kstrided,
   if (epilogue != EPI_NONE && epilogue != EPI_ADD && epilogue != EPI_DGELU_CS) return IA_ERR_UNSUPPORTED;
   return gemm_core(dY, 0, ldy, W, w_kstrided, ldw, dX, 0, ldx, M_rows, N_in, K_out, epilogue, nullptr, aux, ldaux, C2, 0, workspace,
                    workspace_bytes, nullptr, stream, 0, 1.f, nullptr, row_blocks);
+}
+// library-internal (common.h): a forward GEMM Y = X W^T (+ epilogue) with a list already built (layer_forward: one list, four GEMMs)
+int ia_gemm_fwd_blocks(const void* X, int ldx, const void* W, int ldw, void* Y, int ldy, int M_rows, int N_out, int K_in, int epilogue,
+                       const float* bias, void* C2, int scaled_cols, float col_scale, const int* row_blocks, int fill_dead_rows, hipStream_t stream) {
+  if (epilogue != EPI_NONE && epilogue != EPI_BIAS && epilogue != EPI_BIAS_GELU && epilogue != EPI_BIAS_GELU_ACT) return IA_ERR_UNSUPPORTED;
+  return gemm_core(X, 0, ldx, W, 0, ldw, Y, 0, ldy, M_rows, N_out, K_in, epilogue, bias, nullptr, 0, C2, 0, nullptr, 0, nullptr, stream, scaled_cols,
+                   col_scale, nullptr, row_blocks, fill_dead_rows);
+}
+extern "C" size_t ia_gemm_fwd_rows_workspace_bytes(int M_rows) { return ia_row_blocks_bytes(M_rows); }
+// 1: a call of this shape (rows contiguous: ldx = K_in, ldy = N_out) with row_live computes the live 32-row blocks only; 0: every row
+extern "C" int ia_gemm_fwd_rows_filters(int M_rows, int N_out, int K_in) {
+  if (M_rows <= 0 || N_out <= 0 || K_in <= 0 || (K_in & 7) || (N_out & 7)) return 0;
+  return make_plan(M_rows, N_out, K_in, false).big && dgrad_rows_fit(M_rows, K_in, N_out, 0) ? 1 : 0;
+}
+extern "C" int ia_gemm_fwd_rows(const void* X, int ldx, const void* W, int ldw, void* Y, int ldy, int M_rows, int N_out, int K_in, int epilogue,
+                                const float* bias, void* C2, int scaled_cols, float col_scale, const uint8_t* row_live, int fill_dead_rows,
+                                void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  if (epilogue != EPI_NONE && epilogue != EPI_BIAS && epilogue != EPI_BIAS_GELU && epilogue != EPI_BIAS_GELU_ACT) return IA_ERR_UNSUPPORTED;
+  if (!row_live) return ia_gemm_fwd_blocks(X, ldx, W, ldw, Y, ldy, M_rows, N_out, K_in, epilogue, bias, C2, scaled_cols, col_scale, nullptr, 0, stream);
+  if (M_rows <= 0 || N_out <= 0 || K_in <= 0) return IA_ERR_ARG;
+  if (!workspace || workspace_bytes < ia_row_blocks_bytes(M_rows) || ((uintptr_t)workspace & 31)) return IA_ERR_WORKSPACE;
+  int rc = ia_row_blocks(row_live, M_rows, (int*)workspace, stream);
+  return rc ? rc : ia_gemm_fwd_blocks(X, ldx, W, ldw, Y, ldy, M_rows, N_out, K_in, epilogue, bias, C2, scaled_cols, col_scale, (const int*)workspace,
+                                      fill_dead_rows, stream);
 }
 extern "C" size_t ia_gemm_dgrad_rows_workspace_bytes(int M_rows, int N_in, int K_out) {
   if (M_rows <= 0 || N_in <= 0 || K_out <= 0) return 0;
@@ -2142,7 +2220,7 @@ static int launch_dgelu_colsum(GemmArgs& g, bool big, float* csum, void* workspa
 static int gemm_core(const void* A, int a_kstrided, int lda, const void* B, int b_kstrided, int ldb, void* C, int c_is_f32, int ldc, int M,
                      int N, int K, int epilogue, const float* bias, const void* aux, int ldaux, void* C2, int accumulate, void* workspace,
                      size_t workspace_bytes, const IaViewGemm* view, hipStream_t stream, int qcols, float qscale, const uint32_t* live_kt,
-                     const int* row_blocks) {
+                     const int* row_blocks, int rows_fill, int tail_of) {
   const uint64_t a_window = view ? view->a_window : 0, b_window = view ? view->b_window : 0;
   const int groups = view ? view->groups : 1;
   (void)hipGetLastError();  // drop stale status left by unrelated runtime calls (e.g. hipEventQuery -> NotReady)
@@ -2197,9 +2275,24 @@ static int gemm_core(const void* A, int a_kstrided, int lda, const void* B, int 
   // shifted views of ia_gemm_view -- so the kernel sees a mask or NULL, never a bias.  launch<true, true, EPI_NONE, true> is reached
   // from this function only; a new call site that fills GemmArgs for this form must do the same.
   if (a_kstrided && b_kstrided && c_is_f32 && epilogue == EPI_NONE) g.live_kt = (big && g.nk_per_split <= t256w::LIVE_MAX_KTILES) ? live_kt : nullptr;
-  // the block list of the row-remapped data gradient shares the slot too (these epilogues have no bias): a list or NULL, never a bias
-  if (!a_kstrided && !c_is_f32 && (epilogue == EPI_NONE || epilogue == EPI_ADD || epilogue == EPI_DGELU_CS))
-    g.row_blk = (row_blocks && big && !g.dbg && dgrad_rows_fit(M, lda, ldc, aux ? ldaux : 0)) ? row_blocks : nullptr;
+  // the block list of the row-remapped forms (C2 has C's pitch, so dgrad_rows_fit covers it): a list or NULL
+  const bool fwd_epi = !b_kstrided && (epilogue == EPI_BIAS || epilogue == EPI_BIAS_GELU || epilogue == EPI_BIAS_GELU_ACT);
+  g.row_blk = nullptr; g.rows_fill = rows_fill; g.fill_m = M; g.rows_guarded = tail_of ? 1 : 0;
+  if (!a_kstrided && !c_is_f32 && (epilogue == EPI_NONE || epilogue == EPI_ADD || epilogue == EPI_DGELU_CS || fwd_epi))
+    g.row_blk = (row_blocks && big && !g.dbg && !(N & 7) && dgrad_rows_fit(M, lda, ldc, aux ? ldaux : 0)) ? row_blocks : nullptr;
+  // Scaled columns, M no multiple of 128: the dense kernel rounds the rows behind the last whole 128-row part of M as (acc + bias) * scale
+  // (guarded row-layout epilogue) and the others as acc * scale + bias * scale (accumulator-layout epilogue).  The remap would mix the two
+  // in one wave, so the remapped launch covers the whole parts and the (at most four) blocks behind them get a remapped launch of their
+  // own in front of it: one M-tile taken from the end of the live list, the row-layout epilogue in every wave (tail_of: that call,
+  // GemmArgs::rows_guarded).  The fill of the main launch sees every row.
+  if (g.row_blk && fwd_epi && qcols > 0 && (M & 127) && !tail_of) {
+    const int Mb = M & ~127;
+    int rc = gemm_core(A, 0, lda, B, 0, ldb, C, 0, ldc, M, N, K, epilogue, bias, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, stream, qcols, qscale, nullptr,
+                       row_blocks, 0, 1);
+    if (rc) return rc;
+    g.a_bytes = ((uint64_t)(Mb - 1) * lda + K) * 2;
+    g.M = Mb;
+  }
   const bool needs_bias = epilogue == EPI_BIAS || epilogue == EPI_BIAS_GELU || epilogue == EPI_BIAS_GELU_ACT || epilogue == EPI_BIAS_ADD;
   const bool needs_aux = epilogue == EPI_ADD || epilogue == EPI_DGELU || epilogue == EPI_BIAS_ADD || epilogue == EPI_DGELU_CS;
   if (needs_bias && !bias) return IA_ERR_ARG;

@@ -16,16 +16,37 @@ namespace {
 
 constexpr int MAXV = 8;  // up to 4096 columns
 
-template <int NV>
+// FILTER (live [M], ia_ln_fwd_rows): live[row] == 0 marks a row nobody reads (a padded position under ia_layer_cfg::masked_rows_dead
+// bit 2): none of its input streams is read, y / z_out get a row of zeros and mean / rstd 0.  A template parameter, like the backward's:
+// the unfiltered launches (the ViT's, every dense caller) keep the kernel without the test.  One flag per wave, every lane loading the
+// same byte and the wave balloting it, so the branch is scalar.  The dropout stream is indexed by position: live rows draw what they
+// draw in the unfiltered kernel.
+template <int NV, bool FILTER = false>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const bf16* __restrict__ x, const float* __restrict__ bias,
                                                      const bf16* __restrict__ res, bf16* __restrict__ z_out,
                                                      bf16* __restrict__ y, float* __restrict__ mean_out,
                                                      float* __restrict__ rstd_out, const float* __restrict__ gamma,
                                                      const float* __restrict__ beta, int M, int H, float eps,
-                                                     uint32_t thr16, float inv_keep, uint32_t seed, uint32_t stream) {
+                                                     uint32_t thr16, float inv_keep, uint32_t seed, uint32_t stream,
+                                                     const uint8_t* __restrict__ live = nullptr) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= M) return;
+  if constexpr (FILTER) {
+    if (__ballot(live[row] != 0) == 0ull) {
+      const bf16x8 zero = {};
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const int col = i * 512 + lane * 8;
+        if (col < H) {
+          *reinterpret_cast<bf16x8*>(y + (size_t)row * H + col) = zero;
+          if (z_out) *reinterpret_cast<bf16x8*>(z_out + (size_t)row * H + col) = zero;
+        }
+      }
+      if (lane == 0) { mean_out[row] = 0.f; rstd_out[row] = 0.f; }
+      return;
+    }
+  }
   float v[NV][8];
   float s = 0.f;
 #pragma unroll
@@ -336,17 +357,29 @@ int ln_blocks(int M) { int b = (M + 3) / 4; return b < 512 ? b : 512; }
 
 }  // namespace
 
+extern "C" int ia_ln_fwd_rows(const void* x, const float* bias, const void* residual, void* z_out, void* y, float* mean,
+                              float* rstd, const float* gamma, const float* beta, int M, int H, float eps, float drop_p,
+                              uint32_t seed, uint32_t stream_id, const uint8_t* row_live, hipStream_t stream);
+
 extern "C" int ia_ln_fwd(const void* x, const float* bias, const void* residual, void* z_out, void* y, float* mean,
                          float* rstd, const float* gamma, const float* beta, int M, int H, float eps, float drop_p,
                          uint32_t seed, uint32_t stream_id, hipStream_t stream) {
+  return ia_ln_fwd_rows(x, bias, residual, z_out, y, mean, rstd, gamma, beta, M, H, eps, drop_p, seed, stream_id, nullptr, stream);
+}
+
+// ia_ln_fwd with a row filter: row_live [M] uint8 or NULL (= ia_ln_fwd); a row with row_live[m] == 0 reads nothing and leaves as zeros
+extern "C" int ia_ln_fwd_rows(const void* x, const float* bias, const void* residual, void* z_out, void* y, float* mean,
+                              float* rstd, const float* gamma, const float* beta, int M, int H, float eps, float drop_p,
+                              uint32_t seed, uint32_t stream_id, const uint8_t* row_live, hipStream_t stream) {
   (void)hipGetLastError();  // drop stale status left by unrelated runtime calls (e.g. hipEventQuery -> NotReady)
   if (!x || !y || !mean || !rstd || !gamma || M <= 0 || H <= 0 || (H & 7) || H > 512 * MAXV) return IA_ERR_ARG;
   const uint32_t thr16 = drop_p > 0.f ? (uint32_t)(drop_p * 65536.f + 0.5f) : 0u;
   const float inv_keep = drop_p > 0.f ? 1.f / (1.f - (float)thr16 / 65536.f) : 1.f;
   const int nv = (H + 511) / 512;
   dim3 grid((M + 3) / 4), blk(256);
-#define IA_LN_FWD(NV) hipLaunchKernelGGL((ln_fwd_kernel<NV>), grid, blk, 0, stream, (const bf16*)x, bias, (const bf16*)residual, \
-    (bf16*)z_out, (bf16*)y, mean, rstd, gamma, beta, M, H, eps, thr16, inv_keep, seed, stream_id)
+#define IA_LN_FWD_(NV, F) hipLaunchKernelGGL((ln_fwd_kernel<NV, F>), grid, blk, 0, stream, (const bf16*)x, bias, (const bf16*)residual, \
+    (bf16*)z_out, (bf16*)y, mean, rstd, gamma, beta, M, H, eps, thr16, inv_keep, seed, stream_id, row_live)
+#define IA_LN_FWD(NV) do { if (row_live) IA_LN_FWD_(NV, true); else IA_LN_FWD_(NV, false); } while (0)
   switch (nv) {
     case 1: IA_LN_FWD(1); break;
     case 2: IA_LN_FWD(2); break;
@@ -355,6 +388,7 @@ extern "C" int ia_ln_fwd(const void* x, const float* bias, const void* residual,
     default: IA_LN_FWD(8); break;
   }
 #undef IA_LN_FWD
+#undef IA_LN_FWD_
   return ia_check_launch();
 }
 

@@ -361,7 +361,7 @@ class _EngineStack:
         c.attn_drop = self.attn_drop if training else 0.0
         c.seed = seed
         c.layer_id = self.layer_id_base + i
-        c.masked_rows_dead = int(self.__dict__.get("_masked_rows_dead", False))
+        c.masked_rows_dead = int(self.__dict__.get("_masked_rows_dead", 0))      # bit set: 1 = the backward skips, 2 = the forward too
         return c
 
 
@@ -397,14 +397,17 @@ class RobertaEncoder(nn.Module, _EngineStack):
                     w_fc2=l.output.dense.weight, b_fc2=l.output.dense.bias,
                     ln2_g=l.output.LayerNorm.weight, ln2_b=l.output.LayerNorm.bias)
 
-    def forward(self, hidden_states, attention_mask=None, masked_rows_dead=False):
+    def forward(self, hidden_states, attention_mask=None, masked_rows_dead=False, padded_rows_unread=False):
         """masked_rows_dead: the caller reads no hidden state of a masked position (heads on [CLS] / valid spans) -- the gradient arriving
-        at such rows is then exactly zero in every layer and the attention backward may skip query blocks made of them (ia_layer_cfg)."""
+        at such rows is then exactly zero in every layer and the attention backward may skip query blocks made of them (ia_layer_cfg).
+        padded_rows_unread (with masked_rows_dead): the caller also accepts zeros there in the returned hidden states -- the forward
+        skips the padded rows as well (ia_layer_cfg::masked_rows_dead bit 2)."""
         B, L, H = hidden_states.shape
         km = None
         if attention_mask is not None:
             km = (attention_mask != 0).to(torch.uint8).contiguous()
-        self.__dict__["_masked_rows_dead"] = bool(masked_rows_dead and km is not None)
+        dead = bool(masked_rows_dead and km is not None)
+        self.__dict__["_masked_rows_dead"] = (1 if dead else 0) | (2 if dead and padded_rows_unread else 0)
         outs = Fn.EncoderStackFn.apply(hidden_states.reshape(B * L, H), self.anchor, self, km, B, L, torch.is_grad_enabled(), None)
         return (hidden_states,) + tuple(o.view(B, L, H) for o in outs)
 

@@ -153,13 +153,30 @@ class EncoderStackFn(torch.autograd.Function):
         outs, cur = [], x.contiguous()
         inputs = [cur]
         mp = ptr(key_mask)
+        # masked_rows_dead: the key mask is the same for every layer, forward and backward -- the 32-row block list and the live-k-tile
+        # bitmask are built once here (one small tensor, kept for the backward) instead of once per layer call
+        ctx.row_lists = None
+        flag = cfgs[0].masked_rows_dead
+        if key_mask is not None and cu_seqlens is None and not cfgs[0].pre_ln and ((flag & 1 and keep) or (flag & 3) == 3):
+            M = cur.shape[0]
+            lb = (lib.ia_row_blocks_bytes(M) + 255) & ~255
+            lists = torch.empty(lb + lib.ia_ktile_mask_bytes(M), device=x.device, dtype=torch.uint8)
+            check(lib.ia_row_blocks(mp, M, lists.data_ptr(), stream_ptr()), "ia_row_blocks")
+            if keep:                                       # (the weight gradients' mask: nothing reads it without a backward)
+                check(lib.ia_ktile_mask(mp, M, lists.data_ptr() + lb, stream_ptr()), "ia_ktile_mask")
+            for c in cfgs:
+                c.row_blocks, c.live_ktiles = lists.data_ptr(), (lists.data_ptr() + lb) if keep else None
+            ctx.row_lists = lists
         if keep:
             stash_bytes = lib.ia_layer_stash_bytes(C.byref(cfgs[0]))
-            stash = torch.empty(n * stash_bytes, device=x.device, dtype=torch.uint8)
+            # one allocation per layer (4 GB each at the bench's shape), not one of n layers: a request for 90 GiB in one piece is served
+            # by nothing but an untouched segment of that size -- one live tensor the allocator placed inside the cached block while
+            # it was free (a tower changing streams, another batch shape in between) and the step runs out of memory with 90 GiB free
+            stash = [torch.empty(stash_bytes, device=x.device, dtype=torch.uint8) for _ in range(n)]
             for i in range(n):
                 y = torch.empty_like(cur)
                 check(lib.ia_layer_fwd(C.byref(cfgs[i]), C.byref(stack.weights(i)), cur.data_ptr(), mp, y.data_ptr(),
-                                       stash.data_ptr() + i * stash_bytes, stream_ptr()), f"ia_layer_fwd[{i}]")
+                                       stash[i].data_ptr(), stream_ptr()), f"ia_layer_fwd[{i}]")
                 outs.append(y)
                 cur = y
                 inputs.append(cur)
@@ -187,7 +204,7 @@ class EncoderStackFn(torch.autograd.Function):
         lib = _lib.load()
         stack, cfgs, n = ctx.stack, ctx.cfgs, len(ctx.cfgs)
         scratch_bytes = lib.ia_layer_bwd_scratch_bytes(C.byref(cfgs[0]))
-        scratch = torch.empty(scratch_bytes, device=ctx.stash.device, dtype=torch.uint8)
+        scratch = torch.empty(scratch_bytes, device=ctx.stash[0].device, dtype=torch.uint8)
         mp = ptr(ctx.key_mask)
         dy, dy2buf, have_dy2 = None, None, False
         colsum_done = False
@@ -215,13 +232,14 @@ class EncoderStackFn(torch.autograd.Function):
                 cfgs[i].dy_colsum_done = int(colsum_done)
                 colsum_done = below
             check(lib.ia_layer_bwd2(C.byref(cfgs[i]), C.byref(stack.weights(i)), C.byref(stack.grads(i)), x.data_ptr(), mp,
-                                    ctx.inputs[i + 1].data_ptr(), ctx.stash.data_ptr() + i * ctx.stash_bytes, dy.data_ptr(),
+                                    ctx.inputs[i + 1].data_ptr(), ctx.stash[i].data_ptr(), dy.data_ptr(),
                                     dy2buf.data_ptr() if have_dy2 else None, dy.data_ptr(), dy2buf.data_ptr() if split else None,
                                     scratch.data_ptr(), scratch_bytes, stream_ptr()), f"ia_layer_bwd2[{i}]")
             have_dy2 = split
             _notify(stack.layer_params(i), final=left <= 0)
         ctx.stash = None
         ctx.inputs = None
+        ctx.row_lists = None
         return dy, None, None, None, None, None, None, None
 
 

@@ -48,7 +48,8 @@ class RobertaImageOneTower(RobertaOneTower):
     def _make_backbone(self, config):
         return RobertaImageModel(config, add_pooling_layer=False)
 
-    def _backbone(self, input_ids, attention_mask, token_type_ids, position_ids, cate_ids, inputs_embeds, image_indices):
+    def _backbone(self, input_ids, attention_mask, token_type_ids, position_ids, cate_ids, inputs_embeds, image_indices,
+                  hidden_states_asked=False):
         return self.roberta(input_ids, attention_mask=attention_mask, token_type_ids=token_type_ids, position_ids=position_ids,
                             inputs_embeds=inputs_embeds, image_indices=image_indices)
 
@@ -86,7 +87,7 @@ class CoCaModel(nn.Module):
         # over all L text tokens without a padding mask, reference multimodal.py:529-616), so the unpadded tower run (IA_UNPAD),
         # which leaves zeros there, must not be used
         out = self.text_encoder(input_ids, attention_mask=attention_mask, token_type_ids=token_type_ids, position_ids=position_ids,
-                                allow_unpad=not padded_rows_matter)
+                                allow_unpad=not padded_rows_matter, padded_rows_unread=not padded_rows_matter)
         return out.last_hidden_state
 
     def embed_image(self, images):

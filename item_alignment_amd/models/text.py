@@ -120,7 +120,11 @@ class RobertaModel(HipModule, PretrainedMixin):
         return self.embeddings.word_embeddings
 
     def forward(self, input_ids=None, attention_mask=None, token_type_ids=None, position_ids=None, cate_ids=None, head_mask=None,
-                inputs_embeds=None, output_attentions=None, output_hidden_states=None, return_dict=None, allow_unpad=True, **unused):
+                inputs_embeds=None, output_attentions=None, output_hidden_states=None, return_dict=None, allow_unpad=True,
+                padded_rows_unread=False, **unused):
+        """padded_rows_unread: the caller reads no hidden state of a padded position and accepts zeros there (as under IA_UNPAD): the
+        forward then skips the padded rows too (ia_layer_cfg::masked_rows_dead bit 2).  Opt-in -- a direct caller gets every position
+        of last_hidden_state computed."""
         (self._root if "_root" in self.__dict__ else self).ensure_arena()
         if input_ids is None:
             raise ValueError("You have to specify input_ids")
@@ -134,7 +138,8 @@ class RobertaModel(HipModule, PretrainedMixin):
         # allow_unpad = "nothing the caller reads depends on the padded rows" (every head of the reference reads [CLS] or valid spans; the
         # cross_attn multimodal layers, which attend over ALL text positions, pass False): the padded run may then at least skip what is
         # provably zero in its backward
-        hs = self.encoder(e, attention_mask, masked_rows_dead=allow_unpad and cate_ids is None and not output_hidden_states)
+        dead = allow_unpad and cate_ids is None and not output_hidden_states
+        hs = self.encoder(e, attention_mask, masked_rows_dead=dead, padded_rows_unread=dead and padded_rows_unread)
         return BaseModelOutput(last_hidden_state=hs[-1], hidden_states=hs)
 
     def _forward_unpadded(self, input_ids, attention_mask, token_type_ids, position_ids):
@@ -252,7 +257,8 @@ class RobertaOneTower(_PairTowerBase):
     def _make_backbone(self, config):
         return RobertaModel(config, add_pooling_layer=False)
 
-    def _backbone(self, input_ids, attention_mask, token_type_ids, position_ids, cate_ids, inputs_embeds, image_indices):
+    def _backbone(self, input_ids, attention_mask, token_type_ids, position_ids, cate_ids, inputs_embeds, image_indices,
+                  hidden_states_asked=False):
         # the auxiliary attribute-pair task averages hidden states over caller-given spans (reference text.py:66-102), which may reach
         # into padded positions (the reference computes those rows like any other; the golden fixture's third sample does exactly that):
         # with it, the padded rows matter -- no unpadded run, no skipped query blocks in the attention backward
@@ -260,8 +266,10 @@ class RobertaOneTower(_PairTowerBase):
         # padded position whenever a sequence is shorter than that (the eight-sample golden fixtures hold two such sequences: the row-wise
         # LayerNorm filter of round 6 caught it -- the 32-position attention blocks had not)
         rows_matter = hasattr(self, "auxiliary_task") or self.config.classification_method == "vec_sim"
+        # (a caller that asked for the hidden states gets every position of them computed: the forward keeps the padded rows)
         return self.roberta(input_ids, attention_mask=attention_mask, token_type_ids=token_type_ids, position_ids=position_ids,
-                            cate_ids=cate_ids, allow_unpad=not rows_matter)
+                            cate_ids=cate_ids, allow_unpad=not rows_matter,
+                            padded_rows_unread=not rows_matter and not hidden_states_asked)
 
     def _tgt_index(self):
         return self.max_seq_len
@@ -270,7 +278,8 @@ class RobertaOneTower(_PairTowerBase):
                 inputs_embeds=None, image_indices=None, labels=None, output_attentions=None, output_hidden_states=None,
                 return_dict=None):
         self.ensure_arena()
-        outputs = self._backbone(input_ids, attention_mask, token_type_ids, position_ids, cate_ids, inputs_embeds, image_indices)
+        outputs = self._backbone(input_ids, attention_mask, token_type_ids, position_ids, cate_ids, inputs_embeds, image_indices,
+                                 hidden_states_asked=bool(output_hidden_states))
         hs = outputs.hidden_states
         B, L, H = hs[-1].shape
         dev = hs[-1].device
@@ -325,7 +334,9 @@ class RobertaTwoTower(_PairTowerBase):
         return torch.cat((a, b), dim=0)
 
     def _backbone(self, ids, mask, tts, pids, extra1=None, extra2=None):
-        return self.roberta(ids, attention_mask=mask, token_type_ids=tts, position_ids=pids).last_hidden_state
+        # the head reads the two [CLS] rows only and the wrapper returns no hidden states: the padded rows are neither differentiated
+        # nor computed
+        return self.roberta(ids, attention_mask=mask, token_type_ids=tts, position_ids=pids, padded_rows_unread=True).last_hidden_state
 
     def forward(self, input_ids_1=None, attention_mask_1=None, token_type_ids_1=None, cate_ids_1=None, position_ids_1=None,
                 input_ids_2=None, attention_mask_2=None, token_type_ids_2=None, cate_ids_2=None, position_ids_2=None,
@@ -393,7 +404,8 @@ class PKGMOneTower(RobertaOneTower):
     def _make_backbone(self, config):
         return RobertaPKGMModel(config, add_pooling_layer=False)
 
-    def _backbone(self, input_ids, attention_mask, token_type_ids, position_ids, cate_ids, inputs_embeds, image_indices):
+    def _backbone(self, input_ids, attention_mask, token_type_ids, position_ids, cate_ids, inputs_embeds, image_indices,
+                  hidden_states_asked=False):
         # the cls head reads position 0 of the last layer only; vec_sim reads a fixed second position (RobertaOneTower._backbone)
         return self.roberta(input_ids, attention_mask=attention_mask, token_type_ids=token_type_ids, position_ids=position_ids,
                             masked_rows_dead=self.config.classification_method != "vec_sim")

@@ -123,6 +123,46 @@ def gemm_dgrad_rows(dy, w, row_live=None, *, w_kstrided=True, epilogue=EPI_NONE,
     return out
 
 
+def gemm_fwd_rows(x, w, row_live=None, *, epilogue=EPI_NONE, bias=None, scaled_cols=0, col_scale=1.0, fill=True, out=None, pre_out=None):
+    """Y[M, N] = x[M, K] w[N, K]^T (+ EPI_NONE / EPI_BIAS with scaled_cols, col_scale / EPI_BIAS_GELU / EPI_BIAS_GELU_ACT = 7) over the
+    32-row blocks that hold a live row (row_live uint8 [M]; ia_gemm_fwd_rows).  fill: the other blocks' rows are written as zeros, else
+    not written.  row_live=None is the unfiltered call.  EPI_BIAS_GELU returns (out, pre_out)."""
+    lib = _lib.load()
+    _need(x, BF16, "x"); _need(w, BF16, "w"); _need(bias, F32, "bias"); _need(row_live, torch.uint8, "row_live")
+    M, K = x.shape
+    N, Kw = w.shape
+    if K != Kw or (row_live is not None and row_live.numel() != M):
+        raise ValueError("gemm_fwd_rows: x, w and row_live do not fit together")
+    if out is None:
+        out = torch.empty((M, N), device=x.device, dtype=BF16)
+    _need(out, BF16, "out")
+    if epilogue == EPI_BIAS_GELU and pre_out is None:
+        pre_out = torch.empty((M, N), device=x.device, dtype=BF16)
+    _need(pre_out, BF16, "pre_out")
+    ws_bytes = lib.ia_gemm_fwd_rows_workspace_bytes(M)
+    ws = torch.empty(ws_bytes, device=x.device, dtype=torch.uint8)
+    check(lib.ia_gemm_fwd_rows(x.data_ptr(), K, w.data_ptr(), K, out.data_ptr(), N, M, N, K, epilogue, ptr(bias), ptr(pre_out), scaled_cols,
+                               col_scale, ptr(row_live), int(fill), ws.data_ptr(), ws_bytes, stream_ptr()), "ia_gemm_fwd_rows")
+    if epilogue == EPI_BIAS_GELU:
+        return out, pre_out
+    return out
+
+
+def ln_fwd_rows(x, gamma, beta, eps, row_live, *, bias=None, residual=None, write_z=True, in_place=False, drop_p=0.0, seed=0, stream_id=0):
+    """ln_fwd with a row filter (ia_ln_fwd_rows): rows with row_live == 0 read nothing and leave as zeros.  in_place: z is written over x."""
+    lib = _lib.load()
+    _need(x, BF16, "x"); _need(gamma, F32, "gamma"); _need(beta, F32, "beta"); _need(bias, F32, "bias"); _need(residual, BF16, "residual")
+    _need(row_live, torch.uint8, "row_live")
+    M, H = x.shape
+    y = torch.empty_like(x)
+    z = x if in_place else (torch.empty_like(x) if write_z else None)
+    mean = torch.empty(M, device=x.device, dtype=F32)
+    rstd = torch.empty(M, device=x.device, dtype=F32)
+    check(lib.ia_ln_fwd_rows(x.data_ptr(), ptr(bias), ptr(residual), ptr(z), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                             gamma.data_ptr(), ptr(beta), M, H, eps, drop_p, seed, stream_id, ptr(row_live), stream_ptr()), "ia_ln_fwd_rows")
+    return y, z, mean, rstd
+
+
 def ln_fwd(x, gamma, beta, eps, *, bias=None, residual=None, write_z=True, drop_p=0.0, seed=0, stream_id=0):
     lib = _lib.load()
     _need(x, BF16, "x"); _need(gamma, F32, "gamma"); _need(beta, F32, "beta"); _need(bias, F32, "bias"); _need(residual, BF16, "residual")
