@@ -37,7 +37,7 @@ const char* ia_strerror(int code);
 /* Bumped whenever an entry point is added or the meaning of an argument / output changes (round 2 changed what IA_EPI_BIAS_GELU
  * stores in C2 and what IA_EPI_DGELU expects in aux): a caller built against another header must not run on this library.
  * item_alignment_amd/_lib.py refuses to load a library whose version differs from the one it was written for. */
-#define IA_ABI_VERSION 19
+#define IA_ABI_VERSION 20
 int ia_abi_version(void);
 
 /* ---- GEMM: torch.nn.Linear forward / dgrad / wgrad (src/models/text.py:1241 -> RobertaLayer dense
@@ -133,6 +133,29 @@ int ia_gemm_fwd_rows_filters(int M_rows, int N_out, int K_in);
 int ia_gemm_fwd_rows(const void* X, int ldx, const void* W, int ldw, void* Y, int ldy, int M_rows, int N_out, int K_in, int epilogue,
                      const float* bias, void* C2, int scaled_cols, float col_scale, const uint8_t* row_live, int fill_dead_rows,
                      void* workspace, size_t workspace_bytes, ia_stream_t stream);
+/* (ABI 20) The same for IA_EPI_BIAS_ADD, Y = X W^T + bias + aux (aux [M_rows, N_out] bf16, ldaux): the fc2 of a pre-LN layer with its
+ * residual.  aux is read in the blocks that hold a live row only.  Workspace and the shapes that filter: as ia_gemm_fwd_rows. */
+int ia_gemm_fwd_rows_add(const void* X, int ldx, const void* W, int ldw, void* Y, int ldy, int M_rows, int N_out, int K_in, const float* bias,
+                         const void* aux, int ldaux, const uint8_t* row_live, int fill_dead_rows, void* workspace, size_t workspace_bytes,
+                         ia_stream_t stream);
+/* (ABI 20) The group-aligned list: the layout of ia_row_blocks (same size: ia_row_groups_bytes == ia_row_blocks_bytes), the unit of liveness
+ * a GROUP of 128 rows (rows 128g .. 128g+127, clipped to M_rows).  The live list holds every 32-row block of every group that holds a live
+ * row, ascending -- entries 4i .. 4i+3 are the four blocks of one group; only the last group of M_rows may have fewer -- the dead list the
+ * blocks of the other groups.  ia_row_groups_host: the same list from host memory. */
+size_t ia_row_groups_bytes(int M_rows);
+int ia_row_groups(const uint8_t* row_live, int M_rows, int* list, ia_stream_t stream);
+int ia_row_groups_host(const uint8_t* row_live, int M_rows, int* list);
+/* (ABI 20) ia_gemm_dgrad_rows' IA_EPI_DGELU_COLSUM form with the 128-row group as the unit: a group without a live row is neither fetched
+ * nor multiplied, its rows of dX are written as zeros; every other row of dX is bit-identical to ia_gemm_bf16's, and so is C2: the kernel
+ * forms one fp32 column-sum partial per 128-row group, a kept group's partial lands in the slot the unfiltered call gives it and a left-out
+ * group's slot holds zeros, which is what its rows (all zeros by the contract) add there.  Contract, workspace
+ * (ia_gemm_dgrad_rows_workspace_bytes) and the shapes that filter (ia_gemm_dgrad_rows_filters): as ia_gemm_dgrad_rows. */
+int ia_gemm_dgrad_groups_rows(const void* dY, int ldy, const void* W, int w_kstrided, int ldw, void* dX, int ldx, int M_rows, int N_in,
+                              int K_out, const void* aux, int ldaux, void* C2, const uint8_t* row_live, void* workspace,
+                              size_t workspace_bytes, ia_stream_t stream);
+/* Diagnostics (tests, A/B runs; ABI 20): on == 0 makes the layer calls ignore ia_layer_cfg::out_row_live (every row behind the attention
+ * runs under the layer's other filter, as without it); returns the previous setting. */
+int ia_debug_out_rows(int on);
 
 /* per-launch HIP-event timing of one GEMM instantiation (variant = a_kstrided*1000 + b_kstrided*100 + epilogue*10 + c_is_f32),
  * recorded on the launch stream; used by bench.py for the roofline of the dominant kernel. */
@@ -638,6 +661,21 @@ typedef struct {
    * a caller builds the two once per step and hands them to every call.  Read only under masked_rows_dead (padded rows, post-LN). */
   const int* row_blocks;
   const uint32_t* live_ktiles;
+  /* (ABI 20) optional: a second live-row description for the part of the layer BEHIND the attention, a byte per row [B * L] (device).
+   * Non-NULL = the caller guarantees that it reads this layer's output only in rows with out_row_live != 0 and that the gradient it hands
+   * to the backward (dy, dy2) is all zeros in every other row; every such row must also be a live key.  The out-projection, the
+   * LayerNorm behind it, fc1 + GELU, fc2 and (post-LN) the closing LayerNorm then run these rows only -- GEMMs by 32-row blocks -- and so
+   * do their backward kernels; the x gelu' data gradient runs whole 128-row groups (ia_row_groups), which keeps the fc1 bias gradient
+   * bit-identical.  The QKV projection, the attention, their backward and the pre-LN LN1 keep the key-mask filter (post-LN) or every row
+   * (pre-LN): every row is a key.  y is unspecified outside out_row_live in a pre-LN layer and zeros there in a post-LN layer; dx and
+   * every parameter gradient are bit-identical to the call without it.  Padded rows only (cu_seqlens == NULL).  A stash written with
+   * out_row_live must be consumed by a backward with the same out_row_live.
+   * out_row_blocks (ia_row_blocks), out_live_ktiles (ia_ktile_mask), out_row_groups (ia_row_groups) of out_row_live: optional, NULL = the
+   * layer call builds its own in stash / scratch.  A mask that depends on (B, L) only -- row 0 of each sequence -- is built once and kept. */
+  const uint8_t* out_row_live;
+  const int* out_row_blocks;
+  const uint32_t* out_live_ktiles;
+  const int* out_row_groups;
 } ia_layer_cfg;
 
 /* per-layer activation stash (saved by forward, read by backward) and shared backward scratch */

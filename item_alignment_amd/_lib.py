@@ -28,7 +28,8 @@ class LayerCfg(C.Structure):
     _fields_ = [("B", i32), ("L", i32), ("H", i32), ("I", i32), ("nh", i32), ("pre_ln", i32), ("eps", f32),
                 ("hidden_drop", f32), ("attn_drop", f32), ("seed", u32), ("layer_id", u32), ("cu_seqlens", vp), ("total_tokens", i32),
                 ("dx_colsum_out", vp), ("dy_colsum_done", i32), ("masked_rows_dead", i32),
-                ("row_blocks", vp), ("live_ktiles", vp)]
+                ("row_blocks", vp), ("live_ktiles", vp),
+                ("out_row_live", vp), ("out_row_blocks", vp), ("out_live_ktiles", vp), ("out_row_groups", vp)]
 
 
 # name -> (restype, argtypes); must list every symbol include/itemalign.h declares
@@ -55,6 +56,12 @@ SIGNATURES = {
     "ia_gemm_fwd_rows_filters": (i32, [i32, i32, i32]),
     "ia_gemm_fwd_rows": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, i32, f32, vp, i32, vp, sz, vp]),
     "ia_debug_fwd_rows": (i32, [i32]),
+    "ia_gemm_fwd_rows_add": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp, sz, vp]),
+    "ia_row_groups_bytes": (sz, [i32]),
+    "ia_row_groups": (i32, [vp, i32, vp, vp]),
+    "ia_row_groups_host": (i32, [vp, i32, vp]),
+    "ia_gemm_dgrad_groups_rows": (i32, [vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, sz, vp]),
+    "ia_debug_out_rows": (i32, [i32]),
     "ia_prof_begin": (i32, [i32, i32]),
     "ia_prof_end": (i32, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i32)]),
     "ia_prof_bytes": (C.c_double, []),
@@ -205,7 +212,7 @@ SIGNATURES = {
 _lib = None
 
 
-ABI_VERSION = 19      # = IA_ABI_VERSION of include/itemalign.h (tests/test_cabi_symbols.py keeps the two in step)
+ABI_VERSION = 20      # = IA_ABI_VERSION of include/itemalign.h (tests/test_cabi_symbols.py keeps the two in step)
 
 
 class ItemAlignError(RuntimeError):

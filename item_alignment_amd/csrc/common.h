@@ -218,4 +218,14 @@ __attribute__((visibility("hidden"))) int ia_gemm_dgrad_blocks(const void* dY, i
 __attribute__((visibility("hidden"))) int ia_gemm_fwd_blocks(const void* X, int ldx, const void* W, int ldw, void* Y, int ldy, int M_rows, int N_out,
                                                              int K_in, int epilogue, const float* bias, void* C2, int scaled_cols, float col_scale,
                                                              const int* row_blocks, int fill_dead_rows, hipStream_t stream);
+// the same for Y = X W^T + bias + aux (IA_EPI_BIAS_ADD: the fc2 of a pre-LN layer with its residual); aux is read in the live blocks only
+__attribute__((visibility("hidden"))) int ia_gemm_fwd_blocks_add(const void* X, int ldx, const void* W, int ldw, void* Y, int ldy, int M_rows,
+                                                                 int N_out, int K_in, const float* bias, const void* aux, int ldaux,
+                                                                 const int* row_blocks, int fill_dead_rows, hipStream_t stream);
+// ia_gemm_dgrad_blocks' IA_EPI_DGELU_COLSUM form over a group-aligned list (ia_row_groups): whole 128-row groups are computed or left out, each
+// group's column-sum partial lands in the slot the dense kernel gives it, so C2 is bit-identical to ia_gemm_bf16's (dead groups add zeros)
+__attribute__((visibility("hidden"))) int ia_gemm_dgrad_groups(const void* dY, int ldy, const void* W, int w_kstrided, int ldw, void* dX, int ldx,
+                                                               int M_rows, int N_in, int K_out, const void* aux, int ldaux, void* C2,
+                                                               const int* row_groups, void* workspace, size_t workspace_bytes,
+                                                               hipStream_t stream);
 

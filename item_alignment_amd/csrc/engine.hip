@@ -32,6 +32,7 @@ struct FwdBufs {
   char* hact;   // FFN hidden activation
   float* lse; float* mean1; float* rstd1; float* mean2; float* rstd2;
   int* row_blk;  // masked_rows_dead bit 2: the forward's own 32-row block list (when the caller hands none in ia_layer_cfg::row_blocks)
+  int* out_blk;  // out_row_live: the forward's own block list of it (when the caller hands none in ia_layer_cfg::out_row_blocks)
   size_t bytes;
 };
 
@@ -53,6 +54,7 @@ FwdBufs carve_stash(const ia_layer_cfg* c, void* base) {
   s.mean1 = (float*)a.take(M * 4); s.rstd1 = (float*)a.take(M * 4);
   s.mean2 = (float*)a.take(M * 4); s.rstd2 = (float*)a.take(M * 4);
   s.row_blk = (int*)a.take(ia_row_blocks_bytes((int)M));
+  s.out_blk = (int*)a.take(ia_row_blocks_bytes((int)M));
   s.bytes = a.bytes;
   return s;
 }
@@ -70,12 +72,15 @@ FwdBufs carve_infer(const ia_layer_cfg* c, void* base) {
   s.lse = (float*)a.take((size_t)c->B * c->nh * c->L * 4);
   s.mean1 = s.mean2 = (float*)a.take(M * 4); s.rstd1 = s.rstd2 = (float*)a.take(M * 4);
   s.row_blk = (int*)a.take(ia_row_blocks_bytes((int)M));
+  s.out_blk = (int*)a.take(ia_row_blocks_bytes((int)M));
   s.bytes = a.bytes;
   return s;
 }
 
 struct Scratch {
-  char* g0; char* g1; char* g2; char* gI; char* gqkv; float* delta; char* ws; size_t ws_bytes; char* gws; size_t gws_bytes; uint32_t* live_kt; int* row_blk; size_t bytes;
+  char* g0; char* g1; char* g2; char* gI; char* gqkv; float* delta; char* ws; size_t ws_bytes; char* gws; size_t gws_bytes; uint32_t* live_kt; int* row_blk;
+  uint32_t* out_kt; int* out_blk; int* out_grp;      // out_row_live: its k-tile mask, block list and group list (when the caller hands none)
+  size_t bytes;
 };
 
 size_t max3(size_t a, size_t b, size_t c) { return a > b ? (a > c ? a : c) : (b > c ? b : c); }
@@ -98,6 +103,9 @@ Scratch carve_scratch(const ia_layer_cfg* c, void* base) {
   s.live_kt = (uint32_t*)a.take(ia_ktile_mask_bytes((int)M));
   // ... and which 32-row blocks of the data gradients do (the live list and the dead list, ia_row_blocks)
   s.row_blk = (int*)a.take(ia_row_blocks_bytes((int)M));
+  s.out_kt = (uint32_t*)a.take(ia_ktile_mask_bytes((int)M));
+  s.out_blk = (int*)a.take(ia_row_blocks_bytes((int)M));
+  s.out_grp = (int*)a.take(ia_row_groups_bytes((int)M));
   s.bytes = a.bytes;
   return s;
 }
@@ -111,6 +119,11 @@ bool cfg_ok(const ia_layer_cfg* c) {
 int g_dgrad_rows = 1;
 // ... and 0 makes layer_forward run every row under masked_rows_dead bit 2 (ia_debug_fwd_rows)
 int g_fwd_rows = 1;
+// ... and 0 makes the layer calls ignore ia_layer_cfg::out_row_live (ia_debug_out_rows)
+int g_out_rows = 1;
+// out_row_live (ia_layer_cfg): the rows the caller reads of this layer's output, and the only rows whose incoming gradient is not zero.
+// Everything behind the attention runs these rows only; in front of it every row is a key and stays.  Padded rows only.
+const uint8_t* out_live(const ia_layer_cfg* c) { return (c->out_row_live && !c->cu_seqlens && g_out_rows) ? c->out_row_live : nullptr; }
 
 #define IA_TRY(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
 
@@ -118,7 +131,9 @@ int g_fwd_rows = 1;
 // provides one (both operands k-contiguous: the faster form, ia_layer_weights::wt_*), else W read k-strided.
 // With a block list (ia_row_blocks), over the 32-row blocks that hold a live row only; the other rows of dx are written as zeros.
 int dgrad(const void* dy, int k_out, const void* w, const void* wt, int n_in, void* dx, int M, int epilogue, const void* aux, int ldaux, void* c2,
-          void* ws, size_t ws_bytes, ia_stream_t st, const int* row_blk = nullptr) {
+          void* ws, size_t ws_bytes, ia_stream_t st, const int* row_blk = nullptr, const int* row_grp = nullptr) {
+  if (row_grp && epilogue == IA_EPI_DGELU_COLSUM)      // whole 128-row groups: the column sums keep the dense kernel's partials
+    return ia_gemm_dgrad_groups(dy, k_out, wt ? wt : w, wt ? 0 : 1, wt ? k_out : n_in, dx, n_in, M, n_in, k_out, aux, ldaux, c2, row_grp, ws, ws_bytes, st);
   if (row_blk)
     return ia_gemm_dgrad_blocks(dy, k_out, wt ? wt : w, wt ? 0 : 1, wt ? k_out : n_in, dx, n_in, M, n_in, k_out, epilogue, aux, ldaux, c2, row_blk,
                                 ws, ws_bytes, st);
@@ -194,7 +209,7 @@ int layer_forward(const ia_layer_cfg* c, const ia_layer_weights* w, const void* 
     // Zeros are written where somebody reads every row: q / k / v (the attention kernels), the FFN activation and its derivative (the
     // fc2 weight gradient's partly live k-tiles, the every-row x gelu' epilogue).  The two projection outputs in front of the LayerNorms
     // are not filled: only their LayerNorm reads them, which skips the dead rows and, in the training form, overwrites them in place.
-    const uint8_t* const live = ((c->masked_rows_dead & 3) == 3 && !c->cu_seqlens && key_mask && g_fwd_rows) ? key_mask : nullptr;
+    const uint8_t* live = ((c->masked_rows_dead & 3) == 3 && !c->cu_seqlens && key_mask && g_fwd_rows) ? key_mask : nullptr;
     const int* row_blk = nullptr;
     if (live) {
       row_blk = c->row_blocks;
@@ -203,6 +218,14 @@ int layer_forward(const ia_layer_cfg* c, const ia_layer_weights* w, const void* 
     // qkv = x Wqkv^T + b
     IA_TRY(qkv_proj(c, x, w, s.qkv, M, scale, st, row_blk));
     IA_TRY(attn_fwd(c, s.qkv, key_mask, s.ctx, s.lse, scale, attn_drop, attn_seed, st));
+    // out_row_live: behind the attention only the rows the caller reads are live (a subset of the live keys) -- the same rules with that
+    // mask and its block list: the LayerNorms leave zeros in the other rows (so y1 and, in the training form, z1 / z2 are finite in every
+    // row a partly live k-tile of a weight gradient touches), fc1 fills the other blocks of the activation and its derivative
+    if (const uint8_t* const olive = out_live(c)) {
+      live = olive;
+      row_blk = c->out_row_blocks;
+      if (!row_blk) { IA_TRY(ia_row_blocks(olive, M, s.out_blk, st)); row_blk = s.out_blk; }
+    }
     // z1 = x + dropout(ctx Wo^T + b_o); y1 = LN1(z1)
     if (row_blk) IA_TRY(ia_gemm_fwd_blocks(s.ctx, H, w->w_o, H, s.proj, H, M, H, H, IA_EPI_NONE, nullptr, nullptr, 0, 1.f, row_blk, 0, st));
     else IA_TRY(ia_gemm_bf16(s.ctx, 0, H, w->w_o, 0, H, s.proj, 0, H, M, H, H, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, st));
@@ -222,10 +245,25 @@ int layer_forward(const ia_layer_cfg* c, const ia_layer_weights* w, const void* 
     IA_TRY(attn_fwd(c, s.qkv, key_mask, s.ctx, s.lse, scale, 0.f, 0, st));
     // x1 = x + ctx Wo^T + b_o and LN2(x1): the bias and the residual are added by the LayerNorm kernel (it streams the rows anyway),
     // so the projection keeps the plain epilogue; proj receives x1 in place of the raw projection (the fc2 epilogue's residual)
-    IA_TRY(ia_gemm_bf16(s.ctx, 0, H, w->w_o, 0, H, s.proj, 0, H, M, H, H, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, st));
-    IA_TRY(ia_ln_fwd(s.proj, w->b_o, x, s.proj, s.ln, s.mean2, s.rstd2, w->ln2_g, w->ln2_b, M, H, c->eps, 0.f, 0, 0, st));
-    IA_TRY(ia_gemm_bf16(s.ln, 0, H, w->w_fc1, 0, H, s.hact, 0, I, M, I, H, gelu, w->b_fc1, nullptr, 0, s.hpre, 0, nullptr, 0, st));
-    IA_TRY(ia_gemm_bf16(s.hact, 0, I, w->w_fc2, 0, I, y, 0, H, M, H, I, IA_EPI_BIAS_ADD, w->b_fc2, s.proj, H, nullptr, 0, nullptr, 0, st));
+    // out_row_live (the last block under a head that reads [CLS] only): the out-projection, LN2, fc1 and fc2 run the 32-row blocks / rows
+    // the caller reads.  LN2 leaves zeros in the other rows of x1 and LN2(x1), fc1 fills the other blocks of the activation and its
+    // derivative (the weight gradients' partly live k-tiles and the x gelu' epilogue read them); y is not written outside the live blocks.
+    const uint8_t* const olive = out_live(c);
+    const int* oblk = nullptr;
+    if (olive) {
+      oblk = c->out_row_blocks;
+      if (!oblk) { IA_TRY(ia_row_blocks(olive, M, s.out_blk, st)); oblk = s.out_blk; }
+    }
+    if (oblk) IA_TRY(ia_gemm_fwd_blocks(s.ctx, H, w->w_o, H, s.proj, H, M, H, H, IA_EPI_NONE, nullptr, nullptr, 0, 1.f, oblk, 0, st));
+    else IA_TRY(ia_gemm_bf16(s.ctx, 0, H, w->w_o, 0, H, s.proj, 0, H, M, H, H, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, st));
+    IA_TRY(ia_ln_fwd_rows(s.proj, w->b_o, x, s.proj, s.ln, s.mean2, s.rstd2, w->ln2_g, w->ln2_b, M, H, c->eps, 0.f, 0, 0, olive, st));
+    if (oblk) {
+      IA_TRY(ia_gemm_fwd_blocks(s.ln, H, w->w_fc1, H, s.hact, I, M, I, H, gelu, w->b_fc1, s.hpre, 0, 1.f, oblk, 1, st));
+      IA_TRY(ia_gemm_fwd_blocks_add(s.hact, I, w->w_fc2, I, y, H, M, H, I, w->b_fc2, s.proj, H, oblk, 0, st));
+    } else {
+      IA_TRY(ia_gemm_bf16(s.ln, 0, H, w->w_fc1, 0, H, s.hact, 0, I, M, I, H, gelu, w->b_fc1, nullptr, 0, s.hpre, 0, nullptr, 0, st));
+      IA_TRY(ia_gemm_bf16(s.hact, 0, I, w->w_fc2, 0, I, y, 0, H, M, H, I, IA_EPI_BIAS_ADD, w->b_fc2, s.proj, H, nullptr, 0, nullptr, 0, st));
+    }
   }
   return IA_OK;
 }
@@ -235,6 +273,12 @@ int layer_forward(const ia_layer_cfg* c, const ia_layer_weights* w, const void* 
 extern "C" int ia_debug_fwd_rows(int on) {
   const int was = g_fwd_rows;
   g_fwd_rows = on ? 1 : 0;
+  return was;
+}
+
+extern "C" int ia_debug_out_rows(int on) {
+  const int was = g_out_rows;
+  g_out_rows = on ? 1 : 0;
   return was;
 }
 
@@ -303,6 +347,17 @@ extern "C" int ia_layer_bwd2(const ia_layer_cfg* c, const ia_layer_weights* w, c
   const float scale = 0.125f;
   const uint32_t attn_seed = c->seed * 2654435761u + c->layer_id * 97u + 17u;
   const bool drop = c->hidden_drop > 0.f;
+  // out_row_live: the incoming gradient is zero outside these rows, so every gradient in front of the attention backward is too.  Its
+  // k-tile mask, block list and group list (the caller's, or built here) filter the kernels from the LN2 backward to the out-projection's
+  // gradients; the attention backward and the QKV gradients keep the layer's other filter (every row is a key).
+  const uint8_t* const olive = out_live(c);
+  const uint32_t* okt = nullptr; const int* oblk = nullptr; const int* ogrp = nullptr;
+  if (olive) {
+    okt = c->out_live_ktiles; oblk = c->out_row_blocks; ogrp = c->out_row_groups;
+    if (!okt) { IA_TRY(ia_ktile_mask(olive, M, k.out_kt, st)); okt = k.out_kt; }
+    if (!oblk) { IA_TRY(ia_row_blocks(olive, M, k.out_blk, st)); oblk = k.out_blk; }
+    if (!ogrp) { IA_TRY(ia_row_groups(olive, M, k.out_grp, st)); ogrp = k.out_grp; }
+  }
   if (!c->pre_ln) {
     // masked_rows_dead: every gradient row of a masked position is exactly zero (ia_layer_cfg): the LayerNorm backward kernels skip them,
     // the four weight gradients skip the 64-row k-tiles that hold nothing else (one bitmask per call, in scratch), and the three plain data
@@ -315,27 +370,33 @@ extern "C" int ia_layer_bwd2(const ia_layer_cfg* c, const ia_layer_weights* w, c
     const int* const row_blk = (live && g_dgrad_rows) ? (c->row_blocks ? c->row_blocks : k.row_blk) : nullptr;
     if (live && !c->live_ktiles) IA_TRY(ia_ktile_mask(live, M, k.live_kt, st));
     if (row_blk && !c->row_blocks) IA_TRY(ia_row_blocks(live, M, k.row_blk, st));
+    // behind the attention: out_row_live's lists when given (a subset of the live keys), else the key mask's
+    const uint8_t* const live2 = olive ? olive : live;
+    const uint32_t* const kt2 = olive ? okt : live_kt;
+    const int* const blk2 = olive ? oblk : row_blk;
     // The two residual additions of a post-LN layer make each LayerNorm output's gradient a sum of two terms; both LayerNorm
     // backward kernels take the two terms (ia_ln_bwd2), so the GEMMs in front of them keep the plain epilogue.
     // LN2 backward: d(output) = dy (+ dy2) -> dz2 in g0, masked branch gradient -> g1 (or g0 when p == 0)
     IA_TRY(ia_ln_bwd2_rows(dy, dy2, nullptr, s.ffn, s.mean2, s.rstd2, w->ln2_g, k.g0, drop ? k.g1 : nullptr, g->ln2_g, g->ln2_b, g->b_fc2, M, H,
-                           c->hidden_drop, c->seed, c->layer_id * 4u + 1u, live, k.ws, k.ws_bytes, 1, st));
+                           c->hidden_drop, c->seed, c->layer_id * 4u + 1u, live2, k.ws, k.ws_bytes, 1, st));
     const char* d_ffn = drop ? k.g1 : k.g0;
-    IA_TRY(wgrad(d_ffn, H, s.hact, I, (float*)g->w_fc2, M, live_kt, k.gws, k.gws_bytes, st));
-    // d(pre-activation) = (d_ffn W2) * gelu'(pre), and its column sums (the fc1 bias gradient) out of the same epilogue
-    // (every row, although the remapped kernel serves this epilogue: its column-sum partials would cover other rows, and the fc1 bias
-    // gradient would equal the unfiltered one only up to fp32 summation order -- the backward stays bit-identical to masked_rows_dead = 0)
-    IA_TRY(dgrad(d_ffn, H, w->w_fc2, w->wt_fc2, I, k.gI, M, IA_EPI_DGELU_COLSUM, s.hpre, I, g->b_fc1, k.ws, k.ws_bytes, st));
-    IA_TRY(wgrad(k.gI, I, s.ln, H, (float*)g->w_fc1, M, live_kt, k.gws, k.gws_bytes, st));
-    IA_TRY(dgrad(k.gI, I, w->w_fc1, w->wt_fc1, H, k.g2, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, row_blk));
+    IA_TRY(wgrad(d_ffn, H, s.hact, I, (float*)g->w_fc2, M, kt2, k.gws, k.gws_bytes, st));
+    // d(pre-activation) = (d_ffn W2) * gelu'(pre), and its column sums (the fc1 bias gradient) out of the same epilogue.
+    // ogrp == NULL: every row.  The block remap serves this epilogue, but its column-sum partials would cover other rows and the fc1 bias
+    // gradient would equal the unfiltered one only up to fp32 summation order; the backward stays bit-identical to masked_rows_dead = 0.
+    // ogrp (out_row_live): whole 128-row groups drop out, which leaves every kept partial where and what it was (ia_gemm_dgrad_groups).
+    IA_TRY(dgrad(d_ffn, H, w->w_fc2, w->wt_fc2, I, k.gI, M, IA_EPI_DGELU_COLSUM, s.hpre, I, g->b_fc1, k.ws, k.ws_bytes, st, nullptr, ogrp));
+    IA_TRY(wgrad(k.gI, I, s.ln, H, (float*)g->w_fc1, M, kt2, k.gws, k.gws_bytes, st));
+    IA_TRY(dgrad(k.gI, I, w->w_fc1, w->wt_fc1, H, k.g2, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, blk2));
     // LN1 backward: d(y1) = g2 (through fc1) + g0 (residual into LN2) -> dz1 (the layer input's residual-path gradient) in
     // dz1buf: the caller's dx2 when the split form is wanted, else g0 (in place over the term just consumed)
     char* dz1buf = dx2 ? (char*)dx2 : k.g0;
     IA_TRY(ia_ln_bwd2_rows(k.g2, k.g0, nullptr, s.proj, s.mean1, s.rstd1, w->ln1_g, dz1buf, drop ? k.g1 : nullptr, g->ln1_g, g->ln1_b, g->b_o, M, H,
-                           c->hidden_drop, c->seed, c->layer_id * 4u + 0u, live, k.ws, k.ws_bytes, 1, st));
+                           c->hidden_drop, c->seed, c->layer_id * 4u + 0u, live2, k.ws, k.ws_bytes, 1, st));
     const char* d_att = drop ? k.g1 : dz1buf;
-    IA_TRY(wgrad(d_att, H, s.ctx, H, (float*)g->w_o, M, live_kt, k.gws, k.gws_bytes, st));
-    IA_TRY(dgrad(d_att, H, w->w_o, w->wt_o, H, k.g2, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, row_blk));
+    IA_TRY(wgrad(d_att, H, s.ctx, H, (float*)g->w_o, M, kt2, k.gws, k.gws_bytes, st));
+    // (d_ctx and dz1 are zeros outside out_row_live: the attention backward and the QKV data gradient's "+ dz1" read every live key's row)
+    IA_TRY(dgrad(d_att, H, w->w_o, w->wt_o, H, k.g2, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, blk2));
     IA_TRY(attn_bwd(c, s.qkv, key_mask, s.ctx, k.g2, s.lse, k.delta, k.gqkv, g->b_qkv, k.ws, k.ws_bytes, scale, c->attn_drop, attn_seed, st));
     IA_TRY(wgrad(k.gqkv, 3 * H, x, H, (float*)g->w_qkv, M, live_kt, k.gws, k.gws_bytes, st));
     if (dx2)   // split form: dx = the attention sub-block's data gradient, dx2 = dz1 (already written)
@@ -344,15 +405,17 @@ extern "C" int ia_layer_bwd2(const ia_layer_cfg* c, const ia_layer_weights* w, c
       IA_TRY(dgrad(k.gqkv, 3 * H, w->w_qkv, w->wt_qkv, H, dx, M, IA_EPI_ADD, dz1buf, H, nullptr, nullptr, 0, st, row_blk));
   } else {
     if (!c->dy_colsum_done) IA_TRY(ia_colsum(dy, H, M, H, g->b_fc2, 1, k.ws, k.ws_bytes, st));
-    IA_TRY(ia_gemm_bf16(dy, 1, H, s.hact, 1, I, g->w_fc2, 1, I, H, I, M, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 1, k.gws, k.gws_bytes, st));
-    IA_TRY(dgrad(dy, H, w->w_fc2, w->wt_fc2, I, k.gI, M, IA_EPI_DGELU_COLSUM, s.hpre, I, g->b_fc1, k.ws, k.ws_bytes, st));
-    IA_TRY(ia_gemm_bf16(k.gI, 1, I, s.ln, 1, H, g->w_fc1, 1, H, I, H, M, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 1, k.gws, k.gws_bytes, st));
-    IA_TRY(dgrad(k.gI, I, w->w_fc1, w->wt_fc1, H, k.g0, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st));
+    // (okt / oblk / ogrp are NULL without out_row_live: the helpers then make the plain every-row calls)
+    IA_TRY(wgrad(dy, H, s.hact, I, (float*)g->w_fc2, M, okt, k.gws, k.gws_bytes, st));
+    IA_TRY(dgrad(dy, H, w->w_fc2, w->wt_fc2, I, k.gI, M, IA_EPI_DGELU_COLSUM, s.hpre, I, g->b_fc1, k.ws, k.ws_bytes, st, nullptr, ogrp));
+    IA_TRY(wgrad(k.gI, I, s.ln, H, (float*)g->w_fc1, M, okt, k.gws, k.gws_bytes, st));
+    IA_TRY(dgrad(k.gI, I, w->w_fc1, w->wt_fc1, H, k.g0, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, oblk));
     // LN2 backward (+ residual path dy) -> g1 = d x2 ; its column sum is the proj-bias gradient
-    IA_TRY(ia_ln_bwd(k.g0, dy, s.proj, s.mean2, s.rstd2, w->ln2_g, k.g1, nullptr, g->ln2_g, g->ln2_b, g->b_o, M, H, 0.f, 0, 0, k.ws,
-                     k.ws_bytes, 1, st));
-    IA_TRY(ia_gemm_bf16(k.g1, 1, H, s.ctx, 1, H, g->w_o, 1, H, H, H, M, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 1, k.gws, k.gws_bytes, st));
-    IA_TRY(dgrad(k.g1, H, w->w_o, w->wt_o, H, k.g2, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st));
+    // (the row-filtered launch keeps every row's place in the partial sums: leaving out rows that add exact zeros changes no bit)
+    IA_TRY(ia_ln_bwd2_rows(k.g0, nullptr, dy, s.proj, s.mean2, s.rstd2, w->ln2_g, k.g1, nullptr, g->ln2_g, g->ln2_b, g->b_o, M, H, 0.f, 0, 0, olive,
+                           k.ws, k.ws_bytes, 1, st));
+    IA_TRY(wgrad(k.g1, H, s.ctx, H, (float*)g->w_o, M, okt, k.gws, k.gws_bytes, st));
+    IA_TRY(dgrad(k.g1, H, w->w_o, w->wt_o, H, k.g2, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, oblk));
     IA_TRY(attn_bwd(c, s.qkv, key_mask, s.ctx, k.g2, s.lse, k.delta, k.gqkv, g->b_qkv, k.ws, k.ws_bytes, scale, 0.f, 0, st));
     IA_TRY(ia_gemm_bf16(k.gqkv, 1, 3 * H, s.xn, 1, H, g->w_qkv, 1, H, 3 * H, H, M, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 1, k.gws, k.gws_bytes, st));
     IA_TRY(dgrad(k.gqkv, 3 * H, w->w_qkv, w->wt_qkv, H, k.g0, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st));

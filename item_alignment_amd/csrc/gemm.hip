@@ -48,8 +48,8 @@ constexpr int EPI_NONE_LIVE = 8;
 // (e = EPI_NONE, EPI_ADD or EPI_DGELU_CS) has the token rows as M: a row of dY that is all zeros gives a row of zeros, so only the 32-row
 // blocks that hold a live row are computed -- an M-tile is eight consecutive entries of the live-block list (GemmArgs::row_blk) instead
 // of 256 consecutive rows -- and the dead blocks are written as zeros by a fill launch.  No live row's arithmetic changes.
-// The forward forms (e = EPI_NONE, EPI_BIAS with qcols / qscale, EPI_BIAS_GELU with both outputs, EPI_BIAS_GELU_ACT; both operands
-// k-contiguous) skip the blocks whose rows nobody reads (padded positions under ia_layer_cfg::masked_rows_dead bit 2); there the fill is
+// The forward forms (e = EPI_NONE, EPI_BIAS with qcols / qscale, EPI_BIAS_GELU with both outputs, EPI_BIAS_GELU_ACT, EPI_BIAS_ADD; both
+// operands k-contiguous) skip the blocks whose rows nobody reads (padded positions under ia_layer_cfg::masked_rows_dead bit 2); there the fill is
 // the caller's choice (GemmArgs::rows_fill): without it the dead blocks of C / C2 are not written at all.
 constexpr int EPI_ROWS = 16;
 // EPI_BIAS_GELU_ACT: the forward-only form of EPI_BIAS_GELU (activation only: no derivative is evaluated or stored)
@@ -103,6 +103,10 @@ struct GemmArgs {
   // EPI_ROWS + EPI_BIAS: every wave takes the row-layout epilogue, (acc + bias) * qscale -- the launch over the rows behind the last whole
   // 128-row part of M, which the dense kernel rounds that way (gemm_core)
   int rows_guarded;
+  // EPI_ROWS + EPI_DGELU_CS: the list is group-aligned (ia_row_groups: entries 4i .. 4i+3 are the four 32-row blocks of ONE 128-row group,
+  // so a wave's four block slots are one group in order) and the wave writes its column-sum partial to THAT group's slot of csum_part,
+  // where the dense kernel puts it: the second stage then adds the same fp32 terms in the same places (dead groups' slots are zeroed)
+  int rows_grouped;
 };
 
 // One slot per launch in flight (launches of different streams may overlap; a slot comes round again after CTR_SLOTS launches).
@@ -1209,8 +1213,13 @@ IA_DEV void drain_half(const GemmArgs& p, f32x16 (&acc)[4][4], int m0, int n0, c
         v = ia_add_xor32(ia_add_xor16(v));                                                      // lane ^ 16, lane ^ 32 (common.h)
         cs[r] = v;
       }
-      if (rrow == 0 && n0 + c8 * 8 < p.N) {      // lanes 0..7: 8 consecutive columns each (two 16-byte stores, counted in PEND)
-        float* dst = p.csum_part + (size_t)(m0 >> 7) * p.N + n0 + c8 * 8;
+      int slot = m0 >> 7;
+      bool has_slot = true;
+      if constexpr (ROWS) {      // group-aligned list: the slot of the group itself (none for a wave whose four blocks do not exist)
+        if (p.rows_grouped) { slot = rb.r[0] >> 7; has_slot = rb.r[0] >= 0; }
+      }
+      if (rrow == 0 && n0 + c8 * 8 < p.N && has_slot) {      // lanes 0..7: 8 consecutive columns each (two 16-byte stores, counted in PEND)
+        float* dst = p.csum_part + (size_t)slot * p.N + n0 + c8 * 8;
         gstore16(dst, f32x4{cs[0], cs[1], cs[2], cs[3]});
         gstore16(dst + 4, f32x4{cs[4], cs[5], cs[6], cs[7]});
       }
@@ -1229,7 +1238,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
   constexpr bool GUARDABLE = ROWS && EPI == EPI_BIAS;      // (tile_blocks)
   static_assert(!LIVE || (AKS && BKS && OUTF32), "live k-tiles: the weight-gradient form only");
   static_assert(!ROWS || (!AKS && !OUTF32 && (EPI == EPI_NONE || EPI == EPI_ADD || EPI == EPI_DGELU_CS ||
-                                              (!BKS && (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_GELU_ACT)))),
+                                              (!BKS && (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_GELU_ACT || EPI == EPI_BIAS_ADD)))),
                 "row remap: the data-gradient forms and the k-contiguous forward forms only");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane0 = tid & 63;
@@ -1851,8 +1860,10 @@ uint32_t* next_ctr_slot() {
 // EPI_ROWS launches: the rows of the dead 32-row blocks of C (bf16 [M, N], N a multiple of 8) written as zeros -- not every consumer of a
 // data gradient filters its rows -- and, with column-sum partials, the partial rows behind the last remapped M-tile (the second stage
 // sums a row count the host knows: one pair per 256 rows of M).  Dead blocks and partial rows are dealt out over the grid.
+// grouped (a group-aligned list, GemmArgs::rows_grouped): the partial rows zeroed are the slots of the dead 128-row groups (the first block of
+// each names it) and the slots behind the last group of M.
 __global__ __launch_bounds__(256) void zero_dead_rows_kernel(const int* __restrict__ list, bf16* __restrict__ C, int ldc, int M, int N,
-                                                             float* __restrict__ csum_part, int part_rows) {
+                                                             float* __restrict__ csum_part, int part_rows, int grouped = 0) {
   const int n_live = list[0], n_dead = list[1], nbr = (list[2] + 7) & ~7;
   const int* dead = list + t256w::ROW_BLK_HDR + nbr;
   const int n8 = N >> 3;
@@ -1864,7 +1875,14 @@ __global__ __launch_bounds__(256) void zero_dead_rows_kernel(const int* __restri
       if (r < M) *reinterpret_cast<u32x4*>(C + (size_t)r * ldc + c) = z;
     }
   }
-  if (csum_part) {
+  if (csum_part && grouped) {
+    const int ngrp = (M + 127) >> 7;
+    for (int d = blockIdx.x; d < n_dead + (part_rows - ngrp); d += gridDim.x) {
+      const int g = d < n_dead ? ((dead[d] & 3) ? -1 : dead[d] >> 2) : ngrp + (d - n_dead);
+      if (g < 0) continue;
+      for (int i = threadIdx.x; i < N; i += 256) csum_part[(size_t)g * N + i] = 0.f;
+    }
+  } else if (csum_part) {
     const int first = ((n_live + 7) >> 3) * 2;
     const size_t total = part_rows > first ? (size_t)(part_rows - first) * N : 0;
     float* base = csum_part + (size_t)first * N;
@@ -1877,7 +1895,7 @@ int launch(GemmArgs a, bool big, hipStream_t st) {
   constexpr int vid = AKS * 1000 + BKS * 100 + EPI * 10 + (OUTF32 ? 1 : 0);
   // the forms that may carry a block list (GemmArgs::row_blk): the data gradients, and the forward epilogues on k-contiguous operands
   constexpr bool DROWS = !AKS && !OUTF32 && (EPI == EPI_NONE || EPI == EPI_ADD || EPI == EPI_DGELU_CS ||
-                                             (!BKS && (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_GELU_ACT)));
+                                             (!BKS && (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_GELU_ACT || EPI == EPI_BIAS_ADD)));
   // (a launch over the live k-tiles only is not recorded: the host cannot know how many k-tiles it executed, and the recorded FLOPs are
   // those of launches that executed all of theirs)
   constexpr bool WGRAD = AKS && BKS && EPI == EPI_NONE && OUTF32;      // the form that may carry a live-k-tile mask (GemmArgs::live_kt)
@@ -1910,7 +1928,8 @@ int launch(GemmArgs a, bool big, hipStream_t st) {
         else kern = t256w::gemm_kernel<false, BKS, EPI_ROWS + EPI, false>;
         la = la == 1 ? 4 : 3;
         if (a.rows_fill)
-          hipLaunchKernelGGL(zero_dead_rows_kernel, dim3(1024), dim3(256), 0, st, a.row_blk, (bf16*)a.C, a.ldc, a.fill_m, a.N, a.csum_part, ((a.M + 255) / 256) * 2);
+          hipLaunchKernelGGL(zero_dead_rows_kernel, dim3(1024), dim3(256), 0, st, a.row_blk, (bf16*)a.C, a.ldc, a.fill_m, a.N, a.csum_part, ((a.M + 255) / 256) * 2,
+                             a.rows_grouped);
         if (a.rows_fill && EPI == EPI_BIAS_GELU)
           hipLaunchKernelGGL(zero_dead_rows_kernel, dim3(1024), dim3(256), 0, st, a.row_blk, a.C2, a.ldc, a.fill_m, a.N, (float*)nullptr, 0);
       }
@@ -1956,7 +1975,8 @@ extern "C" size_t ia_gemm_workspace_bytes(int M, int N, int K, int c_is_f32) {
 static int gemm_core(const void* A, int a_kstrided, int lda, const void* B, int b_kstrided, int ldb, void* C, int c_is_f32, int ldc, int M,
                      int N, int K, int epilogue, const float* bias, const void* aux, int ldaux, void* C2, int accumulate, void* workspace,
                      size_t workspace_bytes, const IaViewGemm* view, hipStream_t stream, int qcols = 0, float qscale = 1.f,
-                     const uint32_t* live_kt = nullptr, const int* row_blocks = nullptr, int rows_fill = 1, int tail_of = 0);      // tail_of: below
+                     const uint32_t* live_kt = nullptr, const int* row_blocks = nullptr, int rows_fill = 1, int tail_of = 0,      // tail_of: below
+                     int rows_grouped = 0);
 
 // workspace of an IA_EPI_DGELU_COLSUM GEMM: one fp32 row of N partial sums per 128-row block of the output (and never less than
 // the stand-alone column-sum kernel needs, which small shapes fall back to)
@@ -1989,12 +2009,15 @@ static bool dgrad_rows_fit(int M, int lda, int ldc, int ldaux) {
   return rows * lda * 2 < lim && rows * ldc * 2 < lim && rows * (uint64_t)ldaux * 2 < lim && !(ldc & 7) && !(ldaux & 7);
 }
 // block t = rows 32t .. 32t+31 (clipped to M): live = any row_live set.  One function for the device kernel and the host entry.
-static __host__ __device__ inline bool row_block_live(const uint8_t* row_live, int M, int t) {
-  const uint8_t* r = row_live + (size_t)t * 32;
-  const int n = M - t * 32 < 32 ? M - t * 32 : 32;
+// gshift = 2 (ia_row_groups): live = any row_live set in the block's 128-row GROUP (rows 128 (t >> 2) .. + 127, clipped to M), so the live
+// blocks come as the four blocks of each live group.
+static __host__ __device__ inline bool row_block_live(const uint8_t* row_live, int M, int t, int gshift = 0) {
+  const int len = 32 << gshift, r0 = (t >> gshift) * len;
+  const uint8_t* r = row_live + (size_t)r0;
+  const int n = M - r0 < len ? M - r0 : len;
   uint64_t any = 0;
-  if (n == 32 && ((uintptr_t)r & 7) == 0) {
-    for (int i = 0; i < 4; ++i) any |= reinterpret_cast<const uint64_t*>(r)[i];
+  if (n == len && ((uintptr_t)r & 7) == 0) {
+    for (int i = 0; i < len / 8; ++i) any |= reinterpret_cast<const uint64_t*>(r)[i];
   } else {
     for (int i = 0; i < n; ++i) any |= r[i];
   }
@@ -2006,7 +2029,7 @@ inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 // a CU's LDS).  Lane l looks at blocks 64i + l: first the flags of up to 64 rounds i are gathered into one 64-bit word per lane (loads
 // only, so they overlap), then every round is one ballot: a block's place in the live list is the number of live blocks in front of it,
 // in the dead list the number of dead ones (t minus that).
-__global__ __launch_bounds__(64) void row_blocks_kernel(const uint8_t* __restrict__ row_live, int M, int nb, int* __restrict__ out) {
+__global__ __launch_bounds__(64) void row_blocks_kernel(const uint8_t* __restrict__ row_live, int M, int nb, int* __restrict__ out, int gshift) {
   const int nbr = (nb + 7) & ~7;
   int* const live = out + t256w::ROW_BLK_HDR;
   int* const dead = live + nbr;
@@ -2017,7 +2040,7 @@ __global__ __launch_bounds__(64) void row_blocks_kernel(const uint8_t* __restric
 #pragma unroll 8
     for (int i = 0; i < 64; ++i) {
       const int t = c0 + i * 64 + lane;
-      if (t < nb && row_block_live(row_live, M, t)) flags |= 1ull << i;
+      if (t < nb && row_block_live(row_live, M, t, gshift)) flags |= 1ull << i;
     }
     for (int i = 0; i < 64 && c0 + i * 64 < nb; ++i) {
       const int t = c0 + i * 64 + lane;
@@ -2040,22 +2063,34 @@ extern "C" size_t ia_row_blocks_bytes(int M_rows) {
 extern "C" int ia_row_blocks(const uint8_t* row_live, int M_rows, int* list, hipStream_t stream) {
   (void)hipGetLastError();
   if (!row_live || !list || M_rows <= 0 || ((uintptr_t)list & 31)) return IA_ERR_ARG;
-  hipLaunchKernelGGL(row_blocks_kernel, dim3(1), dim3(64), 0, stream, row_live, M_rows, (M_rows + 31) / 32, list);
+  hipLaunchKernelGGL(row_blocks_kernel, dim3(1), dim3(64), 0, stream, row_live, M_rows, (M_rows + 31) / 32, list, 0);
   return ia_check_launch();
 }
-extern "C" int ia_row_blocks_host(const uint8_t* row_live, int M_rows, int* list) {
+static int row_blocks_host(const uint8_t* row_live, int M_rows, int* list, int gshift) {
   if (!row_live || !list || M_rows <= 0) return IA_ERR_ARG;
   const int nb = (M_rows + 31) / 32, nbr = (nb + 7) & ~7;
   int* const live = list + t256w::ROW_BLK_HDR;
   int* const dead = live + nbr;
   int n_live = 0;
   for (int t = 0; t < nb; ++t) {
-    if (row_block_live(row_live, M_rows, t)) live[n_live++] = t; else dead[t - n_live] = t;
+    if (row_block_live(row_live, M_rows, t, gshift)) live[n_live++] = t; else dead[t - n_live] = t;
   }
   for (int i = 0; i < t256w::ROW_BLK_HDR; ++i) list[i] = 0;
   list[0] = n_live; list[1] = nb - n_live; list[2] = nb;
   return IA_OK;
 }
+extern "C" int ia_row_blocks_host(const uint8_t* row_live, int M_rows, int* list) { return row_blocks_host(row_live, M_rows, list, 0); }
+// The group-aligned list (ABI 20): the layout of ia_row_blocks, the unit of liveness a 128-row group -- every block of a group that holds a
+// live row is listed (in order, so entries 4i .. 4i+3 are one group; only the last group of M may have fewer), the blocks of the other
+// groups are the dead list.
+extern "C" size_t ia_row_groups_bytes(int M_rows) { return ia_row_blocks_bytes(M_rows); }
+extern "C" int ia_row_groups(const uint8_t* row_live, int M_rows, int* list, hipStream_t stream) {
+  (void)hipGetLastError();
+  if (!row_live || !list || M_rows <= 0 || ((uintptr_t)list & 31)) return IA_ERR_ARG;
+  hipLaunchKernelGGL(row_blocks_kernel, dim3(1), dim3(64), 0, stream, row_live, M_rows, (M_rows + 31) / 32, list, 2);
+  return ia_check_launch();
+}
+extern "C" int ia_row_groups_host(const uint8_t* row_live, int M_rows, int* list) { return row_blocks_host(row_live, M_rows, list, 2); }
 // library-internal (common.h): the data gradient with a list already built (ia_layer_bwd2 builds one per call for its four)
 int ia_gemm_dgrad_blocks(const void* dY, int ldy, const void* W, int w_kstrided, int ldw, void* dX, int ldx, int M_rows, int N_in, int K_out,
                          int epilogue, const void* aux, int ldaux, void* C2, const int* row_blocks, void* workspace, size_t workspace_bytes,
@@ -2070,6 +2105,41 @@ int ia_gemm_fwd_blocks(const void* X, int ldx, const void* W, int ldw, void* Y, 
   if (epilogue != EPI_NONE && epilogue != EPI_BIAS && epilogue != EPI_BIAS_GELU && epilogue != EPI_BIAS_GELU_ACT) return IA_ERR_UNSUPPORTED;
   return gemm_core(X, 0, ldx, W, 0, ldw, Y, 0, ldy, M_rows, N_out, K_in, epilogue, bias, nullptr, 0, C2, 0, nullptr, 0, nullptr, stream, scaled_cols,
                    col_scale, nullptr, row_blocks, fill_dead_rows);
+}
+// library-internal (common.h): the x gelu' + column-sums data gradient over the live 128-row groups (a list ia_row_groups built): the
+// column-sum partials land where the dense kernel puts them, so C2 is bit-identical to the unfiltered call's on rows that keep the contract
+int ia_gemm_dgrad_groups(const void* dY, int ldy, const void* W, int w_kstrided, int ldw, void* dX, int ldx, int M_rows, int N_in, int K_out,
+                         const void* aux, int ldaux, void* C2, const int* row_groups, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  return gemm_core(dY, 0, ldy, W, w_kstrided, ldw, dX, 0, ldx, M_rows, N_in, K_out, EPI_DGELU_CS, nullptr, aux, ldaux, C2, 0, workspace,
+                   workspace_bytes, nullptr, stream, 0, 1.f, nullptr, row_groups, 1, 0, 1);
+}
+// library-internal (common.h): Y = X W^T + bias + aux over the live 32-row blocks (the fc2 of a pre-LN layer, bias + residual)
+int ia_gemm_fwd_blocks_add(const void* X, int ldx, const void* W, int ldw, void* Y, int ldy, int M_rows, int N_out, int K_in, const float* bias,
+                           const void* aux, int ldaux, const int* row_blocks, int fill_dead_rows, hipStream_t stream) {
+  return gemm_core(X, 0, ldx, W, 0, ldw, Y, 0, ldy, M_rows, N_out, K_in, EPI_BIAS_ADD, bias, aux, ldaux, nullptr, 0, nullptr, 0, nullptr, stream, 0, 1.f,
+                   nullptr, row_blocks, fill_dead_rows);
+}
+extern "C" int ia_gemm_fwd_rows_add(const void* X, int ldx, const void* W, int ldw, void* Y, int ldy, int M_rows, int N_out, int K_in,
+                                    const float* bias, const void* aux, int ldaux, const uint8_t* row_live, int fill_dead_rows, void* workspace,
+                                    size_t workspace_bytes, hipStream_t stream) {
+  if (!row_live) return ia_gemm_fwd_blocks_add(X, ldx, W, ldw, Y, ldy, M_rows, N_out, K_in, bias, aux, ldaux, nullptr, 0, stream);
+  if (M_rows <= 0 || N_out <= 0 || K_in <= 0) return IA_ERR_ARG;
+  if (!workspace || workspace_bytes < ia_row_blocks_bytes(M_rows) || ((uintptr_t)workspace & 31)) return IA_ERR_WORKSPACE;
+  int rc = ia_row_blocks(row_live, M_rows, (int*)workspace, stream);
+  return rc ? rc : ia_gemm_fwd_blocks_add(X, ldx, W, ldw, Y, ldy, M_rows, N_out, K_in, bias, aux, ldaux, (const int*)workspace, fill_dead_rows, stream);
+}
+extern "C" int ia_gemm_dgrad_groups_rows(const void* dY, int ldy, const void* W, int w_kstrided, int ldw, void* dX, int ldx, int M_rows, int N_in,
+                                         int K_out, const void* aux, int ldaux, void* C2, const uint8_t* row_live, void* workspace,
+                                         size_t workspace_bytes, hipStream_t stream) {
+  if (!row_live)
+    return gemm_core(dY, 0, ldy, W, w_kstrided, ldw, dX, 0, ldx, M_rows, N_in, K_out, EPI_DGELU_CS, nullptr, aux, ldaux, C2, 0, workspace,
+                     workspace_bytes, nullptr, stream);
+  if (M_rows <= 0 || N_in <= 0 || K_out <= 0) return IA_ERR_ARG;
+  const size_t cs_bytes = al256(ia_gemm_colsum_workspace_bytes(M_rows, N_in));      // the column-sum partials in front, the list behind them
+  if (!workspace || workspace_bytes < cs_bytes + ia_row_blocks_bytes(M_rows) || ((uintptr_t)workspace & 31)) return IA_ERR_WORKSPACE;
+  int* list = reinterpret_cast<int*>((char*)workspace + cs_bytes);
+  int rc = ia_row_groups(row_live, M_rows, list, stream);
+  return rc ? rc : ia_gemm_dgrad_groups(dY, ldy, W, w_kstrided, ldw, dX, ldx, M_rows, N_in, K_out, aux, ldaux, C2, list, workspace, cs_bytes, stream);
 }
 extern "C" size_t ia_gemm_fwd_rows_workspace_bytes(int M_rows) { return ia_row_blocks_bytes(M_rows); }
 // 1: a call of this shape (rows contiguous: ldx = K_in, ldy = N_out) with row_live computes the live 32-row blocks only; 0: every row
@@ -2220,7 +2290,7 @@ static int launch_dgelu_colsum(GemmArgs& g, bool big, float* csum, void* workspa
 static int gemm_core(const void* A, int a_kstrided, int lda, const void* B, int b_kstrided, int ldb, void* C, int c_is_f32, int ldc, int M,
                      int N, int K, int epilogue, const float* bias, const void* aux, int ldaux, void* C2, int accumulate, void* workspace,
                      size_t workspace_bytes, const IaViewGemm* view, hipStream_t stream, int qcols, float qscale, const uint32_t* live_kt,
-                     const int* row_blocks, int rows_fill, int tail_of) {
+                     const int* row_blocks, int rows_fill, int tail_of, int rows_grouped) {
   const uint64_t a_window = view ? view->a_window : 0, b_window = view ? view->b_window : 0;
   const int groups = view ? view->groups : 1;
   (void)hipGetLastError();  // drop stale status left by unrelated runtime calls (e.g. hipEventQuery -> NotReady)
@@ -2276,10 +2346,11 @@ static int gemm_core(const void* A, int a_kstrided, int lda, const void* B, int 
   // from this function only; a new call site that fills GemmArgs for this form must do the same.
   if (a_kstrided && b_kstrided && c_is_f32 && epilogue == EPI_NONE) g.live_kt = (big && g.nk_per_split <= t256w::LIVE_MAX_KTILES) ? live_kt : nullptr;
   // the block list of the row-remapped forms (C2 has C's pitch, so dgrad_rows_fit covers it): a list or NULL
-  const bool fwd_epi = !b_kstrided && (epilogue == EPI_BIAS || epilogue == EPI_BIAS_GELU || epilogue == EPI_BIAS_GELU_ACT);
+  const bool fwd_epi = !b_kstrided && (epilogue == EPI_BIAS || epilogue == EPI_BIAS_GELU || epilogue == EPI_BIAS_GELU_ACT || epilogue == EPI_BIAS_ADD);
   g.row_blk = nullptr; g.rows_fill = rows_fill; g.fill_m = M; g.rows_guarded = tail_of ? 1 : 0;
   if (!a_kstrided && !c_is_f32 && (epilogue == EPI_NONE || epilogue == EPI_ADD || epilogue == EPI_DGELU_CS || fwd_epi))
     g.row_blk = (row_blocks && big && !g.dbg && !(N & 7) && dgrad_rows_fit(M, lda, ldc, aux ? ldaux : 0)) ? row_blocks : nullptr;
+  g.rows_grouped = (g.row_blk && epilogue == EPI_DGELU_CS && rows_grouped) ? 1 : 0;
   // Scaled columns, M no multiple of 128: the dense kernel rounds the rows behind the last whole 128-row part of M as (acc + bias) * scale
   // (guarded row-layout epilogue) and the others as acc * scale + bias * scale (accumulator-layout epilogue).  The remap would mix the two
   // in one wave, so the remapped launch covers the whole parts and the (at most four) blocks behind them get a remapped launch of their

@@ -397,17 +397,22 @@ class RobertaEncoder(nn.Module, _EngineStack):
                     w_fc2=l.output.dense.weight, b_fc2=l.output.dense.bias,
                     ln2_g=l.output.LayerNorm.weight, ln2_b=l.output.LayerNorm.bias)
 
-    def forward(self, hidden_states, attention_mask=None, masked_rows_dead=False, padded_rows_unread=False):
+    def forward(self, hidden_states, attention_mask=None, masked_rows_dead=False, padded_rows_unread=False, cls_only_read=False):
         """masked_rows_dead: the caller reads no hidden state of a masked position (heads on [CLS] / valid spans) -- the gradient arriving
         at such rows is then exactly zero in every layer and the attention backward may skip query blocks made of them (ia_layer_cfg).
         padded_rows_unread (with masked_rows_dead): the caller also accepts zeros there in the returned hidden states -- the forward
-        skips the padded rows as well (ia_layer_cfg::masked_rows_dead bit 2)."""
+        skips the padded rows as well (ia_layer_cfg::masked_rows_dead bit 2).
+        cls_only_read (with both of them): of the LAST hidden state the caller reads position 0 of every sequence and nothing else; the
+        last layer then computes what follows its attention for those rows only (ia_layer_cfg::out_row_live) and the other rows of the
+        last hidden state are zeros.  Position 0 of a sequence is such a row only where it is attended (Fn.cls_row_lists takes the key
+        mask): a masked position 0 stays a row of zeros that passes no gradient, as it is under masked_rows_dead."""
         B, L, H = hidden_states.shape
         km = None
         if attention_mask is not None:
             km = (attention_mask != 0).to(torch.uint8).contiguous()
         dead = bool(masked_rows_dead and km is not None)
         self.__dict__["_masked_rows_dead"] = (1 if dead else 0) | (2 if dead and padded_rows_unread else 0)
+        self.__dict__["_out_rows_cls"] = bool(dead and padded_rows_unread and cls_only_read)
         outs = Fn.EncoderStackFn.apply(hidden_states.reshape(B * L, H), self.anchor, self, km, B, L, torch.is_grad_enabled(), None)
         return (hidden_states,) + tuple(o.view(B, L, H) for o in outs)
 

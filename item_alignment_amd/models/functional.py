@@ -130,6 +130,42 @@ class EmbedLNFn(torch.autograd.Function):
 
 
 # --------------------------------------------------------------------------------------- encoder stack
+_cls_row_lists = {}
+_CLS_ROW_LISTS_KEPT = 8      # (shape, stream) pairs: two towers, training and evaluation batch shapes
+
+
+def cls_row_lists(B, L, device, key_mask=None):
+    """ia_layer_cfg::out_row_live and its lists for "row 0 of each of B sequences of L rows": one small tensor (the mask, then
+    ia_row_blocks, ia_ktile_mask and ia_row_groups of it), built by launches on the current stream -- no host synchronisation.
+    Returns (tensor, mask ptr, blocks ptr, k-tile mask ptr, groups ptr).
+    key_mask (uint8 [B, L]): row 0 of a sequence counts only where it is an attended position, so every out_row_live row is a live key
+    by construction (a sequence whose position 0 is masked has no live row behind the attention, as under the key-mask filter); the
+    lists then depend on the batch and are built per call.  Without one they depend on (B, L, device) only: built once per stream that
+    uses them and kept (the last few shapes), so a later step finds them ready in stream order."""
+    stream = torch.cuda.current_stream()
+    key = (int(B), int(L), torch.device(device).index, stream.cuda_stream)
+    if key_mask is None and key in _cls_row_lists:
+        return _cls_row_lists[key]
+    lib = _lib.load()
+    M = B * L
+    al = lambda n: (n + 255) & ~255
+    o_blk = al(M)
+    o_kt = o_blk + al(lib.ia_row_blocks_bytes(M))
+    o_grp = o_kt + al(lib.ia_ktile_mask_bytes(M))
+    buf = torch.zeros(o_grp + al(lib.ia_row_groups_bytes(M)), device=device, dtype=torch.uint8)
+    buf[:M:L] = 1 if key_mask is None else key_mask.reshape(-1)[::L].ne(0).to(torch.uint8)
+    p = buf.data_ptr()
+    check(lib.ia_row_blocks(p, M, p + o_blk, stream_ptr()), "ia_row_blocks")
+    check(lib.ia_ktile_mask(p, M, p + o_kt, stream_ptr()), "ia_ktile_mask")
+    check(lib.ia_row_groups(p, M, p + o_grp, stream_ptr()), "ia_row_groups")
+    got = (buf, p, p + o_blk, p + o_kt, p + o_grp)
+    if key_mask is None and not torch.cuda.is_current_stream_capturing():
+        while len(_cls_row_lists) >= _CLS_ROW_LISTS_KEPT:
+            _cls_row_lists.pop(next(iter(_cls_row_lists)))
+        _cls_row_lists[key] = got
+    return got
+
+
 class EncoderStackFn(torch.autograd.Function):
     """N encoder layers (post-LN RoBERTa or pre-LN ViT) through ia_layer_fwd / ia_layer_bwd.
     Returns every layer's output (the reference's `hidden_states[1:]`, text.py:1452)."""
@@ -167,6 +203,13 @@ class EncoderStackFn(torch.autograd.Function):
             for c in cfgs:
                 c.row_blocks, c.live_ktiles = lists.data_ptr(), (lists.data_ptr() + lb) if keep else None
             ctx.row_lists = lists
+        # the caller reads row 0 of each sequence of the LAST layer's output and nothing else (stack._out_rows_cls, set by the model
+        # classes for the one head that does: CoCaForItemAlignment with ensemble "sum"): ia_layer_cfg::out_row_live on that layer only
+        ctx.out_lists = None
+        if stack.__dict__.get("_out_rows_cls") and cu_seqlens is None:
+            ctx.out_lists = cls_row_lists(B, L, x.device, key_mask)      # (kept until the backward has run)
+            c = cfgs[-1]
+            c.out_row_live, c.out_row_blocks, c.out_live_ktiles, c.out_row_groups = ctx.out_lists[1:]
         if keep:
             stash_bytes = lib.ia_layer_stash_bytes(C.byref(cfgs[0]))
             # one allocation per layer (4 GB each at the bench's shape), not one of n layers: a request for 90 GiB in one piece is served
@@ -240,6 +283,7 @@ class EncoderStackFn(torch.autograd.Function):
         ctx.stash = None
         ctx.inputs = None
         ctx.row_lists = None
+        ctx.out_lists = None
         return dy, None, None, None, None, None, None, None
 
 
@@ -373,10 +417,13 @@ class PairHeadCEFn(torch.autograd.Function):
 
 
 class LayerNormFn(torch.autograd.Function):
-    """Plain LayerNorm over bf16 rows (final ViT norm; timm VisionTransformer.norm)."""
+    """Plain LayerNorm over bf16 rows (final ViT norm; timm VisionTransformer.norm).
+    row_live (uint8 [M] on the GPU, optional): the caller reads y only in rows with row_live != 0 and hands back a gradient that is zero
+    in the others -- those rows are not read, y and dx are zeros there (ia_ln_fwd_rows / ia_ln_bwd2_rows: the gamma / beta gradient
+    sums keep every live row's place, so they do not change by a bit)."""
 
     @staticmethod
-    def forward(ctx, x, anchor, ln, eps):
+    def forward(ctx, x, anchor, ln, eps, row_live=None):
         lib = _lib.load()
         _need_gpu(x, "tokens")
         x = x.contiguous()
@@ -384,9 +431,9 @@ class LayerNormFn(torch.autograd.Function):
         y = torch.empty_like(x)
         mean = torch.empty(M, device=x.device, dtype=F32)
         rstd = torch.empty(M, device=x.device, dtype=F32)
-        check(lib.ia_ln_fwd(x.data_ptr(), None, None, None, y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), ln.weight.data_ptr(),
-                            ln.bias.data_ptr(), M, H, eps, 0.0, 0, 0, stream_ptr()), "ia_ln_fwd")
-        ctx.ln, ctx.saved = ln, (x, mean, rstd)
+        check(lib.ia_ln_fwd_rows(x.data_ptr(), None, None, None, y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), ln.weight.data_ptr(),
+                                 ln.bias.data_ptr(), M, H, eps, 0.0, 0, 0, ptr(row_live), stream_ptr()), "ia_ln_fwd_rows")
+        ctx.ln, ctx.saved, ctx.row_live = ln, (x, mean, rstd), row_live
         return y
 
     @staticmethod
@@ -400,11 +447,11 @@ class LayerNormFn(torch.autograd.Function):
         ws_bytes = lib.ia_ln_bwd_workspace_bytes(M, H)
         ws = torch.empty(ws_bytes, device=x.device, dtype=torch.uint8)
         wg = ln.weight.requires_grad
-        check(lib.ia_ln_bwd(dy.data_ptr(), None, x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), ln.weight.data_ptr(), dz.data_ptr(), None,
-                            ln.weight.grad.data_ptr() if wg else None, ln.bias.grad.data_ptr() if wg else None, None, M, H, 0.0, 0, 0,
-                            ws.data_ptr(), ws_bytes, 1, stream_ptr()), "ia_ln_bwd")
+        check(lib.ia_ln_bwd2_rows(dy.data_ptr(), None, None, x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), ln.weight.data_ptr(), dz.data_ptr(),
+                                  None, ln.weight.grad.data_ptr() if wg else None, ln.bias.grad.data_ptr() if wg else None, None, M, H, 0.0, 0,
+                                  0, ptr(ctx.row_live), ws.data_ptr(), ws_bytes, 1, stream_ptr()), "ia_ln_bwd2_rows")
         _notify([ln.weight, ln.bias])
-        return dz, None, None, None
+        return dz, None, None, None, None
 
 
 class PatchEmbedFn(torch.autograd.Function):

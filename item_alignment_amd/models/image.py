@@ -89,9 +89,13 @@ class VisionTransformer(HipModule, _EngineStack):
                     ln1_g=b.norm1.weight, ln1_b=b.norm1.bias, w_fc1=b.mlp.fc1.weight, b_fc1=b.mlp.fc1.bias,
                     w_fc2=b.mlp.fc2.weight, b_fc2=b.mlp.fc2.bias, ln2_g=b.norm2.weight, ln2_b=b.norm2.bias)
 
-    def forward_features(self, x):
+    def forward_features(self, x, cls_only=False):
         """x: [B, 3, S, S] images, or a tuple / list of such batches that are to run as ONE batch in that order (the two items of a pair:
-        no concatenated copy of the images is made, Fn.PatchEmbedFn)."""
+        no concatenated copy of the images is made, Fn.PatchEmbedFn).
+        cls_only: a contract of the caller, never a default -- it reads token 0 of every image of the result and nothing else
+        (forward_head(pre_logits=True)), and the gradient it sends back is zero in every other row.  The last block then computes what
+        follows its attention, and the final norm, for the [CLS] rows only (ia_layer_cfg::out_row_live); the other rows of the result
+        are zeros."""
         (self._root if "_root" in self.__dict__ else self).ensure_arena()
         xs = tuple(x) if isinstance(x, (tuple, list)) else (x,)
         B = sum(t.shape[0] for t in xs)
@@ -100,8 +104,10 @@ class VisionTransformer(HipModule, _EngineStack):
                 raise ValueError(f"Input image size ({t.shape[-2]}*{t.shape[-1]}) doesn't match model ({self.img_size}*{self.img_size}).")
         N, H = self.num_patches + 1, self.embed_dim
         tok = Fn.PatchEmbedFn.apply(xs[0], self.anchor, self, *xs[1:])
+        self.__dict__["_out_rows_cls"] = bool(cls_only)
         outs = Fn.EncoderStackFn.apply(tok, self.anchor, self, None, B, N, torch.is_grad_enabled(), None)
-        y = Fn.LayerNormFn.apply(outs[-1], self.anchor, self.norm, 1e-6)
+        row_live = Fn.cls_row_lists(B, N, tok.device)[0][:B * N] if cls_only else None
+        y = Fn.LayerNormFn.apply(outs[-1], self.anchor, self.norm, 1e-6, row_live)
         return y.view(B, N, H)
 
     def forward_head(self, x, pre_logits=False):

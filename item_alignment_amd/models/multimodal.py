@@ -9,6 +9,7 @@ from torch import nn
 from . import functional as Fn
 from .base import (ACT_NONE, BaseModelOutput, HipModule, RobertaEmbeddings, RobertaEncoder, RobertaImageEmbeddings, RobertaPooler,
                    SequenceClassifierOutput, TwoTowerClassificationHead, VecSimClassificationHead, cls_rows, init_bert_weights)
+from .image import VisionTransformer
 from .loss import apply_loss, make_loss
 from .text import PretrainedMixin, RobertaOneTower, RobertaTwoTower, adopt
 
@@ -82,15 +83,19 @@ class CoCaModel(nn.Module):
         self.img_encoder = image_encoder
         self.text_encoder = text_encoder
 
-    def embed_text(self, input_ids, attention_mask, token_type_ids, position_ids, padded_rows_matter=False):
+    def embed_text(self, input_ids, attention_mask, token_type_ids, position_ids, padded_rows_matter=False, cls_only_read=False):
         # padded_rows_matter: the caller reads the hidden states of PADDED positions (the cross_attn multimodal layers attend
         # over all L text tokens without a padding mask, reference multimodal.py:529-616), so the unpadded tower run (IA_UNPAD),
         # which leaves zeros there, must not be used
         out = self.text_encoder(input_ids, attention_mask=attention_mask, token_type_ids=token_type_ids, position_ids=position_ids,
-                                allow_unpad=not padded_rows_matter, padded_rows_unread=not padded_rows_matter)
+                                allow_unpad=not padded_rows_matter, padded_rows_unread=not padded_rows_matter,
+                                cls_only_read=cls_only_read and not padded_rows_matter)
         return out.last_hidden_state
 
-    def embed_image(self, images):
+    def embed_image(self, images, cls_only=False):
+        # cls_only: the caller reads token 0 of every image and nothing else (VisionTransformer.forward_features)
+        if cls_only and isinstance(self.img_encoder, VisionTransformer):
+            return self.img_encoder.forward_features(images, cls_only=True)
         return self.img_encoder.forward_features(images)
 
 
@@ -267,9 +272,10 @@ class CoCaForItemAlignment(HipModule):
         # bench's roofline leg, rocprofv3 averages) stop describing the kernels themselves.
         two_streams = TOWER_STREAMS and images_1.is_cuda
         images = (images_1, images_2)               # run as one 2B batch; the patch gather reads the two tensors in turn (no fp32 concat)
+        cls_only = self.reads_cls_only()
 
         def image_tower():
-            img_tok = self.coca.embed_image(images)                                                                  # [2B, N, Hi] bf16
+            img_tok = self.coca.embed_image(images, cls_only=cls_only)                                                                  # [2B, N, Hi] bf16
             i_cls = self.coca.img_encoder.forward_head(img_tok, pre_logits=True)                                   # [2B, Hi] fp32
             if self.img_proj is not None:
                 i_cls = Fn.LinearSmallFn.apply(i_cls, self.img_proj.weight, self.img_proj, ACT_NONE)
@@ -288,7 +294,8 @@ class CoCaForItemAlignment(HipModule):
         else:
             i_cls = image_tower()
         txt = self.coca.embed_text(cat(input_ids_1, input_ids_2), cat(attention_mask_1, attention_mask_2),
-                                   cat(token_type_ids_1, token_type_ids_2), cat(position_ids_1, position_ids_2))   # [2B, L, H]
+                                   cat(token_type_ids_1, token_type_ids_2), cat(position_ids_1, position_ids_2),
+                                   cls_only_read=cls_only)                                                         # [2B, L, H]
         H = txt.shape[-1]
         dev = txt.device
         t_cls = Fn.GatherRowsFn.apply(txt.reshape(2 * B * L, H), self.anchor, cls_rows(2 * B, L, 0, dev), 0.0, 0)   # text_tokens[:, 0]
@@ -298,6 +305,15 @@ class CoCaForItemAlignment(HipModule):
         emb = t_cls + i_cls                                                                                          # multimodal.py:1015
         e1, e2 = emb[:B].contiguous(), emb[B:].contiguous()
         return self._finish(e1, e2, labels)
+
+    def reads_cls_only(self):
+        """The `sum` head reads text_tokens[:, 0] and the image [CLS] and nothing else of either tower, so the last layer of each may skip
+        what follows its attention in every other row (cls_only_read / cls_only: a contract of this caller).  Only for the plain [CLS]
+        head on the last layer: every other configuration keeps every row.  A text position 0 that is not attended -- the reference's
+        collate never produces one -- is no such row (RobertaEncoder.forward): it stays the row of zeros it is under masked_rows_dead."""
+        cfg = self.config
+        return (self.ensemble == "sum" and cfg.classification_method == "cls" and str(getattr(cfg, "cls_layers", "1")) == "1"
+                and not getattr(cfg, "auxiliary_task", False))
 
     def _forward_cross_attn(self, input_ids, attention_mask, token_type_ids, position_ids, images, labels):
         """reference multimodal.py:1003-1013.  Quirk A4 (:1013): `embeds_2 = text_tokens_1[:, 0]` — the target embedding is

@@ -121,8 +121,10 @@ class RobertaModel(HipModule, PretrainedMixin):
 
     def forward(self, input_ids=None, attention_mask=None, token_type_ids=None, position_ids=None, cate_ids=None, head_mask=None,
                 inputs_embeds=None, output_attentions=None, output_hidden_states=None, return_dict=None, allow_unpad=True,
-                padded_rows_unread=False, **unused):
-        """padded_rows_unread: the caller reads no hidden state of a padded position and accepts zeros there (as under IA_UNPAD): the
+                padded_rows_unread=False, cls_only_read=False, **unused):
+        """cls_only_read (with padded_rows_unread): of last_hidden_state the caller reads [:, 0] and nothing else, and reads no other hidden
+        state -- the last layer then runs what follows its attention for the [CLS] rows only (RobertaEncoder.forward).  Opt-in.
+        padded_rows_unread: the caller reads no hidden state of a padded position and accepts zeros there (as under IA_UNPAD): the
         forward then skips the padded rows too (ia_layer_cfg::masked_rows_dead bit 2).  Opt-in -- a direct caller gets every position
         of last_hidden_state computed."""
         (self._root if "_root" in self.__dict__ else self).ensure_arena()
@@ -139,7 +141,8 @@ class RobertaModel(HipModule, PretrainedMixin):
         # cross_attn multimodal layers, which attend over ALL text positions, pass False): the padded run may then at least skip what is
         # provably zero in its backward
         dead = allow_unpad and cate_ids is None and not output_hidden_states
-        hs = self.encoder(e, attention_mask, masked_rows_dead=dead, padded_rows_unread=dead and padded_rows_unread)
+        hs = self.encoder(e, attention_mask, masked_rows_dead=dead, padded_rows_unread=dead and padded_rows_unread,
+                          cls_only_read=dead and padded_rows_unread and cls_only_read)
         return BaseModelOutput(last_hidden_state=hs[-1], hidden_states=hs)
 
     def _forward_unpadded(self, input_ids, attention_mask, token_type_ids, position_ids):
