@@ -156,6 +156,27 @@ int ia_gemm_dgrad_groups_rows(const void* dY, int ldy, const void* W, int w_kstr
 /* Diagnostics (tests, A/B runs; ABI 20): on == 0 makes the layer calls ignore ia_layer_cfg::out_row_live (every row behind the attention
  * runs under the layer's other filter, as without it); returns the previous setting. */
 int ia_debug_out_rows(int on);
+/* (ABI 20, second form) The block-packed list: the layout of ia_row_blocks (8 header words, the slots, the dead blocks; the same size)
+ * with four slots per wave-row of the remapped kernel, eight per M-tile.  A wave-row holds the live 32-row blocks of one or more WHOLE
+ * 128-row groups -- a group's blocks contiguous and ascending, no group across two wave-rows, -1 in the slots behind them; header word 0
+ * counts the slots in use (4 x wave-rows).  Groups with 4 live blocks stand alone, each 3 takes a 1, then 2 + 2, an odd 2 with up to two
+ * 1s, the remaining 1s by four: a deterministic layout, so the device builder and the _host twin give the same list.  At most
+ * 128 x 4096 rows (IA_ERR_UNSUPPORTED beyond).  ia_row_groups_packed_offset: where the list sits behind an ia_row_blocks list when one
+ * buffer holds both (ia_layer_cfg::masked_rows_dead bit 3).
+ * ia_gemm_dgrad_packed: the IA_EPI_DGELU_COLSUM data gradient (as ia_gemm_dgrad_groups_rows, the list handed in) over such a list -- dX
+ * on the live blocks, zeros elsewhere, and C2 += the column sums BIT-IDENTICAL to ia_gemm_bf16's on a dY that is zero wherever the list
+ * has no block: a lane adds the rows of a group's live blocks in the dense kernel's order with nothing in between, the wave folds and
+ * stores at every change of group into that group's slot of the partials, and the second stage is the dense call's.  Workspace:
+ * ia_gemm_colsum_workspace_bytes.  A shape the remapped kernel does not serve (ia_gemm_dgrad_rows_filters == 0) runs every row. */
+size_t ia_row_groups_packed_bytes(int M_rows);
+size_t ia_row_groups_packed_offset(int M_rows);
+int ia_row_groups_packed(const uint8_t* row_live, int M_rows, int* list, ia_stream_t stream);
+int ia_row_groups_packed_host(const uint8_t* row_live, int M_rows, int* list);
+int ia_gemm_dgrad_packed(const void* dY, int ldy, const void* W, int w_kstrided, int ldw, void* dX, int ldx, int M_rows, int N_in, int K_out,
+                         const void* aux, int ldaux, void* C2, const int* packed_list, void* workspace, size_t workspace_bytes,
+                         ia_stream_t stream);
+/* ... on == 0 makes them ignore ia_layer_cfg::out_q_rows (the attention of such a layer runs every query row); returns the previous setting. */
+int ia_debug_q_rows(int on);
 
 /* per-launch HIP-event timing of one GEMM instantiation (variant = a_kstrided*1000 + b_kstrided*100 + epilogue*10 + c_is_f32),
  * recorded on the launch stream; used by bench.py for the roofline of the dominant kernel. */
@@ -243,6 +264,20 @@ int ia_attn_bwd_bias_ex(int flags, const void* q, const void* k, const void* v, 
                         const void* d_out, int ld_o, const float* lse2, float* delta, void* dq, void* dk, void* dv, int ld_dqkv, float* dbias,
                         void* workspace, size_t workspace_bytes, int B, int nh, int L, float scale, float drop_p, uint32_t seed,
                         ia_stream_t stream);
+/* (ABI 20, second form) ia_attn_fwd / ia_attn_fwd_ps and ia_attn_bwd_bias_ex with a query-row limit.  q_rows = n > 0 is the caller's
+ * guarantee that nobody reads `out` at query positions >= n of any sequence and that d_out is exactly zero there (a head that reads
+ * position 0 only: n = 1).  Forward: only the query tiles that reach in front of n are computed; out and lse2 are bit-identical to the
+ * unlimited call in rows < n, and every row the kernel skips is written as zeros (finite whatever the buffer held).  Backward: the
+ * 32-query blocks at or beyond n are dead, with or without a key mask -- zero dq rows (+0 where the unlimited call may give -0), nothing
+ * for dk / dv; dq, dk, dv and dbias equal the unlimited call's on the same d_out bit for bit.  The backward takes the out / lse2 of a
+ * forward with the same limit, a larger one, or none.  q_rows <= 0 or >= L: no limit.  flags: IA_ATTN_Q_PRESCALED (both),
+ * IA_ATTN_MASKED_ROWS_DEAD (backward). */
+int ia_attn_fwd_q_rows(int flags, const void* q, const void* k, const void* v, int ld_qkv, const uint8_t* key_mask, void* out, int ld_o,
+                       float* lse2, int B, int nh, int L, float scale, float drop_p, uint32_t seed, int q_rows, ia_stream_t stream);
+int ia_attn_bwd_bias_q_rows(int flags, const void* q, const void* k, const void* v, int ld_qkv, const uint8_t* key_mask, const void* out,
+                            const void* d_out, int ld_o, const float* lse2, float* delta, void* dq, void* dk, void* dv, int ld_dqkv,
+                            float* dbias, void* workspace, size_t workspace_bytes, int B, int nh, int L, float scale, float drop_p,
+                            uint32_t seed, int q_rows, ia_stream_t stream);
 
 /* General form (cross-attention and multi-query attention of the CoCa multimodal layers, src/models/multimodal.py:590-616
  * ParallelTransformerBlock and :665-706 CrossAttention): Lq queries attend to Lk keys per (sequence, head).  q / out /
@@ -639,6 +674,14 @@ typedef struct {
    * key_mask argument is ignored (every token of a sequence is attendable).  NULL / 0: padded [B, L] rows. */
   const int* cu_seqlens;
   int total_tokens;
+  /* (ABI 20, second form) the query-row limit of a layer with out_row_live: 0 = off; n > 0 = the caller guarantees that out_row_live is
+   * zero at every position >= n of every sequence, so the attention output there is unread and its gradient exactly zero.  The attention
+   * forward then computes the query tiles that reach in front of n only (the other rows of the stash's context are zeros, written by
+   * the kernel) and the attention backward treats the 32-query blocks at or beyond n as dead (ia_attn_fwd_q_rows /
+   * ia_attn_bwd_bias_q_rows); every output row the caller reads and every gradient is bit-identical to out_q_rows = 0.  Honoured only
+   * together with out_row_live and on padded rows (cu_seqlens == NULL).  The member fills what was the padding word in front of
+   * dx_colsum_out: no offset and not the size of the structure changes, and a zero-initialised structure of an older caller says "off". */
+  int out_q_rows;
   /* pre-LN (ViT) stacks, backward only (ABI 5): the b_fc2 gradient of a block is the column sum of its incoming gradient dy, i.e. of
    * the input gradient dx the block ABOVE has just produced.  dx_colsum_out != NULL: this block's last LayerNorm backward also adds
    * the column sums of its dx into that fp32 [H] vector (pass the b_fc2 gradient slot of the block below); dy_colsum_done != 0: the
@@ -654,7 +697,10 @@ typedef struct {
    * zeros at masked positions; q / k / v and the FFN activation (with its derivative) are zeros in blocks without a live row; the two
    * projection outputs are not written there (their LayerNorm writes zeros over the stash's copy).  A stash written under 3 must be
    * consumed by a backward with bit 1 set.  Every value the unmasked positions produce, and every gradient, is bit-identical to
-   * masked_rows_dead = 1. */
+   * masked_rows_dead = 1.
+   * (ABI 20, second form) Bit 3 (value 4), read by the backward together with row_blocks: the buffer row_blocks points into also holds the
+   * block-packed list of the same mask (ia_row_groups_packed) at byte offset ia_row_groups_packed_offset(B * L); without the bit the
+   * backward builds that list per call.  The x gelu' + column-sums data gradient of a post-LN layer runs over it. */
   int masked_rows_dead;
   /* (ABI 19) optional, device pointers, NULL = the layer call builds its own: the 32-row block list (ia_row_blocks) and the live-k-tile
    * mask (ia_ktile_mask) of key_mask taken as row_live [B * L].  The mask is the same for every layer of a stack, forward and backward:
@@ -667,7 +713,7 @@ typedef struct {
    * LayerNorm behind it, fc1 + GELU, fc2 and (post-LN) the closing LayerNorm then run these rows only -- GEMMs by 32-row blocks -- and so
    * do their backward kernels; the x gelu' data gradient runs whole 128-row groups (ia_row_groups), which keeps the fc1 bias gradient
    * bit-identical.  The QKV projection, the attention, their backward and the pre-LN LN1 keep the key-mask filter (post-LN) or every row
-   * (pre-LN): every row is a key.  y is unspecified outside out_row_live in a pre-LN layer and zeros there in a post-LN layer; dx and
+   * (pre-LN): every row is a key (out_q_rows above limits the attention's QUERY rows).  y is unspecified outside out_row_live in a pre-LN layer and zeros there in a post-LN layer; dx and
    * every parameter gradient are bit-identical to the call without it.  Padded rows only (cu_seqlens == NULL).  A stash written with
    * out_row_live must be consumed by a backward with the same out_row_live.
    * out_row_blocks (ia_row_blocks), out_live_ktiles (ia_ktile_mask), out_row_groups (ia_row_groups) of out_row_live: optional, NULL = the

@@ -27,6 +27,7 @@ class LayerGrads(C.Structure):
 class LayerCfg(C.Structure):
     _fields_ = [("B", i32), ("L", i32), ("H", i32), ("I", i32), ("nh", i32), ("pre_ln", i32), ("eps", f32),
                 ("hidden_drop", f32), ("attn_drop", f32), ("seed", u32), ("layer_id", u32), ("cu_seqlens", vp), ("total_tokens", i32),
+                ("out_q_rows", i32),      # (in what was the padding word in front of dx_colsum_out: no offset moves)
                 ("dx_colsum_out", vp), ("dy_colsum_done", i32), ("masked_rows_dead", i32),
                 ("row_blocks", vp), ("live_ktiles", vp),
                 ("out_row_live", vp), ("out_row_blocks", vp), ("out_live_ktiles", vp), ("out_row_groups", vp)]
@@ -62,6 +63,12 @@ SIGNATURES = {
     "ia_row_groups_host": (i32, [vp, i32, vp]),
     "ia_gemm_dgrad_groups_rows": (i32, [vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, sz, vp]),
     "ia_debug_out_rows": (i32, [i32]),
+    "ia_row_groups_packed_bytes": (sz, [i32]),
+    "ia_row_groups_packed_offset": (sz, [i32]),
+    "ia_row_groups_packed": (i32, [vp, i32, vp, vp]),
+    "ia_row_groups_packed_host": (i32, [vp, i32, vp]),
+    "ia_gemm_dgrad_packed": (i32, [vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, sz, vp]),
+    "ia_debug_q_rows": (i32, [i32]),
     "ia_prof_begin": (i32, [i32, i32]),
     "ia_prof_end": (i32, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i32)]),
     "ia_prof_bytes": (C.c_double, []),
@@ -82,6 +89,8 @@ SIGNATURES = {
     "ia_attn_fwd_ps": (i32, [vp, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, f32, f32, u32, vp]),
     "ia_attn_bwd_bias_ps": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, sz, i32, i32, i32, f32, f32, u32, vp]),
     "ia_attn_bwd_bias_ex": (i32, [i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, sz, i32, i32, i32, f32, f32, u32, vp]),
+    "ia_attn_fwd_q_rows": (i32, [i32, vp, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, f32, f32, u32, i32, vp]),
+    "ia_attn_bwd_bias_q_rows": (i32, [i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, sz, i32, i32, i32, f32, f32, u32, i32, vp]),
     "ia_gemm_bf16_qscale": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, vp, i32, f32, vp]),
     "ia_attn_fwd_x": (i32, [vp, i32, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, f32, f32, u32, vp]),
     "ia_attn_bwd_x": (i32, [vp, i32, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, f32, f32, u32, vp]),

@@ -60,6 +60,10 @@ struct AttnArgs {
   int exact_delta;                                // backward, IA_ATTN_EXACT_DELTA=1: `delta` already holds sum_k P dP in fp32 (attn_bwd3_delta_kernel)
   int dead_queries;                               // backward (fused kernel): the caller guarantees d_o == 0 at every masked position, so a 32-query
                                                   // block whose positions are all masked contributes nothing: it is skipped, its dq rows are zeros
+  int q_lim;                                      // 0 = off.  n > 0 (padded self-attention only): nobody reads the output at query positions >= n of
+                                                  // any sequence and d_o is exactly zero there.  Forward: the waves whose queries all lie at or beyond n
+                                                  // do no arithmetic and store zeros (out) / 0 (lse2) for their rows.  Backward: the query blocks at or
+                                                  // beyond n are dead exactly like all-masked ones under dead_queries (zero dq rows, nothing for dk / dv)
 };
 
 // Workgroups are dealt round-robin to the 8 XCDs (each with its own L2): renumber them so that consecutive
@@ -208,6 +212,16 @@ IA_DEV void store_block_rows(char* slot, const f32x16& a0, const f32x16& a1, flo
 // a wave without rows (past the end of the sequence) still contributes its (zero) row
 IA_DEV void zero_cs_row(float* cs_out, int lane) {
   if (lane < 16) *reinterpret_cast<f32x4*>(cs_out + lane * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+// AttnArgs::q_lim, forward: the rows of a wave beyond the limit -- queries q0 .. q0 + nq - 1 (nq <= 64) of sequence b, clipped to Lq -- leave
+// as zeros in head h's 64 columns of `out` and as 0 in lse2.  The kernel writes them (no memset of the caller's buffer): whatever reads
+// every row of the context afterwards (the out-projection's weight gradient over a partly live k-tile multiplies these rows by exact
+// zeros) must meet finite values, also in a buffer that held anything before.
+IA_DEV void zero_unread_rows(const AttnArgs& p, size_t qbase, int b, int h, int q0, int nq, int Lq, int lane) {
+  const int c = lane & 7;
+  for (int r = lane >> 3; r < nq && q0 + r < Lq; r += 8)
+    *reinterpret_cast<u32x4*>(p.out + (qbase + q0 + r) * p.ld_o + h * 64 + c * 8) = u32x4{0u, 0u, 0u, 0u};
+  if (p.lse2 && lane < nq && q0 + lane < Lq) p.lse2[((size_t)b * p.nh + h) * p.Lq + q0 + lane] = 0.f;
 }
 
 // ------------------------------------------------------------------------------------------ forward
@@ -397,7 +411,15 @@ __global__ __launch_bounds__(256, QB == 1 ? 3 : 2) void attn_fwd3_kernel(AttnArg
     if (tile * ROWS >= Lq) return;
   }
   const int q0 = tile * ROWS + wave * 32 * QB;            // this wave's first query (block qb: + 32 qb)
-  const bool active = q0 < Lq;
+  // AttnArgs::q_lim: a wave whose queries all lie at or beyond the limit stores its zeros here, ahead of everything else (nothing of it
+  // stays live into the loop), then keeps its share of the K / V staging and the barriers and skips the arithmetic; a workgroup made of
+  // such waves only leaves.  (A live wave computes all of its 32 QB rows: the rows in front of the limit come out exactly as without one.)
+  const bool unread = p.q_lim > 0 && q0 >= p.q_lim;       // wave-uniform
+  if (unread) {
+    if (q0 < Lq) zero_unread_rows(p, qbase, b, h, q0, 32 * QB, Lq, lane);
+    if (tile * ROWS >= p.q_lim) return;
+  }
+  const bool active = q0 < Lq && !unread;
   // this sequence's K / V rows of head h as buffer windows: rows >= L are out of range and arrive as zeros
   const uint32_t win = (uint32_t)(((size_t)(L - 1) * p.ld_kv + 64) * 2);
   const __amdgpu_buffer_rsrc_t rsK = ia_rsrc(p.k + rowbase * p.ld_kv + h * 64, win);
@@ -740,6 +762,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd3_dq_kernel(AttnArgs p) {
     if (t128 + 1 < nkt_all) any |= s_valid[t128 + 1][0] | s_valid[t128 + 1][1];
     work = active && __builtin_amdgcn_readfirstlane(mine) != 0u;
     if (__builtin_amdgcn_readfirstlane(any) == 0u) nkt = 1;
+  }
+  // AttnArgs::q_lim: the same two cases by position -- dO == 0 at and beyond the limit, with or without a key mask
+  if (p.q_lim > 0) {
+    work = work && q0 < p.q_lim;
+    if (tile * 128 >= p.q_lim) nkt = 1;
   }
   nkt = __builtin_amdgcn_readfirstlane(nkt);
   ragged = __builtin_amdgcn_readfirstlane(ragged);
@@ -1160,6 +1187,14 @@ __global__ __launch_bounds__(256, 2) void attn_bwd3_dkv_kernel(AttnArgs p) {
     const int live = __builtin_amdgcn_readfirstlane(last < 0 ? 1 : (last >> 6) + 1);
     if (live < nqt) nqt = live;
   }
+  // AttnArgs::q_lim: dO == 0 at and beyond the limit whatever the mask says -- the query loop ends with the limit's tile, and inside it
+  // with the limit's 32-query sub tile (qend)
+  int qend = Lq;
+  if (p.q_lim > 0 && p.q_lim < Lq) {
+    qend = p.q_lim;
+    const int live = (qend + 63) >> 6;
+    if (live < nqt) nqt = live;
+  }
   if (nqt > 1) stage_tile(S1{}, 1);
   f32x16 dk0 = zero16(), dk1 = zero16(), dv0 = zero16(), dv1 = zero16();
 
@@ -1272,7 +1307,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd3_dkv_kernel(AttnArgs p) {
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       prescale(((decltype(SLOT_T)::value + 1) % 3) * KV_STAGE);
     }
-    if (qt * 64 + 32 < Lq) sub_tile(std::integral_constant<int, 1>{});
+    if (qt * 64 + 32 < qend) sub_tile(std::integral_constant<int, 1>{});
   };
   {
     int qt = 0;
@@ -1517,6 +1552,9 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_kernel(AttnArgs p) {
   // later, behind the barrier every reader arrives at after reading it).  At an item boundary the run-ahead pauses: the epilogue
   // needs dK / dV and part C the K^T fragments of the old item before the item start overwrites them.
   const int G = cnt * nb;
+  // AttnArgs::q_lim: bit j = query block j of an item starts in front of the limit.  The other blocks are dead the way all-masked ones are
+  // under dead_queries (dO == 0 there): no part A, zero dQ rows from part C, with or without a key mask.
+  const uint32_t qlim_bits = p.q_lim > 0 ? (1u << ((p.q_lim + 31) >> 5)) - 1u : 0xFFFFFFFFu;
   int cj = 0;                                             // block of step g inside its item
   Cur prev = cons;                                        // item of step g-1
   int pcj = 0;                                            // its block
@@ -1568,7 +1606,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_kernel(AttnArgs p) {
           csq = f32x4{0.f, 0.f, 0.f, 0.f};
         }
         // ---- part A of step g
-        if (mine && (!p.dead_queries || ((vbits >> blk) & 1u))) {
+        if (mine && ((qlim_bits >> blk) & 1u) && (!p.dead_queries || ((vbits >> blk) & 1u))) {
           const uint32_t so = (uint32_t)(slot * SLOT);
           f32x16 s, dp;
           const float* const sL = reinterpret_cast<const float*>(smem + RING_OFF + slot * SLOT + SL_LSE) + 4 * hh;
@@ -1661,7 +1699,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_kernel(AttnArgs p) {
         s16x4 lo[8], hi[8];
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
         // (vbits still belongs to the item of step g-1 here: a new item's part A runs behind this part C)
-        if (!p.dead_queries || ((vbits >> pcj) & 1u)) {
+        if (((qlim_bits >> pcj) & 1u) && (!p.dead_queries || ((vbits >> pcj) & 1u))) {
 #pragma unroll
         for (int k = 0; k < 8; ++k) { lo[k] = tr_read<0>(xr + k * 2 * XT); hi[k] = tr_read<16 * XP>(xr2 + k * 2 * XT); }
 #define IA_DQ_STEP(k, n)                                                                                   \
@@ -1816,10 +1854,14 @@ struct Packed { const int* cu; int total; };
 // What the bias forms of the backward add: the QKV bias gradient and the workspace its per-workgroup partial sums go through
 struct BiasOut { float* dbias; void* workspace; size_t workspace_bytes; };
 
+// AttnArgs::q_lim of an entry point's q_rows: honoured on padded rows only, and a limit that covers every position is no limit
+int q_lim_of(int q_rows, bool packed, int Lq) { return (q_rows > 0 && !packed && q_rows < Lq) ? q_rows : 0; }
+
 // The one place that checks the arguments of a forward / backward entry point and fills AttnArgs.  pk / bias: null for the entry points
 // without them.  flags: IA_ATTN_* (the caller has rejected unknown bits).
 int attn_fwd_impl(int flags, const void* q, int ld_q, const void* k, const void* v, int ld_kv, const uint8_t* key_mask, const Packed* pk, void* out,
-                  int ld_o, float* lse2, int B, int nh, int Lq, int Lk, float scale, float drop_p, uint32_t seed, hipStream_t stream) {
+                  int ld_o, float* lse2, int B, int nh, int Lq, int Lk, float scale, float drop_p, uint32_t seed, hipStream_t stream,
+                  int q_rows = 0) {
   (void)hipGetLastError();  // drop stale status left by unrelated runtime calls (e.g. hipEventQuery -> NotReady)
   if (!q || !k || !v || !out || (pk && (!pk->cu || pk->total <= 0))) return IA_ERR_ARG;
   AttnArgs a{};
@@ -1828,6 +1870,7 @@ int attn_fwd_impl(int flags, const void* q, int ld_q, const void* k, const void*
   a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.out = (bf16*)out; a.mask = key_mask; a.lse2 = lse2;
   a.cu = pk ? pk->cu : nullptr;
   a.q_prescaled = (flags & IA_ATTN_Q_PRESCALED) ? 1 : 0;
+  a.q_lim = q_lim_of(q_rows, pk != nullptr, Lq);
   if (a.thr16) launch_fwd<true>(a, stream);
   else launch_fwd<false>(a, stream);
   return ia_check_launch();
@@ -1835,7 +1878,8 @@ int attn_fwd_impl(int flags, const void* q, int ld_q, const void* k, const void*
 
 int attn_bwd_impl(int flags, const void* q, int ld_q, const void* k, const void* v, int ld_kv, const uint8_t* key_mask, const Packed* pk,
                   const void* out, const void* d_out, int ld_o, const float* lse2, float* delta, void* dq, int ld_dq, void* dk, void* dv, int ld_dkv,
-                  const BiasOut* bias, int B, int nh, int Lq, int Lk, float scale, float drop_p, uint32_t seed, hipStream_t stream) {
+                  const BiasOut* bias, int B, int nh, int Lq, int Lk, float scale, float drop_p, uint32_t seed, hipStream_t stream,
+                  int q_rows = 0) {
   (void)hipGetLastError();  // drop stale status left by unrelated runtime calls (e.g. hipEventQuery -> NotReady)
   if (!q || !k || !v || !out || !d_out || !lse2 || !delta || !dq || !dk || !dv) return IA_ERR_ARG;
   if ((pk && (!pk->cu || pk->total <= 0)) || (bias && !bias->dbias)) return IA_ERR_ARG;
@@ -1851,6 +1895,7 @@ int attn_bwd_impl(int flags, const void* q, int ld_q, const void* k, const void*
   a.q_prescaled = (flags & IA_ATTN_Q_PRESCALED) ? 1 : 0;
   a.dead_queries = ((flags & IA_ATTN_MASKED_ROWS_DEAD) && key_mask) ? 1 : 0;
   a.exact_delta = exact_delta_on() ? 1 : 0;
+  a.q_lim = q_lim_of(q_rows, pk != nullptr, Lq);
   if (a.thr16) launch_bwd<true>(a, stream);
   else launch_bwd<false>(a, stream);
   rc = ia_check_launch();
@@ -1920,6 +1965,27 @@ extern "C" int ia_attn_bwd_bias_ex(int flags, const void* q, const void* k, cons
   const BiasOut bias{dbias, workspace, workspace_bytes};
   return attn_bwd_impl(flags, q, ld_qkv, k, v, ld_qkv, key_mask, nullptr, out, d_out, ld_o, lse2, delta, dq, ld_dqkv, dk, dv, ld_dqkv, &bias, B, nh, L, L,
                        scale, drop_p, seed, stream);
+}
+// The query-row limit (ia_layer_cfg::out_q_rows): q_rows = n > 0 is the caller's guarantee that nobody reads `out` at query positions >= n
+// of any sequence and that d_out is exactly zero there.  The forward then computes the query tiles that reach in front of n only -- out
+// and lse2 are bit-identical to the unlimited call in rows < n and hold zeros (written by the kernel) in every row it skips -- and the
+// backward treats the 32-query blocks at or beyond n as dead, with or without a key mask: their dq rows are +0, they add nothing to
+// dk / dv, and the bias gradient's partial sums keep their slots and their fold order.  dq, dk, dv and dbias equal the unlimited call's
+// on the same d_out bit for bit (dead dq rows: +0 where the unlimited call may give -0).  A backward with a limit consumes the out / lse2
+// of a forward with the same or a larger one.  q_rows <= 0 or >= L: no limit.  flags: IA_ATTN_Q_PRESCALED (forward), IA_ATTN_* (backward).
+extern "C" int ia_attn_fwd_q_rows(int flags, const void* q, const void* k, const void* v, int ld_qkv, const uint8_t* key_mask, void* out, int ld_o,
+                                  float* lse2, int B, int nh, int L, float scale, float drop_p, uint32_t seed, int q_rows, hipStream_t stream) {
+  if (flags & ~IA_ATTN_Q_PRESCALED) return IA_ERR_ARG;
+  return attn_fwd_impl(flags, q, ld_qkv, k, v, ld_qkv, key_mask, nullptr, out, ld_o, lse2, B, nh, L, L, scale, drop_p, seed, stream, q_rows);
+}
+extern "C" int ia_attn_bwd_bias_q_rows(int flags, const void* q, const void* k, const void* v, int ld_qkv, const uint8_t* key_mask, const void* out,
+                                       const void* d_out, int ld_o, const float* lse2, float* delta, void* dq, void* dk, void* dv, int ld_dqkv,
+                                       float* dbias, void* workspace, size_t workspace_bytes, int B, int nh, int L, float scale, float drop_p,
+                                       uint32_t seed, int q_rows, hipStream_t stream) {
+  if (flags & ~(IA_ATTN_Q_PRESCALED | IA_ATTN_MASKED_ROWS_DEAD)) return IA_ERR_ARG;
+  const BiasOut bias{dbias, workspace, workspace_bytes};
+  return attn_bwd_impl(flags, q, ld_qkv, k, v, ld_qkv, key_mask, nullptr, out, d_out, ld_o, lse2, delta, dq, ld_dqkv, dk, dv, ld_dqkv, &bias, B, nh, L, L,
+                       scale, drop_p, seed, stream, q_rows);
 }
 extern "C" int ia_attn_bwd_bias(const void* q, const void* k, const void* v, int ld_qkv, const uint8_t* key_mask, const void* out,
                                 const void* d_out, int ld_o, const float* lse2, float* delta, void* dq, void* dk, void* dv, int ld_dqkv,

@@ -79,6 +79,7 @@ FwdBufs carve_infer(const ia_layer_cfg* c, void* base) {
 
 struct Scratch {
   char* g0; char* g1; char* g2; char* gI; char* gqkv; float* delta; char* ws; size_t ws_bytes; char* gws; size_t gws_bytes; uint32_t* live_kt; int* row_blk;
+  int* pack_blk;      // masked_rows_dead: the block-packed list of the x gelu' data gradient (when the caller hands none behind row_blocks)
   uint32_t* out_kt; int* out_blk; int* out_grp;      // out_row_live: its k-tile mask, block list and group list (when the caller hands none)
   size_t bytes;
 };
@@ -103,6 +104,7 @@ Scratch carve_scratch(const ia_layer_cfg* c, void* base) {
   s.live_kt = (uint32_t*)a.take(ia_ktile_mask_bytes((int)M));
   // ... and which 32-row blocks of the data gradients do (the live list and the dead list, ia_row_blocks)
   s.row_blk = (int*)a.take(ia_row_blocks_bytes((int)M));
+  s.pack_blk = (int*)a.take(ia_row_groups_packed_bytes((int)M));
   s.out_kt = (uint32_t*)a.take(ia_ktile_mask_bytes((int)M));
   s.out_blk = (int*)a.take(ia_row_blocks_bytes((int)M));
   s.out_grp = (int*)a.take(ia_row_groups_bytes((int)M));
@@ -124,6 +126,11 @@ int g_out_rows = 1;
 // out_row_live (ia_layer_cfg): the rows the caller reads of this layer's output, and the only rows whose incoming gradient is not zero.
 // Everything behind the attention runs these rows only; in front of it every row is a key and stays.  Padded rows only.
 const uint8_t* out_live(const ia_layer_cfg* c) { return (c->out_row_live && !c->cu_seqlens && g_out_rows) ? c->out_row_live : nullptr; }
+// ... and 0 makes them ignore ia_layer_cfg::out_q_rows (ia_debug_q_rows)
+int g_q_rows = 1;
+// out_q_rows (ia_layer_cfg): out_row_live is zero at every position >= n of every sequence, so the attention output there is unread and
+// its gradient exactly zero -- the attention forward and backward run the query blocks in front of n only.  Only together with out_row_live.
+int out_q_rows(const ia_layer_cfg* c) { return (out_live(c) && c->out_q_rows > 0 && g_q_rows) ? c->out_q_rows : 0; }
 
 #define IA_TRY(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
 
@@ -131,9 +138,11 @@ const uint8_t* out_live(const ia_layer_cfg* c) { return (c->out_row_live && !c->
 // provides one (both operands k-contiguous: the faster form, ia_layer_weights::wt_*), else W read k-strided.
 // With a block list (ia_row_blocks), over the 32-row blocks that hold a live row only; the other rows of dx are written as zeros.
 int dgrad(const void* dy, int k_out, const void* w, const void* wt, int n_in, void* dx, int M, int epilogue, const void* aux, int ldaux, void* c2,
-          void* ws, size_t ws_bytes, ia_stream_t st, const int* row_blk = nullptr, const int* row_grp = nullptr) {
+          void* ws, size_t ws_bytes, ia_stream_t st, const int* row_blk = nullptr, const int* row_grp = nullptr, const int* row_pack = nullptr) {
   if (row_grp && epilogue == IA_EPI_DGELU_COLSUM)      // whole 128-row groups: the column sums keep the dense kernel's partials
     return ia_gemm_dgrad_groups(dy, k_out, wt ? wt : w, wt ? 0 : 1, wt ? k_out : n_in, dx, n_in, M, n_in, k_out, aux, ldaux, c2, row_grp, ws, ws_bytes, st);
+  if (row_pack && epilogue == IA_EPI_DGELU_COLSUM)     // live blocks packed by whole groups: every group's partial keeps its slot and its bits
+    return ia_gemm_dgrad_packed(dy, k_out, wt ? wt : w, wt ? 0 : 1, wt ? k_out : n_in, dx, n_in, M, n_in, k_out, aux, ldaux, c2, row_pack, ws, ws_bytes, st);
   if (row_blk)
     return ia_gemm_dgrad_blocks(dy, k_out, wt ? wt : w, wt ? 0 : 1, wt ? k_out : n_in, dx, n_in, M, n_in, k_out, epilogue, aux, ldaux, c2, row_blk,
                                 ws, ws_bytes, st);
@@ -170,7 +179,9 @@ int attn_fwd(const ia_layer_cfg* c, const char* qkv, const uint8_t* key_mask, ch
   if (c->cu_seqlens)
     return (ps ? ia_attn_fwd_varlen_ps : ia_attn_fwd_varlen)(qkv, qkv + (size_t)H * 2, qkv + (size_t)2 * H * 2, 3 * H, c->cu_seqlens, c->total_tokens, ctx, H, lse, c->B, c->nh,
                               c->L, scale, drop, seed, st);
-  return (ps ? ia_attn_fwd_ps : ia_attn_fwd)(qkv, qkv + (size_t)H * 2, qkv + (size_t)2 * H * 2, 3 * H, key_mask, ctx, H, lse, c->B, c->nh, c->L, scale, drop, seed, st);
+  // (the rows the limit skips leave the kernel as zeros: the stash's ctx is finite in every row, whatever the buffer held)
+  return ia_attn_fwd_q_rows(ps ? IA_ATTN_Q_PRESCALED : 0, qkv, qkv + (size_t)H * 2, qkv + (size_t)2 * H * 2, 3 * H, key_mask, ctx, H, lse, c->B, c->nh,
+                            c->L, scale, drop, seed, out_q_rows(c), st);
 }
 
 // attention backward + the QKV bias gradient (+= into db_qkv): padded rows take the column sums out of the attention kernels'
@@ -185,8 +196,9 @@ int attn_bwd(const ia_layer_cfg* c, const char* qkv, const uint8_t* key_mask, co
     return rc ? rc : ia_colsum(gqkv, 3 * H, (int)rows_of(c), 3 * H, db_qkv, 1, ws, ws_bytes, st);
   }
   const int flags = (ps ? IA_ATTN_Q_PRESCALED : 0) | ((c->masked_rows_dead & 1) ? IA_ATTN_MASKED_ROWS_DEAD : 0);
-  return ia_attn_bwd_bias_ex(flags, qkv, qkv + (size_t)H * 2, qkv + (size_t)2 * H * 2, 3 * H, key_mask, ctx, dctx, H, lse, delta, gqkv,
-                             gqkv + (size_t)H * 2, gqkv + (size_t)2 * H * 2, 3 * H, db_qkv, ws, ws_bytes, c->B, c->nh, c->L, scale, drop, seed, st);
+  return ia_attn_bwd_bias_q_rows(flags, qkv, qkv + (size_t)H * 2, qkv + (size_t)2 * H * 2, 3 * H, key_mask, ctx, dctx, H, lse, delta, gqkv,
+                                 gqkv + (size_t)H * 2, gqkv + (size_t)2 * H * 2, 3 * H, db_qkv, ws, ws_bytes, c->B, c->nh, c->L, scale, drop, seed,
+                                 out_q_rows(c), st);
 }
 
 // Every launch of one layer forward.  keep = the training form, which leaves what the backward needs in s: the dropout masks' seeds,
@@ -282,6 +294,12 @@ extern "C" int ia_debug_out_rows(int on) {
   return was;
 }
 
+extern "C" int ia_debug_q_rows(int on) {
+  const int was = g_q_rows;
+  g_q_rows = on ? 1 : 0;
+  return was;
+}
+
 extern "C" int ia_debug_dgrad_rows(int on) {
   const int was = g_dgrad_rows;
   g_dgrad_rows = on ? 1 : 0;
@@ -370,6 +388,13 @@ extern "C" int ia_layer_bwd2(const ia_layer_cfg* c, const ia_layer_weights* w, c
     const int* const row_blk = (live && g_dgrad_rows) ? (c->row_blocks ? c->row_blocks : k.row_blk) : nullptr;
     if (live && !c->live_ktiles) IA_TRY(ia_ktile_mask(live, M, k.live_kt, st));
     if (row_blk && !c->row_blocks) IA_TRY(ia_row_blocks(live, M, k.row_blk, st));
+    // ... and the x gelu' + column-sums data gradient the same blocks packed by whole 128-row groups (ia_row_groups_packed): the caller's list
+    // behind its row_blocks (masked_rows_dead bit 3), or one per call.  ia_debug_dgrad_rows withholds it with the block list.
+    const int* row_pack = nullptr;
+    if (row_blk && (size_t)M <= (size_t)128 * 4096) {
+      if (c->row_blocks && (c->masked_rows_dead & 4)) row_pack = (const int*)((const char*)c->row_blocks + ia_row_groups_packed_offset(M));
+      else { IA_TRY(ia_row_groups_packed(live, M, k.pack_blk, st)); row_pack = k.pack_blk; }
+    }
     // behind the attention: out_row_live's lists when given (a subset of the live keys), else the key mask's
     const uint8_t* const live2 = olive ? olive : live;
     const uint32_t* const kt2 = olive ? okt : live_kt;
@@ -382,10 +407,12 @@ extern "C" int ia_layer_bwd2(const ia_layer_cfg* c, const ia_layer_weights* w, c
     const char* d_ffn = drop ? k.g1 : k.g0;
     IA_TRY(wgrad(d_ffn, H, s.hact, I, (float*)g->w_fc2, M, kt2, k.gws, k.gws_bytes, st));
     // d(pre-activation) = (d_ffn W2) * gelu'(pre), and its column sums (the fc1 bias gradient) out of the same epilogue.
-    // ogrp == NULL: every row.  The block remap serves this epilogue, but its column-sum partials would cover other rows and the fc1 bias
-    // gradient would equal the unfiltered one only up to fp32 summation order; the backward stays bit-identical to masked_rows_dead = 0.
+    // The plain block remap would regroup the column-sum partials (the fc1 bias gradient then equals the unfiltered one only up to fp32
+    // summation order), so this GEMM takes the blocks packed by whole 128-row groups: each group's partial is formed by one wave from that
+    // group's live blocks in order and stored in the group's slot -- bit-identical to masked_rows_dead = 0 (ia_gemm_dgrad_packed).
     // ogrp (out_row_live): whole 128-row groups drop out, which leaves every kept partial where and what it was (ia_gemm_dgrad_groups).
-    IA_TRY(dgrad(d_ffn, H, w->w_fc2, w->wt_fc2, I, k.gI, M, IA_EPI_DGELU_COLSUM, s.hpre, I, g->b_fc1, k.ws, k.ws_bytes, st, nullptr, ogrp));
+    // Neither list: every row.
+    IA_TRY(dgrad(d_ffn, H, w->w_fc2, w->wt_fc2, I, k.gI, M, IA_EPI_DGELU_COLSUM, s.hpre, I, g->b_fc1, k.ws, k.ws_bytes, st, nullptr, ogrp, row_pack));
     IA_TRY(wgrad(k.gI, I, s.ln, H, (float*)g->w_fc1, M, kt2, k.gws, k.gws_bytes, st));
     IA_TRY(dgrad(k.gI, I, w->w_fc1, w->wt_fc1, H, k.g2, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, blk2));
     // LN1 backward: d(y1) = g2 (through fc1) + g0 (residual into LN2) -> dz1 (the layer input's residual-path gradient) in

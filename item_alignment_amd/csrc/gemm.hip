@@ -106,6 +106,10 @@ struct GemmArgs {
   // EPI_ROWS + EPI_DGELU_CS: the list is group-aligned (ia_row_groups: entries 4i .. 4i+3 are the four 32-row blocks of ONE 128-row group,
   // so a wave's four block slots are one group in order) and the wave writes its column-sum partial to THAT group's slot of csum_part,
   // where the dense kernel puts it: the second stage then adds the same fp32 terms in the same places (dead groups' slots are zeroed)
+  // 2: the list is block-packed (ia_row_groups_packed): a wave's four slots hold the live blocks of one or more whole groups, each group's
+  // blocks contiguous and ascending, empty slots (-1) behind them.  The wave folds and stores its column sums where the group changes,
+  // into that group's slot, and starts the next group from zero: a lane adds the rows of a group's live blocks in the dense kernel's
+  // order with nothing in between (the blocks left out added +-0 there), so every partial keeps its bits.  The fill zeroes all slots.
   int rows_grouped;
 };
 
@@ -198,7 +202,11 @@ constexpr int epi_extra_stores() { return EPI == EPI_DGELU_CS ? 2 : 0; }     // 
 // BUF (full tiles of the one-wave-per-SIMD kernel, bf16 outputs): the output streams are addressed through buffer windows over the
 // wave's rows with one 32-bit lane offset (io.off) instead of 64-bit pointer arithmetic per access (3 VALU instructions each)
 struct BufIO { __amdgpu_buffer_rsrc_t rsC, rsC2; uint32_t off; };
-template <int EPI, bool OUTF32, bool PRE, bool BUF = false>
+// PIN (the remapped x gelu' + column-sums forms): the column-sum arithmetic written out the way the compiled DENSE kernel does it, which
+// differs between its two epilogue paths -- prefetched (full tiles): the product is rounded, then added; guarded (edge tiles): one fused
+// multiply-add -- so that a group's partial keeps its bits wherever the remap puts the group, as long as it takes the path the dense
+// kernel gives it (left to the compiler, the remapped kernel fused some of its prefetched slices and not others).
+template <int EPI, bool OUTF32, bool PRE, bool BUF = false, bool PIN = false>
 IA_DEV void epi_store8(const GemmArgs& p, int m, int n, f32x4 lo, f32x4 hi, f32x4 pb0, f32x4 pb1, bf16x8 ax, float (&cs)[8], const BufIO* io = nullptr) {
   float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
   if (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_GELU_ACT || EPI == EPI_BIAS_ADD) {
@@ -263,6 +271,21 @@ IA_DEV void epi_store8(const GemmArgs& p, int m, int n, f32x4 lo, f32x4 hi, f32x
 #pragma unroll
     for (int i = 0; i < 4; ++i) { v[2 * i] = act[i][0]; v[2 * i + 1] = act[i][1]; }
   }
+  if constexpr (EPI == EPI_DGELU_CS && PIN) {
+    const bf16x8 a = PRE ? ax : *reinterpret_cast<const bf16x8*>(p.aux + (size_t)m * p.ldaux + n);
+    if (PRE) {
+#pragma clang fp contract(off)
+#pragma unroll
+      for (int r = 0; r < 8; ++r) { v[r] *= bf2f(a[r]); cs[r] += v[r]; }
+    } else {
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        const float x = v[r], y = bf2f(a[r]);
+        v[r] = x * y;
+        cs[r] = __builtin_fmaf(x, y, cs[r]);
+      }
+    }
+  } else
   if (EPI == EPI_ADD || EPI == EPI_BIAS_ADD || EPI == EPI_DGELU || EPI == EPI_DGELU_CS) {
     const bf16x8 a = PRE ? ax : *reinterpret_cast<const bf16x8*>(p.aux + (size_t)m * p.ldaux + n);
 #pragma unroll
@@ -1197,14 +1220,38 @@ IA_DEV void drain_half(const GemmArgs& p, f32x16 (&acc)[4][4], int m0, int n0, c
             asm volatile("" ::: "memory");      // the load stays in front of this slice's store (hipcc would sink it behind)
           }
           io.off = voffC + (uint32_t)(((ROWS ? rb.r[mi] : mi * 32) + it * 8) * p.ldc * 2);
-          if (!(IA_DBG(p) & 64)) epi_store8<EPI, OUTF32, true, BUF>(p, m, n, lo[it], hi[it], pb0, pb1, ax[c % (AHEAD + 1)], cs, &io);
+          if (!(IA_DBG(p) & 64)) epi_store8<EPI, OUTF32, true, BUF, ROWS>(p, m, n, lo[it], hi[it], pb0, pb1, ax[c % (AHEAD + 1)], cs, &io);
         } else {
-          if ((!ROWS || rb.r[mi] >= 0) && m < p.M && n < p.N && !(IA_DBG(p) & 64)) epi_store8<EPI, OUTF32, false>(p, m, n, lo[it], hi[it], pb0, pb1, ax[0], cs);
+          if ((!ROWS || rb.r[mi] >= 0) && m < p.M && n < p.N && !(IA_DBG(p) & 64)) epi_store8<EPI, OUTF32, false, false, ROWS>(p, m, n, lo[it], hi[it], pb0, pb1, ax[0], cs);
         }
         if (IA_DBG(p) & 64) asm volatile("" : : "v"(lo[it]), "v"(hi[it]));
       }
+      // GemmArgs::rows_grouped == 2 (block-packed list): block mi closes its group's run when the next slot is empty, belongs to another
+      // group, or does not exist -- the same fold as below, the store into THAT group's slot, and the sums start again from zero.  A wave
+      // with a block has at least one run, i.e. at least the two stores PEND counts: the counted wait in front of the next tile's
+      // main loop only gets stricter by the further ones (wave-uniform conditions: the block rows are scalars).
+      if constexpr (ROWS && EPI == EPI_DGELU_CS) {
+        if (p.rows_grouped == 2 && rb.r[mi] >= 0 && (mi == 3 || rb.r[mi < 3 ? mi + 1 : 3] < 0 || (rb.r[mi < 3 ? mi + 1 : 3] >> 7) != (rb.r[mi] >> 7))) {
+#pragma unroll
+          for (int r = 0; r < 8; ++r) {
+            float v = cs[r];
+            v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, v), __builtin_bit_cast(int, v), 0x128, 0xF, 0xF, false));
+            cs[r] = ia_add_xor32(ia_add_xor16(v));
+          }
+          if (rrow == 0 && n0 + c8 * 8 < p.N) {
+            float* dst = p.csum_part + (size_t)(rb.r[mi] >> 7) * p.N + n0 + c8 * 8;
+            gstore16(dst, f32x4{cs[0], cs[1], cs[2], cs[3]});
+            gstore16(dst + 4, f32x4{cs[4], cs[5], cs[6], cs[7]});
+          }
+#pragma unroll
+          for (int r = 0; r < 8; ++r) cs[r] = 0.f;
+        }
+      }
     }
     if (EPI == EPI_DGELU_CS) {
+      bool packed = false;
+      if constexpr (ROWS) packed = p.rows_grouped == 2;      // (its partials left inside the block loop, fold_store below)
+      if (!packed) {
       // column sums of this half's 128 rows: the 8 lanes that share a column group (lane & 7) differ in lane bits 3..5
 #pragma unroll
       for (int r = 0; r < 8; ++r) {
@@ -1222,6 +1269,7 @@ IA_DEV void drain_half(const GemmArgs& p, f32x16 (&acc)[4][4], int m0, int n0, c
         float* dst = p.csum_part + (size_t)slot * p.N + n0 + c8 * 8;
         gstore16(dst, f32x4{cs[0], cs[1], cs[2], cs[3]});
         gstore16(dst + 4, f32x4{cs[4], cs[5], cs[6], cs[7]});
+      }
       }
     }
   };
@@ -1475,7 +1523,19 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
       RowBlk rb;
 #pragma unroll
       for (int mi = 0; mi < 4; ++mi) rb.r[mi] = (wm ? bl.b[4 + mi] : bl.b[mi]) * 32;      // (-1 -> negative: none)
-      const bool rows_ok = bl.b[7] >= 0 && bl.b[7] * 32 + 32 <= p.M;
+      bool rows_ok = bl.b[7] >= 0 && bl.b[7] * 32 + 32 <= p.M;
+      if constexpr (EPI == EPI_DGELU_CS) {
+        // block-packed list: empty slots lie inside a tile.  Their loads and stores fall outside the buffer windows (a negative row: zeros
+        // read, nothing written) and still count as issued.  Decided per wave, as the dense kernel decides per 128-row group: the
+        // prefetched epilogue when the wave has a block (it then stores at least one partial: the store count PEND stands for) and
+        // every group it holds lies inside M whole; the one group M may cut short sits in a wave-row of its own (ia_row_groups_packed)
+        // and takes the guarded epilogue, as it does in the dense kernel -- the two paths round the column sums differently (epi_store8)
+        if (p.rows_grouped == 2) {
+          rows_ok = rb.r[0] >= 0;
+#pragma unroll
+          for (int mi = 0; mi < 4; ++mi) rows_ok = rows_ok && (rb.r[mi] < 0 || (rb.r[mi] | 127) < p.M);
+        }
+      }
       full_e = rows_ok && n0_pre + 128 <= p.N;
       if (!(IA_DBG(p) & 32)) {
         if constexpr (EPI == EPI_NONE) {
@@ -1875,7 +1935,10 @@ __global__ __launch_bounds__(256) void zero_dead_rows_kernel(const int* __restri
       if (r < M) *reinterpret_cast<u32x4*>(C + (size_t)r * ldc + c) = z;
     }
   }
-  if (csum_part && grouped) {
+  if (csum_part && grouped == 2) {      // block-packed list: every slot (a group without a live block stores none)
+    const size_t total = (size_t)part_rows * N;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) csum_part[i] = 0.f;
+  } else if (csum_part && grouped) {
     const int ngrp = (M + 127) >> 7;
     for (int d = blockIdx.x; d < n_dead + (part_rows - ngrp); d += gridDim.x) {
       const int g = d < n_dead ? ((dead[d] & 3) ? -1 : dead[d] >> 2) : ngrp + (d - n_dead);
@@ -2091,6 +2154,149 @@ extern "C" int ia_row_groups(const uint8_t* row_live, int M_rows, int* list, hip
   return ia_check_launch();
 }
 extern "C" int ia_row_groups_host(const uint8_t* row_live, int M_rows, int* list) { return row_blocks_host(row_live, M_rows, list, 2); }
+// ---- The block-packed list (GemmArgs::rows_grouped == 2): the layout of ia_row_blocks -- header, slots, dead blocks -- with four slots per
+// wave-row of the remapped kernel (eight per M-tile).  A wave-row holds the live 32-row blocks of one or more WHOLE 128-row groups: a group's
+// blocks are contiguous and ascending, no group spans two wave-rows, the slots behind the last group are -1.  Header: [0] slots in use
+// (4 x wave-rows), [1] dead blocks, [2] blocks.  Groups are placed by their number of live blocks (class) and their rank inside the class
+// (ascending group index), a closed form of the class counts, so the device builder and its host twin agree by construction:
+//   4 alone | each 3 with a 1 | 2 + 2 | an odd 2 left over with up to two 1s | the remaining 1s by four
+// (705-733 wave-rows on masks like the benchmark's 512 x 255 rows against ceil(live blocks / 4) = 683-700 and 946-952 whole live groups).
+// The last group when M cuts it short (M no multiple of 128) stays out of the classes and takes a wave-row of its own behind the others:
+// the dense kernel runs that group through its guarded epilogue, whose column sums round differently (epi_store8), and so must the remap.
+struct PackCounts { int n4, n3, n2, n1; };
+static __host__ __device__ inline int pack_left1(const PackCounts& n) { return n.n1 > n.n3 ? n.n1 - n.n3 : 0; }      // 1s not paired with a 3
+static __host__ __device__ inline int pack_take2(const PackCounts& n) { const int l = pack_left1(n); return (n.n2 & 1) ? (l < 2 ? l : 2) : 0; }
+static __host__ __device__ inline int pack_rows(const PackCounts& n) {
+  return n.n4 + n.n3 + ((n.n2 + 1) >> 1) + ((pack_left1(n) - pack_take2(n) + 3) >> 2);
+}
+// group of class c (1 .. 4 live blocks), rank r in its class -> first slot, and how many -1 slots it writes behind its blocks
+static __host__ __device__ inline void pack_place(const PackCounts& n, int c, int r, int& slot, int& pad) {
+  const int base2 = n.n4 + n.n3, base1 = base2 + ((n.n2 + 1) >> 1), take2 = pack_take2(n);
+  pad = 0;
+  if (c == 4) slot = 4 * r;
+  else if (c == 3) { slot = 4 * (n.n4 + r); pad = r < n.n1 ? 0 : 1; }
+  else if (c == 2) { slot = 4 * (base2 + (r >> 1)) + 2 * (r & 1); pad = ((n.n2 & 1) && r == n.n2 - 1 && take2 == 0) ? 2 : 0; }
+  else if (r < n.n3) slot = 4 * (n.n4 + r) + 3;
+  else if (r - n.n3 < take2) { slot = 4 * (base2 + (n.n2 >> 1)) + 2 + (r - n.n3); pad = (r - n.n3 == take2 - 1) ? 2 - take2 : 0; }
+  else {
+    const int q = r - n.n3 - take2;
+    slot = 4 * base1 + q;
+    pad = r == n.n1 - 1 ? 3 - (q & 3) : 0;
+  }
+}
+namespace {
+constexpr int PACK_MAX_GROUPS = 64 * 64;      // one wave, at most 64 rounds of 64 groups (M <= 524 288 rows)
+// One wave, no LDS (see row_blocks_kernel).  Lane l owns groups 64 i + l: the four block flags of up to 64 groups sit in four 64-bit words
+// per lane, a first pass of ballots counts the classes, a second one ranks every group in its class and among the dead blocks; each lane
+// then writes its groups' slots (every slot exactly once: no fill pass) and dead-list entries.
+__global__ __launch_bounds__(64) void row_groups_packed_kernel(const uint8_t* __restrict__ row_live, int M, int nb, int* __restrict__ out) {
+  const int nbr = (nb + 7) & ~7, ngrp = (nb + 3) >> 2;
+  int* const live = out + t256w::ROW_BLK_HDR;
+  int* const dead = live + nbr;
+  const int lane = threadIdx.x;
+  const uint64_t lt = (1ull << lane) - 1ull;
+  uint64_t f[4] = {0, 0, 0, 0};
+  for (int i = 0; i * 64 < ngrp; ++i) {
+    const int g = i * 64 + lane;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (g < ngrp && 4 * g + j < nb && row_block_live(row_live, M, 4 * g + j)) f[j] |= 1ull << i;
+  }
+  auto cls = [&](int i) { return (int)((f[0] >> i) & 1ull) + (int)((f[1] >> i) & 1ull) + (int)((f[2] >> i) & 1ull) + (int)((f[3] >> i) & 1ull); };
+  const int cut = (M & 127) ? ngrp - 1 : -1;     // the group M cuts short: outside the classes, a wave-row of its own at the end
+  int cnt[5] = {0, 0, 0, 0, 0}, cut_rows = 0;
+  for (int i = 0; i * 64 < ngrp; ++i) {
+    const bool is_cut = i * 64 + lane == cut;
+    const int c = is_cut ? 0 : cls(i);
+#pragma unroll
+    for (int k = 1; k <= 4; ++k) cnt[k] += __popcll(__ballot(c == k));
+    cut_rows += __ballot(is_cut && cls(i) > 0) ? 1 : 0;
+  }
+  const PackCounts n{cnt[4], cnt[3], cnt[2], cnt[1]};
+  int rank[5] = {0, 0, 0, 0, 0}, dbase = 0;
+  for (int i = 0; i * 64 < ngrp; ++i) {
+    const int g = i * 64 + lane, c_all = cls(i), c = g == cut ? 0 : c_all;
+    int nblk = g < ngrp ? nb - 4 * g : 0;
+    nblk = nblk > 4 ? 4 : nblk;
+    const int nd = nblk - c_all;                 // dead blocks of this group
+    int r = 0, dpos = dbase;
+#pragma unroll
+    for (int k = 1; k <= 4; ++k) {
+      const uint64_t b = __ballot(c == k), d = __ballot(nd >= k);
+      if (c == k) r = rank[k] + __popcll(b & lt);
+      rank[k] += __popcll(b);
+      dpos += __popcll(d & lt);
+      dbase += __popcll(d);
+    }
+    if (g < ngrp) {
+      if (c_all > 0) {
+        int slot, pad;
+        if (g == cut) { slot = 4 * pack_rows(n); pad = 4 - c_all; }
+        else pack_place(n, c, r, slot, pad);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if ((f[j] >> i) & 1ull) live[slot++] = 4 * g + j;
+        for (int k = 0; k < pad; ++k) live[slot++] = -1;
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (j < nblk && !((f[j] >> i) & 1ull)) dead[dpos++] = 4 * g + j;
+    }
+  }
+  if (lane < t256w::ROW_BLK_HDR) out[lane] = lane == 0 ? 4 * (pack_rows(n) + cut_rows) : (lane == 1 ? dbase : (lane == 2 ? nb : 0));
+}
+}  // namespace
+extern "C" size_t ia_row_groups_packed_bytes(int M_rows) { return ia_row_blocks_bytes(M_rows); }
+// where the packed list sits behind an ia_row_blocks list in ONE buffer (ia_layer_cfg::masked_rows_dead bit 3): byte offset from its start
+extern "C" size_t ia_row_groups_packed_offset(int M_rows) { return al256(ia_row_blocks_bytes(M_rows)); }
+extern "C" int ia_row_groups_packed(const uint8_t* row_live, int M_rows, int* list, hipStream_t stream) {
+  (void)hipGetLastError();
+  if (!row_live || !list || M_rows <= 0 || ((uintptr_t)list & 31)) return IA_ERR_ARG;
+  if ((M_rows + 127) / 128 > PACK_MAX_GROUPS) return IA_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(row_groups_packed_kernel, dim3(1), dim3(64), 0, stream, row_live, M_rows, (M_rows + 31) / 32, list);
+  return ia_check_launch();
+}
+extern "C" int ia_row_groups_packed_host(const uint8_t* row_live, int M_rows, int* list) {
+  if (!row_live || !list || M_rows <= 0) return IA_ERR_ARG;
+  if ((M_rows + 127) / 128 > PACK_MAX_GROUPS) return IA_ERR_UNSUPPORTED;
+  const int nb = (M_rows + 31) / 32, nbr = (nb + 7) & ~7, ngrp = (nb + 3) >> 2;
+  int* const live = list + t256w::ROW_BLK_HDR;
+  int* const dead = live + nbr;
+  PackCounts n{0, 0, 0, 0};
+  auto cls = [&](int g) {
+    int c = 0;
+    for (int j = 0; j < 4 && 4 * g + j < nb; ++j) c += row_block_live(row_live, M_rows, 4 * g + j) ? 1 : 0;
+    return c;
+  };
+  const int cut = (M_rows & 127) ? ngrp - 1 : -1;      // the group M cuts short: a wave-row of its own at the end
+  for (int g = 0; g < ngrp; ++g) {
+    const int c = g == cut ? 0 : cls(g);
+    if (c == 4) ++n.n4; else if (c == 3) ++n.n3; else if (c == 2) ++n.n2; else if (c == 1) ++n.n1;
+  }
+  int rank[5] = {0, 0, 0, 0, 0}, n_dead = 0, cut_rows = 0;
+  for (int g = 0; g < ngrp; ++g) {
+    const int c = cls(g);
+    int slot = 0, pad = 0;
+    if (g == cut && c > 0) { slot = 4 * pack_rows(n); pad = 4 - c; cut_rows = 1; }
+    else if (c > 0) pack_place(n, c, rank[c]++, slot, pad);
+    for (int j = 0; j < 4 && 4 * g + j < nb; ++j) {
+      if (row_block_live(row_live, M_rows, 4 * g + j)) live[slot++] = 4 * g + j; else dead[n_dead++] = 4 * g + j;
+    }
+    for (int k = 0; k < pad; ++k) live[slot++] = -1;
+  }
+  for (int i = 0; i < t256w::ROW_BLK_HDR; ++i) list[i] = 0;
+  list[0] = 4 * (pack_rows(n) + cut_rows); list[1] = n_dead; list[2] = nb;
+  return IA_OK;
+}
+// The x gelu' + column-sums data gradient over a block-packed list: dX = (dY W) * aux on the live 32-row blocks, the other rows as zeros, and
+// C2 += the column sums, bit-identical to ia_gemm_bf16's (IA_EPI_DGELU_COLSUM) on a dY whose rows are zero wherever the list has no block.
+// A shape the remapped kernel does not serve runs every row.
+extern "C" int ia_gemm_dgrad_packed(const void* dY, int ldy, const void* W, int w_kstrided, int ldw, void* dX, int ldx, int M_rows, int N_in, int K_out,
+                                    const void* aux, int ldaux, void* C2, const int* packed_list, void* workspace, size_t workspace_bytes,
+                                    hipStream_t stream) {
+  return gemm_core(dY, 0, ldy, W, w_kstrided, ldw, dX, 0, ldx, M_rows, N_in, K_out, EPI_DGELU_CS, nullptr, aux, ldaux, C2, 0, workspace,
+                   workspace_bytes, nullptr, stream, 0, 1.f, nullptr, packed_list, 1, 0, packed_list ? 2 : 0);
+}
 // library-internal (common.h): the data gradient with a list already built (ia_layer_bwd2 builds one per call for its four)
 int ia_gemm_dgrad_blocks(const void* dY, int ldy, const void* W, int w_kstrided, int ldw, void* dX, int ldx, int M_rows, int N_in, int K_out,
                          int epilogue, const void* aux, int ldaux, void* C2, const int* row_blocks, void* workspace, size_t workspace_bytes,
@@ -2350,7 +2556,7 @@ static int gemm_core(const void* A, int a_kstrided, int lda, const void* B, int 
   g.row_blk = nullptr; g.rows_fill = rows_fill; g.fill_m = M; g.rows_guarded = tail_of ? 1 : 0;
   if (!a_kstrided && !c_is_f32 && (epilogue == EPI_NONE || epilogue == EPI_ADD || epilogue == EPI_DGELU_CS || fwd_epi))
     g.row_blk = (row_blocks && big && !g.dbg && !(N & 7) && dgrad_rows_fit(M, lda, ldc, aux ? ldaux : 0)) ? row_blocks : nullptr;
-  g.rows_grouped = (g.row_blk && epilogue == EPI_DGELU_CS && rows_grouped) ? 1 : 0;
+  g.rows_grouped = (g.row_blk && epilogue == EPI_DGELU_CS && rows_grouped) ? rows_grouped : 0;
   // Scaled columns, M no multiple of 128: the dense kernel rounds the rows behind the last whole 128-row part of M as (acc + bias) * scale
   // (guarded row-layout epilogue) and the others as acc * scale + bias * scale (accumulator-layout epilogue).  The remap would mix the two
   // in one wave, so the remapped launch covers the whole parts and the (at most four) blocks behind them get a remapped launch of their

@@ -195,13 +195,18 @@ class EncoderStackFn(torch.autograd.Function):
         flag = cfgs[0].masked_rows_dead
         if key_mask is not None and cu_seqlens is None and not cfgs[0].pre_ln and ((flag & 1 and keep) or (flag & 3) == 3):
             M = cur.shape[0]
-            lb = (lib.ia_row_blocks_bytes(M) + 255) & ~255
-            lists = torch.empty(lb + lib.ia_ktile_mask_bytes(M), device=x.device, dtype=torch.uint8)
+            lb = lib.ia_row_groups_packed_offset(M)        # (= the block list's size rounded up to 256 bytes)
+            packed = keep and M <= 128 * 4096              # the backward's x gelu' data gradient: the live blocks packed by whole groups
+            lists = torch.empty(2 * lb + lib.ia_ktile_mask_bytes(M), device=x.device, dtype=torch.uint8)
             check(lib.ia_row_blocks(mp, M, lists.data_ptr(), stream_ptr()), "ia_row_blocks")
+            if packed:
+                check(lib.ia_row_groups_packed(mp, M, lists.data_ptr() + lb, stream_ptr()), "ia_row_groups_packed")
             if keep:                                       # (the weight gradients' mask: nothing reads it without a backward)
-                check(lib.ia_ktile_mask(mp, M, lists.data_ptr() + lb, stream_ptr()), "ia_ktile_mask")
+                check(lib.ia_ktile_mask(mp, M, lists.data_ptr() + 2 * lb, stream_ptr()), "ia_ktile_mask")
             for c in cfgs:
-                c.row_blocks, c.live_ktiles = lists.data_ptr(), (lists.data_ptr() + lb) if keep else None
+                c.row_blocks, c.live_ktiles = lists.data_ptr(), (lists.data_ptr() + 2 * lb) if keep else None
+                if packed:
+                    c.masked_rows_dead |= 4                # ia_layer_cfg: the packed list sits behind row_blocks
             ctx.row_lists = lists
         # the caller reads row 0 of each sequence of the LAST layer's output and nothing else (stack._out_rows_cls, set by the model
         # classes for the one head that does: CoCaForItemAlignment with ensemble "sum"): ia_layer_cfg::out_row_live on that layer only
@@ -210,6 +215,7 @@ class EncoderStackFn(torch.autograd.Function):
             ctx.out_lists = cls_row_lists(B, L, x.device, key_mask)      # (kept until the backward has run)
             c = cfgs[-1]
             c.out_row_live, c.out_row_blocks, c.out_live_ktiles, c.out_row_groups = ctx.out_lists[1:]
+            c.out_q_rows = 1      # the mask is zero behind position 0 of every sequence: the layer's attention runs that query block only
         if keep:
             stash_bytes = lib.ia_layer_stash_bytes(C.byref(cfgs[0]))
             # one allocation per layer (4 GB each at the bench's shape), not one of n layers: a request for 90 GiB in one piece is served
