@@ -88,6 +88,19 @@ int ia_gemm_wgrad_rows(const void* dY, int ldy, const void* X, int ldx, float* d
 size_t ia_ktile_mask_bytes(int M_rows);
 int ia_ktile_mask(const uint8_t* row_live, int M_rows, uint32_t* mask, ia_stream_t stream);
 int ia_ktile_mask_host(const uint8_t* row_live, int M_rows, uint32_t* mask);
+/* The same filter at 32-row granularity, the mask handed in.  ia_kblock_mask: bit (b & 31) of mask[b >> 5] = OR of row_live over rows
+ * 32b .. 32b+31, clipped to M_rows; ia_kblock_mask_bytes(M_rows) bytes, one launch, plain stores; ia_kblock_mask_host: the same words from
+ * host memory (diagnostic hook, as ia_ktile_mask_host).  ORing adjacent bit pairs gives ia_ktile_mask's words.
+ * ia_gemm_wgrad_blocks: dW (+)= dY^T X over the 32-row blocks of k whose bit is set -- a block without a live row is neither fetched nor
+ * multiplied; the kernel walks the live blocks of each k-slab two to a 64-row k-tile.  Identical results on inputs that keep row_live's
+ * guarantee (every fp32 sum keeps its terms and their order).  kblock_mask: device pointer, NULL = the ia_gemm_bf16 call.  The workspace
+ * is the split-K one, ia_gemm_workspace_bytes(N_out, N_in, M_rows, 1).  Outputs too small for the 256 x 256-tile kernel, and k-slabs of
+ * more than 1024 k-tiles, read every row. */
+size_t ia_kblock_mask_bytes(int M_rows);
+int ia_kblock_mask(const uint8_t* row_live, int M_rows, uint32_t* mask, ia_stream_t stream);
+int ia_kblock_mask_host(const uint8_t* row_live, int M_rows, uint32_t* mask);
+int ia_gemm_wgrad_blocks(const void* dY, int ldy, const void* X, int ldx, float* dW, int ldw, int N_out, int N_in, int M_rows,
+                         const uint32_t* kblock_mask, int accumulate, void* workspace, size_t workspace_bytes, ia_stream_t stream);
 /* (ABI 18) The data gradient of a Linear over padded token rows: dX[M_rows, N_in] = dY[M_rows, K_out] W (+ epilogue), bf16 -- ia_gemm_bf16's
  * data-gradient form (A = dY k-contiguous; B = W [K_out, N_in] k-strided, w_kstrided = 1, or its transposed shadow [N_in, K_out],
  * w_kstrided = 0; epilogue IA_EPI_NONE, IA_EPI_ADD or IA_EPI_DGELU_COLSUM with aux / C2 as there) -- and a row filter.  row_live [M_rows]
@@ -700,7 +713,11 @@ typedef struct {
    * masked_rows_dead = 1.
    * (ABI 20, second form) Bit 3 (value 4), read by the backward together with row_blocks: the buffer row_blocks points into also holds the
    * block-packed list of the same mask (ia_row_groups_packed) at byte offset ia_row_groups_packed_offset(B * L); without the bit the
-   * backward builds that list per call.  The x gelu' + column-sums data gradient of a post-LN layer runs over it. */
+   * backward builds that list per call.  The x gelu' + column-sums data gradient of a post-LN layer runs over it.
+   * Bit 4 (value 8), read by the backward together with live_ktiles: live_ktiles points at a 32-row block mask (ia_kblock_mask) and the
+   * weight gradients walk live 32-row blocks; without the bit a caller's live_ktiles is a 64-row mask (ia_ktile_mask) and they walk live
+   * 64-row k-tiles.  Bit 5 (value 16): the same of out_live_ktiles.  With a NULL pointer the backward builds the block mask itself.
+   * No bit changes a gradient. */
   int masked_rows_dead;
   /* (ABI 19) optional, device pointers, NULL = the layer call builds its own: the 32-row block list (ia_row_blocks) and the live-k-tile
    * mask (ia_ktile_mask) of key_mask taken as row_live [B * L].  The mask is the same for every layer of a stack, forward and backward:

@@ -80,7 +80,7 @@ FwdBufs carve_infer(const ia_layer_cfg* c, void* base) {
 struct Scratch {
   char* g0; char* g1; char* g2; char* gI; char* gqkv; float* delta; char* ws; size_t ws_bytes; char* gws; size_t gws_bytes; uint32_t* live_kt; int* row_blk;
   int* pack_blk;      // masked_rows_dead: the block-packed list of the x gelu' data gradient (when the caller hands none behind row_blocks)
-  uint32_t* out_kt; int* out_blk; int* out_grp;      // out_row_live: its k-tile mask, block list and group list (when the caller hands none)
+  uint32_t* out_kt; int* out_blk; int* out_grp;      // out_row_live: its 32-row block mask (ia_kblock_mask), block list and group list (when the caller hands none)
   size_t bytes;
 };
 
@@ -100,12 +100,12 @@ Scratch carve_scratch(const ia_layer_cfg* c, void* base) {
   s.gws_bytes = max3(ia_gemm_workspace_bytes((int)(3 * H), (int)H, (int)M, 1), ia_gemm_workspace_bytes((int)I, (int)H, (int)M, 1),
                      max3(ia_gemm_workspace_bytes((int)H, (int)I, (int)M, 1), ia_gemm_workspace_bytes((int)H, (int)H, (int)M, 1), 0));
   s.gws = a.take(s.gws_bytes);
-  // masked_rows_dead: which 64-row k-tiles of the weight gradients hold a live row (one bit each)
-  s.live_kt = (uint32_t*)a.take(ia_ktile_mask_bytes((int)M));
+  // masked_rows_dead: which 32-row blocks of the weight gradients' k hold a live row (one bit each, ia_kblock_mask)
+  s.live_kt = (uint32_t*)a.take(ia_kblock_mask_bytes((int)M));
   // ... and which 32-row blocks of the data gradients do (the live list and the dead list, ia_row_blocks)
   s.row_blk = (int*)a.take(ia_row_blocks_bytes((int)M));
   s.pack_blk = (int*)a.take(ia_row_groups_packed_bytes((int)M));
-  s.out_kt = (uint32_t*)a.take(ia_ktile_mask_bytes((int)M));
+  s.out_kt = (uint32_t*)a.take(ia_kblock_mask_bytes((int)M));
   s.out_blk = (int*)a.take(ia_row_blocks_bytes((int)M));
   s.out_grp = (int*)a.take(ia_row_groups_bytes((int)M));
   s.bytes = a.bytes;
@@ -151,8 +151,11 @@ int dgrad(const void* dy, int k_out, const void* w, const void* wt, int n_in, vo
   return ia_gemm_bf16(dy, 0, k_out, w, 1, n_in, dx, 0, n_in, M, n_in, k_out, epilogue, nullptr, aux, ldaux, c2, 0, ws, ws_bytes, st);
 }
 
-// Weight gradient dW[n_out, n_in] += dy[M, n_out]^T x[M, n_in]; with a live-k-tile mask, over the k-tiles that hold a live row only
-int wgrad(const void* dy, int n_out, const void* x, int n_in, float* dw, int M, const uint32_t* live_kt, void* ws, size_t ws_bytes, ia_stream_t st) {
+// Weight gradient dW[n_out, n_in] += dy[M, n_out]^T x[M, n_in]; with a mask, over the 32-row blocks (kblocks: an ia_kblock_mask) or the
+// 64-row k-tiles (an ia_ktile_mask) that hold a live row only
+int wgrad(const void* dy, int n_out, const void* x, int n_in, float* dw, int M, const uint32_t* live_kt, bool kblocks, void* ws, size_t ws_bytes,
+          ia_stream_t st) {
+  if (live_kt && kblocks) return ia_gemm_wgrad_blocks(dy, n_out, x, n_in, dw, n_in, n_out, n_in, M, live_kt, 1, ws, ws_bytes, st);
   if (live_kt) return ia_gemm_wgrad_masked(dy, n_out, x, n_in, dw, n_in, n_out, n_in, M, live_kt, 1, ws, ws_bytes, st);
   return ia_gemm_bf16(dy, 1, n_out, x, 1, n_in, dw, 1, n_in, n_out, n_in, M, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 1, ws, ws_bytes, st);
 }
@@ -369,16 +372,19 @@ extern "C" int ia_layer_bwd2(const ia_layer_cfg* c, const ia_layer_weights* w, c
   // k-tile mask, block list and group list (the caller's, or built here) filter the kernels from the LN2 backward to the out-projection's
   // gradients; the attention backward and the QKV gradients keep the layer's other filter (every row is a key).
   const uint8_t* const olive = out_live(c);
+  // (a caller's out_live_ktiles is a 32-row block mask under masked_rows_dead bit 16, else a 64-row one; the one built here: 32-row)
   const uint32_t* okt = nullptr; const int* oblk = nullptr; const int* ogrp = nullptr;
+  bool okb = false;
   if (olive) {
     okt = c->out_live_ktiles; oblk = c->out_row_blocks; ogrp = c->out_row_groups;
-    if (!okt) { IA_TRY(ia_ktile_mask(olive, M, k.out_kt, st)); okt = k.out_kt; }
+    okb = !okt || (c->masked_rows_dead & 16);
+    if (!okt) { IA_TRY(ia_kblock_mask(olive, M, k.out_kt, st)); okt = k.out_kt; }
     if (!oblk) { IA_TRY(ia_row_blocks(olive, M, k.out_blk, st)); oblk = k.out_blk; }
     if (!ogrp) { IA_TRY(ia_row_groups(olive, M, k.out_grp, st)); ogrp = k.out_grp; }
   }
   if (!c->pre_ln) {
     // masked_rows_dead: every gradient row of a masked position is exactly zero (ia_layer_cfg): the LayerNorm backward kernels skip them,
-    // the four weight gradients skip the 64-row k-tiles that hold nothing else (one bitmask per call, in scratch), and the three plain data
+    // the four weight gradients skip the 32-row blocks of k that hold nothing else (one bitmask per call, in scratch; a caller's 64-row mask: the 64-row k-tiles), and the three plain data
     // gradients (fc1, out-projection, QKV) the 32-row blocks (one block list per call; their dead rows are written as zeros: the attention backward, the pair
     // kernels and the embedding backward read every row)
     // (the mask is the same for every layer of a stack and step: a caller that built the bitmask and the list once hands them in
@@ -386,7 +392,8 @@ extern "C" int ia_layer_bwd2(const ia_layer_cfg* c, const ia_layer_weights* w, c
     const uint8_t* const live = ((c->masked_rows_dead & 1) && !c->cu_seqlens) ? key_mask : nullptr;
     const uint32_t* const live_kt = live ? (c->live_ktiles ? c->live_ktiles : k.live_kt) : nullptr;
     const int* const row_blk = (live && g_dgrad_rows) ? (c->row_blocks ? c->row_blocks : k.row_blk) : nullptr;
-    if (live && !c->live_ktiles) IA_TRY(ia_ktile_mask(live, M, k.live_kt, st));
+    const bool live_kb = !c->live_ktiles || (c->masked_rows_dead & 8);      // a block mask: the one built here, or the caller's under bit 8
+    if (live && !c->live_ktiles) IA_TRY(ia_kblock_mask(live, M, k.live_kt, st));
     if (row_blk && !c->row_blocks) IA_TRY(ia_row_blocks(live, M, k.row_blk, st));
     // ... and the x gelu' + column-sums data gradient the same blocks packed by whole 128-row groups (ia_row_groups_packed): the caller's list
     // behind its row_blocks (masked_rows_dead bit 3), or one per call.  ia_debug_dgrad_rows withholds it with the block list.
@@ -399,13 +406,14 @@ extern "C" int ia_layer_bwd2(const ia_layer_cfg* c, const ia_layer_weights* w, c
     const uint8_t* const live2 = olive ? olive : live;
     const uint32_t* const kt2 = olive ? okt : live_kt;
     const int* const blk2 = olive ? oblk : row_blk;
+    const bool kb2 = olive ? okb : live_kb;
     // The two residual additions of a post-LN layer make each LayerNorm output's gradient a sum of two terms; both LayerNorm
     // backward kernels take the two terms (ia_ln_bwd2), so the GEMMs in front of them keep the plain epilogue.
     // LN2 backward: d(output) = dy (+ dy2) -> dz2 in g0, masked branch gradient -> g1 (or g0 when p == 0)
     IA_TRY(ia_ln_bwd2_rows(dy, dy2, nullptr, s.ffn, s.mean2, s.rstd2, w->ln2_g, k.g0, drop ? k.g1 : nullptr, g->ln2_g, g->ln2_b, g->b_fc2, M, H,
                            c->hidden_drop, c->seed, c->layer_id * 4u + 1u, live2, k.ws, k.ws_bytes, 1, st));
     const char* d_ffn = drop ? k.g1 : k.g0;
-    IA_TRY(wgrad(d_ffn, H, s.hact, I, (float*)g->w_fc2, M, kt2, k.gws, k.gws_bytes, st));
+    IA_TRY(wgrad(d_ffn, H, s.hact, I, (float*)g->w_fc2, M, kt2, kb2, k.gws, k.gws_bytes, st));
     // d(pre-activation) = (d_ffn W2) * gelu'(pre), and its column sums (the fc1 bias gradient) out of the same epilogue.
     // The plain block remap would regroup the column-sum partials (the fc1 bias gradient then equals the unfiltered one only up to fp32
     // summation order), so this GEMM takes the blocks packed by whole 128-row groups: each group's partial is formed by one wave from that
@@ -413,7 +421,7 @@ extern "C" int ia_layer_bwd2(const ia_layer_cfg* c, const ia_layer_weights* w, c
     // ogrp (out_row_live): whole 128-row groups drop out, which leaves every kept partial where and what it was (ia_gemm_dgrad_groups).
     // Neither list: every row.
     IA_TRY(dgrad(d_ffn, H, w->w_fc2, w->wt_fc2, I, k.gI, M, IA_EPI_DGELU_COLSUM, s.hpre, I, g->b_fc1, k.ws, k.ws_bytes, st, nullptr, ogrp, row_pack));
-    IA_TRY(wgrad(k.gI, I, s.ln, H, (float*)g->w_fc1, M, kt2, k.gws, k.gws_bytes, st));
+    IA_TRY(wgrad(k.gI, I, s.ln, H, (float*)g->w_fc1, M, kt2, kb2, k.gws, k.gws_bytes, st));
     IA_TRY(dgrad(k.gI, I, w->w_fc1, w->wt_fc1, H, k.g2, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, blk2));
     // LN1 backward: d(y1) = g2 (through fc1) + g0 (residual into LN2) -> dz1 (the layer input's residual-path gradient) in
     // dz1buf: the caller's dx2 when the split form is wanted, else g0 (in place over the term just consumed)
@@ -421,11 +429,11 @@ extern "C" int ia_layer_bwd2(const ia_layer_cfg* c, const ia_layer_weights* w, c
     IA_TRY(ia_ln_bwd2_rows(k.g2, k.g0, nullptr, s.proj, s.mean1, s.rstd1, w->ln1_g, dz1buf, drop ? k.g1 : nullptr, g->ln1_g, g->ln1_b, g->b_o, M, H,
                            c->hidden_drop, c->seed, c->layer_id * 4u + 0u, live2, k.ws, k.ws_bytes, 1, st));
     const char* d_att = drop ? k.g1 : dz1buf;
-    IA_TRY(wgrad(d_att, H, s.ctx, H, (float*)g->w_o, M, kt2, k.gws, k.gws_bytes, st));
+    IA_TRY(wgrad(d_att, H, s.ctx, H, (float*)g->w_o, M, kt2, kb2, k.gws, k.gws_bytes, st));
     // (d_ctx and dz1 are zeros outside out_row_live: the attention backward and the QKV data gradient's "+ dz1" read every live key's row)
     IA_TRY(dgrad(d_att, H, w->w_o, w->wt_o, H, k.g2, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, blk2));
     IA_TRY(attn_bwd(c, s.qkv, key_mask, s.ctx, k.g2, s.lse, k.delta, k.gqkv, g->b_qkv, k.ws, k.ws_bytes, scale, c->attn_drop, attn_seed, st));
-    IA_TRY(wgrad(k.gqkv, 3 * H, x, H, (float*)g->w_qkv, M, live_kt, k.gws, k.gws_bytes, st));
+    IA_TRY(wgrad(k.gqkv, 3 * H, x, H, (float*)g->w_qkv, M, live_kt, live_kb, k.gws, k.gws_bytes, st));
     if (dx2)   // split form: dx = the attention sub-block's data gradient, dx2 = dz1 (already written)
       IA_TRY(dgrad(k.gqkv, 3 * H, w->w_qkv, w->wt_qkv, H, dx, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, row_blk));
     else
@@ -433,15 +441,15 @@ extern "C" int ia_layer_bwd2(const ia_layer_cfg* c, const ia_layer_weights* w, c
   } else {
     if (!c->dy_colsum_done) IA_TRY(ia_colsum(dy, H, M, H, g->b_fc2, 1, k.ws, k.ws_bytes, st));
     // (okt / oblk / ogrp are NULL without out_row_live: the helpers then make the plain every-row calls)
-    IA_TRY(wgrad(dy, H, s.hact, I, (float*)g->w_fc2, M, okt, k.gws, k.gws_bytes, st));
+    IA_TRY(wgrad(dy, H, s.hact, I, (float*)g->w_fc2, M, okt, okb, k.gws, k.gws_bytes, st));
     IA_TRY(dgrad(dy, H, w->w_fc2, w->wt_fc2, I, k.gI, M, IA_EPI_DGELU_COLSUM, s.hpre, I, g->b_fc1, k.ws, k.ws_bytes, st, nullptr, ogrp));
-    IA_TRY(wgrad(k.gI, I, s.ln, H, (float*)g->w_fc1, M, okt, k.gws, k.gws_bytes, st));
+    IA_TRY(wgrad(k.gI, I, s.ln, H, (float*)g->w_fc1, M, okt, okb, k.gws, k.gws_bytes, st));
     IA_TRY(dgrad(k.gI, I, w->w_fc1, w->wt_fc1, H, k.g0, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, oblk));
     // LN2 backward (+ residual path dy) -> g1 = d x2 ; its column sum is the proj-bias gradient
     // (the row-filtered launch keeps every row's place in the partial sums: leaving out rows that add exact zeros changes no bit)
     IA_TRY(ia_ln_bwd2_rows(k.g0, nullptr, dy, s.proj, s.mean2, s.rstd2, w->ln2_g, k.g1, nullptr, g->ln2_g, g->ln2_b, g->b_o, M, H, 0.f, 0, 0, olive,
                            k.ws, k.ws_bytes, 1, st));
-    IA_TRY(wgrad(k.g1, H, s.ctx, H, (float*)g->w_o, M, okt, k.gws, k.gws_bytes, st));
+    IA_TRY(wgrad(k.g1, H, s.ctx, H, (float*)g->w_o, M, okt, okb, k.gws, k.gws_bytes, st));
     IA_TRY(dgrad(k.g1, H, w->w_o, w->wt_o, H, k.g2, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, oblk));
     IA_TRY(attn_bwd(c, s.qkv, key_mask, s.ctx, k.g2, s.lse, k.delta, k.gqkv, g->b_qkv, k.ws, k.ws_bytes, scale, 0.f, 0, st));
     IA_TRY(ia_gemm_bf16(k.gqkv, 1, 3 * H, s.xn, 1, H, g->w_qkv, 1, H, 3 * H, H, M, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 1, k.gws, k.gws_bytes, st));

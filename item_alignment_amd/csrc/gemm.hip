@@ -44,6 +44,12 @@ enum { EPI_NONE = 0, EPI_BIAS = 1, EPI_BIAS_GELU = 2, EPI_ADD = 3, EPI_DGELU = 4
 // the token rows as k: a k-tile whose rows of dY are all zeros adds +-0 to every accumulator, so leaving it out changes no bit of the
 // fp32 sums -- the k-slabs of a split-K launch and the order of the reduction stay what they are, a slab just takes fewer trips.
 constexpr int EPI_NONE_LIVE = 8;
+// EPI_NONE_BLK (library-internal, t256w only): the same walk at 32-row granularity.  A k-tile of the loop is made of TWO live 32-row blocks
+// of the slab, the next one of the ascending walk in its lower half (LDS rows 0 .. 31: DMA pieces 0 .. 3, k-steps 0 and 1) and the one
+// after it in its upper half (pieces 4 .. 7, k-steps 2 and 3).  A 32-row block is two whole 32x32x16 MFMAs per accumulator, so every
+// accumulator still sees the MFMAs of its live rows on the same operands in the same order, less those whose dY operand is all zeros:
+// no bit of the fp32 sums changes, and a slab takes ceil(live blocks / 2) trips.
+constexpr int EPI_NONE_BLK = 9;
 // EPI_ROWS + e (library-internal, t256w only; k-contiguous A, bf16 output): epilogue e behind a row remap.  The data gradient dX = dY W
 // (e = EPI_NONE, EPI_ADD or EPI_DGELU_CS) has the token rows as M: a row of dY that is all zeros gives a row of zeros, so only the 32-row
 // blocks that hold a live row are computed -- an M-tile is eight consecutive entries of the live-block list (GemmArgs::row_blk) instead
@@ -630,6 +636,8 @@ namespace t256w {
 constexpr int BM = 256, BN = 256, TILE_BYTES = 32768;        // one operand's k-tile: 256 rows x 64 k (or 64 k x 256 columns) of bf16
 constexpr int STAGE_BYTES = 16 * 64 * 4;                   // epilogue staging slot (16 rows x 64 columns fp32); each of the four waves owns two
 constexpr int LIVE_MAX_KTILES = 64 * 32;                   // EPI_NONE_LIVE: a k-slab's live-k-tile mask is one 32-bit word per lane
+constexpr int BLK_MAX_KTILES = LIVE_MAX_KTILES / 2;        // EPI_NONE_BLK: two mask bits per k-tile of the slab
+constexpr uint32_t OOB_HALF = 0x80000000u;                 // behind every buffer window (< 2 GiB), and three piece advances on top do not wrap
 constexpr int LDS_BYTES = 2 * 2 * TILE_BYTES + 8 * STAGE_BYTES;   // 128 KiB k-tile double buffer (A | B, twice) + 4 x 8 KiB = all 160 KiB of the CU
 
 // One operand's four fragments of a k-step.  A k-strided operand's fragment arrives as two transpose reads: the halves are kept
@@ -805,11 +813,14 @@ IA_DEV int live_next(LiveWalk& k, uint32_t mv) {
 
 // LIVE (both operands k-strided): the k loop runs over the n_tiles set bits of live_mv (the slab's live k-tiles, see LiveWalk) instead of
 // k-tiles 0 .. n_tiles-1 of the slab.
+// LIVE == 2 (EPI_NONE_BLK): over the n_blk set bits of live_mv, which are the slab's live 32-row blocks -- two per trip (n_tiles =
+// ceil(n_blk / 2)); the upper half of the last trip of an odd count goes out of range and arrives as zeros.
 // ROWS (k-contiguous A): piece j of A starts at row offset ro.o[j] (a scalar, where j * stepA sits otherwise) of a window over all of A.
-template <bool AKS, bool BKS, int PEND, bool PEEL_OK = true, bool LIVE = false, bool ROWS = false>
+template <bool AKS, bool BKS, int PEND, bool PEEL_OK = true, int LIVE = 0, bool ROWS = false>
 IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdgpu_buffer_rsrc_t rsA, __amdgpu_buffer_rsrc_t rsB, int xa, int xb,
                       int kt0, int ktaA0, int ktaB0, int n_tiles, int nk_all, int wm, int wn, int wave, int lane, bool prologue_only,
-                      bool stores_in_flight, uint32_t live_mv = 0u, RowOff ro = RowOff{}) {
+                      bool stores_in_flight, uint32_t live_mv = 0u, RowOff ro = RowOff{}, int n_blk = 0) {
+  constexpr bool BLK = LIVE == 2;
   static_assert(!ROWS || !AKS, "the row remap moves the pieces of a k-contiguous A");
   static_assert(!LIVE || (AKS && BKS), "the live-k-tile walk advances the running lane offsets of two k-strided operands");
   constexpr bool ROUND = !AKS && !BKS;      // the k loop's schedule (below)
@@ -833,7 +844,11 @@ IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdg
   // LIVE: the slab-relative indices of the first two live k-tiles (the prologue's)
   [[maybe_unused]] LiveWalk lw;
   int live0 = 0, live1 = 1;
-  if constexpr (LIVE) { live_start(lw, live_mv); live0 = live_next(lw, live_mv); live1 = live_next(lw, live_mv); }
+  [[maybe_unused]] int live0h = 0, live1h = 0;      // BLK: the upper halves' blocks (live0 / live1: the lower halves')
+  if constexpr (BLK) {
+    live_start(lw, live_mv);
+    live0 = live_next(lw, live_mv); live0h = live_next(lw, live_mv); live1 = live_next(lw, live_mv); live1h = live_next(lw, live_mv);
+  } else if constexpr (LIVE) { live_start(lw, live_mv); live0 = live_next(lw, live_mv); live1 = live_next(lw, live_mv); }
 
   // piece i (0..7: A, 8..15: B) of k-tile u -> buffer u & 1.  Branch-free (a branch next to the accumulator updates makes hipcc copy
   // all 256 of them): lim = number of valid k in this k-tile (0 for a k-tile past the end: the whole piece goes out of range and
@@ -842,6 +857,16 @@ IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdg
     const bool isB = i >= 8;
     const int j = i & 7;
     char* dst = my_part + (isB ? TILE_BYTES : 0) + (u & 1) * 2 * TILE_BYTES + j * 4096;
+    if constexpr (BLK) {
+      // pieces 0 .. 3: rows 0 .. 31 of the lower half's block, pieces 4 .. 7 of the upper half's; a half the slab has no block for goes out
+      // of range (zeros).  The whole row address sits in the lane offset: the partial last block of K ends at the window's end.
+      const int h = j >> 2;
+      const int b = u == 0 ? (h ? live0h : live0) : (h ? live1h : live1);
+      const uint32_t soff = (uint32_t)b * ((isB ? kstepB : kstepA) >> 1) + (uint32_t)(j & 3) * (isB ? stepB : stepA);
+      const uint32_t off = (dma_on && 2 * u + h < n_blk) ? (isB ? voffB : voffA) + soff : OOB;
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(isB ? rsB : rsA, IA_LDS(dst), 16, off, 0, 0, 0);
+      return;
+    }
     const int kt = kt0 + u;
     const int kta = (dbg & 4) ? 0 : (isB ? ktaB0 : ktaA0) + (LIVE ? (u == 0 ? live0 : live1) : u);      // dbg 4: every k-tile re-fetches k-tile 0 (cache-resident)
     const bool ks = isB ? BKS : AKS;
@@ -881,13 +906,26 @@ IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdg
 
   // second schedule (a k-strided operand): in-loop pieces of k-tile u+2; the k-strided operand's k-tile advance lives in a running lane offset
   int live2 = 2;
-  if constexpr (LIVE) { if (!prologue_only) live2 = live_next(lw, live_mv); }      // (the prologue call stops at the first two)
+  [[maybe_unused]] int live2h = 0;
+  if constexpr (BLK) { if (!prologue_only) { live2 = live_next(lw, live_mv); live2h = live_next(lw, live_mv); } }
+  else if constexpr (LIVE) { if (!prologue_only) live2 = live_next(lw, live_mv); }      // (the prologue call stops at the first two)
   uint32_t runA = voffA + (uint32_t)((dbg & 4) ? 0 : ktaA0 + live2) * kstepA, runB = voffB + (uint32_t)((dbg & 4) ? 0 : ktaB0 + live2) * kstepB;
+  // BLK: four running lane offsets -- each operand's lower and upper half (blocks 4 and 5 of the walk to begin with)
+  [[maybe_unused]] uint32_t runAh = 0u, runBh = 0u;
+  if constexpr (BLK) {
+    runA = voffA + (uint32_t)live2 * (kstepA >> 1); runB = voffB + (uint32_t)live2 * (kstepB >> 1);
+    runAh = 5 < n_blk ? voffA + (uint32_t)live2h * (kstepA >> 1) : OOB_HALF; runBh = 5 < n_blk ? voffB + (uint32_t)live2h * (kstepB >> 1) : OOB_HALF;
+  }
   auto dma_run = [&](int u, int i) {
     const bool isB = i >= 8;
     if (!(isB ? BKS : AKS) || (dbg & 4)) { dma_piece(u, i); return; }
     const int j = i & 7;
     char* dst = my_part + (isB ? TILE_BYTES : 0) + (u & 1) * 2 * TILE_BYTES + j * 4096;
+    if constexpr (BLK) {
+      const uint32_t off = (j < 4 ? (isB ? runB : runA) : (isB ? runBh : runAh)) + (uint32_t)(j & 3) * (isB ? stepB : stepA);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(isB ? rsB : rsA, IA_LDS(dst), 16, dma_on ? off : OOB, 0, 0, 0);
+      return;
+    }
     const uint32_t off = (isB ? runB : runA) + (uint32_t)j * (isB ? stepB : stepA);
     __builtin_amdgcn_raw_ptr_buffer_load_lds(isB ? rsB : rsA, IA_LDS(dst), 16, dma_on ? off : OOB, 0, 0, 0);
   };
@@ -1023,7 +1061,14 @@ IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdg
     ++u;
     // one running lane offset per k-strided operand, opaque to the loop optimiser: left alone it keeps SIXTEEN induction variables
     // (one per piece) and bumps them all in the last MFMA gap of the trip
-    if constexpr (LIVE) {      // on to the next live k-tile: the same trip, a longer stride
+    if constexpr (BLK) {       // the next two live blocks (trip u + 2: blocks 2u + 4 and 2u + 5 of the walk); past the count the upper half reads zeros
+      const int bl = live_next(lw, live_mv), bh = live_next(lw, live_mv);
+      const bool has_h = 2 * u + 5 < n_blk;
+      runA = voffA + (uint32_t)bl * (kstepA >> 1); asm volatile("" : "+v"(runA));
+      runB = voffB + (uint32_t)bl * (kstepB >> 1); asm volatile("" : "+v"(runB));
+      runAh = has_h ? voffA + (uint32_t)bh * (kstepA >> 1) : OOB_HALF; asm volatile("" : "+v"(runAh));
+      runBh = has_h ? voffB + (uint32_t)bh * (kstepB >> 1) : OOB_HALF; asm volatile("" : "+v"(runBh));
+    } else if constexpr (LIVE) {      // on to the next live k-tile: the same trip, a longer stride
       const int at = lw.cur;
       const uint32_t hop = (uint32_t)(live_next(lw, live_mv) - at);
       runA += hop * kstepA; asm volatile("" : "+v"(runA));
@@ -1278,9 +1323,10 @@ IA_DEV void drain_half(const GemmArgs& p, f32x16 (&acc)[4][4], int m0, int n0, c
 
 // EPI_ = EPI_NONE_LIVE: the plain epilogue behind a k loop over the live k-tiles only (GemmArgs::live_kt; weight-gradient form).  A value
 // of the epilogue parameter, not a parameter of its own: the other instantiations keep their names in profiles and traces.
+// EPI_ = EPI_NONE_BLK: the same over the live 32-row blocks, two to a trip (GemmArgs::live_kt holds an ia_kblock_mask).
 template <bool AKS, bool BKS, int EPI_, bool OUTF32>
 __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
-  constexpr bool LIVE = EPI_ == EPI_NONE_LIVE;
+  constexpr int LIVE = EPI_ == EPI_NONE_LIVE ? 1 : (EPI_ == EPI_NONE_BLK ? 2 : 0);
   constexpr bool ROWS = EPI_ >= EPI_ROWS;
   constexpr int EPI = LIVE ? (int)EPI_NONE : (ROWS ? EPI_ - EPI_ROWS : EPI_);
   constexpr bool GUARDABLE = ROWS && EPI == EPI_BIAS;      // (tile_blocks)
@@ -1326,7 +1372,19 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
   // here -- one vector load pair per lane, waited for on the spot -- so that the k loop's walk over them touches no memory.  A slab starts
   // at any bit of the mask: each lane shifts its 32 bits out of two words, and clips them to the slab's end.
   uint32_t live_mv = 0u;
-  if constexpr (LIVE) {
+  [[maybe_unused]] int n_blk = 0;
+  if constexpr (LIVE == 2) {
+    // block bits 2 kt0 .. 2 (kt0 + n_tiles) - 1 of the mask, clipped to the blocks K has (at most 64 words: the host keeps a slab at
+    // BLK_MAX_KTILES k-tiles or fewer); n_tiles becomes the number of PAIRS of live blocks
+    const int nb_all = (p.K + 31) >> 5, nw = (nb_all + 31) >> 5, first = 2 * kt0 + 32 * lane0, wlo = first >> 5, sh = first & 31;
+    const int left = min(2 * (kt0 + n_tiles), nb_all) - first;
+    const uint32_t lo = wlo < nw ? p.live_kt[wlo] : 0u, hi = wlo + 1 < nw ? p.live_kt[wlo + 1] : 0u;
+    live_mv = sh ? (lo >> sh) | (hi << (32 - sh)) : lo;
+    live_mv = left >= 32 ? live_mv : (left > 0 ? live_mv & ((1u << left) - 1u) : 0u);
+    for (uint64_t rest = __ballot(live_mv != 0u); rest; rest &= rest - 1ull)
+      n_blk += __builtin_popcount(__builtin_amdgcn_readlane(live_mv, __builtin_ctzll(rest)));
+    n_tiles = (n_blk + 1) >> 1;
+  } else if constexpr (LIVE) {
     const int nw = (nk_all + 31) >> 5, first = kt0 + 32 * lane0, wlo = first >> 5, sh = first & 31, left = n_tiles - 32 * lane0;
     const uint32_t lo = wlo < nw ? p.live_kt[wlo] : 0u, hi = wlo + 1 < nw ? p.live_kt[wlo + 1] : 0u;
     live_mv = sh ? (lo >> sh) | (hi << (32 - sh)) : lo;
@@ -1354,7 +1412,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
     // (the bf16 bias form keeps 64 bias values in registers across the main loop -- 468 of 512: the peeled first trip spilled there)
     constexpr bool PEEL_OK = !(EPI == EPI_BIAS && !OUTF32 && !BKS);
     main_loop<AKS, BKS, PEND, PEEL_OK, LIVE, ROWS>(p, smem, acc, rsrc_at(p.A, p.a_bytes, oa), rsrc_at(p.B, p.b_bytes, ob), AKS ? bm * BM : 0, BKS ? bn * BN : 0, kt0,
-                              AKS ? 0 : kt0, BKS ? 0 : kt0, n_tiles, nk_all, wm, wn, wave, lane, prologue_only, stores_in_flight, live_mv, ro);
+                              AKS ? 0 : kt0, BKS ? 0 : kt0, n_tiles, nk_all, wm, wn, wave, lane, prologue_only, stores_in_flight, live_mv, ro, n_blk);
   };
 
   // ---- Dynamic tile claim (persistent launches).  With the static order every workgroup owns the tiles bid, bid + gridDim.x, ...: a
@@ -1954,7 +2012,7 @@ __global__ __launch_bounds__(256) void zero_dead_rows_kernel(const int* __restri
 }
 
 template <bool AKS, bool BKS, int EPI, bool OUTF32>
-int launch(GemmArgs a, bool big, hipStream_t st) {
+int launch(GemmArgs a, bool big, hipStream_t st, bool live_blocks = false) {      // live_blocks: a.live_kt is a mask of 32-row blocks (ia_kblock_mask)
   constexpr int vid = AKS * 1000 + BKS * 100 + EPI * 10 + (OUTF32 ? 1 : 0);
   // the forms that may carry a block list (GemmArgs::row_blk): the data gradients, and the forward epilogues on k-contiguous operands
   constexpr bool DROWS = !AKS && !OUTF32 && (EPI == EPI_NONE || EPI == EPI_ADD || EPI == EPI_DGELU_CS ||
@@ -1974,10 +2032,11 @@ int launch(GemmArgs a, bool big, hipStream_t st) {
     // persistent launches with more than one tile per workgroup claim their tiles dynamically (IA_GEMM_DYNAMIC=0: the static order)
     a.tile_ctr = (a.splits == 1 && ntile > gx) ? next_ctr_slot() : nullptr;
     void (*kern)(GemmArgs) = t256w::gemm_kernel<AKS, BKS, EPI, OUTF32>;
-    static bool attr_set[5] = {false, false, false, false, false};      // per kernel: [0] this instantiation of t256w, [1] t256la, [2] the live-k-tile weight gradient, [3] / [4] the row remap of [0] / [1]
+    static bool attr_set[6] = {false, false, false, false, false, false};      // per kernel: [0] this instantiation of t256w, [1] t256la, [2] the live-k-tile weight gradient, [3] / [4] the row remap of [0] / [1], [5] the live-block weight gradient
     int la = 0;
     if constexpr (WGRAD) {
-      if (a.live_kt) { kern = t256w::gemm_kernel<true, true, EPI_NONE_LIVE, true>; la = 2; }
+      if (a.live_kt && live_blocks) { kern = t256w::gemm_kernel<true, true, EPI_NONE_BLK, true>; la = 5; }
+      else if (a.live_kt) { kern = t256w::gemm_kernel<true, true, EPI_NONE_LIVE, true>; la = 2; }
     }
     // plain NT form, several tiles per workgroup, static order: the look-ahead kernel (t256la; IA_GEMM_LA=0 keeps t256w)
     if constexpr (!AKS && !BKS && EPI == EPI_NONE && !OUTF32) {
@@ -2039,7 +2098,7 @@ static int gemm_core(const void* A, int a_kstrided, int lda, const void* B, int 
                      int N, int K, int epilogue, const float* bias, const void* aux, int ldaux, void* C2, int accumulate, void* workspace,
                      size_t workspace_bytes, const IaViewGemm* view, hipStream_t stream, int qcols = 0, float qscale = 1.f,
                      const uint32_t* live_kt = nullptr, const int* row_blocks = nullptr, int rows_fill = 1, int tail_of = 0,      // tail_of: below
-                     int rows_grouped = 0);
+                     int rows_grouped = 0, int live_blocks = 0);
 
 // workspace of an IA_EPI_DGELU_COLSUM GEMM: one fp32 row of N partial sums per 128-row block of the output (and never less than
 // the stand-alone column-sum kernel needs, which small shapes fall back to)
@@ -2431,11 +2490,55 @@ extern "C" int ia_ktile_mask_host(const uint8_t* row_live, int M_rows, uint32_t*
   for (int t = 0; t < nk; ++t) mask[t >> 5] |= ktile_live(row_live, M_rows, t) << (t & 31);
   return IA_OK;
 }
+// ---- the same at 32-row granularity: bit b of the mask = OR of row_live over rows 32b .. 32b+31 (clipped to M)
+static __host__ __device__ inline uint32_t kblock_live(const uint8_t* row_live, int M, int b) {
+  const uint8_t* r = row_live + (size_t)b * 32;
+  const int n = M - b * 32 < 32 ? M - b * 32 : 32;
+  uint64_t any = 0;
+  if (n == 32 && ((uintptr_t)r & 7) == 0) {
+    for (int i = 0; i < 4; ++i) any |= reinterpret_cast<const uint64_t*>(r)[i];
+  } else {
+    for (int i = 0; i < n; ++i) any |= r[i];
+  }
+  return any != 0 ? 1u : 0u;
+}
+namespace {
+// one thread per block, one 64-bit ballot per wave = two whole mask words, stored by lanes 0 and 32 (plain stores, no atomics)
+__global__ __launch_bounds__(256) void kblock_mask_kernel(const uint8_t* __restrict__ row_live, int M, int nb, uint32_t* __restrict__ mask) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  const uint64_t v = __ballot(b < nb && kblock_live(row_live, M, b));
+  if ((threadIdx.x & 31) == 0 && b < nb) mask[b >> 5] = (uint32_t)(v >> (threadIdx.x & 32));
+}
+}  // namespace
+extern "C" size_t ia_kblock_mask_bytes(int M_rows) {
+  if (M_rows <= 0) return 0;
+  return (size_t)(((M_rows + 31) / 32 + 31) / 32) * sizeof(uint32_t);
+}
+extern "C" int ia_kblock_mask(const uint8_t* row_live, int M_rows, uint32_t* mask, hipStream_t stream) {
+  (void)hipGetLastError();
+  if (!row_live || !mask || M_rows <= 0) return IA_ERR_ARG;
+  const int nb = (M_rows + 31) / 32;
+  hipLaunchKernelGGL(kblock_mask_kernel, dim3((nb + 255) / 256), dim3(256), 0, stream, row_live, M_rows, nb, mask);
+  return ia_check_launch();
+}
+extern "C" int ia_kblock_mask_host(const uint8_t* row_live, int M_rows, uint32_t* mask) {
+  if (!row_live || !mask || M_rows <= 0) return IA_ERR_ARG;
+  const int nb = (M_rows + 31) / 32;
+  for (int w = 0; w < (nb + 31) / 32; ++w) mask[w] = 0u;
+  for (int b = 0; b < nb; ++b) mask[b >> 5] |= kblock_live(row_live, M_rows, b) << (b & 31);
+  return IA_OK;
+}
 // library-internal (common.h): the weight gradient with a mask already built (ia_layer_bwd2 builds one per call for its four)
 int ia_gemm_wgrad_masked(const void* dY, int ldy, const void* X, int ldx, float* dW, int ldw, int N_out, int N_in, int M_rows,
                          const uint32_t* ktile_mask, int accumulate, void* workspace, size_t workspace_bytes, hipStream_t stream) {
   return gemm_core(dY, 1, ldy, X, 1, ldx, dW, 1, ldw, N_out, N_in, M_rows, EPI_NONE, nullptr, nullptr, 0, nullptr, accumulate, workspace,
                    workspace_bytes, nullptr, stream, 0, 1.f, ktile_mask);
+}
+// the weight gradient over the live 32-row blocks of a prebuilt ia_kblock_mask (NULL: every row)
+extern "C" int ia_gemm_wgrad_blocks(const void* dY, int ldy, const void* X, int ldx, float* dW, int ldw, int N_out, int N_in, int M_rows,
+                                    const uint32_t* kblock_mask, int accumulate, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  return gemm_core(dY, 1, ldy, X, 1, ldx, dW, 1, ldw, N_out, N_in, M_rows, EPI_NONE, nullptr, nullptr, 0, nullptr, accumulate, workspace,
+                   workspace_bytes, nullptr, stream, 0, 1.f, kblock_mask, nullptr, 1, 0, 0, kblock_mask ? 1 : 0);
 }
 extern "C" size_t ia_gemm_wgrad_rows_workspace_bytes(int N_out, int N_in, int M_rows) {
   if (N_out <= 0 || N_in <= 0 || M_rows <= 0) return 0;
@@ -2496,7 +2599,7 @@ static int launch_dgelu_colsum(GemmArgs& g, bool big, float* csum, void* workspa
 static int gemm_core(const void* A, int a_kstrided, int lda, const void* B, int b_kstrided, int ldb, void* C, int c_is_f32, int ldc, int M,
                      int N, int K, int epilogue, const float* bias, const void* aux, int ldaux, void* C2, int accumulate, void* workspace,
                      size_t workspace_bytes, const IaViewGemm* view, hipStream_t stream, int qcols, float qscale, const uint32_t* live_kt,
-                     const int* row_blocks, int rows_fill, int tail_of, int rows_grouped) {
+                     const int* row_blocks, int rows_fill, int tail_of, int rows_grouped, int live_blocks) {
   const uint64_t a_window = view ? view->a_window : 0, b_window = view ? view->b_window : 0;
   const int groups = view ? view->groups : 1;
   (void)hipGetLastError();  // drop stale status left by unrelated runtime calls (e.g. hipEventQuery -> NotReady)
@@ -2550,7 +2653,10 @@ static int gemm_core(const void* A, int a_kstrided, int lda, const void* B, int 
   // 256-wide kernel reads the slot as the mask, it is overwritten HERE for every caller -- a stray bias passed with IA_EPI_NONE, the
   // shifted views of ia_gemm_view -- so the kernel sees a mask or NULL, never a bias.  launch<true, true, EPI_NONE, true> is reached
   // from this function only; a new call site that fills GemmArgs for this form must do the same.
-  if (a_kstrided && b_kstrided && c_is_f32 && epilogue == EPI_NONE) g.live_kt = (big && g.nk_per_split <= t256w::LIVE_MAX_KTILES) ? live_kt : nullptr;
+  // (live_blocks: the mask holds 32-row blocks, two bits per k-tile of the slab -- half the slab length, else dense: a block mask cannot
+  // stand in for the 64-row one)
+  if (a_kstrided && b_kstrided && c_is_f32 && epilogue == EPI_NONE)
+    g.live_kt = (big && g.nk_per_split <= (live_blocks ? t256w::BLK_MAX_KTILES : t256w::LIVE_MAX_KTILES)) ? live_kt : nullptr;
   // the block list of the row-remapped forms (C2 has C's pitch, so dgrad_rows_fit covers it): a list or NULL
   const bool fwd_epi = !b_kstrided && (epilogue == EPI_BIAS || epilogue == EPI_BIAS_GELU || epilogue == EPI_BIAS_GELU_ACT || epilogue == EPI_BIAS_ADD);
   g.row_blk = nullptr; g.rows_fill = rows_fill; g.fill_m = M; g.rows_guarded = tail_of ? 1 : 0;
@@ -2597,7 +2703,7 @@ static int gemm_core(const void* A, int a_kstrided, int lda, const void* B, int 
     }
   } else if (a_kstrided && b_kstrided && c_is_f32) {
     if (epilogue == EPI_NONE) {
-      int rc = launch<true, true, EPI_NONE, true>(g, big, stream);
+      int rc = launch<true, true, EPI_NONE, true>(g, big, stream, live_blocks != 0);
       // 256x256 kernel: no spare accumulators for the row sums -> the stand-alone column-sum pass over A (stream-ordered after the
       // split-K reduce, so it may reuse the workspace)
       if (!rc && C2 && big) rc = ia_colsum(A, lda, K, M, (float*)C2, 1, workspace, workspace_bytes, stream);

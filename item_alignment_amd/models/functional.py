@@ -136,8 +136,9 @@ _CLS_ROW_LISTS_KEPT = 8      # (shape, stream) pairs: two towers, training and e
 
 def cls_row_lists(B, L, device, key_mask=None):
     """ia_layer_cfg::out_row_live and its lists for "row 0 of each of B sequences of L rows": one small tensor (the mask, then
-    ia_row_blocks, ia_ktile_mask and ia_row_groups of it), built by launches on the current stream -- no host synchronisation.
-    Returns (tensor, mask ptr, blocks ptr, k-tile mask ptr, groups ptr).
+    ia_row_blocks, ia_kblock_mask and ia_row_groups of it), built by launches on the current stream -- no host synchronisation.
+    Returns (tensor, mask ptr, blocks ptr, 32-row block mask ptr, groups ptr); the block mask goes into ia_layer_cfg::out_live_ktiles
+    together with masked_rows_dead bit 16.
     key_mask (uint8 [B, L]): row 0 of a sequence counts only where it is an attended position, so every out_row_live row is a live key
     by construction (a sequence whose position 0 is masked has no live row behind the attention, as under the key-mask filter); the
     lists then depend on the batch and are built per call.  Without one they depend on (B, L, device) only: built once per stream that
@@ -151,12 +152,12 @@ def cls_row_lists(B, L, device, key_mask=None):
     al = lambda n: (n + 255) & ~255
     o_blk = al(M)
     o_kt = o_blk + al(lib.ia_row_blocks_bytes(M))
-    o_grp = o_kt + al(lib.ia_ktile_mask_bytes(M))
+    o_grp = o_kt + al(lib.ia_kblock_mask_bytes(M))
     buf = torch.zeros(o_grp + al(lib.ia_row_groups_bytes(M)), device=device, dtype=torch.uint8)
     buf[:M:L] = 1 if key_mask is None else key_mask.reshape(-1)[::L].ne(0).to(torch.uint8)
     p = buf.data_ptr()
     check(lib.ia_row_blocks(p, M, p + o_blk, stream_ptr()), "ia_row_blocks")
-    check(lib.ia_ktile_mask(p, M, p + o_kt, stream_ptr()), "ia_ktile_mask")
+    check(lib.ia_kblock_mask(p, M, p + o_kt, stream_ptr()), "ia_kblock_mask")
     check(lib.ia_row_groups(p, M, p + o_grp, stream_ptr()), "ia_row_groups")
     got = (buf, p, p + o_blk, p + o_kt, p + o_grp)
     if key_mask is None and not torch.cuda.is_current_stream_capturing():
@@ -189,22 +190,24 @@ class EncoderStackFn(torch.autograd.Function):
         outs, cur = [], x.contiguous()
         inputs = [cur]
         mp = ptr(key_mask)
-        # masked_rows_dead: the key mask is the same for every layer, forward and backward -- the 32-row block list and the live-k-tile
-        # bitmask are built once here (one small tensor, kept for the backward) instead of once per layer call
+        # masked_rows_dead: the key mask is the same for every layer, forward and backward -- the 32-row block list and the live-block
+        # bitmask (ia_kblock_mask, flagged by masked_rows_dead bit 8) are built once here (one small tensor, kept for the backward) instead of once per layer call
         ctx.row_lists = None
         flag = cfgs[0].masked_rows_dead
         if key_mask is not None and cu_seqlens is None and not cfgs[0].pre_ln and ((flag & 1 and keep) or (flag & 3) == 3):
             M = cur.shape[0]
             lb = lib.ia_row_groups_packed_offset(M)        # (= the block list's size rounded up to 256 bytes)
             packed = keep and M <= 128 * 4096              # the backward's x gelu' data gradient: the live blocks packed by whole groups
-            lists = torch.empty(2 * lb + lib.ia_ktile_mask_bytes(M), device=x.device, dtype=torch.uint8)
+            lists = torch.empty(2 * lb + lib.ia_kblock_mask_bytes(M), device=x.device, dtype=torch.uint8)
             check(lib.ia_row_blocks(mp, M, lists.data_ptr(), stream_ptr()), "ia_row_blocks")
             if packed:
                 check(lib.ia_row_groups_packed(mp, M, lists.data_ptr() + lb, stream_ptr()), "ia_row_groups_packed")
             if keep:                                       # (the weight gradients' mask: nothing reads it without a backward)
-                check(lib.ia_ktile_mask(mp, M, lists.data_ptr() + 2 * lb, stream_ptr()), "ia_ktile_mask")
+                check(lib.ia_kblock_mask(mp, M, lists.data_ptr() + 2 * lb, stream_ptr()), "ia_kblock_mask")
             for c in cfgs:
                 c.row_blocks, c.live_ktiles = lists.data_ptr(), (lists.data_ptr() + 2 * lb) if keep else None
+                if keep:
+                    c.masked_rows_dead |= 8                # ia_layer_cfg: live_ktiles is a 32-row block mask
                 if packed:
                     c.masked_rows_dead |= 4                # ia_layer_cfg: the packed list sits behind row_blocks
             ctx.row_lists = lists
@@ -215,6 +218,7 @@ class EncoderStackFn(torch.autograd.Function):
             ctx.out_lists = cls_row_lists(B, L, x.device, key_mask)      # (kept until the backward has run)
             c = cfgs[-1]
             c.out_row_live, c.out_row_blocks, c.out_live_ktiles, c.out_row_groups = ctx.out_lists[1:]
+            c.masked_rows_dead |= 16                       # ia_layer_cfg: out_live_ktiles is a 32-row block mask
             c.out_q_rows = 1      # the mask is zero behind position 0 of every sequence: the layer's attention runs that query block only
         if keep:
             stash_bytes = lib.ia_layer_stash_bytes(C.byref(cfgs[0]))

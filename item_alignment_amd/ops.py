@@ -70,6 +70,34 @@ def ktile_mask(row_live):
     return out
 
 
+def kblock_mask(row_live):
+    """bit (b & 31) of word b >> 5 = any(row_live[32b : 32b + 32]) (uint8 [M] on the GPU) -> int32 words"""
+    lib = _lib.load()
+    _need(row_live, torch.uint8, "row_live")
+    M = row_live.numel()
+    out = torch.empty(lib.ia_kblock_mask_bytes(M) // 4, device=row_live.device, dtype=torch.int32)
+    check(lib.ia_kblock_mask(row_live.data_ptr(), M, out.data_ptr(), stream_ptr()), "ia_kblock_mask")
+    return out
+
+
+def gemm_wgrad_blocks(dy, x, mask=None, *, out=None, accumulate=False):
+    """dW[N_out, N_in] (+)= dy[M, N_out]^T x[M, N_in] in fp32 over the 32-row blocks whose bit is set in `mask` (kblock_mask's int32
+    words: a clear bit promises that the block's rows of dy are all zeros; ia_gemm_wgrad_blocks).  mask=None is the dense gemm."""
+    lib = _lib.load()
+    _need(dy, BF16, "dy"); _need(x, BF16, "x"); _need(mask, torch.int32, "mask")
+    (M, n_out), (Mx, n_in) = dy.shape, x.shape
+    if M != Mx or (mask is not None and mask.numel() * 4 != lib.ia_kblock_mask_bytes(M)):
+        raise ValueError("gemm_wgrad_blocks: dy and x must have the same number of rows and mask ia_kblock_mask_bytes(M) bytes")
+    if out is None:
+        out = torch.empty((n_out, n_in), device=dy.device, dtype=F32)
+    _need(out, F32, "out")
+    ws_bytes = lib.ia_gemm_workspace_bytes(n_out, n_in, M, 1)
+    ws = torch.empty(max(ws_bytes, 16), device=dy.device, dtype=torch.uint8)
+    check(lib.ia_gemm_wgrad_blocks(dy.data_ptr(), n_out, x.data_ptr(), n_in, out.data_ptr(), n_in, n_out, n_in, M, ptr(mask),
+                                   int(accumulate), ws.data_ptr(), ws_bytes, stream_ptr()), "ia_gemm_wgrad_blocks")
+    return out
+
+
 def gemm_wgrad_rows(dy, x, row_live=None, *, out=None, accumulate=False):
     """dW[N_out, N_in] (+)= dy[M, N_out]^T x[M, N_in] in fp32; row_live (uint8 [M]) == 0 promises that row of dy is all zeros, and
     64-row blocks without a live row are skipped (ia_gemm_wgrad_rows).  row_live=None is gemm(..., a_kstrided, b_kstrided, out_f32)."""
