@@ -1,0 +1,193 @@
+"""Domain-adaptive masked-LM + next-sentence pre-training of BertForPreTraining on the product corpus (reference bert_pretrain.py) on
+the HIP engine.  The checkpoint it writes (`pytorch_model.bin`, `config.json`, `vocab.txt` under --output_dir) is what
+`--pretrained_model_path` of finetune_text.py / finetune_multimodal.py starts the text towers from.
+
+The reference hard-codes its settings in main(); each is a flag here whose default is the reference's value.  Kept as they are: the
+schedule's length counts RECORDS, not examples (records // batch_size * num_epochs), and the next-sentence negatives are never trained
+on (item_alignment_amd/data/bert_pretrain.py).  --model_name_or_path must be a local directory with vocab.txt and config.json (and
+pytorch_model.bin to start from): nothing is ever downloaded.  INTEGRATION.md "BERT pre-training" has the details.
+"""
+import argparse
+import logging
+import os
+import shutil
+import sys
+
+os.environ.setdefault("HF_HUB_OFFLINE", "1")
+os.environ.setdefault("TRANSFORMERS_OFFLINE", "1")
+
+ROOT = os.path.dirname(os.path.abspath(__file__))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+LOGGER = logging.getLogger("bert_pretrain")
+
+
+def get_parser():
+    p = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    a = p.add_argument
+    a("--data_dir", required=True, type=str, help="directory with the JSON-lines corpus files")
+    a("--train_file", default="pretrain_train.jsonl", type=str)
+    a("--valid_file", default="pretrain_valid.jsonl", type=str)
+    a("--max_seq_len", default=510, type=int, help="tokens between [CLS] and [SEP]; the model sees max_seq_len + 2 positions")
+    a("--batch_size", default=32, type=int)
+    a("--num_epochs", default=20, type=int)
+    a("--model_name_or_path", required=True, type=str,
+      help="LOCAL directory with vocab.txt, config.json and (optionally) pytorch_model.bin, e.g. an unpacked bert-base-chinese")
+    a("--output_dir", default=os.path.join("src", "bert", "PretrainBert"), type=str)
+    a("--learning_rate", default=2e-5, type=float)
+    a("--adam_epsilon", default=1e-8, type=float)
+    a("--warmup_steps", default=3000, type=int)
+    a("--max_grad_norm", default=1.0, type=float)
+    a("--log_steps", default=100, type=int)
+    a("--eval_steps", default=2000, type=int)
+    a("--patience_steps", default=20000, type=int)
+    a("--max_steps", default=-1, type=int, help="not in the reference: stop after this many optimiser steps (-1: run the epochs)")
+    a("--seed", default=42, type=int, help="not in the reference: seeds the initialisation, the masking, the shuffles and the dropout")
+    return p
+
+
+def check_model_dir(path):
+    """a hub name such as the reference's 'bert-base-chinese' would mean a download: refused"""
+    if not os.path.isdir(path):
+        raise SystemExit(f"--model_name_or_path {path!r} is not a local directory.  This script never downloads: unpack the checkpoint "
+                         "(vocab.txt, config.json, pytorch_model.bin) into a directory and pass that")
+    for need in ("vocab.txt", "config.json"):
+        if not os.path.isfile(os.path.join(path, need)):
+            raise SystemExit(f"--model_name_or_path {path!r} has no {need}")
+
+
+def load_tokenizer(vocab_file):
+    """BertTokenizer(vocab_file=<dir>/vocab.txt, do_lower_case=True) of the reference's pytorch_transformers, built from the local file
+    alone.  Newer transformers releases take the vocabulary itself (`vocab=`) where older ones take the file name."""
+    import inspect
+    from transformers import BertTokenizer
+    if "vocab" in inspect.signature(BertTokenizer.__init__).parameters:
+        with open(vocab_file, "r", encoding="utf8") as f:
+            vocab = {line.rstrip("\n"): i for i, line in enumerate(f)}
+        return BertTokenizer(vocab=vocab, do_lower_case=True)
+    return BertTokenizer(vocab_file=vocab_file, do_lower_case=True)
+
+
+def linear_schedule(step, total, warmup):
+    """transformers.get_linear_schedule_with_warmup's factor at `step`"""
+    if step < warmup:
+        return step / max(1, warmup)
+    return max(0.0, (total - step) / max(1, total - warmup))
+
+
+def count_records(data_dir, file):
+    with open(os.path.join(data_dir, file), "r", encoding="utf8") as f:
+        return sum(1 for line in f if line.strip())
+
+
+def main(argv=None):
+    args = get_parser().parse_args(argv)
+    check_model_dir(args.model_name_or_path)
+    import torch
+    import item_alignment_amd.models as M
+    from item_alignment_amd.cli_common import load_config
+    from item_alignment_amd.data import bert_pretrain as D
+    from item_alignment_amd.models import functional as Fn
+
+    os.makedirs(args.output_dir, exist_ok=True)
+    LOGGER.setLevel(logging.INFO)
+    LOGGER.propagate = False              # the package configures the root logger: every line once, through the two handlers below
+    fmt = logging.Formatter("%(asctime)s - %(name)s - %(levelname)s - %(message)s")
+    for h in (logging.FileHandler(os.path.join(args.output_dir, "pretrain-bert.log")), logging.StreamHandler(sys.stdout)):
+        h.setFormatter(fmt)
+        LOGGER.addHandler(h)
+    try:                                  # scalars for TensorBoard only where tensorboardX is installed; never required
+        from tensorboardX import SummaryWriter
+        writer = SummaryWriter(logdir=os.path.join(args.output_dir, "tf-logs"))
+    except ImportError:
+        writer = None
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bert_pretrain.py runs on the MI355X HIP engine only (no CPU path); no GPU is visible")
+    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
+    torch.cuda.set_device(device)
+
+    vocab_file = os.path.join(args.model_name_or_path, "vocab.txt")
+    tokenizer = load_tokenizer(vocab_file)
+    config = load_config(os.path.join(args.model_name_or_path, "config.json"))
+    if args.max_seq_len + 2 > config.max_position_embeddings:
+        raise SystemExit(f"--max_seq_len {args.max_seq_len} + [CLS] + [SEP] exceeds max_position_embeddings {config.max_position_embeddings}")
+    if len(tokenizer) > config.vocab_size:
+        raise SystemExit(f"vocab.txt has {len(tokenizer)} entries, the model's word table {config.vocab_size} rows")
+    torch.manual_seed(args.seed)
+    model = M.BertForPreTraining.from_pretrained(args.model_name_or_path, config=config).to(device)
+    LOGGER.info("The BERT model has {:} different named parameters.".format(len(list(model.named_parameters()))))
+    arena = model.param_arena
+    rng = D.Rng(args.seed)
+
+    total_steps = max(1, count_records(args.data_dir, args.train_file) // args.batch_size * args.num_epochs)
+    eval_examples = []
+    for records in D.read_pretrained_data(args.data_dir, args.valid_file, rng, batch_size=-1):
+        eval_examples = D.build_examples(records, tokenizer, args.max_seq_len, rng)
+    LOGGER.info(f"Loading Eval data successfully: {len(eval_examples)} examples")
+
+    def run(batch):
+        input_ids, attention_mask, _token_type_ids, label_ids, next_labels = (b.to(device) for b in batch)
+        # token_type_ids=None, as the reference calls its model: the segment types of the features are not fed in
+        return model(input_ids, token_type_ids=None, attention_mask=attention_mask, masked_lm_labels=label_ids,
+                     next_sentence_label=next_labels)[0]
+
+    def eval_model():
+        model.eval()
+        total, n = 0.0, 0
+        with torch.no_grad():
+            for batch in D.batches(eval_examples, args.batch_size):
+                total += run(batch).item()
+                n += 1
+        model.train()
+        return total / max(1, n)
+
+    def save():
+        model.save_pretrained(args.output_dir)
+        shutil.copyfile(vocab_file, os.path.join(args.output_dir, "vocab.txt"))
+
+    global_steps, best_eval_loss, best_steps = 0, float("inf"), 0
+    model.train()
+    for epoch_idx in range(args.num_epochs):
+        for records in D.read_pretrained_data(args.data_dir, args.train_file, rng):
+            examples = D.build_examples(records, tokenizer, args.max_seq_len, rng)
+            for batch in D.batches(examples, args.batch_size, rng):
+                Fn.set_step_seed((args.seed * 1000003 + global_steps) & 0xFFFFFFFF)
+                Fn.reset_use_counts()
+                arena.zero_grad()
+                loss = run(batch)
+                loss.backward()
+                global_steps += 1
+                # clip_grad_norm_(model.parameters(), max_grad_norm) as a factor on the gradients inside the fused optimiser step
+                norm = arena.grad.norm().item()
+                scale = min(1.0, args.max_grad_norm / (norm + 1e-6))
+                lr = args.learning_rate * linear_schedule(global_steps - 1, total_steps, args.warmup_steps)
+                arena.adamw_step(lr, betas=(0.9, 0.999), eps=args.adam_epsilon, weight_decay=0.0, grad_scale=scale)
+                if global_steps % args.log_steps == 0:
+                    value = loss.item()
+                    if writer:
+                        writer.add_scalar("Train/loss", value, global_steps)
+                    LOGGER.info("Epoch {:>3,}, Steps {:>5,}, Total {:>5,}, Train/Loss {:.6f}".format(epoch_idx + 1, global_steps, total_steps, value))
+                if global_steps % args.eval_steps == 0:
+                    eval_loss = eval_model()
+                    if writer:
+                        writer.add_scalar("Eval/loss", eval_loss, global_steps)
+                    improve = "  No optimization! ..."
+                    if best_eval_loss > eval_loss:
+                        best_eval_loss, best_steps, improve = eval_loss, global_steps, " ^_^"
+                        save()
+                    elif global_steps - best_steps > args.patience_steps:
+                        LOGGER.info(f"Eval loss has not been optimized for {args.patience_steps} steps, Early stopping ...")
+                        LOGGER.info(f"Pretraining successfully, num_epochs:{epoch_idx + 1}, global_steps:{global_steps} ^_^")
+                        return 0
+                    LOGGER.info("* Epoch {:>3,}, Steps {:>5,}, Total {:>5,}, Eval/Loss {:.6f}".format(epoch_idx + 1, global_steps, total_steps,
+                                                                                                   eval_loss) + improve)
+                if 0 < args.max_steps <= global_steps:
+                    LOGGER.info(f"Stopping after --max_steps {args.max_steps}")
+                    return 0
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -843,6 +843,22 @@ int ia_textcnn_pool_bwd_x(const float* g, const int32_t* argmax, const float* co
                           int H, float p1, float p2, uint32_t seed, uint32_t stream_id1, uint32_t stream_id2, void* dx,
                           ia_stream_t stream);
 
+/* ---- cross-entropy over vocabulary logits: nn.CrossEntropyLoss(ignore_index=-1) of the masked-LM head (pytorch_transformers
+ * BertForPreTraining; reference bert_pretrain.py:564-569).  logits [M, ld] fp32 (ld >= V, ld % 4 == 0; columns V .. ld-1 are never
+ * read), labels [M] int64.  lse[r] = log sum_j exp(logits[r][j]) (row maximum subtracted first), loss_row[r] = lse[r] - logits[r][label],
+ * loss[0] = sum loss_row / n_live, loss[1] = n_live.  A row with label < 0 is ignored: nothing of it is read, lse = loss_row = 0, it
+ * is not counted.  A label >= V reads nothing out of bounds: that row's loss_row, hence the mean, is NaN.  n_live == 0: the mean is
+ * NaN, as torch's.  Fixed summation order, no atomics: two runs are bit-identical.  IA_ERR_ARG / IA_ERR_WORKSPACE before any launch.
+ * ia_vocab_ce_bwd: dlogits [M, ldg] bf16 (ldg >= V, ldg % 8 == 0) = bf16((exp(logits - lse) - onehot(label)) * dloss[0] / loss[1]) in
+ * columns < V, exact zeros in columns V .. ldg-1 and in every row that is ignored or whose label is >= V: the A operand of the
+ * hidden-gradient GEMM (k-contiguous) and of the table-gradient GEMM (k-strided) as it stands.  The additions leave IA_ABI_VERSION
+ * at 20: nothing existing changes its meaning. */
+size_t ia_vocab_ce_workspace_bytes(int M);
+int ia_vocab_ce_fwd(const float* logits, int ld, const int64_t* labels, float* lse, float* loss_row, float* loss /* [2]: mean, n_live */,
+                    int M, int V, void* workspace, size_t workspace_bytes, ia_stream_t stream);
+int ia_vocab_ce_bwd(const float* logits, int ld, const int64_t* labels, const float* lse, const float* loss /* reads [1] */,
+                    const float* dloss /* device scalar */, void* dlogits /* bf16 [M, ldg] */, int ldg, int M, int V, ia_stream_t stream);
+
 /* ---- data-parallel gradient exchange (pure data parallelism, one process per GPU; reference loop being sharded:
  * finetune_multimodal.py:371-468).  RCCL over xGMI behind four calls, for hosts that bind only this header (the Python host of this
  * repository uses torch.distributed, i.e. the same RCCL).  Rank 0 obtains an id and hands its IA_COMM_ID_BYTES bytes to the other

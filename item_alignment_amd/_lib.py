@@ -206,6 +206,9 @@ SIGNATURES = {
     "ia_textcnn_pool_fwd": (i32, [vp, i32, PP, IP, i32, i32, i32, i32, f32, f32, u32, u32, u32, vp, vp, vp]),
     "ia_textcnn_pool_bwd_w": (i32, [vp, vp, vp, vp, IP, i32, i32, i32, i32, i32, f32, f32, u32, u32, u32, PP, PP, vp]),
     "ia_textcnn_pool_bwd_x": (i32, [vp, vp, PP, IP, i32, i32, i32, i32, i32, f32, f32, u32, u32, u32, vp, vp]),
+    "ia_vocab_ce_workspace_bytes": (sz, [i32]),
+    "ia_vocab_ce_fwd": (i32, [vp, i32, vp, vp, vp, vp, i32, i32, vp, sz, vp]),
+    "ia_vocab_ce_bwd": (i32, [vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "ia_cast_f32_to_bf16": (i32, [vp, vp, sz, vp]),
     "ia_cast_bf16_to_f32": (i32, [vp, vp, sz, vp]),
     "ia_layer_stash_bytes": (sz, [C.POINTER(LayerCfg)]),

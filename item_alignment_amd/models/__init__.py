@@ -9,3 +9,4 @@ from .image import VisionTransformer, VitTwoTower, NFNetTwoTower, ResNetTwoTower
 from .multimodal import (RobertaImageModel, RobertaImageOneTower, RobertaImageTwoTower, CoCaModel, CoCaForItemAlignment, LayerNorm,
                          Residual, RotaryEmbedding, SwiGLU, ParallelTransformerBlock, CrossAttention)
 from .graph import GCN, GCN2Conv, GCNTwoTower, GraphAdjacency, load_adjacency
+from .bert_pretrain import BertForPreTraining

@@ -374,3 +374,42 @@ def textcnn_pool_bwd_x(g, arg, weights, sizes, L, *, p1=0.0, p2=0.0, seed=0, str
     check(lib.ia_textcnn_pool_bwd_x(g.data_ptr(), arg.data_ptr(), _ptr_array(weights), _int_array(sizes), len(sizes), F_, B, L, H, p1, p2,
                                     seed, stream_id1, stream_id2, dx.data_ptr(), stream_ptr()), "ia_textcnn_pool_bwd_x")
     return dx
+
+
+# ------------------------------------------------------------------------------------------------ vocabulary cross-entropy
+def vocab_ce_fwd(logits, labels, V=None):
+    """nn.CrossEntropyLoss(ignore_index=-1) over logits [M, ld] fp32 (columns V .. ld-1 never read), labels [M] int64 ->
+    (lse [M], loss_row [M], loss [2] = (mean over the labelled rows, their count)), all fp32 (ia_vocab_ce_fwd)."""
+    lib = _lib.load()
+    _need(logits, F32, "logits"); _need(labels, torch.int64, "labels")
+    M, ld = logits.shape
+    V = ld if V is None else V
+    if labels.numel() != M:
+        raise ValueError("vocab_ce_fwd: one label per row of logits")
+    dev = logits.device
+    lse = torch.empty(M, device=dev, dtype=F32)
+    loss_row = torch.empty(M, device=dev, dtype=F32)
+    loss = torch.empty(2, device=dev, dtype=F32)
+    ws_bytes = lib.ia_vocab_ce_workspace_bytes(M)
+    ws = torch.empty(max(ws_bytes, 16), device=dev, dtype=torch.uint8)
+    check(lib.ia_vocab_ce_fwd(logits.data_ptr(), ld, labels.data_ptr(), lse.data_ptr(), loss_row.data_ptr(), loss.data_ptr(), M, V,
+                              ws.data_ptr(), ws_bytes, stream_ptr()), "ia_vocab_ce_fwd")
+    return lse, loss_row, loss
+
+
+def vocab_ce_bwd(logits, labels, lse, loss, dloss, V=None, *, ldg=None, out=None):
+    """dlogits bf16 [M, ldg] = (softmax - onehot) * dloss / n_live, zeros in the pad columns and the ignored rows (ia_vocab_ce_bwd).
+    dloss: fp32 device scalar; loss: what vocab_ce_fwd returned."""
+    lib = _lib.load()
+    _need(logits, F32, "logits"); _need(labels, torch.int64, "labels"); _need(lse, F32, "lse"); _need(loss, F32, "loss")
+    _need(dloss, F32, "dloss")
+    M, ld = logits.shape
+    V = ld if V is None else V
+    if out is None:
+        out = torch.empty((M, (V + 7) & ~7 if ldg is None else ldg), device=logits.device, dtype=BF16)
+    _need(out, BF16, "out")
+    if labels.numel() != M or lse.numel() != M or out.shape[0] != M or loss.numel() != 2 or dloss.numel() != 1:
+        raise ValueError("vocab_ce_bwd: labels, lse and dlogits need one row per row of logits, loss two elements, dloss one")
+    check(lib.ia_vocab_ce_bwd(logits.data_ptr(), ld, labels.data_ptr(), lse.data_ptr(), loss.data_ptr(), dloss.data_ptr(), out.data_ptr(),
+                              out.shape[1], M, V, stream_ptr()), "ia_vocab_ce_bwd")
+    return out
