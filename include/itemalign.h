@@ -859,6 +859,26 @@ int ia_vocab_ce_fwd(const float* logits, int ld, const int64_t* labels, float* l
 int ia_vocab_ce_bwd(const float* logits, int ld, const int64_t* labels, const float* lse, const float* loss /* reads [1] */,
                     const float* dloss /* device scalar */, void* dlogits /* bf16 [M, ldg] */, int ldg, int M, int V, ia_stream_t stream);
 
+/* ---- symmetric contrastive loss between the text and the image embeddings of a batch (CoCaForPretraining; reference
+ * src/models/multimodal.py:843-933).  text [B, ldt], image [B, ldi] fp32 (ld >= H), log_scale a device scalar, s = expf(*log_scale).
+ * ia_contrastive_fwd: sim [B, lds] fp32 (lds >= B) = s text image^T in fp32 FMA, lse_row[i] = log sum_j exp(sim[i][j]), lse_col[j] =
+ * log sum_i exp(sim[i][j]) (maximum subtracted first), loss[0] = 0.5 (mean_i (lse_row[i] - sim[i][i]) + mean_j (lse_col[j] -
+ * sim[j][j])) = 0.5 (CE(sim, arange) + CE(sim^T, arange)).  sim, lse_row and lse_col are what the backward call reads.
+ * ia_contrastive_bwd: G[i][j] = dloss[0] (0.5 / B) (exp(sim[i][j] - lse_row[i]) + exp(sim[i][j] - lse_col[j]) - 2 [i == j]);
+ * dtext [B, lddt] = s G image, dimage [B, lddi] = s G^T text, dlog_scale[0] = (accumulate_dlog_scale ? dlog_scale[0] : 0) +
+ * sum_ij G[i][j] sim[i][j].  Any B >= 1, H >= 1.  The pad columns of the inputs are never read, those of the outputs never written.
+ * Fixed summation order, no atomics: two runs are bit-identical.  IA_ERR_ARG / IA_ERR_WORKSPACE before any launch; the workspace of
+ * ia_contrastive_workspace_bytes(B) serves both calls and carries nothing from one to the other.  The additions leave IA_ABI_VERSION
+ * at 20: nothing existing changes its meaning. */
+size_t ia_contrastive_workspace_bytes(int B);
+int ia_contrastive_fwd(const float* text, int ldt, const float* image, int ldi, const float* log_scale /* device scalar */,
+                       float* sim /* [B, lds] fp32, scaled; kept for backward */, int lds, float* lse_row, float* lse_col,
+                       float* loss /* [1] */, int B, int H, void* workspace, size_t workspace_bytes, ia_stream_t stream);
+int ia_contrastive_bwd(const float* text, int ldt, const float* image, int ldi, const float* log_scale, const float* sim, int lds,
+                       const float* lse_row, const float* lse_col, const float* dloss /* device scalar */, float* dtext, int lddt,
+                       float* dimage, int lddi, float* dlog_scale /* [1] */, int accumulate_dlog_scale, int B, int H, void* workspace,
+                       size_t workspace_bytes, ia_stream_t stream);
+
 /* ---- data-parallel gradient exchange (pure data parallelism, one process per GPU; reference loop being sharded:
  * finetune_multimodal.py:371-468).  RCCL over xGMI behind four calls, for hosts that bind only this header (the Python host of this
  * repository uses torch.distributed, i.e. the same RCCL).  Rank 0 obtains an id and hands its IA_COMM_ID_BYTES bytes to the other

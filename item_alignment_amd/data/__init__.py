@@ -1,2 +1,3 @@
 """Tensor formats feeding the train step (the reference's collate outputs) and synthetic pair generators."""
 from .synthetic import SyntheticCocaPairs, SyntheticItemGraph, one_tower_text, two_tower_text  # noqa: F401
+from .datasets import MultimodalDataset, collate_coca  # noqa: F401,E402

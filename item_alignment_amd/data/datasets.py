@@ -103,6 +103,14 @@ def collate_coca_pair(inputs):
             _t(tpos) if tpos else None, stack_images([i["tgt_image"] for i in keep]), _t([i["labels"] for i in keep]))
 
 
+def collate_coca(inputs):
+    """reference data.py:15-34 (CoCa pre-training): items whose image failed to load are dropped."""
+    keep = [i for i in inputs if i.get("image") is not None]
+    pos = [i["position_ids"] for i in keep if "position_ids" in i]
+    return ([i["item_id"] for i in keep], _t([i["input_ids"] for i in keep]), _t([i["attention_mask"] for i in keep]),
+            _t([i["token_type_ids"] for i in keep]), _t(pos) if pos else None, stack_images([i["image"] for i in keep]))
+
+
 # ------------------------------------------------------------------------------------------------ datasets
 COLON_ID, SEMICOLON_ID = 131, 132        # ":" and ";" in the BERT-zh vocabulary (reference data.py:11-12)
 
@@ -415,6 +423,37 @@ class PairedMultimodalDataset(Dataset):
             rec["tgt_image"] = load_image(tgt_path, self.transform, raw=self.raw)
         except Exception:
             pass
+        return rec
+
+
+class MultimodalDataset(Dataset):
+    """reference data.py:872-915 (CoCa pre-training items: (item_id, title, pvs, image_path)): [BOS] + title [+ [SEP] + pvs] padded to
+    the maximum length, position ids 0..L-1, one image.  The pvs come segmented from the caller, as in the reference's script."""
+
+    def __init__(self, data, image_size, is_training, text_tokenizer, max_seq_len, max_seq_len_pv=None, hflip=0.5, color_jitter=None,
+                 raw=False, seed=None):
+        self.data, self.size, self.raw = data, image_size, raw
+        self.transform = ImageTransform(image_size, is_training, hflip, color_jitter, seed)
+        self.tk, self.max_seq_len, self.max_seq_len_pv = text_tokenizer, max_seq_len, max_seq_len_pv
+
+    def __len__(self):
+        return len(self.data)
+
+    def __getitem__(self, item):
+        item_id, title, pvs, image_path = self.data[item]
+        if self.max_seq_len is None:
+            text, L = pvs, self.max_seq_len_pv
+        elif self.max_seq_len_pv is None:
+            text, L = title, self.max_seq_len
+        else:
+            text, L = " ".join((title, self.tk.sep_token, pvs)), self.max_seq_len + self.max_seq_len_pv
+        rec = dict(_tok(self.tk, " ".join((self.tk.bos_token, text)), L))
+        rec["position_ids"] = list(range(len(rec["input_ids"])))
+        try:
+            rec["image"] = load_image(image_path, self.transform, raw=self.raw)
+        except Exception:
+            pass                        # the collate drops items without an image (reference data.py:902-908, :18-19)
+        rec["item_id"] = item_id
         return rec
 
 

@@ -6,7 +6,7 @@ from .base import (InnerProduct, VecSimClassificationHead, TwoTowerClassificatio
 from .text import (RobertaModel, RobertaOneTower, RobertaTwoTower, RobertaPKGMModel, PKGMOneTower, PKGMTwoTower, TextCNN,
                    TextCNNTwoTower)
 from .image import VisionTransformer, VitTwoTower, NFNetTwoTower, ResNetTwoTower, create_model
-from .multimodal import (RobertaImageModel, RobertaImageOneTower, RobertaImageTwoTower, CoCaModel, CoCaForItemAlignment, LayerNorm,
-                         Residual, RotaryEmbedding, SwiGLU, ParallelTransformerBlock, CrossAttention)
+from .multimodal import (RobertaImageModel, RobertaImageOneTower, RobertaImageTwoTower, CoCaModel, CoCaForItemAlignment, CoCaForPretraining,
+                         LayerNorm, Residual, RotaryEmbedding, SwiGLU, ParallelTransformerBlock, CrossAttention)
 from .graph import GCN, GCN2Conv, GCNTwoTower, GraphAdjacency, load_adjacency
 from .bert_pretrain import BertForPreTraining

@@ -111,6 +111,43 @@ class MaskedLMHeadFn(torch.autograd.Function):
         return dh, None, None, None
 
 
+class TiedCaptionHeadFn(torch.autograd.Function):
+    """CoCaForPretraining's to_logits + CrossEntropyLoss(ignore_index=pad_id) over the rows whose label is not pad (reference
+    multimodal.py:915-922): hidden [B n, H] bf16, rows [M] int64 (the live positions, ascending), labels [M] int64 (none of them pad)
+    -> the mean loss (0-d fp32).  norm: the gamma LayerNorm (`gamma`, the zero `beta` buffer); table: the text tower's word table, whose
+    bf16 shadow is the decoder's weight.  The GEMM and loss calls are MaskedLMHeadFn's, without a bias or a transform."""
+
+    @staticmethod
+    def forward(ctx, hidden, owner, norm, table, rows, labels):
+        x = hidden.index_select(0, rows)
+        y, _, mean, rstd = ops.ln_fwd(x, norm.gamma, norm.beta, 1e-5, write_z=False)
+        logits = ops.gemm(y, owner.arena.shadow_of(table), out_f32=True)
+        lse, _loss_row, loss = ops.vocab_ce_fwd(logits, labels)
+        ctx.owner, ctx.norm, ctx.table, ctx.shape = owner, norm, table, hidden.shape
+        ctx.saved = (x, y, mean, rstd, rows, labels, logits, lse, loss)
+        return loss[0].clone()
+
+    @staticmethod
+    def backward(ctx, dloss):
+        x, y, mean, rstd, rows, labels, logits, lse, loss = ctx.saved
+        norm, table = ctx.norm, ctx.table
+        dlogits = ops.vocab_ce_bwd(logits, labels, lse, loss, dloss.reshape(1).to(F32).contiguous())
+        dy = ops.gemm(dlogits, ctx.owner.arena.shadow_of(table), b_kstrided=True)
+        touched = []
+        if table.requires_grad:      # the decoder's share of the tied table's gradient, += beside the embedding's share
+            ops.gemm(dlogits, y, a_kstrided=True, b_kstrided=True, out=table.grad, out_f32=True, accumulate=True)
+            touched.append(table)
+        wg = norm.gamma.requires_grad
+        dx, _ = ops.ln_bwd(dy, x, mean, rstd, norm.gamma, dgamma=norm.gamma.grad if wg else None)
+        if wg:
+            touched.append(norm.gamma)
+        Fn._notify(touched)
+        dh = torch.zeros(ctx.shape, device=dx.device, dtype=BF16)
+        dh.index_copy_(0, rows, dx)
+        ctx.saved = None
+        return dh, None, None, None, None, None
+
+
 class BertForPreTraining(HipModule, PretrainedMixin):
     """model(input_ids, token_type_ids=None, attention_mask=..., masked_lm_labels=..., next_sentence_label=...) ->
     (total_loss, prediction_scores, seq_relationship_score) with both labels, (prediction_scores, seq_relationship_score) without,

@@ -9,7 +9,7 @@ import ctypes as C
 
 import torch
 
-from .. import _lib
+from .. import _lib, ops
 from .._lib import LayerCfg, LayerGrads, LayerWeights, check, ptr, stream_ptr
 
 BF16, F32 = torch.bfloat16, torch.float32
@@ -844,6 +844,34 @@ class PairSimFn(torch.autograd.Function):
         return dx, dy, None
 
 
+class ContrastiveLossFn(torch.autograd.Function):
+    """0.5 (CE(sim, arange(B)) + CE(sim^T, arange(B))), sim = text_embeds image_embeds^T exp(temperature), as a 0-d fp32 loss (reference
+    multimodal.py:926-930; the embeddings are not normalised).  text_embeds, image_embeds: fp32 [B, H]; temperature: the one-element
+    Parameter, whose gradient is added into its `.grad` view (csrc/contrastive.hip)."""
+
+    @staticmethod
+    def forward(ctx, text_embeds, image_embeds, temperature):
+        _need_gpu(text_embeds, "text embeddings")
+        text_embeds, image_embeds = text_embeds.contiguous(), image_embeds.contiguous()
+        loss, sim, lse_row, lse_col = ops.contrastive_fwd(text_embeds, image_embeds, temperature.detach())
+        ctx.temperature, ctx.saved = temperature, (text_embeds, image_embeds, sim, lse_row, lse_col)
+        return loss[0].clone()
+
+    @staticmethod
+    def backward(ctx, dloss):
+        temperature = ctx.temperature
+        text_embeds, image_embeds, sim, lse_row, lse_col = ctx.saved
+        dloss = dloss.reshape(1).to(F32).contiguous()
+        if temperature.requires_grad:
+            dtext, dimage, _ = ops.contrastive_bwd(text_embeds, image_embeds, temperature.detach(), sim, lse_row, lse_col, dloss,
+                                                   dlog_scale=temperature.grad, accumulate=True)
+            _notify([temperature])
+        else:
+            dtext, dimage, _ = ops.contrastive_bwd(text_embeds, image_embeds, temperature.detach(), sim, lse_row, lse_col, dloss)
+        ctx.saved = None
+        return dtext, dimage, None
+
+
 # --------------------------------------------------------------------------------------------- TextCNN
 # The TextCNN two-tower keeps its parameters as ordinary nn.Parameters outside the arena (TorchAdamW steps them), so these two
 # Functions take the parameters as inputs and hand their gradients back to autograd instead of adding into `.grad` views.
@@ -855,7 +883,6 @@ class TextCNNTowerFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, ids, tcnn, taps, p_embed, p1, p2, stream_base, keep, *params):
-        from .. import ops
         from .base import create_position_ids_from_input_ids
         lib = _lib.load()
         _need_gpu(ids, "input_ids")
@@ -899,7 +926,6 @@ class TextCNNTowerFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from .. import ops
         lib = _lib.load()
         tcnn = ctx.tcnn
         sizes, S = tcnn.filter_sizes, len(tcnn.filter_sizes)

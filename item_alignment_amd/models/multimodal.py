@@ -1,5 +1,6 @@
 """Host-side mirror of the reference's src/models/multimodal.py: RobertaImage{Model,OneTower,TwoTower}
-(RoBERTa + pre-extracted image embeddings) and CoCaForItemAlignment (RoBERTa text tower + ViT image tower).
+(RoBERTa + pre-extracted image embeddings), CoCaForItemAlignment (RoBERTa text tower + ViT image tower) and CoCaForPretraining
+(the same towers under causal multimodal layers, trained with a caption loss and a contrastive loss).
 """
 import os
 
@@ -7,6 +8,7 @@ import torch
 from torch import nn
 
 from . import functional as Fn
+from .bert_pretrain import TiedCaptionHeadFn, _TiedDecoder
 from .base import (ACT_NONE, BaseModelOutput, HipModule, RobertaEmbeddings, RobertaEncoder, RobertaImageEmbeddings, RobertaPooler,
                    SequenceClassifierOutput, TwoTowerClassificationHead, VecSimClassificationHead, cls_rows, init_bert_weights)
 from .image import VisionTransformer
@@ -350,3 +352,92 @@ class CoCaForItemAlignment(HipModule):
         if labels is not None and self.config.loss_type != "ce":
             loss = apply_loss(self.loss_fct, self.config, logits, labels, src, tgt)
         return SequenceClassifierOutput(loss=loss, probs=probs, logits=logits, src_embeds=src, tgt_embeds=tgt)
+
+
+class CoCaForPretraining(HipModule):
+    """reference multimodal.py:843-933: the text tower and the ViT, `num_hidden_layers_multimodal` pairs of a causal
+    ParallelTransformerBlock and a CrossAttention over the image tokens, and `to_logits` = gamma LayerNorm + a Linear tied to the text
+    tower's word table.  forward returns caption_loss_weight * CE(logits, labels, ignore_index=pad_id) + contrastive_loss_weight *
+    0.5 (CE(sim, arange) + CE(sim^T, arange)), sim = text [CLS] . image [CLS] * exp(temperature).  state_dict keys are the reference's.
+
+    The caption head runs on the rows whose label is not pad (TiedCaptionHeadFn), the contrastive loss in csrc/contrastive.hip.  After a
+    forward, `last_losses` holds the two weighted parts (detached) and `caption_live_rows` the number of rows the head ran on.
+
+    Note N2: with labels=None the reference cuts labels = input_ids[:, 2:] against logits of length L - 1 and raises; here
+    the labels are input_ids[:, 1:], the next-token shift that makes the shapes agree.  With explicit labels [B, n] the arithmetic is
+    the reference's.  `image_tokens` is refused: the reference's embed_image drops it too."""
+
+    def __init__(self, config, image_encoder=None, text_encoder=None, pad_id=0):
+        super().__init__()
+        if image_encoder is None or text_encoder is None:
+            raise ValueError("CoCaForPretraining needs both encoders: the image tower feeds the cross-attention and the contrastive loss")
+        if config.vocab_size % 8:
+            raise ValueError(f"CoCaForPretraining: vocab_size {config.vocab_size} is not a multiple of 8, which the decoder GEMMs need: resize "
+                             f"the word table to {(config.vocab_size + 7) // 8 * 8} rows (pad the vocabulary with unused tokens)")
+        img_dim = getattr(image_encoder, "num_features", config.hidden_size)
+        if img_dim != config.hidden_size:
+            raise ValueError(f"CoCaForPretraining: image width {img_dim} != hidden_size {config.hidden_size}: the contrastive product and "
+                             "the cross-attention both need equal widths (the reference's einsum raises there), and no projection is invented")
+        self.config = config
+        self.pad_id = pad_id
+        self.caption_loss_weight = config.caption_loss_weight
+        self.contrastive_loss_weight = config.contrastive_loss_weight
+        self.coca = CoCaModel(config, image_encoder, text_encoder)
+        self.temperature = nn.Parameter(torch.Tensor([1.]))
+        self.multimodal_layers = nn.ModuleList([])
+        dh = config.hidden_size // config.num_attention_heads_multimodal
+        for _ in range(config.num_hidden_layers_multimodal):
+            self.multimodal_layers.append(nn.ModuleList([
+                Residual(ParallelTransformerBlock(dim=config.hidden_size, dim_head=dh, heads=config.num_attention_heads_multimodal,
+                                                  ff_mult=config.feedforward_multiplication_multimodal, is_decoding=True)),
+                Residual(CrossAttention(dim=config.hidden_size, dim_head=dh, heads=config.num_attention_heads_multimodal,
+                                        parallel_ff=True, ff_mult=config.feedforward_multiplication_multimodal))]))
+        # `to_logits.1.weight` is the word table itself, the same Parameter: the arena holds it once
+        self.to_logits = nn.Sequential(LayerNorm(config.hidden_size), _TiedDecoder(text_encoder.embeddings.word_embeddings.weight))
+        self.last_losses, self.caption_live_rows = None, None
+        adopt(self, image_encoder, text_encoder)
+
+    def encode(self, input_ids, attention_mask, token_type_ids, position_ids, images):
+        """-> (text tokens behind the multimodal layers [B n, H] bf16, text [CLS] embeddings [B, H] fp32, image [CLS] embeddings [B, H]
+        fp32): everything in front of the two losses"""
+        B, n = input_ids.shape
+        img_tok = self.coca.embed_image(images)                                                     # [B, N, H] bf16
+        i_cls = self.coca.img_encoder.forward_head(img_tok, pre_logits=True)                        # [B, H] fp32
+        # the multimodal layers attend over all n text positions with no padding mask: the padded rows are read
+        txt = self.coca.embed_text(input_ids, attention_mask, token_type_ids, position_ids, padded_rows_matter=True)   # [B, n, H] bf16
+        H, N = txt.shape[-1], img_tok.shape[1]
+        x = txt.reshape(B * n, H)
+        t_cls = Fn.GatherRowsFn.apply(x, self.anchor, cls_rows(B, n, 0, x.device), 0.0, 0)          # last_hidden[:, 0]
+        ctx = img_tok.reshape(B * N, H)
+        for attn_ff, cross_attn in self.multimodal_layers:
+            x = attn_ff(x, B, n)
+            x = cross_attn(x, ctx, B, n, N)
+        return x, t_cls, i_cls
+
+    def forward(self, input_ids, attention_mask, token_type_ids, position_ids, images=None, image_tokens=None, labels=None):
+        if image_tokens is not None:
+            raise NotImplementedError("CoCaForPretraining: precomputed image_tokens are not supported (the reference's embed_image ignores "
+                                      "them and fails on the missing image embeddings)")
+        if images is None:
+            raise ValueError("CoCaForPretraining: images are required")
+        self.ensure_arena()
+        if labels is None:
+            labels = input_ids[:, 1:]
+            input_ids, attention_mask = input_ids[:, :-1].contiguous(), attention_mask[:, :-1].contiguous()
+            token_type_ids, position_ids = token_type_ids[:, :-1].contiguous(), position_ids[:, :-1].contiguous()
+        B, n = input_ids.shape
+        if tuple(labels.shape) != (B, n):
+            raise ValueError(f"CoCaForPretraining: labels {tuple(labels.shape)} do not match the {B} x {n} logits")
+        x, t_cls, i_cls = self.encode(input_ids, attention_mask, token_type_ids, position_ids, images)
+        flat = labels.reshape(-1).to(torch.long)
+        rows = (flat != self.pad_id).nonzero(as_tuple=False).squeeze(1)      # the one host sync of the head: M_live sizes its tensors
+        self.caption_live_rows = rows.numel()
+        if rows.numel() == 0:
+            caption = torch.full((), float("nan"), device=x.device, dtype=torch.float32)      # torch's mean over no row; no kernel runs with M = 0
+        else:
+            table = self.to_logits[1].weight
+            caption = TiedCaptionHeadFn.apply(x, self, self.to_logits[0], table, rows, flat.index_select(0, rows).contiguous())
+        caption = caption * self.caption_loss_weight
+        contrastive = Fn.ContrastiveLossFn.apply(t_cls, i_cls, self.temperature) * self.contrastive_loss_weight
+        self.last_losses = (caption.detach(), contrastive.detach())
+        return caption + contrastive

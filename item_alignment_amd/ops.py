@@ -413,3 +413,49 @@ def vocab_ce_bwd(logits, labels, lse, loss, dloss, V=None, *, ldg=None, out=None
     check(lib.ia_vocab_ce_bwd(logits.data_ptr(), ld, labels.data_ptr(), lse.data_ptr(), loss.data_ptr(), dloss.data_ptr(), out.data_ptr(),
                               out.shape[1], M, V, stream_ptr()), "ia_vocab_ce_bwd")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ contrastive loss
+def contrastive_fwd(text, image, log_scale):
+    """0.5 (CE(sim, arange) + CE(sim^T, arange)), sim = exp(log_scale) text image^T; text, image [B, H] fp32, log_scale a one-element
+    fp32 device tensor -> (loss [1], sim [B, B], lse_row [B], lse_col [B]), all fp32 (ia_contrastive_fwd)."""
+    lib = _lib.load()
+    _need(text, F32, "text"); _need(image, F32, "image"); _need(log_scale, F32, "log_scale")
+    B, H = text.shape
+    if tuple(image.shape) != (B, H) or log_scale.numel() != 1:
+        raise ValueError(f"contrastive_fwd: text {tuple(text.shape)} and image {tuple(image.shape)} must agree, log_scale has one element")
+    dev = text.device
+    sim = torch.empty((B, B), device=dev, dtype=F32)
+    lse_row = torch.empty(B, device=dev, dtype=F32)
+    lse_col = torch.empty(B, device=dev, dtype=F32)
+    loss = torch.empty(1, device=dev, dtype=F32)
+    ws_bytes = lib.ia_contrastive_workspace_bytes(B)
+    ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+    check(lib.ia_contrastive_fwd(text.data_ptr(), H, image.data_ptr(), H, log_scale.data_ptr(), sim.data_ptr(), B, lse_row.data_ptr(),
+                                 lse_col.data_ptr(), loss.data_ptr(), B, H, ws.data_ptr(), ws_bytes, stream_ptr()), "ia_contrastive_fwd")
+    return loss, sim, lse_row, lse_col
+
+
+def contrastive_bwd(text, image, log_scale, sim, lse_row, lse_col, dloss, *, dlog_scale=None, accumulate=False):
+    """-> (dtext [B, H], dimage [B, H], dlog_scale [1]), fp32 (ia_contrastive_bwd).  dloss: fp32 device scalar; sim, lse_row, lse_col: what
+    contrastive_fwd returned.  accumulate: add into the given dlog_scale instead of writing it."""
+    lib = _lib.load()
+    B, H = text.shape
+    for t, name in ((text, "text"), (image, "image"), (log_scale, "log_scale"), (sim, "sim"), (lse_row, "lse_row"), (lse_col, "lse_col"), (dloss, "dloss"),
+                    (dlog_scale, "dlog_scale")):
+        _need(t, F32, name)
+    if tuple(image.shape) != (B, H) or tuple(sim.shape) != (B, B) or lse_row.numel() != B or lse_col.numel() != B or dloss.numel() != 1:
+        raise ValueError("contrastive_bwd: shapes do not belong to one contrastive_fwd call")
+    if accumulate and dlog_scale is None:
+        raise ValueError("contrastive_bwd: accumulate needs dlog_scale")
+    dev = text.device
+    if dlog_scale is None:
+        dlog_scale = torch.empty(1, device=dev, dtype=F32)
+    dtext = torch.empty((B, H), device=dev, dtype=F32)
+    dimage = torch.empty((B, H), device=dev, dtype=F32)
+    ws_bytes = lib.ia_contrastive_workspace_bytes(B)
+    ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+    check(lib.ia_contrastive_bwd(text.data_ptr(), H, image.data_ptr(), H, log_scale.data_ptr(), sim.data_ptr(), B, lse_row.data_ptr(),
+                                 lse_col.data_ptr(), dloss.data_ptr(), dtext.data_ptr(), H, dimage.data_ptr(), H, dlog_scale.data_ptr(),
+                                 int(accumulate), B, H, ws.data_ptr(), ws_bytes, stream_ptr()), "ia_contrastive_bwd")
+    return dtext, dimage, dlog_scale

@@ -5,4 +5,5 @@ from item_alignment_amd.data.datasets import (RobertaOneTowerDataset, RobertaTwo
                                               RobertaImageOneTowerDataset, RobertaImageTwoTowerDataset, PairedImageDataset,
                                               PairedMultimodalDataset, collate_one_tower, collate_two_tower, collate_image,
                                               collate_multimodal, collate_multimodal_two_tower, collate_coca_pair)
+from item_alignment_amd.data.datasets import MultimodalDataset, collate_coca  # noqa: F401,E402
 from item_alignment_amd.data.datasets import GCNDataset, collate_gnn  # noqa: F401,E402
