@@ -166,6 +166,31 @@ int ia_row_groups_host(const uint8_t* row_live, int M_rows, int* list);
 int ia_gemm_dgrad_groups_rows(const void* dY, int ldy, const void* W, int w_kstrided, int ldw, void* dX, int ldx, int M_rows, int N_in,
                               int K_out, const void* aux, int ldaux, void* C2, const uint8_t* row_live, void* workspace,
                               size_t workspace_bytes, ia_stream_t stream);
+/* (ABI 20, third form) The row filters of ia_gemm_fwd_rows and ia_gemm_dgrad_rows in SLABS of 8 rows (rows 8t .. 8t+7, clipped to
+ * M_rows; aligned to multiples of 8 rows of the tensor, never overlapping): a slab without a live row is neither fetched nor multiplied.
+ * A padded sequence never lines up with 32-row blocks, so every sequence pays for a partly dead block at its end; in slabs it pays for
+ * at most 7 rows.  Every row of a slab that holds a live row is bit-identical to the unfiltered call's.
+ * The slab list (ia_row_slabs, ia_row_slabs_host from host memory; ia_row_slabs_bytes, 32-byte aligned): 8 header words -- [0] live
+ * slabs, [1] dead slabs, [2] slabs -- then the live slabs, ascending, 32 to an M-tile of the kernel and inside a tile in the order
+ * [wave][piece]: the i-th live slab sits at entry (i & ~31) + (i & 3) * 8 + ((i & 31) >> 2), the entries behind the last one of the last
+ * tile are -1; then, behind room for every slab rounded up to a multiple of 32, the dead slabs, ascending.
+ * ia_row_slabs_offset: where the list sits in the buffer ia_layer_cfg::row_blocks points into (masked_rows_dead bit 6, value 32).
+ * ia_gemm_fwd_slabs: epilogue IA_EPI_NONE, IA_EPI_BIAS with scaled_cols / col_scale, or IA_EPI_BIAS_GELU with C2; fill_dead_rows as in
+ * ia_gemm_fwd_rows, by slab.  ia_gemm_dgrad_slabs: IA_EPI_NONE or IA_EPI_ADD; the rows of the dead slabs of dX are written as zeros.
+ * Other epilogues: IA_ERR_UNSUPPORTED.  row_live == NULL: the unfiltered call.  Workspace with row_live (32-byte aligned):
+ * ia_gemm_slabs_workspace_bytes, the list.  The shapes that filter: ia_gemm_fwd_rows_filters / ia_gemm_dgrad_rows_filters; others run
+ * every row. */
+size_t ia_row_slabs_bytes(int M_rows);
+size_t ia_row_slabs_offset(int M_rows);
+int ia_row_slabs(const uint8_t* row_live, int M_rows, int* list, ia_stream_t stream);
+int ia_row_slabs_host(const uint8_t* row_live, int M_rows, int* list);
+size_t ia_gemm_slabs_workspace_bytes(int M_rows);
+int ia_gemm_fwd_slabs(const void* X, int ldx, const void* W, int ldw, void* Y, int ldy, int M_rows, int N_out, int K_in, int epilogue,
+                      const float* bias, void* C2, int scaled_cols, float col_scale, const uint8_t* row_live, int fill_dead_rows,
+                      void* workspace, size_t workspace_bytes, ia_stream_t stream);
+int ia_gemm_dgrad_slabs(const void* dY, int ldy, const void* W, int w_kstrided, int ldw, void* dX, int ldx, int M_rows, int N_in, int K_out,
+                        int epilogue, const void* aux, int ldaux, const uint8_t* row_live, void* workspace, size_t workspace_bytes,
+                        ia_stream_t stream);
 /* Diagnostics (tests, A/B runs; ABI 20): on == 0 makes the layer calls ignore ia_layer_cfg::out_row_live (every row behind the attention
  * runs under the layer's other filter, as without it); returns the previous setting. */
 int ia_debug_out_rows(int on);
@@ -717,6 +742,10 @@ typedef struct {
    * Bit 4 (value 8), read by the backward together with live_ktiles: live_ktiles points at a 32-row block mask (ia_kblock_mask) and the
    * weight gradients walk live 32-row blocks; without the bit a caller's live_ktiles is a 64-row mask (ia_ktile_mask) and they walk live
    * 64-row k-tiles.  Bit 5 (value 16): the same of out_live_ktiles.  With a NULL pointer the backward builds the block mask itself.
+   * (ABI 20, third form) Bit 6 (value 32), read by the forward and the backward together with row_blocks: the buffer row_blocks points
+   * into also holds the 8-row slab list of the same mask (ia_row_slabs) at byte offset ia_row_slabs_offset(B * L); without the bit the
+   * layer calls build that list per call.  The QKV, out-projection, fc1 (training form) and fc2 GEMMs of the forward and the three plain
+   * data gradients run over it: what is said of 32-row blocks above holds of 8-row slabs there.
    * No bit changes a gradient. */
   int masked_rows_dead;
   /* (ABI 19) optional, device pointers, NULL = the layer call builds its own: the 32-row block list (ia_row_blocks) and the live-k-tile

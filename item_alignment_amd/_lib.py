@@ -71,6 +71,13 @@ SIGNATURES = {
     "ia_row_groups_packed_offset": (sz, [i32]),
     "ia_row_groups_packed": (i32, [vp, i32, vp, vp]),
     "ia_row_groups_packed_host": (i32, [vp, i32, vp]),
+    "ia_row_slabs_bytes": (sz, [i32]),
+    "ia_row_slabs_offset": (sz, [i32]),
+    "ia_row_slabs": (i32, [vp, i32, vp, vp]),
+    "ia_row_slabs_host": (i32, [vp, i32, vp]),
+    "ia_gemm_slabs_workspace_bytes": (sz, [i32]),
+    "ia_gemm_fwd_slabs": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, i32, f32, vp, i32, vp, sz, vp]),
+    "ia_gemm_dgrad_slabs": (i32, [vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, sz, vp]),
     "ia_gemm_dgrad_packed": (i32, [vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, sz, vp]),
     "ia_debug_q_rows": (i32, [i32]),
     "ia_prof_begin": (i32, [i32, i32]),

@@ -218,6 +218,14 @@ __attribute__((visibility("hidden"))) int ia_gemm_dgrad_blocks(const void* dY, i
 __attribute__((visibility("hidden"))) int ia_gemm_fwd_blocks(const void* X, int ldx, const void* W, int ldw, void* Y, int ldy, int M_rows, int N_out,
                                                              int K_in, int epilogue, const float* bias, void* C2, int scaled_cols, float col_scale,
                                                              const int* row_blocks, int fill_dead_rows, hipStream_t stream);
+// the two over the 8-row slabs of a slab list (ia_row_slabs): IA_EPI_NONE, IA_EPI_BIAS (scaled_cols / col_scale), IA_EPI_BIAS_GELU forward,
+// IA_EPI_NONE / IA_EPI_ADD data gradient (dead slabs written as zeros).  row_slabs == NULL or a shape the remapped kernel does not serve: every row.
+__attribute__((visibility("hidden"))) int ia_gemm_fwd_slab_list(const void* X, int ldx, const void* W, int ldw, void* Y, int ldy, int M_rows, int N_out,
+                                                                int K_in, int epilogue, const float* bias, void* C2, int scaled_cols, float col_scale,
+                                                                const int* row_slabs, int fill_dead_rows, hipStream_t stream);
+__attribute__((visibility("hidden"))) int ia_gemm_dgrad_slab_list(const void* dY, int ldy, const void* W, int w_kstrided, int ldw, void* dX, int ldx,
+                                                                  int M_rows, int N_in, int K_out, int epilogue, const void* aux, int ldaux,
+                                                                  const int* row_slabs, hipStream_t stream);
 // the same for Y = X W^T + bias + aux (IA_EPI_BIAS_ADD: the fc2 of a pre-LN layer with its residual); aux is read in the live blocks only
 __attribute__((visibility("hidden"))) int ia_gemm_fwd_blocks_add(const void* X, int ldx, const void* W, int ldw, void* Y, int ldy, int M_rows,
                                                                  int N_out, int K_in, const float* bias, const void* aux, int ldaux,

@@ -33,6 +33,7 @@ struct FwdBufs {
   float* lse; float* mean1; float* rstd1; float* mean2; float* rstd2;
   int* row_blk;  // masked_rows_dead bit 2: the forward's own 32-row block list (when the caller hands none in ia_layer_cfg::row_blocks)
   int* out_blk;  // out_row_live: the forward's own block list of it (when the caller hands none in ia_layer_cfg::out_row_blocks)
+  int* row_slab; // masked_rows_dead bit 2: the forward's own 8-row slab list (when the caller hands none behind ia_layer_cfg::row_blocks, bit 6)
   size_t bytes;
 };
 
@@ -55,6 +56,7 @@ FwdBufs carve_stash(const ia_layer_cfg* c, void* base) {
   s.mean2 = (float*)a.take(M * 4); s.rstd2 = (float*)a.take(M * 4);
   s.row_blk = (int*)a.take(ia_row_blocks_bytes((int)M));
   s.out_blk = (int*)a.take(ia_row_blocks_bytes((int)M));
+  s.row_slab = (int*)a.take(ia_row_slabs_bytes((int)M));
   s.bytes = a.bytes;
   return s;
 }
@@ -73,6 +75,7 @@ FwdBufs carve_infer(const ia_layer_cfg* c, void* base) {
   s.mean1 = s.mean2 = (float*)a.take(M * 4); s.rstd1 = s.rstd2 = (float*)a.take(M * 4);
   s.row_blk = (int*)a.take(ia_row_blocks_bytes((int)M));
   s.out_blk = (int*)a.take(ia_row_blocks_bytes((int)M));
+  s.row_slab = (int*)a.take(ia_row_slabs_bytes((int)M));
   s.bytes = a.bytes;
   return s;
 }
@@ -80,6 +83,7 @@ FwdBufs carve_infer(const ia_layer_cfg* c, void* base) {
 struct Scratch {
   char* g0; char* g1; char* g2; char* gI; char* gqkv; float* delta; char* ws; size_t ws_bytes; char* gws; size_t gws_bytes; uint32_t* live_kt; int* row_blk;
   int* pack_blk;      // masked_rows_dead: the block-packed list of the x gelu' data gradient (when the caller hands none behind row_blocks)
+  int* row_slab;      // masked_rows_dead: the 8-row slab list of the plain data gradients (when the caller hands none behind row_blocks, bit 6)
   uint32_t* out_kt; int* out_blk; int* out_grp;      // out_row_live: its 32-row block mask (ia_kblock_mask), block list and group list (when the caller hands none)
   size_t bytes;
 };
@@ -108,6 +112,7 @@ Scratch carve_scratch(const ia_layer_cfg* c, void* base) {
   s.out_kt = (uint32_t*)a.take(ia_kblock_mask_bytes((int)M));
   s.out_blk = (int*)a.take(ia_row_blocks_bytes((int)M));
   s.out_grp = (int*)a.take(ia_row_groups_bytes((int)M));
+  s.row_slab = (int*)a.take(ia_row_slabs_bytes((int)M));
   s.bytes = a.bytes;
   return s;
 }
@@ -138,7 +143,10 @@ int out_q_rows(const ia_layer_cfg* c) { return (out_live(c) && c->out_q_rows > 0
 // provides one (both operands k-contiguous: the faster form, ia_layer_weights::wt_*), else W read k-strided.
 // With a block list (ia_row_blocks), over the 32-row blocks that hold a live row only; the other rows of dx are written as zeros.
 int dgrad(const void* dy, int k_out, const void* w, const void* wt, int n_in, void* dx, int M, int epilogue, const void* aux, int ldaux, void* c2,
-          void* ws, size_t ws_bytes, ia_stream_t st, const int* row_blk = nullptr, const int* row_grp = nullptr, const int* row_pack = nullptr) {
+          void* ws, size_t ws_bytes, ia_stream_t st, const int* row_blk = nullptr, const int* row_grp = nullptr, const int* row_pack = nullptr,
+          const int* row_slab = nullptr) {
+  if (row_slab && (epilogue == IA_EPI_NONE || epilogue == IA_EPI_ADD))      // the live 8-row slabs (ia_row_slabs), the others as zeros
+    return ia_gemm_dgrad_slab_list(dy, k_out, wt ? wt : w, wt ? 0 : 1, wt ? k_out : n_in, dx, n_in, M, n_in, k_out, epilogue, aux, ldaux, row_slab, st);
   if (row_grp && epilogue == IA_EPI_DGELU_COLSUM)      // whole 128-row groups: the column sums keep the dense kernel's partials
     return ia_gemm_dgrad_groups(dy, k_out, wt ? wt : w, wt ? 0 : 1, wt ? k_out : n_in, dx, n_in, M, n_in, k_out, aux, ldaux, c2, row_grp, ws, ws_bytes, st);
   if (row_pack && epilogue == IA_EPI_DGELU_COLSUM)     // live blocks packed by whole groups: every group's partial keeps its slot and its bits
@@ -165,8 +173,11 @@ int wgrad(const void* dy, int n_out, const void* x, int n_in, float* dw, int M, 
 // Needs the q | k boundary on a 128-column tile boundary of the GEMM; other hidden sizes take the plain projection and kernels.
 bool q_prescale(const ia_layer_cfg* c) { return (c->H & 127) == 0; }
 int qkv_proj(const ia_layer_cfg* c, const void* x, const ia_layer_weights* w, void* qkv, int M, float scale, ia_stream_t st,
-             const int* row_blk = nullptr) {
+             const int* row_blk = nullptr, const int* row_slab = nullptr) {
   const int H = c->H;
+  if (row_slab)     // the live 8-row slabs only, the others as zeros
+    return ia_gemm_fwd_slab_list(x, H, w->w_qkv, H, qkv, 3 * H, M, 3 * H, H, IA_EPI_BIAS, w->b_qkv, nullptr, q_prescale(c) ? H : 0,
+                                 q_prescale(c) ? scale * 1.4426950408889634f : 1.f, row_slab, 1, st);
   if (row_blk)      // the live 32-row blocks only, the others as zeros: the attention kernels read every row of q, k and v
     return ia_gemm_fwd_blocks(x, H, w->w_qkv, H, qkv, 3 * H, M, 3 * H, H, IA_EPI_BIAS, w->b_qkv, nullptr, q_prescale(c) ? H : 0,
                               q_prescale(c) ? scale * 1.4426950408889634f : 1.f, row_blk, 1, st);
@@ -226,12 +237,18 @@ int layer_forward(const ia_layer_cfg* c, const ia_layer_weights* w, const void* 
     // are not filled: only their LayerNorm reads them, which skips the dead rows and, in the training form, overwrites them in place.
     const uint8_t* live = ((c->masked_rows_dead & 3) == 3 && !c->cu_seqlens && key_mask && g_fwd_rows) ? key_mask : nullptr;
     const int* row_blk = nullptr;
+    // ... and the GEMMs whose slab form exists take the mask in 8-row slabs (ia_row_slabs: a sequence's rows never line up with 32-row
+    // blocks).  The same readers, the same argument: a dead slab of a live block holds zeros where a dead block does, and is unwritten
+    // where a dead block is (the two projection outputs).  The caller's list under bit 6 (value 32), or one per call.
+    const int* row_slab = nullptr;
     if (live) {
       row_blk = c->row_blocks;
+      if (row_blk && (c->masked_rows_dead & 32)) row_slab = (const int*)((const char*)row_blk + ia_row_slabs_offset(M));
+      else { IA_TRY(ia_row_slabs(live, M, s.row_slab, st)); row_slab = s.row_slab; }
       if (!row_blk) { IA_TRY(ia_row_blocks(live, M, s.row_blk, st)); row_blk = s.row_blk; }
     }
     // qkv = x Wqkv^T + b
-    IA_TRY(qkv_proj(c, x, w, s.qkv, M, scale, st, row_blk));
+    IA_TRY(qkv_proj(c, x, w, s.qkv, M, scale, st, row_blk, row_slab));
     IA_TRY(attn_fwd(c, s.qkv, key_mask, s.ctx, s.lse, scale, attn_drop, attn_seed, st));
     // out_row_live: behind the attention only the rows the caller reads are live (a subset of the live keys) -- the same rules with that
     // mask and its block list: the LayerNorms leave zeros in the other rows (so y1 and, in the training form, z1 / z2 are finite in every
@@ -240,17 +257,22 @@ int layer_forward(const ia_layer_cfg* c, const ia_layer_weights* w, const void* 
       live = olive;
       row_blk = c->out_row_blocks;
       if (!row_blk) { IA_TRY(ia_row_blocks(olive, M, s.out_blk, st)); row_blk = s.out_blk; }
+      row_slab = nullptr;      // (out_row_live keeps its 32-row lists)
     }
     // z1 = x + dropout(ctx Wo^T + b_o); y1 = LN1(z1)
-    if (row_blk) IA_TRY(ia_gemm_fwd_blocks(s.ctx, H, w->w_o, H, s.proj, H, M, H, H, IA_EPI_NONE, nullptr, nullptr, 0, 1.f, row_blk, 0, st));
+    if (row_slab) IA_TRY(ia_gemm_fwd_slab_list(s.ctx, H, w->w_o, H, s.proj, H, M, H, H, IA_EPI_NONE, nullptr, nullptr, 0, 1.f, row_slab, 0, st));
+    else if (row_blk) IA_TRY(ia_gemm_fwd_blocks(s.ctx, H, w->w_o, H, s.proj, H, M, H, H, IA_EPI_NONE, nullptr, nullptr, 0, 1.f, row_blk, 0, st));
     else IA_TRY(ia_gemm_bf16(s.ctx, 0, H, w->w_o, 0, H, s.proj, 0, H, M, H, H, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, st));
     IA_TRY(ia_ln_fwd_rows(s.proj, w->b_o, x, keep ? s.proj : nullptr, s.ln, s.mean1, s.rstd1, w->ln1_g, w->ln1_b, M, H, c->eps, hidden_drop, seed,
                           ln1_stream, live, st));
     // h = gelu(y1 W1^T + b1)
-    if (row_blk) IA_TRY(ia_gemm_fwd_blocks(s.ln, H, w->w_fc1, H, s.hact, I, M, I, H, gelu, w->b_fc1, s.hpre, 0, 1.f, row_blk, 1, st));
+    // (the forward-only activation epilogue has no slab form: it keeps the blocks)
+    if (row_slab && keep) IA_TRY(ia_gemm_fwd_slab_list(s.ln, H, w->w_fc1, H, s.hact, I, M, I, H, gelu, w->b_fc1, s.hpre, 0, 1.f, row_slab, 1, st));
+    else if (row_blk) IA_TRY(ia_gemm_fwd_blocks(s.ln, H, w->w_fc1, H, s.hact, I, M, I, H, gelu, w->b_fc1, s.hpre, 0, 1.f, row_blk, 1, st));
     else IA_TRY(ia_gemm_bf16(s.ln, 0, H, w->w_fc1, 0, H, s.hact, 0, I, M, I, H, gelu, w->b_fc1, nullptr, 0, s.hpre, 0, nullptr, 0, st));
     // z2 = y1 + dropout(h W2^T + b2); y = LN2(z2)
-    if (row_blk) IA_TRY(ia_gemm_fwd_blocks(s.hact, I, w->w_fc2, I, s.ffn, H, M, H, I, IA_EPI_NONE, nullptr, nullptr, 0, 1.f, row_blk, 0, st));
+    if (row_slab) IA_TRY(ia_gemm_fwd_slab_list(s.hact, I, w->w_fc2, I, s.ffn, H, M, H, I, IA_EPI_NONE, nullptr, nullptr, 0, 1.f, row_slab, 0, st));
+    else if (row_blk) IA_TRY(ia_gemm_fwd_blocks(s.hact, I, w->w_fc2, I, s.ffn, H, M, H, I, IA_EPI_NONE, nullptr, nullptr, 0, 1.f, row_blk, 0, st));
     else IA_TRY(ia_gemm_bf16(s.hact, 0, I, w->w_fc2, 0, I, s.ffn, 0, H, M, H, I, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, st));
     IA_TRY(ia_ln_fwd_rows(s.ffn, w->b_fc2, s.ln, keep ? s.ffn : nullptr, y, s.mean2, s.rstd2, w->ln2_g, w->ln2_b, M, H, c->eps, hidden_drop, seed,
                           ln2_stream, live, st));
@@ -402,6 +424,14 @@ extern "C" int ia_layer_bwd2(const ia_layer_cfg* c, const ia_layer_weights* w, c
       if (c->row_blocks && (c->masked_rows_dead & 4)) row_pack = (const int*)((const char*)c->row_blocks + ia_row_groups_packed_offset(M));
       else { IA_TRY(ia_row_groups_packed(live, M, k.pack_blk, st)); row_pack = k.pack_blk; }
     }
+    // ... and the three plain data gradients the same mask in 8-row slabs (ia_row_slabs): the caller's list behind its row_blocks
+    // (masked_rows_dead bit 6, value 32), or one per call.  Withheld with the block list.
+    const int* row_slab = nullptr;
+    if (row_blk) {
+      if (c->row_blocks && (c->masked_rows_dead & 32)) row_slab = (const int*)((const char*)c->row_blocks + ia_row_slabs_offset(M));
+      else { IA_TRY(ia_row_slabs(live, M, k.row_slab, st)); row_slab = k.row_slab; }
+    }
+    const int* const slab2 = olive ? nullptr : row_slab;
     // behind the attention: out_row_live's lists when given (a subset of the live keys), else the key mask's
     const uint8_t* const live2 = olive ? olive : live;
     const uint32_t* const kt2 = olive ? okt : live_kt;
@@ -422,7 +452,7 @@ extern "C" int ia_layer_bwd2(const ia_layer_cfg* c, const ia_layer_weights* w, c
     // Neither list: every row.
     IA_TRY(dgrad(d_ffn, H, w->w_fc2, w->wt_fc2, I, k.gI, M, IA_EPI_DGELU_COLSUM, s.hpre, I, g->b_fc1, k.ws, k.ws_bytes, st, nullptr, ogrp, row_pack));
     IA_TRY(wgrad(k.gI, I, s.ln, H, (float*)g->w_fc1, M, kt2, kb2, k.gws, k.gws_bytes, st));
-    IA_TRY(dgrad(k.gI, I, w->w_fc1, w->wt_fc1, H, k.g2, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, blk2));
+    IA_TRY(dgrad(k.gI, I, w->w_fc1, w->wt_fc1, H, k.g2, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, blk2, nullptr, nullptr, slab2));
     // LN1 backward: d(y1) = g2 (through fc1) + g0 (residual into LN2) -> dz1 (the layer input's residual-path gradient) in
     // dz1buf: the caller's dx2 when the split form is wanted, else g0 (in place over the term just consumed)
     char* dz1buf = dx2 ? (char*)dx2 : k.g0;
@@ -431,13 +461,13 @@ extern "C" int ia_layer_bwd2(const ia_layer_cfg* c, const ia_layer_weights* w, c
     const char* d_att = drop ? k.g1 : dz1buf;
     IA_TRY(wgrad(d_att, H, s.ctx, H, (float*)g->w_o, M, kt2, kb2, k.gws, k.gws_bytes, st));
     // (d_ctx and dz1 are zeros outside out_row_live: the attention backward and the QKV data gradient's "+ dz1" read every live key's row)
-    IA_TRY(dgrad(d_att, H, w->w_o, w->wt_o, H, k.g2, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, blk2));
+    IA_TRY(dgrad(d_att, H, w->w_o, w->wt_o, H, k.g2, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, blk2, nullptr, nullptr, slab2));
     IA_TRY(attn_bwd(c, s.qkv, key_mask, s.ctx, k.g2, s.lse, k.delta, k.gqkv, g->b_qkv, k.ws, k.ws_bytes, scale, c->attn_drop, attn_seed, st));
     IA_TRY(wgrad(k.gqkv, 3 * H, x, H, (float*)g->w_qkv, M, live_kt, live_kb, k.gws, k.gws_bytes, st));
     if (dx2)   // split form: dx = the attention sub-block's data gradient, dx2 = dz1 (already written)
-      IA_TRY(dgrad(k.gqkv, 3 * H, w->w_qkv, w->wt_qkv, H, dx, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, row_blk));
+      IA_TRY(dgrad(k.gqkv, 3 * H, w->w_qkv, w->wt_qkv, H, dx, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, row_blk, nullptr, nullptr, row_slab));
     else
-      IA_TRY(dgrad(k.gqkv, 3 * H, w->w_qkv, w->wt_qkv, H, dx, M, IA_EPI_ADD, dz1buf, H, nullptr, nullptr, 0, st, row_blk));
+      IA_TRY(dgrad(k.gqkv, 3 * H, w->w_qkv, w->wt_qkv, H, dx, M, IA_EPI_ADD, dz1buf, H, nullptr, nullptr, 0, st, row_blk, nullptr, nullptr, row_slab));
   } else {
     if (!c->dy_colsum_done) IA_TRY(ia_colsum(dy, H, M, H, g->b_fc2, 1, k.ws, k.ws_bytes, st));
     // (okt / oblk / ogrp are NULL without out_row_live: the helpers then make the plain every-row calls)

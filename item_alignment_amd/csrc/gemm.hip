@@ -58,6 +58,12 @@ constexpr int EPI_NONE_BLK = 9;
 // operands k-contiguous) skip the blocks whose rows nobody reads (padded positions under ia_layer_cfg::masked_rows_dead bit 2); there the fill is
 // the caller's choice (GemmArgs::rows_fill): without it the dead blocks of C / C2 are not written at all.
 constexpr int EPI_ROWS = 16;
+// EPI_ROWS + EPI_SLABS + e (library-internal; e = EPI_NONE, EPI_ADD, and on k-contiguous operands EPI_BIAS, EPI_BIAS_GELU): the same remap in
+// 8-row slabs.  GemmArgs::row_blk is a list ia_row_slabs wrote; an M-tile is 32 consecutive entries of it.  A DMA piece is 32 rows of
+// which wave w carries rows 8w .. 8w+7, so each wave hands its own slab to each piece (eight scalars per wave, where the block form has
+// eight per workgroup); the epilogue stores in passes of 8 whole rows, one slab each (sixteen scalars per wave).  Slabs are aligned to
+// multiples of 8 rows of the tensor and never overlap: no row is computed, stored or summed twice, and no live row's arithmetic changes.
+constexpr int EPI_SLABS = 32;
 // EPI_BIAS_GELU_ACT: the forward-only form of EPI_BIAS_GELU (activation only: no derivative is evaluated or stored)
 
 struct GemmArgs {
@@ -789,6 +795,66 @@ IA_DEV Blk8 tile_blocks(const GemmArgs& p, int bm, int n_live) {
   return load_blk8(p.row_blk, bm, n_live);
 }
 
+// EPI_SLABS: the list ia_row_slabs wrote -- the header of ia_row_blocks (counted in slabs), then 32 entries per M-tile in the order
+// [wave][piece]: entry w * 8 + j of a tile is its slab 4j + w in ascending order, the 8 rows wave w carries of DMA piece j.  The entries
+// behind the last live slab of the last tile are -1.  A wave's eight DMA sources are one aligned 32-byte scalar load, its sixteen
+// epilogue rows (pieces 4 wm .. 4 wm + 3 of every wave's run) four 16-byte ones.
+constexpr int SLAB_TILE = 32;
+struct RowSlab { int r[16]; };         // first row of the slab behind pass it of the wave's block mi at [mi * 4 + it], negative = none
+IA_DEV int slab_pos(int t) { return (t & 3) * 8 + (t >> 2); }      // where slab t of a tile sits among its 32 entries
+IA_DEV const int* uniform_ptr(const int* q) {
+  const uint64_t a64 = (uint64_t)q;
+  const uint32_t alo = __builtin_amdgcn_readfirstlane((uint32_t)a64), ahi = __builtin_amdgcn_readfirstlane((uint32_t)(a64 >> 32));
+  return (const int*)(((uint64_t)ahi << 32) | alo);
+}
+// GemmArgs::rows_guarded in slabs: slab t of the ONE M-tile is the t-th live slab from the end of the list, as long as it lies behind the
+// last whole 128-row part of M (at most sixteen do); -1 behind them.
+IA_DEV int guarded_slab(const GemmArgs& p, int t, int n_live) {
+  const int g = n_live - 1 - t;
+  if (t >= 16 || g < 0) return -1;
+  const int v = __builtin_amdgcn_readfirstlane(p.row_blk[ROW_BLK_HDR + (g & ~31) + slab_pos(g & 31)]);
+  return v * 8 >= (p.M & ~127) ? v : -1;
+}
+// the byte offsets of the eight A pieces of wave `wave` (a slab the tile does not have: the tensor's first rows, computed and never stored)
+template <bool GUARDABLE>
+IA_DEV RowOff slab_offsets(const GemmArgs& p, int bm, int wave, int n_live) {
+  typedef int i32x8 __attribute__((ext_vector_type(8)));
+  RowOff ro;
+  if constexpr (GUARDABLE) {
+    if (p.rows_guarded) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { const int v = guarded_slab(p, j * 4 + wave, n_live); ro.o[j] = (uint32_t)(v >= 0 ? v : 0) * (uint32_t)(8 * p.lda * 2); }
+      return ro;
+    }
+  }
+  const int* const addr = uniform_ptr(p.row_blk + ROW_BLK_HDR + bm * SLAB_TILE + wave * 8);
+  i32x8 v;
+  asm volatile("s_nop 4\n\ts_load_dwordx8 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(v) : "s"(addr) : "memory");
+#pragma unroll
+  for (int j = 0; j < 8; ++j) ro.o[j] = (uint32_t)(v[j] >= 0 ? v[j] : 0) * (uint32_t)(8 * p.lda * 2);
+  return ro;
+}
+// the sixteen epilogue rows of a wave of wave-row wm
+template <bool GUARDABLE>
+IA_DEV RowSlab slab_rows(const GemmArgs& p, int bm, int wm, int n_live) {
+  typedef int i32x4 __attribute__((ext_vector_type(4)));
+  RowSlab rs;
+  if constexpr (GUARDABLE) {
+    if (p.rows_guarded) {
+#pragma unroll
+      for (int c = 0; c < 16; ++c) rs.r[c] = guarded_slab(p, (wm * 4 + (c >> 2)) * 4 + (c & 3), n_live) * 8;
+      return rs;
+    }
+  }
+  const int* const addr = uniform_ptr(p.row_blk + ROW_BLK_HDR + bm * SLAB_TILE + wm * 4);
+  i32x4 v0, v1, v2, v3;
+  asm volatile("s_nop 4\n\ts_load_dwordx4 %0, %4, 0x0\n\ts_load_dwordx4 %1, %4, 0x20\n\ts_load_dwordx4 %2, %4, 0x40\n\ts_load_dwordx4 %3, %4, 0x60\n\t"
+               "s_waitcnt lgkmcnt(0)" : "=&s"(v0), "=&s"(v1), "=&s"(v2), "=&s"(v3) : "s"(addr) : "memory");
+#pragma unroll
+  for (int mi = 0; mi < 4; ++mi) { rs.r[mi * 4] = v0[mi] * 8; rs.r[mi * 4 + 1] = v1[mi] * 8; rs.r[mi * 4 + 2] = v2[mi] * 8; rs.r[mi * 4 + 3] = v3[mi] * 8; }
+  return rs;
+}
+
 // Walk over the set bits of a k-slab's live-k-tile mask in increasing order.  Lane l of `mv` holds bits 32l .. 32l+31 of the slab (every
 // wave holds the same 64 words, fetched once in front of the first prologue DMA); the walk itself is SALU plus one v_readlane per step --
 // no memory operation, so it can sit next to the k loop's counted waits, and no branch.  Once the bits are used up next() keeps
@@ -816,7 +882,8 @@ IA_DEV int live_next(LiveWalk& k, uint32_t mv) {
 // LIVE == 2 (EPI_NONE_BLK): over the n_blk set bits of live_mv, which are the slab's live 32-row blocks -- two per trip (n_tiles =
 // ceil(n_blk / 2)); the upper half of the last trip of an odd count goes out of range and arrives as zeros.
 // ROWS (k-contiguous A): piece j of A starts at row offset ro.o[j] (a scalar, where j * stepA sits otherwise) of a window over all of A.
-template <bool AKS, bool BKS, int PEND, bool PEEL_OK = true, int LIVE = 0, bool ROWS = false>
+// SLAB: ro.o[j] is this WAVE's slab of piece j -- the lane offset keeps the row inside the slab (row & 7) and the swizzle of the LDS row.
+template <bool AKS, bool BKS, int PEND, bool PEEL_OK = true, int LIVE = 0, bool ROWS = false, bool SLAB = false>
 IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdgpu_buffer_rsrc_t rsA, __amdgpu_buffer_rsrc_t rsB, int xa, int xb,
                       int kt0, int ktaA0, int ktaB0, int n_tiles, int nk_all, int wm, int wn, int wave, int lane, bool prologue_only,
                       bool stores_in_flight, uint32_t live_mv = 0u, RowOff ro = RowOff{}, int n_blk = 0) {
@@ -830,7 +897,7 @@ IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdg
   // fetches does not depend on the piece (the row advance per piece is a multiple of the swizzle period), so the piece and k-tile
   // advances are both scalars folded into the instruction's soffset.
   uint32_t voffA, stepA, voffB, stepB;
-  if (!AKS) { const int row = gt >> 3; voffA = (uint32_t)(((xa + row) * p.lda + (((gt & 7) ^ ((row >> 1) & 7)) * 8)) * 2); stepA = (uint32_t)(32 * p.lda * 2); }
+  if (!AKS) { const int row = gt >> 3; voffA = (uint32_t)(((xa + (SLAB ? row & 7 : row)) * p.lda + (((gt & 7) ^ ((row >> 1) & 7)) * 8)) * 2); stepA = (uint32_t)(32 * p.lda * 2); }
   else { const int row = gt >> 5; voffA = (uint32_t)((row * p.lda + xa + (((gt & 31) ^ ((row & 3) << 2)) * 8)) * 2); stepA = (uint32_t)(8 * p.lda * 2); }
   if (!BKS) { const int row = gt >> 3; voffB = (uint32_t)(((xb + row) * p.ldb + (((gt & 7) ^ ((row >> 1) & 7)) * 8)) * 2); stepB = (uint32_t)(32 * p.ldb * 2); }
   else { const int row = gt >> 5; voffB = (uint32_t)((row * p.ldb + xb + (((gt & 31) ^ ((row & 3) << 2)) * 8)) * 2); stepB = (uint32_t)(8 * p.ldb * 2); }
@@ -1087,9 +1154,10 @@ IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdg
 // WITH_BIAS (k-contiguous B only): bct[ni][q] = the bias of the lane's columns ni*32 + hh*16 + 4q .. +3 (accumulator layout, fetched
 // before the main loop), added in fp32 before the rounding.
 // ROWS: block mi of the wave's rows starts at row rb.r[mi] (none: its stores leave behind the window), the window covers all of C.
-template <bool BKS, int NH, bool WITH_BIAS, bool ROWS = false>
+// SLAB: pass it of block mi starts at row rs.r[mi * 4 + it].
+template <bool BKS, int NH, bool WITH_BIAS, bool ROWS = false, bool SLAB = false>
 IA_DEV void drain_half_plain(const GemmArgs& p, f32x16 (&acc)[4][4], int m0, int n0, char* stg, int lane_e, const f32x4 (&bct)[4][4], float ts = 1.f,
-                             RowBlk rb = RowBlk{}) {
+                             RowBlk rb = RowBlk{}, RowSlab rs = RowSlab{}) {
   static_assert(!(WITH_BIAS && BKS), "bias rows are laid out for the k-contiguous B fragment permutation");
   const int hh = lane_e >> 5, li = lane_e & 31, rrow = lane_e >> 3, c8 = lane_e & 7;
   auto stage = [&](int mi) {
@@ -1156,7 +1224,8 @@ IA_DEV void drain_half_plain(const GemmArgs& p, f32x16 (&acc)[4][4], int m0, int
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
       uint32_t off = voffC + (uint32_t)((mi * 32 + it * 8) * p.ldc * 2);
-      if constexpr (ROWS) off = rb.r[mi] >= 0 ? voffC + (uint32_t)(rb.r[mi] + it * 8) * (uint32_t)(p.ldc * 2) : 0x80000000u;
+      if constexpr (SLAB) off = rs.r[mi * 4 + it] >= 0 ? voffC + (uint32_t)rs.r[mi * 4 + it] * (uint32_t)(p.ldc * 2) : 0x80000000u;
+      else if constexpr (ROWS) off = rb.r[mi] >= 0 ? voffC + (uint32_t)(rb.r[mi] + it * 8) * (uint32_t)(p.ldc * 2) : 0x80000000u;
       if (!IA_GEMM_DBG_HOOKS || !(p.dbg & 64)) __builtin_amdgcn_raw_buffer_store_b128(v[it], rsC, (int)off, 0, 0);
       else asm volatile("" : : "v"(v[it]));
     }
@@ -1176,9 +1245,10 @@ IA_DEV void drain_half_plain(const GemmArgs& p, f32x16 (&acc)[4][4], int m0, int
 // issued behind a store can only be waited for by draining that store; issued ahead, hipcc's own counters leave the younger stores in
 // flight (vmcnt(2 * AHEAD) in the steady state).
 // ROWS: m0 is the wave's first row in the REMAPPED order (it numbers the column-sum partial); block mi lies at row rb.r[mi] of C and aux.
-template <int EPI, bool OUTF32, bool BKS, int NH, bool ROWS = false>
+// SLAB: slice c (pass it = c & 3 of block mi = c >> 2) lies at row rs.r[c] of C and aux.
+template <int EPI, bool OUTF32, bool BKS, int NH, bool ROWS = false, bool SLAB = false>
 IA_DEV void drain_half(const GemmArgs& p, f32x16 (&acc)[4][4], int m0, int n0, char* stg, int lane_e, bool full, bool bias_ready, f32x4 bias_lo,
-                       f32x4 bias_hi, RowBlk rb = RowBlk{}) {
+                       f32x4 bias_hi, RowBlk rb = RowBlk{}, RowSlab rs = RowSlab{}) {
   const int hh = lane_e >> 5, li = lane_e & 31;
   const int rrow = lane_e >> 3, c8 = lane_e & 7;
   constexpr bool HAS_BIAS = EPI == EPI_BIAS || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_GELU_ACT || EPI == EPI_BIAS_ADD;
@@ -1210,7 +1280,8 @@ IA_DEV void drain_half(const GemmArgs& p, f32x16 (&acc)[4][4], int m0, int n0, c
     }
     auto aux_of = [&](int c) {
       int row_in = (c >> 2) * 32 + ((c >> 1) & 1) * 16 + (c & 1) * 8;
-      if constexpr (ROWS) row_in = rb.r[c >> 2] + (c & 3) * 8;      // (PRE: every block of a full tile exists)
+      if constexpr (SLAB) row_in = rs.r[c];
+      else if constexpr (ROWS) row_in = rb.r[c >> 2] + (c & 3) * 8;      // (PRE: every block of a full tile exists)
       if (BUF) return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rsAux, (int)(voffAux + (uint32_t)(row_in * p.ldaux * 2)), 0, 0));
       return *reinterpret_cast<const bf16x8*>(p.aux + (size_t)(m0 + row_in + rrow) * p.ldaux + n0 + c8 * 8);
     };
@@ -1257,17 +1328,17 @@ IA_DEV void drain_half(const GemmArgs& p, f32x16 (&acc)[4][4], int m0, int n0, c
 #pragma unroll
       for (int it = 0; it < 4; ++it) {
         const int row = it * 8 + rrow;
-        const int m = ROWS ? rb.r[mi] + row : m0 + mi * 32 + row, n = n0 + c8 * 8;
         const int c = mi * 4 + it;
+        const int m = SLAB ? rs.r[c] + rrow : (ROWS ? rb.r[mi] + row : m0 + mi * 32 + row), n = n0 + c8 * 8;
         if (PRE) {
           if (HAS_AUX && c + AHEAD < 16) {
             ax[(c + AHEAD) % (AHEAD + 1)] = aux_of(c + AHEAD);
             asm volatile("" ::: "memory");      // the load stays in front of this slice's store (hipcc would sink it behind)
           }
-          io.off = voffC + (uint32_t)(((ROWS ? rb.r[mi] : mi * 32) + it * 8) * p.ldc * 2);
+          io.off = voffC + (uint32_t)((SLAB ? rs.r[c] : (ROWS ? rb.r[mi] : mi * 32) + it * 8) * p.ldc * 2);
           if (!(IA_DBG(p) & 64)) epi_store8<EPI, OUTF32, true, BUF, ROWS>(p, m, n, lo[it], hi[it], pb0, pb1, ax[c % (AHEAD + 1)], cs, &io);
         } else {
-          if ((!ROWS || rb.r[mi] >= 0) && m < p.M && n < p.N && !(IA_DBG(p) & 64)) epi_store8<EPI, OUTF32, false, false, ROWS>(p, m, n, lo[it], hi[it], pb0, pb1, ax[0], cs);
+          if ((!ROWS || (SLAB ? rs.r[c] : rb.r[mi]) >= 0) && m < p.M && n < p.N && !(IA_DBG(p) & 64)) epi_store8<EPI, OUTF32, false, false, ROWS>(p, m, n, lo[it], hi[it], pb0, pb1, ax[0], cs);
         }
         if (IA_DBG(p) & 64) asm volatile("" : : "v"(lo[it]), "v"(hi[it]));
       }
@@ -1328,8 +1399,10 @@ template <bool AKS, bool BKS, int EPI_, bool OUTF32>
 __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
   constexpr int LIVE = EPI_ == EPI_NONE_LIVE ? 1 : (EPI_ == EPI_NONE_BLK ? 2 : 0);
   constexpr bool ROWS = EPI_ >= EPI_ROWS;
-  constexpr int EPI = LIVE ? (int)EPI_NONE : (ROWS ? EPI_ - EPI_ROWS : EPI_);
+  constexpr bool SLAB = EPI_ >= EPI_ROWS + EPI_SLABS;      // the remap in 8-row slabs (EPI_SLABS)
+  constexpr int EPI = LIVE ? (int)EPI_NONE : (ROWS ? EPI_ - EPI_ROWS - (SLAB ? EPI_SLABS : 0) : EPI_);
   constexpr bool GUARDABLE = ROWS && EPI == EPI_BIAS;      // (tile_blocks)
+  static_assert(!SLAB || EPI == EPI_NONE || EPI == EPI_ADD || (!BKS && (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU)), "slab remap: the plain data gradients and three forward forms");
   static_assert(!LIVE || (AKS && BKS && OUTF32), "live k-tiles: the weight-gradient form only");
   static_assert(!ROWS || (!AKS && !OUTF32 && (EPI == EPI_NONE || EPI == EPI_ADD || EPI == EPI_DGELU_CS ||
                                               (!BKS && (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_GELU_ACT || EPI == EPI_BIAS_ADD)))),
@@ -1343,7 +1416,10 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
   [[maybe_unused]] int n_live = 0;
   if constexpr (ROWS) {
     n_live = __builtin_amdgcn_readfirstlane(p.row_blk[0]);
-    p.tiles_m = (n_live + 7) >> 3;
+    p.tiles_m = SLAB ? (n_live + SLAB_TILE - 1) / SLAB_TILE : (n_live + 7) >> 3;
+    if constexpr (GUARDABLE && SLAB) {
+      if (p.rows_guarded) p.tiles_m = guarded_slab(p, 0, n_live) >= 0 ? 1 : 0;      // (the last live slab lies behind the last whole part, or no tile)
+    } else
     if constexpr (GUARDABLE) {
       // one M-tile, or none when no live block lies behind the last whole 128-row part (the usual case: the end of the last sequence
       // is padding) -- every workgroup returns before its first DMA: tile_blocks would have no block to address
@@ -1403,7 +1479,8 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
     int lane = lane0;
     asm volatile("" : "+v"(lane));      // keep per-lane address arithmetic from being hoisted across the tile loop
     RowOff ro{};
-    if constexpr (ROWS) {      // a block the list does not have: the tile's first block once more (computed, never stored)
+    if constexpr (SLAB) ro = slab_offsets<GUARDABLE>(p, bm, wave, n_live);
+    else if constexpr (ROWS) {      // a block the list does not have: the tile's first block once more (computed, never stored)
       const Blk8 bl = tile_blocks<GUARDABLE>(p, bm, n_live);
 #pragma unroll
       for (int j = 0; j < 8; ++j) ro.o[j] = (uint32_t)(bl.b[j] >= 0 ? bl.b[j] : bl.b[0]) * (uint32_t)(32 * p.lda * 2);
@@ -1411,7 +1488,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
     const uint64_t oa = (uint64_t)(AKS ? kt0 * BK : (ROWS ? 0 : bm * BM)) * p.lda, ob = (uint64_t)(BKS ? kt0 * BK : bn * BN) * p.ldb;
     // (the bf16 bias form keeps 64 bias values in registers across the main loop -- 468 of 512: the peeled first trip spilled there)
     constexpr bool PEEL_OK = !(EPI == EPI_BIAS && !OUTF32 && !BKS);
-    main_loop<AKS, BKS, PEND, PEEL_OK, LIVE, ROWS>(p, smem, acc, rsrc_at(p.A, p.a_bytes, oa), rsrc_at(p.B, p.b_bytes, ob), AKS ? bm * BM : 0, BKS ? bn * BN : 0, kt0,
+    main_loop<AKS, BKS, PEND, PEEL_OK, LIVE, ROWS, SLAB>(p, smem, acc, rsrc_at(p.A, p.a_bytes, oa), rsrc_at(p.B, p.b_bytes, ob), AKS ? bm * BM : 0, BKS ? bn * BN : 0, kt0,
                               AKS ? 0 : kt0, BKS ? 0 : kt0, n_tiles, nk_all, wm, wn, wave, lane, prologue_only, stores_in_flight, live_mv, ro, n_blk);
   };
 
@@ -1574,6 +1651,27 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
     asm volatile("" : "+s"(m0), "+s"(n0));
     char* stg = smem + 2 * 2 * TILE_BYTES + wave * 2 * STAGE_BYTES;      // 8 KiB per wave: two staging slots
     bool full_e = full;
+    if constexpr (SLAB) {
+      // the wave's sixteen slabs, ascending by (block, pass): its part of the tile counts as full (exact store count, unguarded epilogue)
+      // when the last of them exists -- then all do -- and is not the partial last slab of M
+      const RowSlab rs = slab_rows<GUARDABLE>(p, bm, wm, n_live);
+      const bool rows_ok = rs.r[15] >= 0 && rs.r[15] + 8 <= p.M;
+      full_e = rows_ok && n0_pre + 128 <= p.N;
+      if (!(IA_DBG(p) & 32)) {
+        if constexpr (EPI == EPI_NONE) {
+          drain_half_plain<BKS, 0, false, true, true>(p, acc, m0, n0, stg, lane_e, bct, 1.f, RowBlk{}, rs);
+          drain_half_plain<BKS, 1, false, true, true>(p, acc, m0, n0 + 64, stg, lane_e, bct, 1.f, RowBlk{}, rs);
+        } else if (BIAS_CT && bias_pre) {      // (a slab the list does not have, a row past M: the stores fall behind the window)
+          if constexpr (BIAS_CT) {
+            drain_half_plain<false, 0, true, true, true>(p, acc, m0, n0, stg, lane_e, bct, ts, RowBlk{}, rs);
+            drain_half_plain<false, 1, true, true, true>(p, acc, m0, n0 + 64, stg, lane_e, bct, ts, RowBlk{}, rs);
+          }
+        } else {
+          drain_half<EPI, OUTF32, BKS, 0, true, true>(p, acc, m0, n0, stg, lane_e, full_e || (rows_ok && n0 + 64 <= p.N), bias_pre, pbv[0], pbv[1], RowBlk{}, rs);
+          drain_half<EPI, OUTF32, BKS, 1, true, true>(p, acc, m0, n0 + 64, stg, lane_e, full_e, bias_pre, pbv[2], pbv[3], RowBlk{}, rs);
+        }
+      }
+    } else
     if constexpr (ROWS) {
       // the wave's four blocks; a tile counts as full (exact store count, unguarded epilogue) when all eight of its blocks exist and
       // none of them is the partial last block of M
@@ -1649,193 +1747,15 @@ using namespace t256w;
 
 // ROWS (GemmArgs::row_blk, see EPI_ROWS): an M-tile is eight entries of the live-block list.  A's windows cover the whole operand (empty
 // behind the last tile, as before) and every A piece takes its row offset -- the current tile's or the next one's -- as a scalar.
+// SLAB (EPI_SLABS): an M-tile is 32 entries of a slab list, and the row offsets are this wave's own.
 template <bool ROWS>
 __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane0 = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  const int nk_all = (p.K + BK - 1) / BK;             // >= 2 (the host sends shorter K to T256W)
-  [[maybe_unused]] int n_live = 0;
-  if constexpr (ROWS) {
-    n_live = __builtin_amdgcn_readfirstlane(p.row_blk[0]);
-    p.tiles_m = (n_live + 7) >> 3;
-  }
-  const int total_tiles = p.tiles_m * p.tiles_n;
-  const int n_tiles = nk_all;
-  if constexpr (ROWS) {
-    if ((int)blockIdx.x >= total_tiles) return;          // fewer live tiles than workgroups
-  }
-  auto coords = [&](int tile, int& bm, int& bn) { tile_of_index(p, tile, total_tiles, bm, bn); };
-  // a tile's operand windows; a tile index past the end gives empty windows: every piece of it reads zeros
-  auto window_a = [&](int tile) {
-    int bm = 0, bn = 0;
-    if (tile < total_tiles) coords(tile, bm, bn);
-    return tile < total_tiles ? rsrc_at(p.A, p.a_bytes, ROWS ? (uint64_t)0 : (uint64_t)bm * BM * p.lda) : ia_rsrc(p.A, 0u);
-  };
-  // ROWS: the row offsets of a tile's eight A pieces (a block the list does not have: the tile's first block once more, never stored)
-  auto rows_a = [&](int tile) {
-    RowOff ro{};
-    if constexpr (ROWS) {
-      if (tile < total_tiles) {
-        int bm = 0, bn = 0;
-        coords(tile, bm, bn);
-        const Blk8 bl = load_blk8(p.row_blk, bm, n_live);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) ro.o[j] = (uint32_t)(bl.b[j] >= 0 ? bl.b[j] : bl.b[0]) * (uint32_t)(32 * p.lda * 2);
-      }
-    }
-    return ro;
-  };
-  auto window_b = [&](int tile) {
-    int bm = 0, bn = 0;
-    if (tile < total_tiles) coords(tile, bm, bn);
-    return tile < total_tiles ? rsrc_at(p.B, p.b_bytes, (uint64_t)bn * BN * p.ldb) : ia_rsrc(p.B, 0u);
-  };
-
-  int lane = lane0;
-  asm volatile("" : "+v"(lane));
-  const int li = lane & 31;
-  const int gt = wave * 64 + lane;
-  // ---- DMA lane constants (t256w::main_loop): 8 pieces per operand and k-tile, one lane offset per operand
-  const int rowd = gt >> 3;
-  const uint32_t voffA = (uint32_t)((rowd * p.lda + (((gt & 7) ^ ((rowd >> 1) & 7)) * 8)) * 2), stepA = (uint32_t)(32 * p.lda * 2);
-  const uint32_t voffB = (uint32_t)((rowd * p.ldb + (((gt & 7) ^ ((rowd >> 1) & 7)) * 8)) * 2), stepB = (uint32_t)(32 * p.ldb * 2);
-  const int kl = ((gt & 7) ^ (((gt >> 3) >> 1) & 7)) * 8;          // the k index of this lane's 16 bytes inside a k-tile
-  char* const my_part = smem + wave * 1024;
-  // ---- fragment addresses
-  const int nperm = ((li >> 2) & 1) * 16 + (li >> 3) * 4 + (li & 3);
-  uint32_t baseA[4], baseB[4];
-  const uint32_t smem_addr = ia_lds_addr(smem);
-  frag_bases<false>(baseA, smem_addr, wm * 128, lane, li);
-  frag_bases<false>(baseB, smem_addr + TILE_BYTES, wn * 128, lane, nperm);
-
-  int tile = blockIdx.x;
-  __amdgpu_buffer_rsrc_t rsA = window_a(tile), rsB = window_b(tile);
-  __amdgpu_buffer_rsrc_t rsAn = window_a(tile + (int)gridDim.x), rsBn = window_b(tile + (int)gridDim.x);
-  [[maybe_unused]] RowOff roA = rows_a(tile), roAn = rows_a(tile + (int)gridDim.x);
-
-  // k-tile v of the CURRENT tile (v >= n_tiles: k-tile v - n_tiles of the NEXT tile) -> lane offset of its pieces, or out of range
-  auto off_of = [&](int v) -> uint32_t {
-    const int kt = v >= n_tiles ? v - n_tiles : v;
-    return kl < p.K - kt * BK ? 1u : 0u;                 // (1 = in range; the operand's own lane offset is selected by the caller)
-  };
-  // piece i (0..7: A, 8..15: B) of k-tile v into the buffer at byte offset `buf`
-  auto dma = [&](int v, int i, uint32_t ok, uint32_t buf) {
-    const bool isB = i >= 8, nx = v >= n_tiles;
-    const int j = i & 7, kt = nx ? v - n_tiles : v;
-    char* dst = my_part + (isB ? TILE_BYTES : 0) + buf + j * 4096;
-    const uint32_t soff = (uint32_t)kt * (uint32_t)(BK * 2) + ((ROWS && !isB) ? (nx ? roAn.o[j] : roA.o[j]) : (uint32_t)j * (isB ? stepB : stepA));
-    const uint32_t off = ok ? (isB ? voffB : voffA) : OOB;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(isB ? (nx ? rsBn : rsB) : (nx ? rsAn : rsA), IA_LDS(dst), 16, off, (int)soff, 0, 0);
-  };
-
-  // ---- the first tile's prologue: k-tiles 0 and 1 whole, landed (once per launch), first set.  Every tile's first trip then finds the
-  // same state: k-tile 1 requested in full BEFORE anything else that is in flight (below).
-#pragma unroll
-  for (int i = 0; i < 16; ++i) dma(0, i, off_of(0), 0u);
-#pragma unroll
-  for (int i = 0; i < 16; ++i) dma(1, i, off_of(1), (uint32_t)(2 * TILE_BYTES));
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  Op<false> a0, a1, a2, a3, b0, b1, b2, b3;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) read_frag<0>(a0, j, baseA, 0u);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) read_frag<0>(b0, j, baseB, 0u);
-  uint32_t bo = 0;                                       // LDS byte offset of the buffer that holds the coming trip's k-tile
-
-  f32x16 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  using Acc = std::false_type;
-
-  const f32x4 no_bias[4][4] = {};
-  while (true) {
-    int bm, bn;
-    coords(tile, bm, bn);
-    const int m0_pre = bm * BM + wm * 128, n0_pre = bn * BN + wn * 128;
-    int u = 0;
-    uint32_t okA = 0u, okB = off_of(1);
-    // one trip = one k-tile (t256w::main_loop, ROUND schedule, with the look-ahead reaching into the next tile)
-    // A tile's FIRST trip: the last four pieces of its k-tile 1 went out in front of the previous tile's drain (or in the launch
-    // prologue), so the counted wait of this trip -- "k-tile 1 has landed" -- can leave the drain's 32 output stores in flight with the 8
-    // pieces it has just issued: vmcnt(40).  VMEM retires in order: with those four pieces issued BEHIND the stores (T256W's order) the
-    // wait was for the stores' completion, i.e. for the whole drain of 128 KiB at the ~18 B per clock a CU's stores sustain.
-    auto trip = [&](auto FIRST_T) {
-      constexpr bool FIRST = decltype(FIRST_T)::value;
-      const uint32_t bn_ = bo ^ (uint32_t)(2 * TILE_BYTES);
-      tie2<0>(a0, b0);
-      mfma_step<FIRST>(acc, a0, b0, [&](int i) {
-        if (i < 4) { read_frag<1>(a1, i, baseA, bo); read_frag<1>(b1, i, baseB, bo); }
-        else if (i < 8) { read_frag<2>(a2, i - 4, baseA, bo); read_frag<2>(b2, i - 4, baseB, bo); }
-        else if (i < 12) { read_frag<3>(a3, i - 8, baseA, bo); read_frag<3>(b3, i - 8, baseB, bo); }
-        if (!FIRST && i % 4 == 3) dma(u + 1, 12 + i / 4, okB, bn_);       // the last four pieces of k-tile u+1 (into the other buffer)
-        if (i == 12) okA = off_of(u + 2);
-      });
-      tie6<0>(a1, b1, a2, b2, a3, b3);
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-      mfma_step<false>(acc, a1, b1, [&](int i) {
-        if (i % 4 == 1) dma(u + 2, i / 4, okA, bo);
-      });
-      mfma_step<false>(acc, a2, b2, [&](int i) {
-        if (i % 4 == 1) dma(u + 2, 4 + i / 4, okA, bo);
-        if (i == 14) okB = off_of(u + 2);
-      });
-      if constexpr (FIRST) asm volatile("s_waitcnt vmcnt(40)" ::: "memory");      // 8 pieces + the previous tile's 32 stores
-      else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-      mfma_step<false>(acc, a3, b3, [&](int i) {
-        if (i < 4) read_frag<0>(a0, i, baseA, bn_);
-        else if (i < 8) read_frag<0>(b0, i - 4, baseB, bn_);
-        if (i % 4 == 3) dma(u + 2, 8 + i / 4, okB, bo);
-      });
-      bo = bn_;
-      ++u;
-    };
-    trip(std::true_type{});
-    do { trip(Acc{}); } while (u < n_tiles);
-    // the next tile's k-tile 1: its last four pieces in front of the drain's stores (see trip)
-    {
-      const uint32_t ok1 = off_of(n_tiles + 1), b1_ = bo ^ (uint32_t)(2 * TILE_BYTES);
-#pragma unroll
-      for (int i = 12; i < 16; ++i) dma(n_tiles + 1, i, ok1, b1_);
-    }
-
-    // ---- drain (t256w's plain epilogue); the pipeline stays loaded: a0 / b0 requested, k-tile 1 of the next tile in flight
-    int lane_e = lane0;
-    asm volatile("" : "+v"(lane_e));
-    int m0 = m0_pre, n0 = n0_pre;
-    asm volatile("" : "+s"(m0), "+s"(n0));
-    char* stg = smem + 2 * 2 * TILE_BYTES + wave * 2 * STAGE_BYTES;
-    if constexpr (ROWS) {
-      const Blk8 bl = load_blk8(p.row_blk, bm, n_live);
-      RowBlk rb;
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi) rb.r[mi] = (wm ? bl.b[4 + mi] : bl.b[mi]) * 32;      // (-1 -> negative: none)
-      drain_half_plain<false, 0, false, true>(p, acc, m0, n0, stg, lane_e, no_bias, 1.f, rb);
-      drain_half_plain<false, 1, false, true>(p, acc, m0, n0 + 64, stg, lane_e, no_bias, 1.f, rb);
-    } else {
-    drain_half_plain<false, 0, false>(p, acc, m0, n0, stg, lane_e, no_bias);
-    drain_half_plain<false, 1, false>(p, acc, m0, n0 + 64, stg, lane_e, no_bias);
-    }
-    tile += (int)gridDim.x;
-    if (tile >= total_tiles) break;
-    rsA = rsAn; rsB = rsBn;
-    rsAn = window_a(tile + (int)gridDim.x); rsBn = window_b(tile + (int)gridDim.x);
-    if constexpr (ROWS) { roA = roAn; roAn = rows_a(tile + (int)gridDim.x); }
-  }
-  tie2<0>(a0, b0);                                        // dead, but in flight
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // the look-ahead pieces of the tile that does not exist target this workgroup's LDS
+  constexpr bool SLAB = false;
+#include "gemm_t256la_body.inc"
+}
+__global__ __launch_bounds__(256) void gemm_slab_kernel(GemmArgs p) {
+  constexpr bool ROWS = true, SLAB = true;
+#include "gemm_t256la_body.inc"
 }
 }  // namespace t256la
 
@@ -2011,8 +1931,24 @@ __global__ __launch_bounds__(256) void zero_dead_rows_kernel(const int* __restri
   }
 }
 
+// EPI_SLABS launches: the same for a slab list (ia_row_slabs) -- the rows of its dead 8-row slabs written as zeros, dealt out over the grid
+// (a workgroup takes four slabs at a time: the 32 rows the block form's fill takes).
+__global__ __launch_bounds__(256) void zero_dead_slabs_kernel(const int* __restrict__ list, bf16* __restrict__ C, int ldc, int M, int N) {
+  const int n_dead = list[1], nsr = (list[2] + t256w::SLAB_TILE - 1) & ~(t256w::SLAB_TILE - 1);
+  const int* dead = list + t256w::ROW_BLK_HDR + nsr;
+  const int n8 = N >> 3;
+  const u32x4 z = {0u, 0u, 0u, 0u};
+  for (int d0 = blockIdx.x * 4; d0 < n_dead; d0 += gridDim.x * 4) {
+    const int nd = n_dead - d0 < 4 ? n_dead - d0 : 4;
+    for (int i = threadIdx.x; i < nd * 8 * n8; i += 256) {
+      const int rr = i / n8, r = dead[d0 + (rr >> 3)] * 8 + (rr & 7), c = (i % n8) * 8;
+      if (r < M) *reinterpret_cast<u32x4*>(C + (size_t)r * ldc + c) = z;
+    }
+  }
+}
+
 template <bool AKS, bool BKS, int EPI, bool OUTF32>
-int launch(GemmArgs a, bool big, hipStream_t st, bool live_blocks = false) {      // live_blocks: a.live_kt is a mask of 32-row blocks (ia_kblock_mask)
+int launch(GemmArgs a, bool big, hipStream_t st, bool live_blocks = false, bool slabs = false) {      // live_blocks: a.live_kt is a mask of 32-row blocks (ia_kblock_mask); slabs: a.row_blk is a slab list (ia_row_slabs)
   constexpr int vid = AKS * 1000 + BKS * 100 + EPI * 10 + (OUTF32 ? 1 : 0);
   // the forms that may carry a block list (GemmArgs::row_blk): the data gradients, and the forward epilogues on k-contiguous operands
   constexpr bool DROWS = !AKS && !OUTF32 && (EPI == EPI_NONE || EPI == EPI_ADD || EPI == EPI_DGELU_CS ||
@@ -2032,7 +1968,7 @@ int launch(GemmArgs a, bool big, hipStream_t st, bool live_blocks = false) {    
     // persistent launches with more than one tile per workgroup claim their tiles dynamically (IA_GEMM_DYNAMIC=0: the static order)
     a.tile_ctr = (a.splits == 1 && ntile > gx) ? next_ctr_slot() : nullptr;
     void (*kern)(GemmArgs) = t256w::gemm_kernel<AKS, BKS, EPI, OUTF32>;
-    static bool attr_set[6] = {false, false, false, false, false, false};      // per kernel: [0] this instantiation of t256w, [1] t256la, [2] the live-k-tile weight gradient, [3] / [4] the row remap of [0] / [1], [5] the live-block weight gradient
+    static bool attr_set[8] = {false, false, false, false, false, false, false, false};      // per kernel: [0] this instantiation of t256w, [1] t256la, [2] the live-k-tile weight gradient, [3] / [4] the row remap of [0] / [1], [5] the live-block weight gradient, [6] / [7] the slab remap of [0] / [1]
     int la = 0;
     if constexpr (WGRAD) {
       if (a.live_kt && live_blocks) { kern = t256w::gemm_kernel<true, true, EPI_NONE_BLK, true>; la = 5; }
@@ -2045,6 +1981,16 @@ int launch(GemmArgs a, bool big, hipStream_t st, bool live_blocks = false) {    
     }
     // over the live 32-row blocks: the remapped form of the kernel chosen above, dead rows zeroed first where the caller asks for it
     if constexpr (DROWS) {
+      constexpr bool DSLABS = EPI == EPI_NONE || EPI == EPI_ADD || (!BKS && (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU));
+      if (a.row_blk && slabs) {
+        if constexpr (DSLABS) {
+          if (la == 1) kern = t256la::gemm_slab_kernel;
+          else kern = t256w::gemm_kernel<false, BKS, EPI_ROWS + EPI_SLABS + EPI, false>;
+          la = la == 1 ? 7 : 6;
+          if (a.rows_fill) hipLaunchKernelGGL(zero_dead_slabs_kernel, dim3(1024), dim3(256), 0, st, a.row_blk, (bf16*)a.C, a.ldc, a.fill_m, a.N);
+          if (a.rows_fill && EPI == EPI_BIAS_GELU) hipLaunchKernelGGL(zero_dead_slabs_kernel, dim3(1024), dim3(256), 0, st, a.row_blk, a.C2, a.ldc, a.fill_m, a.N);
+        } else return IA_ERR_UNSUPPORTED;
+      } else
       if (a.row_blk) {
         if (la == 1) kern = t256la::gemm_kernel<true>;      // (the look-ahead kernel's remapped form where the dense call takes that kernel)
         else kern = t256w::gemm_kernel<false, BKS, EPI_ROWS + EPI, false>;
@@ -2098,7 +2044,7 @@ static int gemm_core(const void* A, int a_kstrided, int lda, const void* B, int 
                      int N, int K, int epilogue, const float* bias, const void* aux, int ldaux, void* C2, int accumulate, void* workspace,
                      size_t workspace_bytes, const IaViewGemm* view, hipStream_t stream, int qcols = 0, float qscale = 1.f,
                      const uint32_t* live_kt = nullptr, const int* row_blocks = nullptr, int rows_fill = 1, int tail_of = 0,      // tail_of: below
-                     int rows_grouped = 0, int live_blocks = 0);
+                     int rows_grouped = 0, int live_blocks = 0, int row_slabs = 0);      // row_slabs: row_blocks is a slab list (ia_row_slabs)
 
 // workspace of an IA_EPI_DGELU_COLSUM GEMM: one fp32 row of N partial sums per 128-row block of the output (and never less than
 // the stand-alone column-sum kernel needs, which small shapes fall back to)
@@ -2213,6 +2159,75 @@ extern "C" int ia_row_groups(const uint8_t* row_live, int M_rows, int* list, hip
   return ia_check_launch();
 }
 extern "C" int ia_row_groups_host(const uint8_t* row_live, int M_rows, int* list) { return row_blocks_host(row_live, M_rows, list, 2); }
+// ---- The slab list (EPI_SLABS): slab t = rows 8t .. 8t+7 (clipped to M), live = any row_live set.  Header: [0] live slabs, [1] dead slabs,
+// [2] slabs.  The live slabs follow, ascending, 32 to an M-tile and inside a tile in the order [wave][piece] (the i-th live slab sits at
+// slab_slot(i)); the entries behind the last one of the last tile are -1.  The dead slabs, ascending, start behind room for every slab
+// rounded up to whole tiles.
+static __host__ __device__ inline int slab_slot(int i) { return (i & ~31) + (i & 3) * 8 + ((i & 31) >> 2); }
+static __host__ __device__ inline bool row_slab_live(const uint8_t* row_live, int M, int t) {
+  const uint8_t* r = row_live + (size_t)t * 8;
+  const int n = M - t * 8 < 8 ? M - t * 8 : 8;
+  if (n == 8 && ((uintptr_t)r & 7) == 0) return *reinterpret_cast<const uint64_t*>(r) != 0;
+  uint8_t any = 0;
+  for (int i = 0; i < n; ++i) any |= r[i];
+  return any != 0;
+}
+namespace {
+// One wave, no LDS (row_blocks_kernel): lane l looks at slabs 64i + l.
+__global__ __launch_bounds__(64) void row_slabs_kernel(const uint8_t* __restrict__ row_live, int M, int ns, int* __restrict__ out) {
+  const int nsr = (ns + 31) & ~31;
+  int* const live = out + t256w::ROW_BLK_HDR;
+  int* const dead = live + nsr;
+  const int lane = threadIdx.x;
+  int base = 0;
+  for (int c0 = 0; c0 < ns; c0 += 64 * 64) {
+    uint64_t flags = 0;
+#pragma unroll 8
+    for (int i = 0; i < 64; ++i) {
+      const int t = c0 + i * 64 + lane;
+      if (t < ns && row_slab_live(row_live, M, t)) flags |= 1ull << i;
+    }
+    for (int i = 0; i < 64 && c0 + i * 64 < ns; ++i) {
+      const int t = c0 + i * 64 + lane;
+      const bool lv = (flags >> i) & 1ull;
+      const uint64_t b = __ballot(lv);
+      const int at = base + __popcll(b & ((1ull << lane) - 1ull));
+      if (t < ns) { if (lv) live[slab_slot(at)] = t; else dead[t - at] = t; }
+      base += __popcll(b);
+    }
+  }
+  if (base + lane < ((base + 31) & ~31)) live[slab_slot(base + lane)] = -1;      // (at most 31 entries: the tail of the last tile)
+  if (lane < t256w::ROW_BLK_HDR) out[lane] = lane == 0 ? base : (lane == 1 ? ns - base : (lane == 2 ? ns : 0));
+}
+}  // namespace
+extern "C" size_t ia_row_slabs_bytes(int M_rows) {
+  if (M_rows <= 0) return 0;
+  const size_t nsr = (size_t)(((M_rows + 7) / 8 + 31) & ~31);
+  return (t256w::ROW_BLK_HDR + 2 * nsr) * sizeof(int);
+}
+// where the slab list sits behind an ia_row_blocks list (and the packed list behind that) in ONE buffer (ia_layer_cfg::masked_rows_dead
+// bit 6, value 32): byte offset from its start
+extern "C" size_t ia_row_slabs_offset(int M_rows) { return 2 * al256(ia_row_blocks_bytes(M_rows)); }      // (behind the block list and the packed list, which has the block list's size)
+extern "C" int ia_row_slabs(const uint8_t* row_live, int M_rows, int* list, hipStream_t stream) {
+  (void)hipGetLastError();
+  if (!row_live || !list || M_rows <= 0 || ((uintptr_t)list & 31)) return IA_ERR_ARG;
+  hipLaunchKernelGGL(row_slabs_kernel, dim3(1), dim3(64), 0, stream, row_live, M_rows, (M_rows + 7) / 8, list);
+  return ia_check_launch();
+}
+extern "C" int ia_row_slabs_host(const uint8_t* row_live, int M_rows, int* list) {
+  if (!row_live || !list || M_rows <= 0) return IA_ERR_ARG;
+  const int ns = (M_rows + 7) / 8, nsr = (ns + 31) & ~31;
+  int* const live = list + t256w::ROW_BLK_HDR;
+  int* const dead = live + nsr;
+  int n_live = 0;
+  for (int t = 0; t < ns; ++t) {
+    if (row_slab_live(row_live, M_rows, t)) live[slab_slot(n_live++)] = t; else dead[t - n_live] = t;
+  }
+  for (int i = n_live; i < ((n_live + 31) & ~31); ++i) live[slab_slot(i)] = -1;
+  for (int i = 0; i < t256w::ROW_BLK_HDR; ++i) list[i] = 0;
+  list[0] = n_live; list[1] = ns - n_live; list[2] = ns;
+  return IA_OK;
+}
 // ---- The block-packed list (GemmArgs::rows_grouped == 2): the layout of ia_row_blocks -- header, slots, dead blocks -- with four slots per
 // wave-row of the remapped kernel (eight per M-tile).  A wave-row holds the live 32-row blocks of one or more WHOLE 128-row groups: a group's
 // blocks are contiguous and ascending, no group spans two wave-rows, the slots behind the last group are -1.  Header: [0] slots in use
@@ -2450,6 +2465,43 @@ extern "C" int ia_gemm_dgrad_rows(const void* dY, int ldy, const void* W, int w_
                                         cs_bytes, stream);
 }
 
+// ---- the same over the live 8-row slabs (EPI_SLABS)
+// library-internal (common.h): with a slab list already built (the layer calls: one list per step or call, seven GEMMs)
+int ia_gemm_fwd_slab_list(const void* X, int ldx, const void* W, int ldw, void* Y, int ldy, int M_rows, int N_out, int K_in, int epilogue,
+                          const float* bias, void* C2, int scaled_cols, float col_scale, const int* row_slabs, int fill_dead_rows, hipStream_t stream) {
+  if (epilogue != EPI_NONE && epilogue != EPI_BIAS && epilogue != EPI_BIAS_GELU) return IA_ERR_UNSUPPORTED;
+  return gemm_core(X, 0, ldx, W, 0, ldw, Y, 0, ldy, M_rows, N_out, K_in, epilogue, bias, nullptr, 0, C2, 0, nullptr, 0, nullptr, stream, scaled_cols,
+                   col_scale, nullptr, row_slabs, fill_dead_rows, 0, 0, 0, 1);
+}
+int ia_gemm_dgrad_slab_list(const void* dY, int ldy, const void* W, int w_kstrided, int ldw, void* dX, int ldx, int M_rows, int N_in, int K_out,
+                            int epilogue, const void* aux, int ldaux, const int* row_slabs, hipStream_t stream) {
+  if (epilogue != EPI_NONE && epilogue != EPI_ADD) return IA_ERR_UNSUPPORTED;
+  return gemm_core(dY, 0, ldy, W, w_kstrided, ldw, dX, 0, ldx, M_rows, N_in, K_out, epilogue, nullptr, aux, ldaux, nullptr, 0, nullptr, 0, nullptr, stream,
+                   0, 1.f, nullptr, row_slabs, 1, 0, 0, 0, 1);
+}
+extern "C" size_t ia_gemm_slabs_workspace_bytes(int M_rows) { return ia_row_slabs_bytes(M_rows); }
+extern "C" int ia_gemm_fwd_slabs(const void* X, int ldx, const void* W, int ldw, void* Y, int ldy, int M_rows, int N_out, int K_in, int epilogue,
+                                 const float* bias, void* C2, int scaled_cols, float col_scale, const uint8_t* row_live, int fill_dead_rows,
+                                 void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  if (epilogue != EPI_NONE && epilogue != EPI_BIAS && epilogue != EPI_BIAS_GELU) return IA_ERR_UNSUPPORTED;
+  if (!row_live) return ia_gemm_fwd_slab_list(X, ldx, W, ldw, Y, ldy, M_rows, N_out, K_in, epilogue, bias, C2, scaled_cols, col_scale, nullptr, 0, stream);
+  if (M_rows <= 0 || N_out <= 0 || K_in <= 0) return IA_ERR_ARG;
+  if (!workspace || workspace_bytes < ia_row_slabs_bytes(M_rows) || ((uintptr_t)workspace & 31)) return IA_ERR_WORKSPACE;
+  int rc = ia_row_slabs(row_live, M_rows, (int*)workspace, stream);
+  return rc ? rc : ia_gemm_fwd_slab_list(X, ldx, W, ldw, Y, ldy, M_rows, N_out, K_in, epilogue, bias, C2, scaled_cols, col_scale, (const int*)workspace,
+                                         fill_dead_rows, stream);
+}
+extern "C" int ia_gemm_dgrad_slabs(const void* dY, int ldy, const void* W, int w_kstrided, int ldw, void* dX, int ldx, int M_rows, int N_in,
+                                   int K_out, int epilogue, const void* aux, int ldaux, const uint8_t* row_live, void* workspace,
+                                   size_t workspace_bytes, hipStream_t stream) {
+  if (epilogue != EPI_NONE && epilogue != EPI_ADD) return IA_ERR_UNSUPPORTED;
+  if (!row_live) return ia_gemm_dgrad_slab_list(dY, ldy, W, w_kstrided, ldw, dX, ldx, M_rows, N_in, K_out, epilogue, aux, ldaux, nullptr, stream);
+  if (M_rows <= 0 || N_in <= 0 || K_out <= 0) return IA_ERR_ARG;
+  if (!workspace || workspace_bytes < ia_row_slabs_bytes(M_rows) || ((uintptr_t)workspace & 31)) return IA_ERR_WORKSPACE;
+  int rc = ia_row_slabs(row_live, M_rows, (int*)workspace, stream);
+  return rc ? rc : ia_gemm_dgrad_slab_list(dY, ldy, W, w_kstrided, ldw, dX, ldx, M_rows, N_in, K_out, epilogue, aux, ldaux, (const int*)workspace, stream);
+}
+
 // ---- weight gradient over the live rows only
 // bit t of the mask = OR of row_live over rows 64t .. 64t+63 (clipped to M).  One function for the device kernel and the host entry.
 static __host__ __device__ inline uint32_t ktile_live(const uint8_t* row_live, int M, int t) {
@@ -2599,7 +2651,7 @@ static int launch_dgelu_colsum(GemmArgs& g, bool big, float* csum, void* workspa
 static int gemm_core(const void* A, int a_kstrided, int lda, const void* B, int b_kstrided, int ldb, void* C, int c_is_f32, int ldc, int M,
                      int N, int K, int epilogue, const float* bias, const void* aux, int ldaux, void* C2, int accumulate, void* workspace,
                      size_t workspace_bytes, const IaViewGemm* view, hipStream_t stream, int qcols, float qscale, const uint32_t* live_kt,
-                     const int* row_blocks, int rows_fill, int tail_of, int rows_grouped, int live_blocks) {
+                     const int* row_blocks, int rows_fill, int tail_of, int rows_grouped, int live_blocks, int row_slabs) {
   const uint64_t a_window = view ? view->a_window : 0, b_window = view ? view->b_window : 0;
   const int groups = view ? view->groups : 1;
   (void)hipGetLastError();  // drop stale status left by unrelated runtime calls (e.g. hipEventQuery -> NotReady)
@@ -2663,6 +2715,8 @@ static int gemm_core(const void* A, int a_kstrided, int lda, const void* B, int 
   if (!a_kstrided && !c_is_f32 && (epilogue == EPI_NONE || epilogue == EPI_ADD || epilogue == EPI_DGELU_CS || fwd_epi))
     g.row_blk = (row_blocks && big && !g.dbg && !(N & 7) && dgrad_rows_fit(M, lda, ldc, aux ? ldaux : 0)) ? row_blocks : nullptr;
   g.rows_grouped = (g.row_blk && epilogue == EPI_DGELU_CS && rows_grouped) ? rows_grouped : 0;
+  const bool slabs = g.row_blk && row_slabs;
+  if (slabs && epilogue != EPI_NONE && epilogue != EPI_ADD && epilogue != EPI_BIAS && epilogue != EPI_BIAS_GELU) return IA_ERR_UNSUPPORTED;
   // Scaled columns, M no multiple of 128: the dense kernel rounds the rows behind the last whole 128-row part of M as (acc + bias) * scale
   // (guarded row-layout epilogue) and the others as acc * scale + bias * scale (accumulator-layout epilogue).  The remap would mix the two
   // in one wave, so the remapped launch covers the whole parts and the (at most four) blocks behind them get a remapped launch of their
@@ -2671,7 +2725,7 @@ static int gemm_core(const void* A, int a_kstrided, int lda, const void* B, int 
   if (g.row_blk && fwd_epi && qcols > 0 && (M & 127) && !tail_of) {
     const int Mb = M & ~127;
     int rc = gemm_core(A, 0, lda, B, 0, ldb, C, 0, ldc, M, N, K, epilogue, bias, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, stream, qcols, qscale, nullptr,
-                       row_blocks, 0, 1);
+                       row_blocks, 0, 1, 0, 0, row_slabs);
     if (rc) return rc;
     g.a_bytes = ((uint64_t)(Mb - 1) * lda + K) * 2;
     g.M = Mb;
@@ -2684,20 +2738,20 @@ static int gemm_core(const void* A, int a_kstrided, int lda, const void* B, int 
 
   if (!a_kstrided && !b_kstrided && !c_is_f32) {
     switch (epilogue) {
-      case EPI_NONE: return launch<false, false, EPI_NONE, false>(g, big, stream);
-      case EPI_BIAS: return launch<false, false, EPI_BIAS, false>(g, big, stream);
-      case EPI_BIAS_GELU: return launch<false, false, EPI_BIAS_GELU, false>(g, big, stream);
+      case EPI_NONE: return launch<false, false, EPI_NONE, false>(g, big, stream, false, slabs);
+      case EPI_BIAS: return launch<false, false, EPI_BIAS, false>(g, big, stream, false, slabs);
+      case EPI_BIAS_GELU: return launch<false, false, EPI_BIAS_GELU, false>(g, big, stream, false, slabs);
       case EPI_BIAS_GELU_ACT: return launch<false, false, EPI_BIAS_GELU_ACT, false>(g, big, stream);
       case EPI_BIAS_ADD: return launch<false, false, EPI_BIAS_ADD, false>(g, big, stream);
-      case EPI_ADD: return launch<false, false, EPI_ADD, false>(g, big, stream);
+      case EPI_ADD: return launch<false, false, EPI_ADD, false>(g, big, stream, false, slabs);
       // (the data-gradient epilogues on a k-contiguous B: the transposed weight shadows of ia_layer_weights::wt_*)
       case EPI_DGELU: return launch<false, false, EPI_DGELU, false>(g, big, stream);
       case EPI_DGELU_CS: return launch_dgelu_colsum<false>(g, big, (float*)C2, workspace, workspace_bytes, stream);
     }
   } else if (!a_kstrided && b_kstrided && !c_is_f32) {
     switch (epilogue) {
-      case EPI_NONE: return launch<false, true, EPI_NONE, false>(g, big, stream);
-      case EPI_ADD: return launch<false, true, EPI_ADD, false>(g, big, stream);
+      case EPI_NONE: return launch<false, true, EPI_NONE, false>(g, big, stream, false, slabs);
+      case EPI_ADD: return launch<false, true, EPI_ADD, false>(g, big, stream, false, slabs);
       case EPI_DGELU: return launch<false, true, EPI_DGELU, false>(g, big, stream);
       case EPI_DGELU_CS: return launch_dgelu_colsum<true>(g, big, (float*)C2, workspace, workspace_bytes, stream);
     }

@@ -198,14 +198,18 @@ class EncoderStackFn(torch.autograd.Function):
             M = cur.shape[0]
             lb = lib.ia_row_groups_packed_offset(M)        # (= the block list's size rounded up to 256 bytes)
             packed = keep and M <= 128 * 4096              # the backward's x gelu' data gradient: the live blocks packed by whole groups
-            lists = torch.empty(2 * lb + lib.ia_kblock_mask_bytes(M), device=x.device, dtype=torch.uint8)
+            so = lib.ia_row_slabs_offset(M)                # (= 2 lb: the 8-row slab list behind the two block lists)
+            ko = so + (lib.ia_row_slabs_bytes(M) + 255) // 256 * 256
+            lists = torch.empty(ko + lib.ia_kblock_mask_bytes(M), device=x.device, dtype=torch.uint8)
             check(lib.ia_row_blocks(mp, M, lists.data_ptr(), stream_ptr()), "ia_row_blocks")
+            check(lib.ia_row_slabs(mp, M, lists.data_ptr() + so, stream_ptr()), "ia_row_slabs")
             if packed:
                 check(lib.ia_row_groups_packed(mp, M, lists.data_ptr() + lb, stream_ptr()), "ia_row_groups_packed")
             if keep:                                       # (the weight gradients' mask: nothing reads it without a backward)
-                check(lib.ia_kblock_mask(mp, M, lists.data_ptr() + 2 * lb, stream_ptr()), "ia_kblock_mask")
+                check(lib.ia_kblock_mask(mp, M, lists.data_ptr() + ko, stream_ptr()), "ia_kblock_mask")
             for c in cfgs:
-                c.row_blocks, c.live_ktiles = lists.data_ptr(), (lists.data_ptr() + 2 * lb) if keep else None
+                c.row_blocks, c.live_ktiles = lists.data_ptr(), (lists.data_ptr() + ko) if keep else None
+                c.masked_rows_dead |= 32                   # ia_layer_cfg: the slab list sits behind row_blocks at ia_row_slabs_offset
                 if keep:
                     c.masked_rows_dead |= 8                # ia_layer_cfg: live_ktiles is a 32-row block mask
                 if packed:

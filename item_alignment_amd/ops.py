@@ -176,6 +176,62 @@ def gemm_fwd_rows(x, w, row_live=None, *, epilogue=EPI_NONE, bias=None, scaled_c
     return out
 
 
+def row_slabs(row_live):
+    """The 8-row slab list of ia_row_slabs (uint8 [M] on the GPU -> int32 words): [0] live count, [1] dead count, [2] slabs; from word 8
+    the live slabs, 32 to a tile in the order [wave][piece] (-1 behind the last); the ascending dead slabs from word 8 + slabs rounded
+    up to 32."""
+    lib = _lib.load()
+    _need(row_live, torch.uint8, "row_live")
+    M = row_live.numel()
+    out = torch.empty(lib.ia_row_slabs_bytes(M) // 4, device=row_live.device, dtype=torch.int32)
+    check(lib.ia_row_slabs(row_live.data_ptr(), M, out.data_ptr(), stream_ptr()), "ia_row_slabs")
+    return out
+
+
+def gemm_dgrad_slabs(dy, w, row_live=None, *, w_kstrided=True, epilogue=EPI_NONE, aux=None, out=None):
+    """gemm_dgrad_rows (EPI_NONE / EPI_ADD) over the 8-row slabs that hold a live row (ia_gemm_dgrad_slabs); the other slabs' rows are
+    written as zeros."""
+    lib = _lib.load()
+    _need(dy, BF16, "dy"); _need(w, BF16, "w"); _need(aux, BF16, "aux"); _need(row_live, torch.uint8, "row_live")
+    M, K = dy.shape
+    Kw, N = w.shape if w_kstrided else w.shape[::-1]
+    if K != Kw or (row_live is not None and row_live.numel() != M):
+        raise ValueError("gemm_dgrad_slabs: dy, w and row_live do not fit together")
+    if out is None:
+        out = torch.empty((M, N), device=dy.device, dtype=BF16)
+    _need(out, BF16, "out")
+    ws_bytes = lib.ia_gemm_slabs_workspace_bytes(M)
+    ws = torch.empty(ws_bytes, device=dy.device, dtype=torch.uint8)
+    check(lib.ia_gemm_dgrad_slabs(dy.data_ptr(), K, w.data_ptr(), int(w_kstrided), w.shape[1], out.data_ptr(), N, M, N, K, epilogue,
+                                  ptr(aux), N if aux is not None else 0, ptr(row_live), ws.data_ptr(), ws_bytes, stream_ptr()),
+          "ia_gemm_dgrad_slabs")
+    return out
+
+
+def gemm_fwd_slabs(x, w, row_live=None, *, epilogue=EPI_NONE, bias=None, scaled_cols=0, col_scale=1.0, fill=True, out=None, pre_out=None):
+    """gemm_fwd_rows (EPI_NONE / EPI_BIAS with scaled_cols, col_scale / EPI_BIAS_GELU) over the 8-row slabs that hold a live row
+    (ia_gemm_fwd_slabs).  fill: the other slabs' rows are written as zeros, else not written.  EPI_BIAS_GELU returns (out, pre_out)."""
+    lib = _lib.load()
+    _need(x, BF16, "x"); _need(w, BF16, "w"); _need(bias, F32, "bias"); _need(row_live, torch.uint8, "row_live")
+    M, K = x.shape
+    N, Kw = w.shape
+    if K != Kw or (row_live is not None and row_live.numel() != M):
+        raise ValueError("gemm_fwd_slabs: x, w and row_live do not fit together")
+    if out is None:
+        out = torch.empty((M, N), device=x.device, dtype=BF16)
+    _need(out, BF16, "out")
+    if epilogue == EPI_BIAS_GELU and pre_out is None:
+        pre_out = torch.empty((M, N), device=x.device, dtype=BF16)
+    _need(pre_out, BF16, "pre_out")
+    ws_bytes = lib.ia_gemm_slabs_workspace_bytes(M)
+    ws = torch.empty(ws_bytes, device=x.device, dtype=torch.uint8)
+    check(lib.ia_gemm_fwd_slabs(x.data_ptr(), K, w.data_ptr(), K, out.data_ptr(), N, M, N, K, epilogue, ptr(bias), ptr(pre_out), scaled_cols,
+                                col_scale, ptr(row_live), int(fill), ws.data_ptr(), ws_bytes, stream_ptr()), "ia_gemm_fwd_slabs")
+    if epilogue == EPI_BIAS_GELU:
+        return out, pre_out
+    return out
+
+
 def ln_fwd_rows(x, gamma, beta, eps, row_live, *, bias=None, residual=None, write_z=True, in_place=False, drop_p=0.0, seed=0, stream_id=0):
     """ln_fwd with a row filter (ia_ln_fwd_rows): rows with row_live == 0 read nothing and leave as zeros.  in_place: z is written over x."""
     lib = _lib.load()
