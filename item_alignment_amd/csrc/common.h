@@ -197,43 +197,46 @@ extern "C" size_t ia_colsum_workspace_bytes(int M, int N);
 extern "C" int ia_colsum(const void* x, int ld, int M, int N, float* out, int accumulate, void* workspace, size_t workspace_bytes,
                          hipStream_t stream);
 __attribute__((visibility("hidden"))) size_t ia_gemm_view_workspace_bytes(int M, int N, int K, int groups);
-// dW[N_out, N_in] (+)= dY^T X over the k-tiles (64 token rows each) whose bit is set in ktile_mask (ia_ktile_mask): the weight-gradient
-// form of ia_gemm_bf16 for a caller that has the mask of its rows already (ia_layer_bwd2: one mask, four weight gradients)
-__attribute__((visibility("hidden"))) int ia_gemm_wgrad_masked(const void* dY, int ldy, const void* X, int ldx, float* dW, int ldw, int N_out,
-                                                               int N_in, int M_rows, const uint32_t* ktile_mask, int accumulate,
-                                                               void* workspace, size_t workspace_bytes, hipStream_t stream);
-
-// dX[M_rows, N_in] = dY[M_rows, K_out] W (+ epilogue: IA_EPI_NONE, IA_EPI_ADD or IA_EPI_DGELU_COLSUM) over the 32-row blocks of the live
-// list of row_blocks (ia_row_blocks), dead blocks written as zeros: the data-gradient form of ia_gemm_bf16 for a caller that has the list
-// of its rows already (ia_layer_bwd2: one list, four data gradients).  row_blocks == NULL or a shape the remapped kernel does not serve:
-// every row, as ia_gemm_bf16.
-__attribute__((visibility("hidden"))) int ia_gemm_dgrad_blocks(const void* dY, int ldy, const void* W, int w_kstrided, int ldw, void* dX, int ldx,
-                                                               int M_rows, int N_in, int K_out, int epilogue, const void* aux, int ldaux, void* C2,
-                                                               const int* row_blocks, void* workspace, size_t workspace_bytes,
-                                                               hipStream_t stream);
-// Y[M_rows, N_out] = X[M_rows, K_in] W[N_out, K_in]^T (+ epilogue: IA_EPI_NONE, IA_EPI_BIAS with scaled_cols / col_scale, IA_EPI_BIAS_GELU
-// with C2, IA_EPI_BIAS_GELU_ACT) over the 32-row blocks of the live list only -- the forward form for a caller whose dead rows nobody
-// reads (layer_forward under masked_rows_dead bit 2).  fill_dead_rows: the dead blocks' rows of Y (and C2) are written as zeros, else not
-// written at all.  row_blocks == NULL or a shape the remapped kernel does not serve: every row, as ia_gemm_bf16 / ia_gemm_bf16_qscale.
-__attribute__((visibility("hidden"))) int ia_gemm_fwd_blocks(const void* X, int ldx, const void* W, int ldw, void* Y, int ldy, int M_rows, int N_out,
-                                                             int K_in, int epilogue, const float* bias, void* C2, int scaled_cols, float col_scale,
-                                                             const int* row_blocks, int fill_dead_rows, hipStream_t stream);
-// the two over the 8-row slabs of a slab list (ia_row_slabs): IA_EPI_NONE, IA_EPI_BIAS (scaled_cols / col_scale), IA_EPI_BIAS_GELU forward,
-// IA_EPI_NONE / IA_EPI_ADD data gradient (dead slabs written as zeros).  row_slabs == NULL or a shape the remapped kernel does not serve: every row.
-__attribute__((visibility("hidden"))) int ia_gemm_fwd_slab_list(const void* X, int ldx, const void* W, int ldw, void* Y, int ldy, int M_rows, int N_out,
-                                                                int K_in, int epilogue, const float* bias, void* C2, int scaled_cols, float col_scale,
-                                                                const int* row_slabs, int fill_dead_rows, hipStream_t stream);
-__attribute__((visibility("hidden"))) int ia_gemm_dgrad_slab_list(const void* dY, int ldy, const void* W, int w_kstrided, int ldw, void* dX, int ldx,
-                                                                  int M_rows, int N_in, int K_out, int epilogue, const void* aux, int ldaux,
-                                                                  const int* row_slabs, hipStream_t stream);
-// the same for Y = X W^T + bias + aux (IA_EPI_BIAS_ADD: the fc2 of a pre-LN layer with its residual); aux is read in the live blocks only
-__attribute__((visibility("hidden"))) int ia_gemm_fwd_blocks_add(const void* X, int ldx, const void* W, int ldw, void* Y, int ldy, int M_rows,
-                                                                 int N_out, int K_in, const float* bias, const void* aux, int ldaux,
-                                                                 const int* row_blocks, int fill_dead_rows, hipStream_t stream);
-// ia_gemm_dgrad_blocks' IA_EPI_DGELU_COLSUM form over a group-aligned list (ia_row_groups): whole 128-row groups are computed or left out, each
-// group's column-sum partial lands in the slot the dense kernel gives it, so C2 is bit-identical to ia_gemm_bf16's (dead groups add zeros)
-__attribute__((visibility("hidden"))) int ia_gemm_dgrad_groups(const void* dY, int ldy, const void* W, int w_kstrided, int ldw, void* dX, int ldx,
-                                                               int M_rows, int N_in, int K_out, const void* aux, int ldaux, void* C2,
-                                                               const int* row_groups, void* workspace, size_t workspace_bytes,
-                                                               hipStream_t stream);
-
+// ---- Row filters.  A GEMM whose rows (or, for a weight gradient, whose k) are token rows may be told which of them are live and skip
+// the others.  One descriptor says which list a pointer is; it travels wherever such a pointer travels.
+//   kind     unit of liveness                      list (builder)                         GEMM forms that take it
+//   BLOCKS   32-row block                          ia_row_blocks                          forward: IA_EPI_NONE / BIAS / BIAS_GELU / BIAS_GELU_ACT /
+//                                                                                         BIAS_ADD; data gradient: IA_EPI_NONE / ADD / DGELU_COLSUM
+//   GROUPS   128-row group, listed by its blocks   ia_row_groups                          data gradient, IA_EPI_DGELU_COLSUM
+//   PACKED   32-row block, packed by whole groups  ia_row_groups_packed                   data gradient, IA_EPI_DGELU_COLSUM
+//   SLABS    8-row slab                            ia_row_slabs                           forward: IA_EPI_NONE / BIAS / BIAS_GELU; data gradient:
+//                                                                                         IA_EPI_NONE / ADD
+//   KTILES   64-row k-tile, one bit each           ia_ktile_mask                          weight gradient
+//   KBLOCKS  32-row block of k, one bit each       ia_kblock_mask                         weight gradient
+// NONE, a null list, or a shape the filtered kernel does not serve: every row, exactly the call ia_gemm_bf16 / ia_gemm_bf16_qscale makes.
+struct IaRowFilter {
+  enum Kind { NONE, BLOCKS, GROUPS, PACKED, SLABS, KTILES, KBLOCKS };
+  Kind kind = NONE;
+  const void* list = nullptr;
+  bool fill = true;      // forward GEMMs: the dead rows of Y (and C2) are written as zeros, else not written at all (data gradients always fill)
+  explicit operator bool() const { return kind != NONE && list; }
+};
+// bytes of the list of a kind over M rows, and its builder (one small launch on the stream; dst 32-byte aligned, the two masks 4)
+__attribute__((visibility("hidden"))) size_t ia_row_filter_bytes(IaRowFilter::Kind kind, int M);
+__attribute__((visibility("hidden"))) int ia_row_filter_build(IaRowFilter::Kind kind, const uint8_t* row_live, int M, void* dst, hipStream_t stream);
+// does the (kind, epilogue) pair have a kernel form?  (the table above; NONE goes with every epilogue of ia_gemm_bf16)
+__attribute__((visibility("hidden"))) bool ia_gemm_fwd_form(IaRowFilter::Kind kind, int epilogue);
+__attribute__((visibility("hidden"))) bool ia_gemm_dgrad_form(IaRowFilter::Kind kind, int epilogue);
+// Y[M_rows, N_out] = X[M_rows, K_in] W[N_out, K_in]^T (+ epilogue; IA_EPI_BIAS with scaled_cols / col_scale, IA_EPI_BIAS_GELU with C2,
+// IA_EPI_BIAS_ADD with aux) over the live rows of the filter only -- the forward form for a caller whose dead rows nobody reads
+// (layer_forward: one list, four GEMMs).  aux is read in the live rows only.  A pair without a form: IA_ERR_UNSUPPORTED.
+__attribute__((visibility("hidden"))) int ia_gemm_fwd_filtered(const void* X, int ldx, const void* W, int ldw, void* Y, int ldy, int M_rows, int N_out,
+                                                               int K_in, int epilogue, const float* bias, const void* aux, int ldaux, void* C2,
+                                                               int scaled_cols, float col_scale, IaRowFilter filter, hipStream_t stream);
+// dX[M_rows, N_in] = dY[M_rows, K_out] W (+ epilogue) over the live rows of the filter, the dead ones written as zeros: the data-gradient
+// form for a caller that has the list of its rows already (ia_layer_bwd2: one list per kind, four data gradients).  GROUPS and PACKED keep
+// the column sums (C2) bit-identical to ia_gemm_bf16's: whole 128-row groups drop out, or each group's partial is formed from that group's
+// live blocks in order and lands in the slot the dense kernel gives it (dead groups add zeros).
+__attribute__((visibility("hidden"))) int ia_gemm_dgrad_filtered(const void* dY, int ldy, const void* W, int w_kstrided, int ldw, void* dX, int ldx,
+                                                                 int M_rows, int N_in, int K_out, int epilogue, const void* aux, int ldaux, void* C2,
+                                                                 IaRowFilter filter, void* workspace, size_t workspace_bytes, hipStream_t stream);
+// dW[N_out, N_in] (+)= dY^T X over the k-tiles / 32-row blocks of k whose bit is set in the mask: the weight-gradient form of ia_gemm_bf16
+// for a caller that has the mask of its rows already (ia_layer_bwd2: one mask, four weight gradients)
+__attribute__((visibility("hidden"))) int ia_gemm_wgrad_filtered(const void* dY, int ldy, const void* X, int ldx, float* dW, int ldw, int N_out,
+                                                                 int N_in, int M_rows, IaRowFilter filter, int accumulate, void* workspace,
+                                                                 size_t workspace_bytes, hipStream_t stream);

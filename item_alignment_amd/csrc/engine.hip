@@ -20,6 +20,10 @@ struct Carver {
   char* take(size_t b) { char* r = base ? base + bytes : nullptr; bytes += al(b); return r; }
 };
 
+// Where a layer call builds the row lists its caller did not hand in (resolve_rows): one slot per filter kind, null where the call
+// never builds that kind
+struct RowSlots { uint32_t* kmask = nullptr; int* blocks = nullptr; int* groups = nullptr; int* packed = nullptr; int* slabs = nullptr; };
+
 // The buffers of one layer forward, by role.  The training stash gives each role its own memory (the backward reads them all); the
 // forward-only scratch aliases the ones whose contents are dead by the time the memory is written again.
 struct FwdBufs {
@@ -31,9 +35,8 @@ struct FwdBufs {
   char* hpre;   // gelu'(pre-activation) (IA_EPI_BIAS_GELU C2); null in the forward-only form
   char* hact;   // FFN hidden activation
   float* lse; float* mean1; float* rstd1; float* mean2; float* rstd2;
-  int* row_blk;  // masked_rows_dead bit 2: the forward's own 32-row block list (when the caller hands none in ia_layer_cfg::row_blocks)
-  int* out_blk;  // out_row_live: the forward's own block list of it (when the caller hands none in ia_layer_cfg::out_row_blocks)
-  int* row_slab; // masked_rows_dead bit 2: the forward's own 8-row slab list (when the caller hands none behind ia_layer_cfg::row_blocks, bit 6)
+  RowSlots key;  // masked_rows_dead bit 2: the forward's own 32-row block list and 8-row slab list of the key mask
+  RowSlots out;  // out_row_live: the forward's own block list of it
   size_t bytes;
 };
 
@@ -54,9 +57,9 @@ FwdBufs carve_stash(const ia_layer_cfg* c, void* base) {
   s.lse = (float*)a.take((size_t)c->B * c->nh * c->L * 4);
   s.mean1 = (float*)a.take(M * 4); s.rstd1 = (float*)a.take(M * 4);
   s.mean2 = (float*)a.take(M * 4); s.rstd2 = (float*)a.take(M * 4);
-  s.row_blk = (int*)a.take(ia_row_blocks_bytes((int)M));
-  s.out_blk = (int*)a.take(ia_row_blocks_bytes((int)M));
-  s.row_slab = (int*)a.take(ia_row_slabs_bytes((int)M));
+  s.key.blocks = (int*)a.take(ia_row_blocks_bytes((int)M));
+  s.out.blocks = (int*)a.take(ia_row_blocks_bytes((int)M));
+  s.key.slabs = (int*)a.take(ia_row_slabs_bytes((int)M));
   s.bytes = a.bytes;
   return s;
 }
@@ -73,18 +76,17 @@ FwdBufs carve_infer(const ia_layer_cfg* c, void* base) {
   s.hpre = nullptr; s.hact = a.take(M * I * 2);
   s.lse = (float*)a.take((size_t)c->B * c->nh * c->L * 4);
   s.mean1 = s.mean2 = (float*)a.take(M * 4); s.rstd1 = s.rstd2 = (float*)a.take(M * 4);
-  s.row_blk = (int*)a.take(ia_row_blocks_bytes((int)M));
-  s.out_blk = (int*)a.take(ia_row_blocks_bytes((int)M));
-  s.row_slab = (int*)a.take(ia_row_slabs_bytes((int)M));
+  s.key.blocks = (int*)a.take(ia_row_blocks_bytes((int)M));
+  s.out.blocks = (int*)a.take(ia_row_blocks_bytes((int)M));
+  s.key.slabs = (int*)a.take(ia_row_slabs_bytes((int)M));
   s.bytes = a.bytes;
   return s;
 }
 
 struct Scratch {
-  char* g0; char* g1; char* g2; char* gI; char* gqkv; float* delta; char* ws; size_t ws_bytes; char* gws; size_t gws_bytes; uint32_t* live_kt; int* row_blk;
-  int* pack_blk;      // masked_rows_dead: the block-packed list of the x gelu' data gradient (when the caller hands none behind row_blocks)
-  int* row_slab;      // masked_rows_dead: the 8-row slab list of the plain data gradients (when the caller hands none behind row_blocks, bit 6)
-  uint32_t* out_kt; int* out_blk; int* out_grp;      // out_row_live: its 32-row block mask (ia_kblock_mask), block list and group list (when the caller hands none)
+  char* g0; char* g1; char* g2; char* gI; char* gqkv; float* delta; char* ws; size_t ws_bytes; char* gws; size_t gws_bytes;
+  RowSlots key;      // masked_rows_dead: the key mask's 32-row block mask (ia_kblock_mask), block list, block-packed list and 8-row slab list
+  RowSlots out;      // out_row_live: its 32-row block mask, block list and group list
   size_t bytes;
 };
 
@@ -105,14 +107,14 @@ Scratch carve_scratch(const ia_layer_cfg* c, void* base) {
                      max3(ia_gemm_workspace_bytes((int)H, (int)I, (int)M, 1), ia_gemm_workspace_bytes((int)H, (int)H, (int)M, 1), 0));
   s.gws = a.take(s.gws_bytes);
   // masked_rows_dead: which 32-row blocks of the weight gradients' k hold a live row (one bit each, ia_kblock_mask)
-  s.live_kt = (uint32_t*)a.take(ia_kblock_mask_bytes((int)M));
+  s.key.kmask = (uint32_t*)a.take(ia_kblock_mask_bytes((int)M));
   // ... and which 32-row blocks of the data gradients do (the live list and the dead list, ia_row_blocks)
-  s.row_blk = (int*)a.take(ia_row_blocks_bytes((int)M));
-  s.pack_blk = (int*)a.take(ia_row_groups_packed_bytes((int)M));
-  s.out_kt = (uint32_t*)a.take(ia_kblock_mask_bytes((int)M));
-  s.out_blk = (int*)a.take(ia_row_blocks_bytes((int)M));
-  s.out_grp = (int*)a.take(ia_row_groups_bytes((int)M));
-  s.row_slab = (int*)a.take(ia_row_slabs_bytes((int)M));
+  s.key.blocks = (int*)a.take(ia_row_blocks_bytes((int)M));
+  s.key.packed = (int*)a.take(ia_row_groups_packed_bytes((int)M));
+  s.out.kmask = (uint32_t*)a.take(ia_kblock_mask_bytes((int)M));
+  s.out.blocks = (int*)a.take(ia_row_blocks_bytes((int)M));
+  s.out.groups = (int*)a.take(ia_row_groups_bytes((int)M));
+  s.key.slabs = (int*)a.take(ia_row_slabs_bytes((int)M));
   s.bytes = a.bytes;
   return s;
 }
@@ -139,50 +141,91 @@ int out_q_rows(const ia_layer_cfg* c) { return (out_live(c) && c->out_q_rows > 0
 
 #define IA_TRY(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
 
-// Data gradient dx[M, n_in] = dy[M, k_out] W[k_out, n_in] (+ epilogue): through the transposed shadow wt[n_in, k_out] when the caller
-// provides one (both operands k-contiguous: the faster form, ia_layer_weights::wt_*), else W read k-strided.
-// With a block list (ia_row_blocks), over the 32-row blocks that hold a live row only; the other rows of dx are written as zeros.
-int dgrad(const void* dy, int k_out, const void* w, const void* wt, int n_in, void* dx, int M, int epilogue, const void* aux, int ldaux, void* c2,
-          void* ws, size_t ws_bytes, ia_stream_t st, const int* row_blk = nullptr, const int* row_grp = nullptr, const int* row_pack = nullptr,
-          const int* row_slab = nullptr) {
-  if (row_slab && (epilogue == IA_EPI_NONE || epilogue == IA_EPI_ADD))      // the live 8-row slabs (ia_row_slabs), the others as zeros
-    return ia_gemm_dgrad_slab_list(dy, k_out, wt ? wt : w, wt ? 0 : 1, wt ? k_out : n_in, dx, n_in, M, n_in, k_out, epilogue, aux, ldaux, row_slab, st);
-  if (row_grp && epilogue == IA_EPI_DGELU_COLSUM)      // whole 128-row groups: the column sums keep the dense kernel's partials
-    return ia_gemm_dgrad_groups(dy, k_out, wt ? wt : w, wt ? 0 : 1, wt ? k_out : n_in, dx, n_in, M, n_in, k_out, aux, ldaux, c2, row_grp, ws, ws_bytes, st);
-  if (row_pack && epilogue == IA_EPI_DGELU_COLSUM)     // live blocks packed by whole groups: every group's partial keeps its slot and its bits
-    return ia_gemm_dgrad_packed(dy, k_out, wt ? wt : w, wt ? 0 : 1, wt ? k_out : n_in, dx, n_in, M, n_in, k_out, aux, ldaux, c2, row_pack, ws, ws_bytes, st);
-  if (row_blk)
-    return ia_gemm_dgrad_blocks(dy, k_out, wt ? wt : w, wt ? 0 : 1, wt ? k_out : n_in, dx, n_in, M, n_in, k_out, epilogue, aux, ldaux, c2, row_blk,
-                                ws, ws_bytes, st);
-  if (wt)
-    return ia_gemm_bf16(dy, 0, k_out, wt, 0, k_out, dx, 0, n_in, M, n_in, k_out, epilogue, nullptr, aux, ldaux, c2, 0, ws, ws_bytes, st);
-  return ia_gemm_bf16(dy, 0, k_out, w, 1, n_in, dx, 0, n_in, M, n_in, k_out, epilogue, nullptr, aux, ldaux, c2, 0, ws, ws_bytes, st);
+// The rows one stretch of a layer call runs: their live bytes (null: every row) and, per kind, the filter made from them (IaRowFilter,
+// common.h).  A kind nobody asked for, and every kind of an every-row plan, stays NONE.
+struct RowPlan {
+  const uint8_t* live = nullptr;
+  IaRowFilter kmask, blocks, groups, packed, slabs;
+};
+enum RowSource { KEY_MASK, OUT_ROWS };
+enum : unsigned { WANT_KMASK = 1, WANT_BLOCKS = 2, WANT_GROUPS = 4, WANT_PACKED = 8, WANT_SLABS = 16 };
+
+// The one place that knows where a caller's lists are and builds the missing ones.  `live`: the key mask (its filters exist under
+// masked_rows_dead bit 1 on padded rows only) or out_row_live; null: an every-row plan.  For each kind of `want` the plan takes the
+// caller's copy, else one built here into `slot` (one small launch).  The caller's copies (the mask is the same for every layer of a
+// stack and step, so a caller builds them once):
+//   key mask   row_blocks (32-row blocks); behind it in the same buffer the block-packed list at ia_row_groups_packed_offset (bit 3,
+//              value 4) and the slab list at ia_row_slabs_offset (bit 6, value 32); live_ktiles (64-row k-tiles; 32-row blocks under
+//              bit 4, value 8)
+//   out rows   out_row_blocks, out_row_groups, out_live_ktiles (32-row blocks under bit 5, value 16)
+// A mask built here holds 32-row blocks.  The packed list serves M <= 128 * 4096 rows (ia_row_groups_packed); beyond, none.
+int resolve_rows(const ia_layer_cfg* c, RowSource which, const uint8_t* live, unsigned want, int M, const RowSlots& slot, ia_stream_t st,
+                 RowPlan* plan) {
+  *plan = RowPlan{};
+  const bool key = which == KEY_MASK;
+  const unsigned bits = (unsigned)c->masked_rows_dead;
+  if (!live || (key && (!(bits & 1) || c->cu_seqlens))) return IA_OK;
+  plan->live = live;
+  auto take = [&](IaRowFilter& f, IaRowFilter::Kind kind, const void* given, void* own) {
+    f = IaRowFilter{kind, given ? given : own};
+    return given ? IA_OK : ia_row_filter_build(kind, live, M, own, st);
+  };
+  const char* const blocks = (const char*)(key ? c->row_blocks : c->out_row_blocks);
+  if (want & WANT_KMASK) {
+    const void* const given = key ? c->live_ktiles : c->out_live_ktiles;
+    IA_TRY(take(plan->kmask, (!given || (bits & (key ? 8 : 16))) ? IaRowFilter::KBLOCKS : IaRowFilter::KTILES, given, slot.kmask));
+  }
+  if (want & WANT_BLOCKS) IA_TRY(take(plan->blocks, IaRowFilter::BLOCKS, blocks, slot.blocks));
+  if (want & WANT_GROUPS) IA_TRY(take(plan->groups, IaRowFilter::GROUPS, key ? nullptr : c->out_row_groups, slot.groups));
+  if ((want & WANT_PACKED) && (size_t)M <= (size_t)128 * 4096)
+    IA_TRY(take(plan->packed, IaRowFilter::PACKED, (key && blocks && (bits & 4)) ? blocks + ia_row_groups_packed_offset(M) : nullptr, slot.packed));
+  if (want & WANT_SLABS)
+    IA_TRY(take(plan->slabs, IaRowFilter::SLABS, (key && blocks && (bits & 32)) ? blocks + ia_row_slabs_offset(M) : nullptr, slot.slabs));
+  return IA_OK;
 }
 
-// Weight gradient dW[n_out, n_in] += dy[M, n_out]^T x[M, n_in]; with a mask, over the 32-row blocks (kblocks: an ia_kblock_mask) or the
-// 64-row k-tiles (an ia_ktile_mask) that hold a live row only
-int wgrad(const void* dy, int n_out, const void* x, int n_in, float* dw, int M, const uint32_t* live_kt, bool kblocks, void* ws, size_t ws_bytes,
-          ia_stream_t st) {
-  if (live_kt && kblocks) return ia_gemm_wgrad_blocks(dy, n_out, x, n_in, dw, n_in, n_out, n_in, M, live_kt, 1, ws, ws_bytes, st);
-  if (live_kt) return ia_gemm_wgrad_masked(dy, n_out, x, n_in, dw, n_in, n_out, n_in, M, live_kt, 1, ws, ws_bytes, st);
-  return ia_gemm_bf16(dy, 1, n_out, x, 1, n_in, dw, 1, n_in, n_out, n_in, M, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 1, ws, ws_bytes, st);
+// Data gradient dx[M, n_in] = dy[M, k_out] W[k_out, n_in] (+ epilogue): through the transposed shadow wt[n_in, k_out] when the caller
+// provides one (both operands k-contiguous: the faster form, ia_layer_weights::wt_*), else W read k-strided.
+// Over the live rows of the plan, the other rows of dx written as zeros: the 8-row slabs where the epilogue has a slab form, else the
+// 32-row blocks.  IA_EPI_DGELU_COLSUM never takes the plain blocks -- that remap would regroup the column-sum partials, and the fc1 bias
+// gradient would equal the unfiltered one only up to fp32 summation order -- but whole 128-row groups (every kept partial stays where
+// and what it was) or else the blocks packed by whole groups (each group's partial is formed by one wave from that group's live blocks
+// in order and stored in the group's slot): both bit-identical to the every-row call.  No list: every row.
+int dgrad(const void* dy, int k_out, const void* w, const void* wt, int n_in, void* dx, int M, int epilogue, const void* aux, int ldaux, void* c2,
+          void* ws, size_t ws_bytes, ia_stream_t st, const RowPlan& rows) {
+  IaRowFilter f = rows.blocks;
+  if (epilogue == IA_EPI_DGELU_COLSUM) f = rows.groups ? rows.groups : rows.packed;
+  else if (rows.slabs && ia_gemm_dgrad_form(IaRowFilter::SLABS, epilogue)) f = rows.slabs;
+  return ia_gemm_dgrad_filtered(dy, k_out, wt ? wt : w, wt ? 0 : 1, wt ? k_out : n_in, dx, n_in, M, n_in, k_out, epilogue, aux, ldaux, c2, f, ws,
+                                ws_bytes, st);
+}
+
+// Weight gradient dW[n_out, n_in] += dy[M, n_out]^T x[M, n_in]; with a mask, over the 32-row blocks (an ia_kblock_mask) or the 64-row
+// k-tiles (an ia_ktile_mask) that hold a live row only
+int wgrad(const void* dy, int n_out, const void* x, int n_in, float* dw, int M, IaRowFilter kmask, void* ws, size_t ws_bytes, ia_stream_t st) {
+  return ia_gemm_wgrad_filtered(dy, n_out, x, n_in, dw, n_in, n_out, n_in, M, kmask, 1, ws, ws_bytes, st);
+}
+
+// A forward GEMM y[M, N] = x[M, K] w[N, K]^T (+ epilogue; aux has y's pitch) over the live rows of the plan: the 8-row slabs where the
+// epilogue has a slab form (a sequence's rows never line up with 32-row blocks), else the 32-row blocks; no list: every row.
+// fill: the dead rows of y (and c2) are written as zeros -- somebody reads every row -- else they are not written at all.
+int fwd_gemm(const void* x, int K, const void* w, void* y, int N, int M, int epilogue, const float* bias, const void* aux, void* c2,
+             const RowPlan& rows, bool fill, ia_stream_t st) {
+  IaRowFilter f = (rows.slabs && ia_gemm_fwd_form(IaRowFilter::SLABS, epilogue)) ? rows.slabs : rows.blocks;
+  f.fill = fill;
+  return ia_gemm_fwd_filtered(x, K, w, K, y, N, M, N, K, epilogue, bias, aux, aux ? N : 0, c2, 0, 1.f, f, st);
 }
 
 // The QKV projection of a layer writes q already multiplied by softmax scale * log2(e) (one bf16 rounding, in the GEMM epilogue where
 // the value is still fp32) and the attention kernels are told so: none of forward / dQ / dK-dV / fused backward re-scales its q tiles.
 // Needs the q | k boundary on a 128-column tile boundary of the GEMM; other hidden sizes take the plain projection and kernels.
+// With a filter (the key mask's slabs), the live rows only and the others as zeros: the attention kernels read every row of q, k and v.
 bool q_prescale(const ia_layer_cfg* c) { return (c->H & 127) == 0; }
-int qkv_proj(const ia_layer_cfg* c, const void* x, const ia_layer_weights* w, void* qkv, int M, float scale, ia_stream_t st,
-             const int* row_blk = nullptr, const int* row_slab = nullptr) {
+int qkv_proj(const ia_layer_cfg* c, const void* x, const ia_layer_weights* w, void* qkv, int M, float scale, ia_stream_t st, IaRowFilter rows) {
   const int H = c->H;
-  if (row_slab)     // the live 8-row slabs only, the others as zeros
-    return ia_gemm_fwd_slab_list(x, H, w->w_qkv, H, qkv, 3 * H, M, 3 * H, H, IA_EPI_BIAS, w->b_qkv, nullptr, q_prescale(c) ? H : 0,
-                                 q_prescale(c) ? scale * 1.4426950408889634f : 1.f, row_slab, 1, st);
-  if (row_blk)      // the live 32-row blocks only, the others as zeros: the attention kernels read every row of q, k and v
-    return ia_gemm_fwd_blocks(x, H, w->w_qkv, H, qkv, 3 * H, M, 3 * H, H, IA_EPI_BIAS, w->b_qkv, nullptr, q_prescale(c) ? H : 0,
-                              q_prescale(c) ? scale * 1.4426950408889634f : 1.f, row_blk, 1, st);
-  if (q_prescale(c)) return ia_gemm_bf16_qscale(x, H, w->w_qkv, H, qkv, 3 * H, M, 3 * H, H, w->b_qkv, H, scale * 1.4426950408889634f, st);
-  return ia_gemm_bf16(x, 0, H, w->w_qkv, 0, H, qkv, 0, 3 * H, M, 3 * H, H, IA_EPI_BIAS, w->b_qkv, nullptr, 0, nullptr, 0, nullptr, 0, st);
+  const bool ps = q_prescale(c);
+  return ia_gemm_fwd_filtered(x, H, w->w_qkv, H, qkv, 3 * H, M, 3 * H, H, IA_EPI_BIAS, w->b_qkv, nullptr, 0, nullptr, ps ? H : 0,
+                              ps ? scale * 1.4426950408889634f : 1.f, rows, st);
 }
 
 // self-attention over the packed qkv projection [rows, 3H]: padded [B, L] rows with a key mask, or packed rows (cu_seqlens)
@@ -235,73 +278,47 @@ int layer_forward(const ia_layer_cfg* c, const ia_layer_weights* w, const void* 
     // Zeros are written where somebody reads every row: q / k / v (the attention kernels), the FFN activation and its derivative (the
     // fc2 weight gradient's partly live k-tiles, the every-row x gelu' epilogue).  The two projection outputs in front of the LayerNorms
     // are not filled: only their LayerNorm reads them, which skips the dead rows and, in the training form, overwrites them in place.
-    const uint8_t* live = ((c->masked_rows_dead & 3) == 3 && !c->cu_seqlens && key_mask && g_fwd_rows) ? key_mask : nullptr;
-    const int* row_blk = nullptr;
     // ... and the GEMMs whose slab form exists take the mask in 8-row slabs (ia_row_slabs: a sequence's rows never line up with 32-row
     // blocks).  The same readers, the same argument: a dead slab of a live block holds zeros where a dead block does, and is unwritten
-    // where a dead block is (the two projection outputs).  The caller's list under bit 6 (value 32), or one per call.
-    const int* row_slab = nullptr;
-    if (live) {
-      row_blk = c->row_blocks;
-      if (row_blk && (c->masked_rows_dead & 32)) row_slab = (const int*)((const char*)row_blk + ia_row_slabs_offset(M));
-      else { IA_TRY(ia_row_slabs(live, M, s.row_slab, st)); row_slab = s.row_slab; }
-      if (!row_blk) { IA_TRY(ia_row_blocks(live, M, s.row_blk, st)); row_blk = s.row_blk; }
-    }
+    // where a dead block is (the two projection outputs).  (The forward-only activation epilogue has no slab form: it keeps the blocks.)
+    RowPlan rows;
+    const bool gate = (c->masked_rows_dead & 3) == 3 && g_fwd_rows;
+    IA_TRY(resolve_rows(c, KEY_MASK, gate ? key_mask : nullptr, WANT_BLOCKS | WANT_SLABS, M, s.key, st, &rows));
     // qkv = x Wqkv^T + b
-    IA_TRY(qkv_proj(c, x, w, s.qkv, M, scale, st, row_blk, row_slab));
+    IA_TRY(qkv_proj(c, x, w, s.qkv, M, scale, st, rows.slabs));
     IA_TRY(attn_fwd(c, s.qkv, key_mask, s.ctx, s.lse, scale, attn_drop, attn_seed, st));
     // out_row_live: behind the attention only the rows the caller reads are live (a subset of the live keys) -- the same rules with that
     // mask and its block list: the LayerNorms leave zeros in the other rows (so y1 and, in the training form, z1 / z2 are finite in every
     // row a partly live k-tile of a weight gradient touches), fc1 fills the other blocks of the activation and its derivative
-    if (const uint8_t* const olive = out_live(c)) {
-      live = olive;
-      row_blk = c->out_row_blocks;
-      if (!row_blk) { IA_TRY(ia_row_blocks(olive, M, s.out_blk, st)); row_blk = s.out_blk; }
-      row_slab = nullptr;      // (out_row_live keeps its 32-row lists)
-    }
+    // (out_row_live keeps its 32-row lists)
+    if (const uint8_t* const olive = out_live(c)) IA_TRY(resolve_rows(c, OUT_ROWS, olive, WANT_BLOCKS, M, s.out, st, &rows));
     // z1 = x + dropout(ctx Wo^T + b_o); y1 = LN1(z1)
-    if (row_slab) IA_TRY(ia_gemm_fwd_slab_list(s.ctx, H, w->w_o, H, s.proj, H, M, H, H, IA_EPI_NONE, nullptr, nullptr, 0, 1.f, row_slab, 0, st));
-    else if (row_blk) IA_TRY(ia_gemm_fwd_blocks(s.ctx, H, w->w_o, H, s.proj, H, M, H, H, IA_EPI_NONE, nullptr, nullptr, 0, 1.f, row_blk, 0, st));
-    else IA_TRY(ia_gemm_bf16(s.ctx, 0, H, w->w_o, 0, H, s.proj, 0, H, M, H, H, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, st));
+    IA_TRY(fwd_gemm(s.ctx, H, w->w_o, s.proj, H, M, IA_EPI_NONE, nullptr, nullptr, nullptr, rows, false, st));
     IA_TRY(ia_ln_fwd_rows(s.proj, w->b_o, x, keep ? s.proj : nullptr, s.ln, s.mean1, s.rstd1, w->ln1_g, w->ln1_b, M, H, c->eps, hidden_drop, seed,
-                          ln1_stream, live, st));
+                          ln1_stream, rows.live, st));
     // h = gelu(y1 W1^T + b1)
-    // (the forward-only activation epilogue has no slab form: it keeps the blocks)
-    if (row_slab && keep) IA_TRY(ia_gemm_fwd_slab_list(s.ln, H, w->w_fc1, H, s.hact, I, M, I, H, gelu, w->b_fc1, s.hpre, 0, 1.f, row_slab, 1, st));
-    else if (row_blk) IA_TRY(ia_gemm_fwd_blocks(s.ln, H, w->w_fc1, H, s.hact, I, M, I, H, gelu, w->b_fc1, s.hpre, 0, 1.f, row_blk, 1, st));
-    else IA_TRY(ia_gemm_bf16(s.ln, 0, H, w->w_fc1, 0, H, s.hact, 0, I, M, I, H, gelu, w->b_fc1, nullptr, 0, s.hpre, 0, nullptr, 0, st));
+    IA_TRY(fwd_gemm(s.ln, H, w->w_fc1, s.hact, I, M, gelu, w->b_fc1, nullptr, s.hpre, rows, true, st));
     // z2 = y1 + dropout(h W2^T + b2); y = LN2(z2)
-    if (row_slab) IA_TRY(ia_gemm_fwd_slab_list(s.hact, I, w->w_fc2, I, s.ffn, H, M, H, I, IA_EPI_NONE, nullptr, nullptr, 0, 1.f, row_slab, 0, st));
-    else if (row_blk) IA_TRY(ia_gemm_fwd_blocks(s.hact, I, w->w_fc2, I, s.ffn, H, M, H, I, IA_EPI_NONE, nullptr, nullptr, 0, 1.f, row_blk, 0, st));
-    else IA_TRY(ia_gemm_bf16(s.hact, 0, I, w->w_fc2, 0, I, s.ffn, 0, H, M, H, I, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, st));
+    IA_TRY(fwd_gemm(s.hact, I, w->w_fc2, s.ffn, H, M, IA_EPI_NONE, nullptr, nullptr, nullptr, rows, false, st));
     IA_TRY(ia_ln_fwd_rows(s.ffn, w->b_fc2, s.ln, keep ? s.ffn : nullptr, y, s.mean2, s.rstd2, w->ln2_g, w->ln2_b, M, H, c->eps, hidden_drop, seed,
-                          ln2_stream, live, st));
+                          ln2_stream, rows.live, st));
   } else {   // no dropout (timm ViT default; ia_layer_fwd refuses it)
     IA_TRY(ia_ln_fwd(x, nullptr, nullptr, nullptr, s.xn, s.mean1, s.rstd1, w->ln1_g, w->ln1_b, M, H, c->eps, 0.f, 0, 0, st));
-    IA_TRY(qkv_proj(c, s.xn, w, s.qkv, M, scale, st));
+    IA_TRY(qkv_proj(c, s.xn, w, s.qkv, M, scale, st, IaRowFilter{}));
     IA_TRY(attn_fwd(c, s.qkv, key_mask, s.ctx, s.lse, scale, 0.f, 0, st));
     // x1 = x + ctx Wo^T + b_o and LN2(x1): the bias and the residual are added by the LayerNorm kernel (it streams the rows anyway),
     // so the projection keeps the plain epilogue; proj receives x1 in place of the raw projection (the fc2 epilogue's residual)
     // out_row_live (the last block under a head that reads [CLS] only): the out-projection, LN2, fc1 and fc2 run the 32-row blocks / rows
     // the caller reads.  LN2 leaves zeros in the other rows of x1 and LN2(x1), fc1 fills the other blocks of the activation and its
     // derivative (the weight gradients' partly live k-tiles and the x gelu' epilogue read them); y is not written outside the live blocks.
-    const uint8_t* const olive = out_live(c);
-    const int* oblk = nullptr;
-    if (olive) {
-      oblk = c->out_row_blocks;
-      if (!oblk) { IA_TRY(ia_row_blocks(olive, M, s.out_blk, st)); oblk = s.out_blk; }
-    }
-    if (oblk) IA_TRY(ia_gemm_fwd_blocks(s.ctx, H, w->w_o, H, s.proj, H, M, H, H, IA_EPI_NONE, nullptr, nullptr, 0, 1.f, oblk, 0, st));
-    else IA_TRY(ia_gemm_bf16(s.ctx, 0, H, w->w_o, 0, H, s.proj, 0, H, M, H, H, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, st));
-    IA_TRY(ia_ln_fwd_rows(s.proj, w->b_o, x, s.proj, s.ln, s.mean2, s.rstd2, w->ln2_g, w->ln2_b, M, H, c->eps, 0.f, 0, 0, olive, st));
-    if (oblk) {
-      IA_TRY(ia_gemm_fwd_blocks(s.ln, H, w->w_fc1, H, s.hact, I, M, I, H, gelu, w->b_fc1, s.hpre, 0, 1.f, oblk, 1, st));
-      IA_TRY(ia_gemm_fwd_blocks_add(s.hact, I, w->w_fc2, I, y, H, M, H, I, w->b_fc2, s.proj, H, oblk, 0, st));
-    } else {
-      IA_TRY(ia_gemm_bf16(s.ln, 0, H, w->w_fc1, 0, H, s.hact, 0, I, M, I, H, gelu, w->b_fc1, nullptr, 0, s.hpre, 0, nullptr, 0, st));
-      IA_TRY(ia_gemm_bf16(s.hact, 0, I, w->w_fc2, 0, I, y, 0, H, M, H, I, IA_EPI_BIAS_ADD, w->b_fc2, s.proj, H, nullptr, 0, nullptr, 0, st));
-    }
+    RowPlan rows;
+    IA_TRY(resolve_rows(c, OUT_ROWS, out_live(c), WANT_BLOCKS, M, s.out, st, &rows));
+    IA_TRY(fwd_gemm(s.ctx, H, w->w_o, s.proj, H, M, IA_EPI_NONE, nullptr, nullptr, nullptr, rows, false, st));
+    IA_TRY(ia_ln_fwd_rows(s.proj, w->b_o, x, s.proj, s.ln, s.mean2, s.rstd2, w->ln2_g, w->ln2_b, M, H, c->eps, 0.f, 0, 0, rows.live, st));
+    IA_TRY(fwd_gemm(s.ln, H, w->w_fc1, s.hact, I, M, gelu, w->b_fc1, nullptr, s.hpre, rows, true, st));
+    IA_TRY(fwd_gemm(s.hact, I, w->w_fc2, y, H, M, IA_EPI_BIAS_ADD, w->b_fc2, s.proj, nullptr, rows, false, st));
   }
+
   return IA_OK;
 }
 
@@ -391,103 +408,67 @@ extern "C" int ia_layer_bwd2(const ia_layer_cfg* c, const ia_layer_weights* w, c
   const uint32_t attn_seed = c->seed * 2654435761u + c->layer_id * 97u + 17u;
   const bool drop = c->hidden_drop > 0.f;
   // out_row_live: the incoming gradient is zero outside these rows, so every gradient in front of the attention backward is too.  Its
-  // k-tile mask, block list and group list (the caller's, or built here) filter the kernels from the LN2 backward to the out-projection's
+  // block mask, block list and group list (the caller's, or built here) filter the kernels from the LN2 backward to the out-projection's
   // gradients; the attention backward and the QKV gradients keep the layer's other filter (every row is a key).
-  const uint8_t* const olive = out_live(c);
-  // (a caller's out_live_ktiles is a 32-row block mask under masked_rows_dead bit 16, else a 64-row one; the one built here: 32-row)
-  const uint32_t* okt = nullptr; const int* oblk = nullptr; const int* ogrp = nullptr;
-  bool okb = false;
-  if (olive) {
-    okt = c->out_live_ktiles; oblk = c->out_row_blocks; ogrp = c->out_row_groups;
-    okb = !okt || (c->masked_rows_dead & 16);
-    if (!okt) { IA_TRY(ia_kblock_mask(olive, M, k.out_kt, st)); okt = k.out_kt; }
-    if (!oblk) { IA_TRY(ia_row_blocks(olive, M, k.out_blk, st)); oblk = k.out_blk; }
-    if (!ogrp) { IA_TRY(ia_row_groups(olive, M, k.out_grp, st)); ogrp = k.out_grp; }
-  }
+  RowPlan out;
+  IA_TRY(resolve_rows(c, OUT_ROWS, out_live(c), WANT_KMASK | WANT_BLOCKS | WANT_GROUPS, M, k.out, st, &out));
   if (!c->pre_ln) {
     // masked_rows_dead: every gradient row of a masked position is exactly zero (ia_layer_cfg): the LayerNorm backward kernels skip them,
-    // the four weight gradients skip the 32-row blocks of k that hold nothing else (one bitmask per call, in scratch; a caller's 64-row mask: the 64-row k-tiles), and the three plain data
-    // gradients (fc1, out-projection, QKV) the 32-row blocks (one block list per call; their dead rows are written as zeros: the attention backward, the pair
-    // kernels and the embedding backward read every row)
-    // (the mask is the same for every layer of a stack and step: a caller that built the bitmask and the list once hands them in
-    // ia_layer_cfg::live_ktiles / row_blocks, and the two launches per call go)
-    const uint8_t* const live = ((c->masked_rows_dead & 1) && !c->cu_seqlens) ? key_mask : nullptr;
-    const uint32_t* const live_kt = live ? (c->live_ktiles ? c->live_ktiles : k.live_kt) : nullptr;
-    const int* const row_blk = (live && g_dgrad_rows) ? (c->row_blocks ? c->row_blocks : k.row_blk) : nullptr;
-    const bool live_kb = !c->live_ktiles || (c->masked_rows_dead & 8);      // a block mask: the one built here, or the caller's under bit 8
-    if (live && !c->live_ktiles) IA_TRY(ia_kblock_mask(live, M, k.live_kt, st));
-    if (row_blk && !c->row_blocks) IA_TRY(ia_row_blocks(live, M, k.row_blk, st));
-    // ... and the x gelu' + column-sums data gradient the same blocks packed by whole 128-row groups (ia_row_groups_packed): the caller's list
-    // behind its row_blocks (masked_rows_dead bit 3), or one per call.  ia_debug_dgrad_rows withholds it with the block list.
-    const int* row_pack = nullptr;
-    if (row_blk && (size_t)M <= (size_t)128 * 4096) {
-      if (c->row_blocks && (c->masked_rows_dead & 4)) row_pack = (const int*)((const char*)c->row_blocks + ia_row_groups_packed_offset(M));
-      else { IA_TRY(ia_row_groups_packed(live, M, k.pack_blk, st)); row_pack = k.pack_blk; }
-    }
-    // ... and the three plain data gradients the same mask in 8-row slabs (ia_row_slabs): the caller's list behind its row_blocks
-    // (masked_rows_dead bit 6, value 32), or one per call.  Withheld with the block list.
-    const int* row_slab = nullptr;
-    if (row_blk) {
-      if (c->row_blocks && (c->masked_rows_dead & 32)) row_slab = (const int*)((const char*)c->row_blocks + ia_row_slabs_offset(M));
-      else { IA_TRY(ia_row_slabs(live, M, k.row_slab, st)); row_slab = k.row_slab; }
-    }
-    const int* const slab2 = olive ? nullptr : row_slab;
-    // behind the attention: out_row_live's lists when given (a subset of the live keys), else the key mask's
-    const uint8_t* const live2 = olive ? olive : live;
-    const uint32_t* const kt2 = olive ? okt : live_kt;
-    const int* const blk2 = olive ? oblk : row_blk;
-    const bool kb2 = olive ? okb : live_kb;
+    // the four weight gradients skip the 32-row blocks of k that hold nothing else (a caller's 64-row mask: the 64-row k-tiles), the two
+    // plain data gradients behind the attention and the QKV one run the live 8-row slabs (their dead rows are written as zeros: the
+    // attention backward, the pair kernels and the embedding backward read every row), and the x gelu' + column-sums data gradient the
+    // live blocks packed by whole 128-row groups.  ia_debug_dgrad_rows withholds the lists of the data gradients, not the mask.
+    RowPlan key;
+    IA_TRY(resolve_rows(c, KEY_MASK, key_mask, WANT_KMASK | (g_dgrad_rows ? WANT_BLOCKS | WANT_PACKED | WANT_SLABS : 0), M, k.key, st, &key));
+    // behind the attention: out_row_live's plan when given (a subset of the live keys), else the key mask's
+    const RowPlan& rows = out.live ? out : key;
     // The two residual additions of a post-LN layer make each LayerNorm output's gradient a sum of two terms; both LayerNorm
     // backward kernels take the two terms (ia_ln_bwd2), so the GEMMs in front of them keep the plain epilogue.
     // LN2 backward: d(output) = dy (+ dy2) -> dz2 in g0, masked branch gradient -> g1 (or g0 when p == 0)
     IA_TRY(ia_ln_bwd2_rows(dy, dy2, nullptr, s.ffn, s.mean2, s.rstd2, w->ln2_g, k.g0, drop ? k.g1 : nullptr, g->ln2_g, g->ln2_b, g->b_fc2, M, H,
-                           c->hidden_drop, c->seed, c->layer_id * 4u + 1u, live2, k.ws, k.ws_bytes, 1, st));
+                           c->hidden_drop, c->seed, c->layer_id * 4u + 1u, rows.live, k.ws, k.ws_bytes, 1, st));
     const char* d_ffn = drop ? k.g1 : k.g0;
-    IA_TRY(wgrad(d_ffn, H, s.hact, I, (float*)g->w_fc2, M, kt2, kb2, k.gws, k.gws_bytes, st));
-    // d(pre-activation) = (d_ffn W2) * gelu'(pre), and its column sums (the fc1 bias gradient) out of the same epilogue.
-    // The plain block remap would regroup the column-sum partials (the fc1 bias gradient then equals the unfiltered one only up to fp32
-    // summation order), so this GEMM takes the blocks packed by whole 128-row groups: each group's partial is formed by one wave from that
-    // group's live blocks in order and stored in the group's slot -- bit-identical to masked_rows_dead = 0 (ia_gemm_dgrad_packed).
-    // ogrp (out_row_live): whole 128-row groups drop out, which leaves every kept partial where and what it was (ia_gemm_dgrad_groups).
-    // Neither list: every row.
-    IA_TRY(dgrad(d_ffn, H, w->w_fc2, w->wt_fc2, I, k.gI, M, IA_EPI_DGELU_COLSUM, s.hpre, I, g->b_fc1, k.ws, k.ws_bytes, st, nullptr, ogrp, row_pack));
-    IA_TRY(wgrad(k.gI, I, s.ln, H, (float*)g->w_fc1, M, kt2, kb2, k.gws, k.gws_bytes, st));
-    IA_TRY(dgrad(k.gI, I, w->w_fc1, w->wt_fc1, H, k.g2, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, blk2, nullptr, nullptr, slab2));
+    IA_TRY(wgrad(d_ffn, H, s.hact, I, (float*)g->w_fc2, M, rows.kmask, k.gws, k.gws_bytes, st));
+    // d(pre-activation) = (d_ffn W2) * gelu'(pre), and its column sums (the fc1 bias gradient) out of the same epilogue
+    IA_TRY(dgrad(d_ffn, H, w->w_fc2, w->wt_fc2, I, k.gI, M, IA_EPI_DGELU_COLSUM, s.hpre, I, g->b_fc1, k.ws, k.ws_bytes, st, rows));
+    IA_TRY(wgrad(k.gI, I, s.ln, H, (float*)g->w_fc1, M, rows.kmask, k.gws, k.gws_bytes, st));
+    IA_TRY(dgrad(k.gI, I, w->w_fc1, w->wt_fc1, H, k.g2, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, rows));
     // LN1 backward: d(y1) = g2 (through fc1) + g0 (residual into LN2) -> dz1 (the layer input's residual-path gradient) in
     // dz1buf: the caller's dx2 when the split form is wanted, else g0 (in place over the term just consumed)
     char* dz1buf = dx2 ? (char*)dx2 : k.g0;
     IA_TRY(ia_ln_bwd2_rows(k.g2, k.g0, nullptr, s.proj, s.mean1, s.rstd1, w->ln1_g, dz1buf, drop ? k.g1 : nullptr, g->ln1_g, g->ln1_b, g->b_o, M, H,
-                           c->hidden_drop, c->seed, c->layer_id * 4u + 0u, live2, k.ws, k.ws_bytes, 1, st));
+                           c->hidden_drop, c->seed, c->layer_id * 4u + 0u, rows.live, k.ws, k.ws_bytes, 1, st));
     const char* d_att = drop ? k.g1 : dz1buf;
-    IA_TRY(wgrad(d_att, H, s.ctx, H, (float*)g->w_o, M, kt2, kb2, k.gws, k.gws_bytes, st));
+    IA_TRY(wgrad(d_att, H, s.ctx, H, (float*)g->w_o, M, rows.kmask, k.gws, k.gws_bytes, st));
     // (d_ctx and dz1 are zeros outside out_row_live: the attention backward and the QKV data gradient's "+ dz1" read every live key's row)
-    IA_TRY(dgrad(d_att, H, w->w_o, w->wt_o, H, k.g2, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, blk2, nullptr, nullptr, slab2));
+    IA_TRY(dgrad(d_att, H, w->w_o, w->wt_o, H, k.g2, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, rows));
     IA_TRY(attn_bwd(c, s.qkv, key_mask, s.ctx, k.g2, s.lse, k.delta, k.gqkv, g->b_qkv, k.ws, k.ws_bytes, scale, c->attn_drop, attn_seed, st));
-    IA_TRY(wgrad(k.gqkv, 3 * H, x, H, (float*)g->w_qkv, M, live_kt, live_kb, k.gws, k.gws_bytes, st));
+    IA_TRY(wgrad(k.gqkv, 3 * H, x, H, (float*)g->w_qkv, M, key.kmask, k.gws, k.gws_bytes, st));
     if (dx2)   // split form: dx = the attention sub-block's data gradient, dx2 = dz1 (already written)
-      IA_TRY(dgrad(k.gqkv, 3 * H, w->w_qkv, w->wt_qkv, H, dx, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, row_blk, nullptr, nullptr, row_slab));
+      IA_TRY(dgrad(k.gqkv, 3 * H, w->w_qkv, w->wt_qkv, H, dx, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, key));
     else
-      IA_TRY(dgrad(k.gqkv, 3 * H, w->w_qkv, w->wt_qkv, H, dx, M, IA_EPI_ADD, dz1buf, H, nullptr, nullptr, 0, st, row_blk, nullptr, nullptr, row_slab));
+      IA_TRY(dgrad(k.gqkv, 3 * H, w->w_qkv, w->wt_qkv, H, dx, M, IA_EPI_ADD, dz1buf, H, nullptr, nullptr, 0, st, key));
   } else {
     if (!c->dy_colsum_done) IA_TRY(ia_colsum(dy, H, M, H, g->b_fc2, 1, k.ws, k.ws_bytes, st));
-    // (okt / oblk / ogrp are NULL without out_row_live: the helpers then make the plain every-row calls)
-    IA_TRY(wgrad(dy, H, s.hact, I, (float*)g->w_fc2, M, okt, okb, k.gws, k.gws_bytes, st));
-    IA_TRY(dgrad(dy, H, w->w_fc2, w->wt_fc2, I, k.gI, M, IA_EPI_DGELU_COLSUM, s.hpre, I, g->b_fc1, k.ws, k.ws_bytes, st, nullptr, ogrp));
-    IA_TRY(wgrad(k.gI, I, s.ln, H, (float*)g->w_fc1, M, okt, okb, k.gws, k.gws_bytes, st));
-    IA_TRY(dgrad(k.gI, I, w->w_fc1, w->wt_fc1, H, k.g0, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, oblk));
+    // (without out_row_live the plan is empty: the helpers then make the plain every-row calls)
+    IA_TRY(wgrad(dy, H, s.hact, I, (float*)g->w_fc2, M, out.kmask, k.gws, k.gws_bytes, st));
+    IA_TRY(dgrad(dy, H, w->w_fc2, w->wt_fc2, I, k.gI, M, IA_EPI_DGELU_COLSUM, s.hpre, I, g->b_fc1, k.ws, k.ws_bytes, st, out));
+    IA_TRY(wgrad(k.gI, I, s.ln, H, (float*)g->w_fc1, M, out.kmask, k.gws, k.gws_bytes, st));
+    IA_TRY(dgrad(k.gI, I, w->w_fc1, w->wt_fc1, H, k.g0, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, out));
     // LN2 backward (+ residual path dy) -> g1 = d x2 ; its column sum is the proj-bias gradient
     // (the row-filtered launch keeps every row's place in the partial sums: leaving out rows that add exact zeros changes no bit)
-    IA_TRY(ia_ln_bwd2_rows(k.g0, nullptr, dy, s.proj, s.mean2, s.rstd2, w->ln2_g, k.g1, nullptr, g->ln2_g, g->ln2_b, g->b_o, M, H, 0.f, 0, 0, olive,
+    IA_TRY(ia_ln_bwd2_rows(k.g0, nullptr, dy, s.proj, s.mean2, s.rstd2, w->ln2_g, k.g1, nullptr, g->ln2_g, g->ln2_b, g->b_o, M, H, 0.f, 0, 0, out.live,
                            k.ws, k.ws_bytes, 1, st));
-    IA_TRY(wgrad(k.g1, H, s.ctx, H, (float*)g->w_o, M, okt, okb, k.gws, k.gws_bytes, st));
-    IA_TRY(dgrad(k.g1, H, w->w_o, w->wt_o, H, k.g2, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, oblk));
+    IA_TRY(wgrad(k.g1, H, s.ctx, H, (float*)g->w_o, M, out.kmask, k.gws, k.gws_bytes, st));
+    IA_TRY(dgrad(k.g1, H, w->w_o, w->wt_o, H, k.g2, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, out));
     IA_TRY(attn_bwd(c, s.qkv, key_mask, s.ctx, k.g2, s.lse, k.delta, k.gqkv, g->b_qkv, k.ws, k.ws_bytes, scale, 0.f, 0, st));
-    IA_TRY(ia_gemm_bf16(k.gqkv, 1, 3 * H, s.xn, 1, H, g->w_qkv, 1, H, 3 * H, H, M, IA_EPI_NONE, nullptr, nullptr, 0, nullptr, 1, k.gws, k.gws_bytes, st));
-    IA_TRY(dgrad(k.gqkv, 3 * H, w->w_qkv, w->wt_qkv, H, k.g0, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st));
+    IA_TRY(wgrad(k.gqkv, 3 * H, s.xn, H, (float*)g->w_qkv, M, IaRowFilter{}, k.gws, k.gws_bytes, st));
+    IA_TRY(dgrad(k.gqkv, 3 * H, w->w_qkv, w->wt_qkv, H, k.g0, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, RowPlan{}));
     // dx = LN1'(g0) + g1 is the incoming gradient of the block below: its column sums (that block's fc2 bias gradient) come out of
     // this kernel's partial sums instead of a separate pass over [M, H] there (cfg->dx_colsum_out)
     IA_TRY(ia_ln_bwd(k.g0, k.g1, x, s.mean1, s.rstd1, w->ln1_g, dx, nullptr, g->ln1_g, g->ln1_b, c->dx_colsum_out, M, H, 0.f, 0, 0, k.ws,
                      k.ws_bytes, 1, st));
   }
+
   return IA_OK;
 }

@@ -1947,8 +1947,22 @@ __global__ __launch_bounds__(256) void zero_dead_slabs_kernel(const int* __restr
   }
 }
 
+// the 256-wide kernels one instantiation of `launch` may start: each needs its dynamic LDS size set once
+enum KernelForm {
+  FORM_T256W,            // this instantiation of t256w
+  FORM_T256LA,           // the look-ahead kernel
+  FORM_WGRAD_KTILES,     // the live-k-tile weight gradient
+  FORM_ROWS_T256W,       // the row remap (32-row blocks) of FORM_T256W ...
+  FORM_ROWS_T256LA,      // ... and of FORM_T256LA
+  FORM_WGRAD_KBLOCKS,    // the live-block weight gradient
+  FORM_SLABS_T256W,      // the slab remap of FORM_T256W ...
+  FORM_SLABS_T256LA,     // ... and of FORM_T256LA
+  FORM_COUNT
+};
+
+// kind: what a.live_kt / a.row_blk point at (KBLOCKS: a mask of 32-row blocks, ia_kblock_mask; SLABS: a slab list, ia_row_slabs)
 template <bool AKS, bool BKS, int EPI, bool OUTF32>
-int launch(GemmArgs a, bool big, hipStream_t st, bool live_blocks = false, bool slabs = false) {      // live_blocks: a.live_kt is a mask of 32-row blocks (ia_kblock_mask); slabs: a.row_blk is a slab list (ia_row_slabs)
+int launch(GemmArgs a, bool big, hipStream_t st, IaRowFilter::Kind kind = IaRowFilter::NONE) {
   constexpr int vid = AKS * 1000 + BKS * 100 + EPI * 10 + (OUTF32 ? 1 : 0);
   // the forms that may carry a block list (GemmArgs::row_blk): the data gradients, and the forward epilogues on k-contiguous operands
   constexpr bool DROWS = !AKS && !OUTF32 && (EPI == EPI_NONE || EPI == EPI_ADD || EPI == EPI_DGELU_CS ||
@@ -1968,33 +1982,33 @@ int launch(GemmArgs a, bool big, hipStream_t st, bool live_blocks = false, bool 
     // persistent launches with more than one tile per workgroup claim their tiles dynamically (IA_GEMM_DYNAMIC=0: the static order)
     a.tile_ctr = (a.splits == 1 && ntile > gx) ? next_ctr_slot() : nullptr;
     void (*kern)(GemmArgs) = t256w::gemm_kernel<AKS, BKS, EPI, OUTF32>;
-    static bool attr_set[8] = {false, false, false, false, false, false, false, false};      // per kernel: [0] this instantiation of t256w, [1] t256la, [2] the live-k-tile weight gradient, [3] / [4] the row remap of [0] / [1], [5] the live-block weight gradient, [6] / [7] the slab remap of [0] / [1]
-    int la = 0;
+    static bool attr_set[FORM_COUNT] = {};
+    KernelForm form = FORM_T256W;
     if constexpr (WGRAD) {
-      if (a.live_kt && live_blocks) { kern = t256w::gemm_kernel<true, true, EPI_NONE_BLK, true>; la = 5; }
-      else if (a.live_kt) { kern = t256w::gemm_kernel<true, true, EPI_NONE_LIVE, true>; la = 2; }
+      if (a.live_kt && kind == IaRowFilter::KBLOCKS) { kern = t256w::gemm_kernel<true, true, EPI_NONE_BLK, true>; form = FORM_WGRAD_KBLOCKS; }
+      else if (a.live_kt) { kern = t256w::gemm_kernel<true, true, EPI_NONE_LIVE, true>; form = FORM_WGRAD_KTILES; }
     }
     // plain NT form, several tiles per workgroup, static order: the look-ahead kernel (t256la; IA_GEMM_LA=0 keeps t256w)
     if constexpr (!AKS && !BKS && EPI == EPI_NONE && !OUTF32) {
       const char* e = getenv("IA_GEMM_LA");       // (read per launch: tests and A/B runs switch it in one process)
-      if ((e ? atoi(e) : 1) && a.splits == 1 && ntile > gx && !a.tile_ctr && a.K >= 2 * BK && !(IA_DBG(a))) { kern = t256la::gemm_kernel<false>; la = 1; }
+      if ((e ? atoi(e) : 1) && a.splits == 1 && ntile > gx && !a.tile_ctr && a.K >= 2 * BK && !(IA_DBG(a))) { kern = t256la::gemm_kernel<false>; form = FORM_T256LA; }
     }
     // over the live 32-row blocks: the remapped form of the kernel chosen above, dead rows zeroed first where the caller asks for it
     if constexpr (DROWS) {
       constexpr bool DSLABS = EPI == EPI_NONE || EPI == EPI_ADD || (!BKS && (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU));
-      if (a.row_blk && slabs) {
+      const bool la = form == FORM_T256LA;
+      if (a.row_blk && kind == IaRowFilter::SLABS) {
         if constexpr (DSLABS) {
-          if (la == 1) kern = t256la::gemm_slab_kernel;
+          if (la) kern = t256la::gemm_slab_kernel;
           else kern = t256w::gemm_kernel<false, BKS, EPI_ROWS + EPI_SLABS + EPI, false>;
-          la = la == 1 ? 7 : 6;
+          form = la ? FORM_SLABS_T256LA : FORM_SLABS_T256W;
           if (a.rows_fill) hipLaunchKernelGGL(zero_dead_slabs_kernel, dim3(1024), dim3(256), 0, st, a.row_blk, (bf16*)a.C, a.ldc, a.fill_m, a.N);
           if (a.rows_fill && EPI == EPI_BIAS_GELU) hipLaunchKernelGGL(zero_dead_slabs_kernel, dim3(1024), dim3(256), 0, st, a.row_blk, a.C2, a.ldc, a.fill_m, a.N);
         } else return IA_ERR_UNSUPPORTED;
-      } else
-      if (a.row_blk) {
-        if (la == 1) kern = t256la::gemm_kernel<true>;      // (the look-ahead kernel's remapped form where the dense call takes that kernel)
+      } else if (a.row_blk) {
+        if (la) kern = t256la::gemm_kernel<true>;      // (the look-ahead kernel's remapped form where the dense call takes that kernel)
         else kern = t256w::gemm_kernel<false, BKS, EPI_ROWS + EPI, false>;
-        la = la == 1 ? 4 : 3;
+        form = la ? FORM_ROWS_T256LA : FORM_ROWS_T256W;
         if (a.rows_fill)
           hipLaunchKernelGGL(zero_dead_rows_kernel, dim3(1024), dim3(256), 0, st, a.row_blk, (bf16*)a.C, a.ldc, a.fill_m, a.N, a.csum_part, ((a.M + 255) / 256) * 2,
                              a.rows_grouped);
@@ -2002,9 +2016,9 @@ int launch(GemmArgs a, bool big, hipStream_t st, bool live_blocks = false, bool 
           hipLaunchKernelGGL(zero_dead_rows_kernel, dim3(1024), dim3(256), 0, st, a.row_blk, a.C2, a.ldc, a.fill_m, a.N, (float*)nullptr, 0);
       }
     }
-    if (!attr_set[la]) {
+    if (!attr_set[form]) {
       if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, t256w::LDS_BYTES) != hipSuccess) return IA_ERR_LAUNCH;
-      attr_set[la] = true;
+      attr_set[form] = true;
     }
     hipLaunchKernelGGL(kern, dim3(gx), dim3(256), t256w::LDS_BYTES, st, a);
   } else {
@@ -2040,11 +2054,25 @@ extern "C" size_t ia_gemm_workspace_bytes(int M, int N, int K, int c_is_f32) {
   return pl.splits > 1 ? (size_t)pl.splits * M * (N + 1) * sizeof(float) : 0;      // + the row-sum partials of the weight-gradient form
 }
 
-static int gemm_core(const void* A, int a_kstrided, int lda, const void* B, int b_kstrided, int ldb, void* C, int c_is_f32, int ldc, int M,
-                     int N, int K, int epilogue, const float* bias, const void* aux, int ldaux, void* C2, int accumulate, void* workspace,
-                     size_t workspace_bytes, const IaViewGemm* view, hipStream_t stream, int qcols = 0, float qscale = 1.f,
-                     const uint32_t* live_kt = nullptr, const int* row_blocks = nullptr, int rows_fill = 1, int tail_of = 0,      // tail_of: below
-                     int rows_grouped = 0, int live_blocks = 0, int row_slabs = 0);      // row_slabs: row_blocks is a slab list (ia_row_slabs)
+// One GEMM call as the host entry points describe it (host only: GemmArgs is what the kernels see).  The operands, output and shape as in
+// ia_gemm_bf16; everything else is optional.
+struct GemmCall {
+  const void* A; int a_kstrided, lda;
+  const void* B; int b_kstrided, ldb;
+  void* C; int c_is_f32, ldc;
+  int M, N, K;
+  int epilogue = EPI_NONE;
+  const float* bias = nullptr;
+  const void* aux = nullptr; int ldaux = 0;
+  void* C2 = nullptr;
+  int accumulate = 0;
+  void* workspace = nullptr; size_t workspace_bytes = 0;
+  const IaViewGemm* view = nullptr;      // ia_gemm_view: shifted operand views, channel groups
+  int qcols = 0; float qscale = 1.f;     // ia_gemm_bf16_qscale: the first qcols columns leave multiplied by qscale
+  IaRowFilter filter;                    // the live rows (a list) or the live k (a mask); honoured by the forms that have a filtered kernel
+  bool tail = false;                     // gemm_core's own second launch for the scaled-column tail (see there)
+};
+static int gemm_core(const GemmCall& c, hipStream_t stream);
 
 // workspace of an IA_EPI_DGELU_COLSUM GEMM: one fp32 row of N partial sums per 128-row block of the output (and never less than
 // the stand-alone column-sum kernel needs, which small shapes fall back to)
@@ -2058,16 +2086,17 @@ extern "C" int ia_gemm_bf16(const void* A, int a_kstrided, int lda, const void* 
                             void* C, int c_is_f32, int ldc, int M, int N, int K, int epilogue,
                             const float* bias, const void* aux, int ldaux, void* C2, int accumulate, void* workspace,
                             size_t workspace_bytes, hipStream_t stream) {
-  return gemm_core(A, a_kstrided, lda, B, b_kstrided, ldb, C, c_is_f32, ldc, M, N, K, epilogue, bias, aux, ldaux, C2, accumulate, workspace,
-                   workspace_bytes, nullptr, stream);
+  GemmCall c{A, a_kstrided, lda, B, b_kstrided, ldb, C, c_is_f32, ldc, M, N, K};
+  c.epilogue = epilogue; c.bias = bias; c.aux = aux; c.ldaux = ldaux; c.C2 = C2; c.accumulate = accumulate;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  return gemm_core(c, stream);
 }
 
 // IA_EPI_BIAS GEMM (k-contiguous operands, bf16 output) whose first scaled_cols columns (a multiple of 128) are multiplied by col_scale
 // after the bias: the fused QKV projection of the encoder layers, q leaving as q * softmax scale * log2 e (GemmArgs::qcols)
 extern "C" int ia_gemm_bf16_qscale(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int M, int N, int K, const float* bias,
                                    int scaled_cols, float col_scale, hipStream_t stream) {
-  return gemm_core(A, 0, lda, B, 0, ldb, C, 0, ldc, M, N, K, EPI_BIAS, bias, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, stream, scaled_cols,
-                   col_scale);
+  return ia_gemm_fwd_filtered(A, lda, B, ldb, C, ldc, M, N, K, EPI_BIAS, bias, nullptr, 0, nullptr, scaled_cols, col_scale, IaRowFilter{}, stream);
 }
 
 // ---- data gradient over the live 32-row blocks only
@@ -2362,81 +2391,196 @@ extern "C" int ia_row_groups_packed_host(const uint8_t* row_live, int M_rows, in
   list[0] = 4 * (pack_rows(n) + cut_rows); list[1] = n_dead; list[2] = nb;
   return IA_OK;
 }
+// ---- the liveness masks of the weight gradients
+// bit t of a mask = OR of row_live over rows ROWS t .. ROWS t + ROWS - 1 (clipped to M).  ROWS = 64: the k-tiles (ia_ktile_mask); 32: the
+// 32-row blocks of k (ia_kblock_mask).  One function for the device kernels and the host entries.
+template <int ROWS>
+static __host__ __device__ inline uint32_t rows_live(const uint8_t* row_live, int M, int t) {
+  const uint8_t* r = row_live + (size_t)t * ROWS;
+  const int n = M - t * ROWS < ROWS ? M - t * ROWS : ROWS;
+  uint64_t any = 0;
+  if (n == ROWS && ((uintptr_t)r & 7) == 0) {
+    for (int i = 0; i < ROWS / 8; ++i) any |= reinterpret_cast<const uint64_t*>(r)[i];
+  } else {
+    for (int i = 0; i < n; ++i) any |= r[i];
+  }
+  return any != 0 ? 1u : 0u;
+}
+namespace {
+// one thread per bit, one 64-bit ballot per wave = two whole mask words, stored by lanes 0 and 32 (plain stores, no atomics)
+__global__ __launch_bounds__(256) void ktile_mask_kernel(const uint8_t* __restrict__ row_live, int M, int nk, uint32_t* __restrict__ mask) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  const uint64_t b = __ballot(t < nk && rows_live<BK>(row_live, M, t));
+  if ((threadIdx.x & 31) == 0 && t < nk) mask[t >> 5] = (uint32_t)(b >> (threadIdx.x & 32));
+}
+__global__ __launch_bounds__(256) void kblock_mask_kernel(const uint8_t* __restrict__ row_live, int M, int nb, uint32_t* __restrict__ mask) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  const uint64_t v = __ballot(b < nb && rows_live<32>(row_live, M, b));
+  if ((threadIdx.x & 31) == 0 && b < nb) mask[b >> 5] = (uint32_t)(v >> (threadIdx.x & 32));
+}
+template <int ROWS>
+size_t live_mask_bytes(int M) { return M <= 0 ? 0 : (size_t)(((M + ROWS - 1) / ROWS + 31) / 32) * sizeof(uint32_t); }
+template <int ROWS>
+int live_mask(const uint8_t* row_live, int M, uint32_t* mask, hipStream_t stream) {
+  (void)hipGetLastError();
+  if (!row_live || !mask || M <= 0) return IA_ERR_ARG;
+  const int nbits = (M + ROWS - 1) / ROWS;
+  hipLaunchKernelGGL((ROWS == BK ? ktile_mask_kernel : kblock_mask_kernel), dim3((nbits + 255) / 256), dim3(256), 0, stream, row_live, M, nbits, mask);
+  return ia_check_launch();
+}
+template <int ROWS>
+int live_mask_host(const uint8_t* row_live, int M, uint32_t* mask) {
+  if (!row_live || !mask || M <= 0) return IA_ERR_ARG;
+  const int nbits = (M + ROWS - 1) / ROWS;
+  for (int w = 0; w < (nbits + 31) / 32; ++w) mask[w] = 0u;
+  for (int t = 0; t < nbits; ++t) mask[t >> 5] |= rows_live<ROWS>(row_live, M, t) << (t & 31);
+  return IA_OK;
+}
+}  // namespace
+extern "C" size_t ia_ktile_mask_bytes(int M_rows) { return live_mask_bytes<BK>(M_rows); }
+extern "C" int ia_ktile_mask(const uint8_t* row_live, int M_rows, uint32_t* mask, hipStream_t stream) { return live_mask<BK>(row_live, M_rows, mask, stream); }
+extern "C" int ia_ktile_mask_host(const uint8_t* row_live, int M_rows, uint32_t* mask) { return live_mask_host<BK>(row_live, M_rows, mask); }
+extern "C" size_t ia_kblock_mask_bytes(int M_rows) { return live_mask_bytes<32>(M_rows); }
+extern "C" int ia_kblock_mask(const uint8_t* row_live, int M_rows, uint32_t* mask, hipStream_t stream) { return live_mask<32>(row_live, M_rows, mask, stream); }
+extern "C" int ia_kblock_mask_host(const uint8_t* row_live, int M_rows, uint32_t* mask) { return live_mask_host<32>(row_live, M_rows, mask); }
+
+// ---- one descriptor for all of them (IaRowFilter, common.h): the list of a kind, by size and by builder
+size_t ia_row_filter_bytes(IaRowFilter::Kind kind, int M) {
+  switch (kind) {
+    case IaRowFilter::BLOCKS: return ia_row_blocks_bytes(M);
+    case IaRowFilter::GROUPS: return ia_row_groups_bytes(M);
+    case IaRowFilter::PACKED: return ia_row_groups_packed_bytes(M);
+    case IaRowFilter::SLABS: return ia_row_slabs_bytes(M);
+    case IaRowFilter::KTILES: return ia_ktile_mask_bytes(M);
+    case IaRowFilter::KBLOCKS: return ia_kblock_mask_bytes(M);
+    case IaRowFilter::NONE: break;
+  }
+  return 0;
+}
+int ia_row_filter_build(IaRowFilter::Kind kind, const uint8_t* row_live, int M, void* dst, hipStream_t stream) {
+  switch (kind) {
+    case IaRowFilter::BLOCKS: return ia_row_blocks(row_live, M, (int*)dst, stream);
+    case IaRowFilter::GROUPS: return ia_row_groups(row_live, M, (int*)dst, stream);
+    case IaRowFilter::PACKED: return ia_row_groups_packed(row_live, M, (int*)dst, stream);
+    case IaRowFilter::SLABS: return ia_row_slabs(row_live, M, (int*)dst, stream);
+    case IaRowFilter::KTILES: return ia_ktile_mask(row_live, M, (uint32_t*)dst, stream);
+    case IaRowFilter::KBLOCKS: return ia_kblock_mask(row_live, M, (uint32_t*)dst, stream);
+    case IaRowFilter::NONE: break;
+  }
+  return IA_ERR_ARG;
+}
+
+// ---- the filtered GEMMs.  Which (kind, epilogue) pairs have a kernel form is stated HERE, once per direction; every entry below asks.
+bool ia_gemm_fwd_form(IaRowFilter::Kind kind, int e) {
+  switch (kind) {
+    case IaRowFilter::NONE: return true;
+    case IaRowFilter::BLOCKS: return e == EPI_NONE || e == EPI_BIAS || e == EPI_BIAS_GELU || e == EPI_BIAS_GELU_ACT || e == EPI_BIAS_ADD;
+    case IaRowFilter::SLABS: return e == EPI_NONE || e == EPI_BIAS || e == EPI_BIAS_GELU;
+    default: return false;
+  }
+}
+bool ia_gemm_dgrad_form(IaRowFilter::Kind kind, int e) {
+  switch (kind) {
+    case IaRowFilter::NONE: return true;
+    case IaRowFilter::BLOCKS: return e == EPI_NONE || e == EPI_ADD || e == EPI_DGELU_CS;
+    // the column sums keep the dense kernel's partials: whole 128-row groups, or the live blocks packed by whole groups
+    case IaRowFilter::GROUPS: case IaRowFilter::PACKED: return e == EPI_DGELU_CS;
+    case IaRowFilter::SLABS: return e == EPI_NONE || e == EPI_ADD;
+    default: return false;
+  }
+}
+int ia_gemm_fwd_filtered(const void* X, int ldx, const void* W, int ldw, void* Y, int ldy, int M_rows, int N_out, int K_in, int epilogue,
+                         const float* bias, const void* aux, int ldaux, void* C2, int scaled_cols, float col_scale, IaRowFilter filter,
+                         hipStream_t stream) {
+  if (!ia_gemm_fwd_form(filter.kind, epilogue)) return IA_ERR_UNSUPPORTED;
+  GemmCall c{X, 0, ldx, W, 0, ldw, Y, 0, ldy, M_rows, N_out, K_in};
+  c.epilogue = epilogue; c.bias = bias; c.aux = aux; c.ldaux = ldaux; c.C2 = C2; c.qcols = scaled_cols; c.qscale = col_scale; c.filter = filter;
+  return gemm_core(c, stream);
+}
+int ia_gemm_dgrad_filtered(const void* dY, int ldy, const void* W, int w_kstrided, int ldw, void* dX, int ldx, int M_rows, int N_in, int K_out,
+                           int epilogue, const void* aux, int ldaux, void* C2, IaRowFilter filter, void* workspace, size_t workspace_bytes,
+                           hipStream_t stream) {
+  if (!ia_gemm_dgrad_form(filter.kind, epilogue)) return IA_ERR_UNSUPPORTED;
+  GemmCall c{dY, 0, ldy, W, w_kstrided, ldw, dX, 0, ldx, M_rows, N_in, K_out};
+  c.epilogue = epilogue; c.aux = aux; c.ldaux = ldaux; c.C2 = C2; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  c.filter = filter; c.filter.fill = true;      // not every consumer of a data gradient filters its rows
+  return gemm_core(c, stream);
+}
+int ia_gemm_wgrad_filtered(const void* dY, int ldy, const void* X, int ldx, float* dW, int ldw, int N_out, int N_in, int M_rows, IaRowFilter filter,
+                           int accumulate, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  if (filter.kind != IaRowFilter::NONE && filter.kind != IaRowFilter::KTILES && filter.kind != IaRowFilter::KBLOCKS) return IA_ERR_UNSUPPORTED;
+  GemmCall c{dY, 1, ldy, X, 1, ldx, dW, 1, ldw, N_out, N_in, M_rows};
+  c.accumulate = accumulate; c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.filter = filter;
+  return gemm_core(c, stream);
+}
 // The x gelu' + column-sums data gradient over a block-packed list: dX = (dY W) * aux on the live 32-row blocks, the other rows as zeros, and
 // C2 += the column sums, bit-identical to ia_gemm_bf16's (IA_EPI_DGELU_COLSUM) on a dY whose rows are zero wherever the list has no block.
 // A shape the remapped kernel does not serve runs every row.
 extern "C" int ia_gemm_dgrad_packed(const void* dY, int ldy, const void* W, int w_kstrided, int ldw, void* dX, int ldx, int M_rows, int N_in, int K_out,
                                     const void* aux, int ldaux, void* C2, const int* packed_list, void* workspace, size_t workspace_bytes,
                                     hipStream_t stream) {
-  return gemm_core(dY, 0, ldy, W, w_kstrided, ldw, dX, 0, ldx, M_rows, N_in, K_out, EPI_DGELU_CS, nullptr, aux, ldaux, C2, 0, workspace,
-                   workspace_bytes, nullptr, stream, 0, 1.f, nullptr, packed_list, 1, 0, packed_list ? 2 : 0);
+  return ia_gemm_dgrad_filtered(dY, ldy, W, w_kstrided, ldw, dX, ldx, M_rows, N_in, K_out, EPI_DGELU_CS, aux, ldaux, C2,
+                                IaRowFilter{IaRowFilter::PACKED, packed_list}, workspace, workspace_bytes, stream);
 }
-// library-internal (common.h): the data gradient with a list already built (ia_layer_bwd2 builds one per call for its four)
-int ia_gemm_dgrad_blocks(const void* dY, int ldy, const void* W, int w_kstrided, int ldw, void* dX, int ldx, int M_rows, int N_in, int K_out,
-                         int epilogue, const void* aux, int ldaux, void* C2, const int* row_blocks, void* workspace, size_t workspace_bytes,
-                         hipStream_t stream) {
-  if (epilogue != EPI_NONE && epilogue != EPI_ADD && epilogue != EPI_DGELU_CS) return IA_ERR_UNSUPPORTED;
-  return gemm_core(dY, 0, ldy, W, w_kstrided, ldw, dX, 0, ldx, M_rows, N_in, K_out, epilogue, nullptr, aux, ldaux, C2, 0, workspace,
-                   workspace_bytes, nullptr, stream, 0, 1.f, nullptr, row_blocks);
+// the weight gradient over the live 32-row blocks of a prebuilt ia_kblock_mask (NULL: every row)
+extern "C" int ia_gemm_wgrad_blocks(const void* dY, int ldy, const void* X, int ldx, float* dW, int ldw, int N_out, int N_in, int M_rows,
+                                    const uint32_t* kblock_mask, int accumulate, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  return ia_gemm_wgrad_filtered(dY, ldy, X, ldx, dW, ldw, N_out, N_in, M_rows, IaRowFilter{IaRowFilter::KBLOCKS, kblock_mask}, accumulate, workspace,
+                                workspace_bytes, stream);
 }
-// library-internal (common.h): a forward GEMM Y = X W^T (+ epilogue) with a list already built (layer_forward: one list, four GEMMs)
-int ia_gemm_fwd_blocks(const void* X, int ldx, const void* W, int ldw, void* Y, int ldy, int M_rows, int N_out, int K_in, int epilogue,
-                       const float* bias, void* C2, int scaled_cols, float col_scale, const int* row_blocks, int fill_dead_rows, hipStream_t stream) {
-  if (epilogue != EPI_NONE && epilogue != EPI_BIAS && epilogue != EPI_BIAS_GELU && epilogue != EPI_BIAS_GELU_ACT) return IA_ERR_UNSUPPORTED;
-  return gemm_core(X, 0, ldx, W, 0, ldw, Y, 0, ldy, M_rows, N_out, K_in, epilogue, bias, nullptr, 0, C2, 0, nullptr, 0, nullptr, stream, scaled_cols,
-                   col_scale, nullptr, row_blocks, fill_dead_rows);
-}
-// library-internal (common.h): the x gelu' + column-sums data gradient over the live 128-row groups (a list ia_row_groups built): the
-// column-sum partials land where the dense kernel puts them, so C2 is bit-identical to the unfiltered call's on rows that keep the contract
-int ia_gemm_dgrad_groups(const void* dY, int ldy, const void* W, int w_kstrided, int ldw, void* dX, int ldx, int M_rows, int N_in, int K_out,
-                         const void* aux, int ldaux, void* C2, const int* row_groups, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  return gemm_core(dY, 0, ldy, W, w_kstrided, ldw, dX, 0, ldx, M_rows, N_in, K_out, EPI_DGELU_CS, nullptr, aux, ldaux, C2, 0, workspace,
-                   workspace_bytes, nullptr, stream, 0, 1.f, nullptr, row_groups, 1, 0, 1);
-}
-// library-internal (common.h): Y = X W^T + bias + aux over the live 32-row blocks (the fc2 of a pre-LN layer, bias + residual)
-int ia_gemm_fwd_blocks_add(const void* X, int ldx, const void* W, int ldw, void* Y, int ldy, int M_rows, int N_out, int K_in, const float* bias,
-                           const void* aux, int ldaux, const int* row_blocks, int fill_dead_rows, hipStream_t stream) {
-  return gemm_core(X, 0, ldx, W, 0, ldw, Y, 0, ldy, M_rows, N_out, K_in, EPI_BIAS_ADD, bias, aux, ldaux, nullptr, 0, nullptr, 0, nullptr, stream, 0, 1.f,
-                   nullptr, row_blocks, fill_dead_rows);
-}
-extern "C" int ia_gemm_fwd_rows_add(const void* X, int ldx, const void* W, int ldw, void* Y, int ldy, int M_rows, int N_out, int K_in,
-                                    const float* bias, const void* aux, int ldaux, const uint8_t* row_live, int fill_dead_rows, void* workspace,
-                                    size_t workspace_bytes, hipStream_t stream) {
-  if (!row_live) return ia_gemm_fwd_blocks_add(X, ldx, W, ldw, Y, ldy, M_rows, N_out, K_in, bias, aux, ldaux, nullptr, 0, stream);
-  if (M_rows <= 0 || N_out <= 0 || K_in <= 0) return IA_ERR_ARG;
-  if (!workspace || workspace_bytes < ia_row_blocks_bytes(M_rows) || ((uintptr_t)workspace & 31)) return IA_ERR_WORKSPACE;
-  int rc = ia_row_blocks(row_live, M_rows, (int*)workspace, stream);
-  return rc ? rc : ia_gemm_fwd_blocks_add(X, ldx, W, ldw, Y, ldy, M_rows, N_out, K_in, bias, aux, ldaux, (const int*)workspace, fill_dead_rows, stream);
-}
-extern "C" int ia_gemm_dgrad_groups_rows(const void* dY, int ldy, const void* W, int w_kstrided, int ldw, void* dX, int ldx, int M_rows, int N_in,
-                                         int K_out, const void* aux, int ldaux, void* C2, const uint8_t* row_live, void* workspace,
-                                         size_t workspace_bytes, hipStream_t stream) {
-  if (!row_live)
-    return gemm_core(dY, 0, ldy, W, w_kstrided, ldw, dX, 0, ldx, M_rows, N_in, K_out, EPI_DGELU_CS, nullptr, aux, ldaux, C2, 0, workspace,
-                     workspace_bytes, nullptr, stream);
-  if (M_rows <= 0 || N_in <= 0 || K_out <= 0) return IA_ERR_ARG;
-  const size_t cs_bytes = al256(ia_gemm_colsum_workspace_bytes(M_rows, N_in));      // the column-sum partials in front, the list behind them
-  if (!workspace || workspace_bytes < cs_bytes + ia_row_blocks_bytes(M_rows) || ((uintptr_t)workspace & 31)) return IA_ERR_WORKSPACE;
-  int* list = reinterpret_cast<int*>((char*)workspace + cs_bytes);
-  int rc = ia_row_groups(row_live, M_rows, list, stream);
-  return rc ? rc : ia_gemm_dgrad_groups(dY, ldy, W, w_kstrided, ldw, dX, ldx, M_rows, N_in, K_out, aux, ldaux, C2, list, workspace, cs_bytes, stream);
+
+// ---- the public entries that take the rows' live bytes: build the list in the workspace, then the filtered call
+// What the seven share (rows: the token rows, n1 / n2: the GEMM's other two sizes).  Without row_live: a filter with no list (every row; the
+// GEMM keeps the caller's whole workspace).  With it: the shape is checked, the list of `kind` is carved behind the first `front` bytes of the workspace (the GEMM's own part: column-sum or
+// split-K partials) and built, and *workspace_bytes leaves as `front`.  The workspace is 32-byte aligned for a list, 16 for a mask.
+static int filter_from_rows(IaRowFilter::Kind kind, const uint8_t* row_live, int fill, int rows, int n1, int n2, size_t front, void* workspace,
+                            size_t* workspace_bytes, hipStream_t stream, IaRowFilter* filter) {
+  *filter = IaRowFilter{kind, nullptr, fill != 0};
+  if (!row_live) return IA_OK;
+  if (rows <= 0 || n1 <= 0 || n2 <= 0) return IA_ERR_ARG;
+  const uintptr_t align = (kind == IaRowFilter::KTILES || kind == IaRowFilter::KBLOCKS) ? 15 : 31;
+  if (!workspace || *workspace_bytes < front + ia_row_filter_bytes(kind, rows) || ((uintptr_t)workspace & align)) return IA_ERR_WORKSPACE;
+  void* const list = (char*)workspace + front;
+  filter->list = list;
+  *workspace_bytes = front;
+  return ia_row_filter_build(kind, row_live, rows, list, stream);
 }
 extern "C" size_t ia_gemm_fwd_rows_workspace_bytes(int M_rows) { return ia_row_blocks_bytes(M_rows); }
+extern "C" size_t ia_gemm_slabs_workspace_bytes(int M_rows) { return ia_row_slabs_bytes(M_rows); }
 // 1: a call of this shape (rows contiguous: ldx = K_in, ldy = N_out) with row_live computes the live 32-row blocks only; 0: every row
 extern "C" int ia_gemm_fwd_rows_filters(int M_rows, int N_out, int K_in) {
   if (M_rows <= 0 || N_out <= 0 || K_in <= 0 || (K_in & 7) || (N_out & 7)) return 0;
   return make_plan(M_rows, N_out, K_in, false).big && dgrad_rows_fit(M_rows, K_in, N_out, 0) ? 1 : 0;
 }
+// ia_gemm_fwd_rows (32-row blocks) and ia_gemm_fwd_slabs (8-row slabs)
+static int gemm_fwd_rows(IaRowFilter::Kind kind, const void* X, int ldx, const void* W, int ldw, void* Y, int ldy, int M_rows, int N_out, int K_in,
+                         int epilogue, const float* bias, void* C2, int scaled_cols, float col_scale, const uint8_t* row_live, int fill_dead_rows,
+                         void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  // (IA_EPI_BIAS_ADD needs an aux these two have no argument for: ia_gemm_fwd_rows_add)
+  if (epilogue == EPI_BIAS_ADD || !ia_gemm_fwd_form(kind, epilogue)) return IA_ERR_UNSUPPORTED;
+  IaRowFilter f;
+  int rc = filter_from_rows(kind, row_live, fill_dead_rows, M_rows, N_out, K_in, 0, workspace, &workspace_bytes, stream, &f);
+  return rc ? rc : ia_gemm_fwd_filtered(X, ldx, W, ldw, Y, ldy, M_rows, N_out, K_in, epilogue, bias, nullptr, 0, C2, scaled_cols, col_scale, f, stream);
+}
 extern "C" int ia_gemm_fwd_rows(const void* X, int ldx, const void* W, int ldw, void* Y, int ldy, int M_rows, int N_out, int K_in, int epilogue,
                                 const float* bias, void* C2, int scaled_cols, float col_scale, const uint8_t* row_live, int fill_dead_rows,
                                 void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  if (epilogue != EPI_NONE && epilogue != EPI_BIAS && epilogue != EPI_BIAS_GELU && epilogue != EPI_BIAS_GELU_ACT) return IA_ERR_UNSUPPORTED;
-  if (!row_live) return ia_gemm_fwd_blocks(X, ldx, W, ldw, Y, ldy, M_rows, N_out, K_in, epilogue, bias, C2, scaled_cols, col_scale, nullptr, 0, stream);
-  if (M_rows <= 0 || N_out <= 0 || K_in <= 0) return IA_ERR_ARG;
-  if (!workspace || workspace_bytes < ia_row_blocks_bytes(M_rows) || ((uintptr_t)workspace & 31)) return IA_ERR_WORKSPACE;
-  int rc = ia_row_blocks(row_live, M_rows, (int*)workspace, stream);
-  return rc ? rc : ia_gemm_fwd_blocks(X, ldx, W, ldw, Y, ldy, M_rows, N_out, K_in, epilogue, bias, C2, scaled_cols, col_scale, (const int*)workspace,
-                                      fill_dead_rows, stream);
+  return gemm_fwd_rows(IaRowFilter::BLOCKS, X, ldx, W, ldw, Y, ldy, M_rows, N_out, K_in, epilogue, bias, C2, scaled_cols, col_scale, row_live,
+                       fill_dead_rows, workspace, workspace_bytes, stream);
+}
+extern "C" int ia_gemm_fwd_slabs(const void* X, int ldx, const void* W, int ldw, void* Y, int ldy, int M_rows, int N_out, int K_in, int epilogue,
+                                 const float* bias, void* C2, int scaled_cols, float col_scale, const uint8_t* row_live, int fill_dead_rows,
+                                 void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  return gemm_fwd_rows(IaRowFilter::SLABS, X, ldx, W, ldw, Y, ldy, M_rows, N_out, K_in, epilogue, bias, C2, scaled_cols, col_scale, row_live,
+                       fill_dead_rows, workspace, workspace_bytes, stream);
+}
+// Y = X W^T + bias + aux over the live 32-row blocks (the fc2 of a pre-LN layer, bias + residual)
+extern "C" int ia_gemm_fwd_rows_add(const void* X, int ldx, const void* W, int ldw, void* Y, int ldy, int M_rows, int N_out, int K_in,
+                                    const float* bias, const void* aux, int ldaux, const uint8_t* row_live, int fill_dead_rows, void* workspace,
+                                    size_t workspace_bytes, hipStream_t stream) {
+  IaRowFilter f;
+  int rc = filter_from_rows(IaRowFilter::BLOCKS, row_live, fill_dead_rows, M_rows, N_out, K_in, 0, workspace, &workspace_bytes, stream, &f);
+  return rc ? rc : ia_gemm_fwd_filtered(X, ldx, W, ldw, Y, ldy, M_rows, N_out, K_in, EPI_BIAS_ADD, bias, aux, ldaux, nullptr, 0, 1.f, f, stream);
 }
 extern "C" size_t ia_gemm_dgrad_rows_workspace_bytes(int M_rows, int N_in, int K_out) {
   if (M_rows <= 0 || N_in <= 0 || K_out <= 0) return 0;
@@ -2448,149 +2592,35 @@ extern "C" int ia_gemm_dgrad_rows_filters(int M_rows, int N_in, int K_out) {
   if (M_rows <= 0 || N_in <= 0 || K_out <= 0 || (K_out & 7)) return 0;
   return make_plan(M_rows, N_in, K_out, false).big && dgrad_rows_fit(M_rows, K_out, N_in, N_in) ? 1 : 0;
 }
+// ia_gemm_dgrad_rows (32-row blocks), ia_gemm_dgrad_groups_rows (128-row groups) and ia_gemm_dgrad_slabs (8-row slabs).  The two with
+// column sums keep those partials in front of the workspace and the list behind them; the slab form has no workspace of the GEMM's own.
+static int gemm_dgrad_rows(IaRowFilter::Kind kind, const void* dY, int ldy, const void* W, int w_kstrided, int ldw, void* dX, int ldx, int M_rows,
+                           int N_in, int K_out, int epilogue, const void* aux, int ldaux, void* C2, const uint8_t* row_live, void* workspace,
+                           size_t workspace_bytes, hipStream_t stream) {
+  if (!ia_gemm_dgrad_form(kind, epilogue)) return IA_ERR_UNSUPPORTED;
+  const size_t front = kind == IaRowFilter::SLABS ? 0 : al256(ia_gemm_colsum_workspace_bytes(M_rows, N_in));
+  IaRowFilter f;
+  int rc = filter_from_rows(kind, row_live, 1, M_rows, N_in, K_out, front, workspace, &workspace_bytes, stream, &f);
+  return rc ? rc : ia_gemm_dgrad_filtered(dY, ldy, W, w_kstrided, ldw, dX, ldx, M_rows, N_in, K_out, epilogue, aux, ldaux, C2, f, workspace,
+                                          workspace_bytes, stream);
+}
 extern "C" int ia_gemm_dgrad_rows(const void* dY, int ldy, const void* W, int w_kstrided, int ldw, void* dX, int ldx, int M_rows, int N_in,
                                   int K_out, int epilogue, const void* aux, int ldaux, void* C2, const uint8_t* row_live, void* workspace,
                                   size_t workspace_bytes, hipStream_t stream) {
-  if (epilogue != EPI_NONE && epilogue != EPI_ADD && epilogue != EPI_DGELU_CS) return IA_ERR_UNSUPPORTED;
-  if (!row_live)
-    return gemm_core(dY, 0, ldy, W, w_kstrided, ldw, dX, 0, ldx, M_rows, N_in, K_out, epilogue, nullptr, aux, ldaux, C2, 0, workspace,
-                     workspace_bytes, nullptr, stream);
-  if (M_rows <= 0 || N_in <= 0 || K_out <= 0) return IA_ERR_ARG;
-  // the column-sum partials in front, the block list behind them
-  const size_t cs_bytes = al256(ia_gemm_colsum_workspace_bytes(M_rows, N_in));
-  if (!workspace || workspace_bytes < cs_bytes + ia_row_blocks_bytes(M_rows) || ((uintptr_t)workspace & 31)) return IA_ERR_WORKSPACE;
-  int* list = reinterpret_cast<int*>((char*)workspace + cs_bytes);
-  int rc = ia_row_blocks(row_live, M_rows, list, stream);
-  return rc ? rc : ia_gemm_dgrad_blocks(dY, ldy, W, w_kstrided, ldw, dX, ldx, M_rows, N_in, K_out, epilogue, aux, ldaux, C2, list, workspace,
-                                        cs_bytes, stream);
+  return gemm_dgrad_rows(IaRowFilter::BLOCKS, dY, ldy, W, w_kstrided, ldw, dX, ldx, M_rows, N_in, K_out, epilogue, aux, ldaux, C2, row_live, workspace,
+                         workspace_bytes, stream);
 }
-
-// ---- the same over the live 8-row slabs (EPI_SLABS)
-// library-internal (common.h): with a slab list already built (the layer calls: one list per step or call, seven GEMMs)
-int ia_gemm_fwd_slab_list(const void* X, int ldx, const void* W, int ldw, void* Y, int ldy, int M_rows, int N_out, int K_in, int epilogue,
-                          const float* bias, void* C2, int scaled_cols, float col_scale, const int* row_slabs, int fill_dead_rows, hipStream_t stream) {
-  if (epilogue != EPI_NONE && epilogue != EPI_BIAS && epilogue != EPI_BIAS_GELU) return IA_ERR_UNSUPPORTED;
-  return gemm_core(X, 0, ldx, W, 0, ldw, Y, 0, ldy, M_rows, N_out, K_in, epilogue, bias, nullptr, 0, C2, 0, nullptr, 0, nullptr, stream, scaled_cols,
-                   col_scale, nullptr, row_slabs, fill_dead_rows, 0, 0, 0, 1);
-}
-int ia_gemm_dgrad_slab_list(const void* dY, int ldy, const void* W, int w_kstrided, int ldw, void* dX, int ldx, int M_rows, int N_in, int K_out,
-                            int epilogue, const void* aux, int ldaux, const int* row_slabs, hipStream_t stream) {
-  if (epilogue != EPI_NONE && epilogue != EPI_ADD) return IA_ERR_UNSUPPORTED;
-  return gemm_core(dY, 0, ldy, W, w_kstrided, ldw, dX, 0, ldx, M_rows, N_in, K_out, epilogue, nullptr, aux, ldaux, nullptr, 0, nullptr, 0, nullptr, stream,
-                   0, 1.f, nullptr, row_slabs, 1, 0, 0, 0, 1);
-}
-extern "C" size_t ia_gemm_slabs_workspace_bytes(int M_rows) { return ia_row_slabs_bytes(M_rows); }
-extern "C" int ia_gemm_fwd_slabs(const void* X, int ldx, const void* W, int ldw, void* Y, int ldy, int M_rows, int N_out, int K_in, int epilogue,
-                                 const float* bias, void* C2, int scaled_cols, float col_scale, const uint8_t* row_live, int fill_dead_rows,
-                                 void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  if (epilogue != EPI_NONE && epilogue != EPI_BIAS && epilogue != EPI_BIAS_GELU) return IA_ERR_UNSUPPORTED;
-  if (!row_live) return ia_gemm_fwd_slab_list(X, ldx, W, ldw, Y, ldy, M_rows, N_out, K_in, epilogue, bias, C2, scaled_cols, col_scale, nullptr, 0, stream);
-  if (M_rows <= 0 || N_out <= 0 || K_in <= 0) return IA_ERR_ARG;
-  if (!workspace || workspace_bytes < ia_row_slabs_bytes(M_rows) || ((uintptr_t)workspace & 31)) return IA_ERR_WORKSPACE;
-  int rc = ia_row_slabs(row_live, M_rows, (int*)workspace, stream);
-  return rc ? rc : ia_gemm_fwd_slab_list(X, ldx, W, ldw, Y, ldy, M_rows, N_out, K_in, epilogue, bias, C2, scaled_cols, col_scale, (const int*)workspace,
-                                         fill_dead_rows, stream);
+extern "C" int ia_gemm_dgrad_groups_rows(const void* dY, int ldy, const void* W, int w_kstrided, int ldw, void* dX, int ldx, int M_rows, int N_in,
+                                         int K_out, const void* aux, int ldaux, void* C2, const uint8_t* row_live, void* workspace,
+                                         size_t workspace_bytes, hipStream_t stream) {
+  return gemm_dgrad_rows(IaRowFilter::GROUPS, dY, ldy, W, w_kstrided, ldw, dX, ldx, M_rows, N_in, K_out, EPI_DGELU_CS, aux, ldaux, C2, row_live,
+                         workspace, workspace_bytes, stream);
 }
 extern "C" int ia_gemm_dgrad_slabs(const void* dY, int ldy, const void* W, int w_kstrided, int ldw, void* dX, int ldx, int M_rows, int N_in,
                                    int K_out, int epilogue, const void* aux, int ldaux, const uint8_t* row_live, void* workspace,
                                    size_t workspace_bytes, hipStream_t stream) {
-  if (epilogue != EPI_NONE && epilogue != EPI_ADD) return IA_ERR_UNSUPPORTED;
-  if (!row_live) return ia_gemm_dgrad_slab_list(dY, ldy, W, w_kstrided, ldw, dX, ldx, M_rows, N_in, K_out, epilogue, aux, ldaux, nullptr, stream);
-  if (M_rows <= 0 || N_in <= 0 || K_out <= 0) return IA_ERR_ARG;
-  if (!workspace || workspace_bytes < ia_row_slabs_bytes(M_rows) || ((uintptr_t)workspace & 31)) return IA_ERR_WORKSPACE;
-  int rc = ia_row_slabs(row_live, M_rows, (int*)workspace, stream);
-  return rc ? rc : ia_gemm_dgrad_slab_list(dY, ldy, W, w_kstrided, ldw, dX, ldx, M_rows, N_in, K_out, epilogue, aux, ldaux, (const int*)workspace, stream);
-}
-
-// ---- weight gradient over the live rows only
-// bit t of the mask = OR of row_live over rows 64t .. 64t+63 (clipped to M).  One function for the device kernel and the host entry.
-static __host__ __device__ inline uint32_t ktile_live(const uint8_t* row_live, int M, int t) {
-  const uint8_t* r = row_live + (size_t)t * BK;
-  const int n = M - t * BK < BK ? M - t * BK : BK;
-  uint64_t any = 0;
-  if (n == BK && ((uintptr_t)r & 7) == 0) {
-    for (int i = 0; i < BK / 8; ++i) any |= reinterpret_cast<const uint64_t*>(r)[i];
-  } else {
-    for (int i = 0; i < n; ++i) any |= r[i];
-  }
-  return any != 0 ? 1u : 0u;
-}
-namespace {
-// one thread per k-tile, one 64-bit ballot per wave = two whole mask words, stored by lanes 0 and 32 (plain stores, no atomics)
-__global__ __launch_bounds__(256) void ktile_mask_kernel(const uint8_t* __restrict__ row_live, int M, int nk, uint32_t* __restrict__ mask) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  const uint64_t b = __ballot(t < nk && ktile_live(row_live, M, t));
-  if ((threadIdx.x & 31) == 0 && t < nk) mask[t >> 5] = (uint32_t)(b >> (threadIdx.x & 32));
-}
-}  // namespace
-
-extern "C" size_t ia_ktile_mask_bytes(int M_rows) {
-  if (M_rows <= 0) return 0;
-  return (size_t)(((M_rows + BK - 1) / BK + 31) / 32) * sizeof(uint32_t);
-}
-extern "C" int ia_ktile_mask(const uint8_t* row_live, int M_rows, uint32_t* mask, hipStream_t stream) {
-  (void)hipGetLastError();
-  if (!row_live || !mask || M_rows <= 0) return IA_ERR_ARG;
-  const int nk = (M_rows + BK - 1) / BK;
-  hipLaunchKernelGGL(ktile_mask_kernel, dim3((nk + 255) / 256), dim3(256), 0, stream, row_live, M_rows, nk, mask);
-  return ia_check_launch();
-}
-extern "C" int ia_ktile_mask_host(const uint8_t* row_live, int M_rows, uint32_t* mask) {
-  if (!row_live || !mask || M_rows <= 0) return IA_ERR_ARG;
-  const int nk = (M_rows + BK - 1) / BK;
-  for (int w = 0; w < (nk + 31) / 32; ++w) mask[w] = 0u;
-  for (int t = 0; t < nk; ++t) mask[t >> 5] |= ktile_live(row_live, M_rows, t) << (t & 31);
-  return IA_OK;
-}
-// ---- the same at 32-row granularity: bit b of the mask = OR of row_live over rows 32b .. 32b+31 (clipped to M)
-static __host__ __device__ inline uint32_t kblock_live(const uint8_t* row_live, int M, int b) {
-  const uint8_t* r = row_live + (size_t)b * 32;
-  const int n = M - b * 32 < 32 ? M - b * 32 : 32;
-  uint64_t any = 0;
-  if (n == 32 && ((uintptr_t)r & 7) == 0) {
-    for (int i = 0; i < 4; ++i) any |= reinterpret_cast<const uint64_t*>(r)[i];
-  } else {
-    for (int i = 0; i < n; ++i) any |= r[i];
-  }
-  return any != 0 ? 1u : 0u;
-}
-namespace {
-// one thread per block, one 64-bit ballot per wave = two whole mask words, stored by lanes 0 and 32 (plain stores, no atomics)
-__global__ __launch_bounds__(256) void kblock_mask_kernel(const uint8_t* __restrict__ row_live, int M, int nb, uint32_t* __restrict__ mask) {
-  const int b = blockIdx.x * 256 + threadIdx.x;
-  const uint64_t v = __ballot(b < nb && kblock_live(row_live, M, b));
-  if ((threadIdx.x & 31) == 0 && b < nb) mask[b >> 5] = (uint32_t)(v >> (threadIdx.x & 32));
-}
-}  // namespace
-extern "C" size_t ia_kblock_mask_bytes(int M_rows) {
-  if (M_rows <= 0) return 0;
-  return (size_t)(((M_rows + 31) / 32 + 31) / 32) * sizeof(uint32_t);
-}
-extern "C" int ia_kblock_mask(const uint8_t* row_live, int M_rows, uint32_t* mask, hipStream_t stream) {
-  (void)hipGetLastError();
-  if (!row_live || !mask || M_rows <= 0) return IA_ERR_ARG;
-  const int nb = (M_rows + 31) / 32;
-  hipLaunchKernelGGL(kblock_mask_kernel, dim3((nb + 255) / 256), dim3(256), 0, stream, row_live, M_rows, nb, mask);
-  return ia_check_launch();
-}
-extern "C" int ia_kblock_mask_host(const uint8_t* row_live, int M_rows, uint32_t* mask) {
-  if (!row_live || !mask || M_rows <= 0) return IA_ERR_ARG;
-  const int nb = (M_rows + 31) / 32;
-  for (int w = 0; w < (nb + 31) / 32; ++w) mask[w] = 0u;
-  for (int b = 0; b < nb; ++b) mask[b >> 5] |= kblock_live(row_live, M_rows, b) << (b & 31);
-  return IA_OK;
-}
-// library-internal (common.h): the weight gradient with a mask already built (ia_layer_bwd2 builds one per call for its four)
-int ia_gemm_wgrad_masked(const void* dY, int ldy, const void* X, int ldx, float* dW, int ldw, int N_out, int N_in, int M_rows,
-                         const uint32_t* ktile_mask, int accumulate, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  return gemm_core(dY, 1, ldy, X, 1, ldx, dW, 1, ldw, N_out, N_in, M_rows, EPI_NONE, nullptr, nullptr, 0, nullptr, accumulate, workspace,
-                   workspace_bytes, nullptr, stream, 0, 1.f, ktile_mask);
-}
-// the weight gradient over the live 32-row blocks of a prebuilt ia_kblock_mask (NULL: every row)
-extern "C" int ia_gemm_wgrad_blocks(const void* dY, int ldy, const void* X, int ldx, float* dW, int ldw, int N_out, int N_in, int M_rows,
-                                    const uint32_t* kblock_mask, int accumulate, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  return gemm_core(dY, 1, ldy, X, 1, ldx, dW, 1, ldw, N_out, N_in, M_rows, EPI_NONE, nullptr, nullptr, 0, nullptr, accumulate, workspace,
-                   workspace_bytes, nullptr, stream, 0, 1.f, kblock_mask, nullptr, 1, 0, 0, kblock_mask ? 1 : 0);
+  return gemm_dgrad_rows(IaRowFilter::SLABS, dY, ldy, W, w_kstrided, ldw, dX, ldx, M_rows, N_in, K_out, epilogue, aux, ldaux, nullptr, row_live, workspace,
+                         workspace_bytes, stream);
 }
 extern "C" size_t ia_gemm_wgrad_rows_workspace_bytes(int N_out, int N_in, int M_rows) {
   if (N_out <= 0 || N_in <= 0 || M_rows <= 0) return 0;
@@ -2604,19 +2634,15 @@ extern "C" int ia_gemm_wgrad_rows_filters(int N_out, int N_in, int M_rows) {
   const int nk = (M_rows + BK - 1) / BK;
   return pl.big && (nk + pl.splits - 1) / pl.splits <= t256w::LIVE_MAX_KTILES ? 1 : 0;
 }
+// the weight gradient over the live 64-row k-tiles: the split-K partials in front of the workspace, the mask behind them
 extern "C" int ia_gemm_wgrad_rows(const void* dY, int ldy, const void* X, int ldx, float* dW, int ldw, int N_out, int N_in, int M_rows,
                                   const uint8_t* row_live, int accumulate, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  if (!row_live)
-    return gemm_core(dY, 1, ldy, X, 1, ldx, dW, 1, ldw, N_out, N_in, M_rows, EPI_NONE, nullptr, nullptr, 0, nullptr, accumulate, workspace,
-                     workspace_bytes, nullptr, stream);
-  if (N_out <= 0 || N_in <= 0 || M_rows <= 0) return IA_ERR_ARG;
-  // the split-K partials in front, the mask behind them
-  const size_t split_bytes = al256(ia_gemm_workspace_bytes(N_out, N_in, M_rows, 1));
-  if (!workspace || workspace_bytes < split_bytes + ia_ktile_mask_bytes(M_rows) || ((uintptr_t)workspace & 15)) return IA_ERR_WORKSPACE;
-  uint32_t* mask = reinterpret_cast<uint32_t*>((char*)workspace + split_bytes);
-  int rc = ia_ktile_mask(row_live, M_rows, mask, stream);
-  return rc ? rc : ia_gemm_wgrad_masked(dY, ldy, X, ldx, dW, ldw, N_out, N_in, M_rows, mask, accumulate, workspace, split_bytes, stream);
+  IaRowFilter f;
+  int rc = filter_from_rows(IaRowFilter::KTILES, row_live, 1, M_rows, N_out, N_in, al256(ia_gemm_workspace_bytes(N_out, N_in, M_rows, 1)), workspace,
+                            &workspace_bytes, stream, &f);
+  return rc ? rc : ia_gemm_wgrad_filtered(dY, ldy, X, ldx, dW, ldw, N_out, N_in, M_rows, f, accumulate, workspace, workspace_bytes, stream);
 }
+
 
 // GEMM with shifted operand views and channel groups batched into one launch (see GemmArgs): the building block of the
 // patch-matrix-free 3x3 convolution in conv.hip (library-internal, declared in common.h).
@@ -2624,8 +2650,10 @@ int ia_gemm_view(const IaViewGemm& v, hipStream_t stream) {
   if ((v.a_view && (v.a_kstrided || (v.a_view != 1 && v.a_view != -1))) || (v.b_view && (!v.b_kstrided || v.b_view < 1 || v.b_view > 2)) ||
       v.pw <= 2 || (!v.a_view && !v.b_view) || v.groups < 1 || v.lca < 3 || v.lcbk < 3 || v.lcbn < 3)
     return IA_ERR_ARG;
-  return gemm_core(v.A, v.a_kstrided, v.lda, v.B, v.b_kstrided, v.ldb, v.C, v.c_is_f32, v.ldc, v.M, v.N, v.K, v.bias ? EPI_BIAS : EPI_NONE,
-                   v.bias, nullptr, 0, v.rsum_out, 0, v.workspace, v.workspace_bytes, &v, stream);
+  GemmCall c{v.A, v.a_kstrided, v.lda, v.B, v.b_kstrided, v.ldb, v.C, v.c_is_f32, v.ldc, v.M, v.N, v.K};
+  c.epilogue = v.bias ? EPI_BIAS : EPI_NONE; c.bias = v.bias; c.C2 = v.rsum_out; c.workspace = v.workspace; c.workspace_bytes = v.workspace_bytes;
+  c.view = &v;
+  return gemm_core(c, stream);
 }
 
 size_t ia_gemm_view_workspace_bytes(int M, int N, int K, int groups) {
@@ -2648,23 +2676,23 @@ static int launch_dgelu_colsum(GemmArgs& g, bool big, float* csum, void* workspa
   return rc ? rc : ia_sum_rows_f32((const float*)workspace, ((g.M + 255) / 256) * 2, g.N, csum, 1, stream);
 }
 
-static int gemm_core(const void* A, int a_kstrided, int lda, const void* B, int b_kstrided, int ldb, void* C, int c_is_f32, int ldc, int M,
-                     int N, int K, int epilogue, const float* bias, const void* aux, int ldaux, void* C2, int accumulate, void* workspace,
-                     size_t workspace_bytes, const IaViewGemm* view, hipStream_t stream, int qcols, float qscale, const uint32_t* live_kt,
-                     const int* row_blocks, int rows_fill, int tail_of, int rows_grouped, int live_blocks, int row_slabs) {
+static int gemm_core(const GemmCall& c, hipStream_t stream) {
+  const IaViewGemm* const view = c.view;
+  const int M = c.M, N = c.N, K = c.K, epilogue = c.epilogue;
+  const bool aks = c.a_kstrided != 0, bks = c.b_kstrided != 0, f32 = c.c_is_f32 != 0;
   const uint64_t a_window = view ? view->a_window : 0, b_window = view ? view->b_window : 0;
   const int groups = view ? view->groups : 1;
   (void)hipGetLastError();  // drop stale status left by unrelated runtime calls (e.g. hipEventQuery -> NotReady)
-  if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0) return IA_ERR_ARG;
-  if ((lda & 7) || (ldb & 7) || (ldc & 3) || (N & 3)) return IA_ERR_ARG;
-  if (((uintptr_t)A & 15) || ((uintptr_t)B & 15) || ((uintptr_t)C & 15)) return IA_ERR_ARG;
+  if (!c.A || !c.B || !c.C || M <= 0 || N <= 0 || K <= 0) return IA_ERR_ARG;
+  if ((c.lda & 7) || (c.ldb & 7) || (c.ldc & 3) || (N & 3)) return IA_ERR_ARG;
+  if (((uintptr_t)c.A & 15) || ((uintptr_t)c.B & 15) || ((uintptr_t)c.C & 15)) return IA_ERR_ARG;
   GemmArgs g;
-  g.A = (const bf16*)A; g.B = (const bf16*)B; g.C = C; g.C2 = (bf16*)C2; g.bias = bias; g.aux = (const bf16*)aux;
-  g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldaux = ldaux; g.accumulate = accumulate;
-  if (qcols < 0 || qcols > N || (qcols & 127) || (qcols && (epilogue != EPI_BIAS || c_is_f32 || a_kstrided || b_kstrided))) return IA_ERR_ARG;
-  g.qcols = qcols; g.qscale = qscale;
-  const uint64_t ab = a_window ? a_window : (a_kstrided ? ((uint64_t)(K - 1) * lda + M) * 2 : ((uint64_t)(M - 1) * lda + K) * 2);
-  const uint64_t bb = b_window ? b_window : (b_kstrided ? ((uint64_t)(K - 1) * ldb + N) * 2 : ((uint64_t)(N - 1) * ldb + K) * 2);
+  g.A = (const bf16*)c.A; g.B = (const bf16*)c.B; g.C = c.C; g.C2 = (bf16*)c.C2; g.bias = c.bias; g.aux = (const bf16*)c.aux;
+  g.M = M; g.N = N; g.K = K; g.lda = c.lda; g.ldb = c.ldb; g.ldc = c.ldc; g.ldaux = c.ldaux; g.accumulate = c.accumulate;
+  if (c.qcols < 0 || c.qcols > N || (c.qcols & 127) || (c.qcols && (epilogue != EPI_BIAS || f32 || aks || bks))) return IA_ERR_ARG;
+  g.qcols = c.qcols; g.qscale = c.qscale;
+  const uint64_t ab = a_window ? a_window : (aks ? ((uint64_t)(K - 1) * c.lda + M) * 2 : ((uint64_t)(M - 1) * c.lda + K) * 2);
+  const uint64_t bb = b_window ? b_window : (bks ? ((uint64_t)(K - 1) * c.ldb + N) * 2 : ((uint64_t)(N - 1) * c.ldb + K) * 2);
   g.csum_part = nullptr; g.split_id = 0; g.tile_ctr = nullptr;
   g.a_view = g.b_view = g.pw = 0; g.lca = g.lcbk = g.lcbn = 6;
   g.groups = 1; g.ga = g.gb = g.gc = g.gbias = 0;
@@ -2672,103 +2700,110 @@ static int gemm_core(const void* A, int a_kstrided, int lda, const void* B, int 
     g.a_view = view->a_view; g.b_view = view->b_view; g.pw = view->pw; g.lca = view->lca; g.lcbk = view->lcbk; g.lcbn = view->lcbn;
     g.groups = groups; g.ga = view->ga; g.gb = view->gb; g.gc = view->gc; g.gbias = view->gbias;
   }
-  if (!a_kstrided && (K & 7)) return IA_ERR_ARG;
+  if (!aks && (K & 7)) return IA_ERR_ARG;
   g.a_bytes = ab; g.b_bytes = bb;
   g.tiles_m = g.tiles_n = 0;
   { static int dbg = -1; if (dbg < 0) { const char* e = getenv("IA_GEMM_DBG"); dbg = e ? atoi(e) : 0; } g.dbg = dbg; }
   const int nk = (K + BK - 1) / BK;
-  Plan pl = make_plan(M, N, K, c_is_f32 != 0, groups);
+  Plan pl = make_plan(M, N, K, f32, groups);
   g.splits = 1; g.nk_per_split = nk; g.ws = nullptr;
   const bool big = pl.big && !view && !(g.dbg & 128);     // the shifted views and the group batching live in the T128 kernel only (dbg 128: force T128)
   // weight-gradient form with C2: the fp32 row sums of A^T (bias gradient) come out of the same launch (T128 kernel)
-  const bool wgrad_form = a_kstrided && b_kstrided && c_is_f32 && epilogue == EPI_NONE;
-  g.rsum_out = (wgrad_form && !big) ? (float*)C2 : nullptr;
+  const bool wgrad_form = aks && bks && f32 && epilogue == EPI_NONE;
+  g.rsum_out = (wgrad_form && !big) ? (float*)c.C2 : nullptr;
   g.rsum_ws = nullptr;
   // split-K sums partial products: only the plain epilogue may be cut (a bias would be added once per k-slab -- the fp32 + bias form
   // came out with 2-8 x the bias until round 2's edge-shape test)
-  if (c_is_f32 && epilogue == EPI_NONE && pl.splits > 1 && workspace &&
-      workspace_bytes >= (size_t)groups * pl.splits * M * (N + (g.rsum_out ? 1 : 0)) * sizeof(float)) {
+  if (f32 && epilogue == EPI_NONE && pl.splits > 1 && c.workspace &&
+      c.workspace_bytes >= (size_t)groups * pl.splits * M * (N + (g.rsum_out ? 1 : 0)) * sizeof(float)) {
     g.nk_per_split = (nk + pl.splits - 1) / pl.splits;
     g.splits = (nk + g.nk_per_split - 1) / g.nk_per_split;
-    g.ws = (float*)workspace;
+    g.ws = (float*)c.workspace;
     g.rsum_ws = g.ws + (size_t)groups * g.splits * M * N;
   }
   {  // every workgroup addresses its operands through a 32-bit buffer window that starts at its tile / k-slab (rsrc_at): that
      // window -- not the tensor -- has to stay below 2 GiB
     const uint64_t margin = view ? 2 * (uint64_t)(view->pw + 1) : 0, slab = (uint64_t)g.nk_per_split * BK + margin, tile = 256 + margin;
-    const uint64_t wa = (a_kstrided ? slab : tile) * (uint64_t)lda * 2 + (a_kstrided ? 0 : (uint64_t)K * 2);
-    const uint64_t wb = (b_kstrided ? slab : tile) * (uint64_t)ldb * 2 + (b_kstrided ? 0 : (uint64_t)K * 2);
+    const uint64_t wa = (aks ? slab : tile) * (uint64_t)c.lda * 2 + (aks ? 0 : (uint64_t)K * 2);
+    const uint64_t wb = (bks ? slab : tile) * (uint64_t)c.ldb * 2 + (bks ? 0 : (uint64_t)K * 2);
     if (wa >= 0x7FFFFFF0ull || wb >= 0x7FFFFFF0ull) return IA_ERR_ARG;
   }
+  // What the filter holds: a mask of the live k (weight gradient), or a list of the live rows (the other forms).  Which (kind, epilogue)
+  // pairs exist is the business of ia_gemm_fwd_form / ia_gemm_dgrad_form; here a filter only ever falls back to every row.
+  const IaRowFilter::Kind kind = c.filter.kind;
+  const bool k_mask = kind == IaRowFilter::KTILES || kind == IaRowFilter::KBLOCKS, row_list = kind != IaRowFilter::NONE && !k_mask;
   // the live-k-tile mask: the 256-wide weight-gradient kernel only, one mask word per lane and k-slab (anything else runs dense)
   // GemmArgs::live_kt shares the slot of GemmArgs::bias (filled above from the caller's argument): in the weight-gradient form, whose
   // 256-wide kernel reads the slot as the mask, it is overwritten HERE for every caller -- a stray bias passed with IA_EPI_NONE, the
   // shifted views of ia_gemm_view -- so the kernel sees a mask or NULL, never a bias.  launch<true, true, EPI_NONE, true> is reached
   // from this function only; a new call site that fills GemmArgs for this form must do the same.
-  // (live_blocks: the mask holds 32-row blocks, two bits per k-tile of the slab -- half the slab length, else dense: a block mask cannot
+  // (KBLOCKS: the mask holds 32-row blocks, two bits per k-tile of the slab -- half the slab length, else dense: a block mask cannot
   // stand in for the 64-row one)
-  if (a_kstrided && b_kstrided && c_is_f32 && epilogue == EPI_NONE)
-    g.live_kt = (big && g.nk_per_split <= (live_blocks ? t256w::BLK_MAX_KTILES : t256w::LIVE_MAX_KTILES)) ? live_kt : nullptr;
-  // the block list of the row-remapped forms (C2 has C's pitch, so dgrad_rows_fit covers it): a list or NULL
-  const bool fwd_epi = !b_kstrided && (epilogue == EPI_BIAS || epilogue == EPI_BIAS_GELU || epilogue == EPI_BIAS_GELU_ACT || epilogue == EPI_BIAS_ADD);
-  g.row_blk = nullptr; g.rows_fill = rows_fill; g.fill_m = M; g.rows_guarded = tail_of ? 1 : 0;
-  if (!a_kstrided && !c_is_f32 && (epilogue == EPI_NONE || epilogue == EPI_ADD || epilogue == EPI_DGELU_CS || fwd_epi))
-    g.row_blk = (row_blocks && big && !g.dbg && !(N & 7) && dgrad_rows_fit(M, lda, ldc, aux ? ldaux : 0)) ? row_blocks : nullptr;
-  g.rows_grouped = (g.row_blk && epilogue == EPI_DGELU_CS && rows_grouped) ? rows_grouped : 0;
-  const bool slabs = g.row_blk && row_slabs;
-  if (slabs && epilogue != EPI_NONE && epilogue != EPI_ADD && epilogue != EPI_BIAS && epilogue != EPI_BIAS_GELU) return IA_ERR_UNSUPPORTED;
+  if (wgrad_form)
+    g.live_kt = (k_mask && big && g.nk_per_split <= (kind == IaRowFilter::KBLOCKS ? t256w::BLK_MAX_KTILES : t256w::LIVE_MAX_KTILES))
+                    ? (const uint32_t*)c.filter.list : nullptr;
+  // the list of the row-remapped forms (C2 has C's pitch, so dgrad_rows_fit covers it): a list or NULL
+  const bool fwd_epi = !bks && (epilogue == EPI_BIAS || epilogue == EPI_BIAS_GELU || epilogue == EPI_BIAS_GELU_ACT || epilogue == EPI_BIAS_ADD);
+  g.row_blk = nullptr; g.rows_fill = c.filter.fill ? 1 : 0; g.fill_m = M; g.rows_guarded = c.tail ? 1 : 0;
+  if (row_list && !aks && !f32 && (epilogue == EPI_NONE || epilogue == EPI_ADD || epilogue == EPI_DGELU_CS || fwd_epi) && big && !g.dbg && !(N & 7) &&
+      dgrad_rows_fit(M, c.lda, c.ldc, c.aux ? c.ldaux : 0))
+    g.row_blk = (const int*)c.filter.list;
+  // (GemmArgs::rows_grouped: 1 = a group-aligned list, 2 = a block-packed one; the column-sum epilogue only)
+  g.rows_grouped = (g.row_blk && epilogue == EPI_DGELU_CS) ? (kind == IaRowFilter::GROUPS ? 1 : kind == IaRowFilter::PACKED ? 2 : 0) : 0;
   // Scaled columns, M no multiple of 128: the dense kernel rounds the rows behind the last whole 128-row part of M as (acc + bias) * scale
   // (guarded row-layout epilogue) and the others as acc * scale + bias * scale (accumulator-layout epilogue).  The remap would mix the two
   // in one wave, so the remapped launch covers the whole parts and the (at most four) blocks behind them get a remapped launch of their
-  // own in front of it: one M-tile taken from the end of the live list, the row-layout epilogue in every wave (tail_of: that call,
+  // own in front of it: one M-tile taken from the end of the live list, the row-layout epilogue in every wave (GemmCall::tail: that call,
   // GemmArgs::rows_guarded).  The fill of the main launch sees every row.
-  if (g.row_blk && fwd_epi && qcols > 0 && (M & 127) && !tail_of) {
-    const int Mb = M & ~127;
-    int rc = gemm_core(A, 0, lda, B, 0, ldb, C, 0, ldc, M, N, K, epilogue, bias, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, stream, qcols, qscale, nullptr,
-                       row_blocks, 0, 1, 0, 0, row_slabs);
+  if (g.row_blk && fwd_epi && c.qcols > 0 && (M & 127) && !c.tail) {
+    GemmCall t{c.A, 0, c.lda, c.B, 0, c.ldb, c.C, 0, c.ldc, M, N, K};
+    t.epilogue = epilogue; t.bias = c.bias; t.qcols = c.qcols; t.qscale = c.qscale; t.filter = c.filter; t.filter.fill = false; t.tail = true;
+    int rc = gemm_core(t, stream);
     if (rc) return rc;
-    g.a_bytes = ((uint64_t)(Mb - 1) * lda + K) * 2;
+    const int Mb = M & ~127;
+    g.a_bytes = ((uint64_t)(Mb - 1) * c.lda + K) * 2;
     g.M = Mb;
   }
   const bool needs_bias = epilogue == EPI_BIAS || epilogue == EPI_BIAS_GELU || epilogue == EPI_BIAS_GELU_ACT || epilogue == EPI_BIAS_ADD;
   const bool needs_aux = epilogue == EPI_ADD || epilogue == EPI_DGELU || epilogue == EPI_BIAS_ADD || epilogue == EPI_DGELU_CS;
-  if (needs_bias && !bias) return IA_ERR_ARG;
-  if (needs_aux && (!aux || (ldaux & 3))) return IA_ERR_ARG;
-  if (epilogue == EPI_BIAS_GELU && !C2) return IA_ERR_ARG;
+  if (needs_bias && !c.bias) return IA_ERR_ARG;
+  if (needs_aux && (!c.aux || (c.ldaux & 3))) return IA_ERR_ARG;
+  if (epilogue == EPI_BIAS_GELU && !c.C2) return IA_ERR_ARG;
 
-  if (!a_kstrided && !b_kstrided && !c_is_f32) {
+  if (!aks && !bks && !f32) {
     switch (epilogue) {
-      case EPI_NONE: return launch<false, false, EPI_NONE, false>(g, big, stream, false, slabs);
-      case EPI_BIAS: return launch<false, false, EPI_BIAS, false>(g, big, stream, false, slabs);
-      case EPI_BIAS_GELU: return launch<false, false, EPI_BIAS_GELU, false>(g, big, stream, false, slabs);
-      case EPI_BIAS_GELU_ACT: return launch<false, false, EPI_BIAS_GELU_ACT, false>(g, big, stream);
-      case EPI_BIAS_ADD: return launch<false, false, EPI_BIAS_ADD, false>(g, big, stream);
-      case EPI_ADD: return launch<false, false, EPI_ADD, false>(g, big, stream, false, slabs);
+      case EPI_NONE: return launch<false, false, EPI_NONE, false>(g, big, stream, kind);
+      case EPI_BIAS: return launch<false, false, EPI_BIAS, false>(g, big, stream, kind);
+      case EPI_BIAS_GELU: return launch<false, false, EPI_BIAS_GELU, false>(g, big, stream, kind);
+      case EPI_BIAS_GELU_ACT: return launch<false, false, EPI_BIAS_GELU_ACT, false>(g, big, stream, kind);
+      case EPI_BIAS_ADD: return launch<false, false, EPI_BIAS_ADD, false>(g, big, stream, kind);
+      case EPI_ADD: return launch<false, false, EPI_ADD, false>(g, big, stream, kind);
       // (the data-gradient epilogues on a k-contiguous B: the transposed weight shadows of ia_layer_weights::wt_*)
       case EPI_DGELU: return launch<false, false, EPI_DGELU, false>(g, big, stream);
-      case EPI_DGELU_CS: return launch_dgelu_colsum<false>(g, big, (float*)C2, workspace, workspace_bytes, stream);
+      case EPI_DGELU_CS: return launch_dgelu_colsum<false>(g, big, (float*)c.C2, c.workspace, c.workspace_bytes, stream);
     }
-  } else if (!a_kstrided && b_kstrided && !c_is_f32) {
+  } else if (!aks && bks && !f32) {
     switch (epilogue) {
-      case EPI_NONE: return launch<false, true, EPI_NONE, false>(g, big, stream, false, slabs);
-      case EPI_ADD: return launch<false, true, EPI_ADD, false>(g, big, stream, false, slabs);
+      case EPI_NONE: return launch<false, true, EPI_NONE, false>(g, big, stream, kind);
+      case EPI_ADD: return launch<false, true, EPI_ADD, false>(g, big, stream, kind);
       case EPI_DGELU: return launch<false, true, EPI_DGELU, false>(g, big, stream);
-      case EPI_DGELU_CS: return launch_dgelu_colsum<true>(g, big, (float*)C2, workspace, workspace_bytes, stream);
+      case EPI_DGELU_CS: return launch_dgelu_colsum<true>(g, big, (float*)c.C2, c.workspace, c.workspace_bytes, stream);
     }
-  } else if (a_kstrided && b_kstrided && c_is_f32) {
+  } else if (aks && bks && f32) {
     if (epilogue == EPI_NONE) {
-      int rc = launch<true, true, EPI_NONE, true>(g, big, stream, live_blocks != 0);
+      int rc = launch<true, true, EPI_NONE, true>(g, big, stream, kind);
       // 256x256 kernel: no spare accumulators for the row sums -> the stand-alone column-sum pass over A (stream-ordered after the
       // split-K reduce, so it may reuse the workspace)
-      if (!rc && C2 && big) rc = ia_colsum(A, lda, K, M, (float*)C2, 1, workspace, workspace_bytes, stream);
+      if (!rc && c.C2 && big) rc = ia_colsum(c.A, c.lda, K, M, (float*)c.C2, 1, c.workspace, c.workspace_bytes, stream);
       return rc;
     }
-  } else if (!a_kstrided && !b_kstrided && c_is_f32) {
+  } else if (!aks && !bks && f32) {
     if (epilogue == EPI_NONE) return launch<false, false, EPI_NONE, true>(g, big, stream);
     if (epilogue == EPI_BIAS) return launch<false, false, EPI_BIAS, true>(g, big, stream);
   }
   return IA_ERR_UNSUPPORTED;
 }
+
 
 // Start recording HIP events around every launch of GEMM instantiation `variant` (at most max_launches).
 extern "C" int ia_prof_begin(int variant, int max_launches) {

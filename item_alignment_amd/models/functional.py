@@ -130,6 +130,24 @@ class EmbedLNFn(torch.autograd.Function):
 
 
 # --------------------------------------------------------------------------------------- encoder stack
+def _row_lists(lib, M, device, names, front=0):
+    """One uint8 buffer for several lists of one row mask of M rows: `front` bytes of the caller's (zeros), then the list of each name
+    (ia_<name>_bytes sizes it) on a 256-byte boundary, in order.  Returns (buffer, {name: device pointer})."""
+    offs, at = {}, front
+    for name in names:
+        at = (at + 255) & ~255
+        offs[name] = at
+        at += getattr(lib, f"ia_{name}_bytes")(M)
+    buf = torch.zeros((at + 255) & ~255, device=device, dtype=torch.uint8) if front else torch.empty(at, device=device, dtype=torch.uint8)
+    return buf, {name: buf.data_ptr() + o for name, o in offs.items()}
+
+
+def _build_row_lists(lib, mask_ptr, M, at, names):
+    """ia_<name>(mask) into at[name] for each name: one small launch each on the current stream"""
+    for name in names:
+        check(getattr(lib, f"ia_{name}")(mask_ptr, M, at[name], stream_ptr()), f"ia_{name}")
+
+
 _cls_row_lists = {}
 _CLS_ROW_LISTS_KEPT = 8      # (shape, stream) pairs: two towers, training and evaluation batch shapes
 
@@ -149,17 +167,12 @@ def cls_row_lists(B, L, device, key_mask=None):
         return _cls_row_lists[key]
     lib = _lib.load()
     M = B * L
-    al = lambda n: (n + 255) & ~255
-    o_blk = al(M)
-    o_kt = o_blk + al(lib.ia_row_blocks_bytes(M))
-    o_grp = o_kt + al(lib.ia_kblock_mask_bytes(M))
-    buf = torch.zeros(o_grp + al(lib.ia_row_groups_bytes(M)), device=device, dtype=torch.uint8)
+    names = ("row_blocks", "kblock_mask", "row_groups")
+    buf, at = _row_lists(lib, M, device, names, front=M)      # the mask in front, its lists behind it
     buf[:M:L] = 1 if key_mask is None else key_mask.reshape(-1)[::L].ne(0).to(torch.uint8)
     p = buf.data_ptr()
-    check(lib.ia_row_blocks(p, M, p + o_blk, stream_ptr()), "ia_row_blocks")
-    check(lib.ia_kblock_mask(p, M, p + o_kt, stream_ptr()), "ia_kblock_mask")
-    check(lib.ia_row_groups(p, M, p + o_grp, stream_ptr()), "ia_row_groups")
-    got = (buf, p, p + o_blk, p + o_kt, p + o_grp)
+    _build_row_lists(lib, p, M, at, names)
+    got = (buf, p) + tuple(at[name] for name in names)
     if key_mask is None and not torch.cuda.is_current_stream_capturing():
         while len(_cls_row_lists) >= _CLS_ROW_LISTS_KEPT:
             _cls_row_lists.pop(next(iter(_cls_row_lists)))
@@ -196,19 +209,16 @@ class EncoderStackFn(torch.autograd.Function):
         flag = cfgs[0].masked_rows_dead
         if key_mask is not None and cu_seqlens is None and not cfgs[0].pre_ln and ((flag & 1 and keep) or (flag & 3) == 3):
             M = cur.shape[0]
-            lb = lib.ia_row_groups_packed_offset(M)        # (= the block list's size rounded up to 256 bytes)
             packed = keep and M <= 128 * 4096              # the backward's x gelu' data gradient: the live blocks packed by whole groups
-            so = lib.ia_row_slabs_offset(M)                # (= 2 lb: the 8-row slab list behind the two block lists)
-            ko = so + (lib.ia_row_slabs_bytes(M) + 255) // 256 * 256
-            lists = torch.empty(ko + lib.ia_kblock_mask_bytes(M), device=x.device, dtype=torch.uint8)
-            check(lib.ia_row_blocks(mp, M, lists.data_ptr(), stream_ptr()), "ia_row_blocks")
-            check(lib.ia_row_slabs(mp, M, lists.data_ptr() + so, stream_ptr()), "ia_row_slabs")
-            if packed:
-                check(lib.ia_row_groups_packed(mp, M, lists.data_ptr() + lb, stream_ptr()), "ia_row_groups_packed")
-            if keep:                                       # (the weight gradients' mask: nothing reads it without a backward)
-                check(lib.ia_kblock_mask(mp, M, lists.data_ptr() + ko, stream_ptr()), "ia_kblock_mask")
+            # ia_layer_cfg finds the packed list and the 8-row slab list behind row_blocks in the same buffer
+            lists, at = _row_lists(lib, M, x.device, ("row_blocks", "row_groups_packed", "row_slabs", "kblock_mask"))
+            assert at["row_groups_packed"] - at["row_blocks"] == lib.ia_row_groups_packed_offset(M)
+            assert at["row_slabs"] - at["row_blocks"] == lib.ia_row_slabs_offset(M)
+            # (the weight gradients' mask: nothing reads it without a backward)
+            build = ("row_blocks", "row_slabs") + (("row_groups_packed",) if packed else ()) + (("kblock_mask",) if keep else ())
+            _build_row_lists(lib, mp, M, at, build)
             for c in cfgs:
-                c.row_blocks, c.live_ktiles = lists.data_ptr(), (lists.data_ptr() + ko) if keep else None
+                c.row_blocks, c.live_ktiles = at["row_blocks"], at["kblock_mask"] if keep else None
                 c.masked_rows_dead |= 32                   # ia_layer_cfg: the slab list sits behind row_blocks at ia_row_slabs_offset
                 if keep:
                     c.masked_rows_dead |= 8                # ia_layer_cfg: live_ktiles is a 32-row block mask

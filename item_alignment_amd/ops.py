@@ -60,24 +60,24 @@ def gemm(a, b, *, a_kstrided=False, b_kstrided=False, epilogue=EPI_NONE, bias=No
     return out
 
 
-def ktile_mask(row_live):
-    """bit (t & 31) of word t >> 5 = any(row_live[64t : 64t + 64]) (uint8 [M] on the GPU) -> int32 words"""
+def _row_list(name, row_live):
+    """One list or mask of the rows' live bytes (uint8 [M] on the GPU) -> int32 words: ia_<name>_bytes sizes it, ia_<name> builds it."""
     lib = _lib.load()
     _need(row_live, torch.uint8, "row_live")
     M = row_live.numel()
-    out = torch.empty(lib.ia_ktile_mask_bytes(M) // 4, device=row_live.device, dtype=torch.int32)
-    check(lib.ia_ktile_mask(row_live.data_ptr(), M, out.data_ptr(), stream_ptr()), "ia_ktile_mask")
+    out = torch.empty(getattr(lib, f"ia_{name}_bytes")(M) // 4, device=row_live.device, dtype=torch.int32)
+    check(getattr(lib, f"ia_{name}")(row_live.data_ptr(), M, out.data_ptr(), stream_ptr()), f"ia_{name}")
     return out
+
+
+def ktile_mask(row_live):
+    """bit (t & 31) of word t >> 5 = any(row_live[64t : 64t + 64]) (uint8 [M] on the GPU) -> int32 words"""
+    return _row_list("ktile_mask", row_live)
 
 
 def kblock_mask(row_live):
     """bit (b & 31) of word b >> 5 = any(row_live[32b : 32b + 32]) (uint8 [M] on the GPU) -> int32 words"""
-    lib = _lib.load()
-    _need(row_live, torch.uint8, "row_live")
-    M = row_live.numel()
-    out = torch.empty(lib.ia_kblock_mask_bytes(M) // 4, device=row_live.device, dtype=torch.int32)
-    check(lib.ia_kblock_mask(row_live.data_ptr(), M, out.data_ptr(), stream_ptr()), "ia_kblock_mask")
-    return out
+    return _row_list("kblock_mask", row_live)
 
 
 def gemm_wgrad_blocks(dy, x, mask=None, *, out=None, accumulate=False):
@@ -119,11 +119,37 @@ def gemm_wgrad_rows(dy, x, row_live=None, *, out=None, accumulate=False):
 def row_blocks(row_live):
     """The 32-row block list of ia_row_blocks (uint8 [M] on the GPU -> int32 words): [0] live count, [1] dead count, [2] blocks,
     the ascending live blocks from word 8, the ascending dead blocks from word 8 + blocks rounded up to 8."""
+    return _row_list("row_blocks", row_live)
+
+
+def row_slabs(row_live):
+    """The 8-row slab list of ia_row_slabs (uint8 [M] on the GPU -> int32 words): [0] live count, [1] dead count, [2] slabs; from word 8
+    the live slabs, 32 to a tile in the order [wave][piece] (-1 behind the last); the ascending dead slabs from word 8 + slabs rounded
+    up to 32."""
+    return _row_list("row_slabs", row_live)
+
+
+def _gemm_dgrad_filtered(unit, dy, w, row_live, w_kstrided, epilogue, aux, out, colsum_out=None):
+    """gemm_dgrad_rows (unit "rows": ia_gemm_dgrad_rows, the one with column sums) and gemm_dgrad_slabs ("slabs": ia_gemm_dgrad_slabs)"""
     lib = _lib.load()
-    _need(row_live, torch.uint8, "row_live")
-    M = row_live.numel()
-    out = torch.empty(lib.ia_row_blocks_bytes(M) // 4, device=row_live.device, dtype=torch.int32)
-    check(lib.ia_row_blocks(row_live.data_ptr(), M, out.data_ptr(), stream_ptr()), "ia_row_blocks")
+    _need(dy, BF16, "dy"); _need(w, BF16, "w"); _need(aux, BF16, "aux"); _need(row_live, torch.uint8, "row_live")
+    _need(colsum_out, F32, "colsum_out")
+    M, K = dy.shape
+    Kw, N = w.shape if w_kstrided else w.shape[::-1]
+    if K != Kw or (row_live is not None and row_live.numel() != M):
+        raise ValueError(f"gemm_dgrad_{unit}: dy, w and row_live do not fit together")
+    slabs = unit == "slabs"
+    if epilogue == EPI_DGELU_COLSUM and colsum_out is None and not slabs:
+        raise ValueError("gemm_dgrad_rows: EPI_DGELU_COLSUM needs colsum_out")
+    if out is None:
+        out = torch.empty((M, N), device=dy.device, dtype=BF16)
+    _need(out, BF16, "out")
+    ws_bytes = lib.ia_gemm_slabs_workspace_bytes(M) if slabs else lib.ia_gemm_dgrad_rows_workspace_bytes(M, N, K)
+    ws = torch.empty(ws_bytes, device=dy.device, dtype=torch.uint8)
+    c2 = () if slabs else (ptr(colsum_out),)
+    check(getattr(lib, f"ia_gemm_dgrad_{unit}")(dy.data_ptr(), K, w.data_ptr(), int(w_kstrided), w.shape[1], out.data_ptr(), N, M, N, K, epilogue,
+                                                ptr(aux), N if aux is not None else 0, *c2, ptr(row_live), ws.data_ptr(), ws_bytes,
+                                                stream_ptr()), f"ia_gemm_dgrad_{unit}")
     return out
 
 
@@ -131,23 +157,36 @@ def gemm_dgrad_rows(dy, w, row_live=None, *, w_kstrided=True, epilogue=EPI_NONE,
     """dX[M, N_in] = dy[M, K_out] W (+ EPI_NONE / EPI_ADD / EPI_DGELU_COLSUM); w: [K_out, N_in] (w_kstrided) or its transpose
     [N_in, K_out].  row_live (uint8 [M]) == 0 promises that row of dy (and of aux for EPI_ADD) is all zeros: 32-row blocks without a
     live row are skipped and written as zeros (ia_gemm_dgrad_rows).  row_live=None is gemm(dy, w, b_kstrided=w_kstrided, ...)."""
+    return _gemm_dgrad_filtered("rows", dy, w, row_live, w_kstrided, epilogue, aux, out, colsum_out)
+
+
+def gemm_dgrad_slabs(dy, w, row_live=None, *, w_kstrided=True, epilogue=EPI_NONE, aux=None, out=None):
+    """gemm_dgrad_rows (EPI_NONE / EPI_ADD) over the 8-row slabs that hold a live row (ia_gemm_dgrad_slabs); the other slabs' rows are
+    written as zeros."""
+    return _gemm_dgrad_filtered("slabs", dy, w, row_live, w_kstrided, epilogue, aux, out)
+
+
+def _gemm_fwd_filtered(unit, x, w, row_live, epilogue, bias, scaled_cols, col_scale, fill, out, pre_out):
+    """gemm_fwd_rows (unit "rows": ia_gemm_fwd_rows) and gemm_fwd_slabs ("slabs": ia_gemm_fwd_slabs): one signature, two entry points"""
     lib = _lib.load()
-    _need(dy, BF16, "dy"); _need(w, BF16, "w"); _need(aux, BF16, "aux"); _need(row_live, torch.uint8, "row_live")
-    _need(colsum_out, F32, "colsum_out")
-    M, K = dy.shape
-    Kw, N = w.shape if w_kstrided else w.shape[::-1]
+    _need(x, BF16, "x"); _need(w, BF16, "w"); _need(bias, F32, "bias"); _need(row_live, torch.uint8, "row_live")
+    M, K = x.shape
+    N, Kw = w.shape
     if K != Kw or (row_live is not None and row_live.numel() != M):
-        raise ValueError("gemm_dgrad_rows: dy, w and row_live do not fit together")
-    if epilogue == EPI_DGELU_COLSUM and colsum_out is None:
-        raise ValueError("gemm_dgrad_rows: EPI_DGELU_COLSUM needs colsum_out")
+        raise ValueError(f"gemm_fwd_{unit}: x, w and row_live do not fit together")
     if out is None:
-        out = torch.empty((M, N), device=dy.device, dtype=BF16)
+        out = torch.empty((M, N), device=x.device, dtype=BF16)
     _need(out, BF16, "out")
-    ws_bytes = lib.ia_gemm_dgrad_rows_workspace_bytes(M, N, K)
-    ws = torch.empty(ws_bytes, device=dy.device, dtype=torch.uint8)
-    check(lib.ia_gemm_dgrad_rows(dy.data_ptr(), K, w.data_ptr(), int(w_kstrided), w.shape[1], out.data_ptr(), N, M, N, K, epilogue,
-                                 ptr(aux), N if aux is not None else 0, ptr(colsum_out), ptr(row_live), ws.data_ptr(), ws_bytes,
-                                 stream_ptr()), "ia_gemm_dgrad_rows")
+    if epilogue == EPI_BIAS_GELU and pre_out is None:
+        pre_out = torch.empty((M, N), device=x.device, dtype=BF16)
+    _need(pre_out, BF16, "pre_out")
+    ws_bytes = lib.ia_gemm_slabs_workspace_bytes(M) if unit == "slabs" else lib.ia_gemm_fwd_rows_workspace_bytes(M)
+    ws = torch.empty(ws_bytes, device=x.device, dtype=torch.uint8)
+    check(getattr(lib, f"ia_gemm_fwd_{unit}")(x.data_ptr(), K, w.data_ptr(), K, out.data_ptr(), N, M, N, K, epilogue, ptr(bias), ptr(pre_out),
+                                              scaled_cols, col_scale, ptr(row_live), int(fill), ws.data_ptr(), ws_bytes, stream_ptr()),
+          f"ia_gemm_fwd_{unit}")
+    if epilogue == EPI_BIAS_GELU:
+        return out, pre_out
     return out
 
 
@@ -155,81 +194,13 @@ def gemm_fwd_rows(x, w, row_live=None, *, epilogue=EPI_NONE, bias=None, scaled_c
     """Y[M, N] = x[M, K] w[N, K]^T (+ EPI_NONE / EPI_BIAS with scaled_cols, col_scale / EPI_BIAS_GELU / EPI_BIAS_GELU_ACT = 7) over the
     32-row blocks that hold a live row (row_live uint8 [M]; ia_gemm_fwd_rows).  fill: the other blocks' rows are written as zeros, else
     not written.  row_live=None is the unfiltered call.  EPI_BIAS_GELU returns (out, pre_out)."""
-    lib = _lib.load()
-    _need(x, BF16, "x"); _need(w, BF16, "w"); _need(bias, F32, "bias"); _need(row_live, torch.uint8, "row_live")
-    M, K = x.shape
-    N, Kw = w.shape
-    if K != Kw or (row_live is not None and row_live.numel() != M):
-        raise ValueError("gemm_fwd_rows: x, w and row_live do not fit together")
-    if out is None:
-        out = torch.empty((M, N), device=x.device, dtype=BF16)
-    _need(out, BF16, "out")
-    if epilogue == EPI_BIAS_GELU and pre_out is None:
-        pre_out = torch.empty((M, N), device=x.device, dtype=BF16)
-    _need(pre_out, BF16, "pre_out")
-    ws_bytes = lib.ia_gemm_fwd_rows_workspace_bytes(M)
-    ws = torch.empty(ws_bytes, device=x.device, dtype=torch.uint8)
-    check(lib.ia_gemm_fwd_rows(x.data_ptr(), K, w.data_ptr(), K, out.data_ptr(), N, M, N, K, epilogue, ptr(bias), ptr(pre_out), scaled_cols,
-                               col_scale, ptr(row_live), int(fill), ws.data_ptr(), ws_bytes, stream_ptr()), "ia_gemm_fwd_rows")
-    if epilogue == EPI_BIAS_GELU:
-        return out, pre_out
-    return out
-
-
-def row_slabs(row_live):
-    """The 8-row slab list of ia_row_slabs (uint8 [M] on the GPU -> int32 words): [0] live count, [1] dead count, [2] slabs; from word 8
-    the live slabs, 32 to a tile in the order [wave][piece] (-1 behind the last); the ascending dead slabs from word 8 + slabs rounded
-    up to 32."""
-    lib = _lib.load()
-    _need(row_live, torch.uint8, "row_live")
-    M = row_live.numel()
-    out = torch.empty(lib.ia_row_slabs_bytes(M) // 4, device=row_live.device, dtype=torch.int32)
-    check(lib.ia_row_slabs(row_live.data_ptr(), M, out.data_ptr(), stream_ptr()), "ia_row_slabs")
-    return out
-
-
-def gemm_dgrad_slabs(dy, w, row_live=None, *, w_kstrided=True, epilogue=EPI_NONE, aux=None, out=None):
-    """gemm_dgrad_rows (EPI_NONE / EPI_ADD) over the 8-row slabs that hold a live row (ia_gemm_dgrad_slabs); the other slabs' rows are
-    written as zeros."""
-    lib = _lib.load()
-    _need(dy, BF16, "dy"); _need(w, BF16, "w"); _need(aux, BF16, "aux"); _need(row_live, torch.uint8, "row_live")
-    M, K = dy.shape
-    Kw, N = w.shape if w_kstrided else w.shape[::-1]
-    if K != Kw or (row_live is not None and row_live.numel() != M):
-        raise ValueError("gemm_dgrad_slabs: dy, w and row_live do not fit together")
-    if out is None:
-        out = torch.empty((M, N), device=dy.device, dtype=BF16)
-    _need(out, BF16, "out")
-    ws_bytes = lib.ia_gemm_slabs_workspace_bytes(M)
-    ws = torch.empty(ws_bytes, device=dy.device, dtype=torch.uint8)
-    check(lib.ia_gemm_dgrad_slabs(dy.data_ptr(), K, w.data_ptr(), int(w_kstrided), w.shape[1], out.data_ptr(), N, M, N, K, epilogue,
-                                  ptr(aux), N if aux is not None else 0, ptr(row_live), ws.data_ptr(), ws_bytes, stream_ptr()),
-          "ia_gemm_dgrad_slabs")
-    return out
+    return _gemm_fwd_filtered("rows", x, w, row_live, epilogue, bias, scaled_cols, col_scale, fill, out, pre_out)
 
 
 def gemm_fwd_slabs(x, w, row_live=None, *, epilogue=EPI_NONE, bias=None, scaled_cols=0, col_scale=1.0, fill=True, out=None, pre_out=None):
     """gemm_fwd_rows (EPI_NONE / EPI_BIAS with scaled_cols, col_scale / EPI_BIAS_GELU) over the 8-row slabs that hold a live row
     (ia_gemm_fwd_slabs).  fill: the other slabs' rows are written as zeros, else not written.  EPI_BIAS_GELU returns (out, pre_out)."""
-    lib = _lib.load()
-    _need(x, BF16, "x"); _need(w, BF16, "w"); _need(bias, F32, "bias"); _need(row_live, torch.uint8, "row_live")
-    M, K = x.shape
-    N, Kw = w.shape
-    if K != Kw or (row_live is not None and row_live.numel() != M):
-        raise ValueError("gemm_fwd_slabs: x, w and row_live do not fit together")
-    if out is None:
-        out = torch.empty((M, N), device=x.device, dtype=BF16)
-    _need(out, BF16, "out")
-    if epilogue == EPI_BIAS_GELU and pre_out is None:
-        pre_out = torch.empty((M, N), device=x.device, dtype=BF16)
-    _need(pre_out, BF16, "pre_out")
-    ws_bytes = lib.ia_gemm_slabs_workspace_bytes(M)
-    ws = torch.empty(ws_bytes, device=x.device, dtype=torch.uint8)
-    check(lib.ia_gemm_fwd_slabs(x.data_ptr(), K, w.data_ptr(), K, out.data_ptr(), N, M, N, K, epilogue, ptr(bias), ptr(pre_out), scaled_cols,
-                                col_scale, ptr(row_live), int(fill), ws.data_ptr(), ws_bytes, stream_ptr()), "ia_gemm_fwd_slabs")
-    if epilogue == EPI_BIAS_GELU:
-        return out, pre_out
-    return out
+    return _gemm_fwd_filtered("slabs", x, w, row_live, epilogue, bias, scaled_cols, col_scale, fill, out, pre_out)
 
 
 def ln_fwd_rows(x, gamma, beta, eps, row_live, *, bias=None, residual=None, write_z=True, in_place=False, drop_p=0.0, seed=0, stream_id=0):

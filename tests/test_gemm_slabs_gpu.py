@@ -245,3 +245,31 @@ def test_live_rows_against_fp64(gpu, operands):
     gelu, normal = fp64_errors(gpu, operands, True)
     print("normal operands: GELU form %.3e, linear forms %.3e" % (max(e for _, e in gelu), max(e for _, e in normal)))
     assert all(e < 2e-2 for _, e in gelu + normal), max(gelu + normal, key=lambda t: t[1])
+
+
+def test_pairs_without_a_kernel_form_are_refused(gpu):
+    """The (filter kind, epilogue) pairs that have no kernel form return IA_ERR_UNSUPPORTED (-4) before anything is launched: the output
+    keeps its sentinel.  M = 40, N = K = 128: the check precedes every launch, so the shape only has to pass argument validation."""
+    from item_alignment_amd import _lib
+    from item_alignment_amd._lib import stream_ptr
+    lib = _lib.load()
+    M, N, K = 40, 128, 128
+    EPI_BIAS_GELU_ACT, EPI_DGELU_COLSUM, UNSUPPORTED = 7, 6, -4
+    x = torch.ones((M, K), device=gpu, dtype=torch.bfloat16)
+    w = torch.ones((N, K), device=gpu, dtype=torch.bfloat16)
+    aux = torch.ones((M, N), device=gpu, dtype=torch.bfloat16)
+    bias = torch.ones(N, device=gpu)
+    live = torch.ones(M, device=gpu, dtype=torch.uint8)
+    out = torch.full((M, N), SENTINEL, device=gpu, dtype=torch.bfloat16)
+    ws_bytes = max(lib.ia_gemm_slabs_workspace_bytes(M), lib.ia_gemm_fwd_rows_workspace_bytes(M), lib.ia_gemm_dgrad_rows_workspace_bytes(M, N, K))
+    ws = torch.zeros(ws_bytes, device=gpu, dtype=torch.uint8)
+    p = lambda t: t.data_ptr()
+    for row_live in (p(live), None):
+        assert lib.ia_gemm_fwd_slabs(p(x), K, p(w), K, p(out), N, M, N, K, EPI_BIAS_GELU_ACT, p(bias), None, 0, 1.0, row_live, 1, p(ws), ws_bytes,
+                                     stream_ptr()) == UNSUPPORTED
+        assert lib.ia_gemm_dgrad_slabs(p(x), K, p(w), 0, K, p(out), N, M, N, K, EPI_DGELU_COLSUM, p(aux), N, row_live, p(ws), ws_bytes,
+                                       stream_ptr()) == UNSUPPORTED
+        assert lib.ia_gemm_fwd_rows(p(x), K, p(w), K, p(out), N, M, N, K, EPI_ADD, p(bias), None, 0, 1.0, row_live, 1, p(ws), ws_bytes,
+                                    stream_ptr()) == UNSUPPORTED
+    torch.cuda.synchronize()
+    assert bool((out == SENTINEL).all()) and not bool(ws.any())
