@@ -47,35 +47,6 @@ def get_parser():
     return p
 
 
-def check_model_dir(path):
-    """a hub name such as the reference's 'bert-base-chinese' would mean a download: refused"""
-    if not os.path.isdir(path):
-        raise SystemExit(f"--model_name_or_path {path!r} is not a local directory.  This script never downloads: unpack the checkpoint "
-                         "(vocab.txt, config.json, pytorch_model.bin) into a directory and pass that")
-    for need in ("vocab.txt", "config.json"):
-        if not os.path.isfile(os.path.join(path, need)):
-            raise SystemExit(f"--model_name_or_path {path!r} has no {need}")
-
-
-def load_tokenizer(vocab_file):
-    """BertTokenizer(vocab_file=<dir>/vocab.txt, do_lower_case=True) of the reference's pytorch_transformers, built from the local file
-    alone.  Newer transformers releases take the vocabulary itself (`vocab=`) where older ones take the file name."""
-    import inspect
-    from transformers import BertTokenizer
-    if "vocab" in inspect.signature(BertTokenizer.__init__).parameters:
-        with open(vocab_file, "r", encoding="utf8") as f:
-            vocab = {line.rstrip("\n"): i for i, line in enumerate(f)}
-        return BertTokenizer(vocab=vocab, do_lower_case=True)
-    return BertTokenizer(vocab_file=vocab_file, do_lower_case=True)
-
-
-def linear_schedule(step, total, warmup):
-    """transformers.get_linear_schedule_with_warmup's factor at `step`"""
-    if step < warmup:
-        return step / max(1, warmup)
-    return max(0.0, (total - step) / max(1, total - warmup))
-
-
 def count_records(data_dir, file):
     with open(os.path.join(data_dir, file), "r", encoding="utf8") as f:
         return sum(1 for line in f if line.strip())
@@ -83,10 +54,10 @@ def count_records(data_dir, file):
 
 def main(argv=None):
     args = get_parser().parse_args(argv)
+    from item_alignment_amd.cli_common import check_model_dir, linear_schedule, load_config, load_vocab_tokenizer
     check_model_dir(args.model_name_or_path)
     import torch
     import item_alignment_amd.models as M
-    from item_alignment_amd.cli_common import load_config
     from item_alignment_amd.data import bert_pretrain as D
     from item_alignment_amd.models import functional as Fn
 
@@ -109,7 +80,7 @@ def main(argv=None):
     torch.cuda.set_device(device)
 
     vocab_file = os.path.join(args.model_name_or_path, "vocab.txt")
-    tokenizer = load_tokenizer(vocab_file)
+    tokenizer = load_vocab_tokenizer(vocab_file)
     config = load_config(os.path.join(args.model_name_or_path, "config.json"))
     if args.max_seq_len + 2 > config.max_position_embeddings:
         raise SystemExit(f"--max_seq_len {args.max_seq_len} + [CLS] + [SEP] exceeds max_position_embeddings {config.max_position_embeddings}")

@@ -84,6 +84,36 @@ def load_tokenizer(args):
     return tk
 
 
+def check_model_dir(path):
+    """--model_name_or_path of bert_pretrain.py / finetune_bert.py / pred_bert.py: a hub name such as the reference's
+    'bert-base-chinese' would mean a download: refused"""
+    if not os.path.isdir(path):
+        raise SystemExit(f"--model_name_or_path {path!r} is not a local directory.  This script never downloads: unpack the checkpoint "
+                         "(vocab.txt, config.json, pytorch_model.bin) into a directory and pass that")
+    for need in ("vocab.txt", "config.json"):
+        if not os.path.isfile(os.path.join(path, need)):
+            raise SystemExit(f"--model_name_or_path {path!r} has no {need}")
+
+
+def load_vocab_tokenizer(vocab_file):
+    """BertTokenizer(vocab_file=<dir>/vocab.txt, do_lower_case=True) of the reference's BERT scripts, built from the local file alone.
+    Newer transformers releases take the vocabulary itself (`vocab=`) where older ones take the file name."""
+    import inspect
+    from transformers import BertTokenizer
+    if "vocab" in inspect.signature(BertTokenizer.__init__).parameters:
+        with open(vocab_file, "r", encoding="utf8") as f:
+            vocab = {line.rstrip("\n"): i for i, line in enumerate(f)}
+        return BertTokenizer(vocab=vocab, do_lower_case=True)
+    return BertTokenizer(vocab_file=vocab_file, do_lower_case=True)
+
+
+def linear_schedule(step, total, warmup):
+    """transformers.get_linear_schedule_with_warmup's factor at `step`"""
+    if step < warmup:
+        return step / max(1, warmup)
+    return max(0.0, (total - step) / max(1, total - warmup))
+
+
 def freeze_and_resume(args, model):
     if args.parameters_to_freeze is not None:
         names = json.load(open(args.parameters_to_freeze, "r", encoding="utf-8"))

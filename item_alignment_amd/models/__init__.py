@@ -10,3 +10,4 @@ from .multimodal import (RobertaImageModel, RobertaImageOneTower, RobertaImageTw
                          LayerNorm, Residual, RotaryEmbedding, SwiGLU, ParallelTransformerBlock, CrossAttention)
 from .graph import GCN, GCN2Conv, GCNTwoTower, GraphAdjacency, load_adjacency
 from .bert_pretrain import BertForPreTraining
+from .bert_align import BertAlignModel

@@ -148,6 +148,31 @@ class TiedCaptionHeadFn(torch.autograd.Function):
         return dh, None, None, None, None, None
 
 
+def init_the_bert_way(model):
+    """What a model whose `model.bert` is a RobertaModel needs to be BERT (BertForPreTraining, BertAlignModel): the weights drawn, absolute
+    positions with a trained row 0, a trainable pooler, one arena."""
+    std = getattr(model.config, "initializer_range", 0.02)
+    init_bert_weights(model, std)
+    # BERT's position table has no padding row: position 0 is [CLS]'s, it is drawn like the others and takes its gradient
+    emb = model.bert.embeddings
+    emb.pos_pad = -1
+    with torch.no_grad():
+        nn.init.normal_(emb.position_embeddings.weight[emb.padding_idx], mean=0.0, std=std)
+    for p in model.bert.pooler.parameters():      # RobertaPooler freezes itself for the pair models; the next-sentence head trains it
+        p.requires_grad = True
+    adopt(model, model.bert)
+
+
+def save_bert_pretrained(model, save_directory):
+    """pytorch_model.bin (the fp32 masters under transformers' key names) + config.json"""
+    os.makedirs(save_directory, exist_ok=True)
+    sd = {k: v.detach().to("cpu", F32 if v.is_floating_point() else v.dtype).clone() for k, v in model.state_dict().items()}
+    torch.save(sd, os.path.join(save_directory, ROBERTA_WEIGHTS_NAME))
+    cfg = model.config.to_dict() if hasattr(model.config, "to_dict") else dict(vars(model.config))
+    with open(os.path.join(save_directory, "config.json"), "w", encoding="utf8") as f:
+        json.dump({k: v for k, v in cfg.items() if isinstance(v, (int, float, str, bool, list, type(None)))}, f, indent=2, sort_keys=True)
+
+
 class BertForPreTraining(HipModule, PretrainedMixin):
     """model(input_ids, token_type_ids=None, attention_mask=..., masked_lm_labels=..., next_sentence_label=...) ->
     (total_loss, prediction_scores, seq_relationship_score) with both labels, (prediction_scores, seq_relationship_score) without,
@@ -167,15 +192,7 @@ class BertForPreTraining(HipModule, PretrainedMixin):
         self.config = config
         self.bert = RobertaModel(config)
         self.cls = BertPreTrainingHeads(config, self.bert.embeddings.word_embeddings.weight)
-        init_bert_weights(self, getattr(config, "initializer_range", 0.02))
-        # BERT's position table has no padding row: position 0 is [CLS]'s, it is drawn like the others and takes its gradient
-        emb = self.bert.embeddings
-        emb.pos_pad = -1
-        with torch.no_grad():
-            nn.init.normal_(emb.position_embeddings.weight[emb.padding_idx], mean=0.0, std=getattr(config, "initializer_range", 0.02))
-        for p in self.bert.pooler.parameters():      # RobertaPooler freezes itself for the pair models; the next-sentence head trains it
-            p.requires_grad = True
-        adopt(self, self.bert)
+        init_the_bert_way(self)
 
     def get_output_embeddings(self):
         return self.cls.predictions.decoder
@@ -215,10 +232,4 @@ class BertForPreTraining(HipModule, PretrainedMixin):
         return mlm_loss + nsp_loss, None, seq_score
 
     def save_pretrained(self, save_directory):
-        """pytorch_model.bin (the fp32 masters under transformers' key names) + config.json"""
-        os.makedirs(save_directory, exist_ok=True)
-        sd = {k: v.detach().to("cpu", F32 if v.is_floating_point() else v.dtype).clone() for k, v in self.state_dict().items()}
-        torch.save(sd, os.path.join(save_directory, ROBERTA_WEIGHTS_NAME))
-        cfg = self.config.to_dict() if hasattr(self.config, "to_dict") else dict(vars(self.config))
-        with open(os.path.join(save_directory, "config.json"), "w", encoding="utf8") as f:
-            json.dump({k: v for k, v in cfg.items() if isinstance(v, (int, float, str, bool, list, type(None)))}, f, indent=2, sort_keys=True)
+        save_bert_pretrained(self, save_directory)

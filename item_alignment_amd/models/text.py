@@ -150,25 +150,58 @@ class RobertaModel(HipModule, PretrainedMixin):
         padding too (data.py:558-559); nothing it returns depends on those rows (keys are masked, heads read valid positions), so
         the padded rows are dropped before the embedding kernel and every layer runs on sum(lengths) rows with the packed
         attention kernels.  Hidden states come back in the padded [B, L, H] shape (zeros at the padding) on demand."""
-        emb, enc = self.embeddings, self.encoder
         B, L = input_ids.shape
-        valid = (attention_mask != 0)
-        lens = valid.sum(dim=1)
-        T, Lmax = (int(v) for v in torch.stack((lens.sum(), lens.max())).tolist())       # one host sync per forward
-        if T == B * L:
+        ids, tts, pids = self.embeddings._ids(input_ids, token_type_ids, position_ids)
+        got = self._forward_packed([(ids, tts, pids, attention_mask)], dense_is_none=True)
+        if got is None:
             return None                                                                # nothing to drop
-        ids, tts, pids = emb._ids(input_ids, token_type_ids, position_ids)
-        idx = valid.reshape(-1).nonzero(as_tuple=False).squeeze(1)                      # packed row -> padded row
-        cu = torch.zeros(B + 1, device=ids.device, dtype=torch.int32)
+        packed, idx, _cu = got
+        return _PaddedView(packed, idx, B, L)
+
+    def _forward_packed(self, fields, dense_is_none=False, strict=False):
+        """The tower on the valid tokens of several padded inputs at once.  fields: a list of (input_ids, token_type_ids, position_ids,
+        attention_mask), each [B_f, L_f] with its own L_f.  The valid tokens of all sequences are kept back to back, field by field and
+        sequence by sequence, and run as ONE ragged batch of sum(B_f) sequences: embedding + LayerNorm, then every layer with the packed
+        attention kernels (ia_layer_cfg::cu_seqlens).  A padded position is never gathered, so nothing returned depends on what it holds.
+        Returns (hidden states: the embedding output and every layer's, each [T, H]; idx [T]: packed row -> row of the fields' flattened
+        positions laid end to end; cu_seqlens int32 [sum(B_f) + 1]).
+        One host synchronisation: T sizes the tensors and the longest sequence the attention launches.
+        dense_is_none: return None, with nothing launched, when no position is padded.
+        strict: a sequence without a valid token, or whose position 0 is not one, raises ValueError with nothing launched."""
+        emb, enc = self.embeddings, self.encoder
+        dev = fields[0][0].device
+        valid = [(f[3] != 0) for f in fields]
+        lens = torch.cat([v.sum(dim=1) for v in valid])
+        first = torch.cat([v[:, 0] for v in valid]).all().to(lens.dtype)
+        T, Lmax, Lmin, first = (int(v) for v in torch.stack((lens.sum(), lens.max(), lens.min(), first)).tolist())   # the one host sync
+        S = lens.numel()
+        if strict and Lmin == 0:
+            raise ValueError("a sequence has an attention mask of zeros only: there is no token to run (the padded form would attend "
+                             "uniformly over its padding)")
+        if strict and not first:
+            raise ValueError("a sequence's position 0 is masked: the packed run reads the first valid token of each sequence as its [CLS]")
+        flat_valid = torch.cat([v.reshape(-1) for v in valid])
+        N = flat_valid.numel()
+        if dense_is_none and T == N:
+            return None
+        # packed row -> flattened position, without a second synchronisation (nonzero() would be one): every valid position writes its
+        # own number into the slot its running count names, every padded one into a spare slot behind the end
+        slot = torch.cumsum(flat_valid, 0) - 1
+        idx = torch.empty(T + 1, device=dev, dtype=torch.long)
+        idx.scatter_(0, torch.where(flat_valid, slot, torch.full_like(slot, T)), torch.arange(N, device=dev, dtype=torch.long))
+        idx = idx[:T]
+        cu = torch.zeros(S + 1, device=dev, dtype=torch.int32)
         cu[1:] = torch.cumsum(lens, 0)
         training = self.training and torch.is_grad_enabled()
         p = emb.drop_p if training else 0.0
-        take = lambda t: t.reshape(-1).index_select(0, idx).contiguous()
-        pk = take(pids)
+        take = lambda k: torch.cat([f[k].reshape(-1) for f in fields]).index_select(0, idx).contiguous()
+        pk = take(2)
         order = torch.argsort(pk, stable=True).to(torch.int32)          # backward walks the rows position by position (embed.hip)
-        e = Fn.EmbedLNFn.apply(emb.anchor, emb, take(ids), take(tts), pk, None, None, p, emb.stream_id, order)
-        outs = Fn.EncoderStackFn.apply(e, enc.anchor, enc, None, B, Lmax, torch.is_grad_enabled(), cu)
-        return _PaddedView((e,) + tuple(outs), idx, B, L)
+        e = Fn.EmbedLNFn.apply(emb.anchor, emb, take(0), take(1), pk, None, None, p, emb.stream_id, order)
+        # a packed batch has no masked row: what an earlier padded call asked of the stack (RobertaEncoder.forward) does not apply
+        enc.__dict__["_masked_rows_dead"], enc.__dict__["_out_rows_cls"] = 0, False
+        outs = Fn.EncoderStackFn.apply(e, enc.anchor, enc, None, S, Lmax, torch.is_grad_enabled(), cu)
+        return (e,) + tuple(outs), idx, cu
 
 
 def adopt(root, *children):
