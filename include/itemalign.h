@@ -37,7 +37,7 @@ const char* ia_strerror(int code);
 /* Bumped whenever an entry point is added or the meaning of an argument / output changes (round 2 changed what IA_EPI_BIAS_GELU
  * stores in C2 and what IA_EPI_DGELU expects in aux): a caller built against another header must not run on this library.
  * item_alignment_amd/_lib.py refuses to load a library whose version differs from the one it was written for. */
-#define IA_ABI_VERSION 20
+#define IA_ABI_VERSION 21
 int ia_abi_version(void);
 
 /* ---- GEMM: torch.nn.Linear forward / dgrad / wgrad (src/models/text.py:1241 -> RobertaLayer dense
@@ -127,15 +127,15 @@ size_t ia_row_blocks_bytes(int M_rows);
 int ia_row_blocks(const uint8_t* row_live, int M_rows, int* list, ia_stream_t stream);
 int ia_row_blocks_host(const uint8_t* row_live, int M_rows, int* list);
 /* Diagnostics (tests, A/B runs): on == 0 makes ia_layer_bwd2 run its data gradients over every row although
- * ia_layer_cfg::masked_rows_dead is set (the block list is withheld; every other row filter stays); returns the previous setting. */
+ * ia_layer_cfg::masked_rows_dead is set (their lists are withheld; every other row filter stays); returns the previous setting. */
 int ia_debug_dgrad_rows(int on);
 /* Diagnostics (tests, A/B runs; ABI 19): on == 0 makes ia_layer_fwd / ia_layer_fwd_infer run every row although
- * ia_layer_cfg::masked_rows_dead has bit 2 set; returns the previous setting. */
+ * ia_layer_cfg::masked_rows_dead has IA_ROWS_DEAD_FWD set; returns the previous setting. */
 int ia_debug_fwd_rows(int on);
 /* (ABI 19) The forward GEMM Y[M_rows, N_out] = X[M_rows, K_in] W[N_out, K_in]^T of ia_gemm_bf16 / ia_gemm_bf16_qscale (both operands
  * k-contiguous, bf16 output; epilogue IA_EPI_NONE, IA_EPI_BIAS with scaled_cols / col_scale, IA_EPI_BIAS_GELU with C2, or
  * IA_EPI_BIAS_GELU_ACT) with a row filter.  row_live [M_rows] uint8 or NULL.  Contract: row_live[m] == 0 = nobody who needs a defined value
- * reads row m of Y / C2 (a padded position under ia_layer_cfg::masked_rows_dead bit 2).  The rows are taken in blocks of 32: a block
+ * reads row m of Y / C2 (a padded position under ia_layer_cfg::masked_rows_dead IA_ROWS_DEAD_FWD).  The rows are taken in blocks of 32: a block
  * without a live row is neither fetched nor multiplied.  fill_dead_rows != 0: its rows of Y (and C2) are written as zeros;
  * fill_dead_rows == 0: they are not written at all (they keep what the buffer held).  Every row of a block that holds a live row is
  * bit-identical to the unfiltered call's.  NULL = the unfiltered call.  With row_live the workspace (32-byte aligned,
@@ -174,14 +174,12 @@ int ia_gemm_dgrad_groups_rows(const void* dY, int ldy, const void* W, int w_kstr
  * slabs, [1] dead slabs, [2] slabs -- then the live slabs, ascending, 32 to an M-tile of the kernel and inside a tile in the order
  * [wave][piece]: the i-th live slab sits at entry (i & ~31) + (i & 3) * 8 + ((i & 31) >> 2), the entries behind the last one of the last
  * tile are -1; then, behind room for every slab rounded up to a multiple of 32, the dead slabs, ascending.
- * ia_row_slabs_offset: where the list sits in the buffer ia_layer_cfg::row_blocks points into (masked_rows_dead bit 6, value 32).
  * ia_gemm_fwd_slabs: epilogue IA_EPI_NONE, IA_EPI_BIAS with scaled_cols / col_scale, or IA_EPI_BIAS_GELU with C2; fill_dead_rows as in
  * ia_gemm_fwd_rows, by slab.  ia_gemm_dgrad_slabs: IA_EPI_NONE or IA_EPI_ADD; the rows of the dead slabs of dX are written as zeros.
  * Other epilogues: IA_ERR_UNSUPPORTED.  row_live == NULL: the unfiltered call.  Workspace with row_live (32-byte aligned):
  * ia_gemm_slabs_workspace_bytes, the list.  The shapes that filter: ia_gemm_fwd_rows_filters / ia_gemm_dgrad_rows_filters; others run
  * every row. */
 size_t ia_row_slabs_bytes(int M_rows);
-size_t ia_row_slabs_offset(int M_rows);
 int ia_row_slabs(const uint8_t* row_live, int M_rows, int* list, ia_stream_t stream);
 int ia_row_slabs_host(const uint8_t* row_live, int M_rows, int* list);
 size_t ia_gemm_slabs_workspace_bytes(int M_rows);
@@ -199,15 +197,13 @@ int ia_debug_out_rows(int on);
  * 128-row groups -- a group's blocks contiguous and ascending, no group across two wave-rows, -1 in the slots behind them; header word 0
  * counts the slots in use (4 x wave-rows).  Groups with 4 live blocks stand alone, each 3 takes a 1, then 2 + 2, an odd 2 with up to two
  * 1s, the remaining 1s by four: a deterministic layout, so the device builder and the _host twin give the same list.  At most
- * 128 x 4096 rows (IA_ERR_UNSUPPORTED beyond).  ia_row_groups_packed_offset: where the list sits behind an ia_row_blocks list when one
- * buffer holds both (ia_layer_cfg::masked_rows_dead bit 3).
+ * 128 x 4096 rows (IA_ERR_UNSUPPORTED beyond).
  * ia_gemm_dgrad_packed: the IA_EPI_DGELU_COLSUM data gradient (as ia_gemm_dgrad_groups_rows, the list handed in) over such a list -- dX
  * on the live blocks, zeros elsewhere, and C2 += the column sums BIT-IDENTICAL to ia_gemm_bf16's on a dY that is zero wherever the list
  * has no block: a lane adds the rows of a group's live blocks in the dense kernel's order with nothing in between, the wave folds and
  * stores at every change of group into that group's slot of the partials, and the second stage is the dense call's.  Workspace:
  * ia_gemm_colsum_workspace_bytes.  A shape the remapped kernel does not serve (ia_gemm_dgrad_rows_filters == 0) runs every row. */
 size_t ia_row_groups_packed_bytes(int M_rows);
-size_t ia_row_groups_packed_offset(int M_rows);
 int ia_row_groups_packed(const uint8_t* row_live, int M_rows, int* list, ia_stream_t stream);
 int ia_row_groups_packed_host(const uint8_t* row_live, int M_rows, int* list);
 int ia_gemm_dgrad_packed(const void* dY, int ldy, const void* W, int w_kstrided, int ldw, void* dX, int ldx, int M_rows, int N_in, int K_out,
@@ -700,6 +696,21 @@ typedef struct { /* fp32 gradient arena slots, same shapes as above; all accumul
   float* w_fc1; float* b_fc1; float* w_fc2; float* b_fc2; float* ln2_g; float* ln2_b;
 } ia_layer_grads;
 
+/* The lists of ONE row mask over B * L rows, each from its public builder (sizes: ia_row_*_bytes, ia_kblock_mask_bytes).  Device
+ * pointers; each stands alone -- nothing is assumed about where one list sits relative to another -- and each is optional: NULL = the
+ * layer call builds its own in its stash / scratch (one small launch).  A member the call's plan does not ask for is not read (which
+ * plan reads which: ia_layer_cfg::key_rows / out_rows). */
+typedef struct {
+  const int* blocks;        /* ia_row_blocks */
+  const int* packed;        /* ia_row_groups_packed */
+  const int* slabs;         /* ia_row_slabs */
+  const int* groups;        /* ia_row_groups */
+  const uint32_t* kblocks;  /* ia_kblock_mask (32-row blocks of k) */
+} ia_row_lists;
+/* the bits of ia_layer_cfg::masked_rows_dead */
+#define IA_ROWS_DEAD_BWD 1
+#define IA_ROWS_DEAD_FWD 2
+
 typedef struct {
   int B, L, H, I, nh;      /* tokens M = B*L; head dim = H/nh = 64 */
   int pre_ln;              /* 0 = BERT post-LN layer (RobertaLayer), 1 = ViT pre-LN block (timm Block) */
@@ -712,13 +723,12 @@ typedef struct {
    * key_mask argument is ignored (every token of a sequence is attendable).  NULL / 0: padded [B, L] rows. */
   const int* cu_seqlens;
   int total_tokens;
-  /* (ABI 20, second form) the query-row limit of a layer with out_row_live: 0 = off; n > 0 = the caller guarantees that out_row_live is
-   * zero at every position >= n of every sequence, so the attention output there is unread and its gradient exactly zero.  The attention
-   * forward then computes the query tiles that reach in front of n only (the other rows of the stash's context are zeros, written by
-   * the kernel) and the attention backward treats the 32-query blocks at or beyond n as dead (ia_attn_fwd_q_rows /
-   * ia_attn_bwd_bias_q_rows); every output row the caller reads and every gradient is bit-identical to out_q_rows = 0.  Honoured only
-   * together with out_row_live and on padded rows (cu_seqlens == NULL).  The member fills what was the padding word in front of
-   * dx_colsum_out: no offset and not the size of the structure changes, and a zero-initialised structure of an older caller says "off". */
+  /* The query-row limit of a layer with out_row_live: 0 = off; n > 0 = the caller guarantees that out_row_live is zero at every position
+   * >= n of every sequence, so the attention output there is unread and its gradient exactly zero.  The attention forward then computes
+   * the query tiles that reach in front of n only (the other rows of the stash's context are zeros, written by the kernel) and the
+   * attention backward treats the 32-query blocks at or beyond n as dead (ia_attn_fwd_q_rows / ia_attn_bwd_bias_q_rows); every output
+   * row the caller reads and every gradient is bit-identical to out_q_rows = 0.  Honoured only together with out_row_live and on padded
+   * rows (cu_seqlens == NULL). */
   int out_q_rows;
   /* pre-LN (ViT) stacks, backward only (ABI 5): the b_fc2 gradient of a block is the column sum of its incoming gradient dy, i.e. of
    * the input gradient dx the block ABOVE has just produced.  dx_colsum_out != NULL: this block's last LayerNorm backward also adds
@@ -726,48 +736,36 @@ typedef struct {
    * block above did that for this block's dy, so the separate column-sum pass over dy is skipped.  Zero / NULL = round-3 behaviour. */
   float* dx_colsum_out;
   int dy_colsum_done;
-  /* (ABI 8) nonzero: no output of a masked position (key_mask == 0) reaches the loss, so the gradient arriving at such rows is exactly
-   * zero in every layer -- the attention backward may skip query blocks made of masked positions only (IA_ATTN_MASKED_ROWS_DEAD).
-   * Zero = the round-5 behaviour (every row is computed).
-   * (ABI 19) A bit set.  Bit 1 (value 1): the meaning above -- the backward skips.  Bit 2 (value 2), only together with bit 1, on padded
-   * rows with a key mask: nobody reads the layer's output at a masked position either, so the forward of a post-LN layer skips too -- the
-   * four GEMMs the 32-row blocks made of masked positions, the two LayerNorms the masked rows.  y, the LayerNorm outputs and sums are
-   * zeros at masked positions; q / k / v and the FFN activation (with its derivative) are zeros in blocks without a live row; the two
-   * projection outputs are not written there (their LayerNorm writes zeros over the stash's copy).  A stash written under 3 must be
-   * consumed by a backward with bit 1 set.  Every value the unmasked positions produce, and every gradient, is bit-identical to
-   * masked_rows_dead = 1.
-   * (ABI 20, second form) Bit 3 (value 4), read by the backward together with row_blocks: the buffer row_blocks points into also holds the
-   * block-packed list of the same mask (ia_row_groups_packed) at byte offset ia_row_groups_packed_offset(B * L); without the bit the
-   * backward builds that list per call.  The x gelu' + column-sums data gradient of a post-LN layer runs over it.
-   * Bit 4 (value 8), read by the backward together with live_ktiles: live_ktiles points at a 32-row block mask (ia_kblock_mask) and the
-   * weight gradients walk live 32-row blocks; without the bit a caller's live_ktiles is a 64-row mask (ia_ktile_mask) and they walk live
-   * 64-row k-tiles.  Bit 5 (value 16): the same of out_live_ktiles.  With a NULL pointer the backward builds the block mask itself.
-   * (ABI 20, third form) Bit 6 (value 32), read by the forward and the backward together with row_blocks: the buffer row_blocks points
-   * into also holds the 8-row slab list of the same mask (ia_row_slabs) at byte offset ia_row_slabs_offset(B * L); without the bit the
-   * layer calls build that list per call.  The QKV, out-projection, fc1 (training form) and fc2 GEMMs of the forward and the three plain
-   * data gradients run over it: what is said of 32-row blocks above holds of 8-row slabs there.
-   * No bit changes a gradient. */
+  /* Two promises of the caller about the masked positions (key_mask == 0); padded rows with a key mask only.  Any other bit: IA_ERR_ARG
+   * from the layer calls, 0 from the three size functions.
+   * IA_ROWS_DEAD_BWD: no output of a masked position reaches the loss, so the gradient arriving at such rows is exactly zero in every
+   * layer.  The backward skips them: the attention backward the query blocks made of masked positions (IA_ATTN_MASKED_ROWS_DEAD), the
+   * LayerNorm backwards the masked rows, the weight gradients the 32-row blocks of k without a live row, the data gradients the 8-row
+   * slabs (x gelu' + column sums: the 32-row blocks packed by whole 128-row groups) without one; their rows of dx are zeros.
+   * IA_ROWS_DEAD_FWD, only together with IA_ROWS_DEAD_BWD: nobody reads the layer's output at a masked position either, so the forward
+   * of a post-LN layer skips too -- the GEMMs the 8-row slabs (the forward-only GELU: the 32-row blocks) made of masked positions, the
+   * two LayerNorms the masked rows.  y, the LayerNorm outputs and sums are zeros at masked positions; q / k / v and the FFN activation
+   * (with its derivative) are zeros in slabs without a live row; the two projection outputs are not written there (their LayerNorm
+   * writes zeros over the stash's copy).  A stash written under both must be consumed by a backward with IA_ROWS_DEAD_BWD set.
+   * Every value the unmasked positions produce, and every parameter gradient, is bit-identical to masked_rows_dead = 0. */
   int masked_rows_dead;
-  /* (ABI 19) optional, device pointers, NULL = the layer call builds its own: the 32-row block list (ia_row_blocks) and the live-k-tile
-   * mask (ia_ktile_mask) of key_mask taken as row_live [B * L].  The mask is the same for every layer of a stack, forward and backward:
-   * a caller builds the two once per step and hands them to every call.  Read only under masked_rows_dead (padded rows, post-LN). */
-  const int* row_blocks;
-  const uint32_t* live_ktiles;
-  /* (ABI 20) optional: a second live-row description for the part of the layer BEHIND the attention, a byte per row [B * L] (device).
+  /* The lists of key_mask taken as row_live [B * L] (ia_row_lists).  The mask is the same for every layer of a stack, forward and
+   * backward: a caller builds them once per step and hands them to every call.  Read only under masked_rows_dead (padded rows,
+   * post-LN):   forward (both promises): blocks, slabs;   backward: kblocks, packed (B * L <= 128 * 4096), slabs;   groups: not read. */
+  ia_row_lists key_rows;
+  /* Optional: a second live-row description for the part of the layer BEHIND the attention, a byte per row [B * L] (device).
    * Non-NULL = the caller guarantees that it reads this layer's output only in rows with out_row_live != 0 and that the gradient it hands
    * to the backward (dy, dy2) is all zeros in every other row; every such row must also be a live key.  The out-projection, the
    * LayerNorm behind it, fc1 + GELU, fc2 and (post-LN) the closing LayerNorm then run these rows only -- GEMMs by 32-row blocks -- and so
    * do their backward kernels; the x gelu' data gradient runs whole 128-row groups (ia_row_groups), which keeps the fc1 bias gradient
    * bit-identical.  The QKV projection, the attention, their backward and the pre-LN LN1 keep the key-mask filter (post-LN) or every row
-   * (pre-LN): every row is a key (out_q_rows above limits the attention's QUERY rows).  y is unspecified outside out_row_live in a pre-LN layer and zeros there in a post-LN layer; dx and
-   * every parameter gradient are bit-identical to the call without it.  Padded rows only (cu_seqlens == NULL).  A stash written with
-   * out_row_live must be consumed by a backward with the same out_row_live.
-   * out_row_blocks (ia_row_blocks), out_live_ktiles (ia_ktile_mask), out_row_groups (ia_row_groups) of out_row_live: optional, NULL = the
-   * layer call builds its own in stash / scratch.  A mask that depends on (B, L) only -- row 0 of each sequence -- is built once and kept. */
+   * (pre-LN): every row is a key (out_q_rows above limits the attention's QUERY rows).  y is unspecified outside out_row_live in a
+   * pre-LN layer and zeros there in a post-LN layer; dx and every parameter gradient are bit-identical to the call without it.  Padded
+   * rows only (cu_seqlens == NULL).  A stash written with out_row_live must be consumed by a backward with the same out_row_live. */
   const uint8_t* out_row_live;
-  const int* out_row_blocks;
-  const uint32_t* out_live_ktiles;
-  const int* out_row_groups;
+  /* The lists of out_row_live.  A mask that depends on (B, L) only -- row 0 of each sequence -- is built once and kept.
+   *   forward: blocks;   backward: kblocks, blocks, groups;   packed, slabs: not read. */
+  ia_row_lists out_rows;
 } ia_layer_cfg;
 
 /* per-layer activation stash (saved by forward, read by backward) and shared backward scratch */
@@ -880,8 +878,8 @@ int ia_textcnn_pool_bwd_x(const float* g, const int32_t* argmax, const float* co
  * NaN, as torch's.  Fixed summation order, no atomics: two runs are bit-identical.  IA_ERR_ARG / IA_ERR_WORKSPACE before any launch.
  * ia_vocab_ce_bwd: dlogits [M, ldg] bf16 (ldg >= V, ldg % 8 == 0) = bf16((exp(logits - lse) - onehot(label)) * dloss[0] / loss[1]) in
  * columns < V, exact zeros in columns V .. ldg-1 and in every row that is ignored or whose label is >= V: the A operand of the
- * hidden-gradient GEMM (k-contiguous) and of the table-gradient GEMM (k-strided) as it stands.  The additions leave IA_ABI_VERSION
- * at 20: nothing existing changes its meaning. */
+ * hidden-gradient GEMM (k-contiguous) and of the table-gradient GEMM (k-strided) as it stands.  The additions did not
+ * bump IA_ABI_VERSION: nothing existing changed its meaning. */
 size_t ia_vocab_ce_workspace_bytes(int M);
 int ia_vocab_ce_fwd(const float* logits, int ld, const int64_t* labels, float* lse, float* loss_row, float* loss /* [2]: mean, n_live */,
                     int M, int V, void* workspace, size_t workspace_bytes, ia_stream_t stream);
@@ -897,8 +895,8 @@ int ia_vocab_ce_bwd(const float* logits, int ld, const int64_t* labels, const fl
  * dtext [B, lddt] = s G image, dimage [B, lddi] = s G^T text, dlog_scale[0] = (accumulate_dlog_scale ? dlog_scale[0] : 0) +
  * sum_ij G[i][j] sim[i][j].  Any B >= 1, H >= 1.  The pad columns of the inputs are never read, those of the outputs never written.
  * Fixed summation order, no atomics: two runs are bit-identical.  IA_ERR_ARG / IA_ERR_WORKSPACE before any launch; the workspace of
- * ia_contrastive_workspace_bytes(B) serves both calls and carries nothing from one to the other.  The additions leave IA_ABI_VERSION
- * at 20: nothing existing changes its meaning. */
+ * ia_contrastive_workspace_bytes(B) serves both calls and carries nothing from one to the other.  The additions did not
+ * bump IA_ABI_VERSION: nothing existing changed its meaning. */
 size_t ia_contrastive_workspace_bytes(int B);
 int ia_contrastive_fwd(const float* text, int ldt, const float* image, int ldi, const float* log_scale /* device scalar */,
                        float* sim /* [B, lds] fp32, scaled; kept for backward */, int lds, float* lse_row, float* lse_col,

@@ -24,13 +24,21 @@ class LayerGrads(C.Structure):
                                   "ln2_g", "ln2_b")]
 
 
+class RowLists(C.Structure):
+    """ia_row_lists: the lists of one row mask, each a device pointer of its own; None = the layer call builds that list"""
+    __slots__ = ()      # a name that is no member raises: ctypes would otherwise keep it as a Python attribute the library never sees
+    _fields_ = [(n, vp) for n in ("blocks", "packed", "slabs", "groups", "kblocks")]
+
+
+ROWS_DEAD_BWD, ROWS_DEAD_FWD = 1, 2      # the bits of ia_layer_cfg::masked_rows_dead (IA_ROWS_DEAD_*)
+
+
 class LayerCfg(C.Structure):
+    __slots__ = ()      # (as RowLists: a caller that still sets a member of an older layout fails here, not silently)
     _fields_ = [("B", i32), ("L", i32), ("H", i32), ("I", i32), ("nh", i32), ("pre_ln", i32), ("eps", f32),
                 ("hidden_drop", f32), ("attn_drop", f32), ("seed", u32), ("layer_id", u32), ("cu_seqlens", vp), ("total_tokens", i32),
-                ("out_q_rows", i32),      # (in what was the padding word in front of dx_colsum_out: no offset moves)
-                ("dx_colsum_out", vp), ("dy_colsum_done", i32), ("masked_rows_dead", i32),
-                ("row_blocks", vp), ("live_ktiles", vp),
-                ("out_row_live", vp), ("out_row_blocks", vp), ("out_live_ktiles", vp), ("out_row_groups", vp)]
+                ("out_q_rows", i32), ("dx_colsum_out", vp), ("dy_colsum_done", i32), ("masked_rows_dead", i32),
+                ("key_rows", RowLists), ("out_row_live", vp), ("out_rows", RowLists)]
 
 
 # name -> (restype, argtypes); must list every symbol include/itemalign.h declares
@@ -68,11 +76,9 @@ SIGNATURES = {
     "ia_gemm_dgrad_groups_rows": (i32, [vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, sz, vp]),
     "ia_debug_out_rows": (i32, [i32]),
     "ia_row_groups_packed_bytes": (sz, [i32]),
-    "ia_row_groups_packed_offset": (sz, [i32]),
     "ia_row_groups_packed": (i32, [vp, i32, vp, vp]),
     "ia_row_groups_packed_host": (i32, [vp, i32, vp]),
     "ia_row_slabs_bytes": (sz, [i32]),
-    "ia_row_slabs_offset": (sz, [i32]),
     "ia_row_slabs": (i32, [vp, i32, vp, vp]),
     "ia_row_slabs_host": (i32, [vp, i32, vp]),
     "ia_gemm_slabs_workspace_bytes": (sz, [i32]),
@@ -238,7 +244,7 @@ SIGNATURES = {
 _lib = None
 
 
-ABI_VERSION = 20      # = IA_ABI_VERSION of include/itemalign.h (tests/test_cabi_symbols.py keeps the two in step)
+ABI_VERSION = 21      # = IA_ABI_VERSION of include/itemalign.h (tests/test_cabi_symbols.py keeps the two in step)
 
 
 class ItemAlignError(RuntimeError):

@@ -35,7 +35,7 @@ struct FwdBufs {
   char* hpre;   // gelu'(pre-activation) (IA_EPI_BIAS_GELU C2); null in the forward-only form
   char* hact;   // FFN hidden activation
   float* lse; float* mean1; float* rstd1; float* mean2; float* rstd2;
-  RowSlots key;  // masked_rows_dead bit 2: the forward's own 32-row block list and 8-row slab list of the key mask
+  RowSlots key;  // IA_ROWS_DEAD_FWD: the forward's own 32-row block list and 8-row slab list of the key mask
   RowSlots out;  // out_row_live: the forward's own block list of it
   size_t bytes;
 };
@@ -85,7 +85,7 @@ FwdBufs carve_infer(const ia_layer_cfg* c, void* base) {
 
 struct Scratch {
   char* g0; char* g1; char* g2; char* gI; char* gqkv; float* delta; char* ws; size_t ws_bytes; char* gws; size_t gws_bytes;
-  RowSlots key;      // masked_rows_dead: the key mask's 32-row block mask (ia_kblock_mask), block list, block-packed list and 8-row slab list
+  RowSlots key;      // masked_rows_dead: the key mask's 32-row block mask (ia_kblock_mask), block-packed list and 8-row slab list
   RowSlots out;      // out_row_live: its 32-row block mask, block list and group list
   size_t bytes;
 };
@@ -108,8 +108,7 @@ Scratch carve_scratch(const ia_layer_cfg* c, void* base) {
   s.gws = a.take(s.gws_bytes);
   // masked_rows_dead: which 32-row blocks of the weight gradients' k hold a live row (one bit each, ia_kblock_mask)
   s.key.kmask = (uint32_t*)a.take(ia_kblock_mask_bytes((int)M));
-  // ... and which 32-row blocks of the data gradients do (the live list and the dead list, ia_row_blocks)
-  s.key.blocks = (int*)a.take(ia_row_blocks_bytes((int)M));
+  // ... and the data gradients' lists of them: the live blocks packed by whole groups, the 8-row slabs (below)
   s.key.packed = (int*)a.take(ia_row_groups_packed_bytes((int)M));
   s.out.kmask = (uint32_t*)a.take(ia_kblock_mask_bytes((int)M));
   s.out.blocks = (int*)a.take(ia_row_blocks_bytes((int)M));
@@ -121,12 +120,13 @@ Scratch carve_scratch(const ia_layer_cfg* c, void* base) {
 
 bool cfg_ok(const ia_layer_cfg* c) {
   if (c && c->cu_seqlens && (c->total_tokens <= 0 || c->total_tokens > c->B * c->L)) return false;
+  if (c && (c->masked_rows_dead & ~(IA_ROWS_DEAD_BWD | IA_ROWS_DEAD_FWD))) return false;   // (an older caller's layout bits: refused)
   return c && c->B > 0 && c->L > 0 && c->H > 0 && c->I > 0 && c->nh > 0 && c->H == c->nh * 64 && (c->H & 7) == 0 && (c->I & 7) == 0;
 }
 
-// Diagnostics: 0 withholds the block list from the data gradients of ia_layer_bwd2 (they run every row); returns the previous setting.
+// Diagnostics: 0 withholds their lists from the data gradients of ia_layer_bwd2 (they run every row); returns the previous setting.
 int g_dgrad_rows = 1;
-// ... and 0 makes layer_forward run every row under masked_rows_dead bit 2 (ia_debug_fwd_rows)
+// ... and 0 makes layer_forward run every row under IA_ROWS_DEAD_FWD (ia_debug_fwd_rows)
 int g_fwd_rows = 1;
 // ... and 0 makes the layer calls ignore ia_layer_cfg::out_row_live (ia_debug_out_rows)
 int g_out_rows = 1;
@@ -150,37 +150,26 @@ struct RowPlan {
 enum RowSource { KEY_MASK, OUT_ROWS };
 enum : unsigned { WANT_KMASK = 1, WANT_BLOCKS = 2, WANT_GROUPS = 4, WANT_PACKED = 8, WANT_SLABS = 16 };
 
-// The one place that knows where a caller's lists are and builds the missing ones.  `live`: the key mask (its filters exist under
-// masked_rows_dead bit 1 on padded rows only) or out_row_live; null: an every-row plan.  For each kind of `want` the plan takes the
-// caller's copy, else one built here into `slot` (one small launch).  The caller's copies (the mask is the same for every layer of a
-// stack and step, so a caller builds them once):
-//   key mask   row_blocks (32-row blocks); behind it in the same buffer the block-packed list at ia_row_groups_packed_offset (bit 3,
-//              value 4) and the slab list at ia_row_slabs_offset (bit 6, value 32); live_ktiles (64-row k-tiles; 32-row blocks under
-//              bit 4, value 8)
-//   out rows   out_row_blocks, out_row_groups, out_live_ktiles (32-row blocks under bit 5, value 16)
-// A mask built here holds 32-row blocks.  The packed list serves M <= 128 * 4096 rows (ia_row_groups_packed); beyond, none.
+// The one place that builds the lists a caller did not hand in.  `live`: the key mask (its filters exist under IA_ROWS_DEAD_BWD on padded
+// rows only) or out_row_live; null: an every-row plan.  For each kind of `want` the plan takes the caller's member of ia_row_lists
+// (key_rows / out_rows: the mask is the same for every layer of a stack and step, so a caller builds them once), else one built here
+// into `slot` (one small launch).  The packed list serves M <= 128 * 4096 rows (ia_row_groups_packed); beyond, none.
 int resolve_rows(const ia_layer_cfg* c, RowSource which, const uint8_t* live, unsigned want, int M, const RowSlots& slot, ia_stream_t st,
                  RowPlan* plan) {
   *plan = RowPlan{};
   const bool key = which == KEY_MASK;
-  const unsigned bits = (unsigned)c->masked_rows_dead;
-  if (!live || (key && (!(bits & 1) || c->cu_seqlens))) return IA_OK;
+  if (!live || (key && (!(c->masked_rows_dead & IA_ROWS_DEAD_BWD) || c->cu_seqlens))) return IA_OK;
   plan->live = live;
-  auto take = [&](IaRowFilter& f, IaRowFilter::Kind kind, const void* given, void* own) {
-    f = IaRowFilter{kind, given ? given : own};
-    return given ? IA_OK : ia_row_filter_build(kind, live, M, own, st);
+  const ia_row_lists& given = key ? c->key_rows : c->out_rows;
+  auto take = [&](IaRowFilter& f, IaRowFilter::Kind kind, const void* theirs, void* own) {
+    f = IaRowFilter{kind, theirs ? theirs : own};
+    return theirs ? IA_OK : ia_row_filter_build(kind, live, M, own, st);
   };
-  const char* const blocks = (const char*)(key ? c->row_blocks : c->out_row_blocks);
-  if (want & WANT_KMASK) {
-    const void* const given = key ? c->live_ktiles : c->out_live_ktiles;
-    IA_TRY(take(plan->kmask, (!given || (bits & (key ? 8 : 16))) ? IaRowFilter::KBLOCKS : IaRowFilter::KTILES, given, slot.kmask));
-  }
-  if (want & WANT_BLOCKS) IA_TRY(take(plan->blocks, IaRowFilter::BLOCKS, blocks, slot.blocks));
-  if (want & WANT_GROUPS) IA_TRY(take(plan->groups, IaRowFilter::GROUPS, key ? nullptr : c->out_row_groups, slot.groups));
-  if ((want & WANT_PACKED) && (size_t)M <= (size_t)128 * 4096)
-    IA_TRY(take(plan->packed, IaRowFilter::PACKED, (key && blocks && (bits & 4)) ? blocks + ia_row_groups_packed_offset(M) : nullptr, slot.packed));
-  if (want & WANT_SLABS)
-    IA_TRY(take(plan->slabs, IaRowFilter::SLABS, (key && blocks && (bits & 32)) ? blocks + ia_row_slabs_offset(M) : nullptr, slot.slabs));
+  if (want & WANT_KMASK) IA_TRY(take(plan->kmask, IaRowFilter::KBLOCKS, given.kblocks, slot.kmask));
+  if (want & WANT_BLOCKS) IA_TRY(take(plan->blocks, IaRowFilter::BLOCKS, given.blocks, slot.blocks));
+  if (want & WANT_GROUPS) IA_TRY(take(plan->groups, IaRowFilter::GROUPS, given.groups, slot.groups));
+  if ((want & WANT_PACKED) && (size_t)M <= (size_t)128 * 4096) IA_TRY(take(plan->packed, IaRowFilter::PACKED, given.packed, slot.packed));
+  if (want & WANT_SLABS) IA_TRY(take(plan->slabs, IaRowFilter::SLABS, given.slabs, slot.slabs));
   return IA_OK;
 }
 
@@ -200,8 +189,8 @@ int dgrad(const void* dy, int k_out, const void* w, const void* wt, int n_in, vo
                                 ws_bytes, st);
 }
 
-// Weight gradient dW[n_out, n_in] += dy[M, n_out]^T x[M, n_in]; with a mask, over the 32-row blocks (an ia_kblock_mask) or the 64-row
-// k-tiles (an ia_ktile_mask) that hold a live row only
+// Weight gradient dW[n_out, n_in] += dy[M, n_out]^T x[M, n_in]; with a mask (an ia_kblock_mask), over the 32-row blocks of k that hold
+// a live row only
 int wgrad(const void* dy, int n_out, const void* x, int n_in, float* dw, int M, IaRowFilter kmask, void* ws, size_t ws_bytes, ia_stream_t st) {
   return ia_gemm_wgrad_filtered(dy, n_out, x, n_in, dw, n_in, n_out, n_in, M, kmask, 1, ws, ws_bytes, st);
 }
@@ -252,7 +241,7 @@ int attn_bwd(const ia_layer_cfg* c, const char* qkv, const uint8_t* key_mask, co
                                 gqkv, gqkv + (size_t)H * 2, gqkv + (size_t)2 * H * 2, 3 * H, c->B, c->nh, c->L, scale, drop, seed, st);
     return rc ? rc : ia_colsum(gqkv, 3 * H, (int)rows_of(c), 3 * H, db_qkv, 1, ws, ws_bytes, st);
   }
-  const int flags = (ps ? IA_ATTN_Q_PRESCALED : 0) | ((c->masked_rows_dead & 1) ? IA_ATTN_MASKED_ROWS_DEAD : 0);
+  const int flags = (ps ? IA_ATTN_Q_PRESCALED : 0) | ((c->masked_rows_dead & IA_ROWS_DEAD_BWD) ? IA_ATTN_MASKED_ROWS_DEAD : 0);
   return ia_attn_bwd_bias_q_rows(flags, qkv, qkv + (size_t)H * 2, qkv + (size_t)2 * H * 2, 3 * H, key_mask, ctx, dctx, H, lse, delta, gqkv,
                                  gqkv + (size_t)H * 2, gqkv + (size_t)2 * H * 2, 3 * H, db_qkv, ws, ws_bytes, c->B, c->nh, c->L, scale, drop, seed,
                                  out_q_rows(c), st);
@@ -271,7 +260,7 @@ int layer_forward(const ia_layer_cfg* c, const ia_layer_weights* w, const void* 
     const float hidden_drop = keep ? c->hidden_drop : 0.f, attn_drop = keep ? c->attn_drop : 0.f;
     const uint32_t seed = keep ? c->seed : 0u, attn_seed = keep ? c->seed * 2654435761u + c->layer_id * 97u + 17u : 0u;
     const uint32_t ln1_stream = keep ? c->layer_id * 4u + 0u : 0u, ln2_stream = keep ? c->layer_id * 4u + 1u : 0u;
-    // masked_rows_dead bits 1 + 2 (padded rows, a key mask): nobody reads this layer's output at a masked position.  Such a row is a
+    // Both promises of masked_rows_dead (padded rows, a key mask): nobody reads this layer's output at a masked position.  Such a row is a
     // masked key of every attention (P = 0 exactly), no head reads it, and its incoming gradient is exactly zero, so whatever the stash
     // holds for it meets an exact zero in every weight-gradient sum: its values may be anything finite.  The GEMMs run the 32-row blocks
     // that hold a live row only (one block list per call, or the caller's), the LayerNorms the live rows only (dead rows leave as zeros).
@@ -282,7 +271,7 @@ int layer_forward(const ia_layer_cfg* c, const ia_layer_weights* w, const void* 
     // blocks).  The same readers, the same argument: a dead slab of a live block holds zeros where a dead block does, and is unwritten
     // where a dead block is (the two projection outputs).  (The forward-only activation epilogue has no slab form: it keeps the blocks.)
     RowPlan rows;
-    const bool gate = (c->masked_rows_dead & 3) == 3 && g_fwd_rows;
+    const bool gate = (c->masked_rows_dead & IA_ROWS_DEAD_FWD) && (c->masked_rows_dead & IA_ROWS_DEAD_BWD) && g_fwd_rows;
     IA_TRY(resolve_rows(c, KEY_MASK, gate ? key_mask : nullptr, WANT_BLOCKS | WANT_SLABS, M, s.key, st, &rows));
     // qkv = x Wqkv^T + b
     IA_TRY(qkv_proj(c, x, w, s.qkv, M, scale, st, rows.slabs));
@@ -414,12 +403,12 @@ extern "C" int ia_layer_bwd2(const ia_layer_cfg* c, const ia_layer_weights* w, c
   IA_TRY(resolve_rows(c, OUT_ROWS, out_live(c), WANT_KMASK | WANT_BLOCKS | WANT_GROUPS, M, k.out, st, &out));
   if (!c->pre_ln) {
     // masked_rows_dead: every gradient row of a masked position is exactly zero (ia_layer_cfg): the LayerNorm backward kernels skip them,
-    // the four weight gradients skip the 32-row blocks of k that hold nothing else (a caller's 64-row mask: the 64-row k-tiles), the two
+    // the four weight gradients skip the 32-row blocks of k that hold nothing else, the two
     // plain data gradients behind the attention and the QKV one run the live 8-row slabs (their dead rows are written as zeros: the
     // attention backward, the pair kernels and the embedding backward read every row), and the x gelu' + column-sums data gradient the
     // live blocks packed by whole 128-row groups.  ia_debug_dgrad_rows withholds the lists of the data gradients, not the mask.
     RowPlan key;
-    IA_TRY(resolve_rows(c, KEY_MASK, key_mask, WANT_KMASK | (g_dgrad_rows ? WANT_BLOCKS | WANT_PACKED | WANT_SLABS : 0), M, k.key, st, &key));
+    IA_TRY(resolve_rows(c, KEY_MASK, key_mask, WANT_KMASK | (g_dgrad_rows ? WANT_PACKED | WANT_SLABS : 0), M, k.key, st, &key));
     // behind the attention: out_row_live's plan when given (a subset of the live keys), else the key mask's
     const RowPlan& rows = out.live ? out : key;
     // The two residual additions of a post-LN layer make each LayerNorm output's gradient a sum of two terms; both LayerNorm

@@ -2234,9 +2234,6 @@ extern "C" size_t ia_row_slabs_bytes(int M_rows) {
   const size_t nsr = (size_t)(((M_rows + 7) / 8 + 31) & ~31);
   return (t256w::ROW_BLK_HDR + 2 * nsr) * sizeof(int);
 }
-// where the slab list sits behind an ia_row_blocks list (and the packed list behind that) in ONE buffer (ia_layer_cfg::masked_rows_dead
-// bit 6, value 32): byte offset from its start
-extern "C" size_t ia_row_slabs_offset(int M_rows) { return 2 * al256(ia_row_blocks_bytes(M_rows)); }      // (behind the block list and the packed list, which has the block list's size)
 extern "C" int ia_row_slabs(const uint8_t* row_live, int M_rows, int* list, hipStream_t stream) {
   (void)hipGetLastError();
   if (!row_live || !list || M_rows <= 0 || ((uintptr_t)list & 31)) return IA_ERR_ARG;
@@ -2350,8 +2347,6 @@ __global__ __launch_bounds__(64) void row_groups_packed_kernel(const uint8_t* __
 }
 }  // namespace
 extern "C" size_t ia_row_groups_packed_bytes(int M_rows) { return ia_row_blocks_bytes(M_rows); }
-// where the packed list sits behind an ia_row_blocks list in ONE buffer (ia_layer_cfg::masked_rows_dead bit 3): byte offset from its start
-extern "C" size_t ia_row_groups_packed_offset(int M_rows) { return al256(ia_row_blocks_bytes(M_rows)); }
 extern "C" int ia_row_groups_packed(const uint8_t* row_live, int M_rows, int* list, hipStream_t stream) {
   (void)hipGetLastError();
   if (!row_live || !list || M_rows <= 0 || ((uintptr_t)list & 31)) return IA_ERR_ARG;

@@ -352,7 +352,7 @@ class _EngineStack:
     def layer_params(self, i):
         return list(self.layers[i].parameters())
 
-    def layer_cfg(self, i, B, L, training, seed):
+    def layer_cfg(self, i, B, L, training, seed, rows=Fn.StackRows()):
         c = LayerCfg()
         c.B, c.L, c.H, c.I, c.nh = B, L, self.hidden_size, self.intermediate_size, self.num_heads
         c.pre_ln = int(self.pre_ln)
@@ -361,7 +361,7 @@ class _EngineStack:
         c.attn_drop = self.attn_drop if training else 0.0
         c.seed = seed
         c.layer_id = self.layer_id_base + i
-        c.masked_rows_dead = int(self.__dict__.get("_masked_rows_dead", 0))      # bit set: 1 = the backward skips, 2 = the forward too
+        c.masked_rows_dead = rows.masked_rows_dead
         return c
 
 
@@ -401,7 +401,7 @@ class RobertaEncoder(nn.Module, _EngineStack):
         """masked_rows_dead: the caller reads no hidden state of a masked position (heads on [CLS] / valid spans) -- the gradient arriving
         at such rows is then exactly zero in every layer and the attention backward may skip query blocks made of them (ia_layer_cfg).
         padded_rows_unread (with masked_rows_dead): the caller also accepts zeros there in the returned hidden states -- the forward
-        skips the padded rows as well (ia_layer_cfg::masked_rows_dead bit 2).
+        skips the padded rows as well (IA_ROWS_DEAD_FWD of ia_layer_cfg::masked_rows_dead).
         cls_only_read (with both of them): of the LAST hidden state the caller reads position 0 of every sequence and nothing else; the
         last layer then computes what follows its attention for those rows only (ia_layer_cfg::out_row_live) and the other rows of the
         last hidden state are zeros.  Position 0 of a sequence is such a row only where it is attended (Fn.cls_row_lists takes the key
@@ -411,9 +411,8 @@ class RobertaEncoder(nn.Module, _EngineStack):
         if attention_mask is not None:
             km = (attention_mask != 0).to(torch.uint8).contiguous()
         dead = bool(masked_rows_dead and km is not None)
-        self.__dict__["_masked_rows_dead"] = (1 if dead else 0) | (2 if dead and padded_rows_unread else 0)
-        self.__dict__["_out_rows_cls"] = bool(dead and padded_rows_unread and cls_only_read)
-        outs = Fn.EncoderStackFn.apply(hidden_states.reshape(B * L, H), self.anchor, self, km, B, L, torch.is_grad_enabled(), None)
+        rows = Fn.StackRows(dead, bool(dead and padded_rows_unread), bool(dead and padded_rows_unread and cls_only_read))
+        outs = Fn.EncoderStackFn.apply(hidden_states.reshape(B * L, H), self.anchor, self, km, B, L, torch.is_grad_enabled(), None, rows)
         return (hidden_states,) + tuple(o.view(B, L, H) for o in outs)
 
 

@@ -6,6 +6,7 @@ parameters' `.grad` views, see arena.py) by the kernels, with accumulate (+=) se
 return None for parameter inputs: autograd only carries activation gradients between Functions.
 """
 import ctypes as C
+from typing import NamedTuple
 
 import torch
 
@@ -148,6 +149,26 @@ def _build_row_lists(lib, mask_ptr, M, at, names):
         check(getattr(lib, f"ia_{name}")(mask_ptr, M, at[name], stream_ptr()), f"ia_{name}")
 
 
+class StackRows(NamedTuple):
+    """What the caller of an encoder stack promises about the rows it reads; the forward that knows computes it and hands it to
+    EncoderStackFn.  The default: every row of every hidden state is read."""
+    dead_bwd: bool = False      # no hidden state of a masked position reaches the loss (ia_layer_cfg::masked_rows_dead, IA_ROWS_DEAD_BWD)
+    dead_fwd: bool = False      # ... and zeros are accepted there in the hidden states (IA_ROWS_DEAD_FWD); only with dead_bwd
+    cls_only: bool = False      # of the LAST layer's output, row 0 of each sequence is read and nothing else (ia_layer_cfg::out_row_live)
+
+    @property
+    def masked_rows_dead(self):
+        return (_lib.ROWS_DEAD_BWD if self.dead_bwd else 0) | (_lib.ROWS_DEAD_FWD if self.dead_bwd and self.dead_fwd else 0)
+
+
+class ClsRowLists(NamedTuple):
+    buf: torch.Tensor           # the mask (B * L bytes) in front, its lists behind it
+    live: int                   # device pointers: ia_layer_cfg::out_row_live ...
+    blocks: int                 # ... and the members of out_rows
+    kblocks: int
+    groups: int
+
+
 _cls_row_lists = {}
 _CLS_ROW_LISTS_KEPT = 8      # (shape, stream) pairs: two towers, training and evaluation batch shapes
 
@@ -155,8 +176,6 @@ _CLS_ROW_LISTS_KEPT = 8      # (shape, stream) pairs: two towers, training and e
 def cls_row_lists(B, L, device, key_mask=None):
     """ia_layer_cfg::out_row_live and its lists for "row 0 of each of B sequences of L rows": one small tensor (the mask, then
     ia_row_blocks, ia_kblock_mask and ia_row_groups of it), built by launches on the current stream -- no host synchronisation.
-    Returns (tensor, mask ptr, blocks ptr, 32-row block mask ptr, groups ptr); the block mask goes into ia_layer_cfg::out_live_ktiles
-    together with masked_rows_dead bit 16.
     key_mask (uint8 [B, L]): row 0 of a sequence counts only where it is an attended position, so every out_row_live row is a live key
     by construction (a sequence whose position 0 is masked has no live row behind the attention, as under the key-mask filter); the
     lists then depend on the batch and are built per call.  Without one they depend on (B, L, device) only: built once per stream that
@@ -172,7 +191,7 @@ def cls_row_lists(B, L, device, key_mask=None):
     buf[:M:L] = 1 if key_mask is None else key_mask.reshape(-1)[::L].ne(0).to(torch.uint8)
     p = buf.data_ptr()
     _build_row_lists(lib, p, M, at, names)
-    got = (buf, p) + tuple(at[name] for name in names)
+    got = ClsRowLists(buf, p, *(at[name] for name in names))
     if key_mask is None and not torch.cuda.is_current_stream_capturing():
         while len(_cls_row_lists) >= _CLS_ROW_LISTS_KEPT:
             _cls_row_lists.pop(next(iter(_cls_row_lists)))
@@ -185,17 +204,19 @@ class EncoderStackFn(torch.autograd.Function):
     Returns every layer's output (the reference's `hidden_states[1:]`, text.py:1452)."""
 
     @staticmethod
-    def forward(ctx, x, anchor, stack, key_mask, B, L, keep, cu_seqlens=None):
+    def forward(ctx, x, anchor, stack, key_mask, B, L, keep, cu_seqlens=None, rows=StackRows()):
         # `keep` = grad mode of the caller (inside Function.forward grad mode is always off): keep the
         # per-layer activation stash for backward and, in train mode, apply dropout.
         # cu_seqlens (int32 [B+1], device): x holds the unpadded token rows of the B sequences back to back, L = the longest one.
+        # rows (StackRows): what the caller reads of the hidden states.
         lib = _lib.load()
         _need_gpu(x, "hidden states")
         ctx.set_materialize_grads(False)
         n = len(stack.layers)
         training = stack.training and keep
         seed = step_seed()
-        cfgs = [stack.layer_cfg(i, B, L, training, seed) for i in range(n)]
+        stack.last_stack_rows = rows      # for inspection (tests): nothing reads it back
+        cfgs = [stack.layer_cfg(i, B, L, training, seed, rows) for i in range(n)]
         if cu_seqlens is not None:
             for c in cfgs:
                 c.cu_seqlens, c.total_tokens = cu_seqlens.data_ptr(), x.shape[0]
@@ -203,36 +224,25 @@ class EncoderStackFn(torch.autograd.Function):
         outs, cur = [], x.contiguous()
         inputs = [cur]
         mp = ptr(key_mask)
-        # masked_rows_dead: the key mask is the same for every layer, forward and backward -- the 32-row block list and the live-block
-        # bitmask (ia_kblock_mask, flagged by masked_rows_dead bit 8) are built once here (one small tensor, kept for the backward) instead of once per layer call
+        # the key mask is the same for every layer, forward and backward: its lists (ia_layer_cfg::key_rows) are built once here (one small
+        # tensor, kept for the backward) instead of once per layer call
         ctx.row_lists = None
-        flag = cfgs[0].masked_rows_dead
-        if key_mask is not None and cu_seqlens is None and not cfgs[0].pre_ln and ((flag & 1 and keep) or (flag & 3) == 3):
+        if key_mask is not None and cu_seqlens is None and not stack.pre_ln and rows.dead_bwd and (keep or rows.dead_fwd):
             M = cur.shape[0]
-            packed = keep and M <= 128 * 4096              # the backward's x gelu' data gradient: the live blocks packed by whole groups
-            # ia_layer_cfg finds the packed list and the 8-row slab list behind row_blocks in the same buffer
-            lists, at = _row_lists(lib, M, x.device, ("row_blocks", "row_groups_packed", "row_slabs", "kblock_mask"))
-            assert at["row_groups_packed"] - at["row_blocks"] == lib.ia_row_groups_packed_offset(M)
-            assert at["row_slabs"] - at["row_blocks"] == lib.ia_row_slabs_offset(M)
-            # (the weight gradients' mask: nothing reads it without a backward)
-            build = ("row_blocks", "row_slabs") + (("row_groups_packed",) if packed else ()) + (("kblock_mask",) if keep else ())
-            _build_row_lists(lib, mp, M, at, build)
+            names = ("row_blocks", "row_slabs")
+            if keep:      # the backward's: the live blocks packed by whole groups (its x gelu' data gradient), the weight gradients' mask
+                names += (("row_groups_packed",) if M <= 128 * 4096 else ()) + ("kblock_mask",)
+            ctx.row_lists, at = _row_lists(lib, M, x.device, names)
+            _build_row_lists(lib, mp, M, at, names)
             for c in cfgs:
-                c.row_blocks, c.live_ktiles = at["row_blocks"], at["kblock_mask"] if keep else None
-                c.masked_rows_dead |= 32                   # ia_layer_cfg: the slab list sits behind row_blocks at ia_row_slabs_offset
-                if keep:
-                    c.masked_rows_dead |= 8                # ia_layer_cfg: live_ktiles is a 32-row block mask
-                if packed:
-                    c.masked_rows_dead |= 4                # ia_layer_cfg: the packed list sits behind row_blocks
-            ctx.row_lists = lists
-        # the caller reads row 0 of each sequence of the LAST layer's output and nothing else (stack._out_rows_cls, set by the model
-        # classes for the one head that does: CoCaForItemAlignment with ensemble "sum"): ia_layer_cfg::out_row_live on that layer only
+                k = c.key_rows
+                k.blocks, k.slabs, k.packed, k.kblocks = (at.get(name) for name in ("row_blocks", "row_slabs", "row_groups_packed", "kblock_mask"))
+        # the last layer under a head that reads row 0 of each sequence only: ia_layer_cfg::out_row_live on that layer
         ctx.out_lists = None
-        if stack.__dict__.get("_out_rows_cls") and cu_seqlens is None:
-            ctx.out_lists = cls_row_lists(B, L, x.device, key_mask)      # (kept until the backward has run)
+        if rows.cls_only and cu_seqlens is None:
+            ctx.out_lists = got = cls_row_lists(B, L, x.device, key_mask)      # (kept until the backward has run)
             c = cfgs[-1]
-            c.out_row_live, c.out_row_blocks, c.out_live_ktiles, c.out_row_groups = ctx.out_lists[1:]
-            c.masked_rows_dead |= 16                       # ia_layer_cfg: out_live_ktiles is a 32-row block mask
+            c.out_row_live, c.out_rows.blocks, c.out_rows.kblocks, c.out_rows.groups = got.live, got.blocks, got.kblocks, got.groups
             c.out_q_rows = 1      # the mask is zero behind position 0 of every sequence: the layer's attention runs that query block only
         if keep:
             stash_bytes = lib.ia_layer_stash_bytes(C.byref(cfgs[0]))
@@ -308,7 +318,7 @@ class EncoderStackFn(torch.autograd.Function):
         ctx.inputs = None
         ctx.row_lists = None
         ctx.out_lists = None
-        return dy, None, None, None, None, None, None, None
+        return dy, None, None, None, None, None, None, None, None
 
 
 # ------------------------------------------------------------------------------------------ small ops

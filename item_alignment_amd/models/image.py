@@ -104,9 +104,8 @@ class VisionTransformer(HipModule, _EngineStack):
                 raise ValueError(f"Input image size ({t.shape[-2]}*{t.shape[-1]}) doesn't match model ({self.img_size}*{self.img_size}).")
         N, H = self.num_patches + 1, self.embed_dim
         tok = Fn.PatchEmbedFn.apply(xs[0], self.anchor, self, *xs[1:])
-        self.__dict__["_out_rows_cls"] = bool(cls_only)
-        outs = Fn.EncoderStackFn.apply(tok, self.anchor, self, None, B, N, torch.is_grad_enabled(), None)
-        row_live = Fn.cls_row_lists(B, N, tok.device)[0][:B * N] if cls_only else None
+        outs = Fn.EncoderStackFn.apply(tok, self.anchor, self, None, B, N, torch.is_grad_enabled(), None, Fn.StackRows(cls_only=bool(cls_only)))
+        row_live = Fn.cls_row_lists(B, N, tok.device).buf[:B * N] if cls_only else None
         y = Fn.LayerNormFn.apply(outs[-1], self.anchor, self.norm, 1e-6, row_live)
         return y.view(B, N, H)
 

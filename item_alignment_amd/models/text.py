@@ -125,7 +125,7 @@ class RobertaModel(HipModule, PretrainedMixin):
         """cls_only_read (with padded_rows_unread): of last_hidden_state the caller reads [:, 0] and nothing else, and reads no other hidden
         state -- the last layer then runs what follows its attention for the [CLS] rows only (RobertaEncoder.forward).  Opt-in.
         padded_rows_unread: the caller reads no hidden state of a padded position and accepts zeros there (as under IA_UNPAD): the
-        forward then skips the padded rows too (ia_layer_cfg::masked_rows_dead bit 2).  Opt-in -- a direct caller gets every position
+        forward then skips the padded rows too (IA_ROWS_DEAD_FWD of ia_layer_cfg::masked_rows_dead).  Opt-in -- a direct caller gets every position
         of last_hidden_state computed."""
         (self._root if "_root" in self.__dict__ else self).ensure_arena()
         if input_ids is None:
@@ -198,9 +198,7 @@ class RobertaModel(HipModule, PretrainedMixin):
         pk = take(2)
         order = torch.argsort(pk, stable=True).to(torch.int32)          # backward walks the rows position by position (embed.hip)
         e = Fn.EmbedLNFn.apply(emb.anchor, emb, take(0), take(1), pk, None, None, p, emb.stream_id, order)
-        # a packed batch has no masked row: what an earlier padded call asked of the stack (RobertaEncoder.forward) does not apply
-        enc.__dict__["_masked_rows_dead"], enc.__dict__["_out_rows_cls"] = 0, False
-        outs = Fn.EncoderStackFn.apply(e, enc.anchor, enc, None, S, Lmax, torch.is_grad_enabled(), cu)
+        outs = Fn.EncoderStackFn.apply(e, enc.anchor, enc, None, S, Lmax, torch.is_grad_enabled(), cu, Fn.StackRows())     # no masked row
         return (e,) + tuple(outs), idx, cu
 
 

@@ -109,7 +109,7 @@ def test_packed_dgelu_colsum_equals_dense(gpu, shadow):
 
 def test_layer_backward_with_packed_dgelu_equals_every_row(gpu):
     """ia_layer_bwd2 (post-LN, masked_rows_dead = 3) with the data gradients' lists withheld (ia_debug_dgrad_rows(0): every row) against the
-    filtered call -- the packed list built per call, and handed in behind row_blocks (masked_rows_dead bit 3).  Every gradient is equal."""
+    filtered call -- the packed list built per call, and handed in (ia_layer_cfg::key_rows.packed).  Every gradient is equal."""
     from item_alignment_amd import _lib
     from item_alignment_amd._lib import LayerCfg, LayerGrads, LayerWeights
     from test_engine_gpu import make_layer
@@ -131,17 +131,16 @@ def test_layer_backward_with_packed_dgelu_equals_every_row(gpu):
     dy = (randn((M, H), 6, gpu) * live[:, None]).to(BF).contiguous()                  # zero at the masked positions: the contract
     base = dict(B=B, L=L, H=H, I=I, nh=NH, pre_ln=0, eps=1e-12, hidden_drop=0.1, attn_drop=0.1, seed=11, layer_id=2, masked_rows_dead=3)
     st = stream()
-    # the caller's lists in one buffer: ia_row_blocks, then the packed list at ia_row_groups_packed_offset
-    off = lib.ia_row_groups_packed_offset(M)
-    lists = torch.zeros(off + lib.ia_row_groups_packed_bytes(M), device=gpu, dtype=torch.uint8)
-    _lib.check(lib.ia_row_blocks(live.data_ptr(), M, lists.data_ptr(), st), "ia_row_blocks")
-    _lib.check(lib.ia_row_groups_packed(live.data_ptr(), M, lists.data_ptr() + off, st), "ia_row_groups_packed")
+    # the caller's lists: ia_row_blocks and the packed list, each in a tensor of its own
+    blocks = torch.zeros(lib.ia_row_blocks_bytes(M), device=gpu, dtype=torch.uint8)
+    packed = torch.zeros(lib.ia_row_groups_packed_bytes(M), device=gpu, dtype=torch.uint8)
+    _lib.check(lib.ia_row_blocks(live.data_ptr(), M, blocks.data_ptr(), st), "ia_row_blocks")
+    _lib.check(lib.ia_row_groups_packed(live.data_ptr(), M, packed.data_ptr(), st), "ia_row_groups_packed")
 
     def step(handed):
         cfg = LayerCfg(**base)
         if handed:
-            cfg.row_blocks = lists.data_ptr()
-            cfg.masked_rows_dead = 3 | 4
+            cfg.key_rows.blocks, cfg.key_rows.packed = blocks.data_ptr(), packed.data_ptr()
         stash = torch.full((lib.ia_layer_stash_bytes(C.byref(cfg)),), 0xFF, device=gpu, dtype=torch.uint8)
         y = torch.zeros((M, H), device=gpu, dtype=BF)
         _lib.check(lib.ia_layer_fwd(C.byref(cfg), C.byref(w), x.data_ptr(), mask.data_ptr(), y.data_ptr(), stash.data_ptr(), st), "fwd")

@@ -9,7 +9,7 @@ The layer of tests/test_engine_dgrad_rows_gpu.py: B = 40, H = 1024, nh = 16, I =
 
 Checks: y and every stash buffer are equal at the live rows and finite everywhere; ia_layer_bwd2 from each of the two stashes, with dy
 zero at the masked positions, returns torch.equal dx, dx2 and parameter gradients; ia_layer_fwd_infer agrees on y in the same way.  One
-case hands the calls the block list and the k-tile mask from the host builders (ia_layer_cfg::row_blocks / live_ktiles), the others
+case hands the calls the block list and the block mask from the host builders (ia_layer_cfg::key_rows.blocks / .kblocks), the others
 leave them NULL (the engine builds its own): same results."""
 import ctypes as C
 
@@ -68,11 +68,11 @@ def test_layer_forward_row_skip_equals_dense(gpu, L, host_lists):
     if host_lists:
         live_np = np.ascontiguousarray(mask.view(-1).cpu().numpy())
         rb = np.zeros(lib.ia_row_blocks_bytes(M) // 4, np.int32)
-        kt = np.zeros(lib.ia_ktile_mask_bytes(M) // 4, np.int32)
+        kb = np.zeros(lib.ia_kblock_mask_bytes(M) // 4, np.int32)
         assert lib.ia_row_blocks_host(live_np.ctypes.data, M, rb.ctypes.data) == 0
-        assert lib.ia_ktile_mask_host(live_np.ctypes.data, M, kt.ctypes.data) == 0
-        lists = (torch.from_numpy(rb).to(gpu), torch.from_numpy(kt).to(gpu))
-        cfg.row_blocks, cfg.live_ktiles = lists[0].data_ptr(), lists[1].data_ptr()
+        assert lib.ia_kblock_mask_host(live_np.ctypes.data, M, kb.ctypes.data) == 0
+        lists = (torch.from_numpy(rb).to(gpu), torch.from_numpy(kb).to(gpu))
+        cfg.key_rows.blocks, cfg.key_rows.kblocks = lists[0].data_ptr(), lists[1].data_ptr()
 
     def forward(skip):
         stash = torch.full((lib.ia_layer_stash_bytes(C.byref(cfg)),), 0xFF, device=gpu, dtype=torch.uint8)

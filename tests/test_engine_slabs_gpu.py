@@ -12,8 +12,8 @@ contract on the path that computes every row.  B = 40, L = 255, H = 1024, nh = 1
 smallest layer whose GEMMs all filter (asserted): there the slab kernels run.  M = 10200 is no multiple of 128, so the QKV projection's
 scaled columns take the guarded one-tile launch on the last rows; 10200 = 8 x 1275: the last slab is whole, the sequences' ends are not.
 
-Each case runs once with the engine building its lists and once with the lists handed in: ia_row_blocks at row_blocks, the slab list at
-ia_row_slabs_offset behind it, masked_rows_dead bit 6 (value 32)."""
+Each case runs once with the engine building its lists and once with the lists handed in: ia_row_blocks and ia_row_slabs of the mask in
+ia_layer_cfg::key_rows.blocks / .slabs."""
 import ctypes as C
 
 import pytest
@@ -78,14 +78,11 @@ def test_two_layers_slab_path_equals_dense(gpu, B, L, H, NH, I, filters, handed_
             for i in range(2)]
     lists = None
     if handed_in:
-        so = lib.ia_row_slabs_offset(M)
-        assert so >= lib.ia_row_blocks_bytes(M) and so % 256 == 0
-        lists = torch.full((so + lib.ia_row_slabs_bytes(M),), 0xFF, device=gpu, dtype=torch.uint8)
-        _lib.check(lib.ia_row_blocks(mask.data_ptr(), M, lists.data_ptr(), st), "ia_row_blocks")
-        _lib.check(lib.ia_row_slabs(mask.data_ptr(), M, lists.data_ptr() + so, st), "ia_row_slabs")
+        lists = [torch.full((getattr(lib, f"ia_{name}_bytes")(M),), 0xFF, device=gpu, dtype=torch.uint8) for name in ("row_blocks", "row_slabs")]
+        _lib.check(lib.ia_row_blocks(mask.data_ptr(), M, lists[0].data_ptr(), st), "ia_row_blocks")
+        _lib.check(lib.ia_row_slabs(mask.data_ptr(), M, lists[1].data_ptr(), st), "ia_row_slabs")
         for c in cfgs:
-            c.row_blocks = lists.data_ptr()
-            c.masked_rows_dead |= 32
+            c.key_rows.blocks, c.key_rows.slabs = lists[0].data_ptr(), lists[1].data_ptr()
 
     def run(skip):
         was_f, was_d = lib.ia_debug_fwd_rows(1 if skip else 0), lib.ia_debug_dgrad_rows(1 if skip else 0)

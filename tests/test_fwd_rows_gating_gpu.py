@@ -32,7 +32,7 @@ def run(model, call, skip, text_model):
         torch.manual_seed(5)
         model.param_arena.zero_grad()
         out = call(model)
-        flag = text_model.encoder.__dict__["_masked_rows_dead"]
+        flag = text_model.encoder.last_stack_rows.masked_rows_dead
         grads = None
         if out.loss is not None:
             out.loss.backward()

@@ -202,12 +202,12 @@ def test_layer_with_out_row_live_equals_every_row_call(gpu, shape, host_lists):
     lists = None
     if host_lists:
         live_np = np.ascontiguousarray(live.cpu().numpy())
-        rb, kt, rg = (np.zeros(n // 4, np.int32) for n in (lib.ia_row_blocks_bytes(M), lib.ia_ktile_mask_bytes(M), lib.ia_row_groups_bytes(M)))
+        rb, kb, rg = (np.zeros(n // 4, np.int32) for n in (lib.ia_row_blocks_bytes(M), lib.ia_kblock_mask_bytes(M), lib.ia_row_groups_bytes(M)))
         assert lib.ia_row_blocks_host(live_np.ctypes.data, M, rb.ctypes.data) == 0
-        assert lib.ia_ktile_mask_host(live_np.ctypes.data, M, kt.ctypes.data) == 0
+        assert lib.ia_kblock_mask_host(live_np.ctypes.data, M, kb.ctypes.data) == 0
         assert lib.ia_row_groups_host(live_np.ctypes.data, M, rg.ctypes.data) == 0
-        lists = [torch.from_numpy(a).to(gpu) for a in (rb, kt, rg)]
-        cfg_f.out_row_blocks, cfg_f.out_live_ktiles, cfg_f.out_row_groups = (t.data_ptr() for t in lists)
+        lists = [torch.from_numpy(a).to(gpu) for a in (rb, kb, rg)]
+        cfg_f.out_rows.blocks, cfg_f.out_rows.kblocks, cfg_f.out_rows.groups = (t.data_ptr() for t in lists)
     mp = None if mask is None else mask.data_ptr()
     st = stream()
 
@@ -299,7 +299,7 @@ def record_cfgs(stack, seen):
 
 
 def out_fields(c):
-    return (c.out_row_live, c.out_row_blocks, c.out_live_ktiles, c.out_row_groups)
+    return (c.out_row_live, c.out_rows.blocks, c.out_rows.kblocks, c.out_rows.groups)
 
 
 def train_step(model, batch, on):
@@ -432,7 +432,7 @@ def test_masked_first_position_is_no_out_row(coca_model):
     mask[2, 0] = 0                                   # sequence 2: position 0 masked, later positions attended
     assert mask[2].any()
     lists = Fn.cls_row_lists(mask.shape[0], mask.shape[1], mask.device, (mask != 0).to(torch.uint8))
-    live = lists[0][: mask.numel()].view(mask.shape)
+    live = lists.buf[: mask.numel()].view(mask.shape)
     assert live[:, 1:].sum().item() == 0 and live[2, 0].item() == 0 and live[:, 0].sum().item() == mask.shape[0] - 1
 
     def step(on):

@@ -90,25 +90,38 @@ def header_text():
     return open(os.path.join(os.path.dirname(_lib._HERE), "include", "itemalign.h")).read()
 
 
-def test_layer_cfg_layout_is_abi_20():
-    lib = _lib.load()
-    header = header_text()
-    assert _lib.ABI_VERSION == 20 == lib.ia_abi_version() == int(re.search(r"#define IA_ABI_VERSION (\d+)", header).group(1))
-    body = re.search(r"typedef struct \{(\s*int B, L, H, I, nh;.*?)\} ia_layer_cfg;", header, re.S).group(1)
+def member_names(header, first, struct):
+    body = re.search(r"typedef struct \{(\s*%s.*?)\} %s;" % (re.escape(first), struct), header, re.S).group(1)
     body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
     names = []
     for decl in re.findall(r"([^;]+);", body):
         for part in decl.split(","):
             names.append(re.findall(r"[A-Za-z_][A-Za-z_0-9]*", part)[-1])
+    return names
+
+
+def test_layer_cfg_layout_is_abi_21():
+    lib = _lib.load()
+    header = header_text()
+    assert _lib.ABI_VERSION == 21 == lib.ia_abi_version() == int(re.search(r"#define IA_ABI_VERSION (\d+)", header).group(1))
+    names = member_names(header, "int B, L, H, I, nh;", "ia_layer_cfg")
     assert names == [n for n, _ in _lib.LayerCfg._fields_]
-    assert names[-4:] == ["out_row_live", "out_row_blocks", "out_live_ktiles", "out_row_groups"]
-    # the new members sit behind the ABI 19 ones, pointer-sized and pointer-aligned
-    f = _lib.LayerCfg
-    assert f.out_row_live.offset == f.live_ktiles.offset + 8
-    assert [getattr(f, n).offset - f.out_row_live.offset for n in names[-4:]] == [0, 8, 16, 24]
-    assert C.sizeof(f) == f.out_row_groups.offset + 8
+    assert names[-4:] == ["masked_rows_dead", "key_rows", "out_row_live", "out_rows"]
+    lists = member_names(header, "const int* blocks;", "ia_row_lists")
+    assert lists == [n for n, _ in _lib.RowLists._fields_] == ["blocks", "packed", "slabs", "groups", "kblocks"]
+    assert (_lib.ROWS_DEAD_BWD, _lib.ROWS_DEAD_FWD) == tuple(int(re.search(r"#define IA_ROWS_DEAD_%s (\d+)" % n, header).group(1)) for n in ("BWD", "FWD")) == (1, 2)
+    # five pointers a list struct, each on its own; the two structs and out_row_live between them pointer-aligned, nothing behind them
+    f, r = _lib.LayerCfg, _lib.RowLists
+    assert [getattr(r, n).offset for n in lists] == [0, 8, 16, 24, 32] and C.sizeof(r) == 40
+    assert f.key_rows.offset == f.masked_rows_dead.offset + 4 and f.key_rows.offset % 8 == 0
+    assert f.out_row_live.offset == f.key_rows.offset + 40 and f.out_rows.offset == f.out_row_live.offset + 8
+    assert C.sizeof(f) == f.out_rows.offset + 40
     c = f()
-    assert c.out_row_live is None and c.out_row_blocks is None and c.out_live_ktiles is None and c.out_row_groups is None
+    assert c.out_row_live is None and all(getattr(rows, n) is None for rows in (c.key_rows, c.out_rows) for n in lists)
+    # a member of the ABI 20 layout is no attribute: setting one raises instead of being kept where the library never looks
+    for stale, obj in (("row_blocks", c), ("live_ktiles", c), ("out_row_groups", c), ("ktiles", c.key_rows)):
+        with pytest.raises(AttributeError):
+            setattr(obj, stale, 256)
 
 
 def test_new_entry_points_are_declared_bound_and_exported():
