@@ -666,6 +666,28 @@ size_t ia_kgpt_lp_workspace_bytes(int B, int D);
 int ia_kgpt_lp_rank(const float* ent, const float* rel, const int64_t* h, const int64_t* t, const int64_t* r, int B, int D, int n_ent,
                     int n_rel, int norm, int side, const int64_t* grp_off, const int64_t* grp_ids, int n_grp, const int64_t* q_grp,
                     int64_t* rank, int64_t* filt_rank, float* scores, void* workspace, size_t workspace_bytes, ia_stream_t stream);
+/* Knowledge-graph completion (torchkge EntityInference / RelationInference): the k best candidates of each of B queries over the raw
+ * tables (no normalisation, no projection term), without a [B, n_cand] matrix.  IA_KGPT_TOPK_TAILS: a = head ids, b = relation ids,
+ * q = ent[a] + rel[b], candidates = the n_ent entity rows; IA_KGPT_TOPK_HEADS: a = tail ids, b = relation ids, q = ent[a] - rel[b],
+ * candidates = entity rows; IA_KGPT_TOPK_RELS: a = head ids, b = tail ids, q = ent[b] - ent[a], candidates = the n_rel relation rows.
+ * score_c = -d(q, cand_c), d as in ia_kgpt_lp_rank (one fp32 accumulator per pair summed in k order): in the entity modes the scores
+ * are bit-identical to what ia_kgpt_lp_rank(..., scores) stores for the same pair.  idx (int64 [B, k]) / score (fp32 [B, k]): row b
+ * holds the k best candidates of query b in the total order (score descending, id ascending); the result is a function of the tables,
+ * the query and the filter alone (not of B, the query's place in the batch, the split count or the launch order).  Filter: the layout
+ * of ia_kgpt_lp_rank (grp_off / grp_ids int64 CSR, each group a sorted list of unique candidate ids, q_grp[b] outside [0, n_grp): no
+ * filter for that query; grp_off == NULL: no filter); the members of the query's group are never returned.  Unused trailing slots
+ * (fewer than k candidates left, k > n_cand) hold idx = -1, score = -inf, and so does the whole row of a query whose a or b lies
+ * outside its table (it reads nothing).  1 <= k <= IA_KGPT_TOPK_MAX_K, D % 4 == 0, norm 1 or 2.  max_splits caps the number of
+ * candidate ranges the scan is split into (0: as the rank scan chooses); the result does not depend on it.  workspace >=
+ * ia_kgpt_topk_workspace_bytes(B, D, n_cand, k, max_splits) = O(B D + B splits k), independent of n_cand. */
+#define IA_KGPT_TOPK_TAILS 0
+#define IA_KGPT_TOPK_HEADS 1
+#define IA_KGPT_TOPK_RELS 2
+#define IA_KGPT_TOPK_MAX_K 64
+size_t ia_kgpt_topk_workspace_bytes(int B, int D, int n_cand, int k, int max_splits);
+int ia_kgpt_topk(const float* ent, const float* rel, const int64_t* a, const int64_t* b, int B, int D, int n_ent, int n_rel, int norm,
+                 int mode, const int64_t* grp_off, const int64_t* grp_ids, int n_grp, const int64_t* q_grp, int k, int max_splits,
+                 int64_t* idx, float* score, void* workspace, size_t workspace_bytes, ia_stream_t stream);
 
 /* ---- whole-layer drivers: one call = every launch of one encoder layer, in order, on `stream`.
  * Weights: bf16 shadows for the GEMM operands, fp32 masters for bias / LayerNorm vectors. */

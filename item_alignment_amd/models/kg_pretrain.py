@@ -1,6 +1,8 @@
 """Knowledge-graph pretraining of the PKGM / TransE embeddings (reference pkgm_pretrain.py over its vendored torchkge fork) on the
 HIP engine: the models, the margin loss, the Bernoulli negative sampler, coupled-L2 Adam, the learning-rate schedule and the
-trainer loop with the reference's quirks (INTEGRATION.md "PKGM knowledge-graph pretraining").
+trainer loop with the reference's quirks (INTEGRATION.md "PKGM knowledge-graph pretraining"); then what the trained tables are used
+for: link-prediction ranks (LinkPredictionEvaluator, ia_kgpt_lp_rank) and completion (EntityInference / RelationInference,
+ia_kgpt_topk).
 
 The tables (`ent_emb.weight`, `rel_emb.weight`) and the projection (`proj_mat.weight`) are fp32 and stay on the device; their
 gradients are dense fp32 buffers that `ia_kgpt_score` accumulates into and `CoupledAdam.step` (ia_kgpt_adam_l2) clears.
@@ -406,11 +408,8 @@ class _DeviceGroups:
         self.n = len(groups)
 
 
-def lp_rank(ent, rel, h, t, r, norm, side, groups=None, q_grp=None, want_scores=False, workspace=None):
-    """One ia_kgpt_lp_rank call over B queries on one side (LP_TAIL: rank t among all entities, LP_HEAD: rank h), on the raw tables.
-    groups: a FilterGroups (or its _DeviceGroups) and q_grp the group index of each query (int64 [B], -1 = none); None = unfiltered.
-    Returns (rank, filt_rank) int64 [B], and the fp32 [B, n_ent] scores the ranks compare when want_scores."""
-    lib = _lib.load()
+def _check_tables(ent, rel):
+    """The tables the ranking and completion kernels read: contiguous 2-D fp32 of one width on one GPU.  Returns the device."""
     if not ent.is_cuda:
         raise RuntimeError("link-prediction ranking runs on the GPU")
     dev = ent.device
@@ -420,6 +419,15 @@ def lp_rank(ent, rel, h, t, r, norm, side, groups=None, q_grp=None, want_scores=
                              f"(contiguous: {x.is_contiguous()})")
     if rel.shape[1] != ent.shape[1]:
         raise ValueError(f"ent and rel widths differ: {ent.shape[1]} != {rel.shape[1]}")
+    return dev
+
+
+def lp_rank(ent, rel, h, t, r, norm, side, groups=None, q_grp=None, want_scores=False, workspace=None):
+    """One ia_kgpt_lp_rank call over B queries on one side (LP_TAIL: rank t among all entities, LP_HEAD: rank h), on the raw tables.
+    groups: a FilterGroups (or its _DeviceGroups) and q_grp the group index of each query (int64 [B], -1 = none); None = unfiltered.
+    Returns (rank, filt_rank) int64 [B], and the fp32 [B, n_ent] scores the ranks compare when want_scores."""
+    lib = _lib.load()
+    dev = _check_tables(ent, rel)
     h, t, r = (x.to(dev).contiguous().long() for x in (h, t, r))
     B = h.shape[0]
     n_ent, D = ent.shape
@@ -535,3 +543,125 @@ class LinkPredictionEvaluator:
 
     def print_results(self, k=None, n_digits=3):
         print(self.results_text(k, n_digits), end="", flush=True)
+
+
+# ------------------------------------------------------------------------------------------------ completion (torchkge inference.py)
+TOPK_TAILS, TOPK_HEADS, TOPK_RELS = 0, 1, 2
+TOPK_MAX_K = 64
+
+
+class WrongArgumentsError(ValueError):
+    """torchkge.exceptions.WrongArgumentsError."""
+
+
+def relation_filter_groups(kgs):
+    """The filter of relation completion over every fact of `kgs`: FilterGroups keyed by (head, tail) whose members are the known
+    relations -- torchkge's dict_of_rels[(h, t)].  The key base is n_ent (key = head * n_ent + tail)."""
+    kgs = [k for k in kgs if k is not None]
+    h, t, r = (np.concatenate([getattr(k, a).numpy() for k in kgs]) for a in ("head_idx", "tail_idx", "relations"))
+    return FilterGroups.build(h, t, r, kgs[0].n_ent)
+
+
+def filter_groups_from_dict(dictionary, key_base):
+    """A torchkge filter dictionary {(key1, key2): iterable of ids} (dict_of_tails, dict_of_heads, dict_of_rels) as FilterGroups with
+    keys key1 * key_base + key2: key_base = n_rel for the entity dictionaries, n_ent for the relation dictionary."""
+    a, b, m = [], [], []
+    for (k1, k2), ids in dictionary.items():
+        ids = [int(i) for i in ids]
+        a += [int(k1)] * len(ids)
+        b += [int(k2)] * len(ids)
+        m += ids
+    return FilterGroups.build(np.asarray(a, np.int64), np.asarray(b, np.int64), np.asarray(m, np.int64), key_base)
+
+
+def kg_topk(ent, rel, a, b, norm, mode, k, groups=None, q_grp=None, max_splits=0, workspace=None):
+    """One ia_kgpt_topk call: the k best candidates of B queries on the raw tables.  TOPK_TAILS: a = heads, b = relations;
+    TOPK_HEADS: a = tails, b = relations; TOPK_RELS: a = heads, b = tails (candidates = relation rows).  groups / q_grp as in lp_rank:
+    the members of a query's group are never returned.  Returns (idx int64 [B, k], score fp32 [B, k]) on the device, best first in the
+    order (score descending, id ascending); unused slots hold -1 / -inf."""
+    lib = _lib.load()
+    dev = _check_tables(ent, rel)
+    a, b = (torch.as_tensor(x).to(dev).contiguous().long() for x in (a, b))
+    B = a.shape[0]
+    if a.shape != (B,) or b.shape != (B,):
+        raise ValueError(f"a and b must be 1-D id tensors of one length, got {tuple(a.shape)} and {tuple(b.shape)}")
+    if not 1 <= k <= TOPK_MAX_K:
+        raise ValueError(f"k must lie in [1, {TOPK_MAX_K}], got {k}")
+    n_ent, D = ent.shape
+    n_cand = rel.shape[0] if mode == TOPK_RELS else n_ent
+    idx = torch.empty(B, k, device=dev, dtype=torch.int64)
+    score = torch.empty(B, k, device=dev, dtype=F32)
+    if B == 0:
+        return idx, score
+    nbytes = lib.ia_kgpt_topk_workspace_bytes(B, D, n_cand, k, max_splits)
+    if workspace is None or workspace.numel() < nbytes:
+        workspace = torch.empty(max(nbytes, 1), device=dev, dtype=torch.uint8)
+    gp = (None, None, 0, None)
+    if groups is not None:
+        dg = groups if isinstance(groups, _DeviceGroups) else _DeviceGroups(groups, dev)
+        qg = torch.as_tensor(q_grp, dtype=torch.int64).to(dev).contiguous()
+        gp = (dg.off.data_ptr(), dg.ids.data_ptr(), dg.n, qg.data_ptr())
+    check(lib.ia_kgpt_topk(ent.data_ptr(), rel.data_ptr(), a.data_ptr(), b.data_ptr(), B, D, n_ent, rel.shape[0], norm, mode, *gp, k,
+                           max_splits, idx.data_ptr(), score.data_ptr(), workspace.data_ptr(), workspace.numel(), stream_ptr()),
+          "ia_kgpt_topk")
+    return idx, score
+
+
+class _Inference:
+    """Common part of EntityInference / RelationInference: queries (a, b) in order, b_size per kernel call."""
+
+    def _setup(self, model, a, b, top_k, mode, dictionary, key_base):
+        self.model, self.top_k, self.dictionary = model, top_k, dictionary
+        self._a, self._b, self._mode = torch.as_tensor(a).long().cpu(), torch.as_tensor(b).long().cpu(), mode
+        if isinstance(dictionary, dict):
+            dictionary = filter_groups_from_dict(dictionary, key_base)       # once, on the host
+        self._groups = dictionary
+        n = len(self._a)
+        self.predictions = torch.empty(n, top_k, dtype=torch.int64)
+        self.scores = torch.empty(n, top_k, dtype=F32)
+
+    @torch.no_grad()
+    def evaluate(self, b_size, verbose=True):
+        """Fills .predictions (int64 [n, top_k]) and .scores (fp32 [n, top_k]) on the CPU; they do not depend on b_size.  verbose is
+        accepted for torchkge's signature; there is no progress bar."""
+        if b_size <= 0:
+            raise ValueError(f"b_size must be positive, got {b_size}")
+        ent, rel = self.model.ent_emb.weight.data, self.model.rel_emb.weight.data
+        if not ent.is_cuda:
+            raise RuntimeError("link-prediction ranking runs on the GPU")
+        dev = ent.device
+        n = len(self._a)
+        a, b = self._a.to(dev), self._b.to(dev)
+        dg = qg = None
+        if self._groups is not None:
+            dg = _DeviceGroups(self._groups, dev)
+            qg = torch.from_numpy(self._groups.group_of(self._a.numpy(), self._b.numpy())).to(dev)
+        pred = torch.empty(n, self.top_k, device=dev, dtype=torch.int64)
+        sc = torch.empty(n, self.top_k, device=dev, dtype=F32)
+        for i0 in range(0, n, b_size):
+            sl = slice(i0, min(n, i0 + b_size))
+            pred[sl], sc[sl] = kg_topk(ent, rel, a[sl], b[sl], self.model.norm, self._mode, self.top_k, dg, None if qg is None else qg[sl])
+        self.predictions, self.scores = pred.cpu(), sc.cpu()
+
+
+class EntityInference(_Inference):
+    """torchkge EntityInference on the device: the top_k entities that complete (known entity, known relation), the known entity being
+    the head (missing='tails') or the tail (missing='heads'), scored on the model's raw tables (PKGM infers like TransE).  dictionary:
+    a FilterGroups or torchkge's dict_of_tails / dict_of_heads {(entity, relation): ids}; its members are never predicted."""
+
+    def __init__(self, model, known_entities, known_relations, top_k=1, missing="tails", dictionary=None):
+        if missing not in ("heads", "tails"):
+            raise WrongArgumentsError("missing entity should either be 'heads' or 'tails'")
+        self.missing = missing
+        self.known_entities, self.known_relations = known_entities, known_relations
+        self._setup(model, known_entities, known_relations, top_k, TOPK_TAILS if missing == "tails" else TOPK_HEADS, dictionary,
+                    model.n_rel if isinstance(dictionary, dict) else None)
+
+
+class RelationInference(_Inference):
+    """torchkge RelationInference on the device: the top_k relations that complete (entities1 = heads, entities2 = tails).  dictionary:
+    a FilterGroups (relation_filter_groups) or a dict {(head, tail): relation ids}."""
+
+    def __init__(self, model, entities1, entities2, top_k=1, dictionary=None):
+        self.entities1, self.entities2 = entities1, entities2
+        self._setup(model, entities1, entities2, top_k, TOPK_RELS, dictionary, model.n_ent if isinstance(dictionary, dict) else None)
