@@ -2686,7 +2686,11 @@ static int gemm_core(const GemmCall& c, hipStream_t stream) {
   g.M = M; g.N = N; g.K = K; g.lda = c.lda; g.ldb = c.ldb; g.ldc = c.ldc; g.ldaux = c.ldaux; g.accumulate = c.accumulate;
   if (c.qcols < 0 || c.qcols > N || (c.qcols & 127) || (c.qcols && (epilogue != EPI_BIAS || f32 || aks || bks))) return IA_ERR_ARG;
   g.qcols = c.qcols; g.qscale = c.qscale;
-  const uint64_t ab = a_window ? a_window : (aks ? ((uint64_t)(K - 1) * c.lda + M) * 2 : ((uint64_t)(M - 1) * c.lda + K) * 2);
+  // (k-strided A with an odd M: the buffer range check works on whole dwords, so a window that ends in the middle of one loses the last
+  // element of the last k row -- C[M-1][*] came out without its k = K-1 product, the row sums without A[K-1][M-1].  The window ends behind
+  // that dword instead: its other half lies inside the row's pitch (lda is a multiple of 8, so lda > M) and only feeds row M, which is
+  // never stored.  Every other operand ends on a dword: K is a multiple of 8 where A is k-contiguous, N a multiple of 4.)
+  const uint64_t ab = a_window ? a_window : (aks ? (((uint64_t)(K - 1) * c.lda + M) * 2 + 3) & ~(uint64_t)3 : ((uint64_t)(M - 1) * c.lda + K) * 2);
   const uint64_t bb = b_window ? b_window : (bks ? ((uint64_t)(K - 1) * c.ldb + N) * 2 : ((uint64_t)(N - 1) * c.ldb + K) * 2);
   g.csum_part = nullptr; g.split_id = 0; g.tile_ctr = nullptr;
   g.a_view = g.b_view = g.pw = 0; g.lca = g.lcbk = g.lcbn = 6;

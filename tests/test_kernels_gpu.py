@@ -161,7 +161,9 @@ def test_gemm_dgelu_with_fused_column_sums(gpu, M, N, K):
 @pytest.mark.parametrize("M,N,K", [(64, 576, 5000), (128, 128, 70000), (1024, 1024, 4096 + 40)])
 def test_gemm_wgrad_form_emits_row_sums(gpu, M, N, K):
     """Weight-gradient form (A, B k-strided, fp32 C) with C2: C2[m] += sum_k A[k][m] -- the bias gradient out of the same launch
-    (T128: one more MFMA against ones, split-K partials folded by the reduce kernel; 256x256 shapes: the column-sum pass)."""
+    (T128: one more MFMA against ones, split-K partials folded by the reduce kernel; 256x256 shapes: the column-sum pass).  All three
+    shapes run T128 today: (1024, 1024, 4136), meant for the column-sum pass, plans 16 tiles x 8 = 128 < 160.  The 256-wide form with C2
+    is in tests/test_gemm_kernels_gpu.py (test_t256w_weight_gradient_split_k, K = 5120 / 5160 / 7168, path asserted)."""
     from item_alignment_amd import _lib
     from item_alignment_amd.ops import check, stream_ptr
     lib = _lib.load()
@@ -605,9 +607,14 @@ def test_gpu_image_pipeline_bit_exact(gpu, tmp_path, H, W, S):
 @pytest.mark.parametrize("M,N,K", [(1024, 1024, 64), (1024, 1024, 128), (1024, 768, 8), (1000, 520, 72), (3000, 4096, 64), (8200, 2056, 256),
                                    (512, 512, 4104)])
 def test_gemm_one_wave_per_simd_kernel_edges(gpu, M, N, K):
-    """The T256W kernel (one wave per SIMD; serves the plain / bias / +residual / fp32 / weight-gradient forms of large GEMMs): one and
-    two k-tiles (its loop prefetches k-tile u+2 and reads k-tile u+1 ahead), ragged K, clipped M / N tiles (bias fetched before the
-    main loop only for full tiles, bf16-staged epilogue vs the fp32-staged fall-back), more tiles than workgroups."""
+    """Written as the edge test of the T256W kernel (one wave per SIMD; serves the plain / bias / +residual / fp32 / weight-gradient forms
+    of large GEMMs): one and two k-tiles (its loop prefetches k-tile u+2 and reads k-tile u+1 ahead), ragged K, clipped M / N tiles (bias
+    fetched before the main loop only for full tiles, bf16-staged epilogue vs the fp32-staged fall-back), more tiles than workgroups.
+    make_plan has since moved the 256-wide kernels to outputs of 160 tiles of 256 x 256 and more (fp32 output: tiles x min(32,
+    k-tiles / 8)): of these seven shapes only (3000, 4096, 64) and (8200, 2056, 256) still reach T256W, the other five run T128 -- no
+    shape here reaches T256W with two k-tiles, with K < 64 or with K = 72.  Those edges, with the path asserted and every element held to
+    fp64, are in tests/test_gemm_kernels_gpu.py (test_t256w_bf16_edges, test_t256w_weight_gradient_split_k); this test stays as the
+    norm check of both kernels at these shapes."""
     from item_alignment_amd import ops
     a, w = rnd((M, K), gpu, 1.0, 61), rnd((N, K), gpu, 0.1, 62)
     bias = torch.randn(N, device=gpu)
