@@ -16,7 +16,9 @@ from item_alignment_amd.utils import ROBERTA_WEIGHTS_NAME, logger
 from src.models import PKGMOneTower, PKGMTwoTower, RobertaOneTower, RobertaTwoTower, TextCNNTwoTower
 
 
-def get_parser():
+def build_parser(extra=None):
+    """extra(parser): called once every flag is in place -- a wrapper script adds its own flags and changes defaults there
+    (model_soup_text.py)"""
     p = argparse.ArgumentParser()
     add_common_flags(p)
     a = p.add_argument
@@ -35,7 +37,13 @@ def get_parser():
     a("--auxiliary_task", action="store_true")
     a("--filter_sizes", default="1,2,3,5", type=str)
     a("--num_filters", default=36, type=int)
-    return p.parse_args()
+    if extra is not None:
+        extra(p)
+    return p
+
+
+def get_parser(extra=None):
+    return build_parser(extra).parse_args()
 
 
 def load_raw_data(args):
@@ -73,8 +81,9 @@ def load_kg_tokenizer(args):
     return read("entity2id.txt"), read("relation2id.txt")
 
 
-def main():
-    args = get_parser()
+def main(args=None, before_run=None):
+    """before_run(args, model): hook between model construction and the train / eval / predict harness (model_soup_text.py)"""
+    args = args or get_parser()
     train.seed_everything(args.seed)
     tokenizer = load_tokenizer(args)
     config = load_config(args.config_file, interaction_type=args.interaction_type, type_vocab_size=args.type_vocab_size,
@@ -101,6 +110,8 @@ def main():
     else:
         raise ValueError("model name should be: roberta or pkgm")
     freeze_and_resume(args, model)
+    if before_run is not None:
+        before_run(args, model)
     train_data, valid_data, test_data = load_raw_data(args)
     logger.info(f"# train samples: {len(train_data)}, # valid samples: {len(valid_data)}, # test samples: {len(test_data)}")
 

@@ -473,3 +473,27 @@ class GCNDataset(Dataset):
 
     def __len__(self):
         return len(self.data)
+
+
+def collate(inputs):
+    """reference data.py:243-259 (single texts, pred_text.py): (ids, input_ids, token_type_ids, attention_mask, position_ids or None)."""
+    pos = [i["position_ids"] for i in inputs if "position_ids" in i]
+    return ([i["idx"] for i in inputs], _t([i["input_ids"] for i in inputs]), _t([i["token_type_ids"] for i in inputs]),
+            _t([i["attention_mask"] for i in inputs]), _t(pos) if pos else None)
+
+
+class RobertaDataset(Dataset):
+    """reference data.py:992-1033: (idx, text) rows, each text tokenised on its own, truncated longest-first and padded to max_seq_len;
+    the record carries the row's idx.  The text comes segmented from the caller, as in the reference's script."""
+
+    def __init__(self, data, text_tokenizer, max_seq_len):
+        self.data, self.text_tokenizer, self.max_seq_len = data, text_tokenizer, max_seq_len
+
+    def __getitem__(self, item):
+        idx, text = self.data[item]
+        rec = dict(_tok(self.text_tokenizer, text, self.max_seq_len))
+        rec["idx"] = idx
+        return rec
+
+    def __len__(self):
+        return len(self.data)

@@ -53,6 +53,9 @@ class BaseModelOutput(OrderedDict):
             self["hidden_states"] = hidden_states
 
     def __getattr__(self, name):
+        if name == "pooler_output" and name not in self:
+            # the reference returns it from every forward (text.py:1254); here it costs two launches and is opt-in
+            raise AttributeError("this output has no pooler_output: call the model with return_pooler_output=True")
         if name in ("last_hidden_state", "pooler_output", "hidden_states"):
             return self.get(name)
         raise AttributeError(name)

@@ -13,7 +13,7 @@ from ..utils import logger, ROBERTA_WEIGHTS_NAME, KG_WEIGHTS_NAME
 from . import functional as Fn
 from .base import (BaseModelOutput, HipModule, RobertaClassificationHead, RobertaEmbeddings, RobertaEncoder, RobertaPKGMEmbeddings,
                    RobertaPooler, SequenceClassifierOutput, TwoTowerClassificationHead, VecSimClassificationHead, cls_rows,
-                   init_bert_weights)
+                   init_bert_weights, ACT_TANH)
 from .loss import make_loss, apply_loss
 
 
@@ -84,8 +84,8 @@ class _PaddedView:
     """hidden_states of an unpadded tower run: a tuple-like of [B, L, H] tensors built on demand from the packed [T, H] rows
     (zeros at the padding); only the layers somebody reads are scattered."""
 
-    def __init__(self, packed, idx, B, L):
-        self.packed, self.idx, self.B, self.L = packed, idx, B, L
+    def __init__(self, packed, idx, B, L, cu=None):
+        self.packed, self.idx, self.B, self.L, self.cu = packed, idx, B, L, cu
         self._cache = {}
 
     def __len__(self):
@@ -121,8 +121,10 @@ class RobertaModel(HipModule, PretrainedMixin):
 
     def forward(self, input_ids=None, attention_mask=None, token_type_ids=None, position_ids=None, cate_ids=None, head_mask=None,
                 inputs_embeds=None, output_attentions=None, output_hidden_states=None, return_dict=None, allow_unpad=True,
-                padded_rows_unread=False, cls_only_read=False, **unused):
-        """cls_only_read (with padded_rows_unread): of last_hidden_state the caller reads [:, 0] and nothing else, and reads no other hidden
+                padded_rows_unread=False, cls_only_read=False, return_pooler_output=False, **unused):
+        """return_pooler_output: the output also carries pooler_output, fp32 [B, H] = tanh(pooler.dense(h[:, 0])) (the reference returns it
+        from every forward, text.py:1254; here it is two more launches -- the [CLS] gather and the small dense + tanh -- and opt-in).
+        cls_only_read (with padded_rows_unread): of last_hidden_state the caller reads [:, 0] and nothing else, and reads no other hidden
         state -- the last layer then runs what follows its attention for the [CLS] rows only (RobertaEncoder.forward).  Opt-in.
         padded_rows_unread: the caller reads no hidden state of a padded position and accepts zeros there (as under IA_UNPAD): the
         forward then skips the padded rows too (IA_ROWS_DEAD_FWD of ia_layer_cfg::masked_rows_dead).  Opt-in -- a direct caller gets every position
@@ -130,12 +132,16 @@ class RobertaModel(HipModule, PretrainedMixin):
         (self._root if "_root" in self.__dict__ else self).ensure_arena()
         if input_ids is None:
             raise ValueError("You have to specify input_ids")
+        if return_pooler_output and self.pooler is None:
+            raise ValueError("return_pooler_output=True on a model built with add_pooling_layer=False: there is no pooler to apply")
         if attention_mask is None:
             attention_mask = torch.ones_like(input_ids)
         if UNPAD and allow_unpad and cate_ids is None:
             hs = self._forward_unpadded(input_ids, attention_mask, token_type_ids, position_ids)
             if hs is not None:
-                return BaseModelOutput(last_hidden_state=hs[-1], hidden_states=hs)
+                # packed rows: the [CLS] of sequence b is the first row of its run, cu_seqlens[b]
+                pooled = self._pool(hs.packed[-1], hs.cu[:-1].contiguous()) if return_pooler_output else None
+                return BaseModelOutput(last_hidden_state=hs[-1], pooler_output=pooled, hidden_states=hs)
         e = self.embeddings(input_ids=input_ids, position_ids=position_ids, token_type_ids=token_type_ids, cate_ids=cate_ids)
         # allow_unpad = "nothing the caller reads depends on the padded rows" (every head of the reference reads [CLS] or valid spans; the
         # cross_attn multimodal layers, which attend over ALL text positions, pass False): the padded run may then at least skip what is
@@ -143,7 +149,16 @@ class RobertaModel(HipModule, PretrainedMixin):
         dead = allow_unpad and cate_ids is None and not output_hidden_states
         hs = self.encoder(e, attention_mask, masked_rows_dead=dead, padded_rows_unread=dead and padded_rows_unread,
                           cls_only_read=dead and padded_rows_unread and cls_only_read)
-        return BaseModelOutput(last_hidden_state=hs[-1], hidden_states=hs)
+        pooled = None
+        if return_pooler_output:
+            B, L, H = hs[-1].shape
+            pooled = self._pool(hs[-1].reshape(B * L, H), cls_rows(B, L, 0, hs[-1].device))
+        return BaseModelOutput(last_hidden_state=hs[-1], pooler_output=pooled, hidden_states=hs)
+
+    def _pool(self, flat, rows):
+        """tanh(pooler.dense(row)) of the given rows of a [rows, H] hidden state, fp32: the head BertAlignModel applies to its packed batch"""
+        cls_h = Fn.GatherRowsFn.apply(flat, self.anchor, rows, 0.0, 0)
+        return Fn.LinearSmallFn.apply(cls_h, self.pooler.dense.weight, self.pooler.dense, ACT_TANH)
 
     def _forward_unpadded(self, input_ids, attention_mask, token_type_ids, position_ids):
         """IA_UNPAD=1: run the tower on the valid tokens only.  The reference pads every sequence to max length and computes on the
@@ -155,8 +170,8 @@ class RobertaModel(HipModule, PretrainedMixin):
         got = self._forward_packed([(ids, tts, pids, attention_mask)], dense_is_none=True)
         if got is None:
             return None                                                                # nothing to drop
-        packed, idx, _cu = got
-        return _PaddedView(packed, idx, B, L)
+        packed, idx, cu = got
+        return _PaddedView(packed, idx, B, L, cu)
 
     def _forward_packed(self, fields, dense_is_none=False, strict=False):
         """The tower on the valid tokens of several padded inputs at once.  fields: a list of (input_ids, token_type_ids, position_ids,

@@ -5,31 +5,12 @@ CLI-compatible with the reference's model_soup_multimodal.py (flags :34-86 = the
 over the listed epochs, non-parameter entries (buffers) are taken from the last listed checkpoint, as the reference does.
 The averaging is a host-side pass over the state_dicts; the prediction runs on the HIP engine like finetune_multimodal.py --do_pred."""
 import os
-from collections import OrderedDict
 
 import torch
 
 import finetune_multimodal as FT
+from item_alignment_amd.soup import load_soup, uniform_soup
 from item_alignment_amd.utils import logger
-
-
-def uniform_soup(model, pattern, epochs):
-    """reference model_soup_multimodal.py:223-239"""
-    names = set(dict(model.named_parameters()))
-    st = OrderedDict()
-    for epoch in epochs:
-        sd = torch.load(pattern.format(epoch), map_location="cpu")
-        for key, val in sd.items():
-            if key not in names:
-                st[key] = val                      # buffers: the last listed epoch wins
-            elif key not in st:
-                st[key] = val.clone()
-            else:
-                st[key] += val
-    for key, val in st.items():
-        if key in names:
-            val /= len(epochs)
-    return st
 
 
 def main():
@@ -43,10 +24,7 @@ def main():
     def soup(args, model):
         epochs = args.epochs.split(",")
         st = uniform_soup(model, pattern, epochs)
-        missing, unexpected = model.load_state_dict(st, strict=False)
-        if unexpected:
-            raise RuntimeError(f"unexpected keys in the checkpoints: {unexpected[:5]}")
-        logger.info(f"Finished uniform soup on epochs: {epochs}")
+        load_soup(model, st, epochs, logger)
         out_dir = os.path.join(args.output_dir, "-".join(str(getattr(args, f)) for f in ("model_name", "data_version", "interaction_type",
                                                                                           "classification_method", "ensemble", "loss_type")))
         os.makedirs(out_dir, exist_ok=True)

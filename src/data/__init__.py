@@ -7,3 +7,4 @@ from item_alignment_amd.data.datasets import (RobertaOneTowerDataset, RobertaTwo
                                               collate_multimodal, collate_multimodal_two_tower, collate_coca_pair)
 from item_alignment_amd.data.datasets import MultimodalDataset, collate_coca  # noqa: F401,E402
 from item_alignment_amd.data.datasets import GCNDataset, collate_gnn  # noqa: F401,E402
+from item_alignment_amd.data.datasets import RobertaDataset, collate  # noqa: F401,E402
