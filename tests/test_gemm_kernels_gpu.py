@@ -17,8 +17,8 @@ Each case ASSERTS the path it is meant for from what the library exports (ia_gem
 ia_gemm_wgrad_rows_filters tell the 256-wide kernels from T128, ia_gemm_workspace_bytes gives the planned split count): a change of
 make_plan turns a silently re-routed case into a failure.  Every comparison prints max error / bar (`-s` shows them).
 
-Out of scope: the shifted views and channel groups of ia_gemm_view (the convolution tests, against MIOpen) and the filtered entry points
-(pinned bit-for-bit to the dense call by their own files).
+Out of scope: the shifted views and channel groups of ia_gemm_view (tests/test_conv_kernels_gpu.py holds them to fp64 element by element
+through the convolution entry points) and the filtered entry points (pinned bit-for-bit to the dense call by their own files).
 """
 import pytest
 import torch
