@@ -37,7 +37,7 @@ const char* ia_strerror(int code);
 /* Bumped whenever an entry point is added or the meaning of an argument / output changes (round 2 changed what IA_EPI_BIAS_GELU
  * stores in C2 and what IA_EPI_DGELU expects in aux): a caller built against another header must not run on this library.
  * item_alignment_amd/_lib.py refuses to load a library whose version differs from the one it was written for. */
-#define IA_ABI_VERSION 21
+#define IA_ABI_VERSION 22
 int ia_abi_version(void);
 
 /* ---- GEMM: torch.nn.Linear forward / dgrad / wgrad (src/models/text.py:1241 -> RobertaLayer dense
@@ -71,26 +71,23 @@ size_t ia_gemm_colsum_workspace_bytes(int M, int N);
 /* (ABI 16) The weight gradient of a Linear over padded token rows: dW[N_out, N_in] (+)= dY^T X with dY [M_rows, N_out] (ldy) and
  * X [M_rows, N_in] (ldx), bf16, dW fp32 (ldw) -- ia_gemm_bf16's weight-gradient form (both operands k-strided, IA_EPI_NONE) -- and a row
  * filter like ia_ln_bwd2_rows': row_live [M_rows] uint8 or NULL; row_live[m] == 0 = the caller guarantees that row m of dY is all
- * zeros (a masked position of an encoder whose heads read no masked position, ia_layer_cfg::masked_rows_dead).  A 64-row block of k
- * without a live row is then neither fetched nor multiplied.  Identical results on such inputs (the k-slabs of the split and the order
- * of the reduction do not depend on row_live); a dY that breaks the guarantee loses those rows' products.  NULL = the ia_gemm_bf16 call.
- * With row_live the workspace (16-byte aligned) holds the split-K partial sums and the bitmask and is required:
- * ia_gemm_wgrad_rows_workspace_bytes. */
+ * zeros (a masked position of an encoder whose heads read no masked position, ia_layer_cfg::masked_rows_dead).  A 32-row block of k
+ * (rows 32b .. 32b+31) without a live row is then neither fetched nor multiplied (ABI 22; whole 64-row k-tiles before).  Identical results
+ * on such inputs (the k-slabs of the split and the order of the reduction do not depend on row_live); a dY that breaks the guarantee loses
+ * those rows' products.  NULL = the ia_gemm_bf16 call.  With row_live the workspace (16-byte aligned) holds the split-K partial sums and
+ * the block bitmask (ia_kblock_mask, below) and is required: ia_gemm_wgrad_rows_workspace_bytes.  The entry builds the mask and makes the
+ * ia_gemm_wgrad_blocks call. */
 size_t ia_gemm_wgrad_rows_workspace_bytes(int N_out, int N_in, int M_rows);
-/* Diagnostics (tests, tools): 1 when a call of this shape honours row_live (outputs large enough for the 256 x 256-tile kernel, whose k loop the filter lives in),
- * 0 when it reads every row as ia_gemm_bf16 does (small outputs; the result is the same either way) */
+/* Diagnostics (tests, tools): 1 when a call of this shape honours row_live or a block mask (outputs large enough for the 256 x 256-tile
+ * kernel, whose k loop the filter lives in, and k-slabs of at most 1024 k-tiles), 0 when it reads every row as ia_gemm_bf16 does (the
+ * result is the same either way) */
 int ia_gemm_wgrad_rows_filters(int N_out, int N_in, int M_rows);
 int ia_gemm_wgrad_rows(const void* dY, int ldy, const void* X, int ldx, float* dW, int ldw, int N_out, int N_in, int M_rows,
                        const uint8_t* row_live, int accumulate, void* workspace, size_t workspace_bytes, ia_stream_t stream);
-/* the bitmask itself: bit (t & 31) of mask[t >> 5] = OR of row_live over rows 64t .. 64t+63, clipped to M_rows; ia_ktile_mask_bytes(M_rows)
- * bytes.  ia_ktile_mask writes it on the device (one launch, plain stores).  ia_ktile_mask_host is a diagnostic hook: the same words from host
- * memory through the per-k-tile function the device kernel calls (it does not exercise the kernel's ballot and stores). */
-size_t ia_ktile_mask_bytes(int M_rows);
-int ia_ktile_mask(const uint8_t* row_live, int M_rows, uint32_t* mask, ia_stream_t stream);
-int ia_ktile_mask_host(const uint8_t* row_live, int M_rows, uint32_t* mask);
-/* The same filter at 32-row granularity, the mask handed in.  ia_kblock_mask: bit (b & 31) of mask[b >> 5] = OR of row_live over rows
- * 32b .. 32b+31, clipped to M_rows; ia_kblock_mask_bytes(M_rows) bytes, one launch, plain stores; ia_kblock_mask_host: the same words from
- * host memory (diagnostic hook, as ia_ktile_mask_host).  ORing adjacent bit pairs gives ia_ktile_mask's words.
+/* The same filter, the mask handed in.  ia_kblock_mask: bit (b & 31) of mask[b >> 5] = OR of row_live over rows 32b .. 32b+31, clipped
+ * to M_rows; ia_kblock_mask_bytes(M_rows) bytes; written on the device by one launch, plain stores.  ia_kblock_mask_host is a diagnostic
+ * hook: the same words from host memory through the per-block function the device kernel calls (it does not exercise the kernel's ballot
+ * and stores).
  * ia_gemm_wgrad_blocks: dW (+)= dY^T X over the 32-row blocks of k whose bit is set -- a block without a live row is neither fetched nor
  * multiplied; the kernel walks the live blocks of each k-slab two to a 64-row k-tile.  Identical results on inputs that keep row_live's
  * guarantee (every fp32 sum keeps its terms and their order).  kblock_mask: device pointer, NULL = the ia_gemm_bf16 call.  The workspace

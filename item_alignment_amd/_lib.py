@@ -51,9 +51,6 @@ SIGNATURES = {
     "ia_gemm_wgrad_rows_workspace_bytes": (sz, [i32, i32, i32]),
     "ia_gemm_wgrad_rows_filters": (i32, [i32, i32, i32]),
     "ia_gemm_wgrad_rows": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, vp, i32, vp, sz, vp]),
-    "ia_ktile_mask_bytes": (sz, [i32]),
-    "ia_ktile_mask": (i32, [vp, i32, vp, vp]),
-    "ia_ktile_mask_host": (i32, [vp, i32, vp]),
     "ia_kblock_mask_bytes": (sz, [i32]),
     "ia_kblock_mask": (i32, [vp, i32, vp, vp]),
     "ia_kblock_mask_host": (i32, [vp, i32, vp]),
@@ -246,7 +243,7 @@ SIGNATURES = {
 _lib = None
 
 
-ABI_VERSION = 21      # = IA_ABI_VERSION of include/itemalign.h (tests/test_cabi_symbols.py keeps the two in step)
+ABI_VERSION = 22      # = IA_ABI_VERSION of include/itemalign.h (tests/test_cabi_symbols.py keeps the two in step)
 
 
 class ItemAlignError(RuntimeError):

@@ -215,7 +215,7 @@ IA_DEV void zero_cs_row(float* cs_out, int lane) {
 }
 // AttnArgs::q_lim, forward: the rows of a wave beyond the limit -- queries q0 .. q0 + nq - 1 (nq <= 64) of sequence b, clipped to Lq -- leave
 // as zeros in head h's 64 columns of `out` and as 0 in lse2.  The kernel writes them (no memset of the caller's buffer): whatever reads
-// every row of the context afterwards (the out-projection's weight gradient over a partly live k-tile multiplies these rows by exact
+// every row of the context afterwards (the out-projection's weight gradient over a partly live 32-row block multiplies these rows by exact
 // zeros) must meet finite values, also in a buffer that held anything before.
 IA_DEV void zero_unread_rows(const AttnArgs& p, size_t qbase, int b, int h, int q0, int nq, int Lq, int lane) {
   const int c = lane & 7;

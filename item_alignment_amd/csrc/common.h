@@ -206,17 +206,16 @@ __attribute__((visibility("hidden"))) size_t ia_gemm_view_workspace_bytes(int M,
 //   PACKED   32-row block, packed by whole groups  ia_row_groups_packed                   data gradient, IA_EPI_DGELU_COLSUM
 //   SLABS    8-row slab                            ia_row_slabs                           forward: IA_EPI_NONE / BIAS / BIAS_GELU; data gradient:
 //                                                                                         IA_EPI_NONE / ADD
-//   KTILES   64-row k-tile, one bit each           ia_ktile_mask                          weight gradient
 //   KBLOCKS  32-row block of k, one bit each       ia_kblock_mask                         weight gradient
 // NONE, a null list, or a shape the filtered kernel does not serve: every row, exactly the call ia_gemm_bf16 / ia_gemm_bf16_qscale makes.
 struct IaRowFilter {
-  enum Kind { NONE, BLOCKS, GROUPS, PACKED, SLABS, KTILES, KBLOCKS };
+  enum Kind { NONE, BLOCKS, GROUPS, PACKED, SLABS, KBLOCKS };
   Kind kind = NONE;
   const void* list = nullptr;
   bool fill = true;      // forward GEMMs: the dead rows of Y (and C2) are written as zeros, else not written at all (data gradients always fill)
   explicit operator bool() const { return kind != NONE && list; }
 };
-// bytes of the list of a kind over M rows, and its builder (one small launch on the stream; dst 32-byte aligned, the two masks 4)
+// bytes of the list of a kind over M rows, and its builder (one small launch on the stream; dst 32-byte aligned, the mask 4)
 __attribute__((visibility("hidden"))) size_t ia_row_filter_bytes(IaRowFilter::Kind kind, int M);
 __attribute__((visibility("hidden"))) int ia_row_filter_build(IaRowFilter::Kind kind, const uint8_t* row_live, int M, void* dst, hipStream_t stream);
 // does the (kind, epilogue) pair have a kernel form?  (the table above; NONE goes with every epilogue of ia_gemm_bf16)
@@ -235,7 +234,7 @@ __attribute__((visibility("hidden"))) int ia_gemm_fwd_filtered(const void* X, in
 __attribute__((visibility("hidden"))) int ia_gemm_dgrad_filtered(const void* dY, int ldy, const void* W, int w_kstrided, int ldw, void* dX, int ldx,
                                                                  int M_rows, int N_in, int K_out, int epilogue, const void* aux, int ldaux, void* C2,
                                                                  IaRowFilter filter, void* workspace, size_t workspace_bytes, hipStream_t stream);
-// dW[N_out, N_in] (+)= dY^T X over the k-tiles / 32-row blocks of k whose bit is set in the mask: the weight-gradient form of ia_gemm_bf16
+// dW[N_out, N_in] (+)= dY^T X over the 32-row blocks of k whose bit is set in the mask: the weight-gradient form of ia_gemm_bf16
 // for a caller that has the mask of its rows already (ia_layer_bwd2: one mask, four weight gradients)
 __attribute__((visibility("hidden"))) int ia_gemm_wgrad_filtered(const void* dY, int ldy, const void* X, int ldx, float* dW, int ldw, int N_out,
                                                                  int N_in, int M_rows, IaRowFilter filter, int accumulate, void* workspace,

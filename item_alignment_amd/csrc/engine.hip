@@ -265,7 +265,7 @@ int layer_forward(const ia_layer_cfg* c, const ia_layer_weights* w, const void* 
     // holds for it meets an exact zero in every weight-gradient sum: its values may be anything finite.  The GEMMs run the 32-row blocks
     // that hold a live row only (one block list per call, or the caller's), the LayerNorms the live rows only (dead rows leave as zeros).
     // Zeros are written where somebody reads every row: q / k / v (the attention kernels), the FFN activation and its derivative (the
-    // fc2 weight gradient's partly live k-tiles, the every-row x gelu' epilogue).  The two projection outputs in front of the LayerNorms
+    // fc2 weight gradient's partly live 32-row blocks, the every-row x gelu' epilogue).  The two projection outputs in front of the LayerNorms
     // are not filled: only their LayerNorm reads them, which skips the dead rows and, in the training form, overwrites them in place.
     // ... and the GEMMs whose slab form exists take the mask in 8-row slabs (ia_row_slabs: a sequence's rows never line up with 32-row
     // blocks).  The same readers, the same argument: a dead slab of a live block holds zeros where a dead block does, and is unwritten
@@ -278,7 +278,7 @@ int layer_forward(const ia_layer_cfg* c, const ia_layer_weights* w, const void* 
     IA_TRY(attn_fwd(c, s.qkv, key_mask, s.ctx, s.lse, scale, attn_drop, attn_seed, st));
     // out_row_live: behind the attention only the rows the caller reads are live (a subset of the live keys) -- the same rules with that
     // mask and its block list: the LayerNorms leave zeros in the other rows (so y1 and, in the training form, z1 / z2 are finite in every
-    // row a partly live k-tile of a weight gradient touches), fc1 fills the other blocks of the activation and its derivative
+    // row a partly live 32-row block of a weight gradient touches), fc1 fills the other blocks of the activation and its derivative
     // (out_row_live keeps its 32-row lists)
     if (const uint8_t* const olive = out_live(c)) IA_TRY(resolve_rows(c, OUT_ROWS, olive, WANT_BLOCKS, M, s.out, st, &rows));
     // z1 = x + dropout(ctx Wo^T + b_o); y1 = LN1(z1)
@@ -299,7 +299,7 @@ int layer_forward(const ia_layer_cfg* c, const ia_layer_weights* w, const void* 
     // so the projection keeps the plain epilogue; proj receives x1 in place of the raw projection (the fc2 epilogue's residual)
     // out_row_live (the last block under a head that reads [CLS] only): the out-projection, LN2, fc1 and fc2 run the 32-row blocks / rows
     // the caller reads.  LN2 leaves zeros in the other rows of x1 and LN2(x1), fc1 fills the other blocks of the activation and its
-    // derivative (the weight gradients' partly live k-tiles and the x gelu' epilogue read them); y is not written outside the live blocks.
+    // derivative (the weight gradients' partly live 32-row blocks and the x gelu' epilogue read them); y is not written outside the live blocks.
     RowPlan rows;
     IA_TRY(resolve_rows(c, OUT_ROWS, out_live(c), WANT_BLOCKS, M, s.out, st, &rows));
     IA_TRY(fwd_gemm(s.ctx, H, w->w_o, s.proj, H, M, IA_EPI_NONE, nullptr, nullptr, nullptr, rows, false, st));

@@ -40,15 +40,14 @@ constexpr int BK = 64;
 constexpr uint32_t OOB = 0xFFFFFFF0u;
 
 enum { EPI_NONE = 0, EPI_BIAS = 1, EPI_BIAS_GELU = 2, EPI_ADD = 3, EPI_DGELU = 4, EPI_BIAS_ADD = 5, EPI_DGELU_CS = 6, EPI_BIAS_GELU_ACT = 7 };
-// EPI_NONE_LIVE (library-internal, t256w only): EPI_NONE behind a k loop over the live k-tiles.  The weight-gradient form dW = dY^T X has
-// the token rows as k: a k-tile whose rows of dY are all zeros adds +-0 to every accumulator, so leaving it out changes no bit of the
-// fp32 sums -- the k-slabs of a split-K launch and the order of the reduction stay what they are, a slab just takes fewer trips.
-constexpr int EPI_NONE_LIVE = 8;
-// EPI_NONE_BLK (library-internal, t256w only): the same walk at 32-row granularity.  A k-tile of the loop is made of TWO live 32-row blocks
-// of the slab, the next one of the ascending walk in its lower half (LDS rows 0 .. 31: DMA pieces 0 .. 3, k-steps 0 and 1) and the one
-// after it in its upper half (pieces 4 .. 7, k-steps 2 and 3).  A 32-row block is two whole 32x32x16 MFMAs per accumulator, so every
-// accumulator still sees the MFMAs of its live rows on the same operands in the same order, less those whose dY operand is all zeros:
-// no bit of the fp32 sums changes, and a slab takes ceil(live blocks / 2) trips.
+// EPI_NONE_BLK (library-internal, t256w only): EPI_NONE behind a k loop over the live 32-row blocks.  The weight-gradient form
+// dW = dY^T X has the token rows as k: a block whose rows of dY are all zeros adds +-0 to every accumulator, so leaving it out changes
+// no bit of the fp32 sums -- the k-slabs of a split-K launch and the order of the reduction stay what they are, a slab just takes fewer
+// trips.  A k-tile of the loop is made of TWO live 32-row blocks of the slab, the next one of the ascending walk in its lower half (LDS
+// rows 0 .. 31: DMA pieces 0 .. 3, k-steps 0 and 1) and the one after it in its upper half (pieces 4 .. 7, k-steps 2 and 3).  A 32-row
+// block is two whole 32x32x16 MFMAs per accumulator, so every accumulator still sees the MFMAs of its live rows on the same operands in
+// the same order, less those whose dY operand is all zeros, and a slab takes ceil(live blocks / 2) trips.  (The value 8 was the walk
+// over whole 64-row k-tiles this one replaced; 9 stays, and with it the kernel's name in the profiles.)
 constexpr int EPI_NONE_BLK = 9;
 // EPI_ROWS + e (library-internal, t256w only; k-contiguous A, bf16 output): epilogue e behind a row remap.  The data gradient dX = dY W
 // (e = EPI_NONE, EPI_ADD or EPI_DGELU_CS) has the token rows as M: a row of dY that is all zeros gives a row of zeros, so only the 32-row
@@ -71,9 +70,10 @@ struct GemmArgs {
   union {
     const float* bias;
     // Weight-gradient form of the 256-wide kernel only (IA_EPI_NONE: no bias; the member shares its slot so that no other kernel's
-    // argument block moves): bit t of this bitmask set = k-tile t (k rows 64t .. 64t+63) has at least one row of A that is not known
-    // to be all zeros; a workgroup walks only the set bits of its k-slab (t256w::gemm_kernel<true, true, EPI_NONE_LIVE, true>).  NULL = every k-tile.
-    const uint32_t* live_kt;
+    // argument block moves): bit t of this bitmask (an ia_kblock_mask) set = block t (k rows 32t .. 32t+31) has at least one row of A that
+    // is not known to be all zeros; a workgroup walks only the set bits of its k-slab (t256w::gemm_kernel<true, true, EPI_NONE_BLK, true>).
+    // NULL = every row.
+    const uint32_t* live_blk;
   };
   const bf16* aux;
   int M, N, K;
@@ -641,8 +641,9 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs p) {
 namespace t256w {
 constexpr int BM = 256, BN = 256, TILE_BYTES = 32768;        // one operand's k-tile: 256 rows x 64 k (or 64 k x 256 columns) of bf16
 constexpr int STAGE_BYTES = 16 * 64 * 4;                   // epilogue staging slot (16 rows x 64 columns fp32); each of the four waves owns two
-constexpr int LIVE_MAX_KTILES = 64 * 32;                   // EPI_NONE_LIVE: a k-slab's live-k-tile mask is one 32-bit word per lane
-constexpr int BLK_MAX_KTILES = LIVE_MAX_KTILES / 2;        // EPI_NONE_BLK: two mask bits per k-tile of the slab
+// EPI_NONE_BLK: a k-slab's live-block mask is one 32-bit word per lane, two bits per k-tile -- 1024 k-tiles at the most.  The one statement
+// of that limit (the host asks it in gemm_core and in ia_gemm_wgrad_rows_filters): a longer k-slab runs every row.
+inline bool blk_mask_fits(int slab_ktiles) { return slab_ktiles <= 64 * 32 / 2; }
 constexpr uint32_t OOB_HALF = 0x80000000u;                 // behind every buffer window (< 2 GiB), and three piece advances on top do not wrap
 constexpr int LDS_BYTES = 2 * 2 * TILE_BYTES + 8 * STAGE_BYTES;   // 128 KiB k-tile double buffer (A | B, twice) + 4 x 8 KiB = all 160 KiB of the CU
 
@@ -855,11 +856,11 @@ IA_DEV RowSlab slab_rows(const GemmArgs& p, int bm, int wm, int n_live) {
   return rs;
 }
 
-// Walk over the set bits of a k-slab's live-k-tile mask in increasing order.  Lane l of `mv` holds bits 32l .. 32l+31 of the slab (every
-// wave holds the same 64 words, fetched once in front of the first prologue DMA); the walk itself is SALU plus one v_readlane per step --
-// no memory operation, so it can sit next to the k loop's counted waits, and no branch.  Once the bits are used up next() keeps
-// returning the index behind the last one it gave: the look-ahead pieces past the end then address what they address in the dense
-// kernel (the k-tiles right behind the last one consumed).
+// Walk over the set bits of a k-slab's live-block mask (one bit per 32-row block) in increasing order.  Lane l of `mv` holds bits
+// 32l .. 32l+31 of the slab (every wave holds the same 64 words, fetched once in front of the first prologue DMA); the walk itself is SALU
+// plus one v_readlane per step -- no memory operation, so it can sit next to the k loop's counted waits, and no branch.  Once the bits
+// are used up next() keeps returning the index behind the last one it gave: a look-ahead piece past the end then addresses the block
+// right behind the last one consumed, as the dense kernel's does, where main_loop does not send it out of range.
 struct LiveWalk {
   uint64_t rest;      // words with a set bit that have not been opened yet
   uint32_t w;         // bits of the open word not handed out yet
@@ -877,19 +878,17 @@ IA_DEV int live_next(LiveWalk& k, uint32_t mv) {
   return idx;
 }
 
-// LIVE (both operands k-strided): the k loop runs over the n_tiles set bits of live_mv (the slab's live k-tiles, see LiveWalk) instead of
-// k-tiles 0 .. n_tiles-1 of the slab.
-// LIVE == 2 (EPI_NONE_BLK): over the n_blk set bits of live_mv, which are the slab's live 32-row blocks -- two per trip (n_tiles =
-// ceil(n_blk / 2)); the upper half of the last trip of an odd count goes out of range and arrives as zeros.
+// BLK (EPI_NONE_BLK; both operands k-strided): the k loop runs over the n_blk set bits of live_mv (the slab's live 32-row blocks, see
+// LiveWalk) instead of k-tiles 0 .. n_tiles-1 of the slab -- two blocks per trip (n_tiles = ceil(n_blk / 2)); the upper half of the
+// last trip of an odd count goes out of range and arrives as zeros.
 // ROWS (k-contiguous A): piece j of A starts at row offset ro.o[j] (a scalar, where j * stepA sits otherwise) of a window over all of A.
 // SLAB: ro.o[j] is this WAVE's slab of piece j -- the lane offset keeps the row inside the slab (row & 7) and the swizzle of the LDS row.
-template <bool AKS, bool BKS, int PEND, bool PEEL_OK = true, int LIVE = 0, bool ROWS = false, bool SLAB = false>
+template <bool AKS, bool BKS, int PEND, bool PEEL_OK = true, bool BLK = false, bool ROWS = false, bool SLAB = false>
 IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdgpu_buffer_rsrc_t rsA, __amdgpu_buffer_rsrc_t rsB, int xa, int xb,
                       int kt0, int ktaA0, int ktaB0, int n_tiles, int nk_all, int wm, int wn, int wave, int lane, bool prologue_only,
                       bool stores_in_flight, uint32_t live_mv = 0u, RowOff ro = RowOff{}, int n_blk = 0) {
-  constexpr bool BLK = LIVE == 2;
   static_assert(!ROWS || !AKS, "the row remap moves the pieces of a k-contiguous A");
-  static_assert(!LIVE || (AKS && BKS), "the live-k-tile walk advances the running lane offsets of two k-strided operands");
+  static_assert(!BLK || (AKS && BKS), "the live-block walk sets the running lane offsets of two k-strided operands");
   constexpr bool ROUND = !AKS && !BKS;      // the k loop's schedule (below)
   const int li = lane & 31;
   const int gt = wave * 64 + lane;                  // thread index inside the workgroup (0..255)
@@ -908,14 +907,13 @@ IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdg
   char* const my_part = smem + wave * 1024;
   const int dbg = IA_GEMM_DBG_HOOKS ? p.dbg : 0;       // the timing ablations (IA_GEMM_DBG bits 2 / 4 / 16) exist in tools builds only
   const bool dma_on = !(dbg & 2);
-  // LIVE: the slab-relative indices of the first two live k-tiles (the prologue's)
+  // BLK: the slab-relative indices of the first four live blocks (the prologue's two k-tiles: lower half, upper half)
   [[maybe_unused]] LiveWalk lw;
-  int live0 = 0, live1 = 1;
-  [[maybe_unused]] int live0h = 0, live1h = 0;      // BLK: the upper halves' blocks (live0 / live1: the lower halves')
+  [[maybe_unused]] int live0 = 0, live0h = 0, live1 = 0, live1h = 0;
   if constexpr (BLK) {
     live_start(lw, live_mv);
     live0 = live_next(lw, live_mv); live0h = live_next(lw, live_mv); live1 = live_next(lw, live_mv); live1h = live_next(lw, live_mv);
-  } else if constexpr (LIVE) { live_start(lw, live_mv); live0 = live_next(lw, live_mv); live1 = live_next(lw, live_mv); }
+  }
 
   // piece i (0..7: A, 8..15: B) of k-tile u -> buffer u & 1.  Branch-free (a branch next to the accumulator updates makes hipcc copy
   // all 256 of them): lim = number of valid k in this k-tile (0 for a k-tile past the end: the whole piece goes out of range and
@@ -935,7 +933,7 @@ IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdg
       return;
     }
     const int kt = kt0 + u;
-    const int kta = (dbg & 4) ? 0 : (isB ? ktaB0 : ktaA0) + (LIVE ? (u == 0 ? live0 : live1) : u);      // dbg 4: every k-tile re-fetches k-tile 0 (cache-resident)
+    const int kta = (dbg & 4) ? 0 : (isB ? ktaB0 : ktaA0) + u;      // dbg 4: every k-tile re-fetches k-tile 0 (cache-resident)
     const bool ks = isB ? BKS : AKS;
     const uint32_t soff = (uint32_t)kta * (isB ? kstepB : kstepA) + ((ROWS && !isB) ? ro.o[j] : (uint32_t)j * (isB ? stepB : stepA));
     if (ks) {
@@ -945,9 +943,7 @@ IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdg
       // slab's first rows instead of zeros: nobody consumes that buffer.)  Data gradient +4 %, weight gradient +0.7 %; the memory-side
       // fetches of both went UP 4-8 % with it (FETCH_SIZE 0.996 -> 1.076 GB per weight-gradient launch, same box, against compare +
       // select per piece): far more than the two look-ahead k-tiles -- the workgroups that share a panel out of one L2 drift further apart.
-      // (LIVE: a slab with fewer than two live k-tiles has nothing behind them to address -- those prologue k-tiles go out of range and
-      // arrive as zeros, which is what the one trip of a slab without any live k-tile multiplies)
-      const uint32_t off = (dma_on && (!LIVE || u < n_tiles)) ? (isB ? voffB : voffA) + soff : OOB;
+      const uint32_t off = dma_on ? (isB ? voffB : voffA) + soff : OOB;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(isB ? rsB : rsA, IA_LDS(dst), 16, off, 0, 0, 0);
     } else {
       const int lim = (u < n_tiles && dma_on) ? p.K - kt * BK : 0;
@@ -972,14 +968,12 @@ IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdg
   };
 
   // second schedule (a k-strided operand): in-loop pieces of k-tile u+2; the k-strided operand's k-tile advance lives in a running lane offset
-  int live2 = 2;
-  [[maybe_unused]] int live2h = 0;
-  if constexpr (BLK) { if (!prologue_only) { live2 = live_next(lw, live_mv); live2h = live_next(lw, live_mv); } }
-  else if constexpr (LIVE) { if (!prologue_only) live2 = live_next(lw, live_mv); }      // (the prologue call stops at the first two)
-  uint32_t runA = voffA + (uint32_t)((dbg & 4) ? 0 : ktaA0 + live2) * kstepA, runB = voffB + (uint32_t)((dbg & 4) ? 0 : ktaB0 + live2) * kstepB;
+  uint32_t runA = voffA + (uint32_t)((dbg & 4) ? 0 : ktaA0 + 2) * kstepA, runB = voffB + (uint32_t)((dbg & 4) ? 0 : ktaB0 + 2) * kstepB;
   // BLK: four running lane offsets -- each operand's lower and upper half (blocks 4 and 5 of the walk to begin with)
   [[maybe_unused]] uint32_t runAh = 0u, runBh = 0u;
   if constexpr (BLK) {
+    int live2 = 2, live2h = 0;
+    if (!prologue_only) { live2 = live_next(lw, live_mv); live2h = live_next(lw, live_mv); }      // (the prologue call stops at the first four)
     runA = voffA + (uint32_t)live2 * (kstepA >> 1); runB = voffB + (uint32_t)live2 * (kstepB >> 1);
     runAh = 5 < n_blk ? voffA + (uint32_t)live2h * (kstepA >> 1) : OOB_HALF; runBh = 5 < n_blk ? voffB + (uint32_t)live2h * (kstepB >> 1) : OOB_HALF;
   }
@@ -1135,11 +1129,6 @@ IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdg
       runB = voffB + (uint32_t)bl * (kstepB >> 1); asm volatile("" : "+v"(runB));
       runAh = has_h ? voffA + (uint32_t)bh * (kstepA >> 1) : OOB_HALF; asm volatile("" : "+v"(runAh));
       runBh = has_h ? voffB + (uint32_t)bh * (kstepB >> 1) : OOB_HALF; asm volatile("" : "+v"(runBh));
-    } else if constexpr (LIVE) {      // on to the next live k-tile: the same trip, a longer stride
-      const int at = lw.cur;
-      const uint32_t hop = (uint32_t)(live_next(lw, live_mv) - at);
-      runA += hop * kstepA; asm volatile("" : "+v"(runA));
-      runB += hop * kstepB; asm volatile("" : "+v"(runB));
     } else {
       if (AKS) { runA += kstepA; asm volatile("" : "+v"(runA)); }
       if (BKS) { runB += kstepB; asm volatile("" : "+v"(runB)); }
@@ -1392,18 +1381,18 @@ IA_DEV void drain_half(const GemmArgs& p, f32x16 (&acc)[4][4], int m0, int n0, c
   if (full && (HAS_BIAS || HAS_AUX) && !(IA_DBG(p) & 256)) drain(std::true_type{}); else drain(std::false_type{});
 }
 
-// EPI_ = EPI_NONE_LIVE: the plain epilogue behind a k loop over the live k-tiles only (GemmArgs::live_kt; weight-gradient form).  A value
-// of the epilogue parameter, not a parameter of its own: the other instantiations keep their names in profiles and traces.
-// EPI_ = EPI_NONE_BLK: the same over the live 32-row blocks, two to a trip (GemmArgs::live_kt holds an ia_kblock_mask).
+// EPI_ = EPI_NONE_BLK: the plain epilogue behind a k loop over the live 32-row blocks only, two to a trip (GemmArgs::live_blk, an
+// ia_kblock_mask; weight-gradient form).  A value of the epilogue parameter, not a parameter of its own: the other instantiations keep
+// their names in profiles and traces.
 template <bool AKS, bool BKS, int EPI_, bool OUTF32>
 __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
-  constexpr int LIVE = EPI_ == EPI_NONE_LIVE ? 1 : (EPI_ == EPI_NONE_BLK ? 2 : 0);
+  constexpr bool BLK = EPI_ == EPI_NONE_BLK;
   constexpr bool ROWS = EPI_ >= EPI_ROWS;
   constexpr bool SLAB = EPI_ >= EPI_ROWS + EPI_SLABS;      // the remap in 8-row slabs (EPI_SLABS)
-  constexpr int EPI = LIVE ? (int)EPI_NONE : (ROWS ? EPI_ - EPI_ROWS - (SLAB ? EPI_SLABS : 0) : EPI_);
+  constexpr int EPI = BLK ? (int)EPI_NONE : (ROWS ? EPI_ - EPI_ROWS - (SLAB ? EPI_SLABS : 0) : EPI_);
   constexpr bool GUARDABLE = ROWS && EPI == EPI_BIAS;      // (tile_blocks)
   static_assert(!SLAB || EPI == EPI_NONE || EPI == EPI_ADD || (!BKS && (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU)), "slab remap: the plain data gradients and three forward forms");
-  static_assert(!LIVE || (AKS && BKS && OUTF32), "live k-tiles: the weight-gradient form only");
+  static_assert(!BLK || (AKS && BKS && OUTF32), "live blocks: the weight-gradient form only");
   static_assert(!ROWS || (!AKS && !OUTF32 && (EPI == EPI_NONE || EPI == EPI_ADD || EPI == EPI_DGELU_CS ||
                                               (!BKS && (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_GELU_ACT || EPI == EPI_BIAS_ADD)))),
                 "row remap: the data-gradient forms and the k-contiguous forward forms only");
@@ -1444,30 +1433,21 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
   }
   const int kt0 = p.split_id * p.nk_per_split;
   int n_tiles = min(nk_all, kt0 + p.nk_per_split) - kt0;
-  // LIVE: the 64 mask words of this k-slab, one per lane (the host refuses the mask for slabs of more than 2048 k-tiles), fetched
+  // BLK: the 64 mask words of this k-slab, one per lane (the host drops the mask for slabs blk_mask_fits refuses), fetched
   // here -- one vector load pair per lane, waited for on the spot -- so that the k loop's walk over them touches no memory.  A slab starts
   // at any bit of the mask: each lane shifts its 32 bits out of two words, and clips them to the slab's end.
   uint32_t live_mv = 0u;
   [[maybe_unused]] int n_blk = 0;
-  if constexpr (LIVE == 2) {
-    // block bits 2 kt0 .. 2 (kt0 + n_tiles) - 1 of the mask, clipped to the blocks K has (at most 64 words: the host keeps a slab at
-    // BLK_MAX_KTILES k-tiles or fewer); n_tiles becomes the number of PAIRS of live blocks
+  if constexpr (BLK) {
+    // block bits 2 kt0 .. 2 (kt0 + n_tiles) - 1 of the mask, clipped to the blocks K has; n_tiles becomes the number of PAIRS of live blocks
     const int nb_all = (p.K + 31) >> 5, nw = (nb_all + 31) >> 5, first = 2 * kt0 + 32 * lane0, wlo = first >> 5, sh = first & 31;
     const int left = min(2 * (kt0 + n_tiles), nb_all) - first;
-    const uint32_t lo = wlo < nw ? p.live_kt[wlo] : 0u, hi = wlo + 1 < nw ? p.live_kt[wlo + 1] : 0u;
+    const uint32_t lo = wlo < nw ? p.live_blk[wlo] : 0u, hi = wlo + 1 < nw ? p.live_blk[wlo + 1] : 0u;
     live_mv = sh ? (lo >> sh) | (hi << (32 - sh)) : lo;
     live_mv = left >= 32 ? live_mv : (left > 0 ? live_mv & ((1u << left) - 1u) : 0u);
     for (uint64_t rest = __ballot(live_mv != 0u); rest; rest &= rest - 1ull)
       n_blk += __builtin_popcount(__builtin_amdgcn_readlane(live_mv, __builtin_ctzll(rest)));
     n_tiles = (n_blk + 1) >> 1;
-  } else if constexpr (LIVE) {
-    const int nw = (nk_all + 31) >> 5, first = kt0 + 32 * lane0, wlo = first >> 5, sh = first & 31, left = n_tiles - 32 * lane0;
-    const uint32_t lo = wlo < nw ? p.live_kt[wlo] : 0u, hi = wlo + 1 < nw ? p.live_kt[wlo + 1] : 0u;
-    live_mv = sh ? (lo >> sh) | (hi << (32 - sh)) : lo;
-    live_mv = left >= 32 ? live_mv : (left > 0 ? live_mv & ((1u << left) - 1u) : 0u);
-    n_tiles = 0;
-    for (uint64_t rest = __ballot(live_mv != 0u); rest; rest &= rest - 1ull)
-      n_tiles += __builtin_popcount(__builtin_amdgcn_readlane(live_mv, __builtin_ctzll(rest)));
   }
   constexpr int PEND = 2 * (16 * epi_stores_per_call<EPI, OUTF32>() + epi_extra_stores<EPI>());   // store instructions of one full-tile epilogue, per wave
   auto coords = [&](int tile, int& bm, int& bn) {
@@ -1488,7 +1468,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
     const uint64_t oa = (uint64_t)(AKS ? kt0 * BK : (ROWS ? 0 : bm * BM)) * p.lda, ob = (uint64_t)(BKS ? kt0 * BK : bn * BN) * p.ldb;
     // (the bf16 bias form keeps 64 bias values in registers across the main loop -- 468 of 512: the peeled first trip spilled there)
     constexpr bool PEEL_OK = !(EPI == EPI_BIAS && !OUTF32 && !BKS);
-    main_loop<AKS, BKS, PEND, PEEL_OK, LIVE, ROWS, SLAB>(p, smem, acc, rsrc_at(p.A, p.a_bytes, oa), rsrc_at(p.B, p.b_bytes, ob), AKS ? bm * BM : 0, BKS ? bn * BN : 0, kt0,
+    main_loop<AKS, BKS, PEND, PEEL_OK, BLK, ROWS, SLAB>(p, smem, acc, rsrc_at(p.A, p.a_bytes, oa), rsrc_at(p.B, p.b_bytes, ob), AKS ? bm * BM : 0, BKS ? bn * BN : 0, kt0,
                               AKS ? 0 : kt0, BKS ? 0 : kt0, n_tiles, nk_all, wm, wn, wave, lane, prologue_only, stores_in_flight, live_mv, ro, n_blk);
   };
 
@@ -1951,7 +1931,6 @@ __global__ __launch_bounds__(256) void zero_dead_slabs_kernel(const int* __restr
 enum KernelForm {
   FORM_T256W,            // this instantiation of t256w
   FORM_T256LA,           // the look-ahead kernel
-  FORM_WGRAD_KTILES,     // the live-k-tile weight gradient
   FORM_ROWS_T256W,       // the row remap (32-row blocks) of FORM_T256W ...
   FORM_ROWS_T256LA,      // ... and of FORM_T256LA
   FORM_WGRAD_KBLOCKS,    // the live-block weight gradient
@@ -1960,17 +1939,17 @@ enum KernelForm {
   FORM_COUNT
 };
 
-// kind: what a.live_kt / a.row_blk point at (KBLOCKS: a mask of 32-row blocks, ia_kblock_mask; SLABS: a slab list, ia_row_slabs)
+// kind: what a.row_blk points at (SLABS: a slab list, ia_row_slabs; else a list of 32-row blocks); a.live_blk is always an ia_kblock_mask
 template <bool AKS, bool BKS, int EPI, bool OUTF32>
 int launch(GemmArgs a, bool big, hipStream_t st, IaRowFilter::Kind kind = IaRowFilter::NONE) {
   constexpr int vid = AKS * 1000 + BKS * 100 + EPI * 10 + (OUTF32 ? 1 : 0);
   // the forms that may carry a block list (GemmArgs::row_blk): the data gradients, and the forward epilogues on k-contiguous operands
   constexpr bool DROWS = !AKS && !OUTF32 && (EPI == EPI_NONE || EPI == EPI_ADD || EPI == EPI_DGELU_CS ||
                                              (!BKS && (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_GELU_ACT || EPI == EPI_BIAS_ADD)));
-  // (a launch over the live k-tiles only is not recorded: the host cannot know how many k-tiles it executed, and the recorded FLOPs are
+  // (a launch over the live blocks only is not recorded: the host cannot know how many blocks it executed, and the recorded FLOPs are
   // those of launches that executed all of theirs)
-  constexpr bool WGRAD = AKS && BKS && EPI == EPI_NONE && OUTF32;      // the form that may carry a live-k-tile mask (GemmArgs::live_kt)
-  const bool rec = g_prof.on && g_prof.variant == vid && g_prof.n < g_prof.cap && !(WGRAD && a.live_kt) && !(DROWS && a.row_blk);
+  constexpr bool WGRAD = AKS && BKS && EPI == EPI_NONE && OUTF32;      // the form that may carry a live-block mask (GemmArgs::live_blk)
+  const bool rec = g_prof.on && g_prof.variant == vid && g_prof.n < g_prof.cap && !(WGRAD && a.live_blk) && !(DROWS && a.row_blk);
   if (rec) (void)hipEventRecord(g_prof.ev[2 * g_prof.n], st);
   if (big) {
     a.tiles_m = (a.M + t256w::BM - 1) / t256w::BM; a.tiles_n = (a.N + t256w::BN - 1) / t256w::BN;
@@ -1985,8 +1964,7 @@ int launch(GemmArgs a, bool big, hipStream_t st, IaRowFilter::Kind kind = IaRowF
     static bool attr_set[FORM_COUNT] = {};
     KernelForm form = FORM_T256W;
     if constexpr (WGRAD) {
-      if (a.live_kt && kind == IaRowFilter::KBLOCKS) { kern = t256w::gemm_kernel<true, true, EPI_NONE_BLK, true>; form = FORM_WGRAD_KBLOCKS; }
-      else if (a.live_kt) { kern = t256w::gemm_kernel<true, true, EPI_NONE_LIVE, true>; form = FORM_WGRAD_KTILES; }
+      if (a.live_blk) { kern = t256w::gemm_kernel<true, true, EPI_NONE_BLK, true>; form = FORM_WGRAD_KBLOCKS; }
     }
     // plain NT form, several tiles per workgroup, static order: the look-ahead kernel (t256la; IA_GEMM_LA=0 keeps t256w)
     if constexpr (!AKS && !BKS && EPI == EPI_NONE && !OUTF32) {
@@ -2386,9 +2364,9 @@ extern "C" int ia_row_groups_packed_host(const uint8_t* row_live, int M_rows, in
   list[0] = 4 * (pack_rows(n) + cut_rows); list[1] = n_dead; list[2] = nb;
   return IA_OK;
 }
-// ---- the liveness masks of the weight gradients
-// bit t of a mask = OR of row_live over rows ROWS t .. ROWS t + ROWS - 1 (clipped to M).  ROWS = 64: the k-tiles (ia_ktile_mask); 32: the
-// 32-row blocks of k (ia_kblock_mask).  One function for the device kernels and the host entries.
+// ---- the liveness mask of the weight gradient
+// bit t of the mask = OR of row_live over rows 32 t .. 32 t + 31 (clipped to M): the 32-row blocks of k (ia_kblock_mask).  One function
+// for the device kernel and the host entry.
 template <int ROWS>
 static __host__ __device__ inline uint32_t rows_live(const uint8_t* row_live, int M, int t) {
   const uint8_t* r = row_live + (size_t)t * ROWS;
@@ -2403,41 +2381,27 @@ static __host__ __device__ inline uint32_t rows_live(const uint8_t* row_live, in
 }
 namespace {
 // one thread per bit, one 64-bit ballot per wave = two whole mask words, stored by lanes 0 and 32 (plain stores, no atomics)
-__global__ __launch_bounds__(256) void ktile_mask_kernel(const uint8_t* __restrict__ row_live, int M, int nk, uint32_t* __restrict__ mask) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  const uint64_t b = __ballot(t < nk && rows_live<BK>(row_live, M, t));
-  if ((threadIdx.x & 31) == 0 && t < nk) mask[t >> 5] = (uint32_t)(b >> (threadIdx.x & 32));
-}
 __global__ __launch_bounds__(256) void kblock_mask_kernel(const uint8_t* __restrict__ row_live, int M, int nb, uint32_t* __restrict__ mask) {
   const int b = blockIdx.x * 256 + threadIdx.x;
   const uint64_t v = __ballot(b < nb && rows_live<32>(row_live, M, b));
   if ((threadIdx.x & 31) == 0 && b < nb) mask[b >> 5] = (uint32_t)(v >> (threadIdx.x & 32));
 }
-template <int ROWS>
-size_t live_mask_bytes(int M) { return M <= 0 ? 0 : (size_t)(((M + ROWS - 1) / ROWS + 31) / 32) * sizeof(uint32_t); }
-template <int ROWS>
-int live_mask(const uint8_t* row_live, int M, uint32_t* mask, hipStream_t stream) {
+}  // namespace
+extern "C" size_t ia_kblock_mask_bytes(int M_rows) { return M_rows <= 0 ? 0 : (size_t)(((M_rows + 31) / 32 + 31) / 32) * sizeof(uint32_t); }
+extern "C" int ia_kblock_mask(const uint8_t* row_live, int M_rows, uint32_t* mask, hipStream_t stream) {
   (void)hipGetLastError();
-  if (!row_live || !mask || M <= 0) return IA_ERR_ARG;
-  const int nbits = (M + ROWS - 1) / ROWS;
-  hipLaunchKernelGGL((ROWS == BK ? ktile_mask_kernel : kblock_mask_kernel), dim3((nbits + 255) / 256), dim3(256), 0, stream, row_live, M, nbits, mask);
+  if (!row_live || !mask || M_rows <= 0) return IA_ERR_ARG;
+  const int nb = (M_rows + 31) / 32;
+  hipLaunchKernelGGL(kblock_mask_kernel, dim3((nb + 255) / 256), dim3(256), 0, stream, row_live, M_rows, nb, mask);
   return ia_check_launch();
 }
-template <int ROWS>
-int live_mask_host(const uint8_t* row_live, int M, uint32_t* mask) {
-  if (!row_live || !mask || M <= 0) return IA_ERR_ARG;
-  const int nbits = (M + ROWS - 1) / ROWS;
-  for (int w = 0; w < (nbits + 31) / 32; ++w) mask[w] = 0u;
-  for (int t = 0; t < nbits; ++t) mask[t >> 5] |= rows_live<ROWS>(row_live, M, t) << (t & 31);
+extern "C" int ia_kblock_mask_host(const uint8_t* row_live, int M_rows, uint32_t* mask) {
+  if (!row_live || !mask || M_rows <= 0) return IA_ERR_ARG;
+  const int nb = (M_rows + 31) / 32;
+  for (int w = 0; w < (nb + 31) / 32; ++w) mask[w] = 0u;
+  for (int t = 0; t < nb; ++t) mask[t >> 5] |= rows_live<32>(row_live, M_rows, t) << (t & 31);
   return IA_OK;
 }
-}  // namespace
-extern "C" size_t ia_ktile_mask_bytes(int M_rows) { return live_mask_bytes<BK>(M_rows); }
-extern "C" int ia_ktile_mask(const uint8_t* row_live, int M_rows, uint32_t* mask, hipStream_t stream) { return live_mask<BK>(row_live, M_rows, mask, stream); }
-extern "C" int ia_ktile_mask_host(const uint8_t* row_live, int M_rows, uint32_t* mask) { return live_mask_host<BK>(row_live, M_rows, mask); }
-extern "C" size_t ia_kblock_mask_bytes(int M_rows) { return live_mask_bytes<32>(M_rows); }
-extern "C" int ia_kblock_mask(const uint8_t* row_live, int M_rows, uint32_t* mask, hipStream_t stream) { return live_mask<32>(row_live, M_rows, mask, stream); }
-extern "C" int ia_kblock_mask_host(const uint8_t* row_live, int M_rows, uint32_t* mask) { return live_mask_host<32>(row_live, M_rows, mask); }
 
 // ---- one descriptor for all of them (IaRowFilter, common.h): the list of a kind, by size and by builder
 size_t ia_row_filter_bytes(IaRowFilter::Kind kind, int M) {
@@ -2446,7 +2410,6 @@ size_t ia_row_filter_bytes(IaRowFilter::Kind kind, int M) {
     case IaRowFilter::GROUPS: return ia_row_groups_bytes(M);
     case IaRowFilter::PACKED: return ia_row_groups_packed_bytes(M);
     case IaRowFilter::SLABS: return ia_row_slabs_bytes(M);
-    case IaRowFilter::KTILES: return ia_ktile_mask_bytes(M);
     case IaRowFilter::KBLOCKS: return ia_kblock_mask_bytes(M);
     case IaRowFilter::NONE: break;
   }
@@ -2458,7 +2421,6 @@ int ia_row_filter_build(IaRowFilter::Kind kind, const uint8_t* row_live, int M, 
     case IaRowFilter::GROUPS: return ia_row_groups(row_live, M, (int*)dst, stream);
     case IaRowFilter::PACKED: return ia_row_groups_packed(row_live, M, (int*)dst, stream);
     case IaRowFilter::SLABS: return ia_row_slabs(row_live, M, (int*)dst, stream);
-    case IaRowFilter::KTILES: return ia_ktile_mask(row_live, M, (uint32_t*)dst, stream);
     case IaRowFilter::KBLOCKS: return ia_kblock_mask(row_live, M, (uint32_t*)dst, stream);
     case IaRowFilter::NONE: break;
   }
@@ -2503,7 +2465,7 @@ int ia_gemm_dgrad_filtered(const void* dY, int ldy, const void* W, int w_kstride
 }
 int ia_gemm_wgrad_filtered(const void* dY, int ldy, const void* X, int ldx, float* dW, int ldw, int N_out, int N_in, int M_rows, IaRowFilter filter,
                            int accumulate, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  if (filter.kind != IaRowFilter::NONE && filter.kind != IaRowFilter::KTILES && filter.kind != IaRowFilter::KBLOCKS) return IA_ERR_UNSUPPORTED;
+  if (filter.kind != IaRowFilter::NONE && filter.kind != IaRowFilter::KBLOCKS) return IA_ERR_UNSUPPORTED;
   GemmCall c{dY, 1, ldy, X, 1, ldx, dW, 1, ldw, N_out, N_in, M_rows};
   c.accumulate = accumulate; c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.filter = filter;
   return gemm_core(c, stream);
@@ -2533,7 +2495,7 @@ static int filter_from_rows(IaRowFilter::Kind kind, const uint8_t* row_live, int
   *filter = IaRowFilter{kind, nullptr, fill != 0};
   if (!row_live) return IA_OK;
   if (rows <= 0 || n1 <= 0 || n2 <= 0) return IA_ERR_ARG;
-  const uintptr_t align = (kind == IaRowFilter::KTILES || kind == IaRowFilter::KBLOCKS) ? 15 : 31;
+  const uintptr_t align = kind == IaRowFilter::KBLOCKS ? 15 : 31;
   if (!workspace || *workspace_bytes < front + ia_row_filter_bytes(kind, rows) || ((uintptr_t)workspace & align)) return IA_ERR_WORKSPACE;
   void* const list = (char*)workspace + front;
   filter->list = list;
@@ -2619,21 +2581,21 @@ extern "C" int ia_gemm_dgrad_slabs(const void* dY, int ldy, const void* W, int w
 }
 extern "C" size_t ia_gemm_wgrad_rows_workspace_bytes(int N_out, int N_in, int M_rows) {
   if (N_out <= 0 || N_in <= 0 || M_rows <= 0) return 0;
-  return al256(ia_gemm_workspace_bytes(N_out, N_in, M_rows, 1)) + ia_ktile_mask_bytes(M_rows);
+  return al256(ia_gemm_workspace_bytes(N_out, N_in, M_rows, 1)) + ia_kblock_mask_bytes(M_rows);
 }
-// 1: a call of this shape with row_live and the workspace of the query above walks the live k-tiles (256-wide kernel, at most
-// LIVE_MAX_KTILES k-tiles per k-slab); 0: it runs every k-tile, like ia_gemm_bf16 (the same conditions as gemm_core's)
+// 1: a call of this shape with row_live and the workspace of the query above walks the live 32-row blocks (256-wide kernel, a k-slab
+// the mask words of one wave cover: t256w::blk_mask_fits); 0: it runs every row, like ia_gemm_bf16 (the same conditions as gemm_core's)
 extern "C" int ia_gemm_wgrad_rows_filters(int N_out, int N_in, int M_rows) {
   if (N_out <= 0 || N_in <= 0 || M_rows <= 0) return 0;
   const Plan pl = make_plan(N_out, N_in, M_rows, true);
   const int nk = (M_rows + BK - 1) / BK;
-  return pl.big && (nk + pl.splits - 1) / pl.splits <= t256w::LIVE_MAX_KTILES ? 1 : 0;
+  return pl.big && t256w::blk_mask_fits((nk + pl.splits - 1) / pl.splits) ? 1 : 0;
 }
-// the weight gradient over the live 64-row k-tiles: the split-K partials in front of the workspace, the mask behind them
+// the weight gradient over the live 32-row blocks: the split-K partials in front of the workspace, the mask behind them
 extern "C" int ia_gemm_wgrad_rows(const void* dY, int ldy, const void* X, int ldx, float* dW, int ldw, int N_out, int N_in, int M_rows,
                                   const uint8_t* row_live, int accumulate, void* workspace, size_t workspace_bytes, hipStream_t stream) {
   IaRowFilter f;
-  int rc = filter_from_rows(IaRowFilter::KTILES, row_live, 1, M_rows, N_out, N_in, al256(ia_gemm_workspace_bytes(N_out, N_in, M_rows, 1)), workspace,
+  int rc = filter_from_rows(IaRowFilter::KBLOCKS, row_live, 1, M_rows, N_out, N_in, al256(ia_gemm_workspace_bytes(N_out, N_in, M_rows, 1)), workspace,
                             &workspace_bytes, stream, &f);
   return rc ? rc : ia_gemm_wgrad_filtered(dY, ldy, X, ldx, dW, ldw, N_out, N_in, M_rows, f, accumulate, workspace, workspace_bytes, stream);
 }
@@ -2730,17 +2692,13 @@ static int gemm_core(const GemmCall& c, hipStream_t stream) {
   // What the filter holds: a mask of the live k (weight gradient), or a list of the live rows (the other forms).  Which (kind, epilogue)
   // pairs exist is the business of ia_gemm_fwd_form / ia_gemm_dgrad_form; here a filter only ever falls back to every row.
   const IaRowFilter::Kind kind = c.filter.kind;
-  const bool k_mask = kind == IaRowFilter::KTILES || kind == IaRowFilter::KBLOCKS, row_list = kind != IaRowFilter::NONE && !k_mask;
-  // the live-k-tile mask: the 256-wide weight-gradient kernel only, one mask word per lane and k-slab (anything else runs dense)
-  // GemmArgs::live_kt shares the slot of GemmArgs::bias (filled above from the caller's argument): in the weight-gradient form, whose
+  const bool k_mask = kind == IaRowFilter::KBLOCKS, row_list = kind != IaRowFilter::NONE && !k_mask;
+  // the live-block mask: the 256-wide weight-gradient kernel only, one mask word per lane and k-slab (anything else runs dense).
+  // GemmArgs::live_blk shares the slot of GemmArgs::bias (filled above from the caller's argument): in the weight-gradient form, whose
   // 256-wide kernel reads the slot as the mask, it is overwritten HERE for every caller -- a stray bias passed with IA_EPI_NONE, the
   // shifted views of ia_gemm_view -- so the kernel sees a mask or NULL, never a bias.  launch<true, true, EPI_NONE, true> is reached
   // from this function only; a new call site that fills GemmArgs for this form must do the same.
-  // (KBLOCKS: the mask holds 32-row blocks, two bits per k-tile of the slab -- half the slab length, else dense: a block mask cannot
-  // stand in for the 64-row one)
-  if (wgrad_form)
-    g.live_kt = (k_mask && big && g.nk_per_split <= (kind == IaRowFilter::KBLOCKS ? t256w::BLK_MAX_KTILES : t256w::LIVE_MAX_KTILES))
-                    ? (const uint32_t*)c.filter.list : nullptr;
+  if (wgrad_form) g.live_blk = (k_mask && big && t256w::blk_mask_fits(g.nk_per_split)) ? (const uint32_t*)c.filter.list : nullptr;
   // the list of the row-remapped forms (C2 has C's pitch, so dgrad_rows_fit covers it): a list or NULL
   const bool fwd_epi = !bks && (epilogue == EPI_BIAS || epilogue == EPI_BIAS_GELU || epilogue == EPI_BIAS_GELU_ACT || epilogue == EPI_BIAS_ADD);
   g.row_blk = nullptr; g.rows_fill = c.filter.fill ? 1 : 0; g.fill_m = M; g.rows_guarded = c.tail ? 1 : 0;

@@ -70,11 +70,6 @@ def _row_list(name, row_live):
     return out
 
 
-def ktile_mask(row_live):
-    """bit (t & 31) of word t >> 5 = any(row_live[64t : 64t + 64]) (uint8 [M] on the GPU) -> int32 words"""
-    return _row_list("ktile_mask", row_live)
-
-
 def kblock_mask(row_live):
     """bit (b & 31) of word b >> 5 = any(row_live[32b : 32b + 32]) (uint8 [M] on the GPU) -> int32 words"""
     return _row_list("kblock_mask", row_live)
@@ -100,7 +95,7 @@ def gemm_wgrad_blocks(dy, x, mask=None, *, out=None, accumulate=False):
 
 def gemm_wgrad_rows(dy, x, row_live=None, *, out=None, accumulate=False):
     """dW[N_out, N_in] (+)= dy[M, N_out]^T x[M, N_in] in fp32; row_live (uint8 [M]) == 0 promises that row of dy is all zeros, and
-    64-row blocks without a live row are skipped (ia_gemm_wgrad_rows).  row_live=None is gemm(..., a_kstrided, b_kstrided, out_f32)."""
+    32-row blocks without a live row are skipped (ia_gemm_wgrad_rows).  row_live=None is gemm(..., a_kstrided, b_kstrided, out_f32)."""
     lib = _lib.load()
     _need(dy, BF16, "dy"); _need(x, BF16, "x"); _need(row_live, torch.uint8, "row_live")
     (M, n_out), (Mx, n_in) = dy.shape, x.shape

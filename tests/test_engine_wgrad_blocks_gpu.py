@@ -1,9 +1,9 @@
 """ia_layer_bwd2 of a post-LN layer with the weight gradients on the 32-row block mask (ia_kblock_mask): the "wide" configuration of
 tests/test_engine_wgrad_rows_gpu.py (H 1024, I 4096, B 32, L 255: all four weight gradients take the 256-wide kernel), three ways --
 (a) masked_rows_dead = 0, (b) masked with the mask the call builds itself, (c) masked with a caller's ia_kblock_mask_host mask in
-ia_layer_cfg::key_rows.kblocks -- and every gradient and dx equal bit for bit across the three.  (d) The 64-row walk, which no layer call
-reaches, at the same width: ia_gemm_wgrad_rows over the key mask on the operands of (a)'s QKV weight gradient (its dy as the backward
-left it in the scratch, and x) gives (a)'s gradient bit for bit.
+ia_layer_cfg::key_rows.kblocks -- and every gradient and dx equal bit for bit across the three.  (d) The same walk through the entry
+that takes the rows' live bytes, at the same width: ia_gemm_wgrad_rows over the key mask on the operands of (a)'s QKV weight gradient (its
+dy as the backward left it in the scratch, and x) gives (a)'s gradient bit for bit.
 
 In (b) and (c) the scratch is filled with 0xFF bytes (bf16 NaN everywhere) before the call: nothing the backward reads there may be left
 over from before the call.  The layer input x -- read by the QKV weight gradient
@@ -129,7 +129,7 @@ def test_layer_bwd2_block_mask_equals_dense(gpu, drop):
     blk_dead = ~pad.view(nb, BLK).any(1)
     dead_rows = blk_dead.repeat_interleave(BLK)[:M]
     halves = torch.cat([blk_dead, blk_dead.new_ones(nb % 2)]).view(-1, 2)
-    half_dead = (halves.sum(1) == 1).sum().item()      # k-tiles with exactly one dead half: what a 64-row walk would read
+    half_dead = (halves.sum(1) == 1).sum().item()      # k-tiles with exactly one dead half: what a walk over whole k-tiles would read
     assert dead_rows.sum().item() >= 40 * BLK and half_dead >= 8
     xp = x.clone()
     xp[dead_rows] = float("inf")

@@ -1,5 +1,5 @@
 """ia_layer_bwd2 of a post-LN layer with ia_layer_cfg::masked_rows_dead: the four weight gradients go through the row-filtered GEMM
-(one live-k-tile bitmask per call, built into the scratch) and every gradient stays what the dense backward (masked_rows_dead = 0)
+(one bitmask of the live 32-row blocks per call, built into the scratch) and every gradient stays what the dense backward (masked_rows_dead = 0)
 returns, bit for bit, with dropout on and off.
 
 Two configurations.  "small": B = 3 sequences of L = 255 with lengths 255, 64 and 27 (a full row, a padding that starts on a 64-row tile
@@ -8,7 +8,7 @@ the 128-wide kernel and read every row, so it checks the plumbing only.  "wide":
 them): all four weight gradients take the 256-wide kernel and honour the bitmask (asserted through ia_gemm_wgrad_rows_filters), so the
 scratch carve of the mask, the helper's shapes and the one-mask-for-four-GEMMs reuse are what the equality checks.  There the layer input x
 -- which the backward reads in the QKV weight gradient only -- is also overwritten with infinities in the rows of k-tiles that are dead as a
-whole: a GEMM that read them would turn 0 x inf into NaN."""
+whole (tests/test_engine_wgrad_blocks_gpu.py does the same for every dead 32-row block): a GEMM that read them would turn 0 x inf into NaN."""
 import ctypes as C
 
 import pytest

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_gemm_wgrad_rows_gpu import patterns as ktile_patterns, rel_err, slab_tiles
+from wgrad_masks import patterns as ktile_patterns, rel_err, slab_tiles
 
 pytestmark = pytest.mark.gpu
 
@@ -18,7 +18,7 @@ SHAPES = [(1280, 1024, 4080), (2560, 2048, 1275), (4352, 4096, 765)]
 
 
 def patterns(n_out, n_in, rows):
-    """name -> row_live (numpy uint8 [rows]): the 64-row file's patterns and the ones only a 32-row walk can get wrong"""
+    """name -> row_live (numpy uint8 [rows]): the patterns laid out on 64-row k-tiles (tests/wgrad_masks.py) and the ones only a 32-row walk can get wrong"""
     out = dict(ktile_patterns(n_out, n_in, rows))
     nk, per = slab_tiles(n_out, n_in, rows)
     nb = (rows + BLK - 1) // BLK
@@ -108,7 +108,7 @@ def test_wgrad_blocks_matches_dense_and_skips_dead_blocks(gpu, operands, n_out, 
             assert not torch.isfinite(ops.gemm(dyp, xp, a_kstrided=True, b_kstrided=True, out_f32=True)).all(), name
 
 
-@pytest.mark.parametrize("rows", [1, 31, 33, 1275, 4080, 130560])
+@pytest.mark.parametrize("rows", [1, 31, 33, 1275, 4080, 130560, 2048 * 64 + 100])
 def test_kblock_mask_kernel_matches_host(gpu, rows):
     from item_alignment_amd import ops
     rs = np.random.RandomState(rows)

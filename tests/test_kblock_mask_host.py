@@ -1,10 +1,13 @@
-"""Host-side checks of the 32-row block mask (no GPU): ia_kblock_mask_host -- the per-block function the device kernel runs too -- against a
-numpy OR-reduce, against ia_ktile_mask_host (a 64-row k-tile is live when either of its two blocks is), and the size query."""
+"""Host-side checks of the row-filtered weight gradient (no GPU): the 32-row block mask as ia_kblock_mask_host computes it -- the
+per-block function the device kernel runs too -- against a numpy OR-reduce at 32 rows and, pairwise, at 64 (a 64-row k-tile is live when
+either of its two blocks is), the size query, and the workspace and filter queries of ia_gemm_wgrad_rows."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
 BLK = 32
-ROWS = [1, 31, 32, 33, 1275, 4080, 130560]
+ROWS = [1, 31, 32, 33, 63, 64, 65, 1275, 4080, 2048 + 17, 2048 * 64, 130560, 2048 * 64 + 100]
 
 
 def numpy_mask(live, step):
@@ -37,14 +40,13 @@ def test_kblock_mask_host_matches_numpy(rows):
 
 
 @pytest.mark.parametrize("rows", ROWS)
-def test_adjacent_block_bits_or_to_the_ktile_mask(rows):
+def test_adjacent_block_bits_or_to_the_64_row_mask(rows):
     from item_alignment_amd import _lib
     lib = _lib.load()
     for density, live in cases(rows):
         blk = np.zeros(lib.ia_kblock_mask_bytes(rows) // 4, np.uint32)
-        kt = np.zeros(lib.ia_ktile_mask_bytes(rows) // 4, np.uint32)
+        kt = numpy_mask(live, 2 * BLK)                      # one bit per 64-row k-tile, straight from row_live
         assert lib.ia_kblock_mask_host(live.ctypes.data, rows, blk.ctypes.data) == 0
-        assert lib.ia_ktile_mask_host(live.ctypes.data, rows, kt.ctypes.data) == 0
         bits = np.unpackbits(blk.view(np.uint8), bitorder="little")
         bits = np.concatenate([bits, np.zeros(-len(bits) % 64, np.uint8)])
         pairs = bits[0::2] | bits[1::2]
@@ -61,3 +63,31 @@ def test_kblock_mask_argument_checks():
     assert lib.ia_kblock_mask_host(one.ctypes.data, 10, None) == -1
     assert lib.ia_kblock_mask_host(one.ctypes.data, 0, one.ctypes.data) == -1
     assert lib.ia_kblock_mask(None, 10, None, None) == -1
+
+
+def test_wgrad_rows_workspace_query():
+    """split-K partials (rounded up to 256 bytes) in front, the block mask behind them"""
+    from item_alignment_amd import _lib
+    lib = _lib.load()
+    al = lambda b: (b + 255) // 256 * 256
+    for n_out, n_in, rows in [(1024, 1024, 130560), (4096, 1024, 130560), (3072, 1024, 32640), (256, 256, 1275), (128, 64, 70)]:
+        want = al(lib.ia_gemm_workspace_bytes(n_out, n_in, rows, 1)) + lib.ia_kblock_mask_bytes(rows)
+        assert lib.ia_gemm_wgrad_rows_workspace_bytes(n_out, n_in, rows) == want
+    assert lib.ia_gemm_wgrad_rows_workspace_bytes(0, 8, 8) == 0
+    # the text towers' weight gradients are filtered, outputs below the 256-wide kernel's plan are not
+    assert lib.ia_gemm_wgrad_rows_filters(1024, 1024, 130560) == 1 and lib.ia_gemm_wgrad_rows_filters(4096, 1024, 130560) == 1
+    assert lib.ia_gemm_wgrad_rows_filters(256, 256, 1275) == 0 and lib.ia_gemm_wgrad_rows_filters(0, 8, 8) == 0
+    # a row filter without the workspace for its bitmask is refused before anything is launched
+    buf = C.create_string_buffer(64)
+    p = C.addressof(buf)
+    assert lib.ia_gemm_wgrad_rows(p, 256, p, 256, p, 256, 256, 256, 1275, p, 0, None, 0, None) == -3
+
+
+def test_wgrad_rows_filters_at_the_slab_length_limit():
+    """The query answers for the kernel that is there: one mask word per lane is 2048 block bits, so a k-slab of more than 1024 k-tiles
+    runs every row.  1024x1024: the plan cuts k into 16 slabs -- 1 044 480 rows are slabs of 1020 k-tiles (filtered), 2 088 960 rows
+    slabs of 2040 (dense).  Host only: the query allocates and launches nothing."""
+    from item_alignment_amd import _lib
+    lib = _lib.load()
+    assert lib.ia_gemm_wgrad_rows_filters(1024, 1024, 1044480) == 1
+    assert lib.ia_gemm_wgrad_rows_filters(1024, 1024, 2088960) == 0

@@ -84,7 +84,7 @@ def test_row_slabs_rejects_bad_arguments():
 def test_slab_entry_points_are_declared_bound_and_exported():
     lib = _lib.load()
     header = open(os.path.join(os.path.dirname(_lib._HERE), "include", "itemalign.h")).read()
-    assert _lib.ABI_VERSION == 21 == lib.ia_abi_version() == int(re.search(r"#define IA_ABI_VERSION (\d+)", header).group(1))
+    assert _lib.ABI_VERSION == 22 == lib.ia_abi_version() == int(re.search(r"#define IA_ABI_VERSION (\d+)", header).group(1))
     for name in ("ia_row_slabs_bytes", "ia_row_slabs", "ia_row_slabs_host", "ia_gemm_slabs_workspace_bytes",
                  "ia_gemm_fwd_slabs", "ia_gemm_dgrad_slabs"):
         assert re.search(r"\b%s\(" % name, header), name
