@@ -8,7 +8,12 @@ Flags and defaults are the reference's; --max_steps and --num_workers are added.
 N2 and N3): the labels of the caption loss are input_ids[:, 1:] (the reference's [:, 2:] cannot run), and gradients accumulate over
 --gradient_accumulation_steps micro-batches (the reference clears them at every micro-step).  The ViT's geometry comes from the config
 file (patch_size, hidden_size, num_hidden_layers, num_attention_heads), as the reference's ViT(config) takes it; its weights from
-image_encoder.bin under --pretrained_image_model_path.  One process, one GPU.
+image_encoder.bin under --pretrained_image_model_path.
+
+One process drives one GPU.  Under a launcher (python -m torch.distributed.run --nproc-per-node N coca_pretrain.py ...) the N ranks
+train data-parallel on one global batch: --train_batch_size stays the total, every rank takes 1/N of it, every item of the other
+ranks is a contrastive negative (CoCaForPretraining.set_data_parallel), gradients are averaged in overlapped buckets
+and rank 0 writes the files.  Without WORLD_SIZE the script is the one-process script.
 """
 import argparse
 import json
@@ -80,6 +85,14 @@ def load_raw_data(args):
     return data
 
 
+def collate_or_none(inputs):
+    """collate_coca, or None where every item of the micro-batch lost its image (a rank's share may be that small)"""
+    from item_alignment_amd.data.datasets import collate_coca
+    if not any(i.get("image") is not None for i in inputs):
+        return None
+    return collate_coca(inputs)
+
+
 def main(argv=None):
     args = get_parser().parse_args(argv)
     import torch
@@ -87,8 +100,9 @@ def main(argv=None):
         raise SystemExit("this model runs on the MI355X HIP engine only (no CPU path); no GPU is visible")
     from types import SimpleNamespace
 
-    from torch.utils.data import DataLoader
+    from torch.utils.data import DataLoader, Subset
 
+    from item_alignment_amd import dist as iadist
     from item_alignment_amd import train
     from item_alignment_amd.cli_common import freeze_and_resume, load_config, load_tokenizer
     from item_alignment_amd.data.datasets import MultimodalDataset, collate_coca
@@ -96,7 +110,12 @@ def main(argv=None):
     from item_alignment_amd.models import functional as Fn
     from item_alignment_amd.utils import VIT_WEIGHTS_NAME, logger
 
-    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
+    rank, world, local = iadist.init_from_env("cuda")
+    dp = world > 1
+    per_rank = args.train_batch_size // world
+    if per_rank * world != args.train_batch_size:
+        raise ValueError(f"--train_batch_size {args.train_batch_size} must be divisible by the world size {world}")
+    device = torch.device("cuda", local % max(1, torch.cuda.device_count()) if dp else local)
     torch.cuda.set_device(device)
     logger.info(f"device: {device}, 16-bits training: {args.fp16} (ignored: bf16 activations, fp32 master weights)")
     train.seed_everything(args.seed)
@@ -128,17 +147,28 @@ def main(argv=None):
     total = int(len(dataset) / args.train_batch_size / args.gradient_accumulation_steps) * (args.num_train_epochs - args.start_epoch)
     warm = int(total * args.warmup_proportion)
 
+    reducer = None
+    if dp:
+        iadist.broadcast_arena(model.param_arena)
+        reducer = iadist.GradBucketReducer.for_arena(model.param_arena)
+        Fn.clear_grad_ready_hooks()
+        Fn.register_grad_ready_hook(reducer.grads_ready)
+        model.set_data_parallel()
+
     out_dir = os.path.join(args.output_dir, args.model_name)
     os.makedirs(out_dir, exist_ok=True)
-    with open(os.path.join(out_dir, "hyperparamter.txt"), "w") as w:
-        print(args, file=w)
-        print("\n", file=w)
-        print(config, file=w)
+    if rank == 0:
+        with open(os.path.join(out_dir, "hyperparamter.txt"), "w") as w:
+            print(args, file=w)
+            print("\n", file=w)
+            print(config, file=w)
 
     logger.info("***** Running training *****")
     logger.info("  Model name = %s", args.model_name)
     logger.info("  Num examples = %d", len(dataset))
     logger.info("  Batch size = %d", args.train_batch_size)
+    if dp:
+        logger.info("  Ranks = %d of %d items each (this is rank %d)", world, per_rank, rank)
     logger.info("  Num steps = %d", total)
     logger.info("  Learning rate = %.3f", args.learning_rate)
 
@@ -148,31 +178,64 @@ def main(argv=None):
         # the shuffle and the augmentation draws depend on (seed, epoch) alone: a run resumed at --start_epoch sees that epoch's batches
         epoch_seed = (args.seed * 1000003 + epoch * 1009) & 0x7FFFFFFF
         random.seed(epoch_seed)
-        loader = DataLoader(dataset, batch_size=args.train_batch_size, shuffle=True, collate_fn=collate_coca, num_workers=args.num_workers,
-                            generator=torch.Generator().manual_seed(epoch_seed))
+        if dp:
+            # every rank takes positions rank::world of the epoch's permutation: equal shares, the same global order at any world size.
+            # The augmentation draws differ per rank (item_alignment_amd/train.py): the ranks hold different items of one batch
+            idx = iadist.shard_indices(len(dataset), rank, world, epoch_seed, shuffle=True)
+            aug_seed = (args.seed * 1000003 + epoch * 1009 + rank * 7919) & 0x7FFFFFFF
+            random.seed(aug_seed)
+            loader = DataLoader(Subset(dataset, idx.tolist()), batch_size=per_rank, shuffle=False, collate_fn=collate_or_none,
+                                num_workers=args.num_workers, generator=torch.Generator().manual_seed(aug_seed))
+        else:
+            loader = DataLoader(dataset, batch_size=args.train_batch_size, shuffle=True, collate_fn=collate_coca, num_workers=args.num_workers,
+                                generator=torch.Generator().manual_seed(epoch_seed))
         opt.zero_grad()
+        micro = 0           # micro-batches run since the epoch began; in one process every step is one
         for step, batch in enumerate(loader):
+            if dp:
+                # the collate drops items whose image failed to load, so the ranks can arrive with different counts.  A rank without an
+                # item has nothing to put into the collectives of the step: every rank skips the micro-batch together
+                counts = [c[0] for c in iadist.gather_ints([0 if batch is None else len(batch[0])])]
+                if min(counts) == 0:
+                    if rank == 0:
+                        logger.info(f"[Epoch-{epoch} Step-{step}] skipped on every rank: item counts {counts}, a rank has none")
+                    continue
             input_ids, attention_mask, token_type_ids, position_ids, images = (t.to(device, non_blocking=True) for t in batch[1:])
-            Fn.set_step_seed((args.seed * 1000003 + global_step * 131 + step) & 0xFFFFFFFF)
+            # dropout streams differ per rank, as the augmentation draws do (rank 0's are the one-process stream)
+            Fn.set_step_seed((args.seed * 1000003 + global_step * 131 + step + rank * 0x9E3779B1) & 0xFFFFFFFF)
             Fn.reset_use_counts()
             loss = model(input_ids, attention_mask, token_type_ids, position_ids, images)
             if args.log_steps is not None and step % args.log_steps == 0:
-                logger.info(f"[Epoch-{epoch} Step-{step}] loss: {loss.item():.6f}")
+                shown = loss.detach().clone()
+                if dp:          # the mean of the ranks' losses is the loss of the global batch; one collective, at log steps only
+                    shown = iadist.all_reduce_scalar(shown) / world
+                if rank == 0:
+                    logger.info(f"[Epoch-{epoch} Step-{step}] loss: {shown.item():.6f}")
             if args.gradient_accumulation_steps > 1:
                 loss = loss / args.gradient_accumulation_steps
+            micro += 1
+            last = micro % args.gradient_accumulation_steps == 0
+            if reducer is not None:       # collectives only start in the backward that completes the accumulated gradient
+                reducer.armed = last
             loss.backward()
-            if (step + 1) % args.gradient_accumulation_steps == 0:
-                opt.step(train.linear_schedule_with_warmup(global_step, warm, total))
+            if last:
+                scale = reducer.finish() if reducer is not None else 1.0
+                opt.step(train.linear_schedule_with_warmup(global_step, warm, total), grad_scale=scale)
                 opt.zero_grad()          # after the optimiser step, so the micro-batches in between accumulate (note N3)
                 global_step += 1
                 if 0 < args.max_steps <= global_step:
                     break
-        logger.info(f"[Epoch-{epoch}] saving model ({global_step} optimiser steps so far)")
-        sd = {k: v.detach().to("cpu", torch.float32 if v.is_floating_point() else v.dtype).clone() for k, v in model.state_dict().items()}
-        torch.save(sd, os.path.join(out_dir, f"coca_pretrain_epoch-{epoch}.bin"))
+        if rank == 0:
+            logger.info(f"[Epoch-{epoch}] saving model ({global_step} optimiser steps so far)")
+            sd = {k: v.detach().to("cpu", torch.float32 if v.is_floating_point() else v.dtype).clone() for k, v in model.state_dict().items()}
+            torch.save(sd, os.path.join(out_dir, f"coca_pretrain_epoch-{epoch}.bin"))
+        if dp:
+            torch.distributed.barrier()          # nobody runs ahead into the next epoch's collectives while rank 0 writes
         if 0 < args.max_steps <= global_step:
             logger.info(f"Stopping after --max_steps {args.max_steps}")
             break
+    if dp:
+        torch.distributed.destroy_process_group()
     return 0
 
 

@@ -925,6 +925,35 @@ int ia_contrastive_bwd(const float* text, int ldt, const float* image, int ldi, 
                        float* dimage, int lddi, float* dlog_scale /* [1] */, int accumulate_dlog_scale, int B, int H, void* workspace,
                        size_t workspace_bytes, ia_stream_t stream);
 
+/* ---- the same loss for one rank's shard of a global batch (data-parallel CoCa pre-training).  `world` ranks share a global batch of
+ * G items; this rank holds its rows row_offset .. row_offset + B - 1 as text_l, image_l [B, ld >= H]; text_g, image_g [G, ld >= H] are
+ * the embeddings of all ranks, gathered rank-major (the caller's collective).  den = (float)G / (float)world.
+ * ia_contrastive_shard_fwd: sim_t [B, lds] (lds >= G) = s text_l image_g^T, rows row_offset + i of the global sim; sim_i [B, lds] =
+ * s image_l text_g^T, its columns row_offset + i, transposed; lse_row_l[i], lse_col_l[i] their row log-sum-exps, i.e. the global
+ * lse_row / lse_col at row_offset + i; loss[0] = 0.5 (sum_i (lse_row_l[i] - sim_t[i][row_offset + i]) / den + sum_i (lse_col_l[i] -
+ * sim_i[i][row_offset + i]) / den).  The mean of the ranks' losses is ia_contrastive_fwd's loss of the global batch.
+ * ia_contrastive_shard_bwd: lse_row_g, lse_col_g [G] are the lse_*_l of all ranks, gathered like the embeddings.  With c = dloss[0]
+ * (0.5 / den) and d = row_offset + i: Gt[i][j] = c (exp(sim_t[i][j] - lse_row_g[d]) + exp(sim_t[i][j] - lse_col_g[j]) - 2 [j == d]),
+ * Gi[i][j] = c (exp(sim_i[i][j] - lse_col_g[d]) + exp(sim_i[i][j] - lse_row_g[j]) - 2 [j == d]); dtext_l [B, lddt] = s Gt image_g,
+ * dimage_l [B, lddi] = s Gi text_g, dlog_scale[0] = (accumulate_dlog_scale ? dlog_scale[0] : 0) + sum_ij Gt[i][j] sim_t[i][j].  These
+ * are `world` times the rank's share of the global-batch gradient: averaged over the ranks (dlog_scale) or taken row by row (dtext_l,
+ * dimage_l, divided by world) they are ia_contrastive_bwd's of the global batch, so the backward needs no collective and nothing
+ * flows back through text_g / image_g.  B >= 1, 0 <= row_offset, row_offset + B <= G, world >= 1, H >= 1.  fp32 FMA, fixed summation
+ * order, no atomics: two runs are bit-identical, and at world = 1, row_offset = 0, G = B every output is bit-identical to
+ * ia_contrastive_fwd / ia_contrastive_bwd.  Pad columns are never read and never written.  IA_ERR_ARG / IA_ERR_WORKSPACE before any
+ * launch; the workspace of ia_contrastive_shard_workspace_bytes(B, G) serves both calls and carries nothing from one to the other.
+ * The additions did not bump IA_ABI_VERSION: nothing existing changed its meaning. */
+size_t ia_contrastive_shard_workspace_bytes(int B, int G);
+int ia_contrastive_shard_fwd(const float* text_l, int ldtl, const float* image_l, int ldil, const float* text_g, int ldtg,
+                             const float* image_g, int ldig, const float* log_scale /* device scalar */, float* sim_t, float* sim_i,
+                             int lds, float* lse_row_l, float* lse_col_l, float* loss /* [1] */, int B, int G, int row_offset, int world,
+                             int H, void* workspace, size_t workspace_bytes, ia_stream_t stream);
+int ia_contrastive_shard_bwd(const float* text_g, int ldtg, const float* image_g, int ldig, const float* log_scale, const float* sim_t,
+                             const float* sim_i, int lds, const float* lse_row_g, const float* lse_col_g,
+                             const float* dloss /* device scalar */, float* dtext_l, int lddt, float* dimage_l, int lddi,
+                             float* dlog_scale /* [1] */, int accumulate_dlog_scale, int B, int G, int row_offset, int world, int H,
+                             void* workspace, size_t workspace_bytes, ia_stream_t stream);
+
 /* ---- data-parallel gradient exchange (pure data parallelism, one process per GPU; reference loop being sharded:
  * finetune_multimodal.py:371-468).  RCCL over xGMI behind four calls, for hosts that bind only this header (the Python host of this
  * repository uses torch.distributed, i.e. the same RCCL).  Rank 0 obtains an id and hands its IA_COMM_ID_BYTES bytes to the other

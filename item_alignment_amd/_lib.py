@@ -224,6 +224,10 @@ SIGNATURES = {
     "ia_contrastive_workspace_bytes": (sz, [i32]),
     "ia_contrastive_fwd": (i32, [vp, i32, vp, i32, vp, vp, i32, vp, vp, vp, i32, i32, vp, sz, vp]),
     "ia_contrastive_bwd": (i32, [vp, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, vp, sz, vp]),
+    "ia_contrastive_shard_workspace_bytes": (sz, [i32, i32]),
+    "ia_contrastive_shard_fwd": (i32, [vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp]),
+    "ia_contrastive_shard_bwd": (i32, [vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32,
+                                       vp, sz, vp]),
     "ia_cast_f32_to_bf16": (i32, [vp, vp, sz, vp]),
     "ia_cast_bf16_to_f32": (i32, [vp, vp, sz, vp]),
     "ia_layer_stash_bytes": (sz, [C.POINTER(LayerCfg)]),

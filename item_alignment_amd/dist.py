@@ -247,6 +247,45 @@ def gather_rows(local, device=None):
     return np.concatenate([p[:c].cpu().numpy() for p, c in zip(parts, counts)], axis=0)
 
 
+def gather_ints(values, group=None):
+    """Every rank hands in the same number of Python ints; every rank gets [[rank 0's], [rank 1's], ...] back.  One small collective
+    (on the host over gloo, on the device over RCCL) and one host read: how the ranks learn each other's item counts."""
+    values = [int(v) for v in values]
+    if not dist.is_initialized():
+        return [values]
+    world = dist.get_world_size(group)
+    device = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend(group) == "nccl" else torch.device("cpu")
+    mine = torch.tensor(values, dtype=torch.int64, device=device)
+    parts = [torch.zeros_like(mine) for _ in range(world)]
+    dist.all_gather(parts, mine, group=group)
+    return torch.stack(parts).cpu().tolist()
+
+
+def gather_shards(local, group=None, counts=None):
+    """local [n_r, k]: this rank's rows, a device tensor (n_r may differ from rank to rank) -> (the rows of all ranks [sum n_r, k],
+    rank-major, and the row at which this rank's begin).  Counts first (skipped when the caller already has them from gather_ints), then
+    one all-gather of the rows padded to the longest shard, then the compaction.  Nothing is differentiable here.  Works over RCCL
+    and over gloo with device tensors, as GradBucketReducer does."""
+    if not dist.is_initialized():
+        return local, 0
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    if counts is None:
+        counts = [c[0] for c in gather_ints([local.shape[0]], group)]
+    counts = [int(c) for c in counts]
+    if len(counts) != world or counts[rank] != local.shape[0]:
+        raise ValueError(f"gather_shards: counts {counts} do not describe {world} ranks with {local.shape[0]} rows on rank {rank}")
+    offset, cap = sum(counts[:rank]), max(counts)
+    if cap == 0:
+        return local, 0
+    buf = local.contiguous()
+    if local.shape[0] < cap:
+        buf = torch.zeros((cap,) + tuple(local.shape[1:]), dtype=local.dtype, device=local.device)
+        buf[:local.shape[0]] = local
+    parts = [torch.empty_like(buf) for _ in range(world)]
+    dist.all_gather(parts, buf, group=group)
+    return torch.cat([p[:c] for p, c in zip(parts, counts)], dim=0), offset
+
+
 def all_reduce_grads(model, world):
     """Gradient averaging for plain torch models without a parameter arena (TextCNN, config C1)."""
     for p in model.parameters():

@@ -896,6 +896,48 @@ class ContrastiveLossFn(torch.autograd.Function):
         return dtext, dimage, None
 
 
+class ShardedContrastiveLossFn(torch.autograd.Function):
+    """ContrastiveLossFn under data parallelism: text_embeds, image_embeds fp32 [B_r, H] are this rank's shard of a global batch, and
+    every other item of the global batch is a negative.  forward all-gathers the item counts (unless `counts`, one per rank, is given),
+    the embeddings ([B, 2H], one collective) and the two log-sum-exp vectors ([B, 2]); backward issues no collective and returns
+    `world` times the rank's share of the global-batch gradient, which the reducer's average over the ranks turns into the
+    global-batch gradient (csrc/contrastive.hip, the shard entries).  The loss is scaled so that the mean of the ranks' losses is the
+    global-batch loss.  Every rank of `group` must call it, with at least one item."""
+
+    @staticmethod
+    def forward(ctx, text_embeds, image_embeds, temperature, group=None, counts=None):
+        from .. import dist as iadist
+        _need_gpu(text_embeds, "text embeddings")
+        B, H = text_embeds.shape
+        if B < 1:
+            raise ValueError("ShardedContrastiveLossFn: a rank without items cannot take part (skip the micro-batch on every rank)")
+        world = torch.distributed.get_world_size(group) if torch.distributed.is_initialized() else 1
+        both, offset = iadist.gather_shards(torch.cat([text_embeds, image_embeds], dim=1), group, counts)
+        text_g, image_g = both[:, :H].contiguous(), both[:, H:].contiguous()
+        log_scale = temperature.detach()
+        loss, sim_t, sim_i, lse_row_l, lse_col_l = ops.contrastive_shard_fwd(text_embeds.contiguous(), image_embeds.contiguous(), text_g,
+                                                                             image_g, log_scale, offset, world)
+        lse_g, _ = iadist.gather_shards(torch.stack([lse_row_l, lse_col_l], dim=1), group, counts)
+        ctx.temperature, ctx.place = temperature, (offset, world)
+        ctx.saved = (text_g, image_g, sim_t, sim_i, lse_g[:, 0].contiguous(), lse_g[:, 1].contiguous())
+        return loss[0].clone()
+
+    @staticmethod
+    def backward(ctx, dloss):
+        temperature, (offset, world) = ctx.temperature, ctx.place
+        text_g, image_g, sim_t, sim_i, lse_row_g, lse_col_g = ctx.saved
+        dloss = dloss.reshape(1).to(F32).contiguous()
+        if temperature.requires_grad:
+            dtext, dimage, _ = ops.contrastive_shard_bwd(text_g, image_g, temperature.detach(), sim_t, sim_i, lse_row_g, lse_col_g, dloss,
+                                                         offset, world, dlog_scale=temperature.grad, accumulate=True)
+            _notify([temperature])
+        else:
+            dtext, dimage, _ = ops.contrastive_shard_bwd(text_g, image_g, temperature.detach(), sim_t, sim_i, lse_row_g, lse_col_g, dloss,
+                                                         offset, world)
+        ctx.saved = None
+        return dtext, dimage, None, None, None
+
+
 # --------------------------------------------------------------------------------------------- TextCNN
 # The TextCNN two-tower keeps its parameters as ordinary nn.Parameters outside the arena (TorchAdamW steps them), so these two
 # Functions take the parameters as inputs and hand their gradients back to autograd instead of adding into `.grad` views.

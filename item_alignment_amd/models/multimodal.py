@@ -354,6 +354,21 @@ class CoCaForItemAlignment(HipModule):
         return SequenceClassifierOutput(loss=loss, probs=probs, logits=logits, src_embeds=src, tgt_embeds=tgt)
 
 
+class _NoLiveCaptionRowFn(torch.autograd.Function):
+    """The caption loss of a data-parallel rank none of whose label rows is live while another rank has some: 0, with a zero gradient
+    into the hidden states.  It reports the parameters TiedCaptionHeadFn would have touched, at the same place of the backward."""
+
+    @staticmethod
+    def forward(ctx, hidden, norm, table):
+        ctx.touched, ctx.shape = [p for p in (table, norm.gamma) if p.requires_grad], hidden.shape
+        return torch.zeros((), device=hidden.device, dtype=torch.float32)
+
+    @staticmethod
+    def backward(ctx, dloss):
+        Fn._notify(ctx.touched)
+        return torch.zeros(ctx.shape, device=dloss.device, dtype=torch.bfloat16), None, None
+
+
 class CoCaForPretraining(HipModule):
     """reference multimodal.py:843-933: the text tower and the ViT, `num_hidden_layers_multimodal` pairs of a causal
     ParallelTransformerBlock and a CrossAttention over the image tokens, and `to_logits` = gamma LayerNorm + a Linear tied to the text
@@ -395,6 +410,7 @@ class CoCaForPretraining(HipModule):
         # `to_logits.1.weight` is the word table itself, the same Parameter: the arena holds it once
         self.to_logits = nn.Sequential(LayerNorm(config.hidden_size), _TiedDecoder(text_encoder.embeddings.word_embeddings.weight))
         self.last_losses, self.caption_live_rows = None, None
+        self._dp = None          # set_data_parallel: (process group,)
         adopt(self, image_encoder, text_encoder)
 
     def encode(self, input_ids, attention_mask, token_type_ids, position_ids, images):
@@ -432,6 +448,8 @@ class CoCaForPretraining(HipModule):
         flat = labels.reshape(-1).to(torch.long)
         rows = (flat != self.pad_id).nonzero(as_tuple=False).squeeze(1)      # the one host sync of the head: M_live sizes its tensors
         self.caption_live_rows = rows.numel()
+        if self._dp is not None:
+            return self._sharded_losses(x, t_cls, i_cls, flat, rows)
         if rows.numel() == 0:
             caption = torch.full((), float("nan"), device=x.device, dtype=torch.float32)      # torch's mean over no row; no kernel runs with M = 0
         else:
@@ -439,5 +457,39 @@ class CoCaForPretraining(HipModule):
             caption = TiedCaptionHeadFn.apply(x, self, self.to_logits[0], table, rows, flat.index_select(0, rows).contiguous())
         caption = caption * self.caption_loss_weight
         contrastive = Fn.ContrastiveLossFn.apply(t_cls, i_cls, self.temperature) * self.contrastive_loss_weight
+        self.last_losses = (caption.detach(), contrastive.detach())
+        return caption + contrastive
+
+    def set_data_parallel(self, group=None):
+        """From now on a forward is one rank's part of a step that the ranks of `group` (None: the default process group) take on a
+        global batch, of which this rank's arguments are a shard: every other item of the global batch is a contrastive negative
+        (Fn.ShardedContrastiveLossFn) and the caption loss is the mean over the live label rows of all ranks.  The mean of the ranks'
+        losses is the loss of one process on the global batch, and gradients averaged over the ranks are its gradients.
+        Every rank must call forward together, each with at least one item; `last_losses` keeps the rank's two parts."""
+        if not torch.distributed.is_initialized():
+            raise RuntimeError("CoCaForPretraining.set_data_parallel: torch.distributed is not initialised")
+        self._dp = (group,)
+
+    def _sharded_losses(self, x, t_cls, i_cls, flat, rows):
+        from .. import dist as iadist
+        group = self._dp[0]
+        world = torch.distributed.get_world_size(group)
+        # one small collective: the item counts the contrastive gathers need and the live label rows the caption mean divides by
+        counts = iadist.gather_ints([t_cls.shape[0], rows.numel()], group)
+        n_live = sum(c[1] for c in counts)
+        table = self.to_logits[1].weight
+        if n_live == 0:
+            caption = torch.full((), float("nan"), device=x.device, dtype=torch.float32)      # as one process: torch's mean over no row
+        elif rows.numel() == 0:
+            # no live row here, some elsewhere: this rank adds 0 to the caption loss and runs no kernel with M = 0, but its backward still
+            # walks the multimodal layers (with a zero gradient), so that every rank starts the gradient buckets in the same order
+            caption = _NoLiveCaptionRowFn.apply(x, self.to_logits[0], table)
+        else:
+            mean = TiedCaptionHeadFn.apply(x, self, self.to_logits[0], table, rows, flat.index_select(0, rows).contiguous())
+            # the rank's mean over its n_r live rows -> its share of the global mean, times world (the ranks' losses are averaged)
+            caption = mean * (rows.numel() * world / n_live)
+        caption = caption * self.caption_loss_weight
+        contrastive = Fn.ShardedContrastiveLossFn.apply(t_cls, i_cls, self.temperature, group, [c[0] for c in counts])
+        contrastive = contrastive * self.contrastive_loss_weight
         self.last_losses = (caption.detach(), contrastive.detach())
         return caption + contrastive

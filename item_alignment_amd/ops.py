@@ -481,3 +481,60 @@ def contrastive_bwd(text, image, log_scale, sim, lse_row, lse_col, dloss, *, dlo
                                  lse_col.data_ptr(), dloss.data_ptr(), dtext.data_ptr(), H, dimage.data_ptr(), H, dlog_scale.data_ptr(),
                                  int(accumulate), B, H, ws.data_ptr(), ws_bytes, stream_ptr()), "ia_contrastive_bwd")
     return dtext, dimage, dlog_scale
+
+
+def contrastive_shard_fwd(text_l, image_l, text_g, image_g, log_scale, row_offset, world):
+    """One rank's part of the contrastive loss of a global batch that `world` ranks share: text_l, image_l [B, H] fp32 are its rows
+    row_offset .. row_offset + B - 1 of the gathered text_g, image_g [G, H] -> (loss [1], sim_t [B, G], sim_i [B, G], lse_row_l [B],
+    lse_col_l [B]), all fp32 (ia_contrastive_shard_fwd).  The mean of the ranks' losses is contrastive_fwd's of the global batch."""
+    lib = _lib.load()
+    for t, name in ((text_l, "text_l"), (image_l, "image_l"), (text_g, "text_g"), (image_g, "image_g"), (log_scale, "log_scale")):
+        _need(t, F32, name)
+    B, H = text_l.shape
+    G = text_g.shape[0]
+    if tuple(image_l.shape) != (B, H) or tuple(text_g.shape) != (G, H) or tuple(image_g.shape) != (G, H) or log_scale.numel() != 1:
+        raise ValueError(f"contrastive_shard_fwd: local {tuple(text_l.shape)} / {tuple(image_l.shape)} and gathered {tuple(text_g.shape)} / "
+                         f"{tuple(image_g.shape)} embeddings do not belong together, log_scale has one element")
+    dev = text_l.device
+    sim_t = torch.empty((B, G), device=dev, dtype=F32)
+    sim_i = torch.empty((B, G), device=dev, dtype=F32)
+    lse_row_l = torch.empty(B, device=dev, dtype=F32)
+    lse_col_l = torch.empty(B, device=dev, dtype=F32)
+    loss = torch.empty(1, device=dev, dtype=F32)
+    ws_bytes = lib.ia_contrastive_shard_workspace_bytes(B, G)
+    ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+    check(lib.ia_contrastive_shard_fwd(text_l.data_ptr(), H, image_l.data_ptr(), H, text_g.data_ptr(), H, image_g.data_ptr(), H,
+                                       log_scale.data_ptr(), sim_t.data_ptr(), sim_i.data_ptr(), G, lse_row_l.data_ptr(), lse_col_l.data_ptr(),
+                                       loss.data_ptr(), B, G, int(row_offset), int(world), H, ws.data_ptr(), ws_bytes, stream_ptr()),
+          "ia_contrastive_shard_fwd")
+    return loss, sim_t, sim_i, lse_row_l, lse_col_l
+
+
+def contrastive_shard_bwd(text_g, image_g, log_scale, sim_t, sim_i, lse_row_g, lse_col_g, dloss, row_offset, world, *, dlog_scale=None,
+                          accumulate=False):
+    """-> (dtext_l [B, H], dimage_l [B, H], dlog_scale [1]), fp32 (ia_contrastive_shard_bwd): `world` times the rank's share of the
+    global-batch gradient.  sim_t, sim_i: what contrastive_shard_fwd returned; lse_row_g, lse_col_g [G]: the lse_row_l / lse_col_l of all
+    ranks, gathered like the embeddings; dloss: fp32 device scalar.  accumulate: add into the given dlog_scale instead of writing it."""
+    lib = _lib.load()
+    G, H = text_g.shape
+    for t, name in ((text_g, "text_g"), (image_g, "image_g"), (log_scale, "log_scale"), (sim_t, "sim_t"), (sim_i, "sim_i"),
+                    (lse_row_g, "lse_row_g"), (lse_col_g, "lse_col_g"), (dloss, "dloss"), (dlog_scale, "dlog_scale")):
+        _need(t, F32, name)
+    B = sim_t.shape[0]
+    if (tuple(image_g.shape) != (G, H) or tuple(sim_t.shape) != (B, G) or tuple(sim_i.shape) != (B, G) or lse_row_g.numel() != G
+            or lse_col_g.numel() != G or dloss.numel() != 1):
+        raise ValueError("contrastive_shard_bwd: shapes do not belong to one contrastive_shard_fwd call")
+    if accumulate and dlog_scale is None:
+        raise ValueError("contrastive_shard_bwd: accumulate needs dlog_scale")
+    dev = text_g.device
+    if dlog_scale is None:
+        dlog_scale = torch.empty(1, device=dev, dtype=F32)
+    dtext = torch.empty((B, H), device=dev, dtype=F32)
+    dimage = torch.empty((B, H), device=dev, dtype=F32)
+    ws_bytes = lib.ia_contrastive_shard_workspace_bytes(B, G)
+    ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+    check(lib.ia_contrastive_shard_bwd(text_g.data_ptr(), H, image_g.data_ptr(), H, log_scale.data_ptr(), sim_t.data_ptr(), sim_i.data_ptr(), G,
+                                       lse_row_g.data_ptr(), lse_col_g.data_ptr(), dloss.data_ptr(), dtext.data_ptr(), H, dimage.data_ptr(), H,
+                                       dlog_scale.data_ptr(), int(accumulate), B, G, int(row_offset), int(world), H, ws.data_ptr(), ws_bytes,
+                                       stream_ptr()), "ia_contrastive_shard_bwd")
+    return dtext, dimage, dlog_scale
