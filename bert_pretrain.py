@@ -6,6 +6,12 @@ The reference hard-codes its settings in main(); each is a flag here whose defau
 schedule's length counts RECORDS, not examples (records // batch_size * num_epochs), and the next-sentence negatives are never trained
 on (item_alignment_amd/data/bert_pretrain.py).  --model_name_or_path must be a local directory with vocab.txt and config.json (and
 pytorch_model.bin to start from): nothing is ever downloaded.  INTEGRATION.md "BERT pre-training" has the details.
+
+One process drives one GPU.  Under a launcher (python -m torch.distributed.run --nproc-per-node N bert_pretrain.py ...) the N ranks
+train data-parallel: every rank runs the whole host pipeline from the same seed and so forms the one-process batches, takes its
+contiguous slice of each, and the ranks together take the optimiser step of one process on the whole batch.  --batch_size stays the
+total.  A batch with fewer rows than ranks is skipped by all ranks (the one departure from the one-process trajectory).  Rank 0 writes
+the files.  Without WORLD_SIZE the script is the one-process script.
 """
 import argparse
 import logging
@@ -30,7 +36,7 @@ def get_parser():
     a("--train_file", default="pretrain_train.jsonl", type=str)
     a("--valid_file", default="pretrain_valid.jsonl", type=str)
     a("--max_seq_len", default=510, type=int, help="tokens between [CLS] and [SEP]; the model sees max_seq_len + 2 positions")
-    a("--batch_size", default=32, type=int)
+    a("--batch_size", default=32, type=int, help="rows of one optimiser step; under a launcher the total over all ranks")
     a("--num_epochs", default=20, type=int)
     a("--model_name_or_path", required=True, type=str,
       help="LOCAL directory with vocab.txt, config.json and (optionally) pytorch_model.bin, e.g. an unpacked bert-base-chinese")
@@ -53,7 +59,13 @@ def count_records(data_dir, file):
 
 
 def main(argv=None):
-    args = get_parser().parse_args(argv)
+    parser = get_parser()
+    args = parser.parse_args(argv)
+    from item_alignment_amd import dist as iadist
+    rank, world, _ = iadist.env_ranks()
+    if args.batch_size % world:
+        parser.error(f"--batch_size {args.batch_size} must be divisible by the world size {world}")
+    dp = world > 1
     from item_alignment_amd.cli_common import check_model_dir, linear_schedule, load_config, load_vocab_tokenizer
     check_model_dir(args.model_name_or_path)
     import torch
@@ -61,22 +73,29 @@ def main(argv=None):
     from item_alignment_amd.data import bert_pretrain as D
     from item_alignment_amd.models import functional as Fn
 
-    os.makedirs(args.output_dir, exist_ok=True)
-    LOGGER.setLevel(logging.INFO)
     LOGGER.propagate = False              # the package configures the root logger: every line once, through the two handlers below
     fmt = logging.Formatter("%(asctime)s - %(name)s - %(levelname)s - %(message)s")
-    for h in (logging.FileHandler(os.path.join(args.output_dir, "pretrain-bert.log")), logging.StreamHandler(sys.stdout)):
+    writer = None
+    if rank == 0:                         # the log file, the scalars and the model directory are rank 0's alone
+        os.makedirs(args.output_dir, exist_ok=True)
+        LOGGER.setLevel(logging.INFO)
+        handlers = (logging.FileHandler(os.path.join(args.output_dir, "pretrain-bert.log")), logging.StreamHandler(sys.stdout))
+        try:                              # scalars for TensorBoard only where tensorboardX is installed; never required
+            from tensorboardX import SummaryWriter
+            writer = SummaryWriter(logdir=os.path.join(args.output_dir, "tf-logs"))
+        except ImportError:
+            pass
+    else:                                 # the other ranks attach no file handler and keep to warnings
+        LOGGER.setLevel(logging.WARNING)
+        handlers = (logging.StreamHandler(sys.stdout),)
+    for h in handlers:
         h.setFormatter(fmt)
         LOGGER.addHandler(h)
-    try:                                  # scalars for TensorBoard only where tensorboardX is installed; never required
-        from tensorboardX import SummaryWriter
-        writer = SummaryWriter(logdir=os.path.join(args.output_dir, "tf-logs"))
-    except ImportError:
-        writer = None
 
     if not torch.cuda.is_available():
         raise SystemExit("bert_pretrain.py runs on the MI355X HIP engine only (no CPU path); no GPU is visible")
-    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
+    rank, world, local = iadist.init_from_env("cuda")
+    device = torch.device("cuda", local % max(1, torch.cuda.device_count()) if dp else local)
     torch.cuda.set_device(device)
 
     vocab_file = os.path.join(args.model_name_or_path, "vocab.txt")
@@ -90,7 +109,14 @@ def main(argv=None):
     model = M.BertForPreTraining.from_pretrained(args.model_name_or_path, config=config).to(device)
     LOGGER.info("The BERT model has {:} different named parameters.".format(len(list(model.named_parameters()))))
     arena = model.param_arena
-    rng = D.Rng(args.seed)
+    reducer = None
+    if dp:
+        iadist.broadcast_arena(arena)
+        reducer = iadist.GradBucketReducer.for_arena(arena)
+        Fn.clear_grad_ready_hooks()
+        Fn.register_grad_ready_hook(reducer.grads_ready)
+        LOGGER.info(f"Data parallel: {world} ranks, --batch_size {args.batch_size} is the total ({args.batch_size // world} rows a rank)")
+    rng = D.Rng(args.seed)            # the same seed on every rank: the same records, masking draws and shuffles, the same global batches
 
     total_steps = max(1, count_records(args.data_dir, args.train_file) // args.batch_size * args.num_epochs)
     eval_examples = []
@@ -98,65 +124,96 @@ def main(argv=None):
         eval_examples = D.build_examples(records, tokenizer, args.max_seq_len, rng)
     LOGGER.info(f"Loading Eval data successfully: {len(eval_examples)} examples")
 
-    def run(batch):
+    def run(batch, shares=None):
         input_ids, attention_mask, _token_type_ids, label_ids, next_labels = (b.to(device) for b in batch)
         # token_type_ids=None, as the reference calls its model: the segment types of the features are not fed in
         return model(input_ids, token_type_ids=None, attention_mask=attention_mask, masked_lm_labels=label_ids,
-                     next_sentence_label=next_labels)[0]
+                     next_sentence_label=next_labels, loss_shares=shares)[0]
 
     def eval_model():
+        """the mean of the per-batch losses (the reference's number).  Data parallel: rank r takes the whole batches i % world == r,
+        the sum and the count are all-reduced, every rank holds the same mean"""
         model.eval()
         total, n = 0.0, 0
         with torch.no_grad():
-            for batch in D.batches(eval_examples, args.batch_size):
+            for i, batch in enumerate(D.batches(eval_examples, args.batch_size)):
+                if i % world != rank:
+                    continue
                 total += run(batch).item()
                 n += 1
         model.train()
+        if dp:
+            both = iadist.all_reduce_scalar(torch.tensor([total, n], dtype=torch.float64, device=device)).tolist()
+            total, n = both[0], int(both[1])
         return total / max(1, n)
 
     def save():
-        model.save_pretrained(args.output_dir)
-        shutil.copyfile(vocab_file, os.path.join(args.output_dir, "vocab.txt"))
+        if rank == 0:
+            model.save_pretrained(args.output_dir)
+            shutil.copyfile(vocab_file, os.path.join(args.output_dir, "vocab.txt"))
+        if dp:
+            torch.distributed.barrier()          # nobody runs ahead into the next step's collectives while rank 0 writes
 
-    global_steps, best_eval_loss, best_steps = 0, float("inf"), 0
-    model.train()
-    for epoch_idx in range(args.num_epochs):
-        for records in D.read_pretrained_data(args.data_dir, args.train_file, rng):
-            examples = D.build_examples(records, tokenizer, args.max_seq_len, rng)
-            for batch in D.batches(examples, args.batch_size, rng):
-                Fn.set_step_seed((args.seed * 1000003 + global_steps) & 0xFFFFFFFF)
-                Fn.reset_use_counts()
-                arena.zero_grad()
-                loss = run(batch)
-                loss.backward()
-                global_steps += 1
-                # clip_grad_norm_(model.parameters(), max_grad_norm) as a factor on the gradients inside the fused optimiser step
-                norm = arena.grad.norm().item()
-                scale = min(1.0, args.max_grad_norm / (norm + 1e-6))
-                lr = args.learning_rate * linear_schedule(global_steps - 1, total_steps, args.warmup_steps)
-                arena.adamw_step(lr, betas=(0.9, 0.999), eps=args.adam_epsilon, weight_decay=0.0, grad_scale=scale)
-                if global_steps % args.log_steps == 0:
-                    value = loss.item()
-                    if writer:
-                        writer.add_scalar("Train/loss", value, global_steps)
-                    LOGGER.info("Epoch {:>3,}, Steps {:>5,}, Total {:>5,}, Train/Loss {:.6f}".format(epoch_idx + 1, global_steps, total_steps, value))
-                if global_steps % args.eval_steps == 0:
-                    eval_loss = eval_model()
-                    if writer:
-                        writer.add_scalar("Eval/loss", eval_loss, global_steps)
-                    improve = "  No optimization! ..."
-                    if best_eval_loss > eval_loss:
-                        best_eval_loss, best_steps, improve = eval_loss, global_steps, " ^_^"
-                        save()
-                    elif global_steps - best_steps > args.patience_steps:
-                        LOGGER.info(f"Eval loss has not been optimized for {args.patience_steps} steps, Early stopping ...")
-                        LOGGER.info(f"Pretraining successfully, num_epochs:{epoch_idx + 1}, global_steps:{global_steps} ^_^")
-                        return 0
-                    LOGGER.info("* Epoch {:>3,}, Steps {:>5,}, Total {:>5,}, Eval/Loss {:.6f}".format(epoch_idx + 1, global_steps, total_steps,
-                                                                                                   eval_loss) + improve)
-                if 0 < args.max_steps <= global_steps:
-                    LOGGER.info(f"Stopping after --max_steps {args.max_steps}")
-                    return 0
+    def train():
+        """the epochs; returns at early stopping and at --max_steps, on every rank at the same step"""
+        global_steps, best_eval_loss, best_steps = 0, float("inf"), 0
+        model.train()
+        for epoch_idx in range(args.num_epochs):
+            for records in D.read_pretrained_data(args.data_dir, args.train_file, rng):
+                examples = D.build_examples(records, tokenizer, args.max_seq_len, rng)
+                for batch in D.batches(examples, args.batch_size, rng):
+                    shares, inv_world = None, 1.0
+                    if dp:
+                        rows = batch[0].shape[0]
+                        if rows < world:      # a rank would hold no row: every rank skips the batch, global_steps does not move
+                            LOGGER.info(f"Epoch {epoch_idx + 1}: a batch of {rows} rows skipped on every rank, fewer rows than the {world} ranks")
+                            continue
+                        lo, hi = iadist.deal_rows(rows, rank, world)
+                        batch = tuple(t[lo:hi] for t in batch)
+                        # the masked-LM term is a mean over labelled rows, the next-sentence term a mean over rows: one count exchange
+                        shares, _ = iadist.loss_shares([int((batch[3] != -1).sum()), hi - lo])
+                    # dropout streams differ per rank (rank 0's is the one-process stream)
+                    Fn.set_step_seed((args.seed * 1000003 + global_steps + rank * 0x9E3779B1) & 0xFFFFFFFF)
+                    Fn.reset_use_counts()
+                    arena.zero_grad()
+                    loss = run(batch, shares)
+                    loss.backward()
+                    if reducer is not None:
+                        inv_world = reducer.finish()          # the arena now holds the SUM over ranks; 1 / world makes it the average
+                    global_steps += 1
+                    # clip_grad_norm_(model.parameters(), max_grad_norm) as a factor on the gradients inside the fused optimiser step;
+                    # the norm is the averaged gradient's, the same number on every rank
+                    norm = arena.grad.norm().item() * inv_world
+                    scale = min(1.0, args.max_grad_norm / (norm + 1e-6)) * inv_world
+                    lr = args.learning_rate * linear_schedule(global_steps - 1, total_steps, args.warmup_steps)
+                    arena.adamw_step(lr, betas=(0.9, 0.999), eps=args.adam_epsilon, weight_decay=0.0, grad_scale=scale)
+                    if global_steps % args.log_steps == 0:
+                        # the weighted rank losses average to the loss of the global batch: one collective, at log steps only
+                        value = (iadist.all_reduce_scalar(loss.detach().clone()).item() / world) if dp else loss.item()
+                        if writer:
+                            writer.add_scalar("Train/loss", value, global_steps)
+                        LOGGER.info("Epoch {:>3,}, Steps {:>5,}, Total {:>5,}, Train/Loss {:.6f}".format(epoch_idx + 1, global_steps, total_steps, value))
+                    if global_steps % args.eval_steps == 0:
+                        eval_loss = eval_model()
+                        if writer:
+                            writer.add_scalar("Eval/loss", eval_loss, global_steps)
+                        improve = "  No optimization! ..."
+                        if best_eval_loss > eval_loss:
+                            best_eval_loss, best_steps, improve = eval_loss, global_steps, " ^_^"
+                            save()
+                        elif global_steps - best_steps > args.patience_steps:
+                            LOGGER.info(f"Eval loss has not been optimized for {args.patience_steps} steps, Early stopping ...")
+                            LOGGER.info(f"Pretraining successfully, num_epochs:{epoch_idx + 1}, global_steps:{global_steps} ^_^")
+                            return
+                        LOGGER.info("* Epoch {:>3,}, Steps {:>5,}, Total {:>5,}, Eval/Loss {:.6f}".format(epoch_idx + 1, global_steps, total_steps,
+                                                                                                       eval_loss) + improve)
+                    if 0 < args.max_steps <= global_steps:
+                        LOGGER.info(f"Stopping after --max_steps {args.max_steps}")
+                        return
+
+    train()
+    if dp:
+        torch.distributed.destroy_process_group()
     return 0
 
 

@@ -9,6 +9,13 @@ Different: bert_align_results.csv goes to --output_dir and 
 classify F1 is 0.0 where the reference divides by zero; --model_name_or_path must be a local directory, nothing is ever downloaded;
 the adversarial modes are not built; a resumed run goes on where the interrupted one stopped (same epoch, same batch) instead of
 starting its epochs again.
+
+One process drives one GPU.  Under a launcher (python -m torch.distributed.run --nproc-per-node N finetune_bert.py ...) the N ranks
+train data-parallel: every rank builds the same loaders from the same seed, takes its contiguous slice of each global batch, and the
+ranks together take the optimiser step of one process on the whole batch.  --batch_size stays the total.  A batch with fewer pairs
+than ranks is skipped by all ranks (the one departure from the one-process trajectory).  Evaluation batches are dealt round-robin
+and gathered, so every rank holds the one-process metrics; rank 0 writes the files.  Without WORLD_SIZE the script is the one-process
+script.
 """
 import argparse
 import csv
@@ -53,7 +60,7 @@ def get_parser():
       help="LOCAL directory with vocab.txt, config.json and (optionally) pytorch_model.bin: an unpacked bert-base-chinese, or the "
            "output directory of bert_pretrain.py")
     a("--restore_path", default="", type=str, help="a state_dict file loaded over the starting weights (keys may carry a module. prefix)")
-    a("--batch_size", default=16, type=int)
+    a("--batch_size", default=16, type=int, help="pairs of one optimiser step; under a launcher the total over all ranks")
     a("--num_epochs", default=20, type=int)
     a("--patience_steps", default=20000, type=int)
     a("--learning_rate", default=2e-5, type=float)
@@ -115,24 +122,41 @@ def forward(model, batch, device, with_labels=True):
     return model(next_sentence_label=d[15] if with_labels else None, **kw), d[15]
 
 
-def evaluate(model, loader, device):
+def gather_in_batch_order(rows, width, device):
+    """rows: this rank's records, each a tuple of `width` numbers whose first is the index of the evaluation batch it came from ->
+    the records of all ranks, in the order one process produces them.  gather_shards concatenates rank-major and keeps every batch's
+    records together and in order; a stable sort by the batch index then restores the file order.  fp64 carries fp32 logits, the
+    labels and the indices exactly."""
+    import torch
+    from item_alignment_amd import dist as iadist
+    local = torch.tensor(rows, dtype=torch.float64, device=device).reshape(-1, width)
+    both = iadist.gather_shards(local)[0].cpu()
+    return both[torch.argsort(both[:, 0], stable=True)].tolist()
+
+
+def evaluate(model, loader, device, rank=0, world=1):
     """-> dict of the best-F1 search over logit[1] - logit[0], the argmax confusion figures and the mean loss (reference
-    finetune_bert.py:129-181)"""
+    finetune_bert.py:129-181).  world > 1: rank r runs the batches i % world == r; the logits, labels and per-batch losses are
+    gathered in the original order and every rank computes the metrics of one process from them."""
     import torch
     from item_alignment_amd.data import bert_align as D
     model.eval()
-    scores, truth, total_loss, n = [], [], 0.0, 0
-    tp = fp = tn = fn = 0
+    rows, losses = [], []          # (batch, logit 0, logit 1, label) per pair; (batch, loss) per batch
     with torch.no_grad():
-        for batch in loader:
+        for i, batch in enumerate(loader):
+            if i % world != rank:
+                continue
             out, labels = forward(model, batch, device)
-            total_loss += out[-1].item()
-            n += 1
-            logits, labels = out[1].float().cpu().tolist(), labels.cpu().tolist()
-            a, b, c, d = D.confusion(logits, labels)
-            tp, fp, tn, fn = tp + a, fp + b, tn + c, fn + d
-            scores += [row[1] - row[0] for row in logits]
-            truth += labels
+            losses.append((i, out[-1].item()))
+            rows += [(i, row[0], row[1], y) for row, y in zip(out[1].float().cpu().tolist(), labels.cpu().tolist())]
+    if world > 1:
+        rows, losses = gather_in_batch_order(rows, 4, device), gather_in_batch_order(losses, 2, device)
+    total_loss, n = 0.0, len(losses)
+    for _, value in losses:
+        total_loss += value
+    logits, truth = [[r[1], r[2]] for r in rows], [int(r[3]) for r in rows]
+    tp, fp, tn, fn = D.confusion(logits, truth) if rows else (0, 0, 0, 0)
+    scores = [row[1] - row[0] for row in logits]
     acc, f1, pre, recall, threshold = D.find_best_f1_and_threshold(scores, truth, True)
     cls_recall = tp / (tp + fn) if tp + fn else 0.0
     cls_pre = tp / (tp + fp) if tp + fp else 0.0
@@ -173,8 +197,20 @@ def restore_optimizer(arena, state):
     arena.step_count = int(state["step"])
 
 
+def batch_size_error(args):
+    """the message of the usage error where the launcher's world size does not divide --batch_size, or None"""
+    from item_alignment_amd import dist as iadist
+    world = iadist.env_ranks()[1]
+    return f"--batch_size {args.batch_size} must be divisible by the world size {world}" if args.batch_size % world else None
+
+
 def run(args):
     """the training run; returns what a caller may want to look at afterwards (the model, the step count)"""
+    from item_alignment_amd import dist as iadist
+    if batch_size_error(args):
+        raise SystemExit(batch_size_error(args))
+    rank, world, _ = iadist.env_ranks()
+    dp = world > 1
     from item_alignment_amd.cli_common import check_model_dir, linear_schedule, load_config, load_vocab_tokenizer
     check_model_dir(args.model_name_or_path)
     import torch
@@ -186,26 +222,36 @@ def run(args):
     check_lengths(args, config)
     if not torch.cuda.is_available():
         raise SystemExit("finetune_bert.py runs on the MI355X HIP engine only (no CPU path); no GPU is visible")
-    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
+    rank, world, local = iadist.init_from_env("cuda")
+    device = torch.device("cuda", local % max(1, torch.cuda.device_count()) if dp else local)
     torch.cuda.set_device(device)
 
     loss_dir, f1_dir = os.path.join(args.output_dir, "LossModel"), os.path.join(args.output_dir, "F1Model")
     log_dir = os.path.join(args.output_dir, "tf-logs")
-    for d in (loss_dir, f1_dir, log_dir):
-        os.makedirs(d, exist_ok=True)
     checkpoint_path = os.path.join(args.output_dir, "checkpoint")
-    LOGGER.setLevel(logging.INFO)
     LOGGER.propagate = False              # the package configures the root logger: every line once, through the two handlers below
     fmt = logging.Formatter("%(asctime)s - %(name)s - %(levelname)s - %(message)s")
-    handlers = [logging.FileHandler(os.path.join(log_dir, f"train-{datetime.date.today()}.log")), logging.StreamHandler(sys.stdout)]
+    writer = None
+    if rank == 0:                         # the directories, the log file, the scalars, the CSV and the models are rank 0's alone
+        for d in (loss_dir, f1_dir, log_dir):
+            os.makedirs(d, exist_ok=True)
+        LOGGER.setLevel(logging.INFO)
+        handlers = [logging.FileHandler(os.path.join(log_dir, f"train-{datetime.date.today()}.log")), logging.StreamHandler(sys.stdout)]
+        try:                              # scalars for TensorBoard only where tensorboardX is installed; never required
+            from tensorboardX import SummaryWriter
+            writer = SummaryWriter(logdir=log_dir)
+        except ImportError:
+            pass
+    else:                                 # the other ranks attach no file handler and keep to warnings
+        LOGGER.setLevel(logging.WARNING)
+        handlers = [logging.StreamHandler(sys.stdout)]
     for h in handlers:
         h.setFormatter(fmt)
         LOGGER.addHandler(h)
-    try:                                  # scalars for TensorBoard only where tensorboardX is installed; never required
-        from tensorboardX import SummaryWriter
-        writer = SummaryWriter(logdir=log_dir)
-    except ImportError:
-        writer = None
+
+    def after_save():
+        if dp:
+            torch.distributed.barrier()          # nobody runs ahead into the next collectives while rank 0 writes
 
     def scalars(prefix, **values):
         if writer:
@@ -243,6 +289,13 @@ def run(args):
             restore_optimizer(arena, optimizer_state)
             LOGGER.info(f"Load checkpoint from {checkpoint_path} successfully: resumed at global_steps {global_steps}, train continue ...")
         LOGGER.info("The BERT model has {:} different named parameters.".format(len(list(model.named_parameters()))))
+        reducer = None
+        if dp:          # after the weights and the checkpoint: rank 0's replica everywhere (every rank has also read the moments itself)
+            iadist.broadcast_arena(arena)
+            reducer = iadist.GradBucketReducer.for_arena(arena)
+            Fn.clear_grad_ready_hooks()
+            Fn.register_grad_ready_hook(reducer.grads_ready)
+            LOGGER.info(f"Data parallel: {world} ranks, --batch_size {args.batch_size} is the total ({args.batch_size // world} pairs a rank)")
 
         per_epoch = len(train_loader)
         total_steps = max(1, per_epoch * args.num_epochs)
@@ -251,14 +304,20 @@ def run(args):
         t0 = time.time()
 
         def save_model(directory):
-            model.save_pretrained(directory)
-            shutil.copyfile(vocab_file, os.path.join(directory, "vocab.txt"))
-            LOGGER.info(f"* Save model to {directory}")
+            if rank == 0:
+                model.save_pretrained(directory)
+                shutil.copyfile(vocab_file, os.path.join(directory, "vocab.txt"))
+                LOGGER.info(f"* Save model to {directory}")
+            after_save()
 
         def done():
             return SimpleNamespace(model=model, global_steps=global_steps, best_f1=best_f1, best_eval_loss=best_eval_loss)
 
-        first_epoch, skip = divmod(global_steps, max(1, per_epoch))
+        # global_steps counts global batches.  Several ranks skip an epoch's last batch where it has fewer pairs than ranks: that epoch
+        # then has one step less than batches (the skipped batch is its last, so batch index and step count still agree inside it)
+        tail = len(train_loader.dataset) % args.batch_size
+        steps_per_epoch = per_epoch - (1 if dp and 0 < tail < world else 0)
+        first_epoch, skip = divmod(global_steps, max(1, steps_per_epoch))
         if 0 < args.max_steps <= global_steps:
             LOGGER.info(f"--max_steps {args.max_steps} was reached before this run")
             return done()
@@ -269,26 +328,42 @@ def run(args):
             for step, batch in enumerate(train_loader):
                 if epoch == first_epoch and step < skip:          # the batches the interrupted run had already trained on
                     continue
-                Fn.set_step_seed((args.seed * 1000003 + global_steps) & 0xFFFFFFFF)
+                inv_world = 1.0
+                if dp:
+                    pairs = batch[0].shape[0]
+                    if pairs < world:     # a rank would hold no pair: every rank skips the batch, global_steps does not move
+                        LOGGER.info(f"Epoch {epoch + 1}: a batch of {pairs} pairs skipped on every rank, fewer pairs than the {world} ranks")
+                        continue
+                    lo, hi = iadist.deal_rows(pairs, rank, world)
+                    batch = [t[lo:hi] for t in batch]
+                # dropout streams differ per rank (rank 0's is the one-process stream)
+                Fn.set_step_seed((args.seed * 1000003 + global_steps + rank * 0x9E3779B1) & 0xFFFFFFFF)
                 Fn.reset_use_counts()
                 arena.zero_grad()
                 loss = forward(model, batch, device)[0][-1]
+                if dp:                    # the mean over this rank's pairs, weighted by its share of the global batch's pairs
+                    loss = loss * iadist.loss_shares([hi - lo])[0][0]
                 loss.backward()
+                if reducer is not None:
+                    inv_world = reducer.finish()          # the arena now holds the SUM over ranks; 1 / world makes it the average
                 global_steps += 1
-                # clip_grad_norm_(model.parameters(), max_grad_norm) as a factor on the gradients inside the fused optimiser step
-                norm = arena.grad.norm().item()
-                scale = min(1.0, args.max_grad_norm / (norm + 1e-6))
+                # clip_grad_norm_(model.parameters(), max_grad_norm) as a factor on the gradients inside the fused optimiser step;
+                # the norm is the averaged gradient's, the same number on every rank
+                norm = arena.grad.norm().item() * inv_world
+                scale = min(1.0, args.max_grad_norm / (norm + 1e-6)) * inv_world
                 lr = args.learning_rate * linear_schedule(global_steps - 1, total_steps, args.warmup_steps)
                 arena.adamw_step(lr, betas=(0.9, 0.999), eps=args.adam_epsilon, weight_decay=0.0, grad_scale=scale)
                 if global_steps % args.log_steps == 0:
-                    value = loss.item()
+                    # the weighted rank losses average to the loss of the global batch: one collective, at log steps only
+                    value = (iadist.all_reduce_scalar(loss.detach().clone()).item() / world) if dp else loss.item()
                     scalars("Train", Loss=value)
                     LOGGER.info("Epoch {:>3,} - Steps {:>5,} - Total {:>5,} - Train/Loss {:.6f} - Total cost: {:}".format(
                         epoch + 1, global_steps, per_epoch, value, datetime.timedelta(seconds=int(time.time() - t0))))
                 if global_steps % args.eval_steps == 0:
                     LOGGER.info("======== Running Eval ========")
-                    r = evaluate(model, eval_loader, device)
-                    write_csv_row(args.output_dir, r, epoch + 1, global_steps)
+                    r = evaluate(model, eval_loader, device, rank, world)
+                    if rank == 0:
+                        write_csv_row(args.output_dir, r, epoch + 1, global_steps)
                     scalars("Eval", Acc=r.acc, Precision=r.pre, Recall=r.recall, F1=r.f1, cls_Acc=r.cls_acc, cls_Precision=r.cls_pre,
                             cls_Recall=r.cls_recall, cls_F1=r.cls_f1, Loss=r.loss)
                     LOGGER.info("* Epoch: {:>3,}, Steps {:>5,}, Accuracy: {:.4f}, Precision: {:.4f}, Recall: {:.4f}, F1: {:.4f}, Eval/Loss: {:.6f}"
@@ -307,8 +382,10 @@ def run(args):
                         improved.append("F1")
                         LOGGER.info(f"* Current Best F1 {best_f1} epoch:{epoch + 1}, steps:{global_steps} Eval/Loss:{r.loss}")
                     if global_steps % args.check_steps == 0:
-                        save_checkpoint(model, arena, global_steps, total_steps, args, checkpoint_path)
-                        LOGGER.info(f"* Save checkpoint to {checkpoint_path} .")
+                        if rank == 0:
+                            save_checkpoint(model, arena, global_steps, total_steps, args, checkpoint_path)
+                            LOGGER.info(f"* Save checkpoint to {checkpoint_path} .")
+                        after_save()
                     if global_steps - best_loss_steps >= args.patience_steps and global_steps - best_f1_steps >= args.patience_steps:
                         LOGGER.info(f"There is no optimizing model after {max(global_steps - best_loss_steps, global_steps - best_f1_steps)} "
                                     "steps, Early stopping ....")
@@ -327,10 +404,16 @@ def run(args):
             h.close()
         if writer:
             writer.close()
+        if dp and torch.distributed.is_initialized():
+            torch.distributed.destroy_process_group()
 
 
 def main(argv=None):
-    run(get_parser().parse_args(argv))
+    parser = get_parser()
+    args = parser.parse_args(argv)
+    if batch_size_error(args):
+        parser.error(batch_size_error(args))
+    run(args)
     return 0
 
 

@@ -30,11 +30,15 @@ BF16_BUCKETS = os.environ.get("IA_DP_BF16") == "1"
 BACKEND = os.environ.get("IA_DP_BACKEND")
 
 
+def env_ranks():
+    """(rank, world, local_rank) as the launcher's environment gives them, without touching torch.distributed or a device: what a
+    script needs to refuse its arguments before anything is initialised"""
+    return int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("LOCAL_RANK", "0"))
+
+
 def init_from_env(device_type="cuda"):
     """RANK / WORLD_SIZE / LOCAL_RANK / MASTER_* from the launcher (torch.distributed.run).  Returns (rank, world, local_rank)."""
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    local = int(os.environ.get("LOCAL_RANK", "0"))
+    rank, world, local = env_ranks()
     # IA_DP_FORCE_COLLECTIVES=1: initialise RCCL and issue every bucket all-reduce even with one rank (lets a 1-GPU box
     # exercise the exact multi-GPU code path: process group, stream hand-over, async bucket launches)
     if (world > 1 or FORCE) and not dist.is_initialized():
@@ -66,6 +70,30 @@ def shard_indices(n_items, rank, world, epoch_seed, shuffle=True):
     perm = torch.randperm(n_items, generator=g) if shuffle else torch.arange(n_items)
     per = n_items // world
     return perm[rank:per * world:world]
+
+
+def deal_rows(n_rows, rank, world):
+    """(start, stop) of rank's contiguous slice of a global batch of n_rows rows, dealt as evenly as possible: the first
+    n_rows % world ranks get one row more.  The slices in rank order are the batch.  Pure arithmetic: every rank computes every
+    rank's slice."""
+    base, extra = divmod(int(n_rows), int(world))
+    start = rank * base + min(rank, extra)
+    return start, start + base + (1 if rank < extra else 0)
+
+
+def loss_shares(counts, group=None):
+    """counts: how many rows each of this rank's mean-over-rows loss terms averages (one int per term, e.g. [labelled rows, rows]).
+    -> (weights, totals): weights[i] = counts[i] * world / totals[i], totals[i] the count over all ranks.  The reducer averages the
+    rank gradients with 1 / world, so a rank that scales term i by weights[i] before backward() contributes
+    (counts[i] / totals[i]) * (its mean) -- summed over the ranks, the mean over the rows of the global batch, also when the shares
+    are unequal.  A rank with count 0 gets weight exactly 0.  totals[i] == 0 (no rank has such a row) gives NaN: the mean over no
+    row, as torch's cross_entropy reports it in one process.  One small collective (gather_ints); without a process group the
+    weights are 1.0 (or NaN)."""
+    counts = [int(c) for c in counts]
+    table = gather_ints(counts, group)
+    world = len(table)
+    totals = [sum(row[i] for row in table) for i in range(len(counts))]
+    return [c * world / t if t > 0 else float("nan") for c, t in zip(counts, totals)], totals
 
 
 class GradBucketReducer:

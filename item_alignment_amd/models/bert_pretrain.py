@@ -198,7 +198,10 @@ class BertForPreTraining(HipModule, PretrainedMixin):
         return self.cls.predictions.decoder
 
     def forward(self, input_ids, token_type_ids=None, attention_mask=None, masked_lm_labels=None, next_sentence_label=None,
-                position_ids=None, **unused):
+                position_ids=None, loss_shares=None, **unused):
+        """loss_shares=(w_mlm, w_nsp): data parallelism (item_alignment_amd.dist.loss_shares) -- each of the two mean losses is scaled
+        by this rank's share of the global batch's rows of its kind, so the ranks' averaged gradients are the gradient of the global
+        means.  None: the model of one process.  last_losses holds the two terms as they were added."""
         self.ensure_arena()
         B, L = input_ids.shape
         dev = input_ids.device
@@ -224,11 +227,17 @@ class BertForPreTraining(HipModule, PretrainedMixin):
         mlm = masked_lm_labels.reshape(-1).to(torch.long)
         rows = (mlm != -1).nonzero(as_tuple=False).squeeze(1)       # the one host sync of the head: M_live sizes its tensors
         if rows.numel() == 0:
-            mlm_loss = torch.full((), float("nan"), device=dev, dtype=F32)      # torch's mean over no row; no kernel runs with M = 0
+            # torch's mean over no row; no kernel runs with M = 0.  Under data parallelism a weight of 0 says that another rank holds
+            # labelled rows: this rank's share of the global mean is then exactly 0, not NaN
+            empty = 0.0 if loss_shares is not None and float(loss_shares[0]) == 0.0 else float("nan")
+            mlm_loss = torch.full((), empty, device=dev, dtype=F32)
         else:
             mlm_loss = MaskedLMHeadFn.apply(flat, self, rows, mlm.index_select(0, rows).contiguous())
         if next_sentence_label is None:
             return None, seq_score
+        if loss_shares is not None:
+            mlm_loss, nsp_loss = mlm_loss * float(loss_shares[0]), nsp_loss * float(loss_shares[1])
+        self.last_losses = (mlm_loss.detach(), nsp_loss.detach())
         return mlm_loss + nsp_loss, None, seq_score
 
     def save_pretrained(self, save_directory):

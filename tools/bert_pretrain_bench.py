@@ -12,6 +12,12 @@ What is timed (medians of the timed repeats after the warm-up, events on the str
     prediction_scores [B L, V] fp32 through the same GEMMs, torch's cross_entropy(ignore_index=-1) and its autograd on them, the
     gradient cast to bf16 for the same backward GEMMs.
 Recorded, not gated: there is no earlier figure to compare with.
+
+    python tools/bert_pretrain_bench.py --world 8 [--batch 32 ...] --out profiles/bert_pretrain_bench.json
+
+times only the train step, as bert_pretrain.py takes it under a launcher: once in one process and once on 8 data-parallel ranks that
+share the same global batch, every rank a fresh child process (tools/dp_bench.py).  The two figures are merged into the profile under
+"data_parallel"; a box with fewer GPUs than ranks records that the 8-rank figure is unmeasured.
 """
 import argparse
 import json
@@ -95,6 +101,37 @@ def timed(fn, steps, warmup):
     return dict(median_ms=times[len(times) // 2], min_ms=times[0], max_ms=times[-1], repeats=steps, warmup=warmup)
 
 
+def dp_child(a):
+    """one rank of the --world measurement: its dist.deal_rows slice of the synthetic global batch, the step of bert_pretrain.py"""
+    import dp_bench
+    import item_alignment_amd.models as M
+    from item_alignment_amd import dist as iadist
+    from item_alignment_amd.data import bert_pretrain as D
+    _, _, local = iadist.env_ranks()
+    dev = torch.device("cuda", local % torch.cuda.device_count())
+    torch.cuda.set_device(dev)
+    rng = D.Rng(a.seed)
+    examples = D.build_examples(synthetic_records(max(4, a.batch // 4), a.seed), _Tokenizer(), a.max_seq_len, rng)
+    assert len(examples) >= a.batch, "too few synthetic examples"
+    ids, mask, _types, labels, nsp = D.collate(examples[:a.batch])
+    torch.manual_seed(a.seed)
+    model = M.BertForPreTraining(config()).to(dev).train()
+
+    staged = {}          # this rank's rows on the device, moved once as the one-process measurement moves its batch once
+
+    def make_loss(lo, hi, rank, world):
+        if not staged:
+            staged.update(ids=ids[lo:hi].to(dev), mask=mask[lo:hi].to(dev), labels=labels[lo:hi].to(dev), nsp=nsp[lo:hi].to(dev))
+        # the count exchange of every step, as in the script
+        shares = iadist.loss_shares([int((labels[lo:hi] != -1).sum()), hi - lo])[0] if world > 1 else None
+        return model(staged["ids"], attention_mask=staged["mask"], masked_lm_labels=staged["labels"], next_sentence_label=staged["nsp"],
+                     loss_shares=shares)[0]
+
+    res = dp_bench.timed_rank_step(make_loss, model.param_arena, a.batch, a.steps, a.warmup)
+    res.update(positions=ids.shape[1], m_live_global=int((labels != -1).sum()))
+    print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
@@ -104,8 +141,18 @@ def main():
     ap.add_argument("--kernel-repeats", type=int, default=50)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--world", type=int, default=0, help="time the train step in one process and on this many data-parallel ranks, nothing else")
+    ap.add_argument("--dp-child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bert_pretrain_bench.py needs the GPU"
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    if a.dp_child:
+        return dp_child(a)
+    if a.world:
+        import dp_bench
+        dp_bench.measure(__file__, ["--batch", str(a.batch), "--max-seq-len", str(a.max_seq_len), "--steps", str(a.steps), "--warmup", str(a.warmup),
+                                    "--seed", str(a.seed)], a.world, a.out)
+        return
     import item_alignment_amd.models as M
     from item_alignment_amd import ops
     from item_alignment_amd.data import bert_pretrain as D

@@ -1,0 +1,105 @@
+"""What the step benchmarks share for their --world option (tools/bert_pretrain_bench.py, tools/finetune_bert_bench.py): the same
+train step timed in one process and on N data-parallel ranks, every rank a fresh child process of the tool itself (never more than
+16), the figures merged into the tool's profile under "data_parallel".
+
+A box that shows fewer GPUs than ranks records that the N-rank figure is unmeasured.  With IA_DP_BACKEND=gloo in the environment the
+ranks are started anyway and share the GPUs: that exercises the path, and the record says that it is no multi-GPU figure.
+"""
+import json
+import os
+import socket
+import subprocess
+import sys
+
+MAX_PROCESSES = 16
+
+
+def _free_port():
+    s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
+
+
+def run_ranks(script, argv, world, timeout=600):
+    """start `world` fresh children of `script` with --dp-child and the launcher's environment; -> the dict rank 0 printed last"""
+    if not 1 <= world < MAX_PROCESSES:
+        raise SystemExit(f"--world {world}: between 1 and {MAX_PROCESSES - 1} ranks (the tool itself is one more process)")
+    port = _free_port()
+    children = []
+    for rank in range(world):
+        env = dict(os.environ, RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+        children.append(subprocess.Popen([sys.executable, os.path.abspath(script), "--dp-child"] + list(argv), env=env, text=True,
+                                         stdout=subprocess.PIPE if rank == 0 else subprocess.DEVNULL))
+    try:
+        out, _ = children[0].communicate(timeout=timeout)
+        codes = [c.wait(timeout=timeout) for c in children]
+    finally:
+        for c in children:
+            if c.poll() is None:
+                c.kill()
+    if any(codes):
+        raise SystemExit(f"{script} --dp-child on {world} rank(s): exit codes {codes}")
+    return json.loads([line for line in out.splitlines() if line.startswith("{")][-1])
+
+
+def measure(script, argv, world, out_path):
+    """the one-process step and the `world`-rank step of the same run -> the "data_parallel" record, merged into out_path"""
+    import torch
+    gpus = torch.cuda.device_count()
+    rec = dict(world_1=run_ranks(script, argv, 1), world=world, gpus_visible=gpus)
+    if gpus >= world or os.environ.get("IA_DP_BACKEND"):
+        rec[f"world_{world}"] = run_ranks(script, argv, world)
+        rec["step_ms_world_n_over_world_1"] = rec[f"world_{world}"]["median_ms"] / rec["world_1"]["median_ms"]
+        if gpus < world:
+            rec["note"] = (f"{world} ranks shared {gpus} GPU(s) over {os.environ['IA_DP_BACKEND']}: the data-parallel path ran, "
+                           "but this is no multi-GPU figure")
+    else:
+        rec["unmeasured"] = f"the {world}-rank step was not run: {gpus} GPU(s) visible, one process per GPU needs {world}"
+    print(json.dumps(dict(data_parallel=rec)))
+    if out_path:
+        res = {}
+        if os.path.isfile(out_path):
+            with open(out_path) as f:
+                res = json.load(f)
+        res["data_parallel"] = rec
+        with open(out_path, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+    return rec
+
+
+def timed_rank_step(make_loss, arena, global_rows, steps, warmup):
+    """The scripts' train step on this rank, timed with events on the stream: zero_grad, forward, backward, the reducer's finish,
+    the gradient norm, fused AdamW.  make_loss(lo, hi, rank, world) -> the weighted loss of this rank's rows [lo, hi) of the global
+    batch.  -> the dict a --dp-child prints (medians over the timed steps; under several ranks every rank times the same step)."""
+    import torch
+    from item_alignment_amd import dist as iadist
+    from item_alignment_amd.models import functional as Fn
+    rank, world, _ = iadist.init_from_env("cuda")
+    reducer = None
+    if world > 1:
+        iadist.broadcast_arena(arena)
+        reducer = iadist.GradBucketReducer.for_arena(arena)
+        Fn.clear_grad_ready_hooks()
+        Fn.register_grad_ready_hook(reducer.grads_ready)
+    lo, hi = iadist.deal_rows(global_rows, rank, world)
+    times = []
+    for i in range(warmup + steps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        Fn.set_step_seed((1000 + i + rank * 0x9E3779B1) & 0xFFFFFFFF)
+        Fn.reset_use_counts()
+        arena.zero_grad()
+        loss = make_loss(lo, hi, rank, world)
+        loss.backward()
+        inv_world = reducer.finish() if reducer is not None else 1.0
+        scale = min(1.0, 1.0 / (arena.grad.norm().item() * inv_world + 1e-6)) * inv_world
+        arena.adamw_step(2e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=scale)
+        e1.record()
+        torch.cuda.synchronize()
+        if i >= warmup:
+            times.append(e0.elapsed_time(e1))
+    times.sort()
+    res = dict(median_ms=times[len(times) // 2], min_ms=times[0], max_ms=times[-1], repeats=steps, warmup=warmup, world=world,
+               rows_global=global_rows, rows_this_rank=hi - lo, gpu=torch.cuda.get_device_name(torch.cuda.current_device()))
+    if world > 1:
+        res["backend"] = torch.distributed.get_backend()
+        torch.distributed.destroy_process_group()
+    return res

@@ -11,6 +11,12 @@ Two forms of the same step (forward, backward, gradient norm, fused AdamW) over 
 Medians of the timed repeats after a warm-up of each form, events on the stream; the two forms alternate, `--rounds` times, and every
 other round starts with the other one, so neither always runs first or behind the same neighbour.  Recorded, not gated: there is no
 earlier figure to compare with.
+
+    python tools/finetune_bert_bench.py --world 8 [--batch 16 ...] --out profiles/finetune_bert_bench.json
+
+times only the ragged train step, as finetune_bert.py takes it under a launcher: once in one process and once on 8 data-parallel
+ranks that share the same global batch, every rank a fresh child process (tools/dp_bench.py).  The two figures are merged into the
+profile under "data_parallel"; a box with fewer GPUs than ranks records that the 8-rank figure is unmeasured.
 """
 import argparse
 import json
@@ -76,6 +82,31 @@ def summary(times, warmup):
     return dict(median_ms=s[len(s) // 2], min_ms=s[0], max_ms=s[-1], repeats=len(s), warmup_per_round=warmup)
 
 
+def dp_child(a):
+    """one rank of the --world measurement: its dist.deal_rows slice of the synthetic global batch, the step of finetune_bert.py"""
+    import dp_bench
+    import item_alignment_amd.models as M
+    from item_alignment_amd import dist as iadist
+    _, _, local = iadist.env_ranks()
+    dev = torch.device("cuda", local % torch.cuda.device_count())
+    torch.cuda.set_device(dev)
+    kw, labels, lengths = synthetic_batch(a.batch, a.seed, config().vocab_size)
+    torch.manual_seed(a.seed)
+    model = M.BertAlignModel(config()).to(dev).train()
+
+    staged = {}          # this rank's pairs on the device, moved once as the one-process measurement moves its batch once
+
+    def make_loss(lo, hi, rank, world):
+        if not staged:
+            staged.update(next_sentence_label=labels[lo:hi].to(dev), **{k: v[lo:hi].to(dev) for k, v in kw.items()})
+        loss = model(**staged)[-1]
+        return loss * iadist.loss_shares([hi - lo])[0][0] if world > 1 else loss          # the count exchange of every step, as in the script
+
+    res = dp_bench.timed_rank_step(make_loss, model.param_arena, a.batch, a.steps, a.warmup)
+    res.update(valid_tokens_global=sum(sum(v) for v in lengths.values()))
+    print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=16)
@@ -84,8 +115,18 @@ def main():
     ap.add_argument("--rounds", type=int, default=4)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--world", type=int, default=0, help="time the ragged train step in one process and on this many data-parallel ranks, nothing else")
+    ap.add_argument("--dp-child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "finetune_bert_bench.py needs the GPU"
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    if a.dp_child:
+        return dp_child(a)
+    if a.world:
+        import dp_bench
+        dp_bench.measure(__file__, ["--batch", str(a.batch), "--steps", str(a.steps), "--warmup", str(a.warmup), "--seed", str(a.seed)],
+                         a.world, a.out)
+        return
     import item_alignment_amd.models as M
     from item_alignment_amd.models import functional as Fn
     from item_alignment_amd.models.base import ACT_TANH, cls_rows
