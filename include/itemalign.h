@@ -545,6 +545,28 @@ int ia_color_jitter_step_u8(uint8_t* frames, const int* op, const float* factor,
 int ia_u8_to_nchw_normalized(const uint8_t* src, const uint8_t* flip, float* out, int B, int S0, int S1, const float* mean3,
                              const float* std3, ia_stream_t stream);
 
+/* ---- baseline JPEG decode on the GPU (--gpu_jpeg; the reference decodes with PIL inside __getitem__, src/data/data.py:848-860).  The
+ * host (item_alignment_amd/data/jpeg.py) parses the headers, removes the stuffed zeros and cuts the scan at its restart markers; the
+ * two stages below turn a batch of such scans into the uint8 [H, W, 3] frames Pillow produces, byte for byte.
+ * Layouts (all built by data/jpeg.py): desc [n_images][16] int32 = W, H, components (1 or 3), luma sampling h, v, MCUs per row,
+ * MCU rows, MCUs per restart segment, segments, first segment (index into the seg_* arrays), pieces, first piece, pieces of the
+ * longest segment, first coefficient (int16 elements), first plane byte, first output byte.  scan: the unstuffed segments, each at a
+ * multiple of 4 bytes; seg_off / seg_len: byte offset / length per segment; seg_piece0: image-local index of a segment's first piece;
+ * piece_seg: image-local segment per piece; tables [n_images][6][1424]: per component a DC and an AC Huffman table (512 x uint16
+ * 9-bit look-ahead, int32 maxcode[18], int32 valoff[17], 256 symbols); qt [n_images][3][64] bytes in natural order.
+ * Coefficients: per image the component grids (block raster over the MCU-padded grid, 64 natural-order int16 per block, DC summed)
+ * with 64 untouched elements in front of, between and behind them.
+ * ia_jpeg_entropy: scan -> coefficients.  subseq_bits (multiple of 32, >= 64) is the piece length; piece_ws = 10 * total_pieces
+ * int32 of scratch.  status[i] != 0: image i did not decode (a code matched nothing, a zigzag index passed 63, or the bits ran out
+ * before the blocks); rounds[i]: synchronisation rounds used.  One launch.
+ * ia_jpeg_reconstruct: coefficients -> RGB (dequantisation, libjpeg's accurate integer IDCT, fancy upsampling, 16.16 YCbCr -> RGB).
+ * planes: scratch, one byte per coefficient.  Two launches, n_images <= 65535. */
+int ia_jpeg_entropy(const int* desc, int n_images, const uint8_t* scan, const int* seg_off, const int* seg_len, const int* seg_piece0,
+                    const int* piece_seg, const uint8_t* tables, int* piece_ws, int total_pieces, int16_t* coef, int subseq_bits,
+                    int* status, int* rounds, ia_stream_t stream);
+int ia_jpeg_reconstruct(const int* desc, int n_images, const int16_t* coef, const uint8_t* qt, uint8_t* planes, uint8_t* out,
+                        ia_stream_t stream);
+
 /* ---- embeddings (src/models/base.py:238-279, :501-556, :394-442).  0 < H <= 4096, H % 8 == 0; extra_idx (may be NULL) needs extra;
  * z_out = bf16(word|extra + type + pos), mean / rstd are the statistics of that rounded z.  The backward call returns IA_ERR_WORKSPACE
  * for a workspace below ia_embed_ln_bwd_workspace_bytes(M, H). */

@@ -6,12 +6,14 @@ train scripts can slice batch[2:] exactly as the reference does.  Tokenisation i
 the tokenizer is whatever object the script passes in (transformers.BertTokenizer when a vocab.txt exists);
 jieba word segmentation is used when importable and skipped otherwise; images are decoded with PIL and go through
 data/transforms.py ImageTransform (the reference's timm create_transform: evaluation = bilinear Resize + CenterCrop, training =
-RandomResizedCrop + flip + colour jitter), on the host or - with raw=True / --gpu_preproc - on the GPU (data/gpu_preproc.py).
+RandomResizedCrop + flip + colour jitter), on the host or - with raw=True / --gpu_preproc - on the GPU (data/gpu_preproc.py);
+with jpeg=True / --gpu_jpeg the decode itself moves to the GPU too (data/jpeg.py) and the host only parses the file's headers.
 """
 import numpy as np
 import torch
 from torch.utils.data import Dataset
 
+from .jpeg import JpegImage, parse_jpeg
 from .transforms import ImageTransform
 
 IMG_TOKEN = "[unused99]"
@@ -355,16 +357,24 @@ class RawImageBatch:
 
 def stack_images(items):
     """torch.stack for processed [3,S,S] tensors (the reference path), RawImageBatch for RawImage samples."""
-    if items and isinstance(items[0], RawImage):
+    if items and isinstance(items[0], (RawImage, JpegImage)):
         return RawImageBatch(items)
     return torch.stack(items)
 
 
-def load_image(path, transform, raw=False):
+def load_image(path, transform, raw=False, jpeg=False):
     """PIL open -> RGB -> `transform` (data/transforms.py ImageTransform = the reference's timm create_transform, data.py:838-866):
     CHW fp32.  raw=True stops after the decode and returns a RawImage carrying the transform's random parameters: crop / resize /
-    flip / jitter / normalisation then run on the GPU (same arithmetic, gpu_preproc.py)."""
+    flip / jitter / normalisation then run on the GPU (same arithmetic, gpu_preproc.py).  jpeg=True stops before the decode: the
+    file's bytes and its parsed headers travel as a JpegImage, the parameters drawn from the SOF's width and height as they are from a
+    decoded frame; a file the GPU decoder does not take (data/jpeg.py parse_jpeg -> None) goes the raw=True way."""
     from PIL import Image
+    if jpeg:
+        data = np.fromfile(path, dtype=np.uint8)
+        plan = parse_jpeg(data)
+        if plan is not None:
+            return JpegImage(torch.from_numpy(data), plan, transform.draw(plan.width, plan.height))
+        raw = True
     img = Image.open(path).convert("RGB")
     params = transform.draw(img.width, img.height)
     if raw:
@@ -375,8 +385,8 @@ def load_image(path, transform, raw=False):
 class PairedImageDataset(Dataset):
     """reference data.py:835-869."""
 
-    def __init__(self, data, input_size, is_training, hflip=0.5, color_jitter=None, raw=False, seed=None):
-        self.data, self.size, self.raw = data, input_size, raw
+    def __init__(self, data, input_size, is_training, hflip=0.5, color_jitter=None, raw=False, seed=None, jpeg=False):
+        self.data, self.size, self.raw, self.jpeg = data, input_size, raw or jpeg, jpeg
         self.transform = ImageTransform(input_size, is_training, hflip, color_jitter, seed)
 
     def __len__(self):
@@ -386,8 +396,8 @@ class PairedImageDataset(Dataset):
         label, src_id, src_path, tgt_id, tgt_path = self.data[item]
         rec = {"labels": int(label), "src_item_id": src_id, "tgt_item_id": tgt_id}
         try:
-            rec["src_input"] = load_image(src_path, self.transform, raw=self.raw)
-            rec["tgt_input"] = load_image(tgt_path, self.transform, raw=self.raw)
+            rec["src_input"] = load_image(src_path, self.transform, raw=self.raw, jpeg=self.jpeg)
+            rec["tgt_input"] = load_image(tgt_path, self.transform, raw=self.raw, jpeg=self.jpeg)
         except Exception:
             pass                        # the collate drops samples without images (reference data.py:848-860, :84)
         return rec
@@ -397,8 +407,8 @@ class PairedMultimodalDataset(Dataset):
     """reference data.py:918-989 (CoCa pairs: text ids with explicit position ids 0..L-1 + two images)."""
 
     def __init__(self, data, ensemble, image_size, is_training, text_tokenizer, max_seq_len, max_seq_len_pv=None, hflip=0.5,
-                 color_jitter=None, raw=False, seed=None):
-        self.data, self.ensemble, self.size, self.raw = data, ensemble, image_size, raw
+                 color_jitter=None, raw=False, seed=None, jpeg=False):
+        self.data, self.ensemble, self.size, self.raw, self.jpeg = data, ensemble, image_size, raw or jpeg, jpeg
         self.transform = ImageTransform(image_size, is_training, hflip, color_jitter, seed)
         self.tk, self.max_seq_len, self.max_seq_len_pv = text_tokenizer, max_seq_len, max_seq_len_pv
 
@@ -419,8 +429,8 @@ class PairedMultimodalDataset(Dataset):
                "tgt_input_ids": t["input_ids"], "tgt_token_type_ids": t["token_type_ids"], "tgt_attention_mask": t["attention_mask"],
                "tgt_position_ids": list(range(len(t["input_ids"])))}
         try:
-            rec["src_image"] = load_image(src_path, self.transform, raw=self.raw)
-            rec["tgt_image"] = load_image(tgt_path, self.transform, raw=self.raw)
+            rec["src_image"] = load_image(src_path, self.transform, raw=self.raw, jpeg=self.jpeg)
+            rec["tgt_image"] = load_image(tgt_path, self.transform, raw=self.raw, jpeg=self.jpeg)
         except Exception:
             pass
         return rec
@@ -431,8 +441,8 @@ class MultimodalDataset(Dataset):
     the maximum length, position ids 0..L-1, one image.  The pvs come segmented from the caller, as in the reference's script."""
 
     def __init__(self, data, image_size, is_training, text_tokenizer, max_seq_len, max_seq_len_pv=None, hflip=0.5, color_jitter=None,
-                 raw=False, seed=None):
-        self.data, self.size, self.raw = data, image_size, raw
+                 raw=False, seed=None, jpeg=False):
+        self.data, self.size, self.raw, self.jpeg = data, image_size, raw or jpeg, jpeg
         self.transform = ImageTransform(image_size, is_training, hflip, color_jitter, seed)
         self.tk, self.max_seq_len, self.max_seq_len_pv = text_tokenizer, max_seq_len, max_seq_len_pv
 
@@ -450,7 +460,7 @@ class MultimodalDataset(Dataset):
         rec = dict(_tok(self.tk, " ".join((self.tk.bos_token, text)), L))
         rec["position_ids"] = list(range(len(rec["input_ids"])))
         try:
-            rec["image"] = load_image(image_path, self.transform, raw=self.raw)
+            rec["image"] = load_image(image_path, self.transform, raw=self.raw, jpeg=self.jpeg)
         except Exception:
             pass                        # the collate drops items without an image (reference data.py:902-908, :18-19)
         rec["item_id"] = item_id

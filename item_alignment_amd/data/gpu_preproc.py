@@ -70,6 +70,8 @@ class GpuImagePipeline:
     process(items)                         RawImage items (data/datasets.py) with the transform's parameters: evaluation items go
                                            through Resize(floor(S / 0.875), bilinear) + CenterCrop(S) batched per frame size, training
                                            items through their own RandomResizedCrop window, then flip / colour jitter / normalisation
+    decode(items)                          --gpu_jpeg: the JpegImage items (data/jpeg.py) among `items` decoded in one batched call,
+                                           returned as RawImage items whose frame lives on the device; process() does this first
     """
 
     def __init__(self, size, device, mean=IMAGENET_MEAN, std=IMAGENET_STD, filt="bilinear"):
@@ -77,6 +79,7 @@ class GpuImagePipeline:
         self._tables = {}
         self._mean = (C.c_float * 3)(*mean)
         self._std = (C.c_float * 3)(*std)
+        self._jpeg = None
 
     def _table(self, n_in, n_out=None, lo=0, count=None):
         """device tables for resizing n_in -> n_out, restricted to the output positions [lo, lo + count)"""
@@ -152,9 +155,29 @@ class GpuImagePipeline:
         self._pass(mid.data_ptr(), 0, 0, out, self._table(h, S), 1, h, S, S, False)
         return x                      # keeps the source alive until the stream has consumed it (caller holds the reference)
 
+    def decode(self, items):
+        """JpegImage items -> RawImage items with the decoded frame on the device (status != 0: decoded by Pillow from the kept bytes;
+        None where Pillow fails too: the caller drops that row, train.py decode_jpeg).  Other items pass through, their frame moved
+        to the device so that frames of one size still stack."""
+        from .datasets import RawImage
+        from .jpeg import GpuJpegDecoder, JpegImage, decode_with_fallback
+        idx = [i for i, it in enumerate(items) if isinstance(it, JpegImage)]
+        if not idx:
+            return list(items)
+        if self._jpeg is None:
+            self._jpeg = GpuJpegDecoder(self.device)
+        frames = decode_with_fallback(self._jpeg, [items[i] for i in idx])
+        out = [it if it is None or isinstance(it, JpegImage) else RawImage(it.u8.to(self.device, non_blocking=True), it.params) for it in items]
+        for i, f in zip(idx, frames):
+            out[i] = None if f is None else RawImage(f.to(self.device, non_blocking=True), items[i].params)
+        return out
+
     def process(self, items):
-        """RawImage items -> fp32 [N, 3, S, S]"""
+        """RawImage (or JpegImage) items -> fp32 [N, 3, S, S]"""
         lib = _lib.load()
+        items = self.decode(items)
+        if any(it is None for it in items):
+            raise ValueError("an image could not be decoded: drop its row first (train.py decode_jpeg)")
         N, S = len(items), self.size
         u8 = torch.empty((N, S, S, 3), device=self.device, dtype=torch.uint8)
         keep = []

@@ -90,15 +90,36 @@ def run(args, model, datasets, collate_fn, call_model, checkpoint_name, path_fie
 
     pipelines = {}
 
-    def gpu_images(raw_batch):
-        """RawImageBatch -> normalised [B, 3, S, S] on the device (data/gpu_preproc.py): the reference's transform, parameters drawn on
-        the host, arithmetic on the GPU."""
+    def pipeline():
         from .data.gpu_preproc import GpuImagePipeline
         size = int(getattr(args, "image_size", 0) or 0)
         pipe = pipelines.get(size)
         if pipe is None:
             pipe = pipelines[size] = GpuImagePipeline(size, device)
-        return pipe.process(raw_batch.items)
+        return pipe
+
+    def gpu_images(raw_batch):
+        """RawImageBatch -> normalised [B, 3, S, S] on the device (data/gpu_preproc.py): the reference's transform, parameters drawn on
+        the host, arithmetic on the GPU."""
+        return pipeline().process(raw_batch.items)
+
+    def decode_jpeg(batch):
+        """--gpu_jpeg: the JpegImage samples of every image element of a collate output are decoded in one batched call on the GPU
+        (data/jpeg.py; one status read per batch) and become RawImage samples whose frame already lives on the device.  A pair one of
+        whose images neither the GPU nor Pillow could decode is dropped from every element of the batch, ids included - the
+        reference's rule for an image that fails to load (data.py:44, :84), applied one stage later.  None: no row is left."""
+        from .data.datasets import RawImageBatch
+        from .data.jpeg import JpegImage, drop_rows
+        raws = [t for t in batch if isinstance(t, RawImageBatch)]
+        if not any(isinstance(it, JpegImage) for t in raws for it in t.items):
+            return batch
+        flat = pipeline().decode([it for t in raws for it in t.items])
+        n, decoded = len(raws[0]), {}
+        for j, t in enumerate(raws):
+            decoded[id(t)] = flat[j * n:(j + 1) * n]
+        keep = [all(d[i] is not None for d in decoded.values()) for i in range(n)]
+        batch = drop_rows(tuple(RawImageBatch(decoded[id(t)]) if isinstance(t, RawImageBatch) else t for t in batch), keep)
+        return batch if any(keep) else None
 
     def to_dev(batch):
         from .data.datasets import RawImageBatch
@@ -124,6 +145,9 @@ def run(args, model, datasets, collate_fn, call_model, checkpoint_name, path_fie
         probs_all, labels_all = None, None
         with torch.no_grad():
             for batch in loader:
+                batch = decode_jpeg(batch)
+                if batch is None:
+                    continue
                 b = to_dev(batch[2:])
                 out = call_model(model, b)
                 probs, labels = out.probs.float().cpu().numpy(), b[-1].cpu().numpy()
@@ -181,6 +205,9 @@ def run(args, model, datasets, collate_fn, call_model, checkpoint_name, path_fie
                                 generator=torch.Generator().manual_seed(aug_seed), **dl_kw)
             opt.zero_grad()
             for step, batch in enumerate(loader):
+                batch = decode_jpeg(batch)
+                if batch is None:
+                    continue
                 b = to_dev(batch[2:])
                 # dropout streams differ per rank (every rank holds other samples of the global batch: identical masks would correlate them)
                 Fn.set_step_seed((args.seed * 1000003 + global_step * 131 + step + rank * 0x9E3779B1) & 0xFFFFFFFF)
@@ -217,6 +244,9 @@ def run(args, model, datasets, collate_fn, call_model, checkpoint_name, path_fie
         loader = DataLoader(datasets["test"], batch_size=args.eval_batch_size, shuffle=False, collate_fn=collate_fn, **dl_kw)
         with open(os.path.join(out_dir, f"deepAI_result_{getattr(args, 'pred_tag', '')}threshold={args.threshold}.jsonl"), "w", encoding="utf-8") as w, torch.no_grad():
             for step, batch in enumerate(loader):
+                batch = decode_jpeg(batch)
+                if batch is None:
+                    continue
                 src_ids, tgt_ids = batch[:2]
                 out = call_model(model, to_dev(batch[2:]))
                 se, te = out.src_embeds.float().cpu().numpy(), out.tgt_embeds.float().cpu().numpy()
