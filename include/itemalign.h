@@ -476,6 +476,22 @@ int ia_silu_pad_fwd(const void* x, void* y, int B, int H, int W, int C, float sc
 int ia_pad_rows(const void* x, void* y, int B, int H, int W, int C, int in_padded, int out_padded, ia_stream_t stream);   /* plain copy */
 int ia_silu_pad_bwd(const void* dy, const void* x, void* dx, int B, int H, int W, int C, float scale, int in_padded, int out_padded,
                     ia_stream_t stream);
+/* ---- forward-only epilogues (NormFreeNet.embed).  The direct stride-1 / stride-2 kernels with the activation that follows the
+ * convolution taken on the fp32 accumulator: y = bf16(silu(acc + bias) * act_scale), one rounding, no pass of its own over the map.
+ * Operands as ia_conv3x3_padded_fwd / ia_conv3x3_s2_padded_fwd.  y_compact = 0: y is the bordered [B, Ho + 2, Wo + 2, Cout] domain and
+ * only its interior is written -- the border belongs to the caller: a buffer whose border was zeroed once stays a valid zero-bordered
+ * input for every later batch; y_compact != 0: y is [B, Ho, Wo, Cout].  Only the direct kernels have this epilogue: a stride-1 channel
+ * pair without one (ia_conv3x3_direct_supported's forward half: ci -> co per group in 64->64, 16->32, 32->64, 64->32, 32->16, groups
+ * <= 64) and every stride-2 shape outside ia_conv3x3_s2_supported return IA_ERR_UNSUPPORTED before anything is launched.
+ * ia_silu_gap_fwd: pooled [B, C] fp32 = scale * mean over HW of silu(x [B, HW, C] bf16), SiLU and sum in fp32 (the tower's tail:
+ * final_act + global pool in one read); C % 8 == 0, workspace of ia_gap_workspace_bytes(B, HW, C).  The additions did not bump
+ * IA_ABI_VERSION: nothing existing changed its meaning. */
+int ia_conv3x3_padded_fwd_act(const void* xp, const void* what, const float* bias, void* y, int B, int H, int W, int Cin, int Cout, int groups,
+                              float act_scale, int y_compact, ia_stream_t stream);
+int ia_conv3x3_s2_padded_fwd_act(const void* xp, const void* what, const float* bias, void* y, int B, int H, int W, int Cin, int Cout,
+                                 int groups, float act_scale, int y_compact, ia_stream_t stream);
+int ia_silu_gap_fwd(const void* x, float* pooled, int B, int HW, int C, float scale, void* workspace, size_t workspace_bytes,
+                    ia_stream_t stream);
 
 /* ---- pre-activation ResNetV2 tower pieces (reference src/models/image.py:298-378 ResNetTwoTower -> timm 0.6.5 resnetv2.py
  * with norm_layer=BatchNormAct2d; README.md:187-197 `--model_name resnetv2_50`).  NHWC rows [B*H*W, C] bf16 as above. */

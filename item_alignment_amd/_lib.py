@@ -160,6 +160,9 @@ SIGNATURES = {
     "ia_conv3x3_s2_padded_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "ia_conv3x3_s2_padded_bwd_weight": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
     "ia_conv3x3_s2_padded_bwd_data_t": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "ia_conv3x3_padded_fwd_act": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, i32, vp]),
+    "ia_conv3x3_s2_padded_fwd_act": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, i32, vp]),
+    "ia_silu_gap_fwd": (i32, [vp, vp, i32, i32, i32, f32, vp, sz, vp]),
     "ia_gn_act_workspace_bytes": (sz, [i32, i32, i32]),
     "ia_gn_act_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp, sz, vp]),
     "ia_gn_act_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp]),

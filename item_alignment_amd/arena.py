@@ -78,6 +78,7 @@ class ParamArena:
         self._transposed_table = None
         self.step_count = 0
         self.stale_refreshes = 0
+        self.shadow_refreshes = 0          # every refresh_shadow(): what a holder of derived weights (NormFreeNet.embed) keys its copies by
         self.optimizer_bound = False
         self.refresh_shadow()
 
@@ -111,6 +112,7 @@ class ParamArena:
         self.join_side_streams()
         check(lib.ia_cast_f32_to_bf16(self.master.data_ptr(), self.shadow.data_ptr(), self.numel, stream_ptr()), "ia_cast_f32_to_bf16")
         self._versions = self._param_versions()
+        self.shadow_refreshes += 1
         self.refresh_transposed()
 
     def register_transposed(self, params):

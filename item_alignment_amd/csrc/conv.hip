@@ -3,6 +3,8 @@
 // so a 1x1 convolution IS the bf16 MFMA GEMM of gemm.hip and a (grouped) 3x3 convolution is a patch gather
 // (im2col, HBM-bound) followed by one GEMM per channel group; weights arrive standardised and laid out [Cout][tap][Cin/g].
 // Everything else here is an HBM-bound element-wise / reduction kernel with 16-byte accesses.
+#include <type_traits>
+
 #include "common.h"
 #include "../../include/itemalign.h"
 
@@ -219,6 +221,8 @@ __global__ __launch_bounds__(256) void avgpool2_bwd_kernel(const bf16* __restric
 
 // ------------------------------------------------------------------------------- spatial reductions
 // part[b][s][c] = sum over the s-th slice of HW of x[b, hw, c] (* y[b, hw, c] if y); fixed slice order -> deterministic
+// SILU (forward-only tail, ia_silu_gap_fwd): the terms are silu(x) in fp32 -- final_act and the global pool in one read of the map
+template <bool SILU = false>
 __global__ __launch_bounds__(256) void spatial_sum_kernel(const bf16* __restrict__ x, const bf16* __restrict__ y, float* __restrict__ part,
                                                           int HW, int C, int nsplit) {
   // C/8 column threads x as many row lanes as fit in the block; row lanes are folded through LDS in a fixed order
@@ -240,6 +244,9 @@ __global__ __launch_bounds__(256) void spatial_sum_kernel(const bf16* __restrict
           const bf16x8 u = *reinterpret_cast<const bf16x8*>(y + ((size_t)b * HW + hw) * C + c);
 #pragma unroll
           for (int j = 0; j < 8; ++j) acc[j] += bf2f(v[j]) * bf2f(u[j]);
+        } else if constexpr (SILU) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) { const float a = bf2f(v[j]); acc[j] += a / (1.f + __expf(-a)); }
         } else {
 #pragma unroll
           for (int j = 0; j < 8; ++j) acc[j] += bf2f(v[j]);
@@ -689,8 +696,20 @@ extern "C" int ia_gap_fwd(const void* x, float* pooled, int B, int HW, int C, vo
   if (!x || !pooled || B <= 0 || HW <= 0 || C <= 0 || (C & 7)) return IA_ERR_ARG;
   if (!workspace || workspace_bytes < ia_gap_workspace_bytes(B, HW, C)) return IA_ERR_WORKSPACE;
   const int ns = nsplit_of(HW);
-  hipLaunchKernelGGL(spatial_sum_kernel, dim3(ns, B), dim3(256), 0, stream, (const bf16*)x, (const bf16*)nullptr, (float*)workspace, HW, C, ns);
+  hipLaunchKernelGGL(spatial_sum_kernel<false>, dim3(ns, B), dim3(256), 0, stream, (const bf16*)x, (const bf16*)nullptr, (float*)workspace, HW, C, ns);
   hipLaunchKernelGGL(spatial_finish_kernel, dim3((B * C + 255) / 256), dim3(256), 0, stream, (const float*)workspace, pooled, C, ns, 1.f / HW, B * C);
+  return ia_check_launch();
+}
+
+// pooled [B, C] fp32 = scale * mean over HW of silu(x [B, HW, C] bf16): final_act + head.global_pool of the forward-only tower
+extern "C" int ia_silu_gap_fwd(const void* x, float* pooled, int B, int HW, int C, float scale, void* workspace, size_t workspace_bytes,
+                               hipStream_t stream) {
+  (void)hipGetLastError();
+  if (!x || !pooled || B <= 0 || HW <= 0 || C <= 0 || (C & 7)) return IA_ERR_ARG;
+  if (!workspace || workspace_bytes < ia_gap_workspace_bytes(B, HW, C)) return IA_ERR_WORKSPACE;
+  const int ns = nsplit_of(HW);
+  hipLaunchKernelGGL(spatial_sum_kernel<true>, dim3(ns, B), dim3(256), 0, stream, (const bf16*)x, (const bf16*)nullptr, (float*)workspace, HW, C, ns);
+  hipLaunchKernelGGL(spatial_finish_kernel, dim3((B * C + 255) / 256), dim3(256), 0, stream, (const float*)workspace, pooled, C, ns, scale / HW, B * C);
   return ia_check_launch();
 }
 
@@ -771,7 +790,7 @@ extern "C" int ia_eca_bwd(const void* dout, const void* x, const float* conv_w, 
   if (!dout || !x || !conv_w || !pooled || !gate || !dx || k <= 0 || k > 16 || !(k & 1) || (C & 7)) return IA_ERR_ARG;
   if (!workspace || workspace_bytes < ia_eca_bwd_workspace_bytes(B, HW, C)) return IA_ERR_WORKSPACE;
   const int ns = nsplit_of(HW);
-  hipLaunchKernelGGL(spatial_sum_kernel, dim3(ns, B), dim3(256), 0, stream, (const bf16*)dout, (const bf16*)x, (float*)workspace, HW, C, ns);
+  hipLaunchKernelGGL(spatial_sum_kernel<false>, dim3(ns, B), dim3(256), 0, stream, (const bf16*)dout, (const bf16*)x, (float*)workspace, HW, C, ns);
   return eca_bwd_tail(dout, conv_w, k, pooled, gate, dx, dconv_w, B, HW, C, coef, workspace, stream);
 }
 
@@ -824,6 +843,15 @@ struct Args {
   int B, H, W, Cin, Cout, groups;
   int tiles_x, tiles_y;
 };
+// the forward-only variant (ACT): the epilogue stores bf16(silu(acc + bias) * act_scale); out_compact: yp is [B, H, W, Cout] without a border
+struct ActArgs : Args { float act_scale; int out_compact; };
+// what an epilogue stores of z = acc + bias.  ACT: silu(z) * scale on the fp32 value -- z * v_rcp_f32(1 + v_exp_f32(-z log2 e)), the two
+// hardware transcendentals (1 ulp each) and three multiplies + one add, no division sequence: the epilogue has nothing to hide under.
+// z -> -inf: exp2 = +inf, rcp = 0, the product -0 (silu's limit); z -> +inf: exp2 = 0, the product z.
+template <bool ACT> IA_DEV float epi(float z, float scale) {
+  if constexpr (ACT) return z * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(z * -1.4426950408889634f)) * scale;
+  else return z;
+}
 
 template <int CI> IA_DEV int akey(int P) { return CI == 64 ? (P & 7) : CI == 32 ? ((P >> 1) & 3) : 0; }     // swizzle key of input pixel P
 template <int CO> IA_DEV int bkey(int row) { return (row >> (CO == 64 ? 3 : CO == 32 ? 2 : 1)) & 3; }      // of filter row n (64-byte rows)
@@ -845,8 +873,8 @@ struct Geo {
   static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 };
 
-template <int CI, int CO>
-__global__ __launch_bounds__(256) void conv3x3_direct_kernel(Args p) {
+template <int CI, int CO, bool ACT = false>
+__global__ __launch_bounds__(256) void conv3x3_direct_kernel(std::conditional_t<ACT, ActArgs, Args> p) {
   using G = Geo<CI, CO>;
   constexpr int PB = G::PB, NC = G::NC, PPP = G::PPP, NS = G::NS, NI = G::NI, IN_BYTES = G::IN_BYTES, W_BYTES = G::W_BYTES;
   constexpr int IN_PIECES = G::IN_PIECES, W_PIECES = G::W_PIECES;
@@ -990,18 +1018,27 @@ __global__ __launch_bounds__(256) void conv3x3_direct_kernel(Args p) {
       const int q = wave * 64 + mi * 16 + li;
       const int y = q / TW, x = q - y * TW;
       if (q >= TILE_PX || y0 + y > p.H || x0 + x > p.W) continue;
-      bf16* const dst = p.yp + (((size_t)b * PH + (y0 + y)) * PW + (x0 + x)) * p.Cout + (size_t)grp * CO + g * (CO / 4);
+      size_t orow = ((size_t)b * PH + (y0 + y)) * PW + (x0 + x);
+      float as = 1.f;
+      if constexpr (ACT) {
+        as = p.act_scale;
+        if (p.out_compact) orow = ((size_t)b * p.H + (y0 + y - 1)) * p.W + (x0 + x - 1);
+      }
+      bf16* const dst = p.yp + orow * p.Cout + (size_t)grp * CO + g * (CO / 4);
       if constexpr (NI == 1) {
         bf16x4 o;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = f2bf(acc[mi][0][j] + bv[0][j]);
+        for (int j = 0; j < 4; ++j) o[j] = f2bf(epi<ACT>(acc[mi][0][j] + bv[0][j], as));
         *reinterpret_cast<bf16x4*>(dst) = o;
       } else {
 #pragma unroll
         for (int h = 0; h < NI / 2; ++h) {
           bf16x8 o;
 #pragma unroll
-          for (int j = 0; j < 4; ++j) { o[j] = f2bf(acc[mi][2 * h][j] + bv[2 * h][j]); o[4 + j] = f2bf(acc[mi][2 * h + 1][j] + bv[2 * h + 1][j]); }
+          for (int j = 0; j < 4; ++j) {
+            o[j] = f2bf(epi<ACT>(acc[mi][2 * h][j] + bv[2 * h][j], as));
+            o[4 + j] = f2bf(epi<ACT>(acc[mi][2 * h + 1][j] + bv[2 * h + 1][j], as));
+          }
           *reinterpret_cast<bf16x8*>(dst + 8 * h) = o;
         }
       }
@@ -1027,9 +1064,10 @@ struct S2Args {
   int tiles_x, tiles_y;
   int out_compact;             // yp is [B, H, W, Cout] without a border (the stem's last convolution feeds compact consumers)
 };
+struct S2ActArgs : S2Args { float act_scale; };                // the forward-only variant, as ActArgs
 
-template <int CO>
-__global__ __launch_bounds__(256) void conv3x3_s2_kernel(S2Args p) {
+template <int CO, bool ACT = false>
+__global__ __launch_bounds__(256) void conv3x3_s2_kernel(std::conditional_t<ACT, S2ActArgs, S2Args> p) {
   constexpr int CI = 64;
   using G = Geo<CI, CO>;
   constexpr int PB = G::PB, NC = G::NC, PPP = G::PPP, NI = G::NI, IN_BYTES = G::IN_BYTES, W_BYTES = G::W_BYTES;
@@ -1161,11 +1199,16 @@ __global__ __launch_bounds__(256) void conv3x3_s2_kernel(S2Args p) {
       if (q >= TILE_PX || y0 + y > p.H || x0 + x > p.W) continue;
       const size_t orow = p.out_compact ? ((size_t)b * p.H + (y0 + y - 1)) * p.W + (x0 + x - 1) : ((size_t)b * PH + (y0 + y)) * PW + (x0 + x);
       bf16* const dst = p.yp + orow * p.Cout + (size_t)grp * CO + g * (CO / 4);
+      float as = 1.f;
+      if constexpr (ACT) as = p.act_scale;
 #pragma unroll
       for (int h = 0; h < NI / 2; ++h) {
         bf16x8 o;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) { o[j] = f2bf(acc[mi][2 * h][j] + bv[2 * h][j]); o[4 + j] = f2bf(acc[mi][2 * h + 1][j] + bv[2 * h + 1][j]); }
+        for (int j = 0; j < 4; ++j) {
+          o[j] = f2bf(epi<ACT>(acc[mi][2 * h][j] + bv[2 * h][j], as));
+          o[4 + j] = f2bf(epi<ACT>(acc[mi][2 * h + 1][j] + bv[2 * h + 1][j], as));
+        }
         *reinterpret_cast<bf16x8*>(dst + 8 * h) = o;
       }
     }
@@ -1375,10 +1418,10 @@ static long slots_per_group(int lds_bytes, int groups, long ntiles) {
   return n < 1 ? 1 : n;
 }
 
-template <int CI, int CO>
-static int launch_t(const Args& a, hipStream_t stream) {
+template <int CI, int CO, bool ACT = false, class A = Args>
+static int launch_t(const A& a, hipStream_t stream) {
   using G = Geo<CI, CO>;
-  auto kern = conv3x3_direct_kernel<CI, CO>;
+  auto kern = conv3x3_direct_kernel<CI, CO, ACT>;
   static bool lds_set = false;
   if (const int rc = allow_lds((const void*)kern, G::LDS_BYTES, lds_set)) return rc;
   const long per_group = slots_per_group(G::LDS_BYTES, a.groups, (long)a.B * a.tiles_x * a.tiles_y);
@@ -1392,6 +1435,19 @@ static int launch(const void* xp, const void* w, const float* bias, void* yp, in
   a.B = B; a.H = H; a.W = W; a.Cin = groups * ci; a.Cout = groups * co; a.groups = groups;
   tiles_of(H, W, a.tiles_x, a.tiles_y);
 #define X(CI, CO) if (ci == CI && co == CO) return launch_t<CI, CO>(a, stream);
+  DCONV_PAIRS(X)
+#undef X
+  return IA_ERR_UNSUPPORTED;
+}
+// y (bordered interior, or compact) = silu(conv3x3(x bordered) + bias) * act_scale: the forward-only epilogue
+static int launch_act(const void* xp, const void* w, const float* bias, void* yp, int B, int H, int W, int ci, int co, int groups, float act_scale,
+                      int out_compact, hipStream_t stream) {
+  ActArgs a;
+  a.xp = (const bf16*)xp; a.w = (const bf16*)w; a.bias = bias; a.yp = (bf16*)yp;
+  a.B = B; a.H = H; a.W = W; a.Cin = groups * ci; a.Cout = groups * co; a.groups = groups;
+  a.act_scale = act_scale; a.out_compact = out_compact;
+  tiles_of(H, W, a.tiles_x, a.tiles_y);
+#define X(CI, CO) if (ci == CI && co == CO) return launch_t<CI, CO, true, ActArgs>(a, stream);
   DCONV_PAIRS(X)
 #undef X
   return IA_ERR_UNSUPPORTED;
@@ -1803,15 +1859,17 @@ static int launch_s2_dgrad(const void* gp, const void* wt, void* dxp, int B, int
 }
 
 // launcher of the stride-2 forward kernel
+template <bool ACT = false>
 static int launch_s2(const void* xp, const void* w, const float* bias, void* yp, int B, int XH, int XW, int Cin, int Cout, int groups, int shared_input,
-                     int out_compact, hipStream_t stream) {
-  S2Args a;
+                     int out_compact, hipStream_t stream, float act_scale = 1.f) {
+  std::conditional_t<ACT, S2ActArgs, S2Args> a;
+  if constexpr (ACT) a.act_scale = act_scale;
   a.xp = (const bf16*)xp; a.w = (const bf16*)w; a.bias = bias; a.yp = (bf16*)yp;
   a.B = B; a.XH = XH; a.XW = XW; a.H = (XH - 1) / 2 + 1; a.W = (XW - 1) / 2 + 1;
   a.Cin = Cin; a.Cout = Cout; a.groups = groups; a.in_gstride = shared_input ? 0 : 64; a.out_compact = out_compact;
   tiles_of(a.H, a.W, a.tiles_x, a.tiles_y);
   using G = Geo<64, 64>;
-  auto kern = conv3x3_s2_kernel<64>;
+  auto kern = conv3x3_s2_kernel<64, ACT>;
   static bool lds_set = false;
   if (const int rc = allow_lds((const void*)kern, G::LDS_BYTES, lds_set)) return rc;
   const long per_group = slots_per_group(G::LDS_BYTES, groups, (long)a.B * a.tiles_x * a.tiles_y);
@@ -1847,6 +1905,18 @@ extern "C" int ia_conv3x3_padded_fwd(const void* xp, const void* what, const flo
   v.a_window = Mp * Cin * 2; v.b_window = (size_t)Cout * 9 * ci * 2;
   v.groups = groups; v.ga = ci; v.gb = (long)co * 9 * ci; v.gc = co; v.gbias = co;
   return ia_gemm_view(v, stream);
+}
+
+// the direct kernel with the forward-only epilogue y = bf16(silu(acc + bias) * act_scale); no view-GEMM form: other pairs are unsupported
+extern "C" int ia_conv3x3_padded_fwd_act(const void* xp, const void* what, const float* bias, void* y, int B, int H, int W, int Cin, int Cout,
+                                         int groups, float act_scale, int y_compact, hipStream_t stream) {
+  (void)hipGetLastError();
+  const int rc = padded_ok(B, H, W, Cin, Cout, groups);
+  if (rc) return rc;
+  if (!xp || !what || !y) return IA_ERR_ARG;
+  const int ci = Cin / groups, co = Cout / groups;
+  if (!dconv::pair_ok(ci, co) || groups > 64) return IA_ERR_UNSUPPORTED;
+  return dconv::launch_act(xp, what, bias, y, B, H, W, ci, co, groups, act_scale, y_compact != 0, stream);
 }
 
 extern "C" int ia_conv3x3_padded_bwd_data(const void* dyp, const void* what, void* dxp, int B, int H, int W, int Cin, int Cout, int groups,
@@ -1962,6 +2032,15 @@ extern "C" int ia_conv3x3_s2_padded_fwd(const void* xp, const void* what, const 
   if (rc) return rc;
   if (!xp || !what || !yp) return IA_ERR_ARG;
   return dconv::launch_s2(xp, what, bias, yp, B, H, W, Cin, Cout, vg, shared, y_compact, stream);
+}
+extern "C" int ia_conv3x3_s2_padded_fwd_act(const void* xp, const void* what, const float* bias, void* y, int B, int H, int W, int Cin, int Cout,
+                                            int groups, float act_scale, int y_compact, hipStream_t stream) {
+  (void)hipGetLastError();
+  int vg, shared;
+  const int rc = s2_ok(B, H, W, Cin, Cout, groups, &vg, &shared);
+  if (rc) return rc;
+  if (!xp || !what || !y) return IA_ERR_ARG;
+  return dconv::launch_s2<true>(xp, what, bias, y, B, H, W, Cin, Cout, vg, shared, y_compact, stream, act_scale);
 }
 // dwhat [Cout][9 * Cin / groups] fp32 (overwritten), dbias [Cout] (+=, may be NULL); dyp needs no particular border
 extern "C" int ia_conv3x3_s2_padded_bwd_weight(const void* xp, const void* dyp, float* dwhat, float* dbias, int B, int H, int W, int Cin, int Cout,

@@ -6,6 +6,9 @@ Activations are NHWC bf16 ([B*H*W, C] rows): a 1x1 convolution is the bf16 MFMA 
 gather + one GEMM per group (csrc/conv.hip).  Module / parameter names are timm's, so `image_encoder.bin` state_dicts load:
 `stem.conv{1..4}.{weight,bias,gain}`, `stages.{s}.{b}.{downsample.conv,conv1,conv2,conv2b,conv3}.{weight,bias,gain}`,
 `stages.{s}.{b}.attn_last.conv.weight`, `final_conv.*`, `head.fc.*`.
+
+`NormFreeNet.embed` is the forward-only path (image_embedding.py): the SiLU behind a direct 3x3 convolution in that kernel's epilogue,
+SiLU + pool in one read, standardised weights held between calls, feature maps in buffers owned per (batch, image size).
 """
 import math
 
@@ -15,6 +18,7 @@ from torch import nn
 from .. import _lib
 from .._lib import check, ptr, stream_ptr
 from . import functional as Fn
+from ..utils import logger
 from .base import HipModule
 
 BF16, F32 = torch.bfloat16, torch.float32
@@ -455,6 +459,15 @@ class ScaledStdConv2d(nn.Module):
         return (self.kernel_size == 3 and self.stride == 2
                 and bool(_lib.load().ia_conv3x3_s2_supported(self.in_channels, self.out_channels, self.groups)))
 
+    @property
+    def embed_direct(self):
+        """a 3x3 convolution whose direct kernel has the forward-only activation epilogue (ia_conv3x3[_s2]_padded_fwd_act)"""
+        if self.kernel_size != 3:
+            return False
+        if self.stride == 2:
+            return self.strided_direct
+        return self.shifted_views and bool(_lib.load().ia_conv3x3_direct_supported(self.in_channels, self.out_channels, self.groups))
+
     def fits_padded(self, B, H, W):
         """row indices of the padded tensor are 32-bit ints (its byte size is not limited)"""
         return B * (H + 2) * (W + 2) < 0x7FFFFFFF
@@ -506,6 +519,10 @@ class NormFreeBlock(nn.Module):
         self.conv2b = ScaledStdConv2d(mid_chs, mid_chs, 3, stride=1, groups=groups)
         self.conv3 = ScaledStdConv2d(mid_chs, out_chs, 1, gain_init=0.0)       # timm: gain_init = 1 if skipinit else 0
         self.attn_last = EcaModule(out_chs)
+
+    def embed_direct(self, B, H, W):
+        """NormFreeNet.embed runs this block, entered at H x W, on the activation-epilogue kernels"""
+        return self.conv2.embed_direct and self.conv2b.embed_direct and self.conv2b.fits_padded(B, H, W)
 
     def forward(self, f, next_block=None):
         """next_block: the NormFreeBlock that consumes this block's output (None: something else does, e.g. final_conv) -- its opening
@@ -649,6 +666,201 @@ class NormFreeNet(HipModule):
 
     def forward(self, images):
         return self.head.global_pool(self.forward_features(images))
+
+    # ------------------------------------------------------------------------------------------ forward-only path
+    def train(self, mode=True):
+        self._drop_embed_state()
+        return super().train(mode)
+
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        self._drop_embed_state()
+        return super().load_state_dict(state_dict, strict=strict, **kw)
+
+    def _drop_embed_state(self):
+        self.__dict__.pop("_embed_held", None)
+        self.__dict__.pop("_embed_plan_held", None)
+
+    def _embed_fallback(self, what):
+        """a stem or block without the activation-epilogue kernels runs on the existing launches: said once per tower, never silently"""
+        if not self.__dict__.get("_embed_fallback_logged"):
+            self.__dict__["_embed_fallback_logged"] = True
+            logger.warning(f"NormFreeNet.embed: {what} has no activation-epilogue kernel and runs through the existing forward launches")
+
+    def _embed_plan(self, B, H, W, device):
+        """ONE plan is kept: it serves every batch of its image size up to its capacity (a smaller batch -- the last partial one, or one
+        with unreadable images left out -- uses a prefix of its per-image buffers); a larger batch or another image size drops it, frees
+        its memory and builds a new one.  What embed retains is therefore bounded by the largest batch seen at the current size."""
+        plan = self.__dict__.get("_embed_plan_held")
+        if plan is None or plan.key != (H, W, device) or B > plan.capacity:
+            self.__dict__.pop("_embed_plan_held", None)
+            del plan
+            torch.cuda.empty_cache()                   # the old buffers go back to the device before the new ones are asked for
+            plan = self.__dict__["_embed_plan_held"] = _EmbedPlan(device, (H, W, device), B)
+        plan.B = B
+        return plan
+
+    def _embed_weights(self, arena):
+        """every ScaledStdConv2d's standardised bf16 weight, computed once and held until a weight may have changed: train(),
+        load_state_dict, an optimiser step, or any write the arena's staleness guard saw (its shadow was refreshed)"""
+        key = (id(arena), arena.shadow_refreshes, arena.step_count)
+        held = self.__dict__.get("_embed_held")
+        if held is None or held[0] != key:
+            what = {}
+            for m in self.modules():
+                if isinstance(m, ScaledStdConv2d):
+                    kk, g = m.kernel_size ** 2, m.groups
+                    what[m] = _standardised(m, m.weight.shape[1], kk, m.in_pad // g)[0]
+            held = self.__dict__["_embed_held"] = (key, what)
+        return held[1]
+
+    def _embed_direct(self, B, H, W):
+        """does every 3x3 convolution of the stem have the activation epilogue at this size?  (conv1 reads the image through the patch
+        matrix; conv2 / conv3 are stride-1 direct pairs, conv4 is a stride-2 shape)"""
+        c1, c2, c3, c4 = (m for m in self.stem.children() if isinstance(m, ScaledStdConv2d))
+        H1, W1 = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        first = self.stages[0][0]          # it reads conv4's epilogue as its opening activation: nothing else may want conv4's plain output
+        return (c1.stride == 2 and c2.embed_direct and c3.embed_direct and c4.embed_direct and c4.stride == 2 and c2.fits_padded(B, H1, W1)
+                and first.downsample is not None and first.embed_direct(B, (H1 - 1) // 2 + 1, (W1 - 1) // 2 + 1))
+
+    @torch.no_grad()
+    def embed(self, images):
+        """images [B, 3, S, S] fp32 -> the pooled features [B, num_features] fp32: the tower's inference path.  The same arithmetic as
+        head.global_pool(forward_features(images)) with fewer roundings and passes: the SiLU behind every direct 3x3 convolution is taken on
+        the fp32 accumulator in that convolution's epilogue (ia_conv3x3[_s2]_padded_fwd_act), final_act and the pool are one read of
+        final_conv's output (ia_silu_gap_fwd), the standardised weights are held between calls and the feature maps live in buffers owned
+        by one _EmbedPlan per image size (see _embed_plan).  Nothing is kept for a backward pass."""
+        root = self._root if "_root" in self.__dict__ else self
+        arena = root.ensure_arena()
+        lib = _lib.load()
+        Fn._need_gpu(images, "images")
+        images = images.contiguous().to(F32)
+        B, C, H, W = images.shape
+        if not self._embed_direct(B, H, W):
+            self._embed_fallback("the stem or the first block")
+            return self.forward(images)                        # the existing launches, all of them
+        what = self._embed_weights(arena)
+        plan = self._embed_plan(B, H, W, images.device)
+        sp = stream_ptr()
+        c1, c2, c3, c4 = (m for m in self.stem.children() if isinstance(m, ScaledStdConv2d))
+        blocks = [blk for stage in self.stages for blk in stage]
+        # ---- stem: image -> NHWC (8 channels) -> conv1 (patch matrix) -> silu, bordered -> conv2 + silu -> conv3 + silu -> conv4 + silu * beta
+        x = plan.buf("image", (B * H * W, 8))
+        check(lib.ia_nchw_to_nhwc_bf16(images.data_ptr(), x.data_ptr(), B, C, H, W, 8, sp), "ia_nchw_to_nhwc_bf16")
+        t, H, W = plan.conv(c1, what[c1], x, "stem1", B, H, W), (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        p = plan.silu_pad(t, "stem1p", B, H, W)
+        p = plan.conv3_act(c2, what[c2], p, "stem2p", B, H, W, 1.0, False)
+        p = plan.conv3_act(c3, what[c3], p, "stem3p", B, H, W, 1.0, False)
+        act = plan.conv3_act(c4, what[c4], p, "stem4", B, H, W, blocks[0].beta, True)
+        H, W = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        f = FeatureMap(None, B, H, W, act=(act, act))
+        # ---- blocks
+        for i, blk in enumerate(blocks):
+            nxt = blocks[i + 1] if i + 1 < len(blocks) else None
+            if blk.embed_direct(f.B, f.H, f.W) and f.act is not None:
+                f = plan.block(blk, what, f, nxt, i)
+            else:
+                self._embed_fallback(f"block {i}")
+                f = blk(f, nxt)                                # the existing launches: freshly allocated tensors, read by the next block
+        # ---- tail: final_conv -> silu + global average pool in one read
+        t = plan.conv(self.final_conv, what[self.final_conv], f.t, "final", f.B, f.H, f.W)
+        pooled = torch.empty((B, self.num_features), device=images.device, dtype=F32)
+        wsb = lib.ia_gap_workspace_bytes(B, f.H * f.W, self.num_features)
+        check(lib.ia_silu_gap_fwd(t.data_ptr(), pooled.data_ptr(), B, f.H * f.W, self.num_features, 1.0, plan.ws(wsb).data_ptr(), wsb, sp),
+              "ia_silu_gap_fwd")
+        return pooled
+
+
+class _EmbedPlan:
+    """The feature-map buffers of NormFreeNet.embed at one image size, for up to `capacity` images: allocated at first use, reused by
+    every later batch.  Every buffer is laid out per image ([B * rows, C]), so a batch of B <= capacity images uses the first B images'
+    worth of each (`buf` returns that prefix; the kernels' range checks end with the B images they are told about).
+    A bordered buffer is zero-filled when it is created and only its interior is written afterwards (ia_silu_pad_fwd rewrites the
+    zeros, the activation epilogues leave the border alone), so it stays a valid zero-bordered input.  A block's buffers are keyed by
+    role and shape -- blocks of one stage share them, the two tensors that outlive a block (`out`, `act`) alternate between two sets."""
+
+    def __init__(self, device, key, capacity):
+        self.device, self.key, self.capacity, self.B = device, key, capacity, capacity
+        self.bufs, self._ws = {}, None
+
+    def buf(self, role, shape, dtype=BF16, zero=False):
+        """shape = (B * rows, ...) of the current batch: the first B images of a buffer allocated for `capacity` images"""
+        rows = shape[0] // self.B
+        assert rows * self.B == shape[0]
+        key = (role, (rows,) + tuple(shape[1:]), dtype)
+        t = self.bufs.get(key)
+        if t is None:
+            t = self.bufs[key] = (torch.zeros if zero else torch.empty)((self.capacity * rows,) + tuple(shape[1:]), device=self.device, dtype=dtype)
+        return t[:shape[0]]
+
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in self.bufs.values()) + (0 if self._ws is None else self._ws.numel())
+
+    def ws(self, nbytes):
+        """one scratch area for every call that wants one (they run in order on one stream)"""
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = _ws(self.device, nbytes)
+        return self._ws
+
+    def conv(self, conv, what, x, role, B, H, W):
+        """a ScaledStdConv2d through ia_conv_nhwc_fwd (1x1: the GEMM; the stem's conv1: patch matrix) on compact rows"""
+        lib = _lib.load()
+        C, Cout, k, s, g = conv.in_pad, conv.out_channels, conv.kernel_size, conv.stride, conv.groups
+        Ho, Wo = (H, W) if k == 1 else ((H - 1) // s + 1, (W - 1) // s + 1)
+        y = self.buf(role, (B * Ho * Wo, Cout))
+        wsb = lib.ia_conv_nhwc_workspace_bytes(B, H, W, C, Cout, k, s, g)
+        check(lib.ia_conv_nhwc_fwd(x.data_ptr(), what.data_ptr(), ptr(conv.bias), y.data_ptr(), B, H, W, C, Cout, k, s, g, self.ws(wsb).data_ptr(), wsb,
+                                   stream_ptr()), "ia_conv_nhwc_fwd")
+        return y
+
+    def silu_pad(self, x, role, B, H, W):
+        """compact -> silu -> bordered (the 1x1 GEMM's epilogue stays as it is: the layout changes here)"""
+        y = self.buf(role, (B * (H + 2) * (W + 2), x.shape[1]), zero=True)
+        check(_lib.load().ia_silu_pad_fwd(x.data_ptr(), y.data_ptr(), B, H, W, x.shape[1], 1.0, 0, 1, stream_ptr()), "ia_silu_pad_fwd")
+        return y
+
+    def conv3_act(self, conv, what, xp, role, B, H, W, scale, compact):
+        """bordered xp at H x W -> silu(conv3x3(xp) + bias) * scale, bordered (interior written) or compact, at H x W or, stride 2, half"""
+        lib = _lib.load()
+        Cin, Cout, g = conv.in_channels, conv.out_channels, conv.groups
+        Ho, Wo = (H, W) if conv.stride == 1 else ((H - 1) // 2 + 1, (W - 1) // 2 + 1)
+        y = self.buf(role, (B * Ho * Wo, Cout)) if compact else self.buf(role, (B * (Ho + 2) * (Wo + 2), Cout), zero=True)
+        fn, nm = ((lib.ia_conv3x3_padded_fwd_act, "ia_conv3x3_padded_fwd_act") if conv.stride == 1
+                  else (lib.ia_conv3x3_s2_padded_fwd_act, "ia_conv3x3_s2_padded_fwd_act"))
+        check(fn(xp.data_ptr(), what.data_ptr(), ptr(conv.bias), y.data_ptr(), B, H, W, Cin, Cout, g, scale, int(compact), stream_ptr()), nm)
+        return y
+
+    def block(self, blk, what, f, nxt, i):
+        """one NormFreeBlock: f.act = silu(x) * beta from the producer; conv1 -> silu_pad -> conv2 + silu -> conv2b + silu -> conv3 -> ECA +
+        residual (+ the next block's opening activation)"""
+        lib = _lib.load()
+        B, H, W = f.B, f.H, f.W
+        a_in = f.act[0]
+        if blk.downsample is not None:
+            sx, sH, sW = a_in, H, W
+            if blk.downsample.stride > 1:
+                sH, sW = (H + 1) // 2, (W + 1) // 2
+                sx = self.buf("pool", (B * sH * sW, a_in.shape[1]))
+                check(lib.ia_avgpool2_fwd(a_in.data_ptr(), sx.data_ptr(), B, H, W, a_in.shape[1], stream_ptr()), "ia_avgpool2_fwd")
+            shortcut = self.conv(blk.downsample.conv, what[blk.downsample.conv], sx, "shortcut", B, sH, sW)
+        else:
+            shortcut = f.t
+        t = self.conv(blk.conv1, what[blk.conv1], a_in, "mid1", B, H, W)
+        p = self.silu_pad(t, "mid1p", B, H, W)
+        p = self.conv3_act(blk.conv2, what[blk.conv2], p, "mid2p", B, H, W, 1.0, False)
+        if blk.conv2.stride == 2:
+            H, W = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        a = self.conv3_act(blk.conv2b, what[blk.conv2b], p, "mid3", B, H, W, 1.0, True)
+        x3 = self.conv(blk.conv3, what[blk.conv3], a, "mid4", B, H, W)
+        C, k, Cmid = x3.shape[1], blk.attn_last.conv.weight.shape[-1], a.shape[1]
+        out = self.buf("out%d" % (i & 1), (B * H * W, C))
+        act = self.buf("act%d" % (i & 1), (B * H * W, C)) if nxt is not None else None
+        pooled, gate = self.buf("pooled", (B, C), F32), self.buf("gate", (B, C), F32)
+        wsb = lib.ia_eca_fwd_linear_workspace_bytes(B, H * W, Cmid)
+        check(lib.ia_eca_fwd_linear(x3.data_ptr(), a.data_ptr(), what[blk.conv3].data_ptr(), ptr(blk.conv3.bias), Cmid, blk.attn_last.conv.weight.data_ptr(),
+                                    k, shortcut.data_ptr(), out.data_ptr(), ptr(act), nxt.beta if nxt is not None else 1.0, pooled.data_ptr(),
+                                    gate.data_ptr(), B, H * W, C, blk.attn_gain * blk.alpha, self.ws(wsb).data_ptr(), wsb, stream_ptr()),
+              "ia_eca_fwd_linear")
+        return FeatureMap(out, B, H, W, act=None if act is None else (act, act))
 
 
 def create_nfnet(model_name, **kwargs):
