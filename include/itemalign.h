@@ -98,6 +98,22 @@ int ia_kblock_mask(const uint8_t* row_live, int M_rows, uint32_t* mask, ia_strea
 int ia_kblock_mask_host(const uint8_t* row_live, int M_rows, uint32_t* mask);
 int ia_gemm_wgrad_blocks(const void* dY, int ldy, const void* X, int ldx, float* dW, int ldw, int N_out, int N_in, int M_rows,
                          const uint32_t* kblock_mask, int accumulate, void* workspace, size_t workspace_bytes, ia_stream_t stream);
+/* The same walk over 16-row steps.  ia_kstep_mask: bit (s & 31) of mask[s >> 5] = OR of row_live over rows 16s .. 16s+15, clipped to
+ * M_rows; ia_kstep_mask_bytes(M_rows) bytes; one launch, plain stores; ia_kstep_mask_host: the same words from host memory through the
+ * per-step function the device kernel calls (a diagnostic hook, as ia_kblock_mask_host).
+ * ia_gemm_wgrad_steps: the twin of ia_gemm_wgrad_blocks over the 16-row steps of k whose bit is set, four to a 64-row k-tile -- a step
+ * is one whole MFMA per accumulator, so the results are identical to ia_gemm_wgrad_blocks' and ia_gemm_bf16's on inputs that keep
+ * row_live's guarantee.  kstep_mask: device pointer, NULL = the ia_gemm_bf16 call.  The step walk serves k-slabs of at most 512 k-tiles.
+ * A longer one takes the block walk from the block mask of the step mask, which the call builds behind the split-K partials (one small
+ * launch) when the workspace has ia_gemm_wgrad_rows_workspace_bytes; with the plain split-K workspace such a shape reads every row.
+ * ia_gemm_wgrad_walk (diagnostics): the walk a filtered weight gradient of this shape takes given a step mask and that workspace --
+ * 2 = 16-row steps, 1 = 32-row blocks, 0 = every row.  The additions did not bump IA_ABI_VERSION: nothing existing changed its meaning. */
+size_t ia_kstep_mask_bytes(int M_rows);
+int ia_kstep_mask(const uint8_t* row_live, int M_rows, uint32_t* mask, ia_stream_t stream);
+int ia_kstep_mask_host(const uint8_t* row_live, int M_rows, uint32_t* mask);
+int ia_gemm_wgrad_steps(const void* dY, int ldy, const void* X, int ldx, float* dW, int ldw, int N_out, int N_in, int M_rows,
+                        const uint32_t* kstep_mask, int accumulate, void* workspace, size_t workspace_bytes, ia_stream_t stream);
+int ia_gemm_wgrad_walk(int N_out, int N_in, int M_rows);
 /* (ABI 18) The data gradient of a Linear over padded token rows: dX[M_rows, N_in] = dY[M_rows, K_out] W (+ epilogue), bf16 -- ia_gemm_bf16's
  * data-gradient form (A = dY k-contiguous; B = W [K_out, N_in] k-strided, w_kstrided = 1, or its transposed shadow [N_in, K_out],
  * w_kstrided = 0; epilogue IA_EPI_NONE, IA_EPI_ADD or IA_EPI_DGELU_COLSUM with aux / C2 as there) -- and a row filter.  row_live [M_rows]

@@ -55,6 +55,11 @@ SIGNATURES = {
     "ia_kblock_mask": (i32, [vp, i32, vp, vp]),
     "ia_kblock_mask_host": (i32, [vp, i32, vp]),
     "ia_gemm_wgrad_blocks": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, vp, i32, vp, sz, vp]),
+    "ia_kstep_mask_bytes": (sz, [i32]),
+    "ia_kstep_mask": (i32, [vp, i32, vp, vp]),
+    "ia_kstep_mask_host": (i32, [vp, i32, vp]),
+    "ia_gemm_wgrad_steps": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, vp, i32, vp, sz, vp]),
+    "ia_gemm_wgrad_walk": (i32, [i32, i32, i32]),
     "ia_gemm_dgrad_rows_workspace_bytes": (sz, [i32, i32, i32]),
     "ia_gemm_dgrad_rows_filters": (i32, [i32, i32, i32]),
     "ia_gemm_dgrad_rows": (i32, [vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, sz, vp]),

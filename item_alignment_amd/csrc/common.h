@@ -209,7 +209,7 @@ __attribute__((visibility("hidden"))) size_t ia_gemm_view_workspace_bytes(int M,
 //   KBLOCKS  32-row block of k, one bit each       ia_kblock_mask                         weight gradient
 // NONE, a null list, or a shape the filtered kernel does not serve: every row, exactly the call ia_gemm_bf16 / ia_gemm_bf16_qscale makes.
 struct IaRowFilter {
-  enum Kind { NONE, BLOCKS, GROUPS, PACKED, SLABS, KBLOCKS };
+  enum Kind { NONE, BLOCKS, GROUPS, PACKED, SLABS, KBLOCKS, KSTEPS };
   Kind kind = NONE;
   const void* list = nullptr;
   bool fill = true;      // forward GEMMs: the dead rows of Y (and C2) are written as zeros, else not written at all (data gradients always fill)

@@ -22,7 +22,7 @@ struct Carver {
 
 // Where a layer call builds the row lists its caller did not hand in (resolve_rows): one slot per filter kind, null where the call
 // never builds that kind
-struct RowSlots { uint32_t* kmask = nullptr; int* blocks = nullptr; int* groups = nullptr; int* packed = nullptr; int* slabs = nullptr; };
+struct RowSlots { uint32_t* kmask = nullptr; int* blocks = nullptr; int* groups = nullptr; int* packed = nullptr; int* slabs = nullptr; uint32_t* ksteps = nullptr; };
 
 // The buffers of one layer forward, by role.  The training stash gives each role its own memory (the backward reads them all); the
 // forward-only scratch aliases the ones whose contents are dead by the time the memory is written again.
@@ -85,8 +85,8 @@ FwdBufs carve_infer(const ia_layer_cfg* c, void* base) {
 
 struct Scratch {
   char* g0; char* g1; char* g2; char* gI; char* gqkv; float* delta; char* ws; size_t ws_bytes; char* gws; size_t gws_bytes;
-  RowSlots key;      // masked_rows_dead: the key mask's 32-row block mask (ia_kblock_mask), block-packed list and 8-row slab list
-  RowSlots out;      // out_row_live: its 32-row block mask, block list and group list
+  RowSlots key;      // masked_rows_dead: the key mask's 32-row block mask (ia_kblock_mask), block-packed list, 8-row slab list, step mask
+  RowSlots out;      // out_row_live: its 32-row block mask, block list, group list and 16-row step mask (ia_kstep_mask)
   size_t bytes;
 };
 
@@ -114,6 +114,10 @@ Scratch carve_scratch(const ia_layer_cfg* c, void* base) {
   s.out.blocks = (int*)a.take(ia_row_blocks_bytes((int)M));
   s.out.groups = (int*)a.take(ia_row_groups_bytes((int)M));
   s.key.slabs = (int*)a.take(ia_row_slabs_bytes((int)M));
+  // the weight gradients' 16-row step masks (ia_kstep_mask), always built here: ia_row_lists has no member for them.  Behind everything
+  // else: a reader of the scratch finds every other piece where it was.
+  s.key.ksteps = (uint32_t*)a.take(ia_kstep_mask_bytes((int)M));
+  s.out.ksteps = (uint32_t*)a.take(ia_kstep_mask_bytes((int)M));
   s.bytes = a.bytes;
   return s;
 }
@@ -145,10 +149,10 @@ int out_q_rows(const ia_layer_cfg* c) { return (out_live(c) && c->out_q_rows > 0
 // common.h).  A kind nobody asked for, and every kind of an every-row plan, stays NONE.
 struct RowPlan {
   const uint8_t* live = nullptr;
-  IaRowFilter kmask, blocks, groups, packed, slabs;
+  IaRowFilter kmask, blocks, groups, packed, slabs, ksteps;
 };
 enum RowSource { KEY_MASK, OUT_ROWS };
-enum : unsigned { WANT_KMASK = 1, WANT_BLOCKS = 2, WANT_GROUPS = 4, WANT_PACKED = 8, WANT_SLABS = 16 };
+enum : unsigned { WANT_KMASK = 1, WANT_BLOCKS = 2, WANT_GROUPS = 4, WANT_PACKED = 8, WANT_SLABS = 16, WANT_KSTEPS = 32 };
 
 // The one place that builds the lists a caller did not hand in.  `live`: the key mask (its filters exist under IA_ROWS_DEAD_BWD on padded
 // rows only) or out_row_live; null: an every-row plan.  For each kind of `want` the plan takes the caller's member of ia_row_lists
@@ -170,6 +174,7 @@ int resolve_rows(const ia_layer_cfg* c, RowSource which, const uint8_t* live, un
   if (want & WANT_GROUPS) IA_TRY(take(plan->groups, IaRowFilter::GROUPS, given.groups, slot.groups));
   if ((want & WANT_PACKED) && (size_t)M <= (size_t)128 * 4096) IA_TRY(take(plan->packed, IaRowFilter::PACKED, given.packed, slot.packed));
   if (want & WANT_SLABS) IA_TRY(take(plan->slabs, IaRowFilter::SLABS, given.slabs, slot.slabs));
+  if (want & WANT_KSTEPS) IA_TRY(take(plan->ksteps, IaRowFilter::KSTEPS, nullptr, slot.ksteps));      // (no member of ia_row_lists: always built here)
   return IA_OK;
 }
 
@@ -189,10 +194,18 @@ int dgrad(const void* dy, int k_out, const void* w, const void* wt, int n_in, vo
                                 ws_bytes, st);
 }
 
-// Weight gradient dW[n_out, n_in] += dy[M, n_out]^T x[M, n_in]; with a mask (an ia_kblock_mask), over the 32-row blocks of k that hold
-// a live row only
-int wgrad(const void* dy, int n_out, const void* x, int n_in, float* dw, int M, IaRowFilter kmask, void* ws, size_t ws_bytes, ia_stream_t st) {
-  return ia_gemm_wgrad_filtered(dy, n_out, x, n_in, dw, n_in, n_out, n_in, M, kmask, 1, ws, ws_bytes, st);
+// Weight gradient dW[n_out, n_in] += dy[M, n_out]^T x[M, n_in] over the live k of the plan: the 16-row steps that hold a live row (an
+// ia_kstep_mask) where the shape takes that walk, else the 32-row blocks (an ia_kblock_mask); an every-row plan: every row
+bool wgrad_steps(int n_out, int n_in, int M) { return ia_gemm_wgrad_walk(n_out, n_in, M) == 2; }
+int wgrad(const void* dy, int n_out, const void* x, int n_in, float* dw, int M, const RowPlan& rows, void* ws, size_t ws_bytes, ia_stream_t st) {
+  const IaRowFilter f = (rows.ksteps && wgrad_steps(n_out, n_in, M)) ? rows.ksteps : rows.kmask;
+  return ia_gemm_wgrad_filtered(dy, n_out, x, n_in, dw, n_in, n_out, n_in, M, f, 1, ws, ws_bytes, st);
+}
+// the masks a backward asks for: the step mask when one of the shapes it serves walks steps, the block mask when one does not
+unsigned want_wgrad_masks(const int (*shapes)[2], int n, int M) {
+  unsigned want = 0;
+  for (int i = 0; i < n; ++i) want |= wgrad_steps(shapes[i][0], shapes[i][1], M) ? WANT_KSTEPS : WANT_KMASK;
+  return want;
 }
 
 // A forward GEMM y[M, N] = x[M, K] w[N, K]^T (+ epilogue; aux has y's pitch) over the live rows of the plan: the 8-row slabs where the
@@ -399,16 +412,20 @@ extern "C" int ia_layer_bwd2(const ia_layer_cfg* c, const ia_layer_weights* w, c
   // out_row_live: the incoming gradient is zero outside these rows, so every gradient in front of the attention backward is too.  Its
   // block mask, block list and group list (the caller's, or built here) filter the kernels from the LN2 backward to the out-projection's
   // gradients; the attention backward and the QKV gradients keep the layer's other filter (every row is a key).
+  // The weight gradients walk the live 16-row steps of k where the shape allows (ia_gemm_wgrad_walk), from a step mask this call builds
+  // in its scratch (one small launch per mask), else the live 32-row blocks of the caller's block mask or one built here.
+  const int behind_attn[3][2] = {{H, I}, {I, H}, {H, H}}, qkv_shape[1][2] = {{3 * H, H}};
   RowPlan out;
-  IA_TRY(resolve_rows(c, OUT_ROWS, out_live(c), WANT_KMASK | WANT_BLOCKS | WANT_GROUPS, M, k.out, st, &out));
+  IA_TRY(resolve_rows(c, OUT_ROWS, out_live(c), want_wgrad_masks(behind_attn, 3, M) | WANT_BLOCKS | WANT_GROUPS, M, k.out, st, &out));
   if (!c->pre_ln) {
     // masked_rows_dead: every gradient row of a masked position is exactly zero (ia_layer_cfg): the LayerNorm backward kernels skip them,
-    // the four weight gradients skip the 32-row blocks of k that hold nothing else, the two
+    // the four weight gradients skip the 16-row steps of k that hold nothing else (32-row blocks where the k-slab is too long), the two
     // plain data gradients behind the attention and the QKV one run the live 8-row slabs (their dead rows are written as zeros: the
     // attention backward, the pair kernels and the embedding backward read every row), and the x gelu' + column-sums data gradient the
     // live blocks packed by whole 128-row groups.  ia_debug_dgrad_rows withholds the lists of the data gradients, not the mask.
     RowPlan key;
-    IA_TRY(resolve_rows(c, KEY_MASK, key_mask, WANT_KMASK | (g_dgrad_rows ? WANT_PACKED | WANT_SLABS : 0), M, k.key, st, &key));
+    const unsigned key_masks = want_wgrad_masks(qkv_shape, 1, M) | (out.live ? 0u : want_wgrad_masks(behind_attn, 3, M));
+    IA_TRY(resolve_rows(c, KEY_MASK, key_mask, key_masks | (g_dgrad_rows ? WANT_PACKED | WANT_SLABS : 0), M, k.key, st, &key));
     // behind the attention: out_row_live's plan when given (a subset of the live keys), else the key mask's
     const RowPlan& rows = out.live ? out : key;
     // The two residual additions of a post-LN layer make each LayerNorm output's gradient a sum of two terms; both LayerNorm
@@ -417,10 +434,10 @@ extern "C" int ia_layer_bwd2(const ia_layer_cfg* c, const ia_layer_weights* w, c
     IA_TRY(ia_ln_bwd2_rows(dy, dy2, nullptr, s.ffn, s.mean2, s.rstd2, w->ln2_g, k.g0, drop ? k.g1 : nullptr, g->ln2_g, g->ln2_b, g->b_fc2, M, H,
                            c->hidden_drop, c->seed, c->layer_id * 4u + 1u, rows.live, k.ws, k.ws_bytes, 1, st));
     const char* d_ffn = drop ? k.g1 : k.g0;
-    IA_TRY(wgrad(d_ffn, H, s.hact, I, (float*)g->w_fc2, M, rows.kmask, k.gws, k.gws_bytes, st));
+    IA_TRY(wgrad(d_ffn, H, s.hact, I, (float*)g->w_fc2, M, rows, k.gws, k.gws_bytes, st));
     // d(pre-activation) = (d_ffn W2) * gelu'(pre), and its column sums (the fc1 bias gradient) out of the same epilogue
     IA_TRY(dgrad(d_ffn, H, w->w_fc2, w->wt_fc2, I, k.gI, M, IA_EPI_DGELU_COLSUM, s.hpre, I, g->b_fc1, k.ws, k.ws_bytes, st, rows));
-    IA_TRY(wgrad(k.gI, I, s.ln, H, (float*)g->w_fc1, M, rows.kmask, k.gws, k.gws_bytes, st));
+    IA_TRY(wgrad(k.gI, I, s.ln, H, (float*)g->w_fc1, M, rows, k.gws, k.gws_bytes, st));
     IA_TRY(dgrad(k.gI, I, w->w_fc1, w->wt_fc1, H, k.g2, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, rows));
     // LN1 backward: d(y1) = g2 (through fc1) + g0 (residual into LN2) -> dz1 (the layer input's residual-path gradient) in
     // dz1buf: the caller's dx2 when the split form is wanted, else g0 (in place over the term just consumed)
@@ -428,11 +445,11 @@ extern "C" int ia_layer_bwd2(const ia_layer_cfg* c, const ia_layer_weights* w, c
     IA_TRY(ia_ln_bwd2_rows(k.g2, k.g0, nullptr, s.proj, s.mean1, s.rstd1, w->ln1_g, dz1buf, drop ? k.g1 : nullptr, g->ln1_g, g->ln1_b, g->b_o, M, H,
                            c->hidden_drop, c->seed, c->layer_id * 4u + 0u, rows.live, k.ws, k.ws_bytes, 1, st));
     const char* d_att = drop ? k.g1 : dz1buf;
-    IA_TRY(wgrad(d_att, H, s.ctx, H, (float*)g->w_o, M, rows.kmask, k.gws, k.gws_bytes, st));
+    IA_TRY(wgrad(d_att, H, s.ctx, H, (float*)g->w_o, M, rows, k.gws, k.gws_bytes, st));
     // (d_ctx and dz1 are zeros outside out_row_live: the attention backward and the QKV data gradient's "+ dz1" read every live key's row)
     IA_TRY(dgrad(d_att, H, w->w_o, w->wt_o, H, k.g2, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, rows));
     IA_TRY(attn_bwd(c, s.qkv, key_mask, s.ctx, k.g2, s.lse, k.delta, k.gqkv, g->b_qkv, k.ws, k.ws_bytes, scale, c->attn_drop, attn_seed, st));
-    IA_TRY(wgrad(k.gqkv, 3 * H, x, H, (float*)g->w_qkv, M, key.kmask, k.gws, k.gws_bytes, st));
+    IA_TRY(wgrad(k.gqkv, 3 * H, x, H, (float*)g->w_qkv, M, key, k.gws, k.gws_bytes, st));
     if (dx2)   // split form: dx = the attention sub-block's data gradient, dx2 = dz1 (already written)
       IA_TRY(dgrad(k.gqkv, 3 * H, w->w_qkv, w->wt_qkv, H, dx, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, key));
     else
@@ -440,18 +457,18 @@ extern "C" int ia_layer_bwd2(const ia_layer_cfg* c, const ia_layer_weights* w, c
   } else {
     if (!c->dy_colsum_done) IA_TRY(ia_colsum(dy, H, M, H, g->b_fc2, 1, k.ws, k.ws_bytes, st));
     // (without out_row_live the plan is empty: the helpers then make the plain every-row calls)
-    IA_TRY(wgrad(dy, H, s.hact, I, (float*)g->w_fc2, M, out.kmask, k.gws, k.gws_bytes, st));
+    IA_TRY(wgrad(dy, H, s.hact, I, (float*)g->w_fc2, M, out, k.gws, k.gws_bytes, st));
     IA_TRY(dgrad(dy, H, w->w_fc2, w->wt_fc2, I, k.gI, M, IA_EPI_DGELU_COLSUM, s.hpre, I, g->b_fc1, k.ws, k.ws_bytes, st, out));
-    IA_TRY(wgrad(k.gI, I, s.ln, H, (float*)g->w_fc1, M, out.kmask, k.gws, k.gws_bytes, st));
+    IA_TRY(wgrad(k.gI, I, s.ln, H, (float*)g->w_fc1, M, out, k.gws, k.gws_bytes, st));
     IA_TRY(dgrad(k.gI, I, w->w_fc1, w->wt_fc1, H, k.g0, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, out));
     // LN2 backward (+ residual path dy) -> g1 = d x2 ; its column sum is the proj-bias gradient
     // (the row-filtered launch keeps every row's place in the partial sums: leaving out rows that add exact zeros changes no bit)
     IA_TRY(ia_ln_bwd2_rows(k.g0, nullptr, dy, s.proj, s.mean2, s.rstd2, w->ln2_g, k.g1, nullptr, g->ln2_g, g->ln2_b, g->b_o, M, H, 0.f, 0, 0, out.live,
                            k.ws, k.ws_bytes, 1, st));
-    IA_TRY(wgrad(k.g1, H, s.ctx, H, (float*)g->w_o, M, out.kmask, k.gws, k.gws_bytes, st));
+    IA_TRY(wgrad(k.g1, H, s.ctx, H, (float*)g->w_o, M, out, k.gws, k.gws_bytes, st));
     IA_TRY(dgrad(k.g1, H, w->w_o, w->wt_o, H, k.g2, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, out));
     IA_TRY(attn_bwd(c, s.qkv, key_mask, s.ctx, k.g2, s.lse, k.delta, k.gqkv, g->b_qkv, k.ws, k.ws_bytes, scale, 0.f, 0, st));
-    IA_TRY(wgrad(k.gqkv, 3 * H, s.xn, H, (float*)g->w_qkv, M, IaRowFilter{}, k.gws, k.gws_bytes, st));
+    IA_TRY(wgrad(k.gqkv, 3 * H, s.xn, H, (float*)g->w_qkv, M, RowPlan{}, k.gws, k.gws_bytes, st));
     IA_TRY(dgrad(k.gqkv, 3 * H, w->w_qkv, w->wt_qkv, H, k.g0, M, IA_EPI_NONE, nullptr, 0, nullptr, nullptr, 0, st, RowPlan{}));
     // dx = LN1'(g0) + g1 is the incoming gradient of the block below: its column sums (that block's fc2 bias gradient) come out of
     // this kernel's partial sums instead of a separate pass over [M, H] there (cfg->dx_colsum_out)

@@ -49,6 +49,12 @@ enum { EPI_NONE = 0, EPI_BIAS = 1, EPI_BIAS_GELU = 2, EPI_ADD = 3, EPI_DGELU = 4
 // the same order, less those whose dY operand is all zeros, and a slab takes ceil(live blocks / 2) trips.  (The value 8 was the walk
 // over whole 64-row k-tiles this one replaced; 9 stays, and with it the kernel's name in the profiles.)
 constexpr int EPI_NONE_BLK = 9;
+// EPI_NONE_STP (library-internal, t256w only): the same walk over the live 16-row STEPS of an ia_kstep_mask, FOUR to a k-tile.  A 16-row
+// step is one whole 32x32x16 MFMA per accumulator, so the argument above holds unchanged: step q of a trip is DMA pieces 2q and 2q + 1
+// (LDS rows 16q .. 16q + 15) and k-step q, and a slab takes ceil(live steps / 4) trips.  A 32-row block with one live row costs a whole
+// block under the block walk and half of one here (0.60-0.62 of the rows against 0.66-0.68 at the benchmark's lengths).  The slab's bits
+// are one word per lane, four per k-tile: slabs of up to 512 k-tiles (step_mask_fits); longer ones keep the block walk.
+constexpr int EPI_NONE_STP = 10;
 // EPI_ROWS + e (library-internal, t256w only; k-contiguous A, bf16 output): epilogue e behind a row remap.  The data gradient dX = dY W
 // (e = EPI_NONE, EPI_ADD or EPI_DGELU_CS) has the token rows as M: a row of dY that is all zeros gives a row of zeros, so only the 32-row
 // blocks that hold a live row are computed -- an M-tile is eight consecutive entries of the live-block list (GemmArgs::row_blk) instead
@@ -644,6 +650,8 @@ constexpr int STAGE_BYTES = 16 * 64 * 4;                   // epilogue staging s
 // EPI_NONE_BLK: a k-slab's live-block mask is one 32-bit word per lane, two bits per k-tile -- 1024 k-tiles at the most.  The one statement
 // of that limit (the host asks it in gemm_core and in ia_gemm_wgrad_rows_filters): a longer k-slab runs every row.
 inline bool blk_mask_fits(int slab_ktiles) { return slab_ktiles <= 64 * 32 / 2; }
+// EPI_NONE_STP: four bits per k-tile -- 512 k-tiles at the most; a longer k-slab takes the block walk
+inline bool step_mask_fits(int slab_ktiles) { return slab_ktiles <= 64 * 32 / 4; }
 constexpr uint32_t OOB_HALF = 0x80000000u;                 // behind every buffer window (< 2 GiB), and three piece advances on top do not wrap
 constexpr int LDS_BYTES = 2 * 2 * TILE_BYTES + 8 * STAGE_BYTES;   // 128 KiB k-tile double buffer (A | B, twice) + 4 x 8 KiB = all 160 KiB of the CU
 
@@ -737,7 +745,10 @@ IA_DEV void read_frag(Op<KS>& f, int j, const uint32_t (&base)[4], uint32_t bufo
 // the 16 MFMAs of one k-step on the fragment sets fa / fb; filler(i) is issued right behind MFMA i and pinned there
 // FRESH (the first k-step of a tile's peeled first trip): the MFMAs take a zero C operand, so nothing has to clear the accumulators
 // (two 16x16x32 MFMAs in place of each 32x32x16 ran 8-14 % slower: the MFMA shape is not what separates this loop from the vendor's)
-template <bool FRESH, typename FA, typename FB, typename Filler>
+// PIN (the walk forms, whose fillers are long runs of scalar arithmetic): each MFMA's result passes through an empty volatile asm in
+// front of its filler -- an MFMA has no side effect, and instruction selection is otherwise free to emit it behind fillers that have
+// one (with the walk in the gaps the first MFMA of the trip came out behind 114 instructions).  The other forms are not touched.
+template <bool FRESH, bool PIN = false, typename FA, typename FB, typename Filler>
 IA_DEV void mfma_step(f32x16 (&acc)[4][4], const FA& fa, const FB& fb, Filler&& filler) {
   bf16x8 va[4], vb[4];
 #pragma unroll
@@ -750,6 +761,7 @@ IA_DEV void mfma_step(f32x16 (&acc)[4][4], const FA& fa, const FB& fb, Filler&& 
         const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vb[ni], va[mi], z, 0, 0, 0);
       } else acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vb[ni], va[mi], acc[mi][ni], 0, 0, 0);
+      if constexpr (PIN) asm volatile("" : "+a"(acc[mi][ni]));
       filler(mi * 4 + ni);
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -867,28 +879,40 @@ struct LiveWalk {
   int wi, cur;        // the open word; the last index handed out
 };
 IA_DEV void live_start(LiveWalk& k, uint32_t mv) { k.rest = __ballot(mv != 0u); k.w = 0u; k.wi = 0; k.cur = -1; }
-IA_DEV int live_next(LiveWalk& k, uint32_t mv) {
+// One step in two halves, so that the k loop can give each a MFMA gap of its own: live_open opens the next word with a set bit when the
+// open one is used up, live_take hands out the open word's lowest bit.
+IA_DEV void live_open(LiveWalk& k, uint32_t mv) {
   const bool open = k.w == 0u, any = k.rest != 0ull;
   const int wi = open ? (any ? __builtin_ctzll(k.rest) : 0) : k.wi;
   const uint32_t fetched = __builtin_amdgcn_readlane(mv, wi);
-  const uint32_t w = open ? (any ? fetched : 0u) : k.w;
+  k.w = open ? (any ? fetched : 0u) : k.w;
   k.rest = open ? (k.rest & (k.rest - 1ull)) : k.rest;
-  const int idx = w != 0u ? wi * 32 + __builtin_ctz(w) : k.cur + 1;
-  k.w = w & (w - 1u); k.wi = wi; k.cur = idx;
+  k.wi = wi;
+}
+IA_DEV int live_take(LiveWalk& k) {
+  const uint32_t w = k.w;
+  const int bit = __builtin_ctz(w | 0x80000000u);      // (w == 0: unused)
+  const int idx = w != 0u ? k.wi * 32 + bit : k.cur + 1;
+  // (the lowest set bit cleared by its index: `w & (w - 1)` next to `w == 0` becomes a subtract-with-borrow on the VALU)
+  k.w = w & ~(1u << bit) & (w != 0u ? 0xFFFFFFFFu : 0u); k.cur = idx;
   return idx;
 }
+IA_DEV int live_next(LiveWalk& k, uint32_t mv) { live_open(k, mv); return live_take(k); }
 
 // BLK (EPI_NONE_BLK; both operands k-strided): the k loop runs over the n_blk set bits of live_mv (the slab's live 32-row blocks, see
 // LiveWalk) instead of k-tiles 0 .. n_tiles-1 of the slab -- two blocks per trip (n_tiles = ceil(n_blk / 2)); the upper half of the
 // last trip of an odd count goes out of range and arrives as zeros.
 // ROWS (k-contiguous A): piece j of A starts at row offset ro.o[j] (a scalar, where j * stepA sits otherwise) of a window over all of A.
 // SLAB: ro.o[j] is this WAVE's slab of piece j -- the lane offset keeps the row inside the slab (row & 7) and the swizzle of the LDS row.
-template <bool AKS, bool BKS, int PEND, bool PEEL_OK = true, bool BLK = false, bool ROWS = false, bool SLAB = false>
+template <bool AKS, bool BKS, int PEND, bool PEEL_OK = true, bool BLK = false, bool ROWS = false, bool SLAB = false, bool STP = false>
 IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdgpu_buffer_rsrc_t rsA, __amdgpu_buffer_rsrc_t rsB, int xa, int xb,
                       int kt0, int ktaA0, int ktaB0, int n_tiles, int nk_all, int wm, int wn, int wave, int lane, bool prologue_only,
                       bool stores_in_flight, uint32_t live_mv = 0u, RowOff ro = RowOff{}, int n_blk = 0) {
   static_assert(!ROWS || !AKS, "the row remap moves the pieces of a k-contiguous A");
   static_assert(!BLK || (AKS && BKS), "the live-block walk sets the running lane offsets of two k-strided operands");
+  static_assert(!STP || BLK, "the 16-row step walk is a form of the live-block walk");
+  // BLK: a trip's k-tile is made of NQ parts of the walk (two 32-row blocks, or STP: four 16-row steps), PP DMA pieces of 8 k rows each
+  constexpr int NQ = STP ? 4 : 2, PP = 8 / NQ, QSH = STP ? 2 : 1;
   constexpr bool ROUND = !AKS && !BKS;      // the k loop's schedule (below)
   const int li = lane & 31;
   const int gt = wave * 64 + lane;                  // thread index inside the workgroup (0..255)
@@ -907,12 +931,13 @@ IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdg
   char* const my_part = smem + wave * 1024;
   const int dbg = IA_GEMM_DBG_HOOKS ? p.dbg : 0;       // the timing ablations (IA_GEMM_DBG bits 2 / 4 / 16) exist in tools builds only
   const bool dma_on = !(dbg & 2);
-  // BLK: the slab-relative indices of the first four live blocks (the prologue's two k-tiles: lower half, upper half)
+  // BLK: the slab-relative indices of the first 2 NQ live parts (the prologue's two k-tiles, part by part)
   [[maybe_unused]] LiveWalk lw;
-  [[maybe_unused]] int live0 = 0, live0h = 0, live1 = 0, live1h = 0;
+  [[maybe_unused]] int live01[2][NQ] = {};
   if constexpr (BLK) {
     live_start(lw, live_mv);
-    live0 = live_next(lw, live_mv); live0h = live_next(lw, live_mv); live1 = live_next(lw, live_mv); live1h = live_next(lw, live_mv);
+#pragma unroll
+    for (int t = 0; t < 2 * NQ; ++t) live01[t / NQ][t % NQ] = live_next(lw, live_mv);
   }
 
   // piece i (0..7: A, 8..15: B) of k-tile u -> buffer u & 1.  Branch-free (a branch next to the accumulator updates makes hipcc copy
@@ -923,12 +948,13 @@ IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdg
     const int j = i & 7;
     char* dst = my_part + (isB ? TILE_BYTES : 0) + (u & 1) * 2 * TILE_BYTES + j * 4096;
     if constexpr (BLK) {
-      // pieces 0 .. 3: rows 0 .. 31 of the lower half's block, pieces 4 .. 7 of the upper half's; a half the slab has no block for goes out
-      // of range (zeros).  The whole row address sits in the lane offset: the partial last block of K ends at the window's end.
-      const int h = j >> 2;
-      const int b = u == 0 ? (h ? live0h : live0) : (h ? live1h : live1);
-      const uint32_t soff = (uint32_t)b * ((isB ? kstepB : kstepA) >> 1) + (uint32_t)(j & 3) * (isB ? stepB : stepA);
-      const uint32_t off = (dma_on && 2 * u + h < n_blk) ? (isB ? voffB : voffA) + soff : OOB;
+      // pieces 0 .. 3: rows 0 .. 31 of the lower half's block, pieces 4 .. 7 of the upper half's (STP: pieces 2q and 2q + 1 are the 16 rows
+      // of the trip's step q); a part the slab has no block / step for goes out of range (zeros).  The whole row address sits in the
+      // lane offset: the partial last block / step of K ends at the window's end.
+      const int h = j / PP;
+      const int b = live01[u & 1][h];
+      const uint32_t soff = (uint32_t)b * ((isB ? kstepB : kstepA) >> QSH) + (uint32_t)(j % PP) * (isB ? stepB : stepA);
+      const uint32_t off = (dma_on && NQ * u + h < n_blk) ? (isB ? voffB : voffA) + soff : OOB;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(isB ? rsB : rsA, IA_LDS(dst), 16, off, 0, 0, 0);
       return;
     }
@@ -969,21 +995,17 @@ IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdg
 
   // second schedule (a k-strided operand): in-loop pieces of k-tile u+2; the k-strided operand's k-tile advance lives in a running lane offset
   uint32_t runA = voffA + (uint32_t)((dbg & 4) ? 0 : ktaA0 + 2) * kstepA, runB = voffB + (uint32_t)((dbg & 4) ? 0 : ktaB0 + 2) * kstepB;
-  // BLK: four running lane offsets -- each operand's lower and upper half (blocks 4 and 5 of the walk to begin with)
-  [[maybe_unused]] uint32_t runAh = 0u, runBh = 0u;
-  if constexpr (BLK) {
-    int live2 = 2, live2h = 0;
-    if (!prologue_only) { live2 = live_next(lw, live_mv); live2h = live_next(lw, live_mv); }      // (the prologue call stops at the first four)
-    runA = voffA + (uint32_t)live2 * (kstepA >> 1); runB = voffB + (uint32_t)live2 * (kstepB >> 1);
-    runAh = 5 < n_blk ? voffA + (uint32_t)live2h * (kstepA >> 1) : OOB_HALF; runBh = 5 < n_blk ? voffB + (uint32_t)live2h * (kstepB >> 1) : OOB_HALF;
-  }
+  // BLK: NQ running lane offsets per operand, one per part of the trip's k-tile.  They are set under k-step 1 of the trip whose
+  // k-steps 2 and 3 send them out (walk_open, walk_take, walk_offsets): nothing of the walk stands in front of the trip's first MFMA or behind its last.
+  [[maybe_unused]] uint32_t runQA[NQ] = {}, runQB[NQ] = {};
+  [[maybe_unused]] int nextQ[NQ] = {};           // the parts' indices of the walk between walk_take and walk_offsets
   auto dma_run = [&](int u, int i) {
     const bool isB = i >= 8;
     if (!(isB ? BKS : AKS) || (dbg & 4)) { dma_piece(u, i); return; }
     const int j = i & 7;
     char* dst = my_part + (isB ? TILE_BYTES : 0) + (u & 1) * 2 * TILE_BYTES + j * 4096;
     if constexpr (BLK) {
-      const uint32_t off = (j < 4 ? (isB ? runB : runA) : (isB ? runBh : runAh)) + (uint32_t)(j & 3) * (isB ? stepB : stepA);
+      const uint32_t off = (isB ? runQB[j / PP] : runQA[j / PP]) + (uint32_t)(j % PP) * (isB ? stepB : stepA);
       __builtin_amdgcn_raw_ptr_buffer_load_lds(isB ? rsB : rsA, IA_LDS(dst), 16, dma_on ? off : OOB, 0, 0, 0);
       return;
     }
@@ -1080,21 +1102,52 @@ IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdg
   tie2<0>(a0, b0);
   return;
   }
+  // BLK: the walk, in MFMA gaps that carry nothing else -- the parts NQ (u + 2) .. NQ (u + 2) + NQ - 1 of the walk are k-tile u + 2,
+  // whose pieces leave under k-steps 2 and 3 of trip u.  Their indices are taken under k-step 2 of trip u - 1 (the even gaps, between
+  // the DMA pieces; in front of the loop for trip 0) and turned into lane offsets under the second half of k-step 1 of trip u.  (In the
+  // gaps of k-step 0 of trip u, beside the LDS reads that feed k-step 1, the same work cost 0.6 % of the step: ab_wgrad_ksteps.txt.)  walk_open() and walk_take(q): the two halves of one step of
+  // the walk (LiveWalk); walk_offsets(q): part q's two lane offsets.  A part past the count goes out of range through its SCALAR term (OOB_HALF on top of a lane offset inside the
+  // window does not wrap): one v_add per offset, no select on a vector.  Part 0 needs no test: where k-tile u + 2 has no part at all
+  // nobody reads its buffer (the dense loop's look-ahead reads real rows there too).
+  // Both are pure arithmetic, which instruction selection would gather at the top of the trip whatever gap the source names: each
+  // starts from and ends in an empty volatile asm on its inputs and results, which keeps it between the gap's neighbours.
+  [[maybe_unused]] auto walk_open = [&]() {
+    asm volatile("" : "+s"(lw.rest), "+s"(lw.w), "+s"(lw.wi));
+    live_open(lw, live_mv);
+    asm volatile("" : "+s"(lw.rest), "+s"(lw.w), "+s"(lw.wi));
+  };
+  [[maybe_unused]] auto walk_take = [&](int q) {
+    asm volatile("" : "+s"(lw.w), "+s"(lw.wi), "+s"(lw.cur));
+    nextQ[q] = live_take(lw);
+    asm volatile("" : "+s"(lw.w), "+s"(lw.cur), "+s"(nextQ[q]));
+  };
+  [[maybe_unused]] auto walk_offsets = [&](int q) {
+    asm volatile("" : "+s"(nextQ[q]));
+    const bool has = q == 0 || NQ * (u + 2) + q < n_blk;
+    const uint32_t sa = has ? (uint32_t)nextQ[q] * (kstepA >> QSH) : OOB_HALF, sb = has ? (uint32_t)nextQ[q] * (kstepB >> QSH) : OOB_HALF;
+    runQA[q] = voffA + sa; runQB[q] = voffB + sb;
+    asm volatile("" : "+v"(runQA[q]), "+v"(runQB[q]));
+  };
+  if constexpr (BLK) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) nextQ[q] = live_next(lw, live_mv);      // k-tile 2's parts; every trip then walks for the one behind it
+  }
   do {
     const uint32_t bn = bo ^ (uint32_t)(2 * TILE_BYTES);
     // k-step 0: sets 1 and 2 requested, one fragment behind each MFMA
     tie<0>(a0); tie<0>(b0);
-    mfma_step<false>(acc, a0, b0, [&](int i) {
+    mfma_step<false, BLK>(acc, a0, b0, [&](int i) {
       if (i < 4) read_frag<1>(a1, i, baseA, bo);
       else if (i < 8) read_frag<1>(b1, i - 4, baseB, bo);
       else if (i < 12) read_frag<2>(a2, i - 8, baseA, bo);
       else read_frag<2>(b2, i - 12, baseB, bo);
     });
-    // k-step 1: set 3 requested in the first half
+    // k-step 1: set 3 requested in the first half; BLK: this trip's offsets in the second
     tie<NR15>(a1); tie<NR15>(b1);
-    mfma_step<false>(acc, a1, b1, [&](int i) {
+    mfma_step<false, BLK>(acc, a1, b1, [&](int i) {
       if (i < 4) read_frag<3>(a3, i, baseA, bo);
       else if (i < 8) read_frag<3>(b3, i - 4, baseB, bo);
+      if constexpr (BLK) { if (i >= 8 && (i - 8) % (8 / NQ) == 0) walk_offsets((i - 8) / (8 / NQ)); }
     });
     // every fragment of k-tile u is in registers: once all waves are here its buffer is free for k-tile u+2
     tie<0>(a2); tie<0>(b2); tie<0>(a3); tie<0>(b3);
@@ -1103,15 +1156,18 @@ IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdg
     __builtin_amdgcn_sched_barrier(0);
     // k-step 2: the A half of k-tile u+2, one piece per two MFMAs (one per three, spread over k-steps 2, 3 and the next trip's
     // k-step 0, measured data gradient +-0, weight gradient -0.9 %: what helps the forward forms does not help these)
-    mfma_step<false>(acc, a2, b2, [&](int i) {
+    mfma_step<false, BLK>(acc, a2, b2, [&](int i) {
       if (i & 1) dma_run(u + 2, i >> 1);
+      if constexpr (BLK) {      // the NEXT trip's walk, one half per gap that carries no DMA piece
+        if (i % (8 / NQ) == 0) { const int h = i / (8 / NQ); if (h % 2 == 0) walk_open(); else walk_take(h / 2); }
+      }
     });
     // k-step 3: k-tile u+1 has landed (this wave's share: all but the 8 pieces just issued; everybody's: the barrier)
     asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     if (!(dbg & 16)) __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-    mfma_step<false>(acc, a3, b3, [&](int i) {
+    mfma_step<false, BLK>(acc, a3, b3, [&](int i) {
       if (i & 1) dma_run(u + 2, 8 + (i >> 1));
       if (!(i & 1)) {
         if (i < 8) read_frag<0>(a0, i >> 1, baseA, bn);
@@ -1122,14 +1178,7 @@ IA_DEV void main_loop(const GemmArgs& p, char* smem, f32x16 (&acc)[4][4], __amdg
     ++u;
     // one running lane offset per k-strided operand, opaque to the loop optimiser: left alone it keeps SIXTEEN induction variables
     // (one per piece) and bumps them all in the last MFMA gap of the trip
-    if constexpr (BLK) {       // the next two live blocks (trip u + 2: blocks 2u + 4 and 2u + 5 of the walk); past the count the upper half reads zeros
-      const int bl = live_next(lw, live_mv), bh = live_next(lw, live_mv);
-      const bool has_h = 2 * u + 5 < n_blk;
-      runA = voffA + (uint32_t)bl * (kstepA >> 1); asm volatile("" : "+v"(runA));
-      runB = voffB + (uint32_t)bl * (kstepB >> 1); asm volatile("" : "+v"(runB));
-      runAh = has_h ? voffA + (uint32_t)bh * (kstepA >> 1) : OOB_HALF; asm volatile("" : "+v"(runAh));
-      runBh = has_h ? voffB + (uint32_t)bh * (kstepB >> 1) : OOB_HALF; asm volatile("" : "+v"(runBh));
-    } else {
+    if constexpr (!BLK) {      // (BLK: the walk sets its offsets inside the trip)
       if (AKS) { runA += kstepA; asm volatile("" : "+v"(runA)); }
       if (BKS) { runB += kstepB; asm volatile("" : "+v"(runB)); }
     }
@@ -1382,11 +1431,12 @@ IA_DEV void drain_half(const GemmArgs& p, f32x16 (&acc)[4][4], int m0, int n0, c
 }
 
 // EPI_ = EPI_NONE_BLK: the plain epilogue behind a k loop over the live 32-row blocks only, two to a trip (GemmArgs::live_blk, an
-// ia_kblock_mask; weight-gradient form).  A value of the epilogue parameter, not a parameter of its own: the other instantiations keep
+// ia_kblock_mask; weight-gradient form); EPI_NONE_STP: over the live 16-row steps, four to a trip (live_blk is an ia_kstep_mask).  A value of the epilogue parameter, not a parameter of its own: the other instantiations keep
 // their names in profiles and traces.
 template <bool AKS, bool BKS, int EPI_, bool OUTF32>
 __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
-  constexpr bool BLK = EPI_ == EPI_NONE_BLK;
+  constexpr bool STP = EPI_ == EPI_NONE_STP;      // the same walk over 16-row steps, four to a trip
+  constexpr bool BLK = EPI_ == EPI_NONE_BLK || STP;
   constexpr bool ROWS = EPI_ >= EPI_ROWS;
   constexpr bool SLAB = EPI_ >= EPI_ROWS + EPI_SLABS;      // the remap in 8-row slabs (EPI_SLABS)
   constexpr int EPI = BLK ? (int)EPI_NONE : (ROWS ? EPI_ - EPI_ROWS - (SLAB ? EPI_SLABS : 0) : EPI_);
@@ -1440,14 +1490,16 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
   [[maybe_unused]] int n_blk = 0;
   if constexpr (BLK) {
     // block bits 2 kt0 .. 2 (kt0 + n_tiles) - 1 of the mask, clipped to the blocks K has; n_tiles becomes the number of PAIRS of live blocks
-    const int nb_all = (p.K + 31) >> 5, nw = (nb_all + 31) >> 5, first = 2 * kt0 + 32 * lane0, wlo = first >> 5, sh = first & 31;
-    const int left = min(2 * (kt0 + n_tiles), nb_all) - first;
+    // (STP: step bits 4 kt0 .. 4 (kt0 + n_tiles) - 1 of an ia_kstep_mask, clipped to the steps K has; the number of live steps by FOURS)
+    constexpr int NQ = STP ? 4 : 2, PSH = STP ? 4 : 5;
+    const int nb_all = (p.K + (1 << PSH) - 1) >> PSH, nw = (nb_all + 31) >> 5, first = NQ * kt0 + 32 * lane0, wlo = first >> 5, sh = first & 31;
+    const int left = min(NQ * (kt0 + n_tiles), nb_all) - first;
     const uint32_t lo = wlo < nw ? p.live_blk[wlo] : 0u, hi = wlo + 1 < nw ? p.live_blk[wlo + 1] : 0u;
     live_mv = sh ? (lo >> sh) | (hi << (32 - sh)) : lo;
     live_mv = left >= 32 ? live_mv : (left > 0 ? live_mv & ((1u << left) - 1u) : 0u);
     for (uint64_t rest = __ballot(live_mv != 0u); rest; rest &= rest - 1ull)
       n_blk += __builtin_popcount(__builtin_amdgcn_readlane(live_mv, __builtin_ctzll(rest)));
-    n_tiles = (n_blk + 1) >> 1;
+    n_tiles = (n_blk + NQ - 1) / NQ;
   }
   constexpr int PEND = 2 * (16 * epi_stores_per_call<EPI, OUTF32>() + epi_extra_stores<EPI>());   // store instructions of one full-tile epilogue, per wave
   auto coords = [&](int tile, int& bm, int& bn) {
@@ -1468,7 +1520,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
     const uint64_t oa = (uint64_t)(AKS ? kt0 * BK : (ROWS ? 0 : bm * BM)) * p.lda, ob = (uint64_t)(BKS ? kt0 * BK : bn * BN) * p.ldb;
     // (the bf16 bias form keeps 64 bias values in registers across the main loop -- 468 of 512: the peeled first trip spilled there)
     constexpr bool PEEL_OK = !(EPI == EPI_BIAS && !OUTF32 && !BKS);
-    main_loop<AKS, BKS, PEND, PEEL_OK, BLK, ROWS, SLAB>(p, smem, acc, rsrc_at(p.A, p.a_bytes, oa), rsrc_at(p.B, p.b_bytes, ob), AKS ? bm * BM : 0, BKS ? bn * BN : 0, kt0,
+    main_loop<AKS, BKS, PEND, PEEL_OK, BLK, ROWS, SLAB, STP>(p, smem, acc, rsrc_at(p.A, p.a_bytes, oa), rsrc_at(p.B, p.b_bytes, ob), AKS ? bm * BM : 0, BKS ? bn * BN : 0, kt0,
                               AKS ? 0 : kt0, BKS ? 0 : kt0, n_tiles, nk_all, wm, wn, wave, lane, prologue_only, stores_in_flight, live_mv, ro, n_blk);
   };
 
@@ -1934,12 +1986,14 @@ enum KernelForm {
   FORM_ROWS_T256W,       // the row remap (32-row blocks) of FORM_T256W ...
   FORM_ROWS_T256LA,      // ... and of FORM_T256LA
   FORM_WGRAD_KBLOCKS,    // the live-block weight gradient
+  FORM_WGRAD_KSTEPS,     // the live-step weight gradient
   FORM_SLABS_T256W,      // the slab remap of FORM_T256W ...
   FORM_SLABS_T256LA,     // ... and of FORM_T256LA
   FORM_COUNT
 };
 
-// kind: what a.row_blk points at (SLABS: a slab list, ia_row_slabs; else a list of 32-row blocks); a.live_blk is always an ia_kblock_mask
+// kind: what a.row_blk points at (SLABS: a slab list, ia_row_slabs; else a list of 32-row blocks), and what a.live_blk does (KSTEPS: an
+// ia_kstep_mask; else an ia_kblock_mask)
 template <bool AKS, bool BKS, int EPI, bool OUTF32>
 int launch(GemmArgs a, bool big, hipStream_t st, IaRowFilter::Kind kind = IaRowFilter::NONE) {
   constexpr int vid = AKS * 1000 + BKS * 100 + EPI * 10 + (OUTF32 ? 1 : 0);
@@ -1964,7 +2018,8 @@ int launch(GemmArgs a, bool big, hipStream_t st, IaRowFilter::Kind kind = IaRowF
     static bool attr_set[FORM_COUNT] = {};
     KernelForm form = FORM_T256W;
     if constexpr (WGRAD) {
-      if (a.live_blk) { kern = t256w::gemm_kernel<true, true, EPI_NONE_BLK, true>; form = FORM_WGRAD_KBLOCKS; }
+      if (a.live_blk && kind == IaRowFilter::KSTEPS) { kern = t256w::gemm_kernel<true, true, EPI_NONE_STP, true>; form = FORM_WGRAD_KSTEPS; }
+      else if (a.live_blk) { kern = t256w::gemm_kernel<true, true, EPI_NONE_BLK, true>; form = FORM_WGRAD_KBLOCKS; }
     }
     // plain NT form, several tiles per workgroup, static order: the look-ahead kernel (t256la; IA_GEMM_LA=0 keeps t256w)
     if constexpr (!AKS && !BKS && EPI == EPI_NONE && !OUTF32) {
@@ -2402,6 +2457,42 @@ extern "C" int ia_kblock_mask_host(const uint8_t* row_live, int M_rows, uint32_t
   for (int t = 0; t < nb; ++t) mask[t >> 5] |= rows_live<32>(row_live, M_rows, t) << (t & 31);
   return IA_OK;
 }
+// ... and of its walk over 16-row steps: bit s = OR of row_live over rows 16 s .. 16 s + 15 (clipped to M) (ia_kstep_mask).  The same
+// per-bit function, the same launch shape.
+namespace {
+__global__ __launch_bounds__(256) void kstep_mask_kernel(const uint8_t* __restrict__ row_live, int M, int ns, uint32_t* __restrict__ mask) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  const uint64_t v = __ballot(b < ns && rows_live<16>(row_live, M, b));
+  if ((threadIdx.x & 31) == 0 && b < ns) mask[b >> 5] = (uint32_t)(v >> (threadIdx.x & 32));
+}
+// the block mask of a step mask (block t = steps 2t and 2t + 1), for a launch whose k-slab is too long for the step walk: one thread per
+// block bit, the same ballot and plain stores
+__global__ __launch_bounds__(256) void kblock_of_ksteps_kernel(const uint32_t* __restrict__ steps, int ns, int nb, uint32_t* __restrict__ mask) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  bool live = false;
+  if (b < nb) {
+    const uint32_t w = steps[(2 * b) >> 5] >> ((2 * b) & 31);      // (steps 2b and 2b + 1 share a word; a step behind ns has a zero bit)
+    live = (w & (2 * b + 1 < ns ? 3u : 1u)) != 0u;
+  }
+  const uint64_t v = __ballot(live);
+  if ((threadIdx.x & 31) == 0 && b < nb) mask[b >> 5] = (uint32_t)(v >> (threadIdx.x & 32));
+}
+}  // namespace
+extern "C" size_t ia_kstep_mask_bytes(int M_rows) { return M_rows <= 0 ? 0 : (size_t)(((M_rows + 15) / 16 + 31) / 32) * sizeof(uint32_t); }
+extern "C" int ia_kstep_mask(const uint8_t* row_live, int M_rows, uint32_t* mask, hipStream_t stream) {
+  (void)hipGetLastError();
+  if (!row_live || !mask || M_rows <= 0) return IA_ERR_ARG;
+  const int ns = (M_rows + 15) / 16;
+  hipLaunchKernelGGL(kstep_mask_kernel, dim3((ns + 255) / 256), dim3(256), 0, stream, row_live, M_rows, ns, mask);
+  return ia_check_launch();
+}
+extern "C" int ia_kstep_mask_host(const uint8_t* row_live, int M_rows, uint32_t* mask) {
+  if (!row_live || !mask || M_rows <= 0) return IA_ERR_ARG;
+  const int ns = (M_rows + 15) / 16;
+  for (int w = 0; w < (ns + 31) / 32; ++w) mask[w] = 0u;
+  for (int t = 0; t < ns; ++t) mask[t >> 5] |= rows_live<16>(row_live, M_rows, t) << (t & 31);
+  return IA_OK;
+}
 
 // ---- one descriptor for all of them (IaRowFilter, common.h): the list of a kind, by size and by builder
 size_t ia_row_filter_bytes(IaRowFilter::Kind kind, int M) {
@@ -2411,6 +2502,7 @@ size_t ia_row_filter_bytes(IaRowFilter::Kind kind, int M) {
     case IaRowFilter::PACKED: return ia_row_groups_packed_bytes(M);
     case IaRowFilter::SLABS: return ia_row_slabs_bytes(M);
     case IaRowFilter::KBLOCKS: return ia_kblock_mask_bytes(M);
+    case IaRowFilter::KSTEPS: return ia_kstep_mask_bytes(M);
     case IaRowFilter::NONE: break;
   }
   return 0;
@@ -2422,6 +2514,7 @@ int ia_row_filter_build(IaRowFilter::Kind kind, const uint8_t* row_live, int M, 
     case IaRowFilter::PACKED: return ia_row_groups_packed(row_live, M, (int*)dst, stream);
     case IaRowFilter::SLABS: return ia_row_slabs(row_live, M, (int*)dst, stream);
     case IaRowFilter::KBLOCKS: return ia_kblock_mask(row_live, M, (uint32_t*)dst, stream);
+    case IaRowFilter::KSTEPS: return ia_kstep_mask(row_live, M, (uint32_t*)dst, stream);
     case IaRowFilter::NONE: break;
   }
   return IA_ERR_ARG;
@@ -2463,9 +2556,28 @@ int ia_gemm_dgrad_filtered(const void* dY, int ldy, const void* W, int w_kstride
   c.filter = filter; c.filter.fill = true;      // not every consumer of a data gradient filters its rows
   return gemm_core(c, stream);
 }
+extern "C" int ia_gemm_wgrad_walk(int N_out, int N_in, int M_rows);
 int ia_gemm_wgrad_filtered(const void* dY, int ldy, const void* X, int ldx, float* dW, int ldw, int N_out, int N_in, int M_rows, IaRowFilter filter,
                            int accumulate, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-  if (filter.kind != IaRowFilter::NONE && filter.kind != IaRowFilter::KBLOCKS) return IA_ERR_UNSUPPORTED;
+  if (filter.kind != IaRowFilter::NONE && filter.kind != IaRowFilter::KBLOCKS && filter.kind != IaRowFilter::KSTEPS) return IA_ERR_UNSUPPORTED;
+  // A step mask on a shape whose k-slab is too long for the step walk (ia_gemm_wgrad_walk says 1): the block walk, from the block mask
+  // of the step mask, built behind the split-K partials where the workspace has the room ia_gemm_wgrad_rows_workspace_bytes asks for
+  // (one small launch); without that room, every row.
+  if (filter.kind == IaRowFilter::KSTEPS && filter.list && ia_gemm_wgrad_walk(N_out, N_in, M_rows) == 1) {
+    const size_t front = al256(ia_gemm_workspace_bytes(N_out, N_in, M_rows, 1));
+    const uint32_t* const steps = (const uint32_t*)filter.list;
+    filter = IaRowFilter{};
+    if (workspace && workspace_bytes >= front + ia_kblock_mask_bytes(M_rows)) {
+      uint32_t* const bm = (uint32_t*)((char*)workspace + front);
+      const int ns = (M_rows + 15) / 16, nb = (M_rows + 31) / 32;
+      (void)hipGetLastError();
+      hipLaunchKernelGGL(kblock_of_ksteps_kernel, dim3((nb + 255) / 256), dim3(256), 0, stream, steps, ns, nb, bm);
+      int rc = ia_check_launch();
+      if (rc) return rc;
+      filter = IaRowFilter{IaRowFilter::KBLOCKS, bm};
+      workspace_bytes = front;
+    }
+  }
   GemmCall c{dY, 1, ldy, X, 1, ldx, dW, 1, ldw, N_out, N_in, M_rows};
   c.accumulate = accumulate; c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.filter = filter;
   return gemm_core(c, stream);
@@ -2483,6 +2595,14 @@ extern "C" int ia_gemm_dgrad_packed(const void* dY, int ldy, const void* W, int 
 extern "C" int ia_gemm_wgrad_blocks(const void* dY, int ldy, const void* X, int ldx, float* dW, int ldw, int N_out, int N_in, int M_rows,
                                     const uint32_t* kblock_mask, int accumulate, void* workspace, size_t workspace_bytes, hipStream_t stream) {
   return ia_gemm_wgrad_filtered(dY, ldy, X, ldx, dW, ldw, N_out, N_in, M_rows, IaRowFilter{IaRowFilter::KBLOCKS, kblock_mask}, accumulate, workspace,
+                                workspace_bytes, stream);
+}
+
+// ... and over the live 16-row steps of a prebuilt ia_kstep_mask (NULL: every row), four to a k-tile.  Bit-identical to the call above on
+// the same rows.  A shape whose k-slabs are too long for the step walk (ia_gemm_wgrad_walk) takes the block walk.
+extern "C" int ia_gemm_wgrad_steps(const void* dY, int ldy, const void* X, int ldx, float* dW, int ldw, int N_out, int N_in, int M_rows,
+                                   const uint32_t* kstep_mask, int accumulate, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  return ia_gemm_wgrad_filtered(dY, ldy, X, ldx, dW, ldw, N_out, N_in, M_rows, IaRowFilter{IaRowFilter::KSTEPS, kstep_mask}, accumulate, workspace,
                                 workspace_bytes, stream);
 }
 
@@ -2591,6 +2711,15 @@ extern "C" int ia_gemm_wgrad_rows_filters(int N_out, int N_in, int M_rows) {
   const int nk = (M_rows + BK - 1) / BK;
   return pl.big && t256w::blk_mask_fits((nk + pl.splits - 1) / pl.splits) ? 1 : 0;
 }
+// which walk a filtered weight gradient of this shape takes: 2 = the live 16-row steps (given a step mask: ia_gemm_wgrad_steps, the engine),
+// 1 = the live 32-row blocks (the k-slab is too long for the step walk's mask words, step_mask_fits), 0 = every row
+extern "C" int ia_gemm_wgrad_walk(int N_out, int N_in, int M_rows) {
+  if (N_out <= 0 || N_in <= 0 || M_rows <= 0) return 0;
+  const Plan pl = make_plan(N_out, N_in, M_rows, true);
+  const int nk = (M_rows + BK - 1) / BK, slab = (nk + pl.splits - 1) / pl.splits;
+  if (!pl.big) return 0;
+  return t256w::step_mask_fits(slab) ? 2 : (t256w::blk_mask_fits(slab) ? 1 : 0);
+}
 // the weight gradient over the live 32-row blocks: the split-K partials in front of the workspace, the mask behind them
 extern "C" int ia_gemm_wgrad_rows(const void* dY, int ldy, const void* X, int ldx, float* dW, int ldw, int N_out, int N_in, int M_rows,
                                   const uint8_t* row_live, int accumulate, void* workspace, size_t workspace_bytes, hipStream_t stream) {
@@ -2692,13 +2821,15 @@ static int gemm_core(const GemmCall& c, hipStream_t stream) {
   // What the filter holds: a mask of the live k (weight gradient), or a list of the live rows (the other forms).  Which (kind, epilogue)
   // pairs exist is the business of ia_gemm_fwd_form / ia_gemm_dgrad_form; here a filter only ever falls back to every row.
   const IaRowFilter::Kind kind = c.filter.kind;
-  const bool k_mask = kind == IaRowFilter::KBLOCKS, row_list = kind != IaRowFilter::NONE && !k_mask;
+  const bool k_steps = kind == IaRowFilter::KSTEPS, k_mask = kind == IaRowFilter::KBLOCKS || k_steps, row_list = kind != IaRowFilter::NONE && !k_mask;
   // the live-block mask: the 256-wide weight-gradient kernel only, one mask word per lane and k-slab (anything else runs dense).
   // GemmArgs::live_blk shares the slot of GemmArgs::bias (filled above from the caller's argument): in the weight-gradient form, whose
   // 256-wide kernel reads the slot as the mask, it is overwritten HERE for every caller -- a stray bias passed with IA_EPI_NONE, the
   // shifted views of ia_gemm_view -- so the kernel sees a mask or NULL, never a bias.  launch<true, true, EPI_NONE, true> is reached
   // from this function only; a new call site that fills GemmArgs for this form must do the same.
-  if (wgrad_form) g.live_blk = (k_mask && big && t256w::blk_mask_fits(g.nk_per_split)) ? (const uint32_t*)c.filter.list : nullptr;
+  // (a step mask on a slab step_mask_fits refuses runs every row HERE: ia_gemm_wgrad_filtered hands such a shape a block mask instead)
+  if (wgrad_form)
+    g.live_blk = (k_mask && big && (k_steps ? t256w::step_mask_fits(g.nk_per_split) : t256w::blk_mask_fits(g.nk_per_split))) ? (const uint32_t*)c.filter.list : nullptr;
   // the list of the row-remapped forms (C2 has C's pitch, so dgrad_rows_fit covers it): a list or NULL
   const bool fwd_epi = !bks && (epilogue == EPI_BIAS || epilogue == EPI_BIAS_GELU || epilogue == EPI_BIAS_GELU_ACT || epilogue == EPI_BIAS_ADD);
   g.row_blk = nullptr; g.rows_fill = c.filter.fill ? 1 : 0; g.fill_m = M; g.rows_guarded = c.tail ? 1 : 0;

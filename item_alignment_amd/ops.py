@@ -93,6 +93,29 @@ def gemm_wgrad_blocks(dy, x, mask=None, *, out=None, accumulate=False):
     return out
 
 
+def kstep_mask(row_live):
+    """bit (s & 31) of word s >> 5 = any(row_live[16s : 16s + 16]) (uint8 [M] on the GPU) -> int32 words"""
+    return _row_list("kstep_mask", row_live)
+
+
+def gemm_wgrad_steps(dy, x, mask=None, *, out=None, accumulate=False):
+    """gemm_wgrad_blocks over the 16-row steps whose bit is set in `mask` (kstep_mask's int32 words; ia_gemm_wgrad_steps), four to a
+    k-tile.  A shape whose k-slabs are too long for that walk (ia_gemm_wgrad_walk != 2) takes the block walk.  mask=None is the dense gemm."""
+    lib = _lib.load()
+    _need(dy, BF16, "dy"); _need(x, BF16, "x"); _need(mask, torch.int32, "mask")
+    (M, n_out), (Mx, n_in) = dy.shape, x.shape
+    if M != Mx or (mask is not None and mask.numel() * 4 != lib.ia_kstep_mask_bytes(M)):
+        raise ValueError("gemm_wgrad_steps: dy and x must have the same number of rows and mask ia_kstep_mask_bytes(M) bytes")
+    if out is None:
+        out = torch.empty((n_out, n_in), device=dy.device, dtype=F32)
+    _need(out, F32, "out")
+    ws_bytes = lib.ia_gemm_wgrad_rows_workspace_bytes(n_out, n_in, M)      # (room for the block mask of a shape that walks blocks)
+    ws = torch.empty(max(ws_bytes, 16), device=dy.device, dtype=torch.uint8)
+    check(lib.ia_gemm_wgrad_steps(dy.data_ptr(), n_out, x.data_ptr(), n_in, out.data_ptr(), n_in, n_out, n_in, M, ptr(mask),
+                                  int(accumulate), ws.data_ptr(), ws_bytes, stream_ptr()), "ia_gemm_wgrad_steps")
+    return out
+
+
 def gemm_wgrad_rows(dy, x, row_live=None, *, out=None, accumulate=False):
     """dW[N_out, N_in] (+)= dy[M, N_out]^T x[M, N_in] in fp32; row_live (uint8 [M]) == 0 promises that row of dy is all zeros, and
     32-row blocks without a live row are skipped (ia_gemm_wgrad_rows).  row_live=None is gemm(..., a_kstrided, b_kstrided, out_f32)."""
