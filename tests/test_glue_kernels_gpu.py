@@ -18,12 +18,11 @@ import pytest
 import torch
 
 import glue_reference as R
+from fp64_bars import TINY, U24, ULP16, _ratio, bf16_close, bits, sum_close
 
 pytestmark = pytest.mark.gpu
 
 F64, F32, BF16 = torch.float64, torch.float32, torch.bfloat16
-U24, ULP16 = R.U24, R.BF16_ULP
-TINY = 2.0 ** -125            # results below the fp32 normal range may be flushed
 ERR_ARG, ERR_WS = -1, -3
 
 
@@ -72,40 +71,6 @@ def gen(seed):
 
 def randn(shape, seed, scale=1.0, dtype=F32):
     return (torch.randn(shape, generator=gen(seed)) * scale).to(dtype)
-
-
-def _ratio(name, err, bound):
-    assert torch.isfinite(err).all(), (name, "non-finite output")
-    exact = bound == 0
-    assert (err[exact] == 0).all(), (name, "an element whose bound is zero is not exact", float(err[exact].max()))
-    r = float((err[~exact] / bound[~exact]).max()) if (~exact).any() else 0.0
-    print(f"[glue] {name}: max error / bound = {r:.3f}")
-    return r
-
-
-def bits(name, got, want):
-    """got (device tensor) equals want bit for bit; want is fp64 (converted the way torch converts) or already got's dtype."""
-    got = got.detach().cpu()
-    want = want.to(F32).to(got.dtype) if want.dtype == F64 else want.cpu()
-    assert got.shape == want.shape, (name, got.shape, want.shape)
-    iv = {BF16: torch.int16, F32: torch.int32}[got.dtype]
-    same = got.contiguous().view(iv) == want.contiguous().view(iv)
-    assert same.all(), (name, int((~same).sum()), "elements differ in their bits")
-
-
-def bf16_close(name, got, want, a):
-    got, want = got.detach().cpu().to(F64), want.to(F64)
-    assert got.shape == want.shape, (name, got.shape, want.shape)
-    a = a if torch.is_tensor(a) else torch.full_like(want, float(a))
-    r = _ratio(name, (got - want).abs(), ULP16 * want.abs() + a.expand_as(want))
-    assert r <= 1.0, (name, r)
-
-
-def sum_close(name, got, want, S, c):
-    got, want = got.detach().cpu().to(F64), want.to(F64)
-    assert got.shape == want.shape, (name, got.shape, want.shape)
-    r = _ratio(name, (got - want).abs(), c * U24 * S.to(F64).expand_as(want))
-    assert r <= 1.0, (name, r, "c =", c)
 
 
 def nv_of(H):
