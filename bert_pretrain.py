@@ -62,41 +62,34 @@ def main(argv=None):
     parser = get_parser()
     args = parser.parse_args(argv)
     from item_alignment_amd import dist as iadist
-    rank, world, _ = iadist.env_ranks()
-    if args.batch_size % world:
-        parser.error(f"--batch_size {args.batch_size} must be divisible by the world size {world}")
-    dp = world > 1
-    from item_alignment_amd.cli_common import check_model_dir, linear_schedule, load_config, load_vocab_tokenizer
+    ranks = iadist.Ranks()
+    if args.batch_size % ranks.world:
+        parser.error(f"--batch_size {args.batch_size} must be divisible by the world size {ranks.world}")
+    from item_alignment_amd.cli_common import check_model_dir, rank0_run_logging
     check_model_dir(args.model_name_or_path)
+    if ranks.rank == 0:                   # the log file, the scalars and the model directory are rank 0's alone
+        os.makedirs(args.output_dir, exist_ok=True)
+    with rank0_run_logging(LOGGER, ranks.rank, os.path.join(args.output_dir, "pretrain-bert.log"), os.path.join(args.output_dir, "tf-logs")) as writer:
+        try:
+            pretrain(args, ranks, writer)
+        finally:
+            ranks.close()
+    return 0
+
+
+def pretrain(args, ranks, writer):
     import torch
     import item_alignment_amd.models as M
+    from item_alignment_amd import dist as iadist
+    from item_alignment_amd.cli_common import linear_schedule, load_config, load_vocab_tokenizer
     from item_alignment_amd.data import bert_pretrain as D
     from item_alignment_amd.models import functional as Fn
-
-    LOGGER.propagate = False              # the package configures the root logger: every line once, through the two handlers below
-    fmt = logging.Formatter("%(asctime)s - %(name)s - %(levelname)s - %(message)s")
-    writer = None
-    if rank == 0:                         # the log file, the scalars and the model directory are rank 0's alone
-        os.makedirs(args.output_dir, exist_ok=True)
-        LOGGER.setLevel(logging.INFO)
-        handlers = (logging.FileHandler(os.path.join(args.output_dir, "pretrain-bert.log")), logging.StreamHandler(sys.stdout))
-        try:                              # scalars for TensorBoard only where tensorboardX is installed; never required
-            from tensorboardX import SummaryWriter
-            writer = SummaryWriter(logdir=os.path.join(args.output_dir, "tf-logs"))
-        except ImportError:
-            pass
-    else:                                 # the other ranks attach no file handler and keep to warnings
-        LOGGER.setLevel(logging.WARNING)
-        handlers = (logging.StreamHandler(sys.stdout),)
-    for h in handlers:
-        h.setFormatter(fmt)
-        LOGGER.addHandler(h)
+    from item_alignment_amd.train import clipped_adamw_step
 
     if not torch.cuda.is_available():
         raise SystemExit("bert_pretrain.py runs on the MI355X HIP engine only (no CPU path); no GPU is visible")
-    rank, world, local = iadist.init_from_env("cuda")
-    device = torch.device("cuda", local % max(1, torch.cuda.device_count()) if dp else local)
-    torch.cuda.set_device(device)
+    device = ranks.init("cuda").device
+    rank, world, dp = ranks.rank, ranks.world, ranks.dp
 
     vocab_file = os.path.join(args.model_name_or_path, "vocab.txt")
     tokenizer = load_vocab_tokenizer(vocab_file)
@@ -109,12 +102,8 @@ def main(argv=None):
     model = M.BertForPreTraining.from_pretrained(args.model_name_or_path, config=config).to(device)
     LOGGER.info("The BERT model has {:} different named parameters.".format(len(list(model.named_parameters()))))
     arena = model.param_arena
-    reducer = None
+    reducer = ranks.attach(arena)
     if dp:
-        iadist.broadcast_arena(arena)
-        reducer = iadist.GradBucketReducer.for_arena(arena)
-        Fn.clear_grad_ready_hooks()
-        Fn.register_grad_ready_hook(reducer.grads_ready)
         LOGGER.info(f"Data parallel: {world} ranks, --batch_size {args.batch_size} is the total ({args.batch_size // world} rows a rank)")
     rng = D.Rng(args.seed)            # the same seed on every rank: the same records, masking draws and shuffles, the same global batches
 
@@ -151,70 +140,56 @@ def main(argv=None):
         if rank == 0:
             model.save_pretrained(args.output_dir)
             shutil.copyfile(vocab_file, os.path.join(args.output_dir, "vocab.txt"))
-        if dp:
-            torch.distributed.barrier()          # nobody runs ahead into the next step's collectives while rank 0 writes
+        ranks.written()
 
-    def train():
-        """the epochs; returns at early stopping and at --max_steps, on every rank at the same step"""
-        global_steps, best_eval_loss, best_steps = 0, float("inf"), 0
-        model.train()
-        for epoch_idx in range(args.num_epochs):
-            for records in D.read_pretrained_data(args.data_dir, args.train_file, rng):
-                examples = D.build_examples(records, tokenizer, args.max_seq_len, rng)
-                for batch in D.batches(examples, args.batch_size, rng):
-                    shares, inv_world = None, 1.0
-                    if dp:
-                        rows = batch[0].shape[0]
-                        if rows < world:      # a rank would hold no row: every rank skips the batch, global_steps does not move
-                            LOGGER.info(f"Epoch {epoch_idx + 1}: a batch of {rows} rows skipped on every rank, fewer rows than the {world} ranks")
-                            continue
-                        lo, hi = iadist.deal_rows(rows, rank, world)
-                        batch = tuple(t[lo:hi] for t in batch)
-                        # the masked-LM term is a mean over labelled rows, the next-sentence term a mean over rows: one count exchange
-                        shares, _ = iadist.loss_shares([int((batch[3] != -1).sum()), hi - lo])
-                    # dropout streams differ per rank (rank 0's is the one-process stream)
-                    Fn.set_step_seed((args.seed * 1000003 + global_steps + rank * 0x9E3779B1) & 0xFFFFFFFF)
-                    Fn.reset_use_counts()
-                    arena.zero_grad()
-                    loss = run(batch, shares)
-                    loss.backward()
-                    if reducer is not None:
-                        inv_world = reducer.finish()          # the arena now holds the SUM over ranks; 1 / world makes it the average
-                    global_steps += 1
-                    # clip_grad_norm_(model.parameters(), max_grad_norm) as a factor on the gradients inside the fused optimiser step;
-                    # the norm is the averaged gradient's, the same number on every rank
-                    norm = arena.grad.norm().item() * inv_world
-                    scale = min(1.0, args.max_grad_norm / (norm + 1e-6)) * inv_world
-                    lr = args.learning_rate * linear_schedule(global_steps - 1, total_steps, args.warmup_steps)
-                    arena.adamw_step(lr, betas=(0.9, 0.999), eps=args.adam_epsilon, weight_decay=0.0, grad_scale=scale)
-                    if global_steps % args.log_steps == 0:
-                        # the weighted rank losses average to the loss of the global batch: one collective, at log steps only
-                        value = (iadist.all_reduce_scalar(loss.detach().clone()).item() / world) if dp else loss.item()
-                        if writer:
-                            writer.add_scalar("Train/loss", value, global_steps)
-                        LOGGER.info("Epoch {:>3,}, Steps {:>5,}, Total {:>5,}, Train/Loss {:.6f}".format(epoch_idx + 1, global_steps, total_steps, value))
-                    if global_steps % args.eval_steps == 0:
-                        eval_loss = eval_model()
-                        if writer:
-                            writer.add_scalar("Eval/loss", eval_loss, global_steps)
-                        improve = "  No optimization! ..."
-                        if best_eval_loss > eval_loss:
-                            best_eval_loss, best_steps, improve = eval_loss, global_steps, " ^_^"
-                            save()
-                        elif global_steps - best_steps > args.patience_steps:
-                            LOGGER.info(f"Eval loss has not been optimized for {args.patience_steps} steps, Early stopping ...")
-                            LOGGER.info(f"Pretraining successfully, num_epochs:{epoch_idx + 1}, global_steps:{global_steps} ^_^")
-                            return
-                        LOGGER.info("* Epoch {:>3,}, Steps {:>5,}, Total {:>5,}, Eval/Loss {:.6f}".format(epoch_idx + 1, global_steps, total_steps,
-                                                                                                       eval_loss) + improve)
-                    if 0 < args.max_steps <= global_steps:
-                        LOGGER.info(f"Stopping after --max_steps {args.max_steps}")
+    # the epochs; the function returns at early stopping and at --max_steps, on every rank at the same step
+    global_steps, best_eval_loss, best_steps = 0, float("inf"), 0
+    model.train()
+    for epoch_idx in range(args.num_epochs):
+        for records in D.read_pretrained_data(args.data_dir, args.train_file, rng):
+            examples = D.build_examples(records, tokenizer, args.max_seq_len, rng)
+            for whole in D.batches(examples, args.batch_size, rng):
+                shares, inv_world = None, 1.0
+                batch = ranks.cut(whole)
+                if batch is None:             # global_steps does not move
+                    LOGGER.info(f"Epoch {epoch_idx + 1}: a batch of {whole[0].shape[0]} rows skipped on every rank, fewer rows than the {world} ranks")
+                    continue
+                if dp:
+                    # the masked-LM term is a mean over labelled rows, the next-sentence term a mean over rows: one count exchange
+                    shares, _ = iadist.loss_shares([int((batch[3] != -1).sum()), batch[0].shape[0]])
+                Fn.set_step_seed(ranks.seed(args.seed * 1000003 + global_steps))
+                Fn.reset_use_counts()
+                arena.zero_grad()
+                loss = run(batch, shares)
+                loss.backward()
+                if reducer is not None:
+                    inv_world = reducer.finish()
+                global_steps += 1
+                lr = args.learning_rate * linear_schedule(global_steps - 1, total_steps, args.warmup_steps)
+                clipped_adamw_step(arena, lr, args.max_grad_norm, inv_world, betas=(0.9, 0.999), eps=args.adam_epsilon, weight_decay=0.0)
+                if global_steps % args.log_steps == 0:
+                    # the weighted rank losses average to the loss of the global batch
+                    value = ranks.mean(loss)
+                    if writer:
+                        writer.add_scalar("Train/loss", value, global_steps)
+                    LOGGER.info("Epoch {:>3,}, Steps {:>5,}, Total {:>5,}, Train/Loss {:.6f}".format(epoch_idx + 1, global_steps, total_steps, value))
+                if global_steps % args.eval_steps == 0:
+                    eval_loss = eval_model()
+                    if writer:
+                        writer.add_scalar("Eval/loss", eval_loss, global_steps)
+                    improve = "  No optimization! ..."
+                    if best_eval_loss > eval_loss:
+                        best_eval_loss, best_steps, improve = eval_loss, global_steps, " ^_^"
+                        save()
+                    elif global_steps - best_steps > args.patience_steps:
+                        LOGGER.info(f"Eval loss has not been optimized for {args.patience_steps} steps, Early stopping ...")
+                        LOGGER.info(f"Pretraining successfully, num_epochs:{epoch_idx + 1}, global_steps:{global_steps} ^_^")
                         return
-
-    train()
-    if dp:
-        torch.distributed.destroy_process_group()
-    return 0
+                    LOGGER.info("* Epoch {:>3,}, Steps {:>5,}, Total {:>5,}, Eval/Loss {:.6f}".format(epoch_idx + 1, global_steps, total_steps,
+                                                                                                   eval_loss) + improve)
+                if 0 < args.max_steps <= global_steps:
+                    LOGGER.info(f"Stopping after --max_steps {args.max_steps}")
+                    return
 
 
 if __name__ == "__main__":

@@ -110,132 +110,114 @@ def main(argv=None):
     from item_alignment_amd.models import functional as Fn
     from item_alignment_amd.utils import VIT_WEIGHTS_NAME, logger
 
-    rank, world, local = iadist.init_from_env("cuda")
-    dp = world > 1
-    per_rank = args.train_batch_size // world
-    if per_rank * world != args.train_batch_size:
-        raise ValueError(f"--train_batch_size {args.train_batch_size} must be divisible by the world size {world}")
-    device = torch.device("cuda", local % max(1, torch.cuda.device_count()) if dp else local)
-    torch.cuda.set_device(device)
-    logger.info(f"device: {device}, 16-bits training: {args.fp16} (ignored: bf16 activations, fp32 master weights)")
-    train.seed_everything(args.seed)
+    ranks = iadist.Ranks()
+    try:
+        device = ranks.init("cuda").device
+        rank, world, dp = ranks.rank, ranks.world, ranks.dp
+        per_rank = args.train_batch_size // world
+        if per_rank * world != args.train_batch_size:
+            raise ValueError(f"--train_batch_size {args.train_batch_size} must be divisible by the world size {world}")
+        logger.info(f"device: {device}, 16-bits training: {args.fp16} (ignored: bf16 activations, fp32 master weights)")
+        train.seed_everything(args.seed)
 
-    tokenizer = load_tokenizer(SimpleNamespace(pretrained_model_path=args.pretrained_text_model_path, do_lower_case=args.do_lower_case))
-    config_file = args.config_file if os.path.isfile(args.config_file) else os.path.join(args.output_dir, args.config_file)
-    config = load_config(config_file, image_size=args.image_size, max_seq_len=args.max_seq_len, max_seq_len_pv=args.max_seq_len_pv,
-                         caption_loss_weight=args.caption_loss_weight, contrastive_loss_weight=args.contrastive_loss_weight)
+        tokenizer = load_tokenizer(SimpleNamespace(pretrained_model_path=args.pretrained_text_model_path, do_lower_case=args.do_lower_case))
+        config_file = args.config_file if os.path.isfile(args.config_file) else os.path.join(args.output_dir, args.config_file)
+        config = load_config(config_file, image_size=args.image_size, max_seq_len=args.max_seq_len, max_seq_len_pv=args.max_seq_len_pv,
+                             caption_loss_weight=args.caption_loss_weight, contrastive_loss_weight=args.contrastive_loss_weight)
 
-    text_encoder = RobertaModel.from_pretrained(args.pretrained_text_model_path, config=config)
-    image_encoder = VisionTransformer(img_size=args.image_size, patch_size=getattr(config, "patch_size", 16), embed_dim=config.hidden_size,
-                                      depth=config.num_hidden_layers, num_heads=config.num_attention_heads)
-    f = args.pretrained_image_model_path
-    f = os.path.join(f, VIT_WEIGHTS_NAME) if os.path.isdir(f) else f
-    if os.path.exists(f):
-        image_encoder.load_state_dict(torch.load(f, map_location="cpu"), strict=False)
-    else:
-        logger.warning(f"{f} not found: the image encoder keeps its random initialisation (no network for timm weights)")
-    model = CoCaForPretraining(config, text_encoder=text_encoder, image_encoder=image_encoder)
-    freeze_and_resume(args, model)
-
-    train_data = load_raw_data(args)
-    logger.info(f"# train samples: {len(train_data)}")
-    dataset = MultimodalDataset(train_data, image_size=args.image_size, is_training=True, text_tokenizer=tokenizer,
-                                max_seq_len=args.max_seq_len, max_seq_len_pv=args.max_seq_len_pv, hflip=args.hflip,
-                                color_jitter=args.color_jitter)
-    model.to(device)
-    opt = train.ArenaAdamW(model, args.learning_rate, args.adam_epsilon, args.weight_decay)
-    total = int(len(dataset) / args.train_batch_size / args.gradient_accumulation_steps) * (args.num_train_epochs - args.start_epoch)
-    warm = int(total * args.warmup_proportion)
-
-    reducer = None
-    if dp:
-        iadist.broadcast_arena(model.param_arena)
-        reducer = iadist.GradBucketReducer.for_arena(model.param_arena)
-        Fn.clear_grad_ready_hooks()
-        Fn.register_grad_ready_hook(reducer.grads_ready)
-        model.set_data_parallel()
-
-    out_dir = os.path.join(args.output_dir, args.model_name)
-    os.makedirs(out_dir, exist_ok=True)
-    if rank == 0:
-        with open(os.path.join(out_dir, "hyperparamter.txt"), "w") as w:
-            print(args, file=w)
-            print("\n", file=w)
-            print(config, file=w)
-
-    logger.info("***** Running training *****")
-    logger.info("  Model name = %s", args.model_name)
-    logger.info("  Num examples = %d", len(dataset))
-    logger.info("  Batch size = %d", args.train_batch_size)
-    if dp:
-        logger.info("  Ranks = %d of %d items each (this is rank %d)", world, per_rank, rank)
-    logger.info("  Num steps = %d", total)
-    logger.info("  Learning rate = %.3f", args.learning_rate)
-
-    global_step = 0
-    for epoch in range(int(args.start_epoch), int(args.num_train_epochs)):
-        model.train()
-        # the shuffle and the augmentation draws depend on (seed, epoch) alone: a run resumed at --start_epoch sees that epoch's batches
-        epoch_seed = (args.seed * 1000003 + epoch * 1009) & 0x7FFFFFFF
-        random.seed(epoch_seed)
-        if dp:
-            # every rank takes positions rank::world of the epoch's permutation: equal shares, the same global order at any world size.
-            # The augmentation draws differ per rank (item_alignment_amd/train.py): the ranks hold different items of one batch
-            idx = iadist.shard_indices(len(dataset), rank, world, epoch_seed, shuffle=True)
-            aug_seed = (args.seed * 1000003 + epoch * 1009 + rank * 7919) & 0x7FFFFFFF
-            random.seed(aug_seed)
-            loader = DataLoader(Subset(dataset, idx.tolist()), batch_size=per_rank, shuffle=False, collate_fn=collate_or_none,
-                                num_workers=args.num_workers, generator=torch.Generator().manual_seed(aug_seed))
+        text_encoder = RobertaModel.from_pretrained(args.pretrained_text_model_path, config=config)
+        image_encoder = VisionTransformer(img_size=args.image_size, patch_size=getattr(config, "patch_size", 16), embed_dim=config.hidden_size,
+                                          depth=config.num_hidden_layers, num_heads=config.num_attention_heads)
+        f = args.pretrained_image_model_path
+        f = os.path.join(f, VIT_WEIGHTS_NAME) if os.path.isdir(f) else f
+        if os.path.exists(f):
+            image_encoder.load_state_dict(torch.load(f, map_location="cpu"), strict=False)
         else:
-            loader = DataLoader(dataset, batch_size=args.train_batch_size, shuffle=True, collate_fn=collate_coca, num_workers=args.num_workers,
-                                generator=torch.Generator().manual_seed(epoch_seed))
-        opt.zero_grad()
-        micro = 0           # micro-batches run since the epoch began; in one process every step is one
-        for step, batch in enumerate(loader):
-            if dp:
-                # the collate drops items whose image failed to load, so the ranks can arrive with different counts.  A rank without an
-                # item has nothing to put into the collectives of the step: every rank skips the micro-batch together
-                counts = [c[0] for c in iadist.gather_ints([0 if batch is None else len(batch[0])])]
-                if min(counts) == 0:
-                    if rank == 0:
-                        logger.info(f"[Epoch-{epoch} Step-{step}] skipped on every rank: item counts {counts}, a rank has none")
-                    continue
-            input_ids, attention_mask, token_type_ids, position_ids, images = (t.to(device, non_blocking=True) for t in batch[1:])
-            # dropout streams differ per rank, as the augmentation draws do (rank 0's are the one-process stream)
-            Fn.set_step_seed((args.seed * 1000003 + global_step * 131 + step + rank * 0x9E3779B1) & 0xFFFFFFFF)
-            Fn.reset_use_counts()
-            loss = model(input_ids, attention_mask, token_type_ids, position_ids, images)
-            if args.log_steps is not None and step % args.log_steps == 0:
-                shown = loss.detach().clone()
-                if dp:          # the mean of the ranks' losses is the loss of the global batch; one collective, at log steps only
-                    shown = iadist.all_reduce_scalar(shown) / world
-                if rank == 0:
-                    logger.info(f"[Epoch-{epoch} Step-{step}] loss: {shown.item():.6f}")
-            if args.gradient_accumulation_steps > 1:
-                loss = loss / args.gradient_accumulation_steps
-            micro += 1
-            last = micro % args.gradient_accumulation_steps == 0
-            if reducer is not None:       # collectives only start in the backward that completes the accumulated gradient
-                reducer.armed = last
-            loss.backward()
-            if last:
-                scale = reducer.finish() if reducer is not None else 1.0
-                opt.step(train.linear_schedule_with_warmup(global_step, warm, total), grad_scale=scale)
-                opt.zero_grad()          # after the optimiser step, so the micro-batches in between accumulate (note N3)
-                global_step += 1
-                if 0 < args.max_steps <= global_step:
-                    break
-        if rank == 0:
-            logger.info(f"[Epoch-{epoch}] saving model ({global_step} optimiser steps so far)")
-            sd = {k: v.detach().to("cpu", torch.float32 if v.is_floating_point() else v.dtype).clone() for k, v in model.state_dict().items()}
-            torch.save(sd, os.path.join(out_dir, f"coca_pretrain_epoch-{epoch}.bin"))
+            logger.warning(f"{f} not found: the image encoder keeps its random initialisation (no network for timm weights)")
+        model = CoCaForPretraining(config, text_encoder=text_encoder, image_encoder=image_encoder)
+        freeze_and_resume(args, model)
+
+        train_data = load_raw_data(args)
+        logger.info(f"# train samples: {len(train_data)}")
+        dataset = MultimodalDataset(train_data, image_size=args.image_size, is_training=True, text_tokenizer=tokenizer,
+                                    max_seq_len=args.max_seq_len, max_seq_len_pv=args.max_seq_len_pv, hflip=args.hflip,
+                                    color_jitter=args.color_jitter)
+        model.to(device)
+        opt = train.ArenaAdamW(model, args.learning_rate, args.adam_epsilon, args.weight_decay)
+        total = int(len(dataset) / args.train_batch_size / args.gradient_accumulation_steps) * (args.num_train_epochs - args.start_epoch)
+        warm = int(total * args.warmup_proportion)
+
+        reducer = ranks.attach(model.param_arena)
         if dp:
-            torch.distributed.barrier()          # nobody runs ahead into the next epoch's collectives while rank 0 writes
-        if 0 < args.max_steps <= global_step:
-            logger.info(f"Stopping after --max_steps {args.max_steps}")
-            break
-    if dp:
-        torch.distributed.destroy_process_group()
+            model.set_data_parallel()          # every item of the other ranks is a contrastive negative
+
+        out_dir = os.path.join(args.output_dir, args.model_name)
+        os.makedirs(out_dir, exist_ok=True)
+        if rank == 0:
+            train.dump_hyperparameters(out_dir, args, config)
+
+        logger.info("***** Running training *****")
+        logger.info("  Model name = %s", args.model_name)
+        logger.info("  Num examples = %d", len(dataset))
+        logger.info("  Batch size = %d", args.train_batch_size)
+        if dp:
+            logger.info("  Ranks = %d of %d items each (this is rank %d)", world, per_rank, rank)
+        logger.info("  Num steps = %d", total)
+        logger.info("  Learning rate = %.3f", args.learning_rate)
+
+        global_step = 0
+        for epoch in range(int(args.start_epoch), int(args.num_train_epochs)):
+            model.train()
+            # the shuffle and the augmentation draws depend on (seed, epoch) alone: a run resumed at --start_epoch sees that epoch's batches
+            epoch_seed = (args.seed * 1000003 + epoch * 1009) & 0x7FFFFFFF
+            random.seed(epoch_seed)
+            if dp:
+                # every rank takes positions rank::world of the epoch's permutation: equal shares, the same global order at any world size.
+                # The augmentation draws differ per rank (item_alignment_amd/train.py): the ranks hold different items of one batch
+                idx = iadist.shard_indices(len(dataset), rank, world, epoch_seed, shuffle=True)
+                aug_seed = (args.seed * 1000003 + epoch * 1009 + rank * 7919) & 0x7FFFFFFF
+                random.seed(aug_seed)
+                loader = DataLoader(Subset(dataset, idx.tolist()), batch_size=per_rank, shuffle=False, collate_fn=collate_or_none,
+                                    num_workers=args.num_workers, generator=torch.Generator().manual_seed(aug_seed))
+            else:
+                loader = DataLoader(dataset, batch_size=args.train_batch_size, shuffle=True, collate_fn=collate_coca, num_workers=args.num_workers,
+                                    generator=torch.Generator().manual_seed(epoch_seed))
+            opt.zero_grad()
+            micro = 0           # micro-batches run since the epoch began; in one process every step is one
+            for step, batch in enumerate(loader):
+                if dp:
+                    # the collate drops items whose image failed to load, so the ranks can arrive with different counts.  A rank without an
+                    # item has nothing to put into the collectives of the step: every rank skips the micro-batch together
+                    counts = [c[0] for c in iadist.gather_ints([0 if batch is None else len(batch[0])])]
+                    if min(counts) == 0:
+                        if rank == 0:
+                            logger.info(f"[Epoch-{epoch} Step-{step}] skipped on every rank: item counts {counts}, a rank has none")
+                        continue
+                input_ids, attention_mask, token_type_ids, position_ids, images = (t.to(device, non_blocking=True) for t in batch[1:])
+                Fn.set_step_seed(ranks.seed(args.seed * 1000003 + global_step * 131 + step))
+                Fn.reset_use_counts()
+                loss = model(input_ids, attention_mask, token_type_ids, position_ids, images)
+                if args.log_steps is not None and step % args.log_steps == 0:
+                    shown = ranks.mean(loss, in_dtype=True)          # the mean of the ranks' losses is the loss of the global batch
+                    if rank == 0:
+                        logger.info(f"[Epoch-{epoch} Step-{step}] loss: {shown:.6f}")
+                micro += 1
+                # the micro-batches of one optimiser step accumulate (note N3)
+                if train.accumulate_step(opt, loss, micro % args.gradient_accumulation_steps == 0, args.gradient_accumulation_steps,
+                                         train.linear_schedule_with_warmup(global_step, warm, total), reducer):
+                    global_step += 1
+                    if 0 < args.max_steps <= global_step:
+                        break
+            if rank == 0:
+                logger.info(f"[Epoch-{epoch}] saving model ({global_step} optimiser steps so far)")
+                sd = {k: v.detach().to("cpu", torch.float32 if v.is_floating_point() else v.dtype).clone() for k, v in model.state_dict().items()}
+                torch.save(sd, os.path.join(out_dir, f"coca_pretrain_epoch-{epoch}.bin"))
+            ranks.written()
+            if 0 < args.max_steps <= global_step:
+                logger.info(f"Stopping after --max_steps {args.max_steps}")
+                break
+    finally:
+        ranks.close()
     return 0
 
 

@@ -20,7 +20,6 @@ script.
 import argparse
 import csv
 import datetime
-import logging
 import os
 import shutil
 import sys
@@ -209,203 +208,162 @@ def run(args):
     from item_alignment_amd import dist as iadist
     if batch_size_error(args):
         raise SystemExit(batch_size_error(args))
-    rank, world, _ = iadist.env_ranks()
-    dp = world > 1
-    from item_alignment_amd.cli_common import check_model_dir, linear_schedule, load_config, load_vocab_tokenizer
+    ranks = iadist.Ranks()
+    rank, world, dp = ranks.rank, ranks.world, ranks.dp
+    from item_alignment_amd.cli_common import check_model_dir, linear_schedule, load_config, load_vocab_tokenizer, rank0_run_logging
     check_model_dir(args.model_name_or_path)
     import torch
     import item_alignment_amd.models as M
     from item_alignment_amd.data.bert_align import LOGGER
     from item_alignment_amd.models import functional as Fn
+    from item_alignment_amd.train import clipped_adamw_step
 
     config = load_config(os.path.join(args.model_name_or_path, "config.json"))
     check_lengths(args, config)
     if not torch.cuda.is_available():
         raise SystemExit("finetune_bert.py runs on the MI355X HIP engine only (no CPU path); no GPU is visible")
-    rank, world, local = iadist.init_from_env("cuda")
-    device = torch.device("cuda", local % max(1, torch.cuda.device_count()) if dp else local)
-    torch.cuda.set_device(device)
-
     loss_dir, f1_dir = os.path.join(args.output_dir, "LossModel"), os.path.join(args.output_dir, "F1Model")
     log_dir = os.path.join(args.output_dir, "tf-logs")
     checkpoint_path = os.path.join(args.output_dir, "checkpoint")
-    LOGGER.propagate = False              # the package configures the root logger: every line once, through the two handlers below
-    fmt = logging.Formatter("%(asctime)s - %(name)s - %(levelname)s - %(message)s")
-    writer = None
-    if rank == 0:                         # the directories, the log file, the scalars, the CSV and the models are rank 0's alone
-        for d in (loss_dir, f1_dir, log_dir):
-            os.makedirs(d, exist_ok=True)
-        LOGGER.setLevel(logging.INFO)
-        handlers = [logging.FileHandler(os.path.join(log_dir, f"train-{datetime.date.today()}.log")), logging.StreamHandler(sys.stdout)]
-        try:                              # scalars for TensorBoard only where tensorboardX is installed; never required
-            from tensorboardX import SummaryWriter
-            writer = SummaryWriter(logdir=log_dir)
-        except ImportError:
-            pass
-    else:                                 # the other ranks attach no file handler and keep to warnings
-        LOGGER.setLevel(logging.WARNING)
-        handlers = [logging.StreamHandler(sys.stdout)]
-    for h in handlers:
-        h.setFormatter(fmt)
-        LOGGER.addHandler(h)
-
-    def after_save():
-        if dp:
-            torch.distributed.barrier()          # nobody runs ahead into the next collectives while rank 0 writes
-
-    def scalars(prefix, **values):
-        if writer:
-            for k, v in values.items():
-                writer.add_scalar(f"{prefix}/{k}", v, global_steps)
-
     try:
-        vocab_file = os.path.join(args.model_name_or_path, "vocab.txt")
-        tokenizer = load_vocab_tokenizer(vocab_file)
-        if len(tokenizer) > config.vocab_size:
-            raise SystemExit(f"vocab.txt has {len(tokenizer)} entries, the model's word table {config.vocab_size} rows")
-        lengths = lengths_of(args)
-        order = torch.Generator()          # the training order of an epoch is a function of (seed, epoch) alone: a resumed run finds it again
-        train_loader = load_pairs(args.data_dir, args.train_file, args.batch_size, tokenizer, "train", lengths, args.shuffle_pvs, args.seed,
-                                  order)
-        eval_loader = load_pairs(args.data_dir, args.valid_file, args.batch_size, tokenizer, "eval", lengths)
+        device = ranks.init("cuda").device
+        if rank == 0:                     # the directories, the log file, the scalars, the CSV and the models are rank 0's alone
+            for d in (loss_dir, f1_dir, log_dir):
+                os.makedirs(d, exist_ok=True)
+        with rank0_run_logging(LOGGER, rank, os.path.join(log_dir, f"train-{datetime.date.today()}.log"), log_dir) as writer:
+            def scalars(prefix, **values):
+                if writer:
+                    for k, v in values.items():
+                        writer.add_scalar(f"{prefix}/{k}", v, global_steps)
 
-        torch.manual_seed(args.seed)
-        model = M.BertAlignModel.from_pretrained(args.model_name_or_path, config=config)
-        if args.restore_path:
-            LOGGER.info(f"Loaded {load_state_file(model, args.restore_path)} tensors from {args.restore_path}")
-        else:
-            LOGGER.info("There is no restore model path.")
-        global_steps, optimizer_state = 0, None
-        if os.path.exists(checkpoint_path):
-            ck = torch.load(checkpoint_path, map_location="cpu")
-            model.load_state_dict({(k[len("module."):] if k.startswith("module.") else k): v for k, v in ck["model_state_dict"].items()})
-            global_steps, optimizer_state = int(ck["global_steps"]), ck["optimizer_state_dict"]
-            del ck
-        else:
-            LOGGER.info("There is no resume model path.")
-        model.to(device)
-        arena = model.param_arena
-        if optimizer_state is not None:
-            restore_optimizer(arena, optimizer_state)
-            LOGGER.info(f"Load checkpoint from {checkpoint_path} successfully: resumed at global_steps {global_steps}, train continue ...")
-        LOGGER.info("The BERT model has {:} different named parameters.".format(len(list(model.named_parameters()))))
-        reducer = None
-        if dp:          # after the weights and the checkpoint: rank 0's replica everywhere (every rank has also read the moments itself)
-            iadist.broadcast_arena(arena)
-            reducer = iadist.GradBucketReducer.for_arena(arena)
-            Fn.clear_grad_ready_hooks()
-            Fn.register_grad_ready_hook(reducer.grads_ready)
-            LOGGER.info(f"Data parallel: {world} ranks, --batch_size {args.batch_size} is the total ({args.batch_size // world} pairs a rank)")
+            vocab_file = os.path.join(args.model_name_or_path, "vocab.txt")
+            tokenizer = load_vocab_tokenizer(vocab_file)
+            if len(tokenizer) > config.vocab_size:
+                raise SystemExit(f"vocab.txt has {len(tokenizer)} entries, the model's word table {config.vocab_size} rows")
+            lengths = lengths_of(args)
+            order = torch.Generator()          # the training order of an epoch is a function of (seed, epoch) alone: a resumed run finds it again
+            train_loader = load_pairs(args.data_dir, args.train_file, args.batch_size, tokenizer, "train", lengths, args.shuffle_pvs, args.seed,
+                                      order)
+            eval_loader = load_pairs(args.data_dir, args.valid_file, args.batch_size, tokenizer, "eval", lengths)
 
-        per_epoch = len(train_loader)
-        total_steps = max(1, per_epoch * args.num_epochs)
-        best_f1, best_eval_loss = 0.0, float("inf")
-        best_loss_steps = best_f1_steps = global_steps
-        t0 = time.time()
+            torch.manual_seed(args.seed)
+            model = M.BertAlignModel.from_pretrained(args.model_name_or_path, config=config)
+            if args.restore_path:
+                LOGGER.info(f"Loaded {load_state_file(model, args.restore_path)} tensors from {args.restore_path}")
+            else:
+                LOGGER.info("There is no restore model path.")
+            global_steps, optimizer_state = 0, None
+            if os.path.exists(checkpoint_path):
+                ck = torch.load(checkpoint_path, map_location="cpu")
+                model.load_state_dict({(k[len("module."):] if k.startswith("module.") else k): v for k, v in ck["model_state_dict"].items()})
+                global_steps, optimizer_state = int(ck["global_steps"]), ck["optimizer_state_dict"]
+                del ck
+            else:
+                LOGGER.info("There is no resume model path.")
+            model.to(device)
+            arena = model.param_arena
+            if optimizer_state is not None:
+                restore_optimizer(arena, optimizer_state)
+                LOGGER.info(f"Load checkpoint from {checkpoint_path} successfully: resumed at global_steps {global_steps}, train continue ...")
+            LOGGER.info("The BERT model has {:} different named parameters.".format(len(list(model.named_parameters()))))
+            reducer = ranks.attach(arena)          # after the weights and the checkpoint (every rank has also read the moments itself)
+            if dp:
+                LOGGER.info(f"Data parallel: {world} ranks, --batch_size {args.batch_size} is the total ({args.batch_size // world} pairs a rank)")
 
-        def save_model(directory):
-            if rank == 0:
-                model.save_pretrained(directory)
-                shutil.copyfile(vocab_file, os.path.join(directory, "vocab.txt"))
-                LOGGER.info(f"* Save model to {directory}")
-            after_save()
+            per_epoch = len(train_loader)
+            total_steps = max(1, per_epoch * args.num_epochs)
+            best_f1, best_eval_loss = 0.0, float("inf")
+            best_loss_steps = best_f1_steps = global_steps
+            t0 = time.time()
 
-        def done():
-            return SimpleNamespace(model=model, global_steps=global_steps, best_f1=best_f1, best_eval_loss=best_eval_loss)
+            def save_model(directory):
+                if rank == 0:
+                    model.save_pretrained(directory)
+                    shutil.copyfile(vocab_file, os.path.join(directory, "vocab.txt"))
+                    LOGGER.info(f"* Save model to {directory}")
+                ranks.written()
 
-        # global_steps counts global batches.  Several ranks skip an epoch's last batch where it has fewer pairs than ranks: that epoch
-        # then has one step less than batches (the skipped batch is its last, so batch index and step count still agree inside it)
-        tail = len(train_loader.dataset) % args.batch_size
-        steps_per_epoch = per_epoch - (1 if dp and 0 < tail < world else 0)
-        first_epoch, skip = divmod(global_steps, max(1, steps_per_epoch))
-        if 0 < args.max_steps <= global_steps:
-            LOGGER.info(f"--max_steps {args.max_steps} was reached before this run")
-            return done()
-        for epoch in range(first_epoch, args.num_epochs):
-            LOGGER.info("======== Training Epoch {:} / {:} ========".format(epoch + 1, args.num_epochs))
-            model.train()
-            order.manual_seed(args.seed * 1000003 + epoch)
-            for step, batch in enumerate(train_loader):
-                if epoch == first_epoch and step < skip:          # the batches the interrupted run had already trained on
-                    continue
-                inv_world = 1.0
-                if dp:
-                    pairs = batch[0].shape[0]
-                    if pairs < world:     # a rank would hold no pair: every rank skips the batch, global_steps does not move
-                        LOGGER.info(f"Epoch {epoch + 1}: a batch of {pairs} pairs skipped on every rank, fewer pairs than the {world} ranks")
+            def done():
+                return SimpleNamespace(model=model, global_steps=global_steps, best_f1=best_f1, best_eval_loss=best_eval_loss)
+
+            # global_steps counts global batches.  Several ranks skip an epoch's last batch where it has fewer pairs than ranks: that epoch
+            # then has one step less than batches (the skipped batch is its last, so batch index and step count still agree inside it)
+            tail = len(train_loader.dataset) % args.batch_size
+            steps_per_epoch = per_epoch - (1 if dp and 0 < tail < world else 0)
+            first_epoch, skip = divmod(global_steps, max(1, steps_per_epoch))
+            if 0 < args.max_steps <= global_steps:
+                LOGGER.info(f"--max_steps {args.max_steps} was reached before this run")
+                return done()
+            for epoch in range(first_epoch, args.num_epochs):
+                LOGGER.info("======== Training Epoch {:} / {:} ========".format(epoch + 1, args.num_epochs))
+                model.train()
+                order.manual_seed(args.seed * 1000003 + epoch)
+                for step, whole in enumerate(train_loader):
+                    if epoch == first_epoch and step < skip:          # the batches the interrupted run had already trained on
                         continue
-                    lo, hi = iadist.deal_rows(pairs, rank, world)
-                    batch = [t[lo:hi] for t in batch]
-                # dropout streams differ per rank (rank 0's is the one-process stream)
-                Fn.set_step_seed((args.seed * 1000003 + global_steps + rank * 0x9E3779B1) & 0xFFFFFFFF)
-                Fn.reset_use_counts()
-                arena.zero_grad()
-                loss = forward(model, batch, device)[0][-1]
-                if dp:                    # the mean over this rank's pairs, weighted by its share of the global batch's pairs
-                    loss = loss * iadist.loss_shares([hi - lo])[0][0]
-                loss.backward()
-                if reducer is not None:
-                    inv_world = reducer.finish()          # the arena now holds the SUM over ranks; 1 / world makes it the average
-                global_steps += 1
-                # clip_grad_norm_(model.parameters(), max_grad_norm) as a factor on the gradients inside the fused optimiser step;
-                # the norm is the averaged gradient's, the same number on every rank
-                norm = arena.grad.norm().item() * inv_world
-                scale = min(1.0, args.max_grad_norm / (norm + 1e-6)) * inv_world
-                lr = args.learning_rate * linear_schedule(global_steps - 1, total_steps, args.warmup_steps)
-                arena.adamw_step(lr, betas=(0.9, 0.999), eps=args.adam_epsilon, weight_decay=0.0, grad_scale=scale)
-                if global_steps % args.log_steps == 0:
-                    # the weighted rank losses average to the loss of the global batch: one collective, at log steps only
-                    value = (iadist.all_reduce_scalar(loss.detach().clone()).item() / world) if dp else loss.item()
-                    scalars("Train", Loss=value)
-                    LOGGER.info("Epoch {:>3,} - Steps {:>5,} - Total {:>5,} - Train/Loss {:.6f} - Total cost: {:}".format(
-                        epoch + 1, global_steps, per_epoch, value, datetime.timedelta(seconds=int(time.time() - t0))))
-                if global_steps % args.eval_steps == 0:
-                    LOGGER.info("======== Running Eval ========")
-                    r = evaluate(model, eval_loader, device, rank, world)
-                    if rank == 0:
-                        write_csv_row(args.output_dir, r, epoch + 1, global_steps)
-                    scalars("Eval", Acc=r.acc, Precision=r.pre, Recall=r.recall, F1=r.f1, cls_Acc=r.cls_acc, cls_Precision=r.cls_pre,
-                            cls_Recall=r.cls_recall, cls_F1=r.cls_f1, Loss=r.loss)
-                    LOGGER.info("* Epoch: {:>3,}, Steps {:>5,}, Accuracy: {:.4f}, Precision: {:.4f}, Recall: {:.4f}, F1: {:.4f}, Eval/Loss: {:.6f}"
-                                .format(epoch + 1, global_steps, r.acc, r.pre, r.recall, r.f1, r.loss))
-                    LOGGER.info("* CLS Epoch: {:>3,}, Steps {:>5,}, Accuracy: {:.4f}, Precision: {:.4f}, Recall: {:.4f}, F1: {:.4f}"
-                                .format(epoch + 1, global_steps, r.cls_acc, r.cls_pre, r.cls_recall, r.cls_f1))
-                    improved = []
-                    if best_eval_loss > r.loss:
-                        best_eval_loss, best_loss_steps = r.loss, global_steps
-                        save_model(loss_dir)
-                        improved.append("Eval/Loss")
-                        LOGGER.info(f"* Current Best Eval/Loss {best_eval_loss} epoch:{epoch + 1}, steps:{global_steps}")
-                    if best_f1 < r.f1:
-                        best_f1, best_f1_steps = r.f1, global_steps
-                        save_model(f1_dir)
-                        improved.append("F1")
-                        LOGGER.info(f"* Current Best F1 {best_f1} epoch:{epoch + 1}, steps:{global_steps} Eval/Loss:{r.loss}")
-                    if global_steps % args.check_steps == 0:
+                    inv_world = 1.0
+                    batch = ranks.cut(whole)
+                    if batch is None:             # global_steps does not move
+                        LOGGER.info(f"Epoch {epoch + 1}: a batch of {whole[0].shape[0]} pairs skipped on every rank, fewer pairs than the {world} ranks")
+                        continue
+                    Fn.set_step_seed(ranks.seed(args.seed * 1000003 + global_steps))
+                    Fn.reset_use_counts()
+                    arena.zero_grad()
+                    loss = forward(model, batch, device)[0][-1]
+                    if dp:                    # the mean over this rank's pairs, weighted by its share of the global batch's pairs
+                        loss = loss * iadist.loss_shares([batch[0].shape[0]])[0][0]
+                    loss.backward()
+                    if reducer is not None:
+                        inv_world = reducer.finish()
+                    global_steps += 1
+                    lr = args.learning_rate * linear_schedule(global_steps - 1, total_steps, args.warmup_steps)
+                    clipped_adamw_step(arena, lr, args.max_grad_norm, inv_world, betas=(0.9, 0.999), eps=args.adam_epsilon, weight_decay=0.0)
+                    if global_steps % args.log_steps == 0:
+                        value = ranks.mean(loss)          # the weighted rank losses average to the loss of the global batch
+                        scalars("Train", Loss=value)
+                        LOGGER.info("Epoch {:>3,} - Steps {:>5,} - Total {:>5,} - Train/Loss {:.6f} - Total cost: {:}".format(
+                            epoch + 1, global_steps, per_epoch, value, datetime.timedelta(seconds=int(time.time() - t0))))
+                    if global_steps % args.eval_steps == 0:
+                        LOGGER.info("======== Running Eval ========")
+                        r = evaluate(model, eval_loader, device, rank, world)
                         if rank == 0:
-                            save_checkpoint(model, arena, global_steps, total_steps, args, checkpoint_path)
-                            LOGGER.info(f"* Save checkpoint to {checkpoint_path} .")
-                        after_save()
-                    if global_steps - best_loss_steps >= args.patience_steps and global_steps - best_f1_steps >= args.patience_steps:
-                        LOGGER.info(f"There is no optimizing model after {max(global_steps - best_loss_steps, global_steps - best_f1_steps)} "
-                                    "steps, Early stopping ....")
-                        LOGGER.info(f"* Best F1 {best_f1} after {epoch + 1} epochs, {global_steps} steps training.")
+                            write_csv_row(args.output_dir, r, epoch + 1, global_steps)
+                        scalars("Eval", Acc=r.acc, Precision=r.pre, Recall=r.recall, F1=r.f1, cls_Acc=r.cls_acc, cls_Precision=r.cls_pre,
+                                cls_Recall=r.cls_recall, cls_F1=r.cls_f1, Loss=r.loss)
+                        LOGGER.info("* Epoch: {:>3,}, Steps {:>5,}, Accuracy: {:.4f}, Precision: {:.4f}, Recall: {:.4f}, F1: {:.4f}, Eval/Loss: {:.6f}"
+                                    .format(epoch + 1, global_steps, r.acc, r.pre, r.recall, r.f1, r.loss))
+                        LOGGER.info("* CLS Epoch: {:>3,}, Steps {:>5,}, Accuracy: {:.4f}, Precision: {:.4f}, Recall: {:.4f}, F1: {:.4f}"
+                                    .format(epoch + 1, global_steps, r.cls_acc, r.cls_pre, r.cls_recall, r.cls_f1))
+                        improved = []
+                        if best_eval_loss > r.loss:
+                            best_eval_loss, best_loss_steps = r.loss, global_steps
+                            save_model(loss_dir)
+                            improved.append("Eval/Loss")
+                            LOGGER.info(f"* Current Best Eval/Loss {best_eval_loss} epoch:{epoch + 1}, steps:{global_steps}")
+                        if best_f1 < r.f1:
+                            best_f1, best_f1_steps = r.f1, global_steps
+                            save_model(f1_dir)
+                            improved.append("F1")
+                            LOGGER.info(f"* Current Best F1 {best_f1} epoch:{epoch + 1}, steps:{global_steps} Eval/Loss:{r.loss}")
+                        if global_steps % args.check_steps == 0:
+                            if rank == 0:
+                                save_checkpoint(model, arena, global_steps, total_steps, args, checkpoint_path)
+                                LOGGER.info(f"* Save checkpoint to {checkpoint_path} .")
+                            ranks.written()
+                        if global_steps - best_loss_steps >= args.patience_steps and global_steps - best_f1_steps >= args.patience_steps:
+                            LOGGER.info(f"There is no optimizing model after {max(global_steps - best_loss_steps, global_steps - best_f1_steps)} "
+                                        "steps, Early stopping ....")
+                            LOGGER.info(f"* Best F1 {best_f1} after {epoch + 1} epochs, {global_steps} steps training.")
+                            return done()
+                        model.train()
+                        LOGGER.info((("Optimize " + " and ".join(improved)) if improved else "No optimization") + ", continue training ...")
+                    if 0 < args.max_steps <= global_steps:
+                        LOGGER.info(f"Stopping after --max_steps {args.max_steps}")
                         return done()
-                    model.train()
-                    LOGGER.info((("Optimize " + " and ".join(improved)) if improved else "No optimization") + ", continue training ...")
-                if 0 < args.max_steps <= global_steps:
-                    LOGGER.info(f"Stopping after --max_steps {args.max_steps}")
-                    return done()
-        LOGGER.info("Training successfully.")
-        return done()
+            LOGGER.info("Training successfully.")
+            return done()
     finally:
-        for h in handlers:
-            LOGGER.removeHandler(h)
-            h.close()
-        if writer:
-            writer.close()
-        if dp and torch.distributed.is_initialized():
-            torch.distributed.destroy_process_group()
+        ranks.close()
 
 
 def main(argv=None):

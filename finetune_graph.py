@@ -97,7 +97,6 @@ def load_raw_data(args):
 
 def evaluate(model, loader, feature_matrix, adj, tag):
     """reference finetune_graph.py:364-426: P / R / F1 swept over the thresholds 0.1 .. 0.9."""
-    from sklearn.metrics import f1_score, precision_score, recall_score
     model.eval()
     probs_all, labels_all = None, None
     with torch.no_grad():
@@ -106,11 +105,7 @@ def evaluate(model, loader, feature_matrix, adj, tag):
             probs = model(feature_matrix=feature_matrix, adjacency_matrix=adj, pairs=batch).probs.cpu().numpy()
             probs_all = probs if probs_all is None else np.append(probs_all, probs)
             labels_all = labels if labels_all is None else np.append(labels_all, labels)
-    for threshold in np.arange(0.1, 1.0, 0.1):
-        pred = probs_all >= threshold
-        p, r, f1 = (precision_score(labels_all, pred, zero_division=0), recall_score(labels_all, pred, zero_division=0),
-                    f1_score(labels_all, pred, zero_division=0))
-        logger.info(f"{tag}threshold={threshold}, precision={p}, recall={r}, f1={f1}")
+    T.log_threshold_sweep(probs_all, labels_all, tag)
 
 
 def main(argv=None):
@@ -151,10 +146,7 @@ def main(argv=None):
         opt = T.ArenaAdamW(model, args.learning_rate, args.adam_epsilon, args.weight_decay)
         total = int(len(train_ds) / args.train_batch_size / args.gradient_accumulation_steps) * (args.num_train_epochs - args.start_epoch)
         warm = int(total * args.warmup_proportion)
-        with open(os.path.join(out_dir, "hyperparamter.txt"), "w") as f:
-            print(args, file=f)
-            print("\n", file=f)
-            print(config, file=f)
+        T.dump_hyperparameters(out_dir, args, config)
         logger.info("***** Running training *****")
         logger.info("  Model name = %s", os.path.basename(out_dir))
         logger.info("  Num examples = %d", len(train_ds))
@@ -173,12 +165,8 @@ def main(argv=None):
                 losses.append(loss.detach())
                 if args.log_steps is not None and step % args.log_steps == 0:
                     logger.info(f"[Epoch-{epoch} Step-{step}] loss: {loss}")
-                if args.gradient_accumulation_steps > 1:
-                    loss = loss / args.gradient_accumulation_steps
-                loss.backward()
-                if (step + 1) % args.gradient_accumulation_steps == 0:
-                    opt.step(T.linear_schedule_with_warmup(global_step, warm, total))
-                    opt.zero_grad()
+                if T.accumulate_step(opt, loss, (step + 1) % args.gradient_accumulation_steps == 0, args.gradient_accumulation_steps,
+                                     T.linear_schedule_with_warmup(global_step, warm, total)):
                     global_step += 1
             logger.info(f"[Epoch-{epoch}] mean training loss: {float(torch.stack(losses).mean())}")
             if args.save_epochs is not None and epoch % args.save_epochs == 0:
@@ -193,18 +181,13 @@ def main(argv=None):
     if args.do_pred:
         model.eval()
         test_loader = DataLoader(GCNDataset(test_data), batch_size=args.eval_batch_size, shuffle=False, collate_fn=collate_gnn)
-        with open(os.path.join(out_dir, f"deepAI_result_threshold={args.threshold}.jsonl"), "w", encoding="utf-8") as w, torch.no_grad():
-            for step, batch in enumerate(test_loader):
-                output = model(feature_matrix=feature_matrix, adjacency_matrix=adj, pairs=batch)
-                src_embeds, tgt_embeds = output.src_embeds.cpu().numpy(), output.tgt_embeds.cpu().numpy()
-                for b, s, t in zip(batch, src_embeds, tgt_embeds):
-                    s = ",".join(str(e) for e in s) if isinstance(s, np.ndarray) else str(s)
-                    t = ",".join(str(e) for e in t) if isinstance(t, np.ndarray) else str(t)
-                    w.write(json.dumps({"src_item_id": b["src_item_id"], "src_item_emb": f"[{s}]", "tgt_item_id": b["tgt_item_id"],
-                                        "tgt_item_emb": f"[{t}]", "threshold": args.threshold}) + "\n")
-                if args.log_steps is not None and step % args.log_steps == 0:
-                    logger.info(f"[Prediction] {step} samples processed")
-        logger.info("[Prediction] Finished")
+
+        def rows_of(batch):
+            output = model(feature_matrix=feature_matrix, adjacency_matrix=adj, pairs=batch)
+            return [b["src_item_id"] for b in batch], [b["tgt_item_id"] for b in batch], output.src_embeds.cpu().numpy(), output.tgt_embeds.cpu().numpy()
+
+        T.write_pair_embeddings(os.path.join(out_dir, f"deepAI_result_threshold={args.threshold}.jsonl"), test_loader, rows_of, args.threshold,
+                                args.log_steps)
     return out_dir
 
 

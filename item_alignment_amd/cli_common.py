@@ -1,7 +1,10 @@
 """Pieces the three finetune_*.py scripts share: flags common to all of them, config /
 tokenizer loading, the optional freeze / resume handling (reference finetune_multimodal.py:233-267)."""
+import contextlib
 import json
+import logging
 import os
+import sys
 from types import SimpleNamespace
 
 import torch
@@ -109,10 +112,38 @@ def load_vocab_tokenizer(vocab_file):
 
 
 def linear_schedule(step, total, warmup):
-    """transformers.get_linear_schedule_with_warmup's factor at `step`"""
-    if step < warmup:
-        return step / max(1, warmup)
-    return max(0.0, (total - step) / max(1, total - warmup))
+    """train.linear_schedule_with_warmup in the argument order of the BERT scripts"""
+    from .train import linear_schedule_with_warmup
+    return linear_schedule_with_warmup(step, warmup, total)
+
+
+@contextlib.contextmanager
+def rank0_run_logging(log, rank, log_file, tensorboard_dir):
+    """The run set-up of bert_pretrain.py and finetune_bert.py: rank 0 alone owns the log file and the scalars (file + stdout handlers at
+    INFO, a tensorboardX writer where that is installed; its directories exist already), the other ranks keep to warnings on stdout.
+    Yields the writer or None; every way out removes and closes what was added, so a second run in the process logs each line once."""
+    log.propagate = False                 # the package configures the root logger: every line once, through the handlers below
+    log.setLevel(logging.INFO if rank == 0 else logging.WARNING)
+    writer, handlers = None, [logging.StreamHandler(sys.stdout)]
+    if rank == 0:
+        handlers.insert(0, logging.FileHandler(log_file))
+        try:
+            from tensorboardX import SummaryWriter
+            writer = SummaryWriter(logdir=tensorboard_dir)
+        except ImportError:
+            pass
+    fmt = logging.Formatter("%(asctime)s - %(name)s - %(levelname)s - %(message)s")
+    for h in handlers:
+        h.setFormatter(fmt)
+        log.addHandler(h)
+    try:
+        yield writer
+    finally:
+        for h in handlers:
+            log.removeHandler(h)
+            h.close()
+        if writer:
+            writer.close()
 
 
 def freeze_and_resume(args, model):

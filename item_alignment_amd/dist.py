@@ -63,6 +63,73 @@ def init_from_env(device_type="cuda"):
     return rank, world, local
 
 
+class Ranks:
+    """This process among the ranks of a run: what every training script decides about data parallelism, decided once.  Built from the
+    launcher's environment alone (a script refuses its arguments with .rank / .world before anything is initialised); init() joins
+    the process group.  Without WORLD_SIZE no group is ever created and every method is the identity."""
+
+    def __init__(self):
+        self.rank, self.world, self.local = env_ranks()
+        self.dp, self.device, self.created = self.world > 1, None, False
+
+    def init(self, device="cuda"):
+        """init_from_env.  "cuda": the rank's own GPU (LOCAL_RANK; modulo the visible GPUs under a launcher, where the tests put two ranks
+        on one GPU over gloo) is chosen and made current here; a torch.device: the caller has done both (cli_common.pick_device)"""
+        had_group, chosen = dist.is_initialized(), device == "cuda"
+        if chosen:
+            device = torch.device("cuda", self.local % max(1, torch.cuda.device_count()) if self.dp else self.local)
+        self.device = torch.device(device)
+        init_from_env(self.device.type)
+        self.created = dist.is_initialized() and not had_group
+        if chosen:
+            torch.cuda.set_device(self.device)
+        return self
+
+    def attach(self, arena, always=False):
+        """Once the weights are final (finetune_bert.py: after --restore_path and the checkpoint): rank 0's weights everywhere, a bucket
+        reducer over the arena's gradients, its hook in the backward -> the reducer, or None in one process.  always: also at world size 1
+        (train.run: IA_DP_FORCE_COLLECTIVES=1 drives the collectives of a one-GPU run); the other scripts attach under a launcher only"""
+        if not (self.dp or always):
+            return None
+        from .models import functional as Fn
+        broadcast_arena(arena)
+        reducer = GradBucketReducer.for_arena(arena)
+        Fn.clear_grad_ready_hooks()
+        Fn.register_grad_ready_hook(reducer.grads_ready)
+        return reducer
+
+    def cut(self, batch):
+        """the tensors of a global batch -> this rank's deal_rows slice of each; None: fewer rows than ranks, every rank skips the batch"""
+        if not self.dp:
+            return batch
+        if batch[0].shape[0] < self.world:
+            return None
+        lo, hi = deal_rows(batch[0].shape[0], self.rank, self.world)
+        return tuple(t[lo:hi] for t in batch)
+
+    def seed(self, base):
+        """this rank's dropout seed (the ranks hold different rows of a batch: the same masks would correlate them); rank 0's is `base`"""
+        return (base + self.rank * 0x9E3779B1) & 0xFFFFFFFF
+
+    def mean(self, value, in_dtype=False):
+        """a scalar tensor of every rank -> its mean, a float: divided in double (the BERT scripts) or, in_dtype, as a tensor (coca_pretrain.py)"""
+        if not self.dp:
+            return value.item()
+        total = all_reduce_scalar(value.detach().clone())
+        return (total / self.world).item() if in_dtype else total.item() / self.world
+
+    def written(self):
+        """after rank 0 alone wrote files: nobody runs ahead into the next collectives meanwhile (train.run has never waited here)"""
+        if self.dp:
+            dist.barrier()
+
+    def close(self):
+        """destroys the process group if, and only if, init() created it; every script calls it from a `finally`"""
+        if self.created and dist.is_initialized():
+            dist.destroy_process_group()
+        self.created = False
+
+
 def shard_indices(n_items, rank, world, epoch_seed, shuffle=True):
     """Rank r takes positions r::world of the epoch permutation drawn from the shared seed: identical global
     order at any world size; shards are truncated to equal length (the loss is a batch mean)."""

@@ -339,11 +339,8 @@ def schedule_steps(n_facts, batch_size, grad_accum, n_epochs, start_epoch, warmu
 
 
 def linear_schedule_lambda(num_warmup_steps, num_training_steps):
-    def lr_lambda(current_step):
-        if current_step < num_warmup_steps:
-            return float(current_step) / float(max(1, num_warmup_steps))
-        return max(0.0, float(num_training_steps - current_step) / float(max(1, num_training_steps - num_warmup_steps)))
-    return lr_lambda
+    from ..train import linear_schedule_with_warmup
+    return lambda current_step: linear_schedule_with_warmup(current_step, num_warmup_steps, num_training_steps)
 
 
 def stepping_batches(n_batches_per_epoch, grad_accum):

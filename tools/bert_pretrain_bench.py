@@ -88,16 +88,8 @@ class AllRowsScoresFn(torch.autograd.Function):
 
 
 def timed(fn, steps, warmup):
-    times = []
-    for i in range(warmup + steps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn(i)
-        e1.record()
-        torch.cuda.synchronize()
-        if i >= warmup:
-            times.append(e0.elapsed_time(e1))
-    times.sort()
+    import dp_bench
+    times = sorted(dp_bench.timed(fn, steps, warmup))
     return dict(median_ms=times[len(times) // 2], min_ms=times[0], max_ms=times[-1], repeats=steps, warmup=warmup)
 
 
@@ -107,9 +99,8 @@ def dp_child(a):
     import item_alignment_amd.models as M
     from item_alignment_amd import dist as iadist
     from item_alignment_amd.data import bert_pretrain as D
-    _, _, local = iadist.env_ranks()
-    dev = torch.device("cuda", local % torch.cuda.device_count())
-    torch.cuda.set_device(dev)
+    ranks = iadist.Ranks().init("cuda")
+    dev = ranks.device
     rng = D.Rng(a.seed)
     examples = D.build_examples(synthetic_records(max(4, a.batch // 4), a.seed), _Tokenizer(), a.max_seq_len, rng)
     assert len(examples) >= a.batch, "too few synthetic examples"
@@ -127,7 +118,7 @@ def dp_child(a):
         return model(staged["ids"], attention_mask=staged["mask"], masked_lm_labels=staged["labels"], next_sentence_label=staged["nsp"],
                      loss_shares=shares)[0]
 
-    res = dp_bench.timed_rank_step(make_loss, model.param_arena, a.batch, a.steps, a.warmup)
+    res = dp_bench.timed_rank_step(make_loss, model.param_arena, a.batch, a.steps, a.warmup, ranks)
     res.update(positions=ids.shape[1], m_live_global=int((labels != -1).sum()))
     print(json.dumps(res), flush=True)
 
@@ -146,10 +137,10 @@ def main():
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bert_pretrain_bench.py needs the GPU"
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import dp_bench
     if a.dp_child:
         return dp_child(a)
     if a.world:
-        import dp_bench
         dp_bench.measure(__file__, ["--batch", str(a.batch), "--max-seq-len", str(a.max_seq_len), "--steps", str(a.steps), "--warmup", str(a.warmup),
                                     "--seed", str(a.seed)], a.world, a.out)
         return
@@ -182,17 +173,7 @@ def main():
         _, _, nsp_loss = Fn.PairHeadCEFn.apply(pooled, None, model.cls.seq_relationship, nsp)
         return F.cross_entropy(scores, labels.view(-1), ignore_index=-1) + nsp_loss
 
-    def step(loss_fn):
-        def run(i):
-            Fn.set_step_seed(1000 + i)
-            Fn.reset_use_counts()
-            arena.zero_grad()
-            loss = loss_fn()
-            loss.backward()
-            scale = min(1.0, 1.0 / (arena.grad.norm().item() + 1e-6))
-            arena.adamw_step(2e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=scale)
-        return run
-
+    step = lambda loss_fn: dp_bench.train_step(arena, loss_fn)
     live_loss = lambda: model(ids, attention_mask=mask, masked_lm_labels=labels, next_sentence_label=nsp)[0]
     res = dict(gpu=torch.cuda.get_device_name(0), batch=B, positions=L, layers=cfg.num_hidden_layers, hidden=H, vocab=V, m_live=m_live,
                live_fraction=m_live / (B * L))

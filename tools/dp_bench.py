@@ -65,41 +65,52 @@ def measure(script, argv, world, out_path):
     return rec
 
 
-def timed_rank_step(make_loss, arena, global_rows, steps, warmup):
-    """The scripts' train step on this rank, timed with events on the stream: zero_grad, forward, backward, the reducer's finish,
-    the gradient norm, fused AdamW.  make_loss(lo, hi, rank, world) -> the weighted loss of this rank's rows [lo, hi) of the global
-    batch.  -> the dict a --dp-child prints (medians over the timed steps; under several ranks every rank times the same step)."""
+def timed(fn, steps, warmup):
+    """fn(i) for i in range(warmup + steps), each call between two events on the stream -> the ms of the calls after the warm-up"""
     import torch
-    from item_alignment_amd import dist as iadist
-    from item_alignment_amd.models import functional as Fn
-    rank, world, _ = iadist.init_from_env("cuda")
-    reducer = None
-    if world > 1:
-        iadist.broadcast_arena(arena)
-        reducer = iadist.GradBucketReducer.for_arena(arena)
-        Fn.clear_grad_ready_hooks()
-        Fn.register_grad_ready_hook(reducer.grads_ready)
-    lo, hi = iadist.deal_rows(global_rows, rank, world)
     times = []
     for i in range(warmup + steps):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        Fn.set_step_seed((1000 + i + rank * 0x9E3779B1) & 0xFFFFFFFF)
-        Fn.reset_use_counts()
-        arena.zero_grad()
-        loss = make_loss(lo, hi, rank, world)
-        loss.backward()
-        inv_world = reducer.finish() if reducer is not None else 1.0
-        scale = min(1.0, 1.0 / (arena.grad.norm().item() * inv_world + 1e-6)) * inv_world
-        arena.adamw_step(2e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=scale)
+        fn(i)
         e1.record()
         torch.cuda.synchronize()
         if i >= warmup:
             times.append(e0.elapsed_time(e1))
-    times.sort()
+    return times
+
+
+def train_step(arena, loss_fn, ranks=None, reducer=None):
+    """-> step(i): the train step of bert_pretrain.py / finetune_bert.py, through the functions the scripts call: zero_grad, forward,
+    backward, the reducer's finish, the gradient norm and fused AdamW (train.clipped_adamw_step)"""
+    from item_alignment_amd import dist as iadist
+    from item_alignment_amd.models import functional as Fn
+    from item_alignment_amd.train import clipped_adamw_step
+    ranks = ranks or iadist.Ranks()
+
+    def step(i):
+        Fn.set_step_seed(ranks.seed(1000 + i))
+        Fn.reset_use_counts()
+        arena.zero_grad()
+        loss_fn().backward()
+        inv_world = reducer.finish() if reducer is not None else 1.0
+        clipped_adamw_step(arena, 2e-5, 1.0, inv_world, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0)
+    return step
+
+
+def timed_rank_step(make_loss, arena, global_rows, steps, warmup, ranks):
+    """train_step on this rank (ranks: the child's dist.Ranks, initialised), timed with events on the stream.  make_loss(lo, hi, rank,
+    world) -> the weighted loss of this rank's rows [lo, hi) of the global batch.  -> the dict a --dp-child prints (medians over the
+    timed steps; under several ranks every rank times the same step)."""
+    import torch
+    from item_alignment_amd import dist as iadist
+    rank, world = ranks.rank, ranks.world
+    lo, hi = iadist.deal_rows(global_rows, rank, world)
+    step = train_step(arena, lambda: make_loss(lo, hi, rank, world), ranks, ranks.attach(arena))
+    times = sorted(timed(step, steps, warmup))
     res = dict(median_ms=times[len(times) // 2], min_ms=times[0], max_ms=times[-1], repeats=steps, warmup=warmup, world=world,
                rows_global=global_rows, rows_this_rank=hi - lo, gpu=torch.cuda.get_device_name(torch.cuda.current_device()))
     if world > 1:
         res["backend"] = torch.distributed.get_backend()
-        torch.distributed.destroy_process_group()
+    ranks.close()
     return res

@@ -64,19 +64,6 @@ def synthetic_batch(batch, seed, vocab=21128):
     return kw, labels, lengths
 
 
-def timed(fn, steps, warmup):
-    times = []
-    for i in range(warmup + steps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn(i)
-        e1.record()
-        torch.cuda.synchronize()
-        if i >= warmup:
-            times.append(e0.elapsed_time(e1))
-    return times
-
-
 def summary(times, warmup):
     s = sorted(times)
     return dict(median_ms=s[len(s) // 2], min_ms=s[0], max_ms=s[-1], repeats=len(s), warmup_per_round=warmup)
@@ -87,9 +74,8 @@ def dp_child(a):
     import dp_bench
     import item_alignment_amd.models as M
     from item_alignment_amd import dist as iadist
-    _, _, local = iadist.env_ranks()
-    dev = torch.device("cuda", local % torch.cuda.device_count())
-    torch.cuda.set_device(dev)
+    ranks = iadist.Ranks().init("cuda")
+    dev = ranks.device
     kw, labels, lengths = synthetic_batch(a.batch, a.seed, config().vocab_size)
     torch.manual_seed(a.seed)
     model = M.BertAlignModel(config()).to(dev).train()
@@ -102,7 +88,7 @@ def dp_child(a):
         loss = model(**staged)[-1]
         return loss * iadist.loss_shares([hi - lo])[0][0] if world > 1 else loss          # the count exchange of every step, as in the script
 
-    res = dp_bench.timed_rank_step(make_loss, model.param_arena, a.batch, a.steps, a.warmup)
+    res = dp_bench.timed_rank_step(make_loss, model.param_arena, a.batch, a.steps, a.warmup, ranks)
     res.update(valid_tokens_global=sum(sum(v) for v in lengths.values()))
     print(json.dumps(res), flush=True)
 
@@ -120,10 +106,10 @@ def main():
     a = ap.parse_args()
     assert torch.cuda.is_available(), "finetune_bert_bench.py needs the GPU"
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import dp_bench
     if a.dp_child:
         return dp_child(a)
     if a.world:
-        import dp_bench
         dp_bench.measure(__file__, ["--batch", str(a.batch), "--steps", str(a.steps), "--warmup", str(a.warmup), "--seed", str(a.seed)],
                          a.world, a.out)
         return
@@ -157,17 +143,7 @@ def main():
             pool = pool + Fn.LinearSmallFn.apply(x, model.bert.pooler.dense.weight, model.bert.pooler.dense, ACT_TANH)
         return Fn.PairHeadCEFn.apply(pool, None, model.cls.seq_relationship, labels)[2]
 
-    def step(loss_fn):
-        def run(i):
-            Fn.set_step_seed(1000 + i)
-            Fn.reset_use_counts()
-            arena.zero_grad()
-            loss = loss_fn()
-            loss.backward()
-            scale = min(1.0, 1.0 / (arena.grad.norm().item() + 1e-6))
-            arena.adamw_step(2e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=scale)
-        return run
-
+    step = lambda loss_fn: dp_bench.train_step(arena, loss_fn)
     # the two forms compute the same function: their losses on the same weights, in evaluation mode (no dropout), side by side
     model.eval()
     with torch.no_grad():
@@ -181,7 +157,7 @@ def main():
         order = ("ragged", "padded") if r % 2 == 0 else ("padded", "ragged")
         row = {}
         for name in order:
-            t = timed(forms[name], a.steps, a.warmup)
+            t = dp_bench.timed(forms[name], a.steps, a.warmup)
             times[name] += t
             row[name] = sorted(t)[len(t) // 2]
         per_round.append(dict(order=list(order), median_ms=row))
