@@ -739,6 +739,29 @@ size_t ia_kgpt_topk_workspace_bytes(int B, int D, int n_cand, int k, int max_spl
 int ia_kgpt_topk(const float* ent, const float* rel, const int64_t* a, const int64_t* b, int B, int D, int n_ent, int n_rel, int norm,
                  int mode, const int64_t* grp_off, const int64_t* grp_ids, int n_grp, const int64_t* q_grp, int k, int max_splits,
                  int64_t* idx, float* score, void* workspace, size_t workspace_bytes, ia_stream_t stream);
+/* Same-item retrieval: the k most similar catalogue rows of each of B query rows by inner product (cosine on normalised rows), on the
+ * bf16 matrix cores, without a [B, n_cand] matrix.  (Added without an ABI bump: nothing existing changed its meaning.)
+ * Prepared rows are bf16 [rows, pitch], pitch = ia_sim_row_pitch(D) elements = D rounded up to the scan's k-step (>= D; 0 for D < 1),
+ * the columns D .. pitch - 1 zero, the buffer 16-byte aligned.  ia_sim_rows_bf16 makes them, one row per wave:
+ * out[r][c] = bf16(x[r * ldx + c] * inv_r), inv_r = 1 (normalize 0: a plain round-to-nearest-even conversion) or
+ * 1 / max(sqrt(sum_c x[r][c]^2), 1e-12) in fp32 (normalize 1; an all-zero row stays zero); nothing past column D of a row of x is read
+ * (ldx >= D).  1 <= D <= 2^20.
+ * ia_sim_topk: s[b][c] = sum_k q[b][k] cand[c][k] with one fp32 MFMA accumulator per pair that walks k in the same order whatever the
+ * split count (splits are over candidates, never over k): the score of a pair is a function of the two rows alone.  idx (int64 [B, k]) /
+ * score (fp32 [B, k]): row b holds the k best candidates of query b in the total order (score descending, candidate index ascending);
+ * the result does not depend on B, the query's place in the batch, max_splits or the launch order.  Candidate skip[b] is never returned
+ * to query b (-1, or any value outside [0, n_cand): skip none; skip == NULL: no query skips) -- how an item is kept out of its own
+ * neighbour list.  Unused trailing slots (k > n_cand, or the only candidates skipped) hold idx = -1, score = -inf.  The inputs must
+ * be finite (a NaN score has no place in the order).  1 <= k <= IA_SIM_TOPK_MAX_K; max_splits caps the number of candidate ranges
+ * (0: the scan's choice).  B == 0 and n_cand == 0 are no errors (every slot unused).  Null q / cand / idx / score, k or D out of range,
+ * negative sizes, misaligned rows and a workspace below ia_sim_topk_workspace_bytes(B, D, n_cand, k, max_splits) = O(B splits k)
+ * (0 when B or n_cand is 0; NULL is accepted then) return IA_ERR_ARG before any launch. */
+#define IA_SIM_TOPK_MAX_K 64
+size_t ia_sim_row_pitch(int D);
+int ia_sim_rows_bf16(const float* x, int ldx, int rows, int D, int normalize, void* out, ia_stream_t stream);
+size_t ia_sim_topk_workspace_bytes(int B, int D, int n_cand, int k, int max_splits);
+int ia_sim_topk(const void* q, const void* cand, int B, int D, int n_cand, const int64_t* skip, int k, int max_splits, int64_t* idx,
+                float* score, void* workspace, size_t workspace_bytes, ia_stream_t stream);
 
 /* ---- whole-layer drivers: one call = every launch of one encoder layer, in order, on `stream`.
  * Weights: bf16 shadows for the GEMM operands, fp32 masters for bias / LayerNorm vectors. */

@@ -215,6 +215,10 @@ SIGNATURES = {
     "ia_kgpt_lp_rank": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, sz, vp]),
     "ia_kgpt_topk_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
     "ia_kgpt_topk": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, i32, vp, vp, vp, sz, vp]),
+    "ia_sim_row_pitch": (sz, [i32]),
+    "ia_sim_rows_bf16": (i32, [vp, i32, i32, i32, i32, vp, vp]),
+    "ia_sim_topk_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
+    "ia_sim_topk": (i32, [vp, vp, i32, i32, i32, vp, i32, i32, vp, vp, vp, sz, vp]),
     "ia_gcn_propagate_fwd": (i32, [vp, vp, i32, vp, vp, vp, vp, i32, i32, f32, f32, u32, u32, vp, i32, vp]),
     "ia_gcn_propagate_bwd": (i32, [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, f32, f32, u32, u32, vp, i32, vp]),
     "ia_gcn_mix_fwd": (i32, [vp, vp, vp, i32, i32, f32, f32, u32, u32, vp]),

@@ -19,31 +19,11 @@
 #include "common.h"
 #include "../../include/itemalign.h"
 #include "kgpair.h"
+#include "topk_list.h"   // tk_key, TK_EMPTY, tk_lane, tk_up1, tk_insert, tk_merge
 
 namespace {
 
-typedef unsigned long long tk_key;
-constexpr tk_key TK_EMPTY = ~0ull;          // an unused slot; larger than every key (ids are < 2^31)
-
 IA_DEV tk_key tk_make(float d, int id) { return ((tk_key)__float_as_uint(d) << 32) | (uint32_t)id; }
-IA_DEV tk_key tk_lane(tk_key v, int lane) {   // lane: wave-uniform
-  const uint32_t lo = __builtin_amdgcn_readlane((int)(uint32_t)v, lane), hi = __builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), lane);
-  return ((tk_key)hi << 32) | lo;
-}
-IA_DEV tk_key tk_up1(tk_key v) {              // the value of lane - 1 (lane 0: its own)
-  const uint32_t lo = __shfl_up((int)(uint32_t)v, 1), hi = __shfl_up((int)(uint32_t)(v >> 32), 1);
-  return ((tk_key)hi << 32) | lo;
-}
-// Insert key into the sorted k-list held one entry per lane (lanes >= k hold TK_EMPTY); whole wave, key wave-uniform.
-// Returns false (list unchanged) when key is not among the k smallest.
-IA_DEV bool tk_insert(tk_key& e, tk_key key, int k, int lane, int& pos) {
-  pos = __popcll(__ballot(e < key));
-  if (pos >= k) return false;
-  const tk_key prev = tk_up1(e);
-  e = lane < pos ? e : (lane == pos ? key : prev);
-  if (lane >= k) e = TK_EMPTY;
-  return true;
-}
 
 // ------------------------------------------------------------------------------------------------ 1. query rows
 __global__ __launch_bounds__(256) void tk_prep_kernel(const float* __restrict__ ent, const float* __restrict__ rel, const int64_t* __restrict__ a,
@@ -216,20 +196,13 @@ __global__ __launch_bounds__(256) void tk_scan_kernel(const float* __restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------------ 3. merge of the splits
-// One wave per query: the running list sits one entry per lane; every split's list (sorted) is inserted entry by entry until one fails.
+// One wave per query: the running list sits one entry per lane; every split's list (sorted) is inserted entry by entry until one fails
+// (tk_merge).
 __global__ __launch_bounds__(256) void tk_merge_kernel(const tk_key* __restrict__ part, int B, int k, int n_splits, int64_t* __restrict__ idx,
                                                        float* __restrict__ score) {
   const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (b >= B) return;                                          // wave-uniform
-  tk_key cur = TK_EMPTY;
-  for (int s = 0; s < n_splits; ++s) {
-    const tk_key mine = lane < k ? part[((size_t)b * n_splits + s) * k + lane] : TK_EMPTY;
-    for (int t = 0; t < k; ++t) {
-      const tk_key key = tk_lane(mine, t);
-      int pos;
-      if (key == TK_EMPTY || !tk_insert(cur, key, k, lane, pos)) break;
-    }
-  }
+  const tk_key cur = tk_merge(part, b, k, n_splits, lane);
   if (lane < k) {
     const bool used = cur != TK_EMPTY;
     idx[(size_t)b * k + lane] = used ? (int64_t)(uint32_t)cur : -1;
