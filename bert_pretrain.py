@@ -45,6 +45,8 @@ def get_parser():
     a("--adam_epsilon", default=1e-8, type=float)
     a("--warmup_steps", default=3000, type=int)
     a("--max_grad_norm", default=1.0, type=float)
+    from item_alignment_amd.train import add_optimizer_flag
+    add_optimizer_flag(p)
     a("--log_steps", default=100, type=int)
     a("--eval_steps", default=2000, type=int)
     a("--patience_steps", default=20000, type=int)
@@ -84,7 +86,8 @@ def pretrain(args, ranks, writer):
     from item_alignment_amd.cli_common import linear_schedule, load_config, load_vocab_tokenizer
     from item_alignment_amd.data import bert_pretrain as D
     from item_alignment_amd.models import functional as Fn
-    from item_alignment_amd.train import clipped_adamw_step
+    from item_alignment_amd.train import clipped_step
+    clipped_optimizer_step = clipped_step(args)
 
     if not torch.cuda.is_available():
         raise SystemExit("bert_pretrain.py runs on the MI355X HIP engine only (no CPU path); no GPU is visible")
@@ -166,7 +169,7 @@ def pretrain(args, ranks, writer):
                     inv_world = reducer.finish()
                 global_steps += 1
                 lr = args.learning_rate * linear_schedule(global_steps - 1, total_steps, args.warmup_steps)
-                clipped_adamw_step(arena, lr, args.max_grad_norm, inv_world, betas=(0.9, 0.999), eps=args.adam_epsilon, weight_decay=0.0)
+                clipped_optimizer_step(arena, lr, args.max_grad_norm, inv_world, betas=(0.9, 0.999), eps=args.adam_epsilon, weight_decay=0.0)
                 if global_steps % args.log_steps == 0:
                     # the weighted rank losses average to the loss of the global batch
                     value = ranks.mean(loss)

@@ -66,6 +66,8 @@ def get_parser():
     a("--adam_epsilon", default=1e-8, type=float)
     a("--warmup_steps", default=3000, type=int)
     a("--max_grad_norm", default=1.0, type=float)
+    from item_alignment_amd.train import add_optimizer_flag
+    add_optimizer_flag(p)
     a("--log_steps", default=100, type=int)
     a("--eval_steps", default=1000, type=int)
     a("--check_steps", default=1000, type=int)
@@ -176,16 +178,26 @@ def write_csv_row(output_dir, r, epoch, steps):
 
 def save_checkpoint(model, arena, global_steps, total_steps, args, path):
     """model_state_dict, optimizer_state_dict, scheduler_state_dict, global_steps -- the reference's four keys.  The optimiser is the
-    arena's fused AdamW: its state is the two moment buffers and the step count; the schedule is a function of the step."""
+    arena's fused AdamW or LAMB (--optimizer, recorded by name): its state is the two moment buffers and the step count; the schedule
+    is a function of the step."""
     import torch
     torch.save({
         "model_state_dict": {k: v.detach().cpu().clone() for k, v in model.state_dict().items()},
         "optimizer_state_dict": {"exp_avg": arena.exp_avg.cpu(), "exp_avg_sq": arena.exp_avg_sq.cpu(), "step": arena.step_count,
-                                 "names": list(arena.names), "offsets": list(arena.offsets)},
+                                 "optimizer": args.optimizer, "names": list(arena.names), "offsets": list(arena.offsets)},
         "scheduler_state_dict": {"last_epoch": global_steps, "total_steps": total_steps, "warmup_steps": args.warmup_steps,
                                  "base_lr": args.learning_rate},
         "global_steps": global_steps,
     }, path)
+
+
+def check_checkpoint_optimizer(state, args):
+    """a checkpoint continues with the optimiser that wrote it (one written before the flag existed: adamw): the moments of the one
+    are no state of the other"""
+    saved = state.get("optimizer", "adamw")
+    if saved != args.optimizer:
+        raise SystemExit(f"the checkpoint was written with --optimizer {saved}: resuming it with --optimizer {args.optimizer} is refused "
+                         "(pass the same optimiser, or start from --restore_path without the checkpoint)")
 
 
 def restore_optimizer(arena, state):
@@ -216,7 +228,8 @@ def run(args):
     import item_alignment_amd.models as M
     from item_alignment_amd.data.bert_align import LOGGER
     from item_alignment_amd.models import functional as Fn
-    from item_alignment_amd.train import clipped_adamw_step
+    from item_alignment_amd.train import clipped_step
+    clipped_optimizer_step = clipped_step(args)
 
     config = load_config(os.path.join(args.model_name_or_path, "config.json"))
     check_lengths(args, config)
@@ -257,6 +270,7 @@ def run(args):
                 ck = torch.load(checkpoint_path, map_location="cpu")
                 model.load_state_dict({(k[len("module."):] if k.startswith("module.") else k): v for k, v in ck["model_state_dict"].items()})
                 global_steps, optimizer_state = int(ck["global_steps"]), ck["optimizer_state_dict"]
+                check_checkpoint_optimizer(optimizer_state, args)
                 del ck
             else:
                 LOGGER.info("There is no resume model path.")
@@ -317,7 +331,7 @@ def run(args):
                         inv_world = reducer.finish()
                     global_steps += 1
                     lr = args.learning_rate * linear_schedule(global_steps - 1, total_steps, args.warmup_steps)
-                    clipped_adamw_step(arena, lr, args.max_grad_norm, inv_world, betas=(0.9, 0.999), eps=args.adam_epsilon, weight_decay=0.0)
+                    clipped_optimizer_step(arena, lr, args.max_grad_norm, inv_world, betas=(0.9, 0.999), eps=args.adam_epsilon, weight_decay=0.0)
                     if global_steps % args.log_steps == 0:
                         value = ranks.mean(loss)          # the weighted rank losses average to the loss of the global batch
                         scalars("Train", Loss=value)

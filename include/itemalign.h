@@ -672,6 +672,26 @@ int ia_transpose_bf16_batched(const void* src, void* dst, const void* table, int
 int ia_adamw_flat(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, void* shadow_bf16, const void* chunk_table,
                   int n_chunks, float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
                   ia_stream_t stream);
+/* LAMB (You et al., ICLR 2020) over the same five arenas (a pure addition: the ABI version is unchanged).  With t = step >= 1:
+ *   s = grad_scale                                                             if max_grad_norm <= 0
+ *     = grad_scale * min(1, max_grad_norm / (grad_scale * ||g||_2 + 1e-6))     otherwise (||g|| over every chunk of the table)
+ *   g' = s g;  m = b1 m + (1 - b1) g';  v = b2 v + (1 - b2) g'^2
+ *   u  = (m / (1 - b1^t)) / (sqrt(v / (1 - b2^t)) + eps) + wd w          wd = weight_decay where the chunk's decay word is set, else 0
+ *   r_T = ||w_T||_2 / ||u_T||_2 if the tensor has IA_LAMB_ADAPT and both norms are > 0, else 1  (w before the update; no clamp)
+ *   w  = w - lr r_T u;  shadow = bf16(w), round to nearest even (shadow_bf16 may be NULL)
+ * chunk_table: as for ia_adamw_flat (n_chunks x {offset_lo, offset_hi, count <= 4096, decay}, offsets 4-element aligned).
+ * tensor_table: n_tensors x {first_chunk, n_chunks, flags} (uint32 x 3, device memory): the chunks of one tensor are adjacent and
+ * ascending in chunk_table; every chunk belongs to exactly one tensor (a chunk no tensor claims is stepped with r = 1).  Elements
+ * outside the chunks (alignment padding, frozen tensors) are neither read nor written.
+ * Three launches on `stream` (five with clipping), no host synchronisation, nothing read back, no atomics: partial sums are fp32 inside
+ * a chunk and combined in fp64 in an order fixed by the tables, so equal inputs give equal bits on every run and every rank.
+ * workspace: >= ia_lamb_workspace_bytes(n_chunks, n_tensors), 16-byte aligned; after the step the float at byte 16 + 4 i is r_T of
+ * tensor i.  IA_ERR_ARG: a null pointer, n_chunks / n_tensors / step <= 0; IA_ERR_WORKSPACE: workspace null, small or misaligned. */
+#define IA_LAMB_ADAPT 1
+size_t ia_lamb_workspace_bytes(int n_chunks, int n_tensors);
+int ia_lamb_flat(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, void* shadow_bf16, const void* chunk_table,
+                 int n_chunks, const void* tensor_table, int n_tensors, float lr, float beta1, float beta2, float eps, float weight_decay,
+                 int step, float grad_scale, float max_grad_norm, void* workspace, size_t workspace_bytes, ia_stream_t stream);
 int ia_cast_f32_to_bf16(const float* src, void* dst, size_t n, ia_stream_t stream);
 int ia_cast_bf16_to_f32(const void* src, float* dst, size_t n, ia_stream_t stream);
 

@@ -205,6 +205,8 @@ SIGNATURES = {
     "ia_pair_head_ce_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "ia_transpose_bf16_batched": (i32, [vp, vp, vp, i32, i32, vp]),
     "ia_adamw_flat": (i32, [vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, f32, f32, i32, f32, vp]),
+    "ia_lamb_workspace_bytes": (sz, [i32, i32]),
+    "ia_lamb_flat": (i32, [vp, vp, vp, vp, vp, vp, i32, vp, i32, f32, f32, f32, f32, f32, i32, f32, f32, vp, sz, vp]),
     "ia_kgpt_workspace_bytes": (sz, [i32, i32, i32]),
     "ia_kgpt_score": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz,
                             vp]),

@@ -19,10 +19,41 @@ from ._lib import check, stream_ptr
 ALIGN = 64          # elements; 256 B for fp32, 128 B for the bf16 shadow
 CHUNK = 4096        # elements handled by one workgroup of the AdamW kernel
 NO_DECAY = ("bias", "LayerNorm.weight")
+LAMB_ADAPT = 1      # IA_LAMB_ADAPT: the tensor's update is rescaled by |w| / |u|
 
 
 def _round_up(n, a):
     return (n + a - 1) // a * a
+
+
+class LambTables:
+    """The device tables and workspace of one ia_lamb_flat launch over `entries` = (element offset, numel, decays, adapted) per tensor:
+    the chunk table of ia_adamw_flat, {first_chunk, n_chunks, flags} per tensor, and the workspace whose bytes 16.. hold r_T."""
+
+    def __init__(self, entries, device):
+        chunks, tensors = [], []
+        for o, n, decay, adapt in entries:
+            tensors.append((len(chunks), (n + CHUNK - 1) // CHUNK, LAMB_ADAPT if adapt else 0))
+            for c in range(0, n, CHUNK):
+                chunks.append(((o + c) & 0xFFFFFFFF, (o + c) >> 32, min(CHUNK, n - c), 1 if decay else 0))
+        self.n_chunks, self.n_tensors = len(chunks), len(tensors)
+        self.chunk_table = torch.from_numpy(np.asarray(chunks, dtype=np.uint32).reshape(-1, 4)).to(device)
+        self.tensor_table = torch.from_numpy(np.asarray(tensors, dtype=np.uint32).reshape(-1, 3)).to(device)
+        self.workspace_bytes = _lib.load().ia_lamb_workspace_bytes(self.n_chunks, self.n_tensors) if tensors else 0
+        self.workspace = torch.zeros(max(1, self.workspace_bytes), dtype=torch.uint8, device=device)
+
+    def step(self, arena, lr, beta1, beta2, eps, weight_decay, step, grad_scale, max_grad_norm):
+        check(_lib.load().ia_lamb_flat(arena.master.data_ptr(), arena.grad.data_ptr(), arena.exp_avg.data_ptr(), arena.exp_avg_sq.data_ptr(),
+                                       arena.shadow.data_ptr(), self.chunk_table.data_ptr(), self.n_chunks, self.tensor_table.data_ptr(),
+                                       self.n_tensors, lr, beta1, beta2, eps, weight_decay, step, grad_scale, max_grad_norm,
+                                       self.workspace.data_ptr(), self.workspace_bytes, stream_ptr()), "ia_lamb_flat")
+
+    def set_adapt(self, adapt):
+        self.tensor_table[:, 2] = LAMB_ADAPT if adapt else 0
+
+    def ratios(self):
+        """r_T of the last step, one per tensor in table order (a device -> host copy)"""
+        return self.workspace[16:16 + 4 * self.n_tensors].view(torch.float32).cpu().tolist()
 
 
 class ParamArena:
@@ -77,6 +108,7 @@ class ParamArena:
         self._transposed = {}              # element offset -> (rows, cols)
         self._transposed_table = None
         self.step_count = 0
+        self._lamb = None                  # LambTables, built by the first lamb_step()
         self.stale_refreshes = 0
         self.shadow_refreshes = 0          # every refresh_shadow(): what a holder of derived weights (NormFreeNet.embed) keys its copies by
         self.optimizer_bound = False
@@ -208,6 +240,30 @@ class ParamArena:
                                 self.shadow.data_ptr(), self.chunk_table.data_ptr(), self.n_chunks, lr, betas[0], betas[1], eps,
                                 weight_decay, self.step_count, grad_scale, stream_ptr()), "ia_adamw_flat")
         self.refresh_transposed()
+
+    def lamb_step(self, lr, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, grad_scale=1.0, max_grad_norm=0.0):
+        """One LAMB update over the whole arena + bf16 shadow refresh (DESIGN.md "LAMB"): the Adam direction plus decoupled decay,
+        rescaled per parameter tensor by |w| / |u|.  Tensors the AdamW step does not decay ("bias", "LayerNorm.weight") are neither
+        decayed nor rescaled.  max_grad_norm > 0 clips by the global gradient norm on the device (no host sync).  The tensor table
+        and the workspace are built at the first call."""
+        if self._lamb is None:
+            self._lamb_names, entries = [], []
+            for n, p, o in zip(self.names, self.params, self.offsets):
+                if p.requires_grad:
+                    decay = not any(nd in n for nd in NO_DECAY)
+                    self._lamb_names.append(n)
+                    entries.append((o, p.numel(), decay, decay))
+            self._lamb = LambTables(entries, self.device)
+        self.step_count += 1
+        self.join_side_streams()
+        self._lamb.step(self, lr, betas[0], betas[1], eps, weight_decay, self.step_count, grad_scale, max_grad_norm)
+        self.refresh_transposed()
+
+    def last_trust_ratios(self):
+        """{parameter name: r_T} of the last lamb_step (a device -> host copy: for tests and logging, not for the training loop)"""
+        if self._lamb is None:
+            raise RuntimeError("last_trust_ratios: no lamb_step has run on this arena")
+        return dict(zip(self._lamb_names, self._lamb.ratios()))
 
     def grad_buckets(self, bucket_bytes=64 << 20):
         """Contiguous slices of the gradient arena, last-to-first (backward produces the last layers'

@@ -37,6 +37,8 @@ def add_common_flags(parser, config_required=True):
     a("--warmup_proportion", default=0.3, type=float)
     a("--gradient_accumulation_steps", default=1, type=int)
     a("--adam_epsilon", default=1e-8, type=float)
+    from .train import add_optimizer_flag
+    add_optimizer_flag(parser)
     a("--fp16", action="store_true", help="kept for CLI compatibility: the HIP engine always computes in bf16 with fp32 master weights")
     a("--margin", default=1.0, type=float)
     # not in the reference (its DataLoader has 0 workers and transforms run inside __getitem__): host-side decode workers and

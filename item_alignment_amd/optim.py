@@ -39,7 +39,7 @@ class AdamW(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0):
         if lr < 0 or eps < 0 or not 0 <= betas[0] < 1 or not 0 <= betas[1] < 1 or weight_decay < 0:
             raise ValueError("invalid AdamW hyper-parameter")
-        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay))
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, **self._extra_defaults()))
         self.grad_scale = grad_scale            # the data-parallel 1 / world factor (dist.GradBucketReducer.finish()) when gradients are summed
         self.arena = None
         self._tables = None
@@ -49,6 +49,9 @@ class AdamW(torch.optim.Optimizer):
         # binding to the arena happens at the first step() / zero_grad() that finds one.
         if all(getattr(p, "_ia_arena", None) is not None for g in self.param_groups for p in g["params"]):
             self._bind()
+
+    def _extra_defaults(self):
+        return {}
 
     def _bind(self):
         if self._tables is not None:
@@ -67,7 +70,7 @@ class AdamW(torch.optim.Optimizer):
         offset_of = {id(p): o for p, o in zip(arena.params, arena.offsets)}
         tables, step_tensors = [], []
         for group in self.param_groups:
-            chunks = []
+            entries = []
             # torch keeps a `step` tensor per parameter; all parameters of a group step together, so they share ONE tensor per group
             # that step() updates in place (no per-parameter host work in the loop)
             step_t = torch.full((), float(group.get("step_count", 0)), dtype=torch.float32)
@@ -76,16 +79,20 @@ class AdamW(torch.optim.Optimizer):
                 if not p.requires_grad:
                     continue
                 o, n = offset_of[id(p)], p.numel()
-                for c in range(0, n, CHUNK):
-                    chunks.append(((o + c) & 0xFFFFFFFF, (o + c) >> 32, min(CHUNK, n - c), 1))
+                entries.append((o, n))
                 # torch's per-parameter state, as views of the arenas (never re-allocated: the kernel writes them in place)
                 self.state[p] = {"step": step_t,
                                  "exp_avg": arena.exp_avg[o:o + n].view(p.shape), "exp_avg_sq": arena.exp_avg_sq[o:o + n].view(p.shape)}
-            table = torch.from_numpy(np.asarray(chunks, dtype=np.uint32).reshape(-1, 4)).to(arena.device) if chunks else None
-            tables.append((table, len(chunks)))
+            tables.append(self._group_table(group, entries, arena.device))
         self._tables, self._step_tensors = tables, step_tensors
         arena.optimizer_bound = True
         return True
+
+    def _group_table(self, group, entries, device):
+        """(device chunk table, number of chunks) over the (element offset, numel) slices of one parameter group"""
+        chunks = [((o + c) & 0xFFFFFFFF, (o + c) >> 32, min(CHUNK, n - c), 1) for o, n in entries for c in range(0, n, CHUNK)]
+        table = torch.from_numpy(np.asarray(chunks, dtype=np.uint32).reshape(-1, 4)).to(device) if chunks else None
+        return table, len(chunks)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -150,3 +157,54 @@ class AdamW(torch.optim.Optimizer):
             if steps:
                 group["step_count"] = max(steps)
             step_t.fill_(float(group["step_count"]))
+
+
+class LAMB(AdamW):
+    """LAMB over a model that lives in a ParamArena (DESIGN.md "LAMB"): the AdamW front above with `ia_lamb_flat` as the launch.  Each
+    parameter group is one launch; `lr`, `betas`, `eps`, `weight_decay` and `adapt` are read from the group at every step.  `adapt=False`
+    leaves a group's tensors at trust ratio 1 (the exclude_from_layer_adaptation of the BERT recipe: give biases and LayerNorm weights a
+    group with weight_decay=0, adapt=False).  No clipping of its own: see train.clipped_lamb_step."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=1e-2, adapt=True, grad_scale=1.0):
+        self._adapt = bool(adapt)               # read by _extra_defaults() inside the base constructor
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale)
+
+    def _extra_defaults(self):
+        return {"adapt": self._adapt}
+
+    def _group_table(self, group, entries, device):
+        from .arena import LambTables
+        tables = LambTables([(o, n, True, bool(group["adapt"])) for o, n in entries], device)
+        tables.adapt = bool(group["adapt"])
+        return tables, len(entries)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        self._bind()
+        arena = self.arena
+        arena.join_side_streams()
+        for group, (tables, n), step_t in zip(self.param_groups, self._tables, self._step_tensors):
+            if n == 0:
+                continue
+            if bool(group["adapt"]) != tables.adapt:        # the flag was changed between two steps: rewrite the table's flag column
+                tables.adapt = bool(group["adapt"])
+                tables.set_adapt(tables.adapt)
+            group["step_count"] += 1
+            b1, b2 = group["betas"]
+            tables.step(arena, float(group["lr"]), b1, b2, group["eps"], group["weight_decay"], group["step_count"], float(self.grad_scale), 0.0)
+            step_t.fill_(float(group["step_count"]))
+        arena.step_count += 1
+        arena.refresh_transposed()
+        return loss
+
+    def trust_ratios(self):
+        """{parameter: r_T} of the last step (a device -> host copy)"""
+        out = {}
+        for group, (tables, n) in zip(self.param_groups, self._tables or []):
+            if n:
+                out.update(zip([p for p in group["params"] if p.requires_grad], tables.ratios()))
+        return out

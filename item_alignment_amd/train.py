@@ -78,6 +78,45 @@ def clipped_adamw_step(arena, lr, max_grad_norm, inv_world=1.0, *, betas, eps, w
     arena.adamw_step(lr, betas=betas, eps=eps, weight_decay=weight_decay, grad_scale=scale)
 
 
+class ArenaLAMB:
+    """LAMB over the flat parameter arena (arena.lamb_step): ArenaAdamW's interface, the script's own betas, epsilon and weight decay"""
+
+    def __init__(self, model, lr, eps, weight_decay, betas=(0.9, 0.98)):
+        self.arena = model.param_arena
+        self.base_lr, self.eps, self.wd, self.betas = lr, eps, weight_decay, betas
+
+    def zero_grad(self):
+        self.arena.zero_grad()
+
+    def step(self, lr_mult, grad_scale=1.0):
+        self.arena.lamb_step(self.base_lr * lr_mult, betas=self.betas, eps=self.eps, weight_decay=self.wd, grad_scale=grad_scale)
+
+
+def clipped_lamb_step(arena, lr, max_grad_norm, inv_world=1.0, *, betas, eps, weight_decay):
+    """clipped_adamw_step's clipping with the LAMB update: the same factor, formed on the device from the gradient norm inside the
+    optimiser step (no .item(), no host sync)"""
+    arena.lamb_step(lr, betas=betas, eps=eps, weight_decay=weight_decay, grad_scale=inv_world, max_grad_norm=max_grad_norm)
+
+
+OPTIMIZERS = ("adamw", "lamb")
+
+
+def add_optimizer_flag(parser):
+    parser.add_argument("--optimizer", default="adamw", choices=OPTIMIZERS,
+                        help="adamw: the reference's optimiser.  lamb: the same direction rescaled per parameter tensor by |w| / |u| "
+                             "(You et al. 2020), for large total batches; keeps this script's betas, epsilon, weight decay and schedule")
+
+
+def require_arena_for_lamb(args, is_hip):
+    if getattr(args, "optimizer", "adamw") == "lamb" and not is_hip:
+        raise SystemExit("--optimizer lamb runs over the GPU parameter arena: this model has none here (TextCNN on the CPU); use --optimizer adamw")
+
+
+def clipped_step(args):
+    """the clipped optimiser step --optimizer selects"""
+    return clipped_lamb_step if getattr(args, "optimizer", "adamw") == "lamb" else clipped_adamw_step
+
+
 def accumulate_step(opt, loss, last, accumulation_steps, lr_mult, reducer=None, average_grads=None):
     """backward() of one micro-batch; on the `last` one of an optimiser step also the reduction over the ranks, opt.step(lr_mult)
     and zero_grad.  average_grads: called before the step where no reducer averages (plain torch models on several ranks).  -> last"""
@@ -232,7 +271,9 @@ def train_epochs(args, model, datasets, collate_fn, call_model, checkpoint_name,
     per_rank = args.train_batch_size // world
     if per_rank * world != args.train_batch_size:
         raise ValueError(f"--train_batch_size {args.train_batch_size} must be divisible by the world size {world}")
-    opt = (ArenaAdamW if is_hip else TorchAdamW)(model, args.learning_rate, args.adam_epsilon, args.weight_decay)
+    require_arena_for_lamb(args, is_hip)
+    opt_cls = ArenaLAMB if getattr(args, "optimizer", "adamw") == "lamb" else (ArenaAdamW if is_hip else TorchAdamW)
+    opt = opt_cls(model, args.learning_rate, args.adam_epsilon, args.weight_decay)
     steps_per_epoch = int(len(train_ds) / args.train_batch_size / args.gradient_accumulation_steps)
     total = steps_per_epoch * (args.num_train_epochs - args.start_epoch)
     warm = int(total * args.warmup_proportion)
