@@ -782,6 +782,42 @@ int ia_sim_rows_bf16(const float* x, int ldx, int rows, int D, int normalize, vo
 size_t ia_sim_topk_workspace_bytes(int B, int D, int n_cand, int k, int max_splits);
 int ia_sim_topk(const void* q, const void* cand, int B, int D, int n_cand, const int64_t* skip, int k, int max_splits, int64_t* idx,
                 float* score, void* workspace, size_t workspace_bytes, ia_stream_t stream);
+/* The same scan over G ragged problems in one call: the hot path of an inverted-file index.  (Added without an ABI bump.)
+ * Group g pairs the query rows [q_off[g], q_off[g + 1]) of q (prepared bf16 [P, pitch]) with the candidate rows
+ * [c_off[g], c_off[g + 1]) of cand (prepared bf16 [n_cand, pitch]).  q_off and c_off are int64 [G + 1] arrays ON THE DEVICE,
+ * non-decreasing, within [0, P] and [0, n_cand]; they are never read on the host, so the call launches and returns without a
+ * synchronisation, and an offset out of range or out of order cannot be refused: it is clamped, or makes an empty range, inside the
+ * kernels (no row outside the two matrices is touched; what such a group's rows receive is unspecified).  The grid is the upper bound
+ * P / QT + G query tiles (QT = 256 rows for k <= 32, 128 above) and a workgroup finds its group by search.
+ * idx (int64 [P, k]) / score (fp32 [P, k]): row p, a query row of group g, holds the k best candidates of group g in the total order
+ * (score descending, REPORTED id ascending).  The reported id of candidate row c is label[c] (label_bits 32: int32, 64: int64; values in
+ * [0, 2^31)), or c itself where label == NULL (label_bits 0).  The score of a pair is bit for bit what ia_sim_topk gives for the same
+ * two rows; the result does not depend on the order of the groups, on how many share a call, on max_splits (the cap on the candidate
+ * ranges a group is cut into; 0: the scan's choice; never over k) or on the launch order.  skip[p] is a POSITION in cand (not a
+ * label): candidate row skip[p] is never returned to query row p; -1 or any row outside the group's range skips nothing; skip == NULL:
+ * no row skips.  Groups without query rows, without candidates or with fewer than k candidates, and G == 0 or P == 0, are no errors:
+ * unused trailing slots hold idx = -1, score = -inf.  Rows of q outside [q_off[0], q_off[G]) and rows of cand outside
+ * [c_off[0], c_off[G]) are not read, and the rows of idx / score outside [q_off[0], q_off[G]) are not written.  A tail tile reads no row of
+ * the next group.  Null q / cand / q_off / c_off / idx / score, a label without label_bits 32 or 64 (or label_bits without a label),
+ * k or D out of range as for ia_sim_topk, negative sizes, q / cand / workspace off 16 bytes, another array off its element size, and a
+ * workspace below ia_sim_topk_groups_workspace_bytes(P, G, D, n_cand, k, max_splits) (0 when P or G is 0) return IA_ERR_ARG before
+ * any launch.
+ * ia_sim_topk_fold: out row b = the k best, in the same total order, of the union of the rows rows_of[b * nprobe + j], j < nprobe, of
+ * idx_in / score_in ([n_rows, k], as ia_sim_topk_groups writes them; rows_of: int64 on the device; -1 or a value outside [0, n_rows):
+ * no list).  The lists of one b must hold no id twice (the lists of an index partition the catalogue and a query's probes are
+ * distinct).  B == 0 is no error.
+ * ia_sim_centroid_sums (k-means): sums[l][c] = the fp32 sum over i in [list_off[l], list_off[l + 1]), in that order, of
+ * rows[order[i]][c] (rows: prepared bf16 [n_rows, pitch]; order: int64 [n_order], list_off: int64 [nlist + 1], both on the device;
+ * sums: fp32 [nlist, D]; counts: int64 [nlist], the rows added).  One thread owns an output and adds in order, no atomics: equal inputs
+ * give equal bits.  An empty list gives zeros and count 0; an order entry outside [0, n_rows) is left out. */
+size_t ia_sim_topk_groups_workspace_bytes(int P, int G, int D, int n_cand, int k, int max_splits);
+int ia_sim_topk_groups(const void* q, const void* cand, const int64_t* q_off, const int64_t* c_off, int G, int P, int D, int n_cand,
+                       const void* label, int label_bits, const int64_t* skip, int k, int max_splits, int64_t* idx, float* score,
+                       void* workspace, size_t workspace_bytes, ia_stream_t stream);
+int ia_sim_topk_fold(const int64_t* idx_in, const float* score_in, int n_rows, const int64_t* rows_of, int B, int nprobe, int k,
+                     int64_t* idx, float* score, ia_stream_t stream);
+int ia_sim_centroid_sums(const void* rows, int n_rows, int D, const int64_t* order, int n_order, const int64_t* list_off, int nlist,
+                         float* sums, int64_t* counts, ia_stream_t stream);
 
 /* ---- whole-layer drivers: one call = every launch of one encoder layer, in order, on `stream`.
  * Weights: bf16 shadows for the GEMM operands, fp32 masters for bias / LayerNorm vectors. */

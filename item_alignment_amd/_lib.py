@@ -221,6 +221,10 @@ SIGNATURES = {
     "ia_sim_rows_bf16": (i32, [vp, i32, i32, i32, i32, vp, vp]),
     "ia_sim_topk_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
     "ia_sim_topk": (i32, [vp, vp, i32, i32, i32, vp, i32, i32, vp, vp, vp, sz, vp]),
+    "ia_sim_topk_groups_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32]),
+    "ia_sim_topk_groups": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, i32, i32, vp, vp, vp, sz, vp]),
+    "ia_sim_topk_fold": (i32, [vp, vp, i32, vp, i32, i32, i32, vp, vp, vp]),
+    "ia_sim_centroid_sums": (i32, [vp, i32, i32, vp, i32, vp, i32, vp, vp, vp]),
     "ia_gcn_propagate_fwd": (i32, [vp, vp, i32, vp, vp, vp, vp, i32, i32, f32, f32, u32, u32, vp, i32, vp]),
     "ia_gcn_propagate_bwd": (i32, [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, f32, f32, u32, u32, vp, i32, vp]),
     "ia_gcn_mix_fwd": (i32, [vp, vp, vp, i32, i32, f32, f32, u32, u32, vp]),

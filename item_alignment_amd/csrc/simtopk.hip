@@ -19,22 +19,9 @@
 #include "common.h"
 #include "../../include/itemalign.h"
 #include "topk_list.h"
+#include "simscan.h"
 
 namespace {
-
-constexpr int ST_CT = 128;            // candidates of a tile
-constexpr int ST_BK = 64;             // k depth of one LDS stage = the unit of the row pitch
-constexpr int ST_LD = ST_BK + 8;      // LDS row stride in elements: 144 B, the 16 rows of a ds_read_b128 lane group fall on 16 different slots
-constexpr int ST_TARGET_WGS = 512;    // two workgroups a CU
-constexpr int ST_NQ_MAX_K = 32;       // largest k served by the 256-query tile
-
-// the high word of a key: smaller = better score.  s + 0 turns -0 into +0 (equal scores, one key word)
-IA_DEV uint32_t st_order(float s) {
-  const uint32_t u = __float_as_uint(s + 0.f);
-  return (u & 0x80000000u) ? u : (~u & 0x7FFFFFFFu);
-}
-// its inverse; the word of TK_EMPTY gives NaN
-IA_DEV float st_score(uint32_t w) { return __uint_as_float((w & 0x80000000u) ? w : (~w & 0x7FFFFFFFu)); }
 
 // ------------------------------------------------------------------------------------------------ 1. rows
 // one wave per row
@@ -58,25 +45,10 @@ __global__ __launch_bounds__(256) void st_rows_kernel(const float* __restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------------ 2. scan + selection
-template <int N>
-IA_DEV void st_load(u32x4 (&g)[N], const bf16* __restrict__ base, int row0, int n_rows, int pitch, int k0) {
-#pragma unroll
-  for (int s = 0; s < N; ++s) {
-    const int e = threadIdx.x + 256 * s, row = row0 + (e >> 3), kc = e & 7;
-    g[s] = row < n_rows ? *reinterpret_cast<const u32x4*>(base + (size_t)row * pitch + k0 + kc * 8) : u32x4{0u, 0u, 0u, 0u};
-  }
-}
-template <int N>
-IA_DEV void st_store(const u32x4 (&g)[N], bf16* __restrict__ lds) {
-#pragma unroll
-  for (int s = 0; s < N; ++s) {
-    const int e = threadIdx.x + 256 * s;
-    *reinterpret_cast<u32x4*>(lds + (e >> 3) * ST_LD + (e & 7) * 8) = g[s];
-  }
-}
-
 // Workgroup (x, y): queries [QT x, + QT), candidate tiles [y tps, y tps + tps).  LDS: Qs [QT][ST_LD] | Cs [ST_CT][ST_LD] | the QT lists,
 // k keys each.  part[(b * n_splits + y) * k + l]: the list of query b over this split.
+// KEEP IN STEP with sg_scan_kernel (simtopk_groups.hip), which is this body over a group's ranges: a change to the stages, the k loop or
+// the selection is made in both, or the two entry points stop giving a pair the same bits.
 template <int NQ>
 __global__ __launch_bounds__(256) void st_scan_kernel(const bf16* __restrict__ q, const bf16* __restrict__ cand, const int64_t* __restrict__ skip,
                                                       int B, int pitch, int n_cand, int tiles_per_split, int k, tk_key* __restrict__ part) {
@@ -196,8 +168,6 @@ __global__ __launch_bounds__(256) void st_merge_kernel(const tk_key* __restrict_
   }
 }
 
-int st_pitch(int D) { return (D + ST_BK - 1) / ST_BK * ST_BK; }
-int st_qt(int k) { return k <= ST_NQ_MAX_K ? 256 : 128; }
 // the largest split count a call may use
 int st_split_cap(int B, int n_cand, int k, int max_splits) {
   const int q_tiles = (B + st_qt(k) - 1) / st_qt(k), n_tiles = (n_cand + ST_CT - 1) / ST_CT;
